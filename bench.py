@@ -18,8 +18,12 @@ One "step" = one pass of the hot path over one synthetic input that is already r
   --replicas        N > 1: every rank proves its own trace (weak scaling, no data-path exchange) -- the proving-farm mode.
   --workload c4     BN128 Poseidon (arity 16) commit of the config-4 trace; --workload c2: config 2.
   --shard-of K      (with a sharded mode, one GPU) rank 0's share of a K-rank job run alone; not a contract line.
+  --full            everything beside the headline figure as well: the instrumented pass (stages), per-kernel timings and
+                    rooflines, board power, witness upload, proofs from host memory, the Node-driven proof, the CPU baseline and
+                    the other BASELINE configurations.  A plain run sets up, warms up, times the K steps and prints the line.
+  --dump-outputs DIR  after the timed steps, what the last timed step computed, as DIR/<name>.npy (see dump_outputs)
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c2|c3|c4|c5|NBITSxCOLS] [--mode ...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c2|c3|c4|c5|NBITSxCOLS] [--mode ...] [--full] [--dump-outputs DIR]
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (torch.distributed.run, 127.0.0.1) and relays
 rank 0's JSON line; under torchrun WORLD_SIZE must equal --gpus.
@@ -64,7 +68,13 @@ def parse():
     ap.add_argument("--air", default="fib", choices=["fib", "perm"], help="prove modes: fib = C/2 Fibonacci machines, one witness stage (the headline line); "
                     "perm = C/11 permutation checks, TWO witness stages with grand-product hints (2 + 9 base columns each: polutils.js:105-164, hints_helpers.js:81-123)")
     ap.add_argument("--shard-of", type=int, default=0, help="a sharded mode on ONE GPU: run rank 0's share of a K-GPU job (per-GPU time/memory rehearsal, e.g. --workload c5 --shard-of 8)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline figure (stages, per-kernel timings, "
+                    "rooflines, board power, host-memory proofs, Node-driven proof, CPU baseline, other configurations)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def make_trace(n_rows, n_cols, seed, device):
@@ -693,6 +703,54 @@ def proof_sha256(proof):
     return hashlib.sha256(canon(proof).encode()).hexdigest()
 
 
+def _int_leaves(v, acc):
+    """the integers of a nest of dicts / lists / tuples (a proof), in order"""
+    if isinstance(v, dict):
+        for x in v.values():
+            _int_leaves(x, acc)
+    elif isinstance(v, (list, tuple)):
+        for x in v:
+            _int_leaves(x, acc)
+    else:
+        acc.append(int(v))
+    return acc
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: every output as <out_dir>/<name>.npy, float64 of shape (count, limbs) holding the 16-bit limbs of each
+    unsigned integer, least significant first: exact in float64, and a changed value moves some limb by at least 1.  An output
+    is a uint64 array (64-bit words: 4 limbs) or a nest of Python integers (as many limbs as its largest value needs: 4 for
+    Goldilocks elements, 16 for BN254 ones)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in outputs.items():
+        if isinstance(v, np.ndarray):
+            a = ((v.reshape(-1, 1) >> np.arange(0, 64, 16, dtype=np.uint64)) & np.uint64(0xFFFF)).astype(np.float64)
+        else:
+            vals = _int_leaves(v, [])
+            n = max(4, -(-max([x.bit_length() for x in vals] + [1]) // 16))
+            a = np.array([[(x >> s) & 0xFFFF for s in range(0, 16 * n, 16)] for x in vals], dtype=np.float64).reshape(-1, n)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def proof_outputs(res):
+    """what a prover's caller receives: the proof, field by field, and the publics"""
+    out = {"proof_" + k: v for k, v in res["proof"].items()}
+    out["publics"] = res["publics"]
+    return out
+
+
+def commit_outputs(elements, width, nodes, root, seed=0x5EED):
+    """what extendAndMerkelize's caller receives, as a fixed seeded sample (config 3's extension alone is 107 GB): rows of the
+    extended matrix (at most 2^19 words), 4096 node digests of 4 words, and the root"""
+    g = np.random.default_rng(seed)
+    rows = elements.numel() // width
+    ri = torch.from_numpy(np.sort(g.integers(0, rows, min(4096, max(1, (1 << 19) // width))))).to(elements.device)
+    ni = torch.from_numpy(np.sort(g.integers(0, nodes.numel() // 4, 4096))).to(nodes.device)
+    return {"elements_sample": elements.view(rows, width)[ri].cpu().numpy().view(np.uint64),
+            "nodes_sample": nodes.view(-1, 4)[ni].cpu().numpy().view(np.uint64),
+            "root": root}
+
+
 def node_driven_proof(info, exprs, setup, publics, start_row, res):
     """The same proof once more with the JS ORCHESTRATION driving (north_star: "the JS orchestration keeps driving"): a fresh `node`
     child process runs tests/js/prove_c3.js -- prover.js's stage order (src/prover/prover.js:7-127) over the JS drop-in modules, every
@@ -728,9 +786,10 @@ def node_driven_proof(info, exprs, setup, publics, start_row, res):
             os.unlink(path)
 
 
-def bn128_commit_line(dev, n_bits, n_cols, steps, warmup):
+def bn128_commit_line(dev, n_bits, n_cols, steps, warmup, full=True, dump_dir=None):
     """config 4: extendAndMerkelize with the BN128 MerkleHash (merklehash_bn128_p.js:47-129, arity 16, non-custom): the GL
-    LDE of the 2^24 x 100 trace and the BN254-Poseidon linear hash + 16-ary tree over all 2^27 extended rows"""
+    LDE of the 2^24 x 100 trace and the BN254-Poseidon linear hash + 16-ary tree over all 2^27 extended rows.
+    full: board power, per-kernel times and rooflines as well"""
     import pil2gl
     from pil2gl import bn128
     arity = 16
@@ -745,12 +804,23 @@ def bn128_commit_line(dev, n_bits, n_cols, steps, warmup):
         return MH.merkelize(dst, n_cols, E)
     for _ in range(warmup):
         step()
-    power = BoardPower().start() if os.environ.get("PIL2GL_BENCH_POWER", "1") != "0" else None
+    power = BoardPower().start() if full and os.environ.get("PIL2GL_BENCH_POWER", "1") != "0" else None
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(steps):
         tree = step()
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
     board_power = power.finish() if power is not None else None
+    root = MH.root(tree)
+    if dump_dir:
+        dump_outputs(dump_dir, commit_outputs(dst, n_cols, tree["nodes"], root))
+    out = {"metric": "trace-cells/s, STARK commit step (extend + BN128 Poseidon Merkle tree, arity 16), blow-up 8",
+           "value": N * n_cols / dt, "unit": "trace-cells/s", "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": dt * 1e3,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (BN254 Fr, Montgomery) + u64 (Goldilocks LDE)", "data": "synthetic",
+           "config": {"workload": "config 4: extendAndMerkelize 2^%d rows x %d cols -> 2^%d rows, BN128 Poseidon linear hash + %d-ary tree over all 2^%d extended rows" % (n_bits, n_cols, n_bits + EXT_BITS, arity, n_bits + EXT_BITS),
+                      "mode": "commit", "nBits": n_bits, "nCols": n_cols, "nBitsExt": n_bits + EXT_BITS, "hash": "BN128-Poseidon (t = 17, 17, 3 per row; t = 17 in the tree)", "parallelism": "single GPU"}}
+    if not full:
+        out["root"] = hex(root)
+        return out
     t_lde = ev_time(lambda: pil2gl.interpolate(src, n_cols, n_bits, dst, n_bits + EXT_BITS), 1)
     t_tree = ev_time(lambda: MH.merkelize(dst, n_cols, E), 1)
     n_el = (n_cols + 2) // 3
@@ -766,11 +836,7 @@ def bn128_commit_line(dev, n_bits, n_cols, steps, warmup):
     floor_mfma_cyc = mfmas * 32.0 / N_SIMD                                          # 32 cycles of a SIMD's matrix pipe per 32x32x32 i8 instruction
     floor_ms = max(floor_cyc, floor_mfma_cyc) / CLOCK_HZ * 1e3                      # the two pipes run side by side (two waves per SIMD)
     alg = 8 * E * n_cols + 32 * (E + tree_perms)
-    out = {"metric": "trace-cells/s, STARK commit step (extend + BN128 Poseidon Merkle tree, arity 16), blow-up 8",
-           "value": N * n_cols / dt, "unit": "trace-cells/s", "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": dt * 1e3,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (BN254 Fr, Montgomery) + u64 (Goldilocks LDE)", "data": "synthetic",
-           "config": {"workload": "config 4: extendAndMerkelize 2^%d rows x %d cols -> 2^%d rows, BN128 Poseidon linear hash + %d-ary tree over all 2^%d extended rows" % (n_bits, n_cols, n_bits + EXT_BITS, arity, n_bits + EXT_BITS),
-                      "mode": "commit", "nBits": n_bits, "nCols": n_cols, "nBitsExt": n_bits + EXT_BITS, "hash": "BN128-Poseidon (t = 17, 17, 3 per row; t = 17 in the tree)", "parallelism": "single GPU"},
+    out.update({
            "roofline": {"bound": "hbm", "kernel": "bn_linear_hash_kernel + bn_merkle_level_kernel", "achieved": alg / t_tree / 1e6, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": alg / t_tree / 1e6 / HBM_PEAK_GBS, "traffic": None,
                         "note": "BN254 Poseidon is integer-issue bound by three orders of magnitude; see roofline_int_issue"},
@@ -781,15 +847,15 @@ def bn128_commit_line(dev, n_bits, n_cols, steps, warmup):
                                   "note": "floor = the larger of (a) every 32x32 product left on the vector ALU -- the S-boxes' Montgomery products and the rows' carry / reduction steps (bn128_work) -- issued back to back at the measured 4.5 cycles and (b) every matrix instruction of the linear layers at 32 cycles of its SIMD's matrix pipe; round 4's all-vector form needed 971 648 products per row (floor 3 847 ms)"},
            "kernels": [{"kernel": "BN128 merkelize (leaf hash + tree)", "ms": t_tree, "perms": leaf_perms + tree_perms, "Mperm_s": (leaf_perms + tree_perms) / t_tree / 1e3},
                        {"kernel": "interpolate", "ms": t_lde, "alg_bytes": 8 * N * n_cols * (1 + (1 << EXT_BITS)), "GBps": 8 * N * n_cols * 9 / t_lde / 1e6}],
-           "root": hex(MH.root(tree))}
+           "root": hex(root)})
     if board_power is not None:
         out["board_power"] = board_power
     return out
 
 
 def bench_bn128(args, dev, wl, n_bits, n_cols):
-    out = bn128_commit_line(dev, n_bits, n_cols, args.steps, args.warmup)
-    if not args.no_cpu_baseline:
+    out = bn128_commit_line(dev, n_bits, n_cols, args.steps, args.warmup, args.full, args.dump_outputs)
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_bn128(n_cols, 16)
         out["speedup_vs_cpu_port"] = out["value"] / out["cpu_baseline"]["value"]
     print(json.dumps(out), flush=True)
@@ -817,8 +883,11 @@ def bench_bn128_prove(args, dev, n_bits, n_cols):
     for _ in range(args.steps):
         res = stark.stark_gen(be, src, setup, info, exprs, publics)
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, proof_outputs(res))
     stages = {}
-    stark.stark_gen(be, src, setup, info, exprs, publics, timings=stages); torch.cuda.synchronize()
+    if args.full:
+        stark.stark_gen(be, src, setup, info, exprs, publics, timings=stages); torch.cuda.synchronize()
     N = 1 << n_bits
     out = {"metric": "STARK prove time (ms_per_step) and trace-cells/s, synthetic Fibonacci AIR, BN128 Poseidon (arity 16) Merkle trees and transcript + FRI, blow-up 8",
            "value": N * n_cols / dt, "unit": "trace-cells/s", "n_gpus": 1, "steps": args.steps, "warmup": max(1, args.warmup), "ms_per_step": dt * 1e3,
@@ -826,8 +895,10 @@ def bench_bn128_prove(args, dev, n_bits, n_cols):
            "config": {"workload": "full proof (commit, Q, evals, FRI %s, 64 queries) of 2^%d rows x %d cols -> 2^%d rows, verificationHashType BN128, 16-ary trees" % (
                           "/".join(str(b) for b in fri_steps_for(n_bits + EXT_BITS)), n_bits, n_cols, n_bits + EXT_BITS),
                       "mode": "prove", "config": "c4", "nBits": n_bits, "nCols": n_cols, "nBitsExt": n_bits + EXT_BITS, "hash": "BN128-Poseidon (arity 16)", "parallelism": "single GPU"},
-           "prove": {"seconds": dt, "stages_s": {k: round(v, 4) for k, v in stages.items()}, "const_tree_s": round(t_setup, 3)},
+           "prove": {"seconds": dt, "const_tree_s": round(t_setup, 3)},
            "root1": hex(res["proof"]["root1"]), "proofSha256": proof_sha256(res["proof"])}
+    if args.full:
+        out["prove"]["stages_s"] = {k: round(v, 4) for k, v in stages.items()}
     print(json.dumps(out), flush=True)
 
 
@@ -883,6 +954,83 @@ def other_configs(dev, be, main_wl, main_split):
     return res
 
 
+def kernel_figures(args, be, dev, src, dst, prove_ctx, wl, world, sharded_mode, n_bits, n_cols):
+    """--full: per-kernel timing with HIP events on the launch stream (each call below is exactly one kernel, or one kernel
+    family named in DESIGN.md), at the size this rank runs them: the whole extension, or its cosets; and the rooflines"""
+    import pil2gl
+    N = 1 << n_bits
+    cc = ((1 << EXT_BITS) // world) if sharded_mode else (1 << EXT_BITS)
+    rows = N * cc
+    if dst is None or dst.numel() != rows * n_cols:
+        dst = None
+        dst = torch.empty(rows * n_cols, dtype=torch.int64, device=dev)
+    iters = max(1, min(3, args.steps))
+    digests = torch.empty(rows * 4, dtype=torch.int64, device=dev)
+    # (--air perm: the witness is two stages of 2K and 9K columns; the per-kernel figures are taken on one N x 11K matrix)
+    ksrc = make_trace(N, n_cols, 77, dev) if (prove_ctx is not None and args.air == "perm") else src
+    if sharded_mode:
+        ws = src if wl == "c5" else None
+        lde = lambda: be.interpolate_cosets(ksrc, n_cols, n_bits, dst, n_bits + EXT_BITS, 0, cc, ws)
+    else:
+        lde = lambda: pil2gl.interpolate(ksrc, n_cols, n_bits, dst, n_bits + EXT_BITS)
+    t_lde = ev_time(lde, iters)
+    t_leaf = ev_time(lambda: pil2gl.linearHash(dst, n_cols, args.split, digests), iters)
+    leaf_clock_mhz = clock_under_hash_load()
+    # the other leaf form (splitLinearHash, linearhash_gpu.js:30-66: the reference's own *.starkstruct.gpu.json files set it), same rows
+    t_leaf_other = ev_time(lambda: pil2gl.linearHash(dst, n_cols, not args.split, digests), iters) if n_cols > 8 else None
+    lvl = torch.empty(rows * 2, dtype=torch.int64, device=dev)
+    t_lvl = ev_time(lambda: pil2gl.merkelizeLevel(digests, lvl), iters)
+    leaf_perms = rows * ((n_cols + 7) // 8) if n_cols > 4 else 0
+    if args.split and n_cols > 4:
+        batch = max(8, (n_cols + 3) // 4); nb = (n_cols + batch - 1) // batch
+        leaf_perms = rows * (sum((min(batch, n_cols - b * batch) + 7) // 8 if min(batch, n_cols - b * batch) > 4 else 0 for b in range(nb)) + (((4 * nb) + 7) // 8 if nb > 1 else 0))
+    # the FRI polynomial's weighted row sums over the stage matrix (2 openings): the HBM-bound kernel of the proof
+    t_dot = None
+    if n_cols % 2 == 0 and 32 <= n_cols <= 112:
+        import numpy as _np
+        from pil2gl import _lib as _l
+        coef = _np.random.default_rng(5).integers(0, 2 ** 63, (2, n_cols, 3), dtype=_np.uint64) % _np.uint64(0xFFFFFFFF00000001)
+        dacc = torch.empty(rows * 6, dtype=torch.int64, device=dev)
+        t_dot = ev_time(lambda: _l.call("pil2gl_rows_dot_ext_dev", pil2gl._ptr(dst), n_cols, rows, pil2gl._ptr(coef), 2, pil2gl._ptr(dacc), 0, None), iters)
+        del dacc
+    kernels = [
+        {"kernel": "linear_hash_kernel", "ms": t_leaf, "alg_bytes": 8 * rows * n_cols + 32 * rows, "perms": leaf_perms},
+        {"kernel": "interpolate (ntt_pass_kernel x / lde_mid_kernel)", "ms": t_lde, "alg_bytes": 8 * N * n_cols * (1 + cc)},
+        {"kernel": "merkle_level_kernel (first level)", "ms": t_lvl, "alg_bytes": 32 * rows + 16 * rows, "perms": rows // 2},
+    ]
+    if t_dot is not None:
+        kernels.append({"kernel": "rows_dot_mfma_kernel (FRI polynomial: weighted sums of every row, 2 openings)", "ms": t_dot, "alg_bytes": 8 * rows * n_cols + 48 * rows,
+                        "bound": "hbm"})
+    def split_perms(w):
+        batch = max(8, (w + 3) // 4); nb_ = (w + batch - 1) // batch
+        return sum((min(batch, w - b * batch) + 7) // 8 if min(batch, w - b * batch) > 4 else 0 for b in range(nb_)) + (((4 * nb_) + 7) // 8 if nb_ > 1 else 0)
+    if t_leaf_other is not None:
+        other_perms = rows * ((n_cols + 7) // 8 if args.split else split_perms(n_cols))
+        kernels.append({"kernel": "linear_hash_kernel (plain form)" if args.split else "linear_hash_split_kernel (splitLinearHash form of the same leaves)",
+                        "ms": t_leaf_other, "alg_bytes": 8 * rows * n_cols + 32 * rows, "perms": other_perms})
+    if wl == "c3" and not sharded_mode:                    # the committed PMC passes were taken at config 3, one GPU
+        pf = pmc_file()
+        kernels[0]["traffic"] = load_pmc(pf, "linear_hash_kernel")
+        kernels[1]["traffic"] = load_pmc_lde_traffic(pf)
+        kernels[2]["traffic"] = load_pmc(pf, "merkle_level_kernel")
+        for k in kernels[:3]:
+            k["traffic_source"] = "committed rocprofv3 PMC passes of one config-3 proof (profiles/%s: bytes by request size; not measured in this run)" % pf
+    for k in kernels:
+        k["GBps"] = k["alg_bytes"] / k["ms"] / 1e6
+        k["hbm_frac"] = k["GBps"] / HBM_PEAK_GBS
+        if k.get("perms"):
+            k["Gperm_s"] = k["perms"] / k["ms"] / 1e6
+    dom = max(kernels[:3] + [k for k in kernels[3:] if k.get("bound") == "hbm"], key=lambda k: k["ms"])
+    roofline = {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": dom["hbm_frac"], "traffic": dom.get("traffic"), "traffic_source": dom.get("traffic_source"),
+                "note": "Poseidon hashing is integer-issue bound (no 64-bit multiplier on gfx950): its HBM fraction is small by nature; roofline_int_issue prices it against its own roof, kernels[1] is the HBM-bound LDE"}
+    figs = {"roofline": roofline, "roofline_int_issue": poseidon_int_roofline(kernels[0]["perms"], kernels[0]["ms"], leaf_clock_mhz) if kernels[0]["perms"] else None,
+            "roofline_int_issue_lde": lde_int_roofline(n_bits, n_cols, cc, kernels[1]["ms"]), "kernels": kernels}
+    if t_leaf_other is not None:
+        figs["leaf_plain_ms" if args.split else "leaf_split_ms"] = t_leaf_other
+    return figs
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -901,6 +1049,8 @@ def main():
             mode = "prove-sharded"
     elif mode == "commit" and world > 1 and not args.replicas:
         mode = "commit-sharded"
+    if args.dump_outputs and (args.shard_of or mode == "commit-sharded"):
+        raise SystemExit("bench.py: --dump-outputs is not available for a commit-sharded run or a --shard-of rehearsal")
     if args.shard_of:
         if args.workload == "auto":
             args.workload = "c3"
@@ -1044,13 +1194,13 @@ def main():
     gc.collect(); gc.disable()
     if comm is not None:
         comm.reset_stats()
-    power = BoardPower().start() if rank == 0 and os.environ.get("PIL2GL_BENCH_POWER", "1") != "0" else None
+    power = BoardPower().start() if args.full and rank == 0 and os.environ.get("PIL2GL_BENCH_POWER", "1") != "0" else None
     barrier()
     t0 = time.perf_counter()
     step_marks = []
     for i in range(args.steps):
         mark("timed step %d" % i)
-        step()
+        res = step()
         step_marks.append(time.perf_counter())               # host clock only: no extra synchronisation inside the timed region
     barrier()
     mark("timed region done")
@@ -1070,81 +1220,15 @@ def main():
         for k in ("collectives", "bytes_sent_per_rank", "bytes_received_per_rank"):
             exchange[k] = exchange[k] // args.steps            # per step
         exchange["backend"] = backend + (" + HIP IPC windows (ranks share a GPU)" if exchange["mode"] == "ipc" else (" (RCCL over xGMI)" if backend == "nccl" else ""))
-    # one more pass, outside the timed region, with a synchronisation after every stage (collective in the sharded mode: all ranks)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, proof_outputs(res) if prove_ctx is not None else commit_outputs(dst, n_cols, nodes, MH.root({"nodes": nodes})))
+    # --full: one more pass, outside the timed region, with a synchronisation after every stage (collective in the sharded mode: all ranks)
     stage_times = {}
     last_proof = None
-    if mode in ("prove", "prove-sharded") and (rank == 0 or mode == "prove-sharded"):
+    if args.full and mode in ("prove", "prove-sharded") and (rank == 0 or mode == "prove-sharded"):
         last_proof = step(timings=stage_times); torch.cuda.synchronize()
 
     if rank == 0:
-        # ---- per-kernel timing with HIP events on the launch stream (each call below is exactly one kernel, or one kernel
-        #      family named in DESIGN.md), at the size this rank runs them: the whole extension, or its cosets ----
-        cc = ((1 << EXT_BITS) // world) if sharded_mode else (1 << EXT_BITS)
-        rows = N * cc
-        if dst is None or dst.numel() != rows * n_cols:
-            dst = None
-            dst = torch.empty(rows * n_cols, dtype=torch.int64, device=dev)
-        iters = max(1, min(3, args.steps))
-        digests = torch.empty(rows * 4, dtype=torch.int64, device=dev)
-        # (--air perm: the witness is two stages of 2K and 9K columns; the per-kernel figures are taken on one N x 11K matrix)
-        ksrc = make_trace(N, n_cols, 77, dev) if (prove_ctx is not None and args.air == "perm") else src
-        if sharded_mode:
-            ws = src if wl == "c5" else None
-            lde = lambda: be.interpolate_cosets(ksrc, n_cols, n_bits, dst, n_bits + EXT_BITS, 0, cc, ws)
-        else:
-            lde = lambda: pil2gl.interpolate(ksrc, n_cols, n_bits, dst, n_bits + EXT_BITS)
-        t_lde = ev_time(lde, iters)
-        t_leaf = ev_time(lambda: pil2gl.linearHash(dst, n_cols, args.split, digests), iters)
-        leaf_clock_mhz = clock_under_hash_load()
-        # the other leaf form (splitLinearHash, linearhash_gpu.js:30-66: the reference's own *.starkstruct.gpu.json files set it), same rows
-        t_leaf_other = ev_time(lambda: pil2gl.linearHash(dst, n_cols, not args.split, digests), iters) if n_cols > 8 else None
-        lvl = torch.empty(rows * 2, dtype=torch.int64, device=dev)
-        t_lvl = ev_time(lambda: pil2gl.merkelizeLevel(digests, lvl), iters)
-        leaf_perms = rows * ((n_cols + 7) // 8) if n_cols > 4 else 0
-        if args.split and n_cols > 4:
-            batch = max(8, (n_cols + 3) // 4); nb = (n_cols + batch - 1) // batch
-            leaf_perms = rows * (sum((min(batch, n_cols - b * batch) + 7) // 8 if min(batch, n_cols - b * batch) > 4 else 0 for b in range(nb)) + (((4 * nb) + 7) // 8 if nb > 1 else 0))
-        # the FRI polynomial's weighted row sums over the stage matrix (2 openings): the HBM-bound kernel of the proof
-        t_dot = None
-        if n_cols % 2 == 0 and 32 <= n_cols <= 112:
-            import numpy as _np
-            from pil2gl import _lib as _l
-            coef = _np.random.default_rng(5).integers(0, 2 ** 63, (2, n_cols, 3), dtype=_np.uint64) % _np.uint64(0xFFFFFFFF00000001)
-            dacc = torch.empty(rows * 6, dtype=torch.int64, device=dev)
-            t_dot = ev_time(lambda: _l.call("pil2gl_rows_dot_ext_dev", pil2gl._ptr(dst), n_cols, rows, pil2gl._ptr(coef), 2, pil2gl._ptr(dacc), 0, None), iters)
-            del dacc
-        kernels = [
-            {"kernel": "linear_hash_kernel", "ms": t_leaf, "alg_bytes": 8 * rows * n_cols + 32 * rows, "perms": leaf_perms},
-            {"kernel": "interpolate (ntt_pass_kernel x / lde_mid_kernel)", "ms": t_lde, "alg_bytes": 8 * N * n_cols * (1 + cc)},
-            {"kernel": "merkle_level_kernel (first level)", "ms": t_lvl, "alg_bytes": 32 * rows + 16 * rows, "perms": rows // 2},
-        ]
-        if t_dot is not None:
-            kernels.append({"kernel": "rows_dot_mfma_kernel (FRI polynomial: weighted sums of every row, 2 openings)", "ms": t_dot, "alg_bytes": 8 * rows * n_cols + 48 * rows,
-                            "bound": "hbm"})
-        def split_perms(w):
-            batch = max(8, (w + 3) // 4); nb_ = (w + batch - 1) // batch
-            return sum((min(batch, w - b * batch) + 7) // 8 if min(batch, w - b * batch) > 4 else 0 for b in range(nb_)) + (((4 * nb_) + 7) // 8 if nb_ > 1 else 0)
-        if t_leaf_other is not None:
-            other_perms = rows * ((n_cols + 7) // 8 if args.split else split_perms(n_cols))
-            kernels.append({"kernel": "linear_hash_kernel (plain form)" if args.split else "linear_hash_split_kernel (splitLinearHash form of the same leaves)",
-                            "ms": t_leaf_other, "alg_bytes": 8 * rows * n_cols + 32 * rows, "perms": other_perms})
-        if wl == "c3" and not sharded_mode:                    # the committed PMC passes were taken at config 3, one GPU
-            pf = pmc_file()
-            kernels[0]["traffic"] = load_pmc(pf, "linear_hash_kernel")
-            kernels[1]["traffic"] = load_pmc_lde_traffic(pf)
-            kernels[2]["traffic"] = load_pmc(pf, "merkle_level_kernel")
-            for k in kernels[:3]:
-                k["traffic_source"] = "committed rocprofv3 PMC passes of one config-3 proof (profiles/%s: bytes by request size; not measured in this run)" % pf
-        for k in kernels:
-            k["GBps"] = k["alg_bytes"] / k["ms"] / 1e6
-            k["hbm_frac"] = k["GBps"] / HBM_PEAK_GBS
-            if k.get("perms"):
-                k["Gperm_s"] = k["perms"] / k["ms"] / 1e6
-        dom = max(kernels[:3] + [k for k in kernels[3:] if k.get("bound") == "hbm"], key=lambda k: k["ms"])
-        roofline = {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": dom["hbm_frac"], "traffic": dom.get("traffic"), "traffic_source": dom.get("traffic_source"),
-                    "note": "Poseidon hashing is integer-issue bound (no 64-bit multiplier on gfx950): its HBM fraction is small by nature; roofline_int_issue prices it against its own roof, kernels[1] is the HBM-bound LDE"}
-        out = {}
         if prove_ctx is not None:
             info = prove_ctx[1]
             air_name = "two-stage permutation-check AIR (%d checks: 2 + 9 base columns each, grand-product hints)" % (n_cols // 11) if args.air == "perm" else "Fibonacci AIR"
@@ -1167,14 +1251,11 @@ def main():
             "config": {"workload": workload, "mode": mode, "config": wl,
                        "nBits": n_bits, "nCols": n_cols, "nBitsExt": n_bits + EXT_BITS, "hash": "GL-Poseidon-12",
                        "parallelism": ("coset-sharded x%d" % world) if sharded_mode else ("replicas x%d" % world if world > 1 else "single GPU")},
-            "roofline": roofline, "roofline_int_issue": poseidon_int_roofline(kernels[0]["perms"], kernels[0]["ms"], leaf_clock_mhz) if kernels[0]["perms"] else None,
-            "roofline_int_issue_lde": lde_int_roofline(n_bits, n_cols, cc, kernels[1]["ms"]),
-            "kernels": kernels,
         }
+        if args.full:
+            out.update(kernel_figures(args, be, dev, src, dst, prove_ctx, wl, world, sharded_mode, n_bits, n_cols))
         if board_power is not None:
             out["board_power"] = board_power
-        if t_leaf_other is not None:
-            out["leaf_plain_ms" if args.split else "leaf_split_ms"] = t_leaf_other
         if dist is not None:
             out["n_ranks"] = dist.get_world_size()
             out["ranks_share_gpus"] = bool(shared_gpu)
@@ -1186,30 +1267,30 @@ def main():
         if prove_ctx is not None:
             cexp = prove_ctx[2]["expressionsCode"][prove_ctx[1]["cExpId"]]["code"]["code"]
             fexp = prove_ctx[2]["expressionsCode"][prove_ctx[1]["friExpId"]]["code"]["code"]
-            out["prove"] = {"seconds": ms_per_step / 1e3, "stages_s": {k: round(v, 4) for k, v in stage_times.items()}, "host_ms_of_each_step": step_ms,
+            out["prove"] = {"seconds": ms_per_step / 1e3, "host_ms_of_each_step": step_ms,
                             "air": {"name": args.air, "machines": (n_cols // 11) if args.air == "perm" else n_cols // 2, "witness_stages": prove_ctx[1]["nStages"],
                                     "stage_widths": {k: v for k, v in prove_ctx[1]["mapSectionsN"].items()}, "hints": len(prove_ctx[1].get("hints", [])),
                                     "constraint_ops_per_extended_row": len(cexp), "fri_ops_per_extended_row": len(fexp),
                                     "openings": len(prove_ctx[1]["openingPoints"]), "evaluations": len(prove_ctx[1]["evMap"])}}
-        if world == 1:
+            if args.full:
+                out["prove"]["stages_s"] = {k: round(v, 4) for k, v in stage_times.items()}
+        if args.full and world == 1:
             out["witness_upload"] = h2d_sample(dev, 8 * N * n_cols)
-        if world == 1 and mode == "prove" and os.environ.get("PIL2GL_BENCH_FROM_HOST", "1") != "0":
-            del dst, digests, lvl                               # (back to torch's allocator cache: the proofs below reuse the blocks)
+        if args.full and world == 1 and mode == "prove" and os.environ.get("PIL2GL_BENCH_FROM_HOST", "1") != "0":
             setup_, info_, exprs_, publics_ = prove_ctx
             out["prove_from_host"] = prove_from_host(dev, src, lambda buf: stark.stark_gen(be, buf, setup_, info_, exprs_, publics_))
-        if world == 1 and mode == "prove" and args.air != "perm" and last_proof is not None and os.environ.get("PIL2GL_BENCH_NODE", "1") != "0":
+        if args.full and world == 1 and mode == "prove" and args.air != "perm" and last_proof is not None and os.environ.get("PIL2GL_BENCH_NODE", "1") != "0":
             import numpy as _np2
             start_row = [int(v) for v in src[:n_cols].cpu().numpy().view(_np2.uint64)]
-            dst = digests = lvl = None
             gc.collect(); torch.cuda.empty_cache()             # the child needs its own 143 GB at config 3; this process keeps the witness and the constant tree (~25 GB): 168 of 288 GB
             out["node_driven"] = node_driven_proof(prove_ctx[1], prove_ctx[2], prove_ctx[0], prove_ctx[3], start_row, last_proof)
             out["node_driven_ok"] = bool(out["node_driven"].get("proofSha256_equal")) or "skipped" in out["node_driven"]      # a failed child shows at the top level, not only inside its record
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline_prove(n_cols, args.split, args.air) if prove_ctx is not None else cpu_baseline_commit(n_cols, args.split)
             out["speedup_vs_cpu_port"] = value / out["cpu_baseline"]["value"]
-        if world == 1 and mode == "prove" and args.air != "perm" and os.environ.get("PIL2GL_BENCH_OTHER", "1") != "0":
+        if args.full and world == 1 and mode == "prove" and args.air != "perm" and os.environ.get("PIL2GL_BENCH_OTHER", "1") != "0":
             # the other BASELINE configurations, timed by this run too (outside `value`): everything of the headline workload goes first
-            src = dst = digests = lvl = nodes = last_proof = prove_ctx = setup = consts = ksrc = lde = None
+            src = dst = nodes = last_proof = prove_ctx = setup = consts = res = None
             gc.collect(); torch.cuda.empty_cache()
             out["other_configs"] = other_configs(dev, be, wl, args.split)
         print(json.dumps(out), flush=True)

@@ -4,7 +4,7 @@ set -eu; : "${GRAFT_REPO_ROOT:?run on the GPU box: gpurun -- bash tools/pmc_cloc
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_clock; mkdir -p $O
 export PIL2GL_BENCH_FROM_HOST=0
-rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT --kernel-trace --output-format csv -d $O/a -o p -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $O/a.log 2>&1
+rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT --kernel-trace --output-format csv -d $O/a -o p -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $O/a.log 2>&1
 python3 - <<PY
 import csv, collections, glob
 dur = {}
