@@ -8,12 +8,15 @@
 // host by the published Poseidon parameter generation (Grain LFSR) and agree with every constant set the reference holds
 // (tests/test_bn128_oracle.py pins the same generator; tests/test_gpu_bn128.py compares this one with it).
 //
-// The partial rounds run in the sparse form (derivation below, next to derive_sparse()): 2t-1 products per round instead
-// of t^2; outputs are the same field elements as the dense statement (the dense form is kept for tests).
-//
-// Layout: one permutation per lane; the t state elements (8 limbs each, Montgomery form) live in LDS as
-// [element][limb][lane] (conflict-free, element index may be a run-time value); a dense layer keeps its new rows in
-// registers until all are done (dense_mul).  A row is accumulated unreduced in 17 limbs (t products) and reduced once.
+// One pipeline per width (bn_perm), one permutation per lane, the linear layers on the matrix cores (bn_mfma.cuh) and the S-box in radix
+// 2^29 (bn_field29.cuh):
+//   t = 2..4    perm_small: round by round as poseidon.circom states it, state and tiles in registers;
+//   t = 5..16   the partial rounds in the sparse form (derivation below, next to derive_sparse(): 2t-1 products per round instead of t^2),
+//               four to a block on the matrix cores (partial_rounds_mfma), the rp % 4 rounds left over on the vector ALU (partial_rounds);
+//   t = 17      the same phases in ONE function body (the arity-16 trees).
+// Between the layers the state is a lazy representative (< 2^255) in LDS as [element][limb][lane] for the lower elements and in private
+// memory for the others ("Where the state lives" below); every round constant but the first rides on a layer's row constants.
+// Few permutations (<= WAVE_PER_PERM_MAX) run the circuit's dense statement instead, a wave each (bn_sponge_chain_kernel).
 // Nodes are stored as the reference stores them: 4 little-endian u64 words of the Montgomery form.
 #include "common.h"
 #include "bn_field.cuh"
@@ -22,45 +25,29 @@
 #include <mutex>
 #include <vector>
 #include <string.h>
-#include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
 
 using namespace pil2gl;
 using bn::u32;
 
-// The S-box of the matrix-core pipeline in radix 2^29 (bn_field29.cuh: no carry instructions; its output is the state form times 2^-20,
-// which the tiles reading it take back).  -DBN_SBOX29=0: the 32-bit-limb products (A/B builds).
-#ifndef BN_SBOX29
-#define BN_SBOX29 1
-#endif
-// State elements kept in LDS (the rest in private memory: "Where the state lives" below) and the batch in which the partial rounds fetch the others'
-// operands (partial_rounds_mfma_impl::rows): both shape the order of the tile stream the host writes (mfma_partial_tables).
-#ifndef BN_LDS_ELEMS
-#define BN_LDS_ELEMS 10
-#endif
-#ifndef BN_SMALL_T
-#define BN_SMALL_T 4                    // widths up to this run the permutation round by round with the state and the layer's tiles in registers (perm_small)
-#endif
-#ifndef BN_HI_BATCH
-#define BN_HI_BATCH 4
-#endif
-
 namespace {
 
+// State elements kept in LDS (the rest in private memory: "Where the state lives" below): 10 = 20 KB per wave, two waves per SIMD.  With the
+// batch in which the partial rounds fetch the others' operands (partial_rounds_mfma_impl::rows: a batch of four leaves the registers for the
+// accumulators) it shapes the order of the tile stream the host writes (mfma_partial_tables).
+constexpr int BN_LDS_ELEMS = 10;
+constexpr int BN_HI_BATCH = 4;
+constexpr int BN_SMALL_T = 4;                        // widths up to this run the permutation round by round with the state and the layer's tiles in registers (perm_small)
 constexpr int BN_BLOCK = 64;                         // lanes of a wave = permutations a wave carries
 // Waves per workgroup.  Every wave works alone on its own 64 permutations and its own LDS slice; what the waves of a workgroup share is
 // TIME: a barrier at the start of every matrix phase (dense layer, rows on y, column update) keeps them on the same operand tiles, so that
 // of the workgroup's loads of a tile one goes to the L2 and the others hit the CU's L1.
-#ifndef BN_WG_WAVES
-#define BN_WG_WAVES 4
-#endif
+constexpr int BN_WG_WAVES = 4;
 constexpr int BN_THREADS = BN_BLOCK * BN_WG_WAVES;
-#if BN_WG_WAVES > 1
-#define BN_SYNC() __syncthreads()
-#else
-#define BN_SYNC()
-#endif
+// Up to this many permutations in one call run a wave each (bn_sponge_chain_kernel): a lane each would leave them at the latency of one wave
+// working alone (~3 ms at t = 17); a wave each runs them in ~0.5 ms while the SIMDs outnumber them
+constexpr long WAVE_PER_PERM_MAX = 2048;
 constexpr int N_ROUNDS_F = 8;
 const int N_ROUNDS_P[16] = { 56, 57, 56, 60, 60, 63, 64, 63, 60, 66, 60, 65, 70, 60, 64, 68 };   // poseidon.circom:8
 
@@ -130,11 +117,11 @@ struct Grain {
 
 // device tables of one state width t, Montgomery form, 8 limbs per element, one allocation:
 //   C8[8][t]  constants of the 4+4 full rounds (the first of the second half also carries what the partial rounds pushed out)
-//   M[t][t]   dense MDS;  D[t-1][t-1] = Mhat^RP;  S[RP] scalar constants;  V[RP][t-1], W[RP][t-1] sparse rows / columns
-//   Cd[(8+RP)][t] the original constants, for the dense (test) form
-//   Mt / Dt   the same two dense layers as matrix-core operand tiles (bn_mfma.cuh), MK / DK their per-row constants;
+//   M[t][t]   dense MDS;  S[RP] scalar constants;  V[RP][t-1], W[RP][t-1] sparse rows / columns
+//   Cd[(8+RP)][t] the original constants (the dense statement of the chain kernel, perm_small's first round)
+//   Mt / Dt   the dense layer and D = diag(1, Mhat^RP) as matrix-core operand tiles (bn_mfma.cuh), MK / DK their per-row constants;
 //   Pt        the tile stream of the blocked partial rounds, KR / KU its row constants (mfma_partial_tables)
-struct Params { int t = 0, rp = 0; u32 *base = nullptr, *C8, *M, *D, *S, *V, *W, *Cd; u32 m00[8];
+struct Params { int t = 0, rp = 0; u32 *base = nullptr, *C8, *M, *S, *V, *W, *Cd; u32 m00[8];
                 const bnm::v4i *Mt = nullptr, *Dt = nullptr, *Pt = nullptr; const u32 *MK = nullptr, *DK = nullptr, *KR = nullptr, *KU = nullptr;
                 const bnm::v4i *Mt0 = nullptr; const u32 *MK0 = nullptr, *C0p = nullptr;        // the first layer for inputs S-boxed as plain integers (plain_sbox_store)
                 const bnm::v4i *St = nullptr; const u32 *SK = nullptr; };                         // widths <= BN_SMALL_T: the round-by-round form in registers (perm_small)
@@ -232,7 +219,7 @@ struct MfmaConsts {
 // one tile (1 KB, lane order) of the coefficient a0 (Montgomery form); tot += the sum of its 32 constants.  sboxed: the operand this tile
 // multiplies comes straight out of the S-box, i.e. (bn_field29.cuh) carries a factor 2^-20: the coefficient takes it back
 void mfma_tile(const MfmaConsts &mc, const U256 &a0, int8_t *tile, U256 &tot, bool sboxed, const U256 *extra = nullptr) {
-    U256 a = sboxed && BN_SBOX29 ? h_mont(a0, h_to_mont(U256{ { 1ull << 20, 0, 0, 0 } })) : a0;
+    U256 a = sboxed ? h_mont(a0, h_to_mont(U256{ { 1ull << 20, 0, 0, 0 } })) : a0;
     if (extra) a = h_mont(a, *extra);                // (a further factor in Montgomery form: the plain-input first layer)
     for (int b = 0; b < 32; b++) {
         const U256 c = h_mont(a, mc.P[b]);           // a 2^(8b+32) mod r as a plain integer
@@ -336,11 +323,11 @@ int get_params(int t, const Params **out) {
         P2_TRY(derive_sparse(t, rp, C, M, C8, D, S, V, W));
         Vec all;
         auto put = [&](const Vec &x) { size_t o = all.size(); all.insert(all.end(), x.begin(), x.end()); return o; };
-        const size_t oC8 = put(C8), oM = put(M), oD = put(D), oS = put(S), oV = put(V), oW = put(W), oCd = put(C);
+        const size_t oC8 = put(C8), oM = put(M), oS = put(S), oV = put(V), oW = put(W), oCd = put(C);
         u32 *d = nullptr;
         HIP_TRY(hipMalloc((void **)&d, all.size() * 32));
         HIP_TRY(hipMemcpy(d, all.data(), all.size() * 32, hipMemcpyHostToDevice));
-        P.base = d; P.C8 = d + oC8 * 8; P.M = d + oM * 8; P.D = d + oD * 8; P.S = d + oS * 8; P.V = d + oV * 8; P.W = d + oW * 8; P.Cd = d + oCd * 8;
+        P.base = d; P.C8 = d + oC8 * 8; P.M = d + oM * 8; P.S = d + oS * 8; P.V = d + oV * 8; P.W = d + oW * 8; P.Cd = d + oCd * 8;
         memcpy(P.m00, M[0].w, 32);
         {
             std::vector<int8_t> tm, td, tpr, tm0; Vec km0, km, kd, kr, ku, km0p, c0p;
@@ -363,17 +350,15 @@ int get_params(int t, const Params **out) {
             // C8[4] on elements 1..n -- element 0 gets C8[4][0] from the last partial round's row when that round is one of the
             // blocked ones (rp % 4 == 0), from the vector code otherwise.  MK: one set per dense layer of the permutation, 8 x t.
             km.resize((size_t)8 * t);
-            const bool nofold = getenv("PIL2GL_BN128_NOFOLD") && atoi(getenv("PIL2GL_BN128_NOFOLD"));
             for (int inst = 0; inst < 8; inst++) for (int i = 0; i < t; i++) {
                 U256 f = { { 0, 0, 0, 0 } };
-                if (nofold) {}
-                else if (inst == 3) { if (i == 0) f = S[0]; }
+                if (inst == 3) { if (i == 0) f = S[0]; }
                 else if (inst < 7) f = C8[(size_t)(inst + 1) * t + i];
                 km[(size_t)inst * t + i] = h_addmod(km0[i], f);
             }
-            for (int i = 0; i < t; i++) km0p[i] = h_addmod(km0p[i], C8[(size_t)t + i]);      // (used without PIL2GL_BN128_NOFOLD only)
-            if (!nofold) for (int i = 0; i < n; i++) kd[i] = h_addmod(kd[i], C8[(size_t)4 * t + 1 + i]);
-            if (!nofold && rp % 4 == 0 && rp >= 4) kr[(size_t)rp - 1] = h_addmod(kr[(size_t)rp - 1], C8[(size_t)4 * t]);
+            for (int i = 0; i < t; i++) km0p[i] = h_addmod(km0p[i], C8[(size_t)t + i]);
+            for (int i = 0; i < n; i++) kd[i] = h_addmod(kd[i], C8[(size_t)4 * t + 1 + i]);
+            if (rp % 4 == 0 && rp >= 4) kr[(size_t)rp - 1] = h_addmod(kr[(size_t)rp - 1], C8[(size_t)4 * t]);
             // Small widths (t <= BN_SMALL_T): poseidon.circom:22-44 as written, every round one t x t layer of the SAME matrix -- two tile sets (after a full
             // round every column comes out of the S-box, after a partial round only column 0) that stay in registers, and one row constant per round and row
             // (the layer's own + the next round's constants).  No tile stream, no sparse blocks: a width-3 permutation is a chain of 65 short rounds whose
@@ -425,36 +410,12 @@ int get_params(int t, const Params **out) {
 }
 
 // ------------------------------------------------------------------------------------------ device side
-// -DBN_STAMPS: a diagnostic build that sums, per phase of the matrix-core permutation, the shader cycles a wave spends in it
-// (s_memtime around each phase, lane 0 adds into g_bn_stamps at the end of a permutation; pil2gl_bn128_debug_stamps reads them).
-// No stamp executes in the product build.
-#ifdef BN_STAMPS
-__device__ unsigned long long g_bn_stamps[16];
-__device__ __forceinline__ unsigned long long bn_now() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    return t;
-}
-#define BN_STAMP(slot, expr) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t0_ = bn_now(); __builtin_amdgcn_sched_barrier(0); expr; \
-    __builtin_amdgcn_sched_barrier(0); const unsigned long long t1_ = bn_now(); __builtin_amdgcn_sched_barrier(0); if (st.lane == 0) atomicAdd(&g_bn_stamps[slot], t1_ - t0_); }
-#else
-#define BN_STAMP(slot, expr) { expr; }
-#endif
-// -DBN_PRIO_MFMA=n: the wave raises its issue priority to n while it feeds the matrix pipe (dense layers, rows on y, column updates) and drops it
-// to 0 for its vector phases, so that of a SIMD's two waves the one in a matrix phase is served first (A/B builds; 0 = no s_setprio at all)
-#ifndef BN_PRIO_MFMA
-#define BN_PRIO_MFMA 0
-#endif
-#if BN_PRIO_MFMA
-#define BN_PRIO(n) __builtin_amdgcn_s_setprio(n)
-#else
-#define BN_PRIO(n)
-#endif
-struct PermArgs { const u32 *C8, *M, *D, *S, *V, *W, *Cd; int t, rp, dense; u32 m00[8];
-                  const bnm::v4i *Mt, *Dt, *Pt; const u32 *MK, *DK, *KR, *KU; int mfma, nofold;
-                  const bnm::v4i *Mt0; const u32 *MK0, *C0p; int plain;
+struct PermArgs { const u32 *C8, *M, *S, *V, *W, *Cd; int t, rp; u32 m00[8];
+                  const bnm::v4i *Mt, *Dt, *Pt; const u32 *MK, *DK, *KR, *KU;
+                  const bnm::v4i *Mt0; const u32 *MK0, *C0p;
+                  int plain;         // plain: elements 1..t-1 arrive S-boxed from the absorb (leaf kernel, width 17)
                   int nout1;         // nout1: the caller reads element 0 of the result only (sponges, tree nodes): the last layer computes ONE row
-                  const bnm::v4i *St; const u32 *SK; int small_; };      // small_: the width runs perm_small      // plain: elements 1..t-1 arrive S-boxed from the absorb (leaf kernel, width 17)
+                  const bnm::v4i *St; const u32 *SK; };
 
 // Where the state lives.  Elements [0, BN_LDS_ELEMS) in LDS as [element][limb][lane]; the elements above -- only the states
 // wider than BN_LDS_ELEMS have any: t = 11..17 -- in the lane's own private (scratch) memory, which the hardware swizzles so
@@ -470,9 +431,6 @@ __host__ __device__ constexpr int lds_words(int tmax) { return (tmax < BN_LDS_EL
 #define S_LDS(st, j, l) (st).S[(((j) * 8 + (l)) * BN_BLOCK) + (st).lane]
 
 __device__ __forceinline__ void lds_load(const St st, int j, u32 x[8]) {
-#ifdef BN_ABLATE_SCRATCH
-    if (j >= BN_LDS_ELEMS) j -= 17 - BN_LDS_ELEMS;   // timing experiments only: the upper elements aliased onto LDS slots, results meaningless
-#endif
     if (j < BN_LDS_ELEMS) {
 #pragma unroll
         for (int l = 0; l < 8; l++) x[l] = S_LDS(st, j, l);
@@ -484,9 +442,6 @@ __device__ __forceinline__ void lds_load(const St st, int j, u32 x[8]) {
     }
 }
 __device__ __forceinline__ void lds_store(const St st, int j, const u32 x[8]) {
-#ifdef BN_ABLATE_SCRATCH
-    if (j >= BN_LDS_ELEMS) j -= 17 - BN_LDS_ELEMS;
-#endif
     if (j < BN_LDS_ELEMS) {
 #pragma unroll
         for (int l = 0; l < 8; l++) S_LDS(st, j, l) = x[l];
@@ -512,38 +467,23 @@ __device__ __forceinline__ void lds_store_b(const St st, int j, const bnm::v4i &
     for (int q = 0; q < 4; q++) { x[q] = (u32)b0[q]; x[4 + q] = (u32)b1[q]; }
     lds_store(st, j, x);
 }
-// wave-uniform address.  WIDE: the tables live in global memory; saying so (the pointers reach the out-of-line helpers as
-// generic ones) turns the flat loads into global loads, whose counter is separate from the LDS one and in order, so that a
-// request for the next term can stay in flight across the current multiply
+// wave-uniform address.  The tables live in global memory; saying so (the pointers reach the out-of-line helpers as generic ones)
+// turns the flat loads into global loads, whose counter is separate from the LDS one and in order, so that a request for the
+// next term can stay in flight across the current multiply
 typedef const u32 __attribute__((address_space(1))) *gconst_u32;
-template <bool WIDE>
 __device__ __forceinline__ void load_const(const u32 *p, size_t idx, u32 c[8]) {
-    if constexpr (WIDE) {
-        gconst_u32 q = (gconst_u32)(p + idx * 8);
+    gconst_u32 q = (gconst_u32)(p + idx * 8);
 #pragma unroll
-        for (int l = 0; l < 8; l++) c[l] = q[l];
-    } else {
-#pragma unroll
-        for (int l = 0; l < 8; l++) c[l] = p[idx * 8 + l];
-    }
+    for (int l = 0; l < 8; l++) c[l] = q[l];
 }
 __device__ __forceinline__ void pow5(u32 x[8]) {
     u32 x2[8], x4[8];
     bn::fr_mul(x2, x, x); bn::fr_mul(x4, x2, x2); bn::fr_mul(x, x4, x);
 }
-// the same on lazy representatives: x < 0.69 * 2^256 in (a layer's output < 2^255, plus a round constant at most), x^5 < 0.63 * 2^256
-// out -- any 256-bit value will do for the matrix operand that reads it (bn_field.cuh fr_mul_nr)
-__device__ __forceinline__ void pow5_lazy(u32 x[8]) {
-#ifdef BN_ABLATE_SBOX
-    return;                                          // timing experiments only (tools): the S-box left out, results meaningless
-#endif
-#if BN_SBOX29
-    bn29::pow5(x);                                   // x^5 in the state's form times 2^-20 (the next layer's tiles carry 2^20)
-#else
-    u32 x2[8], x4[8];
-    bn::fr_mul_nr(x2, x, x); bn::fr_mul_nr(x4, x2, x2); bn::fr_mul_nr(x, x4, x);
-#endif
-}
+// the same on lazy representatives (a layer's output < 2^255, plus a round constant at most), in radix 2^29 (bn_field29.cuh: no carry
+// instructions): x^5 in the state's form times 2^-20 -- the next layer's tiles carry 2^20 -- and any 256-bit value will do for the
+// matrix operand that reads it
+__device__ __forceinline__ void pow5_lazy(u32 x[8]) { bn29::pow5(x); }
 // x + c for a lazy x < 2^255 and a constant c < r: < 0.69 * 2^256, left as it is (the S-box that follows takes it, pow5_lazy)
 __device__ __forceinline__ void add_lazy(u32 x[8], const u32 c[8]) { bnm::add_chain8(x, c); }
 // The S-box layer of a full round in the matrix-core pipeline: the round's constants arrive with the previous layer's rows
@@ -560,7 +500,7 @@ __device__ __forceinline__ void sbox_lazy_impl(const St st, int t, const u32 *C)
         if (j + 1 < t) lds_load(st, j + 1, xn);
         if (C) {
             u32 c[8];
-            load_const<true>(C, (size_t)j, c);
+            load_const(C, (size_t)j, c);
             add_lazy(x, c);
         }
         pow5_lazy(x);
@@ -577,71 +517,13 @@ __device__ __noinline__ void canon_state(const St st, int t) {
     }
 }
 
-// x^5 on elements [0, nSbox) after adding constants C[0..t), then the dense n x n matrix A applied to elements
-// [first, first+n) of buffer cur into buffer cur^1 (elements below `first` are copied)
-template <bool WIDE>
-__device__ __noinline__ void add_sbox(const St st, int cur, int t, const u32 *C, size_t cOff, int nSbox) {
-    for (int j = 0; j < t; j++) {
-        u32 x[8], c[8];
-        lds_load(st, j, x);
-        load_const<WIDE>(C, cOff + j, c);
-        bn::fr_add(x, c);
-        if (j < nSbox) pow5(x);
-        lds_store(st, j, x);
-    }
-}
-// In place: every row reads the whole old state, so the n new elements wait in a per-lane private array (scratch memory,
-// 17 x 32 B, a few KB of traffic per permutation against ~10^5 multiply steps) until all rows are done; one LDS buffer per
-// wave then suffices (4 waves per CU at t = 17 instead of 2).
-template <bool WIDE>
-__device__ __noinline__ void dense_mul(const St st, int cur, const u32 *A, int n, int first) {
-    u32 nw[17 * 8];
-    for (int i = 0; i < n; i++) {
-        u32 acc[17];
-#pragma unroll
-        for (int l = 0; l < 17; l++) acc[l] = 0;
-        if constexpr (WIDE) {
-            // operands of term j+1 are requested before term j is multiplied: the LDS read and the (wave-uniform) table
-            // load then overlap the ~600 issue cycles of a multiply-accumulate instead of stalling the wave, which at this
-            // width is alone on its SIMD.  One multiply in the loop body: the permutation has to stay in the instruction cache.
-            u32 y[8], m[8];
-            lds_load(st, first, y);
-            load_const<true>(A, (size_t)i * n, m);
-            for (int j = 0; j < n; j++) {
-                u32 yn[8], mn[8];
-                if (j + 1 < n) {
-                    lds_load(st, first + j + 1, yn);
-                    load_const<true>(A, (size_t)i * n + j + 1, mn);
-                }
-                __builtin_amdgcn_sched_barrier(0);   // keep the requests ahead of the multiply (the scheduler sinks them otherwise)
-                bn::mac17(acc, y, m);
-#pragma unroll
-                for (int l = 0; l < 8; l++) { y[l] = yn[l]; m[l] = mn[l]; }
-            }
-        } else {
-            for (int j = 0; j < n; j++) {
-                u32 y[8], m[8];
-                lds_load(st, first + j, y);
-                load_const<false>(A, (size_t)i * n + j, m);
-                bn::mac17(acc, y, m);
-            }
-        }
-        u32 o[8];
-        bn::redc17(o, acc);
-#pragma unroll
-        for (int l = 0; l < 8; l++) nw[i * 8 + l] = o[l];
-    }
-    for (int i = 0; i < n; i++) lds_store(st, first + i, &nw[i * 8]);
-}
-
-// The same layer on the matrix cores (bn_mfma.cuh): the N operand pairs are made once and stay in registers, a row is N pairs of
+// A dense layer on the matrix cores (bn_mfma.cuh): the N operand pairs are made once and stay in registers, a row is N pairs of
 // MFMAs and one short finish; no 32x32 product of the state is left.  The operand tiles come from the L2 as ONE linear stream
 // (row after row, tile after tile) read MFMA_AHEAD tiles ahead of their use -- a load per tile and lane, the oldest awaited
 // alone -- so the table carries MFMA_AHEAD spare tiles after its last one.
 constexpr int MFMA_AHEAD = 8;
-#ifndef BN_DENSE_AHEAD_SBOX
-#define BN_DENSE_AHEAD_SBOX 6
-#endif
+// with the S-box in the row loop the ring is shorter: the S-box needs some of its registers (4 / 6 / 8 tiles 27.15 / 26.9 / 26.9 ms)
+constexpr int MFMA_AHEAD_SBOX = 6;
 // SBOX: the NEXT round's S-box is applied to every finished row before it is stored (its constant came with the row): the separate S-box pass over
 // the state -- a load and a store of every element, seven of them in private memory -- disappears for that round.
 // STORE_B: the rows of elements 1.. are stored in operand form (the layer before the partial rounds); LOAD_B: the inputs are in that form (the layer after).
@@ -660,32 +542,21 @@ __device__ __forceinline__ void dense_mfma_impl(const St st, const bnm::v4i *til
     }
     const bnm::Sh sh = bnm::sh_init();
     bnm::gtile tp = (bnm::gtile)tiles + st.lane;
-    constexpr int AHEAD = SBOX ? BN_DENSE_AHEAD_SBOX : MFMA_AHEAD;      // (the S-box in the row loop needs some of the ring's registers: 4 / 6 / 8 tiles 27.15 / 26.9 / 26.9 ms)
+    constexpr int AHEAD = SBOX ? MFMA_AHEAD_SBOX : MFMA_AHEAD;
     bnm::v4i q[AHEAD];
-    BN_SYNC();                                       // the workgroup's waves start the layer's tile stream together
+    __syncthreads();                                 // the workgroup's waves start the layer's tile stream together
 #pragma unroll
     for (int k = 0; k < AHEAD; k++) q[k] = tp[(size_t)k * 64];
-#ifdef BN_STAMPS
-    unsigned long long sBurst = 0, sCarry = 0, sFinish = 0;
-#endif
     for (int i = 0; i < nrows; i++) {
         u32 k[8], o[8];
-#ifdef BN_STAMPS
-        __builtin_amdgcn_sched_barrier(0); const unsigned long long tr0 = bn_now(); __builtin_amdgcn_sched_barrier(0);
-#endif
-        load_const<true>(kc, (size_t)i, k);          // asked for ahead of the row's tiles: an in-order counter waits for everything older than what it wants
+        load_const(kc, (size_t)i, k);                // asked for ahead of the row's tiles: an in-order counter waits for everything older than what it wants
         bnm::v16i a0, a1;
-        BN_PRIO(BN_PRIO_MFMA);
 #pragma unroll
         for (int j = 0; j < N; j++) {
             const bnm::v4i a = q[0];
 #pragma unroll
             for (int k = 0; k + 1 < AHEAD; k++) q[k] = q[k + 1];
-#ifdef BN_ABLATE_TILEADDR
-            q[AHEAD - 1] = ((bnm::gtile)tiles + st.lane)[(size_t)((j + AHEAD) & 7) * 64];      // timing experiments only: every tile from one 8 KB window
-#else
             q[AHEAD - 1] = tp[(size_t)(j + AHEAD) * 64];
-#endif
             if (j == 0) bnm::mfma_first(a, B0[0], B1[0], a0, a1);
             else {
                 a0 = bnm::mfma(a, B0[j], a0);
@@ -693,40 +564,17 @@ __device__ __forceinline__ void dense_mfma_impl(const St st, const bnm::v4i *til
             }
         }
         tp += (size_t)N * 64;
-        BN_PRIO(0);
-#ifdef BN_STAMPS
-        // (the burst ends when the first accumulator can be read: the stamp after an instruction that depends on both)
-        u32 w[10];
-        __builtin_amdgcn_sched_barrier(0); const unsigned long long tr1 = bn_now(); __builtin_amdgcn_sched_barrier(0);
-        bnm::carry_pair(a0, a1, w, sh);
-        __builtin_amdgcn_sched_barrier(0); const unsigned long long tr2 = bn_now(); __builtin_amdgcn_sched_barrier(0);
-        bnm::finish_words(w, k, o);
-        if constexpr (SBOX) pow5_lazy(o);
-        if (STORE_B && first + i >= 1) { bnm::v4i ob0, ob1; bnm::b_prep(o, ob0, ob1); lds_store_b(st, first + i, ob0, ob1); }
-        else lds_store(st, first + i, o);
-        __builtin_amdgcn_sched_barrier(0); const unsigned long long tr3 = bn_now(); __builtin_amdgcn_sched_barrier(0);
-        sBurst += tr1 - tr0; sCarry += tr2 - tr1; sFinish += tr3 - tr2;
-#else
         bnm::finish_row(a0, a1, k, o, sh);
         if constexpr (SBOX) pow5_lazy(o);
         if (STORE_B && first + i >= 1) { bnm::v4i ob0, ob1; bnm::b_prep(o, ob0, ob1); lds_store_b(st, first + i, ob0, ob1); }
         else lds_store(st, first + i, o);            // the old state is in B0 / B1: the new row can go straight to its place
-#endif
     }
-#ifdef BN_STAMPS
-    if (st.lane == 0) { atomicAdd(&g_bn_stamps[13], sBurst); atomicAdd(&g_bn_stamps[14], sCarry); atomicAdd(&g_bn_stamps[15], sFinish); atomicAdd(&g_bn_stamps[6], (unsigned long long)nrows); }
-#endif
 }
 template <int N>
 __device__ __noinline__ void dense_mfma_n(const St st, const bnm::v4i *tiles, const u32 *kc, int first, int nrows) { dense_mfma_impl<N>(st, tiles, kc, first, nrows < N ? nrows : N); }
+// the widths 5..16 of bn_perm: the full rounds' layers (n = t) and the closing layer diag(1, Mh^RP) of the partial rounds (n = t - 1)
 __device__ __forceinline__ void dense_mfma(const St st, const bnm::v4i *tiles, const u32 *kc, int n, int first, int nrows = 17) {
-#ifdef BN_ABLATE_DENSE
-    return;                                          // timing experiments only: the layer left out, results meaningless
-#endif
     switch (n) {
-    case 1: dense_mfma_n<1>(st, tiles, kc, first, nrows); break;
-    case 2: dense_mfma_n<2>(st, tiles, kc, first, nrows); break;
-    case 3: dense_mfma_n<3>(st, tiles, kc, first, nrows); break;
     case 4: dense_mfma_n<4>(st, tiles, kc, first, nrows); break;
     case 5: dense_mfma_n<5>(st, tiles, kc, first, nrows); break;
     case 6: dense_mfma_n<6>(st, tiles, kc, first, nrows); break;
@@ -739,15 +587,12 @@ __device__ __forceinline__ void dense_mfma(const St st, const bnm::v4i *tiles, c
     case 13: dense_mfma_n<13>(st, tiles, kc, first, nrows); break;
     case 14: dense_mfma_n<14>(st, tiles, kc, first, nrows); break;
     case 15: dense_mfma_n<15>(st, tiles, kc, first, nrows); break;
-    case 16: dense_mfma_n<16>(st, tiles, kc, first, nrows); break;
-    default: dense_mfma_n<17>(st, tiles, kc, first, nrows); break;
+    default: dense_mfma_n<16>(st, tiles, kc, first, nrows); break;
     }
 }
 
-// partial rounds, sparse form, in place: element 0 stays in registers.  WIDE: the next term's requests are pinned ahead of
-// the current term's two products (see dense_mul)
-template <bool WIDE>
-__device__ __noinline__ void partial_rounds(const St st, int cur, const PermArgs &A, int kFirst) {
+// partial rounds, sparse form, in place: element 0 stays in registers (the rp % 4 rounds the blocks leave over, on canonical values)
+__device__ __noinline__ void partial_rounds(const St st, const PermArgs &A, int kFirst) {
     const int t = A.t;
     u32 x0[8], m00[8];
     lds_load(st, 0, x0);
@@ -756,43 +601,22 @@ __device__ __noinline__ void partial_rounds(const St st, int cur, const PermArgs
     const int n = t - 1;
     for (int k = kFirst; k < A.rp; k++) {
         u32 c[8];
-        load_const<WIDE>(A.S, (size_t)k, c);
+        load_const(A.S, (size_t)k, c);
         bn::fr_add(x0, c);
         pow5(x0);
         u32 acc[17];
 #pragma unroll
         for (int l = 0; l < 17; l++) acc[l] = 0;
         bn::mac17(acc, x0, m00);
-        if constexpr (WIDE) {
-            u32 y[8], vv[8], ww[8];
-            lds_load(st, 1, y);
-            load_const<true>(A.V, (size_t)k * n, vv);
-            load_const<true>(A.W, (size_t)k * n, ww);
-            for (int j = 0; j < n; j++) {
-                u32 yn[8], vn[8], wn[8], p[8];
-                if (j + 1 < n) {
-                    lds_load(st, 2 + j, yn);
-                    load_const<true>(A.V, (size_t)k * n + j + 1, vn);
-                    load_const<true>(A.W, (size_t)k * n + j + 1, wn);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                bn::mac17_and_fr_mul(acc, y, vv, p, x0, ww);   // row 0: m00*x0 + sum V_kj * y_j;  column: y_j + W_kj * x0
-                bn::fr_add(y, p);
-                lds_store(st, 1 + j, y);
-#pragma unroll
-                for (int l = 0; l < 8; l++) { y[l] = yn[l]; vv[l] = vn[l]; ww[l] = wn[l]; }
-            }
-        } else {
-            for (int j = 0; j < n; j++) {
-                u32 y[8], vv[8], ww[8], p[8];
-                lds_load(st, 1 + j, y);
-                load_const<false>(A.V, (size_t)k * n + j, vv);
-                bn::mac17(acc, y, vv);               // row 0:   m00*x0 + sum V_kj * y_j
-                load_const<false>(A.W, (size_t)k * n + j, ww);
-                bn::fr_mul(p, x0, ww);               // column:  y_j + W_kj * x0
-                bn::fr_add(y, p);
-                lds_store(st, 1 + j, y);
-            }
+        for (int j = 0; j < n; j++) {
+            u32 y[8], vv[8], ww[8], p[8];
+            lds_load(st, 1 + j, y);
+            load_const(A.V, (size_t)k * n + j, vv);
+            bn::mac17(acc, y, vv);                   // row 0:   m00*x0 + sum V_kj * y_j
+            load_const(A.W, (size_t)k * n + j, ww);
+            bn::fr_mul(p, x0, ww);                   // column:  y_j + W_kj * x0
+            bn::fr_add(y, p);
+            lds_store(st, 1 + j, y);
         }
         bn::redc17(x0, acc);
     }
@@ -805,24 +629,12 @@ __device__ __noinline__ void partial_rounds(const St st, int cur, const PermArgs
 // cross terms of row i (<= 4 pairs) added to the row's stored part, one short finish = the next x0.  Per super-block, once: the n columns
 // y_j + sum_k W z_k (1 + 8 pairs and one finish each -- the costliest phase, hence every eight rounds, not four).  No 32x32 product is left
 // but the S-box's.  The tiles are ONE linear stream in consumption order, read PR_AHEAD tiles ahead.
-#ifndef BN_KR_LATE
-#define BN_KR_LATE 0
-#endif
-#ifndef BN_PR_AHEAD
-#define BN_PR_AHEAD 4
-#endif
-constexpr int PR_AHEAD = BN_PR_AHEAD;
+constexpr int PR_AHEAD = 4;                          // (deeper read-ahead measured nothing; the registers go to the rows' accumulators and operand batches)
 struct TileStream {
     bnm::gtile p;
     bnm::v4i q[PR_AHEAD];
-#ifdef BN_ABLATE_TILEADDR
-    bnm::gtile base; unsigned cnt = 0;
-#endif
     __device__ __forceinline__ void start(const bnm::v4i *tiles, int lane) {
         p = (bnm::gtile)tiles + lane;
-#ifdef BN_ABLATE_TILEADDR
-        base = p;
-#endif
 #pragma unroll
         for (int k = 0; k < PR_AHEAD; k++) q[k] = p[(size_t)k * 64];
     }
@@ -833,11 +645,7 @@ struct TileStream {
 #pragma unroll
         for (int k = 0; k + 1 < PR_AHEAD; k++) q[k] = q[k + 1];
         __builtin_amdgcn_sched_barrier(0);
-#ifdef BN_ABLATE_TILEADDR
-        q[PR_AHEAD - 1] = base[(size_t)(cnt++ & 7) * 64];
-#else
         q[PR_AHEAD - 1] = p[(size_t)PR_AHEAD * 64];
-#endif
         __builtin_amdgcn_sched_barrier(0);
         p += 64;
         return a;
@@ -857,7 +665,7 @@ __device__ __forceinline__ void partial_rounds_mfma_impl(const St st, const bnm:
     const int nb = rp / 4, nsb = (nb + 1) / 2;
     const bnm::Sh sh = bnm::sh_init();
     TileStream ts;
-    BN_SYNC();
+    __syncthreads();
     ts.start(Pt, st.lane);
     // x0 (S[0] came with the row of the layer before) stays in its LDS slot outside the rounds: the rows' pass and the columns need the registers
     // BFORM: the upper columns as the column update leaves them (operand form) stay in registers into the first rows' pass of the NEXT super-block
@@ -877,8 +685,7 @@ __device__ __forceinline__ void partial_rounds_mfma_impl(const St st, const bnm:
         // the four rows' parts on y of one block; H = 1: the second block of a super-block (two instances: no branch inside the ring's straight line)
         auto rows = [&](auto Hc) {
             constexpr int H = decltype(Hc)::value;
-            BN_SYNC();
-            BN_PRIO(BN_PRIO_MFMA);
+            __syncthreads();
             // The upper columns as operands, in at most two batches of private-memory elements fetched just before their columns (all seven kept through a
             // pass do not fit beside the accumulators: hipcc spilled them, ~700 spill stores per wave).  The SECOND batch (columns SPL.., at most
             // BN_HI_BATCH of them) is still in its registers when the second pass begins: that pass takes it first, re-reads only the first batch,
@@ -975,25 +782,15 @@ __device__ __forceinline__ void partial_rounds_mfma_impl(const St st, const bnm:
 #pragma unroll
                 for (int r = 0; r < 2; r++) bnm::carry_pair(P0[r], P1[r], pc[2 * pass + r], sh);
             }
-            BN_PRIO(0);
         };
-#ifdef BN_STAMPS
-        unsigned long long tp0 = bn_now();
-#endif
         rows(std::integral_constant<int, 0>{});          // (outside the loop over the blocks: the carried columns must not be live around its back edge)
         for (int h = 0; h < halves; h++) {
             const int b = 2 * sb + h;
             if (h == 1) {
-#ifdef BN_STAMPS
-                tp0 = bn_now();
-#endif
 #pragma unroll
                 for (int s = 0; s < 4; s++) { zbA0[s] = zb0[s]; zbA1[s] = zb1[s]; }
                 rows(std::integral_constant<int, 1>{});
             }
-#ifdef BN_STAMPS
-            { const unsigned long long t_ = bn_now(); if (st.lane == 0) atomicAdd(&g_bn_stamps[3], t_ - tp0); tp0 = t_; }
-#endif
             u32 x0[8];
             lds_load(st, 0, x0);
             // the four rounds, unrolled: round i's cross terms are i + 1 tiles (z_0 .. z_i of this block), its row's part pc[i] and its operand slot
@@ -1001,13 +798,8 @@ __device__ __forceinline__ void partial_rounds_mfma_impl(const St st, const bnm:
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 u32 k[8];
-#if !BN_KR_LATE
-                load_const<true>(KR, (size_t)(4 * b + i), k);         // (long before its use: the S-box hides it)
-#endif
+                load_const(KR, (size_t)(4 * b + i), k);               // (long before its use: the S-box hides it)
                 pow5_lazy(x0);
-#if BN_KR_LATE
-                load_const<true>(KR, (size_t)(4 * b + i), k);         // (behind the S-box, whose registers it would otherwise take: the cross terms' products hide it)
-#endif
                 bnm::b_prep(x0, zb0[i], zb1[i]);
                 bnm::v16i c0, c1;
 #pragma unroll
@@ -1025,24 +817,17 @@ __device__ __forceinline__ void partial_rounds_mfma_impl(const St st, const bnm:
                 bnm::finish_words(w, k, x0);
             }
             lds_store(st, 0, x0);
-#ifdef BN_STAMPS
-            { const unsigned long long t_ = bn_now(); if (st.lane == 0) atomicAdd(&g_bn_stamps[4], t_ - tp0); }
-#endif
         }
-#ifdef BN_STAMPS
-        unsigned long long tu0 = bn_now();
-#endif
         // the columns, once per super-block: y_j + sum over its rounds of W z -- 1 + 8 tiles and one finish each (a last super-block of one block
         // has four zero tiles for the first block's operands, which are zero: ONE form of the column, mfma_partial_tables)
         auto column = [&](u32 y[8], int j) {
             u32 k[8];
-            load_const<true>(KU, (size_t)sb * N + j, k);              // (asked for early: used after the products)
+            load_const(KU, (size_t)sb * N + j, k);                    // (asked for early: used after the products)
             bnm::v4i b0, b1;
             if constexpr (BFORM) {
 #pragma unroll
                 for (int q4 = 0; q4 < 4; q4++) { b0[q4] = (int)y[q4]; b1[q4] = (int)y[4 + q4]; }
             } else bnm::b_prep(y, b0, b1);
-            BN_PRIO(BN_PRIO_MFMA);
             bnm::v4i a = ts.next();
             bnm::v16i c0, c1;
             bnm::mfma_first(a, b0, b1, c0, c1);
@@ -1058,7 +843,6 @@ __device__ __forceinline__ void partial_rounds_mfma_impl(const St st, const bnm:
                 c0 = bnm::mfma(a, zb0[s], c0);
                 c1 = bnm::mfma(a, zb1[s], c1);
             }
-            BN_PRIO(0);
             bnm::finish_row(c0, c1, k, y, sh);
             if constexpr (BFORM) {                                    // back to the form it is kept in
                 bnm::v4i nb0, nb1;
@@ -1071,7 +855,7 @@ __device__ __forceinline__ void partial_rounds_mfma_impl(const St st, const bnm:
 #pragma unroll
             for (int s = 0; s < 4; s++) { zbA0[s] = bnm::v4i{ 0, 0, 0, 0 }; zbA1[s] = bnm::v4i{ 0, 0, 0, 0 }; }
         }
-        BN_SYNC();
+        __syncthreads();
         if (NLO) {                                                    // the lower columns: a loop (LDS takes a run-time index; the ring turns by three tiles per column)
             u32 yn[8];
             lds_load(st, 1, yn);
@@ -1093,18 +877,13 @@ __device__ __forceinline__ void partial_rounds_mfma_impl(const St st, const bnm:
 #pragma unroll
             for (int q = 0; q < NHI; q++) lds_store(st, 1 + NLO + q, yh[q]);
         }
-#ifdef BN_STAMPS
-        { const unsigned long long t_ = bn_now(); if (st.lane == 0) atomicAdd(&g_bn_stamps[5], t_ - tu0); }
-#endif
     }
 }
 template <int N>
 __device__ __noinline__ void partial_rounds_mfma_n(const St st, const bnm::v4i *Pt, const u32 *KR, const u32 *KU, int rp) { partial_rounds_mfma_impl<N>(st, Pt, KR, KU, rp); }
+// the widths 5..16 of bn_perm (N = t - 1)
 __device__ __forceinline__ void partial_rounds_mfma(const St st, const PermArgs &A) {
     switch (A.t - 1) {
-    case 1: partial_rounds_mfma_n<1>(st, A.Pt, A.KR, A.KU, A.rp); break;
-    case 2: partial_rounds_mfma_n<2>(st, A.Pt, A.KR, A.KU, A.rp); break;
-    case 3: partial_rounds_mfma_n<3>(st, A.Pt, A.KR, A.KU, A.rp); break;
     case 4: partial_rounds_mfma_n<4>(st, A.Pt, A.KR, A.KU, A.rp); break;
     case 5: partial_rounds_mfma_n<5>(st, A.Pt, A.KR, A.KU, A.rp); break;
     case 6: partial_rounds_mfma_n<6>(st, A.Pt, A.KR, A.KU, A.rp); break;
@@ -1116,8 +895,7 @@ __device__ __forceinline__ void partial_rounds_mfma(const St st, const PermArgs 
     case 12: partial_rounds_mfma_n<12>(st, A.Pt, A.KR, A.KU, A.rp); break;
     case 13: partial_rounds_mfma_n<13>(st, A.Pt, A.KR, A.KU, A.rp); break;
     case 14: partial_rounds_mfma_n<14>(st, A.Pt, A.KR, A.KU, A.rp); break;
-    case 15: partial_rounds_mfma_n<15>(st, A.Pt, A.KR, A.KU, A.rp); break;
-    default: partial_rounds_mfma_n<16>(st, A.Pt, A.KR, A.KU, A.rp); break;
+    default: partial_rounds_mfma_n<15>(st, A.Pt, A.KR, A.KU, A.rp); break;
     }
 }
 
@@ -1133,7 +911,7 @@ __device__ __noinline__ void perm_small(const St st, const PermArgs &A) {
     for (int j = 0; j < T; j++) {
         u32 c[8];
         lds_load(st, j, x[j]);
-        load_const<true>(A.Cd, (size_t)j, c);
+        load_const(A.Cd, (size_t)j, c);
         add_lazy(x[j], c);
     }
     const bnm::Sh sh = bnm::sh_init();
@@ -1152,7 +930,7 @@ __device__ __noinline__ void perm_small(const St st, const PermArgs &A) {
         }
         u32 k[T][8];
 #pragma unroll
-        for (int i = 0; i < T; i++) load_const<true>(A.SK, (size_t)r * T + i, k[i]);      // (asked for ahead of the S-boxes, which hide them)
+        for (int i = 0; i < T; i++) load_const(A.SK, (size_t)r * T + i, k[i]);      // (asked for ahead of the S-boxes, which hide them)
         pow5_lazy(x[0]);
         if (full) {
 #pragma unroll
@@ -1177,25 +955,16 @@ __device__ __noinline__ void perm_small(const St st, const PermArgs &A) {
     for (int j = 0; j < T; j++) lds_store(st, j, x[j]);
 }
 
-// permutation of the t elements in buffer `cur`; returns the buffer holding the result
-template <bool WIDE>
-__device__ __noinline__ int bn_perm(const St st, int cur, const PermArgs &A) {
+// the permutation of the t elements of the state, in place: one pipeline per width
+__device__ __noinline__ void bn_perm(const St st, const PermArgs &A) {
     const int t = A.t;
-    if (A.small_) {
+    if (t <= BN_SMALL_T) {
         if (t == 2) perm_small<2>(st, A);
         else if (t == 3) perm_small<3>(st, A);
         else perm_small<4>(st, A);
-        return cur;
+        return;
     }
-    if (A.dense) {                                   // poseidon.circom:22-44 as written (tests)
-        for (int r = 0; r < N_ROUNDS_F + A.rp; r++) {
-            const bool full = r < N_ROUNDS_F / 2 || r >= N_ROUNDS_F / 2 + A.rp;
-            add_sbox<WIDE>(st, cur, t, A.Cd, (size_t)r * t, full ? t : 1);
-            dense_mul<WIDE>(st, cur, A.M, t, 0);
-        }
-        return cur;
-    }
-    if (A.mfma && !A.nofold && t == 17) {
+    if (t == 17) {
         // The width of the arity-16 trees (config 4) in ONE function body: every phase called out of line saves and restores the callee-saved
         // half of its 256 registers in private memory (92-112 words per lane and call, ~480 KB per wave and permutation -- a third of the
         // kernel's private-memory traffic, which the chip pays for in power: tools/power_probe.py).  One copy of each phase: the partial rounds
@@ -1204,60 +973,42 @@ __device__ __noinline__ int bn_perm(const St st, int cur, const PermArgs &A) {
         // out of the partial rounds, alone afterwards); only round 0's is a pass of its own.  Two copies of the wide layer (with / without the S-box).
         // A.plain (leaf kernel): elements 1..16 went through round 0's S-box where they were absorbed, as plain integers (plain_sbox_store): only element 0 is left,
         // and the first layer reads its own copy of the tiles
-        if (A.plain) { u32 x[8], c[8]; lds_load(st, 0, x); load_const<true>(A.C8, 0, c); add_lazy(x, c); pow5_lazy(x); lds_store(st, 0, x); }
-        else BN_STAMP(0, sbox_lazy_impl(st, 17, A.C8));
+        if (A.plain) { u32 x[8], c[8]; lds_load(st, 0, x); load_const(A.C8, 0, c); add_lazy(x, c); pow5_lazy(x); lds_store(st, 0, x); }
+        else sbox_lazy_impl(st, 17, A.C8);
         for (int r = 0; r < 8; r++) {                                         // (one copy of each form of the layer)
             const bnm::v4i *Mt = r == 0 && A.plain ? A.Mt0 : A.Mt;
             const u32 *MK = r == 0 && A.plain ? A.MK0 : A.MK + (size_t)r * 17 * 8;
-            if (r == 3) BN_STAMP(1, (dense_mfma_impl<17, false, true>(st, Mt, MK, 0)))      // its rows 1..16: the partial rounds' y, in operand form
-            else if (r == 7) BN_STAMP(1, dense_mfma_impl<17>(st, Mt, MK, 0, A.nout1 ? 1 : 17))
-            else BN_STAMP(1, (dense_mfma_impl<17, true>(st, Mt, MK, 0)))
+            if (r == 3) dense_mfma_impl<17, false, true>(st, Mt, MK, 0);    // its rows 1..16: the partial rounds' y, in operand form
+            else if (r == 7) dense_mfma_impl<17>(st, Mt, MK, 0, A.nout1 ? 1 : 17);
+            else dense_mfma_impl<17, true>(st, Mt, MK, 0);
             if (r == 3) {
-                BN_STAMP(2, (partial_rounds_mfma_impl<16, true>(st, A.Pt, A.KR, A.KU, A.rp)));
-                BN_STAMP(1, (dense_mfma_impl<16, true, false, true>(st, A.Dt, A.DK, 1)));  // diag(1, Mh^RP) on the y as they are, then round 4's S-box on elements 1..16
+                partial_rounds_mfma_impl<16, true>(st, A.Pt, A.KR, A.KU, A.rp);
+                dense_mfma_impl<16, true, false, true>(st, A.Dt, A.DK, 1);  // diag(1, Mh^RP) on the y as they are, then round 4's S-box on elements 1..16
                 u32 x[8]; lds_load(st, 0, x); pow5_lazy(x); lds_store(st, 0, x);
             }
         }
-        return cur;
+        return;
     }
-    if (A.mfma) {
-        // the linear layers on the matrix cores (bn_mfma.cuh); between them the state is lazy (< 2^255), every constant but the first
-        // round's arrives with a layer's rows, and the only 32x32 products left are the S-boxes'
-        for (int r = 0; r < 4; r++) {
-            BN_STAMP(0, sbox_lazy(st, t, r == 0 || A.nofold ? A.C8 + (size_t)r * t * 8 : nullptr));
-            BN_STAMP(1, dense_mfma(st, A.Mt, A.MK + (size_t)r * t * 8, t, 0));
-        }
-        if (A.nofold) { u32 x[8], c[8]; lds_load(st, 0, x); load_const<true>(A.S, 0, c); add_lazy(x, c); lds_store(st, 0, x); }
-        if (A.rp >= 4) BN_STAMP(2, partial_rounds_mfma(st, A));
-        if (A.rp % 4 || A.rp < 4) {                  // the rounds left over, one by one on canonical values
-            canon_state(st, t);
-            partial_rounds<WIDE>(st, cur, A, A.rp & ~3);
-            if (!A.nofold) {
-                u32 x[8], c[8];
-                lds_load(st, 0, x);
-                load_const<true>(A.C8, (size_t)4 * t, c);
-                bn::fr_add(x, c);
-                lds_store(st, 0, x);
-            }
-        }
-        BN_STAMP(1, dense_mfma(st, A.Dt, A.DK, t - 1, 1));        // diag(1, Mh^RP)
-        for (int r = 4; r < 8; r++) {
-            BN_STAMP(0, sbox_lazy(st, t, A.nofold ? A.C8 + (size_t)r * t * 8 : nullptr));
-            BN_STAMP(1, dense_mfma(st, A.Mt, A.MK + (size_t)r * t * 8, t, 0, r == 7 && A.nout1 ? 1 : 17));
-        }
-        return cur;
-    }
+    // widths 5..16: between the layers the state is lazy (< 2^255), every constant but the first round's arrives with a layer's rows
     for (int r = 0; r < 4; r++) {
-        add_sbox<WIDE>(st, cur, t, A.C8, (size_t)r * t, t);
-        dense_mul<WIDE>(st, cur, A.M, t, 0);
+        sbox_lazy(st, t, r == 0 ? A.C8 : nullptr);
+        dense_mfma(st, A.Mt, A.MK + (size_t)r * t * 8, t, 0);
     }
-    partial_rounds<WIDE>(st, cur, A, 0);
-    dense_mul<WIDE>(st, cur, A.D, t - 1, 1);         // diag(1, Mh^RP)
+    partial_rounds_mfma(st, A);
+    if (A.rp % 4) {                                  // the rounds left over, one by one on canonical values
+        canon_state(st, t);
+        partial_rounds(st, A, A.rp & ~3);
+        u32 x[8], c[8];
+        lds_load(st, 0, x);
+        load_const(A.C8, (size_t)4 * t, c);
+        bn::fr_add(x, c);
+        lds_store(st, 0, x);
+    }
+    dense_mfma(st, A.Dt, A.DK, t - 1, 1);            // diag(1, Mh^RP)
     for (int r = 4; r < 8; r++) {
-        add_sbox<WIDE>(st, cur, t, A.C8, (size_t)r * t, t);
-        dense_mul<WIDE>(st, cur, A.M, t, 0);
+        sbox_lazy(st, t, nullptr);
+        dense_mfma(st, A.Mt, A.MK + (size_t)r * t * 8, t, 0, r == 7 && A.nout1 ? 1 : 17);
     }
-    return cur;
 }
 
 __device__ __forceinline__ void to_mont_store(const St st, int j, const u64 w[4]) {
@@ -1275,7 +1026,7 @@ __device__ __forceinline__ void plain_sbox_store(const St st, int j, const u64 w
     u32 x[8], c[8];
 #pragma unroll
     for (int k = 0; k < 4; k++) { x[2 * k] = (u32)w[k]; x[2 * k + 1] = (u32)(w[k] >> 32); }
-    load_const<true>(C0p, (size_t)j, c);
+    load_const(C0p, (size_t)j, c);
     bnm::add_chain8(x, c);
     pow5_lazy(x);
     lds_store(st, j, x);
@@ -1293,7 +1044,6 @@ __device__ __forceinline__ void digest_out(const St st, int j, u64 *o) {
 }
 
 // leaf digests (merklehash_bn128_worker.js:42-98): one row per lane
-template <bool WIDE>
 __global__ void __launch_bounds__(BN_THREADS) __attribute__((amdgpu_waves_per_eu(2))) bn_linear_hash_kernel(const u64 *__restrict__ in, u64 width, u64 height, int arity, int custom,
                                                                     PermArgs full, PermArgs last, u64 *__restrict__ out) {
     extern __shared__ u32 S[];
@@ -1303,10 +1053,6 @@ __global__ void __launch_bounds__(BN_THREADS) __attribute__((amdgpu_waves_per_eu
     const u64 row0 = ((u64)blockIdx.x * BN_WG_WAVES + wv) * BN_BLOCK + lane;
     const bool live = row0 < height;
     const u64 *v = in + (live ? row0 : height - 1) * width;
-    int cur = 0;
-#ifdef BN_STAMPS
-    const unsigned long long tk0 = bn_now(), tr0 = __builtin_amdgcn_s_memrealtime();
-#endif
     if (width <= 4) {                                // :45-50: up to four words taken as one 256-bit integer
         u64 w[4] = { 0, 0, 0, 0 };
         for (u64 k = 0; k < width; k++) w[k] = v[k];
@@ -1324,23 +1070,19 @@ __global__ void __launch_bounds__(BN_THREADS) __attribute__((amdgpu_waves_per_eu
                 if (plain) plain_sbox_store(st, 1 + (int)k, w, full.C0p);
                 else to_mont_store(st, 1 + (int)k, w);
             }
-            if (n == (u64)arity) cur = bn_perm<WIDE>(st, cur, full);
+            if (n == (u64)arity) bn_perm(st, full);
             else if (custom) {                       // :87-93: zero-pad the last chunk to `arity` inputs
                 const u64 z[4] = { 0, 0, 0, 0 };
                 for (u64 k = n; k < (u64)arity; k++) { if (plain) plain_sbox_store(st, 1 + (int)k, z, full.C0p); else zero_store(st, 1 + (int)k); }
-                cur = bn_perm<WIDE>(st, cur, full);
-            } else cur = bn_perm<WIDE>(st, cur, last);      // :85-86: t = nLast + 1
+                bn_perm(st, full);
+            } else bn_perm(st, last);      // :85-86: t = nLast + 1
             e += n;
         }
     }
     if (live) digest_out(st, 0, out + 4 * row0);
-#ifdef BN_STAMPS
-    if (lane == 0) { atomicAdd(&g_bn_stamps[7], bn_now() - tk0); atomicAdd(&g_bn_stamps[8], 1ull); atomicAdd(&g_bn_stamps[12], __builtin_amdgcn_s_memrealtime() - tr0); }
-#endif
 }
 
 // parents (merklehash_bn128_worker.js:104-144): out[i] = Poseidon(0; in[arity*i .. arity*i+arity-1])[0]
-template <bool WIDE>
 __global__ void __launch_bounds__(BN_THREADS) __attribute__((amdgpu_waves_per_eu(2))) bn_merkle_level_kernel(const u64 *__restrict__ in, u64 nOps, int arity, PermArgs full, u64 *__restrict__ out) {
     extern __shared__ u32 S[];
     const int lane = threadIdx.x % BN_BLOCK, wv = threadIdx.x / BN_BLOCK, tmax = arity + 1;
@@ -1356,12 +1098,11 @@ __global__ void __launch_bounds__(BN_THREADS) __attribute__((amdgpu_waves_per_eu
         for (int q = 0; q < 4; q++) { const u64 w = v[4 * k + q]; x[2 * q] = (u32)w; x[2 * q + 1] = (u32)(w >> 32); }
         lds_store(st, 1 + k, x);
     }
-    (void)bn_perm<WIDE>(st, 0, full);
+    bn_perm(st, full);
     if (live) digest_out(st, 0, out + 4 * i0);
 }
 
 // circomlibjs poseidon(inputs, initState, nOut): normal-form words in and out (transcript, verification, tests)
-template <bool WIDE>
 __global__ void __launch_bounds__(BN_THREADS) __attribute__((amdgpu_waves_per_eu(2))) bn_poseidon_kernel(const u64 *__restrict__ in, const u64 *__restrict__ init, u64 count, int nIn, int nOut,
                                                                  PermArgs full, u64 *__restrict__ out) {
     extern __shared__ u32 S[];
@@ -1378,7 +1119,7 @@ __global__ void __launch_bounds__(BN_THREADS) __attribute__((amdgpu_waves_per_eu
         for (int q = 0; q < 4; q++) w[q] = in[(i * nIn + k) * 4 + q];
         to_mont_store(st, 1 + k, w);
     }
-    (void)bn_perm<WIDE>(st, 0, full);
+    bn_perm(st, full);
     if (!live) return;
     for (int k = 0; k < nOut; k++) {                 // out of Montgomery form: multiply by 1
         u32 x[8], one[8] = { 1, 0, 0, 0, 0, 0, 0, 0 }, o[8];
@@ -1429,7 +1170,7 @@ __global__ void __launch_bounds__(64) bn_sponge_chain_kernel(const u64 *__restri
         if (l > 0) load_mont(blocks + (b * nIn + (l - 1)) * 4);
         for (int r = 0; r < nRounds; r++) {
             u32 c[8];
-            load_const<true>(A.Cd, (size_t)r * t + l, c);
+            load_const(A.Cd, (size_t)r * t + l, c);
             bn::fr_add(x, c);
             const bool full = r < N_ROUNDS_F / 2 || r >= N_ROUNDS_F / 2 + A.rp;
             if (full || l == 0) pow5(x);
@@ -1446,7 +1187,7 @@ __global__ void __launch_bounds__(64) bn_sponge_chain_kernel(const u64 *__restri
                 u32 y[8], m[8];
 #pragma unroll
                 for (int i = 0; i < 8; i++) y[i] = sh[j * 8 + i];
-                load_const<true>(A.M, (size_t)l * t + j, m);
+                load_const(A.M, (size_t)l * t + j, m);
                 bn::mac17(acc, y, m);
             }
             if (act) {
@@ -1510,30 +1251,18 @@ __global__ void bn_group_proofs_kernel(const u64 *__restrict__ elems, const u64 
     }
 }
 
-size_t lds_bytes(int tmax) {                         // the elements above BN_LDS_ELEMS live in private memory
-    static const size_t pad = getenv("PIL2GL_BN128_LDS_PAD") ? (size_t)atol(getenv("PIL2GL_BN128_LDS_PAD")) : 0;   // occupancy experiments: extra bytes per workgroup
-    return (size_t)lds_words(tmax) * 4 * BN_WG_WAVES + pad;
-}
+size_t lds_bytes(int tmax) { return (size_t)lds_words(tmax) * 4 * BN_WG_WAVES; }     // the elements above BN_LDS_ELEMS live in private memory
 
+// plainInputs: the leaf kernel's absorb S-boxes elements 1..t-1 as plain integers (width 17 only); firstOnly: the caller reads element 0 alone
 PermArgs perm_args(const Params *P, bool plainInputs = false, bool firstOnly = false) {
     PermArgs a;
-    a.C8 = P->C8; a.M = P->M; a.D = P->D; a.S = P->S; a.V = P->V; a.W = P->W; a.Cd = P->Cd; a.t = P->t; a.rp = P->rp;
-    static const bool dense = getenv("PIL2GL_BN128_DENSE") && atoi(getenv("PIL2GL_BN128_DENSE"));
-    a.dense = dense ? 1 : 0;
-    static const bool mfma = !(getenv("PIL2GL_BN128_MFMA") && !atoi(getenv("PIL2GL_BN128_MFMA")));   // =0: the layers on the vector ALU (A/B runs)
-    a.mfma = mfma ? 1 : 0;
-    static const bool nofold = getenv("PIL2GL_BN128_NOFOLD") && atoi(getenv("PIL2GL_BN128_NOFOLD"));
-    a.nofold = nofold ? 1 : 0;
+    a.C8 = P->C8; a.M = P->M; a.S = P->S; a.V = P->V; a.W = P->W; a.Cd = P->Cd; a.t = P->t; a.rp = P->rp;
     a.Mt = P->Mt; a.Dt = P->Dt; a.Pt = P->Pt; a.MK = P->MK; a.DK = P->DK; a.KR = P->KR; a.KU = P->KU;
     memcpy(a.m00, P->m00, 32);
     a.Mt0 = P->Mt0; a.MK0 = P->MK0; a.C0p = P->C0p;
     a.St = P->St; a.SK = P->SK;
-    static const bool nosmall = getenv("PIL2GL_BN128_SMALL") && !atoi(getenv("PIL2GL_BN128_SMALL"));       // =0: small widths through the blocked pipeline as well (A/B runs)
-    a.small_ = P->St && !nosmall && a.mfma && !a.nofold && !a.dense && BN_SBOX29 ? 1 : 0;
-    static const bool noplain = getenv("PIL2GL_BN128_PLAIN") && !atoi(getenv("PIL2GL_BN128_PLAIN"));   // =0: inputs converted and S-boxed by the permutation (A/B runs)
-    static const bool allrows = getenv("PIL2GL_BN128_ALLROWS") && atoi(getenv("PIL2GL_BN128_ALLROWS"));   // =1: every row of the last layer whatever the caller reads (A/B runs)
-    a.nout1 = firstOnly && !allrows ? 1 : 0;
-    a.plain = plainInputs && !noplain && a.mfma && !a.nofold && !a.dense && BN_SBOX29 && P->t == 17 ? 1 : 0;
+    a.plain = plainInputs && P->t == 17 ? 1 : 0;
+    a.nout1 = firstOnly ? 1 : 0;
     return a;
 }
 
@@ -1541,18 +1270,6 @@ template <typename K>
 int set_lds_attr(K kernel, size_t bytes) {
     HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return PIL2GL_OK;
-}
-
-// The kernel instances that request the next term's operands before multiplying the current one (WIDE) were the faster ones
-// while a wide state (t >= 10) kept its whole state in LDS and ran ONE wave per SIMD.  With the upper elements in private memory
-// (BN_LDS_ELEMS) two waves fit, the second wave covers the operand latency, and the kernels turn out to be bound by their vector
-// instruction COUNT (5.3e10 per 2^20 x 100 arity-16 commit = 0.85 of the vector issue slots of its 110 ms): the plain instances,
-// which do not rotate prefetched operands through registers, are 12 % faster (121.1 -> 106.6 ms).  PIL2GL_BN128_WIDE=1 selects
-// the prefetching instances for an A/B run.
-bool wide_state(int t) {
-    static const int force = getenv("PIL2GL_BN128_WIDE") ? atoi(getenv("PIL2GL_BN128_WIDE")) : 0;
-    (void)t;
-    return force != 0;
 }
 
 int check_arity(uint32_t arity) {
@@ -1563,14 +1280,6 @@ int check_arity(uint32_t arity) {
 }  // namespace
 
 extern "C" {
-
-#ifdef BN_STAMPS
-int pil2gl_bn128_debug_stamps(uint64_t *host16, int reset) {
-    HIP_TRY(hipMemcpyFromSymbol(host16, HIP_SYMBOL(g_bn_stamps), 128));
-    if (reset) { uint64_t z[16] = { 0 }; HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_bn_stamps), z, 128)); }
-    return PIL2GL_OK;
-}
-#endif
 
 uint64_t pil2gl_bn128_merkle_num_nodes(uint64_t height, uint32_t arity) {      // merklehash_bn128_p.js:31-45, in nodes
     if (height == 0 || arity < 2) return 0;
@@ -1596,21 +1305,12 @@ int pil2gl_bn128_linear_hash_rows_dev(const uint64_t *in, uint64_t width, uint64
     const size_t lds = lds_bytes((int)arity + 1);
     const uint64_t blocks = (height + BN_THREADS - 1) / BN_THREADS;
     if (blocks > 0x7fffffffull) return fail(PIL2GL_EINVAL, "grid too large");
-    if (wide_state((int)arity + 1)) {
-        P2_TRY(set_lds_attr(bn_linear_hash_kernel<true>, lds));
-        bn_linear_hash_kernel<true><<<(unsigned)blocks, BN_THREADS, lds, as_stream(stream)>>>(in, width, height, (int)arity, custom ? 1 : 0, perm_args(pf, true, true), perm_args(pl, false, true), out);
-    } else {
-        P2_TRY(set_lds_attr(bn_linear_hash_kernel<false>, lds));
-        bn_linear_hash_kernel<false><<<(unsigned)blocks, BN_THREADS, lds, as_stream(stream)>>>(in, width, height, (int)arity, custom ? 1 : 0, perm_args(pf, true, true), perm_args(pl, false, true), out);
-    }
+    P2_TRY(set_lds_attr(bn_linear_hash_kernel, lds));
+    bn_linear_hash_kernel<<<(unsigned)blocks, BN_THREADS, lds, as_stream(stream)>>>(in, width, height, (int)arity, custom ? 1 : 0, perm_args(pf, true, true), perm_args(pl, false, true), out);
     KERNEL_CHECK();
     return PIL2GL_OK;
 }
 
-static long wave_per_perm_max() {
-    static const long v = getenv("PIL2GL_BN128_WAVE_PER_PERM_MAX") ? atol(getenv("PIL2GL_BN128_WAVE_PER_PERM_MAX")) : 2048;
-    return v;
-}
 int pil2gl_bn128_merkelize_level_dev(const uint64_t *in, uint64_t nOps, uint32_t arity, uint64_t *out, void *stream) {
     P2_TRY(ensure_init());
     if (nOps == 0) return PIL2GL_OK;
@@ -1621,18 +1321,13 @@ int pil2gl_bn128_merkelize_level_dev(const uint64_t *in, uint64_t nOps, uint32_t
     const size_t lds = lds_bytes((int)arity + 1);
     const uint64_t blocks = (nOps + BN_THREADS - 1) / BN_THREADS;
     if (blocks > 0x7fffffffull) return fail(PIL2GL_EINVAL, "grid too large");
-    if ((long)nOps <= wave_per_perm_max()) {          // the levels near the root: a wave per parent (see pil2gl_bn128_poseidon_dev)
+    if ((long)nOps <= WAVE_PER_PERM_MAX) {           // the levels near the root: a wave per parent
         bn_sponge_chain_kernel<<<(unsigned)nOps, 64, 0, as_stream(stream)>>>(in, 1, (int)arity, nullptr, perm_args(pf), 1, 1, out);
         KERNEL_CHECK();
         return PIL2GL_OK;
     }
-    if (wide_state((int)arity + 1)) {
-        P2_TRY(set_lds_attr(bn_merkle_level_kernel<true>, lds));
-        bn_merkle_level_kernel<true><<<(unsigned)blocks, BN_THREADS, lds, as_stream(stream)>>>(in, nOps, (int)arity, perm_args(pf, false, true), out);
-    } else {
-        P2_TRY(set_lds_attr(bn_merkle_level_kernel<false>, lds));
-        bn_merkle_level_kernel<false><<<(unsigned)blocks, BN_THREADS, lds, as_stream(stream)>>>(in, nOps, (int)arity, perm_args(pf, false, true), out);
-    }
+    P2_TRY(set_lds_attr(bn_merkle_level_kernel, lds));
+    bn_merkle_level_kernel<<<(unsigned)blocks, BN_THREADS, lds, as_stream(stream)>>>(in, nOps, (int)arity, perm_args(pf, false, true), out);
     KERNEL_CHECK();
     return PIL2GL_OK;
 }
@@ -1667,20 +1362,13 @@ int pil2gl_bn128_poseidon_dev(const uint64_t *in, const uint64_t *init, uint64_t
     P2_TRY(get_params((int)nIn + 1, &pf));
     const size_t lds = lds_bytes((int)nIn + 1);
     const unsigned pblocks = (unsigned)((count + BN_THREADS - 1) / BN_THREADS);
-    // few permutations (a transcript squeeze, the levels of a handful of Merkle paths): a lane each would leave them at the
-    // latency of one wave working alone (~3 ms at t = 17); a wave each runs them in ~0.5 ms while the SIMDs outnumber them
-    if ((long)count <= wave_per_perm_max()) {
+    if ((long)count <= WAVE_PER_PERM_MAX) {          // few permutations (a transcript squeeze, the levels of a handful of Merkle paths): a wave each
         bn_sponge_chain_kernel<<<(unsigned)count, 64, 0, as_stream(stream)>>>(in, 1, (int)nIn, init, perm_args(pf), (int)nOut, 0, out);
         KERNEL_CHECK();
         return PIL2GL_OK;
     }
-    if (wide_state((int)nIn + 1)) {
-        P2_TRY(set_lds_attr(bn_poseidon_kernel<true>, lds));
-        bn_poseidon_kernel<true><<<pblocks, BN_THREADS, lds, as_stream(stream)>>>(in, init, count, (int)nIn, (int)nOut, perm_args(pf), out);
-    } else {
-        P2_TRY(set_lds_attr(bn_poseidon_kernel<false>, lds));
-        bn_poseidon_kernel<false><<<pblocks, BN_THREADS, lds, as_stream(stream)>>>(in, init, count, (int)nIn, (int)nOut, perm_args(pf), out);
-    }
+    P2_TRY(set_lds_attr(bn_poseidon_kernel, lds));
+    bn_poseidon_kernel<<<pblocks, BN_THREADS, lds, as_stream(stream)>>>(in, init, count, (int)nIn, (int)nOut, perm_args(pf), out);
     KERNEL_CHECK();
     return PIL2GL_OK;
 }

@@ -214,27 +214,6 @@ __device__ __forceinline__ void mac17(u32 acc[17], const u32 a[8], const u32 b[8
     mac17_col<0>(lo, hi, acc, a, b);
     acc[16] += (u32)lo;
 }
-// acc += a * b  and  out = c * d / 2^256 mod r  together, column by column in turn: the two chains are independent, so
-// the wait state each asm statement owes its successor (see acc_madn) is filled by the other chain's statement
-template <int K>
-__device__ __forceinline__ void mac17_fr_mul_col(u64 &lo1, u32 &hi1, u32 acc[17], const u32 a[8], const u32 b[8],
-                                                 u64 &lo2, u32 &hi2, const u32 c[8], const u32 d[8], u32 m[8], const u32 rl[8], u32 t[9]) {
-    mac17_step<K>(lo1, hi1, acc, a, b);
-    fr_mul_step<K>(lo2, hi2, c, d, m, rl, t);
-    if constexpr (K < 15) mac17_fr_mul_col<K + 1>(lo1, hi1, acc, a, b, lo2, hi2, c, d, m, rl, t);
-}
-__device__ __forceinline__ void mac17_and_fr_mul(u32 acc[17], const u32 a[8], const u32 b[8], u32 out[8], const u32 c[8], const u32 d[8]) {
-    u32 m[8], t[9], rl[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) rl[i] = r_limb(i);
-    u64 lo1 = 0, lo2 = 0; u32 hi1 = 0, hi2 = 0;
-    mac17_fr_mul_col<0>(lo1, hi1, acc, a, b, lo2, hi2, c, d, m, rl, t);
-    acc[16] += (u32)lo1;
-    t[8] = (u32)lo2;
-    cond_sub_r(t);
-#pragma unroll
-    for (int i = 0; i < 8; i++) out[i] = t[i];
-}
 // operand-scanning form (reference implementation for tests)
 __device__ __forceinline__ void mac17_os(u32 acc[17], const u32 a[8], const u32 b[8]) {
     u32 p[16];

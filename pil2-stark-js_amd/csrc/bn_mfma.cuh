@@ -36,13 +36,6 @@ typedef const v4i __attribute__((address_space(1))) *gtile;
 
 constexpr int ACC_BIAS = 1 << 30;         // 2.0f's bit pattern: an inline constant of the matrix instruction (its C operand), no register set-up per accumulator
 
-__device__ __forceinline__ v16i acc_init() {
-    v16i a;
-#pragma unroll
-    for (int k = 0; k < 16; k++) a[k] = ACC_BIAS;
-    return a;
-}
-
 // the operands of both tiles from the lane's own eight limbs
 // (the swaps go through the builtin: hipcc pads a vector write against the swap that reads it -- two wait states -- itself;
 // their inputs must therefore come from compiler-generated instructions, not straight out of an asm statement)
@@ -58,18 +51,12 @@ __device__ __forceinline__ void b_prep(const u32 x[8], v4i &b0, v4i &b1) {
 __device__ __forceinline__ v16i mfma(v4i a, v4i b, v16i c) { return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0); }
 // The FIRST products of a row's two accumulators, started at the bias as the instruction's inline constant (C = 2.0: the bit pattern 2^30) instead of
 // sixteen registers per accumulator set up first (hipcc has no way to say that: 16 v_mov_b64 per row).  One asm statement that keeps the hazards the
-// compiler keeps around the builtin: two wait states after the vector writes of the operands (the swaps of b_prep), and the 8-pass result's eleven
-// before anything but a matrix instruction accumulating on it may read it.  -DBN_ACC_INLINE=0: the builtin on acc_init() (A/B builds).
-#ifndef BN_ACC_INLINE
-#define BN_ACC_INLINE 1
-#endif
+// compiler keeps around the builtin: two wait states after the vector writes of the operands (the swaps of b_prep), and after the 8-pass results
+// twelve wait states, what hipcc puts after the builtin on gfx950 before anything but a matrix instruction accumulating on it may read it
+// (tests/test_abi_cpu.py reads hipcc's figure and checks every site of this statement against it).
 __device__ __forceinline__ void mfma_first(v4i a, v4i b0, v4i b1, v16i &c0, v16i &c1) {
-#if BN_ACC_INLINE
-    asm("s_nop 1\n\tv_mfma_i32_32x32x32_i8 %0, %2, %3, 2.0\n\tv_mfma_i32_32x32x32_i8 %1, %2, %4, 2.0\n\ts_nop 10"
+    asm("s_nop 1\n\tv_mfma_i32_32x32x32_i8 %0, %2, %3, 2.0\n\tv_mfma_i32_32x32x32_i8 %1, %2, %4, 2.0\n\ts_nop 11"
         : "=&v"(c0), "=&v"(c1) : "v"(a), "v"(b0), "v"(b1));
-#else
-    c0 = mfma(a, b0, acc_init()); c1 = mfma(a, b1, acc_init());
-#endif
 }
 
 // ---- carry chains through vcc, one statement each (the compiler's 64-bit emulation costs two to three times the instructions)

@@ -142,20 +142,55 @@ def test_no_early_clobber_overlap_in_bn128_isa(tmp_path):
     against -- `v_cndmask_b32 v8, v8, v8, vcc` in the earlier bn::cond_sub_r when its result was copied back over its input inside a loop: both
     outcomes of the select are then the difference, silently wrong for every value below r.  bn::cond_sub_r works in place since round 6
     (no select is left in it); this scan stays as a backstop for any select whose two sources are the same register, in the ISA of the
-    files that carry such asm statements (no GPU needed: hipcc cross-compiles)."""
+    files that carry such asm statements (no GPU needed: hipcc cross-compiles).
+    The same ISA carries bnm::mfma_first's two hand-written v_mfma_i32_32x32x32_i8 (accumulators started at 2.0), which the compiler cannot
+    see to pad: the s_nop after each pair must give at least the wait states hipcc itself puts between that instruction and a vector
+    read of its result -- read here from a one-instruction kernel compiled by the same hipcc, not written down."""
     import re
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
+    probe = tmp_path / "one_mfma.hip"
+    probe.write_text("#include <hip/hip_runtime.h>\n"
+                     "typedef int v4i __attribute__((ext_vector_type(4)));\n"
+                     "typedef int v16i __attribute__((ext_vector_type(16)));\n"
+                     "__global__ void one_mfma(const v4i *a, const v4i *b, int *out) {\n"
+                     "    const v4i x = a[threadIdx.x], y = b[threadIdx.x];\n"
+                     "    const v16i c = __builtin_amdgcn_mfma_i32_32x32x32_i8(x, y, v16i{}, 0, 0, 0);\n"
+                     "    out[threadIdx.x] = c[0] ^ 0x55;\n"
+                     "}\n")
+    subprocess.check_call([hipcc, "-O3", "--offload-arch=gfx950", "-S", "--cuda-device-only", str(probe), "-o", str(tmp_path / "one_mfma.s")],
+                          stderr=subprocess.DEVNULL)
+    lines = [l.split(";")[0].strip() for l in (tmp_path / "one_mfma.s").read_text().splitlines()]
+    lines = [l for l in lines if l and not l.startswith(".") and not l.endswith(":")]
+    at = next(i for i, l in enumerate(lines) if l.startswith("v_mfma_i32_32x32x32_i8 "))
+    lo, hi = map(int, re.match(r"v_mfma_i32_32x32x32_i8 v\[(\d+):(\d+)\]", lines[at]).groups())
+    need = 0                                         # wait states from the result's write to its first reader
+    for l in lines[at + 1:]:
+        nop = re.match(r"s_nop (\d+)$", l)
+        regs = [(int(m[0] or m[2]), int(m[1] or m[2])) for m in re.findall(r"\bv(?:\[(\d+):(\d+)\]|(\d+)\b)", l)]
+        if nop:
+            need += int(nop.group(1)) + 1
+        elif any(a <= hi and b >= lo for a, b in regs):
+            break
+        else:
+            need += 1
+    assert need >= 1, "no pad found after the probe's matrix instruction"
     pkg = os.path.join(ROOT, "pil2-stark-js_amd")
     for src in ("bn128.hip",):
         out = tmp_path / (src + ".s")
         subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "-ffp-contract=off", "-I" + os.path.join(pkg, "build"),
                                "-S", "--cuda-device-only", os.path.join(pkg, "csrc", src), "-o", str(out)], stderr=subprocess.DEVNULL)
-        bad = re.findall(r"v_cndmask_b32(?:_e32|_e64)? v\d+, (v\d+), \1, (?:vcc|s\[\d+:\d+\])", out.read_text())     # ANY select whose two sources are one register
+        isa = out.read_text()
+        bad = re.findall(r"v_cndmask_b32(?:_e32|_e64)? v\d+, (v\d+), \1, (?:vcc|s\[\d+:\d+\])", isa)     # ANY select whose two sources are one register
         assert not bad, "%s: a select between a register and itself (%d sites)" % (src, len(bad))
+        pads = re.findall(r"v_mfma_i32_32x32x32_i8 [^\n]*, 2\.0\n\s*v_mfma_i32_32x32x32_i8 [^\n]*, 2\.0\n\s*s_nop (\d+)", isa)
+        n_inline = len(re.findall(r"v_mfma_i32_32x32x32_i8 [^\n]*, 2\.0\n", isa))
+        assert pads and 2 * len(pads) == n_inline, "%s: %d matrix instructions on the inline bias, %d padded pairs" % (src, n_inline, len(pads))
+        short = [int(n) for n in pads if int(n) + 1 < need]
+        assert not short, "%s: %d pairs padded with s_nop %d, hipcc pads %d wait states" % (src, len(short), min(short), need)
 
 
 def test_bn254_sbox_columns_model_and_generated_file():

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; L=$R/pil2-stark-js_amd/lib_ab; O=$R/gpurun_out/bn_ab; mkdir 
 cd $R
 VARIANTS="${VARIANTS:?names of lib_ab builds}"
 {
-for v in $VARIANTS; do echo "== check $v"; PIL2GL_LIB=$L/libpil2gl_$v.so timeout 300 python3 tools/check_bn_mfma.py 2>&1 | tail -n 1; done
+for v in $VARIANTS; do echo "== check $v"; PIL2GL_LIB=$L/libpil2gl_$v.so timeout 600 python3 -m pytest -q tests/test_gpu_bn128.py -k every_width 2>&1 | tail -n 1; done
 for v in $VARIANTS $VARIANTS; do
   echo "== bench $v"
   for i in 1 2; do PIL2GL_LIB=$L/libpil2gl_$v.so python3 tools/bench_bn128.py 20 100 16 | tail -n 1; done
