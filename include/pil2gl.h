@@ -316,6 +316,9 @@ int pil2gl_debug_compact_program(const glx_program *prog, glx_op *outOps, uint32
 /* host-only: run the optimiser, generate the straight-line kernel source of the program and compile it with hiprtc
  * (the path long programs take at run time); reports the code object size and the number of fused Horner terms. */
 int pil2gl_debug_jit_compile(const glx_program *prog, const glx_ctx *ctx, uint64_t *codeBytes, uint32_t *fusedOps);
+/* host-only: the program as pil2gl_eval_program_dev optimises it for this context, Horner fusion included: outInfo[0] = temporary
+ * slots (what the choice between the compiled kernel and the two interpreter forms reads), [1] = ops, [2] = fused Horner terms */
+int pil2gl_debug_plan_program(const glx_program *prog, const glx_ctx *ctx, uint32_t *outInfo);
 /* the two hand-written Goldilocks products on n pairs of arbitrary u64 operands (host pointers): x[i] = a*b by the exact form
  * the transform kernels use (gl_field.cuh mul_lazy_x), pb[i] = a*b by the flagged form of the S-boxes (mul_lazy_b), both canonical;
  * flag[i] != 0 where the flagged form asks to be recomputed (its last subtraction borrowed: probability ~2^-32 on random operands) */

@@ -590,6 +590,17 @@ extern "C" int pil2gl_debug_jit_compile(const glx_program *prog, const glx_ctx *
     return PIL2GL_OK;
 }
 
+// test hook (host only): the program as pil2gl_eval_program_dev optimises it for this context (Horner fusion included, unless
+// PIL2GL_EXPR_NOFUSE is set) -- the slot and op counts its choice of kernel reads
+extern "C" int pil2gl_debug_plan_program(const glx_program *prog, const glx_ctx *ctx, uint32_t *outInfo /* [3]: slots, ops, fused */) {
+    if (!prog || !ctx || !outInfo) return fail(PIL2GL_EINVAL, "null argument");
+    std::vector<IOp> ops; std::vector<u32> pool; u32 n = 0;
+    P2_TRY(compile_program(prog, ctx, ops, n, pool, getenv("PIL2GL_EXPR_NOFUSE") == nullptr));
+    u32 f = 0; for (const IOp &o : ops) f += o.op == GLX_LZ_MAD;
+    outInfo[0] = n; outInfo[1] = (uint32_t)ops.size(); outInfo[2] = f;
+    return PIL2GL_OK;
+}
+
 extern "C" int pil2gl_eval_program_dev(const glx_program *prog, const glx_ctx *ctx, void *stream) {
     P2_TRY(ensure_init());
     if (!prog || !ctx || (prog->nOps && !prog->ops)) return fail(PIL2GL_EINVAL, "null program");

@@ -104,6 +104,61 @@ def test_tmp_compaction_preserves_program(oracle):
             assert (a == b).all(), n_ops
 
 
+def test_evaluator_routing_of_the_reference_programs(oracle):
+    """why each evaluator test takes the kernel it takes: (ops as encoded, slots after compaction) of the programs the GPU tests run,
+    from pil2gl_debug_compact_program, and the slots the evaluator's own choice reads (pil2gl_debug_plan_program: Horner fusion
+    included, which moves some counts by one).  The compiled kernel takes programs of at most 200 slots: the two long programs the
+    reference wrote are over that cap and run in the global-memory interpreter; the FRI program of fibonacci_air(k) (2k + 2 slots)
+    crosses it between k = 99 and k = 100; 40 slots (k = 19) is the largest that keeps its temporaries in LDS.  Fails when
+    compaction or fusion changes, so that the routing the GPU tests assert is revisited."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bn128_oracle as bn
+    import evalpath as ep
+    from conftest import rand_field
+    from pil2gl import stark
+    from test_gpu_parity import _random_program
+    import test_ref_oplist
+    import test_reference_proof
+    W = {"x_ext": 3, "f_ext": 3, "Zi_ext#0": 1, "const_ext": 64, "cm1_ext": 1024, "cm2_ext": 6, "cm3_ext": 64, "cm4_ext": 64,
+         "q_ext": 3, "xDivXSubXi_ext": 6}
+
+    def counts(ops, n_tmp, secs, scalars):
+        slots, _ = ep.compact(ops, n_tmp)
+        return len(ops), slots, ep.plan(ops, n_tmp, [W[s] for s in secs], scalars)[0]
+    # verifyEvals verifierCode + its store
+    inp = test_ref_oplist._inputs(4)
+    ctx = {"pilInfo": {}, "publics": inp["publics"], "evals": inp["evals"], "challengesFlat": inp["challengesFlat"], "challenges": []}
+    assert counts(*stark.encode_code(test_ref_oplist._load(), "ext", ctx)) == (3258, 330, 331)
+    # test/final qVerifier (muladd expanded) and queryVerifier
+    info, vinfo, _, z = test_reference_proof._final()
+    tr = test_reference_proof._final_transcript(bn.TranscriptBN128(16), z, info)
+    ctx = {"pilInfo": info, "publics": [int(v) for v in z["publics"]], "evals": [[int(v) for v in e] for e in z["evals"]], "challenges": tr["challenges"]}
+    assert counts(*stark.encode_code(vinfo["qVerifier"]["code"], "ext", ctx)) == (2697, 309, 310)
+    assert counts(*stark.encode_code(vinfo["queryVerifier"]["code"], "ext", ctx)) == (317, 37, 36)
+    # fibonacci_air(k): constraint program (expressionsCode[0]) and FRI program ([1])
+    fib = {}
+    for k in (19, 20, 50, 99, 100, 150, 400):
+        pr = [ep.fibonacci_program(k, e, 8, 0, seed=k) for e in (0, 1)]
+        fib[k] = [counts(p["ops"], p["n_tmp"], p["names"], p["scalars"]) for p in pr]
+    assert [fib[k][0] for k in (50, 150, 400)] == [(661, 7, 6), (1961, 7, 6), (5211, 7, 7)]
+    for k in fib:
+        assert fib[k][1] == (12 * k + 12, 2 * k + 2, 2 * k + 2), k
+    cap = ep.SLOT_CAP
+    assert fib[99][1][2] <= cap < fib[100][1][2]
+    assert max(fib[k][0][2] for k in (50, 150, 400)) <= cap < min(331, 310)
+    assert (ep.interp_form(fib[19][1][2]), ep.interp_form(fib[20][1][2])) == (("lds", 1 << 20), ("global", 1 << 19))
+    # _random_program(300) of test_expression_evaluator_interpreter_and_jit_agree (the table counts its ops after compaction: 340)
+    rng = np.random.default_rng(1300)
+    widths = [5, 9, 1, 3]
+    for w in widths:
+        rand_field(rng, (1 << 10, w))
+    scalars = rand_field(rng, 40)
+    ops, n_tmp = _random_program(rng, 300, widths, scalars.size, 3)
+    assert ep.compact(ops, n_tmp) == (77, 340)
+    assert ep.plan(ops, n_tmp, widths, scalars)[0] == 77
+
+
 def test_constraint_program_compiles_with_hiprtc_and_fuses_horner():
     """the run-time compiled evaluator path: optimiser + source generator + hiprtc, on the synthetic AIR's cExp (no GPU)"""
     import time

@@ -83,15 +83,19 @@ def test_proof_from_bytecode_equals_proof_from_oplists_cpu(oracle, tmp_path, air
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("jit", ["0", "1"])
-def test_proof_from_bytecode_on_gpu(oracle, tmp_path, jit, monkeypatch):
+def test_proof_from_bytecode_on_gpu(oracle, tmp_path, jit, monkeypatch, capfd):
     monkeypatch.setenv("PIL2GL_EXPR_JIT", jit)
+    import evalpath
     from pil2gl import stark
     ss = {"nBits": 10, "nBitsExt": 13, "nQueries": 8, "verificationHashType": "GL", "steps": [{"nBits": 13}, {"nBits": 9}, {"nBits": 4}]}
     info, exprs, vinfo = stark.fibonacci_air(20, ss)
     cm, consts, publics = stark.fibonacci_trace(10, 20)
     gpu = stark.GpuBackend(0)
     setup = stark.build_const_tree(gpu, consts, info)
-    want = stark.stark_gen(gpu, gpu.from_host(cm), setup, info, exprs, publics)
     exprs2, _ = _through_bytecode(info, exprs, tmp_path)
-    got = stark.stark_gen(gpu, gpu.from_host(cm), setup, info, exprs2, publics)
+    box = {}
+    for name, ex in (("want", exprs), ("got", exprs2)):         # "1": the compiled kernel ran in each proof; "0": only the interpreter did
+        launches = evalpath.jit_launches(capfd, monkeypatch, lambda: box.update({name: stark.stark_gen(gpu, gpu.from_host(cm), setup, info, ex, publics)}))
+        assert len(launches) >= 1 if jit == "1" else launches == [], (name, launches)
+    want, got = box["want"], box["got"]
     assert got["proof"] == want["proof"]

@@ -901,7 +901,7 @@ def test_expression_evaluator(gl, oracle, n_ops, prime_shift):
 
 
 @pytest.mark.parametrize("jit", ["0", "1"])
-def test_expression_evaluator_minimal_programs_of_the_first_kernels_miscompile(gl, oracle, jit, monkeypatch):
+def test_expression_evaluator_minimal_programs_of_the_first_kernels_miscompile(gl, oracle, jit, monkeypatch, capfd):
     """The first evaluator kernel (commit 8435cfa) returned components 0 and 1 of ext values wrong whenever a program
     contained a COPY: hipcc -O1..-O3 dropped r[0] = a[0], r[1] = a[1] of the `default:` arm of its switch over the op code
     (reproduced and bisected with the old source in round 2).  These are the smallest programs that
@@ -911,6 +911,7 @@ def test_expression_evaluator_minimal_programs_of_the_first_kernels_miscompile(g
     import ctypes as C
     from pil2gl import _lib
     from gl_oracle import TMP, SEC, SCALAR
+    import evalpath as ep
     monkeypatch.setenv("PIL2GL_EXPR_JIT", jit)
     rng = np.random.default_rng(4)
     n_bits, widths = 4, [5, 9, 1, 3]
@@ -938,7 +939,9 @@ def test_expression_evaluator_minimal_programs_of_the_first_kernels_miscompile(g
         for i, t in enumerate(dsecs):
             csecs[i].ptr = t.data_ptr(); csecs[i].width = widths[i]
         ctx = _lib.GlxCtx(n_bits, 0, 4, scalars.size, csecs, scalars.ctypes.data_as(_lib.u64p))
-        _lib.call("pil2gl_eval_program_dev", C.byref(prog), C.byref(ctx), None)
+        path, info = ep.eval_path(capfd, monkeypatch, lambda: _lib.call("pil2gl_eval_program_dev", C.byref(prog), C.byref(ctx), None),
+                                  ops, n_tmp, widths, scalars, n_bits, 0)
+        assert path == ("jit" if jit == "1" else "interp"), (path, info, ops)
         torch.cuda.synchronize()
         assert (dsecs[3].cpu().numpy().view(np.uint64).reshape(ref[3].shape) == ref[3]).all(), ops
 
@@ -1259,12 +1262,13 @@ def test_rows_and_cols_dot_ext(gl, oracle, monkeypatch, mode):
 
 
 @pytest.mark.parametrize("jit", ["0", "1", "wide0", "wide"])
-def test_expression_evaluator_interpreter_and_jit_agree(gl, oracle, jit, monkeypatch):
+def test_expression_evaluator_interpreter_and_jit_agree(gl, oracle, jit, monkeypatch, capfd):
     """the same random programs through the interpreter (PIL2GL_EXPR_JIT=0) and the hiprtc-compiled kernel (=1), on narrow sections and
     on WIDE ones (20 and 34 columns, row offsets -2..2 and -8..8: interpreter "wide0", compiled "wide")"""
     import torch
     import ctypes as C
     from pil2gl import _lib
+    import evalpath as ep
     monkeypatch.setenv("PIL2GL_EXPR_JIT", "0" if jit in ("0", "wide0") else "1")
     for n_ops, prime_shift in [(40, 0), (300, 2)]:
         rng = np.random.default_rng(1000 + n_ops)
@@ -1281,13 +1285,15 @@ def test_expression_evaluator_interpreter_and_jit_agree(gl, oracle, jit, monkeyp
         for i, s in enumerate(dsecs):
             csecs[i].ptr = s.data_ptr(); csecs[i].width = widths[i]
         ctx = _lib.GlxCtx(n_bits, prime_shift, len(dsecs), scalars.size, csecs, scalars.ctypes.data_as(_lib.u64p))
-        _lib.call("pil2gl_eval_program_dev", C.byref(prog), C.byref(ctx), None)
+        path, info = ep.eval_path(capfd, monkeypatch, lambda: _lib.call("pil2gl_eval_program_dev", C.byref(prog), C.byref(ctx), None),
+                                  ops, n_tmp, widths, scalars, n_bits, prime_shift)
+        assert path == ("interp" if jit in ("0", "wide0") else "jit"), (path, info, n_ops)
         torch.cuda.synchronize()
         assert (dsecs[-1].cpu().numpy().view(np.uint64).reshape(ref_secs[-1].shape) == ref_secs[-1]).all()
 
 
 @pytest.mark.parametrize("mulcall", ["0", "1"])
-def test_compiled_evaluator_lazy_products_reach_their_readers_non_canonical(gl, oracle, mulcall, monkeypatch):
+def test_compiled_evaluator_lazy_products_reach_their_readers_non_canonical(gl, oracle, mulcall, monkeypatch, capfd):
     """the run-time compiled kernel keeps a product lazy when only products and fused multiply-accumulates read it.  Random
     operands give a representative >= p once in 2^32; here (2^32+1)(2^32-1) = 2^64-1 does in every row where the columns hold
     those two, so the readers -- a product, a dim-3 scaling, a Horner chain fused into lazy multiply-accumulates -- all see it"""
@@ -1295,6 +1301,7 @@ def test_compiled_evaluator_lazy_products_reach_their_readers_non_canonical(gl, 
     import ctypes as C
     from pil2gl import _lib
     from gl_oracle import TMP, SEC, SCALAR
+    import evalpath as ep
     monkeypatch.setenv("PIL2GL_EXPR_JIT", "1")
     monkeypatch.setenv("PIL2GL_EXPR_MULCALL", mulcall)
     rng = np.random.default_rng(77)
@@ -1327,11 +1334,69 @@ def test_compiled_evaluator_lazy_products_reach_their_readers_non_canonical(gl, 
     for i, x in enumerate(dsecs):
         csecs[i].ptr = x.data_ptr(); csecs[i].width = widths[i]
     ctx = _lib.GlxCtx(n_bits, 0, len(dsecs), scalars.size, csecs, scalars.ctypes.data_as(_lib.u64p))
-    _lib.call("pil2gl_eval_program_dev", C.byref(prog), C.byref(ctx), None)
+    path, info = ep.eval_path(capfd, monkeypatch, lambda: _lib.call("pil2gl_eval_program_dev", C.byref(prog), C.byref(ctx), None),
+                              ops, n_tmp, widths, scalars, n_bits, 0)
+    assert path == "jit", info
     torch.cuda.synchronize()
     got = dsecs[-1].cpu().numpy().view(np.uint64).reshape(ref[-1].shape)
     assert (got < np.uint64(P)).all()
     assert (got == ref[-1]).all()
+
+
+# ------------------------------------------------------------------ the evaluator's kernels at circuit size (tests/evalpath.py)
+def _default_routing(monkeypatch):
+    for v in ("PIL2GL_EXPR_JIT", "PIL2GL_EXPR_MULCALL", "PIL2GL_EXPR_LAZYMUL", "PIL2GL_EXPR_NOFUSE"):
+        monkeypatch.delenv(v, raising=False)
+
+
+@pytest.mark.parametrize("k,n_ops", [(50, 661), (150, 1961), (400, 5211)])
+def test_compiled_evaluator_constraint_programs_at_circuit_size(gl, oracle, capfd, monkeypatch, k, n_ops):
+    """the constraint program of fibonacci_air(k) -- up to eight times the 666 ops of the bench AIR, Horner chains fused into hundreds of
+    lazy multiply-accumulates, products called and lazy -- at 2^16 rows, primeShift 3, routed as the product routes it: it must take the
+    compiled kernel and agree with the oracle on every row (edge rows included) and with the big-integer interpreter on three"""
+    import evalpath as ep
+    _default_routing(monkeypatch)
+    pr = ep.fibonacci_program(k, 0, 16, 3, seed=k)
+    assert len(pr["ops"]) == n_ops
+    path, info = ep.check_at_size(oracle, capfd, monkeypatch, pr)
+    print("fibonacci_air(%d) constraint program:" % k, path, info)
+    assert path == "jit", info
+
+
+@pytest.mark.parametrize("k,slots,path", [(99, 200, "jit"), (100, 202, "interp")])
+def test_evaluator_slot_cap_boundary(gl, oracle, capfd, monkeypatch, k, slots, path):
+    """the FRI program of fibonacci_air(k) needs 2k + 2 slots: 200 at k = 99, the largest program the compiled kernel takes, 202 at
+    k = 100, the smallest it refuses (global-memory interpreter).  Both bit-exact at 2^16 rows in the default environment.
+    The 200-slot kernel is the largest the product compiles: on the MI355X it reported regs 472, scratch 0 (one wave per SIMD, no
+    spill to private memory) and took 38 s to build with hiprtc (LAB_NOTES.md 13)."""
+    import evalpath as ep
+    _default_routing(monkeypatch)
+    pr = ep.fibonacci_program(k, 1, 16, 0, seed=k)
+    assert len(pr["ops"]) == 12 * k + 12
+    assert ep.plan(pr["ops"], pr["n_tmp"], [s.shape[1] for s in pr["secs"]], pr["scalars"], 16, 0)[0] == slots
+    got, info = ep.check_at_size(oracle, capfd, monkeypatch, pr)
+    print("fibonacci_air(%d) FRI program, %d slots:" % (k, slots), got, info)
+    assert got == path, info
+    if path == "interp":
+        assert info["form"] == "global", info
+
+
+@pytest.mark.parametrize("k,n_bits,form", [(19, 21, "lds"), (20, 20, "global")])
+def test_evaluator_interpreter_loops_past_one_grid(gl, oracle, capfd, monkeypatch, k, n_bits, form):
+    """the interpreter's persistent lanes: the FRI program of fibonacci_air(19) has 40 slots (LDS form, 64 threads, 16384 blocks:
+    2^20 lanes) and runs at 2^21 rows; that of fibonacci_air(20) has 42 (global form, 2048 x 256 = 2^19 lanes) and runs at 2^20 rows.
+    Either way the row loop turns twice.  Bit-exact against the oracle on 4096-row windows at the start, around the lane count
+    and at the end; three rows against the big-integer interpreter"""
+    import evalpath as ep
+    _default_routing(monkeypatch)
+    monkeypatch.setenv("PIL2GL_EXPR_JIT", "0")
+    pr = ep.fibonacci_program(k, 1, n_bits, 0, seed=k)
+    slots = ep.plan(pr["ops"], pr["n_tmp"], [s.shape[1] for s in pr["secs"]], pr["scalars"], n_bits, 0)[0]
+    assert slots == 2 * k + 2
+    f, lanes = ep.interp_form(slots)
+    assert (f, 2 * lanes) == (form, 1 << n_bits)
+    path, info = ep.check_at_size(oracle, capfd, monkeypatch, pr, wins=ep.windows(1 << n_bits, lanes))
+    assert (path, info["form"], info["lanes"]) == ("interp", form, lanes), info
 
 
 def test_clock_probe_reports_a_plausible_shader_clock(gl):

@@ -190,3 +190,35 @@ def test_js_and_python_encoders_agree_on_muladd_and_subproof_values():
     assert (got["nOps"], got["nTmp"], got["secs"]) == (len(ops), n_tmp, secs)
     assert [int(v) for v in got["scalars"]] == [int(v) for v in scalars]
     assert bytes.fromhex(got["ops"]) == want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_bits", [16, 20])
+def test_reference_oplist_at_large_domains(oracle, capfd, monkeypatch, n_bits):
+    """the 3 258-op program at circuit-size domains, routed as the product routes it (no PIL2GL_EXPR_* set): its 330 slots exceed the
+    compiled kernel's cap of 200, so the global-memory interpreter runs it -- at 2^20 rows for two turns of its persistent lanes.
+    Bit-exact against the oracle on every row (2^16) or on 4096-row windows at the start, around the lane count and at the end (2^20);
+    the first, middle and last rows against the big-integer interpreter.  If a later change moves this program onto the compiled
+    kernel, the routing assertion fails on purpose: that change updates it."""
+    import evalpath as ep
+    from pil2gl import stark
+    for v in ("PIL2GL_EXPR_JIT", "PIL2GL_EXPR_MULCALL", "PIL2GL_EXPR_LAZYMUL", "PIL2GL_EXPR_NOFUSE"):
+        monkeypatch.delenv(v, raising=False)
+    code, N = _load(), 1 << n_bits
+    inp = _inputs(4, seed=14)
+    inp["x"] = ep.fill_section(np.random.default_rng(15), N, 3, 0)
+    ctx = {"pilInfo": {}, "publics": inp["publics"], "evals": inp["evals"], "challengesFlat": inp["challengesFlat"], "challenges": []}
+    ops, n_tmp, secs, scalars = stark.encode_code(code, "ext", ctx)
+    assert secs == ["x_ext", "f_ext"] and len(ops) == 3258
+    arrays = [inp["x"], np.zeros((N, 3), np.uint64)]
+    box = {}
+    path, info = ep.eval_path(capfd, monkeypatch, lambda: box.update(got=ep.run_device(ops, n_tmp, arrays, scalars, n_bits, 0, 1)),
+                              ops, n_tmp, [3, 3], scalars, n_bits, 0)
+    over_the_slot_cap = info.get("slots", 0) > ep.SLOT_CAP
+    assert (path, info.get("form"), over_the_slot_cap) == ("interp", "global", True), (path, info)
+    got = box["got"].reshape(N, 3)
+    wins = ep.windows(N, info["lanes"]) if N > info["lanes"] else None
+    want = ep.run_oracle(oracle, ops, n_tmp, arrays, scalars, n_bits, 0, 1, wins)
+    rows = np.concatenate([np.arange(b, e) for b, e in wins]) if wins else np.arange(N)
+    assert (got[rows] == want[rows]).all()
+    assert (got[[0, N // 2, N - 1]] == _bigint_rows(code, inp, [0, N // 2, N - 1])).all()

@@ -370,3 +370,47 @@ def test_final_proof_full_device_verification():
     bad_tr = dict(tr, challenges=[list(c) for c in tr["challenges"]]); bad_tr["challenges"][3] = [[1, 2, 3]]
     ok, _ = stark.stark_verify(be, proof, publics, root_c, info, None, vinfo, challenges=bad_tr, legacy_transcript_queries=True)
     assert not ok
+
+
+@pytest.mark.gpu
+def test_final_qverifier_program_at_a_large_domain(oracle, capfd, monkeypatch):
+    """the BN128 reference proof's qVerifier (2 568 ops, its 129 `muladd`s expanded: 2 697, plus a store of its value) with the proof's
+    own evaluations, publics and challenges and a random dim-1 Zi_ext#0 column, at 2^16 rows in the default routing: its 309 slots
+    exceed the compiled kernel's cap of 200, so the global-memory interpreter runs it (if a later change moves it onto the compiled
+    kernel, this assertion fails on purpose).  Bit-exact against the oracle on every row; at three rows the value equals
+    stark.execute_code run with that row's Zi"""
+    import bn128_oracle as bn
+    import evalpath as ep
+    from pil2gl import stark
+    for v in ("PIL2GL_EXPR_JIT", "PIL2GL_EXPR_MULCALL", "PIL2GL_EXPR_LAZYMUL", "PIL2GL_EXPR_NOFUSE"):
+        monkeypatch.delenv(v, raising=False)
+    info, vinfo, _, z = _final()
+    tr = _final_transcript(bn.TranscriptBN128(16), z, info)
+    code = vinfo["qVerifier"]["code"]
+    last = code[-1]["dest"]
+    stored = code + [{"op": "copy", "dest": {"type": "f", "dim": 3}, "src": [{"type": "tmp", "id": last["id"], "dim": last["dim"]}]}]
+    evals, publics = [[int(v) for v in e] for e in z["evals"]], [int(v) for v in z["publics"]]
+    ctx = {"pilInfo": info, "publics": publics, "evals": evals, "challenges": tr["challenges"]}
+    ops, n_tmp, secs, scalars = stark.encode_code(stored, "ext", ctx)
+    assert secs == ["Zi_ext#0", "f_ext"] and len(ops) == 2697 + 1
+    n_bits = 16
+    N = 1 << n_bits
+    zi = ep.fill_section(np.random.default_rng(16), N, 1, 0)
+    arrays = [zi, np.zeros((N, 3), np.uint64)]
+    box = {}
+    path, pinfo = ep.eval_path(capfd, monkeypatch, lambda: box.update(got=ep.run_device(ops, n_tmp, arrays, scalars, n_bits, 0, 1)),
+                               ops, n_tmp, [1, 3], scalars, n_bits, 0)
+    over_the_slot_cap = pinfo.get("slots", 0) > ep.SLOT_CAP
+    assert (path, pinfo.get("form"), over_the_slot_cap) == ("interp", "global", True), (path, pinfo)
+    got = box["got"].reshape(N, 3)
+    assert (got == ep.run_oracle(oracle, ops, n_tmp, arrays, scalars, n_bits, 0, 1)).all()
+    for row in (0, N // 2, N - 1):
+        def resolve(r, row=row):
+            ty = r["type"]
+            if ty == "eval": return evals[r["id"]]
+            if ty == "challenge": return tr["challenges"][r["stage"] - 1][r["stageId"]]
+            if ty == "public": return publics[r["id"]]
+            if ty == "number": return int(r["value"]) % P
+            if ty == "Zi": return int(zi[row, 0])
+            raise ValueError(ty)
+        assert [int(v) for v in got[row]] == stark.execute_code(code, resolve), row

@@ -51,6 +51,55 @@ def test_prove_and_verify_on_oracle_backend(oracle, n_bits, n_pairs, steps):
     assert not ok2
 
 
+def _gen_code_recursive(expr, dest):
+    """stark.gen_code as it was written first (recursive post-order, codegen.js:75-95): the iterative form must emit the same op-lists"""
+    code, n = [], [0]
+
+    def rec(e):
+        if e.op == "leaf":
+            return dict(e.leaf)
+        ra, rb = rec(e.a), rec(e.b)
+        r = {"type": "tmp", "id": n[0], "dim": max(ra.get("dim", 1), rb.get("dim", 1))}
+        n[0] += 1
+        code.append({"op": e.op, "dest": r, "src": [ra, rb]})
+        return r
+    r = rec(expr)
+    if dest is None:
+        return {"tmpUsed": n[0], "code": code}
+    if r["type"] != "tmp":
+        code.append({"op": "copy", "dest": dict(dest), "src": [r]})
+    else:
+        code[-1]["dest"] = dict(dest)
+        n[0] -= 1
+    return {"tmpUsed": n[0], "code": code}
+
+
+def test_gen_code_builds_wide_airs_and_keeps_the_op_lists(monkeypatch):
+    """stark.gen_code walks the expression tree with an explicit stack: fibonacci_air(400) builds (the recursive form stopped between
+    k = 220 and 249 at Python's recursion limit), and for k = 1, 10, 50, in every variant of the AIR, the op-lists and their encoding
+    are those of the recursive form"""
+    from pil2gl import stark
+    ss = {"nBits": 10, "nBitsExt": 13, "nQueries": 8, "steps": [{"nBits": 13}, {"nBits": 9}]}
+    info, exprs, vinfo = stark.fibonacci_air(400, ss)
+    assert [len(e["code"]["code"]) for e in exprs["expressionsCode"]] == [5211, 12 * 400 + 12] and len(vinfo["qVerifier"]["code"]) > 5000
+
+    def lists(k, kw):
+        info, exprs, vinfo = stark.fibonacci_air(k, ss, **kw)
+        rng = np.random.default_rng(k)
+        r3 = lambda: [int(v) for v in rng.integers(0, P, 3, dtype=np.uint64)]
+        ctx = {"pilInfo": info, "publics": [1, 2, 3], "challenges": [[], [r3()], [r3()], [r3(), r3()]], "evals": [r3() for _ in info["evMap"]]}
+        codes = [e["code"] for e in exprs["expressionsCode"]] + exprs["imPolsCode"] + [vinfo["qVerifier"]] + exprs["constraints"]
+        enc = [stark.encode_code(c["code"], "ext", ctx) for c in codes[:2]]
+        return codes, [(ops, n_tmp, secs, scalars.tolist()) for ops, n_tmp, secs, scalars in enc]
+    for k in (1, 10, 50):
+        for kw in ({}, {"prev_row": True}, {"im_pols": True}, {"boundaries": True}, {"public_hints": True}):
+            new = lists(k, kw)
+            monkeypatch.setattr(stark, "gen_code", _gen_code_recursive)
+            old = lists(k, kw)
+            monkeypatch.undo()
+            assert new == old, (k, kw)
+
+
 def test_fri_opening_order_is_the_references_key_order():
     """friPolinomial.js:42-50 folds the openings in the order of Object.keys(friExps): node itself is asked for that order"""
     import json, shutil, subprocess
@@ -193,13 +242,17 @@ def test_gpu_previous_row_opening_proof_is_identical_to_oracle_proof(oracle, n_b
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_bits,n_pairs,steps,split,jit", [(8, 2, [11, 7, 3], False, "0"), (10, 1, [11, 7, 3], False, "0"), (12, 5, [15, 11, 7, 3], False, "1"), (10, 4, [13, 9, 4], True, "1"), (13, 40, [16, 11, 6], False, "0")])
-def test_gpu_proof_is_bit_identical_to_oracle_proof(oracle, n_bits, n_pairs, steps, split, jit, monkeypatch):
+def test_gpu_proof_is_bit_identical_to_oracle_proof(oracle, n_bits, n_pairs, steps, split, jit, monkeypatch, capfd):
     monkeypatch.setenv("PIL2GL_EXPR_JIT", jit)
+    import evalpath
     import stark_ref
     stark, info, exprs, vinfo, cm, consts, publics = _setup(n_bits, n_pairs, steps)
     gpu = stark.GpuBackend(0, split)
     s_gpu = stark.build_const_tree(gpu, consts, info)
-    r_gpu = stark.stark_gen(gpu, gpu.from_host(cm), s_gpu, info, exprs, publics)
+    box = {}
+    launches = evalpath.jit_launches(capfd, monkeypatch, lambda: box.update(r=stark.stark_gen(gpu, gpu.from_host(cm), s_gpu, info, exprs, publics)))
+    assert len(launches) >= 1 if jit == "1" else launches == [], launches      # "1": the compiled kernel ran; "0": only the interpreter did
+    r_gpu = box["r"]
     cpu = stark_ref.OracleBackend(split)
     s_cpu = stark.build_const_tree(cpu, consts, info)
     r_cpu = stark.stark_gen(cpu, cpu.from_host(cm), s_cpu, info, exprs, publics)
