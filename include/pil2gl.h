@@ -24,13 +24,17 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins.
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; land_rows with a null hostFirstBad.
+ *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
+ *    stream (or order it against the stream given) and return.
  *    The following _dev calls BLOCK until their work on the stream has finished, because they hand a result to the host or
  *    stage host-side tables in a scratch slot the next call reuses:
  *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi / cols_dot_ext /
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
  *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], build_lev (small host tables),
- *      h1h2, synth_fibonacci, group_proof / group_proofs and bn128_group_proof (openings copied to host memory).
+ *      h1h2, synth_fibonacci, group_proof / group_proofs and bn128_group_proof (openings copied to host memory),
+ *      land_rows with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
+ *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
  *    A whole config-3 proof keeps the GPU busy 99.3 % of its wall time with these.
  *  - Every function returns 0 on success, a negative PIL2GL_E* code otherwise;
  *    pil2gl_last_error() describes the failure (the reference throws Error /
@@ -67,6 +71,51 @@ int pil2gl_dev_zero(uint64_t *p, uint64_t nWords, void *stream);
 int pil2gl_dev_upload(uint64_t *dst, const uint64_t *hostSrc, uint64_t nWords);
 int pil2gl_dev_download(uint64_t *hostDst, const uint64_t *src, uint64_t nWords);
 int pil2gl_sync(void *stream);
+
+/* ---- the host <-> HBM leg: pinned memory, asynchronous copies, file loaders (csrc/hostleg.hip) --------------------
+ * How a witness or a constant tree reaches HBM when it starts in host memory or in a file, as the reference's does
+ * (src/witness/witnessCalculator.js:145-214, src/prover/prover.js:24, merklehash_p.js:228-278).
+ * pinned host memory (hipHostMalloc) for callers without a HIP allocator, and pinning of memory the caller owns */
+int pil2gl_host_alloc(uint64_t nWords, uint64_t **out);
+int pil2gl_host_free(uint64_t *p);
+int pil2gl_host_register(uint64_t *p, uint64_t nWords);
+int pil2gl_host_unregister(uint64_t *p);
+/* Copies on a library-owned COPY stream (created non-blocking on first use, so it overlaps with the NULL stream; destroyed by
+ * pil2gl_shutdown).  hostSrc / hostDst must be pinned or registered over the whole range, else PIL2GL_EINVAL: the copy never
+ * degrades to a synchronous one.  (The runtime tells no extent of registered memory: the first and the last byte of the range are
+ * what is checked; a range must lie in ONE pinned or registered block.)  These only enqueue.  Order them against compute streams with the two event calls:
+ *   pil2gl_copy_after(s)   copies enqueued from now on start after the work now on s   (s may still be reading the target)
+ *   pil2gl_copy_fence(s)   work enqueued on s from now on starts after the copies enqueued so far
+ *   pil2gl_copy_sync()     the host waits for the copy stream
+ * Double-buffered use: copy_after(s); dev_upload_async(next, ...); <proof k on s>; copy_fence(s); <proof k + 1 on s reads next>. */
+int pil2gl_dev_upload_async(uint64_t *dst, const uint64_t *hostSrc, uint64_t nWords);
+int pil2gl_dev_download_async(uint64_t *hostDst, const uint64_t *src, uint64_t nWords);
+int pil2gl_copy_after(void *stream);
+int pil2gl_copy_fence(void *stream);
+int pil2gl_copy_sync(void);
+/* The landing pass of words that came from outside, one read of each: *hostFirstBad = the smallest flat index into src of a
+ * word that is not canonical (>= p), UINT64_MAX when all are -- a file is the one input nobody has checked, and every kernel
+ * relies on canonical inputs.  The data is landed either way; the caller decides.  dstCols > srcCols: row r of dst = the srcCols
+ * words of row r of src, then dstCols - srcCols zeros (writeToBigBuffer(buff, nCols), witnessCalculator.js:198-214); src and dst
+ * must not overlap.  dstCols == srcCols: a copy, or with src == dst the check alone.  dstCols < srcCols: PIL2GL_EINVAL.
+ * Pointers need 8-byte alignment only.  With hostFirstBad the call blocks until the answer is on the host; with NULL it only
+ * enqueues and nothing is checked. */
+int pil2gl_land_rows_dev(const uint64_t *src, uint64_t srcCols, uint64_t *dst, uint64_t dstCols, uint64_t nRows,
+                         uint64_t *hostFirstBad, void *stream);
+/* file <-> HBM through two pinned chunks of chunkWords (0 = 2^25 words = 256 MB, the reference's MaxBuffSize) on the copy
+ * stream: one chunk is read from (written to) the file while the other is in flight.  Both block until done.
+ * Both work on the COPY stream and order themselves against nothing else: when a compute stream may still write src (save)
+ * or still read or write dst (load) -- most _dev calls only enqueue -- call pil2gl_copy_after(thatStream) first, or
+ * synchronise it.  (The JS and Python wrappers do: DevBuffer.toFile / fromFile, io.save_pols_dev / load_pols_dev.)
+ * dev_load_file: nRows x srcCols words from byteOffset land as nRows x dstCols (rules of land_rows; widening needs
+ * chunkWords >= srcCols); hostFirstBad as above, flat index into the file's words, NULL = no check.  A file shorter than
+ * byteOffset + 8*nRows*srcCols bytes fails with PIL2GL_EINVAL naming file, found and expected size before anything is copied.
+ * dev_save_file: the file is created if missing, cut at byteOffset, and nWords words are appended there (a header first,
+ * then each section at its offset in ascending order, writes a `.consttree`).  A byteOffset beyond the file's end is
+ * PIL2GL_EINVAL (nothing is padded).  When a copy or a write fails midway the file is left holding the chunks written so far. */
+int pil2gl_dev_load_file(const char *fileName, uint64_t byteOffset, uint64_t nRows, uint64_t srcCols,
+                         uint64_t *dst, uint64_t dstCols, uint64_t chunkWords, uint64_t *hostFirstBad);
+int pil2gl_dev_save_file(const char *fileName, uint64_t byteOffset, const uint64_t *src, uint64_t nWords, uint64_t chunkWords);
 
 /* ---- NTT / LDE: src/helpers/fft/fft_p.js -------------------------------- */
 /* interpolate(buffSrc,nPols,nBits,buffDst,nBitsExt)  fft_p.js:187-297:

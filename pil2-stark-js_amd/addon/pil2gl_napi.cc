@@ -9,6 +9,7 @@
 #include <string.h>
 #include <string>
 #include <vector>
+#include <unordered_map>
 #include "pil2gl.h"
 
 #define NAPI_CALL(env, call)                                                         \
@@ -58,6 +59,7 @@ static napi_value mk_undefined(napi_env env) { napi_value v; napi_get_undefined(
 static napi_value mk_bigint(napi_env env, uint64_t x) { napi_value v; napi_create_bigint_uint64(env, x, &v); return v; }
 
 #define FN(name) static napi_value name(napi_env env, napi_callback_info info)
+#define DP(i) ((uint64_t *)(uintptr_t)a.u64(i))      // a device address carried as BigInt
 
 FN(Init) { Args a(env, info); int dev = a.is_nullish(0) ? 0 : (int)a.u64(0); if (!a.ok) return nullptr; P2(env, pil2gl_init(dev)); return mk_undefined(env); }
 FN(Shutdown) { pil2gl_shutdown(); return mk_undefined(env); }
@@ -84,6 +86,77 @@ FN(DevDownload) {    // (BigUint64Array, devPtr, offsetWords)
     P2(env, pil2gl_dev_download(h, (uint64_t *)(uintptr_t)p + off, n)); return mk_undefined(env);
 }
 FN(Sync) { P2(env, pil2gl_sync(nullptr)); return mk_undefined(env); }
+
+// ---- the host <-> HBM leg (csrc/hostleg.hip): pinned memory, asynchronous copies on the library's copy stream, file loaders ----
+// hostAlloc(nWords) -> BigUint64Array over pinned memory (an external ArrayBuffer); the memory goes back when the ArrayBuffer is
+// collected, or at hostFree(array) -- after which the array must not be touched (js/native.js PinnedBuffer drops it).
+// Liveness is kept PER ALLOCATION: each ArrayBuffer's finalizer carries its own record.  An address comes back from the allocator
+// once it is freed, so the finalizer of an array freed by hand must never take the address's word for it.
+struct PinnedRec { uint64_t *p; bool freed; };
+static std::unordered_map<void *, PinnedRec *> &pinned_live() { static std::unordered_map<void *, PinnedRec *> m; return m; }     // address -> its LIVE allocation
+static void pinned_finalize(napi_env, void *, void *hint) {
+    PinnedRec *rec = (PinnedRec *)hint;
+    if (!rec->freed) { pinned_live().erase(rec->p); (void)pil2gl_host_free(rec->p); }
+    delete rec;
+}
+FN(HostAlloc) {
+    Args a(env, info); uint64_t n = a.u64(0); if (!a.ok) return nullptr;
+    uint64_t *p; P2(env, pil2gl_host_alloc(n, &p));
+    PinnedRec *rec = new PinnedRec{ p, false };
+    napi_value ab, ta;
+    if (napi_create_external_arraybuffer(env, p, n * 8, pinned_finalize, rec, &ab) != napi_ok) {
+        delete rec; (void)pil2gl_host_free(p); napi_throw_error(env, nullptr, "pinned memory cannot be wrapped in an ArrayBuffer of this length"); return nullptr; }
+    pinned_live()[p] = rec;                 // from here on the ArrayBuffer's finalizer owns rec
+    if (napi_create_typedarray(env, napi_biguint64_array, n, ab, 0, &ta) != napi_ok) { napi_throw_error(env, nullptr, "pinned memory cannot be wrapped in a BigUint64Array of this length"); return nullptr; }
+    return ta;
+}
+FN(HostFree) {       // (BigUint64Array from hostAlloc)
+    Args a(env, info); uint64_t *h = a.arr(0, 0); if (!a.ok) return nullptr;
+    auto &m = pinned_live(); auto it = m.find(h);
+    if (it == m.end()) { napi_throw_error(env, nullptr, "hostFree: not a live hostAlloc array"); return nullptr; }
+    it->second->freed = true;               // its finalizer will find nothing left to do, whoever holds the address by then
+    m.erase(it);
+    P2(env, pil2gl_host_free(h)); return mk_undefined(env);
+}
+FN(HostRegister) { Args a(env, info); uint64_t n = 0; uint64_t *h = a.arr(0, 1, &n); if (!a.ok) return nullptr; P2(env, pil2gl_host_register(h, n)); return mk_undefined(env); }
+FN(HostUnregister) { Args a(env, info); uint64_t *h = a.arr(0, 1); if (!a.ok) return nullptr; P2(env, pil2gl_host_unregister(h)); return mk_undefined(env); }
+FN(DevUploadAsync) {   // (devPtr, offsetWords, pinned BigUint64Array): enqueues on the copy stream; keep the array alive until copySync / a fenced stream is done
+    Args a(env, info); uint64_t p = a.u64(0), off = a.u64(1), n = 0; uint64_t *h = a.arr(2, 0, &n); if (!a.ok) return nullptr;
+    P2(env, pil2gl_dev_upload_async((uint64_t *)(uintptr_t)p + off, h, n)); return mk_undefined(env);
+}
+FN(DevDownloadAsync) { // (pinned BigUint64Array, devPtr, offsetWords)
+    Args a(env, info); uint64_t n = 0; uint64_t *h = a.arr(0, 0, &n); uint64_t p = a.u64(1), off = a.u64(2); if (!a.ok) return nullptr;
+    P2(env, pil2gl_dev_download_async(h, (uint64_t *)(uintptr_t)p + off, n)); return mk_undefined(env);
+}
+FN(CopyAfter) { Args a(env, info); P2(env, pil2gl_copy_after(a.stream(0))); return mk_undefined(env); }
+FN(CopyFence) { Args a(env, info); P2(env, pil2gl_copy_fence(a.stream(0))); return mk_undefined(env); }
+FN(CopySync) { P2(env, pil2gl_copy_sync()); return mk_undefined(env); }
+FN(LandRowsDev) {      // (dSrc, srcCols, dDst, dstCols, nRows, check[, stream]) -> first non-canonical index as BigInt (2^64-1: none), undefined without check
+    Args a(env, info); uint64_t *s = DP(0); uint64_t sc = a.u64(1); uint64_t *d = DP(2); uint64_t dc = a.u64(3), nRows = a.u64(4); bool check = a.u64(5) != 0; if (!a.ok) return nullptr;
+    uint64_t bad = ~0ull;
+    P2(env, pil2gl_land_rows_dev(s, sc, d, dc, nRows, check ? &bad : nullptr, a.stream(6)));
+    return check ? mk_bigint(env, bad) : mk_undefined(env);
+}
+static bool get_string(Args &a, size_t i, std::string &out) {
+    size_t len = 0;
+    if (i >= a.argc || napi_get_value_string_utf8(a.env, a.argv[i], nullptr, 0, &len) != napi_ok) return a.fail("expected a file name");
+    out.resize(len + 1);
+    napi_get_value_string_utf8(a.env, a.argv[i], &out[0], len + 1, &len);
+    out.resize(len);
+    return true;
+}
+FN(DevLoadFile) {      // (fileName, byteOffset, nRows, srcCols, dDst, dstCols, chunkWords, check) -> first non-canonical index as BigInt / undefined
+    Args a(env, info); std::string name; get_string(a, 0, name);
+    uint64_t off = a.u64(1), nRows = a.u64(2), sc = a.u64(3); uint64_t *d = DP(4); uint64_t dc = a.u64(5), chunk = a.u64(6); bool check = a.u64(7) != 0; if (!a.ok) return nullptr;
+    uint64_t bad = ~0ull;
+    P2(env, pil2gl_dev_load_file(name.c_str(), off, nRows, sc, d, dc, chunk, check ? &bad : nullptr));
+    return check ? mk_bigint(env, bad) : mk_undefined(env);
+}
+FN(DevSaveFile) {      // (fileName, byteOffset, dSrc, nWords, chunkWords)
+    Args a(env, info); std::string name; get_string(a, 0, name);
+    uint64_t off = a.u64(1); uint64_t *s = DP(2); uint64_t n = a.u64(3), chunk = a.u64(4); if (!a.ok) return nullptr;
+    P2(env, pil2gl_dev_save_file(name.c_str(), off, s, n, chunk)); return mk_undefined(env);
+}
 
 // ---- NTT ----
 FN(Interpolate) {    // (src, nPols, nBits, dst, nBitsExt)  fft_p.js:187
@@ -168,7 +241,6 @@ FN(RootsFromGroupProofs) {  // (packed BigUint64Array(n*(width+4*levels)), width
 }
 
 // ---- STARK step helpers and stage-2 hints (device pointers; js/stark_gen_helpers.js and js/polutils.js stage host buffers) ----
-#define DP(i) ((uint64_t *)(uintptr_t)a.u64(i))
 FN(BuildXDev) {        // (nBits, shift, dX)  stark_gen_helpers.js:111-116,139-144
     Args a(env, info); uint32_t nBits = (uint32_t)a.u64(0); uint64_t shift = a.u64(1); uint64_t *x = DP(2); if (!a.ok) return nullptr;
     P2(env, pil2gl_build_x_dev(nBits, shift, x, a.stream(3))); return mk_undefined(env);
@@ -386,6 +458,9 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     struct { const char *name; napi_callback fn; } fns[] = {
         { "init", Init }, { "shutdown", Shutdown }, { "deviceInfo", DeviceInfo },
         { "devAlloc", DevAlloc }, { "devFree", DevFree }, { "devZero", DevZero }, { "devUpload", DevUpload }, { "devDownload", DevDownload }, { "sync", Sync },
+        { "hostAlloc", HostAlloc }, { "hostFree", HostFree }, { "hostRegister", HostRegister }, { "hostUnregister", HostUnregister },
+        { "devUploadAsync", DevUploadAsync }, { "devDownloadAsync", DevDownloadAsync }, { "copyAfter", CopyAfter }, { "copyFence", CopyFence }, { "copySync", CopySync },
+        { "landRowsDev", LandRowsDev }, { "devLoadFile", DevLoadFile }, { "devSaveFile", DevSaveFile },
         { "interpolate", Interpolate }, { "fft", Fft }, { "ifft", Ifft },
         { "interpolateDev", InterpolateDev }, { "fftDev", FftDev }, { "ifftDev", IfftDev },
         { "poseidon", Poseidon }, { "linearHashRows", LinearHashRows }, { "merkelizeLevel", MerkelizeLevel },

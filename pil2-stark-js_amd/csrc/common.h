@@ -24,6 +24,7 @@ int  hip_fail(hipError_t e, const char *what);      // -> PIL2GL_EHIP
 int ensure_init();                                   // pil2gl_init(current device) on first use
 std::recursive_mutex &runtime_lock();                // guards the process-global runtime state (tables, scratch, kernel cache)
 void jit_clear();                                    // unloads the run-time compiled expression kernels (expr.hip)
+void hostleg_shutdown();                             // destroys the copy stream, its events and the pinned file chunks (hostleg.hip)
 
 // host-side Goldilocks (table construction and scalar parameters only) ---------
 u64 h_mul(u64 a, u64 b);

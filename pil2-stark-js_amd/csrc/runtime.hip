@@ -145,6 +145,7 @@ void pil2gl_shutdown(void) {
     if (!g_ready) return;
     (void)hipDeviceSynchronize();
     jit_clear();                                          // compiled expression kernels belong to the device being left
+    hostleg_shutdown();                                   // so do the copy stream, its events and the pinned chunks
     for (u32 i = 0; i < N_SCRATCH; i++) { if (g_scratch[i]) (void)hipFree(g_scratch[i]); g_scratch[i] = nullptr; g_scratch_words[i] = 0; }
     if (g_tables_mem) (void)hipFree(g_tables_mem);
     g_tables_mem = nullptr;

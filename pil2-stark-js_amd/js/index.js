@@ -3,6 +3,10 @@
 module.exports = {
     native: require("./native.js").addon,
     DevBuffer: require("./native.js").DevBuffer,
+    PinnedBuffer: require("./native.js").PinnedBuffer,
+    copyAfter: require("./native.js").copyAfter,
+    copyFence: require("./native.js").copyFence,
+    copySync: require("./native.js").copySync,
     fft_p: require("./fft_p.js"),
     fft_worker: require("./fft_worker.js"),
     buildMerkleHash: require("./merklehash_p.js"),

@@ -5,7 +5,7 @@
 // The reference obtains its permutation from circomlibjs / wasmcurves; here it is libpil2gl's (csrc/bn128.hip).
 "use strict";
 const fs = require("fs");
-const { addon, isFlat, upload } = require("./native.js");
+const { addon, isFlat, DevBuffer, upload } = require("./native.js");
 
 const R = 21888242871839275222246405745257275088548364400416034343698204186575808495617n;
 const M64 = 0xFFFFFFFFFFFFFFFFn;
@@ -201,17 +201,30 @@ class MerkleHash {
         await fd.close();
     }
 
-    async readFromFile(fileName) {
+    // merklehash_bn128_p.js:265-285.  {device: true}: elements and nodes are DevBuffers streamed from the file into HBM by the library
+    // (the elements checked canonical; the nodes are Montgomery-form BN254 words, which no Goldilocks bound applies to).  Without it, one
+    // BigUint64Array each as before, or a chunked host container when the elements are larger than a typed array can be.
+    async readFromFile(fileName, opts = {}) {
+        const { hostContainer, readInto } = require("./merklehash_p.js");
         const fd = await fs.promises.open(fileName, "r");
-        const header = new BigUint64Array(2);
-        await fd.read(new Uint8Array(header.buffer), 0, 16, 0);
-        const tree = { width: Number(header[0]), height: Number(header[1]) };
-        tree.elements = new BigUint64Array(tree.width * tree.height);
-        tree.nodes = new BigUint64Array(this._getNNodes(tree.height) * 4);
-        await fd.read(new Uint8Array(tree.elements.buffer), 0, tree.elements.byteLength, 16);
-        await fd.read(new Uint8Array(tree.nodes.buffer), 0, tree.nodes.byteLength, 16 + tree.elements.byteLength);
-        await fd.close();
-        return tree;
+        try {
+            const header = new BigUint64Array(2);
+            await fd.read(new Uint8Array(header.buffer), 0, 16, 0);
+            const tree = { width: Number(header[0]), height: Number(header[1]) };
+            const nEl = tree.width * tree.height, nNodes = this._getNNodes(tree.height) * 4;
+            if (opts.device) {
+                tree.elements = DevBuffer.fromFile(fileName, tree.height, tree.width, { byteOffset: 16, check: opts.check, chunkWords: opts.chunkWords });
+                tree.nodes = DevBuffer.fromFile(fileName, 1, nNodes, { byteOffset: 16 + 8 * nEl, check: false, chunkWords: opts.chunkWords });
+                return tree;
+            }
+            tree.elements = hostContainer(nEl, opts.chunkWords);
+            tree.nodes = new BigUint64Array(nNodes);
+            const pos = await readInto(fd, tree.elements, 16);
+            await readInto(fd, tree.nodes, pos);
+            return tree;
+        } finally {
+            await fd.close();
+        }
     }
 }
 

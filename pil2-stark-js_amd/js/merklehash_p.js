@@ -4,7 +4,7 @@
 // the caller's buffer (:47), nodes is a new BigUint64Array laid out exactly as the reference's (:28-42, :87-103).
 "use strict";
 const fs = require("fs");
-const { addon, isFlat, isDev, DevBuffer, upload } = require("./native.js");
+const { addon, isFlat, isDev, DevBuffer, ChunkedBuffer, upload } = require("./native.js");
 const getPoseidon = require("./poseidon.js");
 
 module.exports = async function buildMerkleHash(splitLinearHash = false) {
@@ -149,24 +149,48 @@ class MerkleHash {
         await fd.close();
     }
 
-    async readFromFile(fileName) {                  // merklehash_p.js:248-278 (elements returned as one BigUint64Array)
+    // merklehash_p.js:248-278.  Default: elements and nodes as one BigUint64Array each; when one of them is larger than a typed
+    // array can be, a chunked host container with BigBuffer's surface (the reference returns a BigBuffer there).
+    // {device: true}: both are DevBuffers, streamed from the file into HBM by the library (pil2gl_dev_load_file: two pinned chunks,
+    // every word checked canonical); {check: false} skips the check, {chunkWords} sets the chunk size.
+    async readFromFile(fileName, opts = {}) {
         const fd = await fs.promises.open(fileName, "r");
-        const header = new BigUint64Array(2);
-        await fd.read(new Uint8Array(header.buffer), 0, 16, 0);
-        const tree = { width: Number(header[0]), height: Number(header[1]) };
-        tree.elements = new BigUint64Array(tree.width * tree.height);
-        tree.nodes = new BigUint64Array(this._getNNodes(tree.height * 4));
-        let pos = 16;
-        for (const buff of [tree.elements, tree.nodes]) {
-            const b8 = new Uint8Array(buff.buffer, buff.byteOffset, buff.byteLength);
-            const CH = 1 << 28;
-            for (let o = 0; o < b8.length; o += CH) await fd.read(b8, o, Math.min(CH, b8.length - o), pos + o);
-            pos += b8.length;
+        try {
+            const header = new BigUint64Array(2);
+            await fd.read(new Uint8Array(header.buffer), 0, 16, 0);
+            const tree = { width: Number(header[0]), height: Number(header[1]) };
+            const nEl = tree.width * tree.height, nNodes = this._getNNodes(tree.height * 4);
+            if (opts.device) {
+                tree.elements = DevBuffer.fromFile(fileName, tree.height, tree.width, { byteOffset: 16, check: opts.check, chunkWords: opts.chunkWords });
+                tree.nodes = DevBuffer.fromFile(fileName, 1, nNodes, { byteOffset: 16 + 8 * nEl, check: opts.check, chunkWords: opts.chunkWords });
+                return tree;
+            }
+            tree.elements = hostContainer(nEl, opts.chunkWords);
+            tree.nodes = hostContainer(nNodes, opts.chunkWords);
+            let pos = 16;
+            for (const buff of [tree.elements, tree.nodes]) pos = await readInto(fd, buff, pos);
+            return tree;
+        } finally {
+            await fd.close();
         }
-        await fd.close();
-        return tree;
     }
 }
+// one typed array when the words fit one (what readFromFile has always returned), else chunks of the largest size Node allows
+function hostContainer(nWords, chunkWords) {
+    const limit = Math.floor(require("buffer").kMaxLength / 8);
+    return (nWords <= limit && !chunkWords) ? new BigUint64Array(nWords) : new ChunkedBuffer(nWords, chunkWords);
+}
+async function readInto(fd, buff, pos) {
+    for (const arr of (isFlat(buff) ? [buff] : buff.chunks)) {
+        const b8 = new Uint8Array(arr.buffer, arr.byteOffset, arr.byteLength);
+        const CH = 1 << 28;
+        for (let o = 0; o < b8.length; o += CH) await fd.read(b8, o, Math.min(CH, b8.length - o), pos + o);
+        pos += b8.length;
+    }
+    return pos;
+}
+module.exports.hostContainer = hostContainer;
+module.exports.readInto = readInto;
 module.exports.MerkleHash = MerkleHash;
 // The reference's own operator granularity (merklehash_worker.js:37-117, the functions its worker pool runs on slices of the rows):
 //   linearHash(buffIn, width, st_i, st_n, splitLinearHash) -> BigUint64Array(height * 4)      one digest per row of buffIn

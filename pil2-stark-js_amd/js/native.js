@@ -24,8 +24,86 @@ class DevBuffer {
     zero() { addon.devZero(this.ptr, 0, this.length); }
     toHost() { return this.slice(0, this.length); }
     free() { if (this.owned && this.ptr !== null) { addon.devFree(this.ptr); this.ptr = null; } }
+
+    // ---- the asynchronous leg: copies on the library's copy stream, ordered against the NULL stream by copyAfter / copyFence ----
+    // uploadAsync / downloadAsync only enqueue; the PinnedBuffer must stay alive and untouched until copySync() or until work
+    // fenced behind the copy has finished.
+    uploadAsync(pinned, offWords = 0) { eachPinned(pinned, (arr, o) => addon.devUploadAsync(this.ptr, offWords + o, arr)); return this; }
+    downloadAsync(pinned, offWords = 0) { eachPinned(pinned, (arr, o) => addon.devDownloadAsync(arr, this.ptr, offWords + o)); return this; }
+    // a new device buffer filled from pinned memory; {after: true} first orders the copy after the work now on the NULL stream
+    static fromHost(pinned, opts = {}) { const d = new DevBuffer(pinned.length); if (opts.after) addon.copyAfter(); return d.uploadAsync(pinned); }
+    // nRows x nCols words of a `.commit` / `.const` file (raw little-endian u64, witnessCalculator.js:145-196) streamed into HBM through
+    // the library's two pinned chunks; {dstCols} pads every row with zeros (writeToBigBuffer(buff, nCols), :198-214), {check} (default
+    // true) throws when a word is not a canonical field element.  Blocks until the data is in HBM.
+    static fromFile(fileName, nRows, nCols, opts = {}) {
+        const dstCols = opts.dstCols === undefined ? nCols : opts.dstCols, check = opts.check === undefined ? true : !!opts.check;
+        const d = new DevBuffer(nRows * dstCols);
+        try {
+            const bad = addon.devLoadFile(fileName, opts.byteOffset || 0, nRows, nCols, d.ptr, dstCols, opts.chunkWords || 0, check);
+            if (check && bad !== NO_BAD) {
+                const r = bad / BigInt(nCols), c = bad % BigInt(nCols);
+                throw new Error(fileName + ": word " + bad + " is " + d.getElement(Number(r) * dstCols + Number(c)) + ", not a canonical field element");
+            }
+        } catch (e) { d.free(); throw e; }
+        return d;
+    }
+    // the words are read on the copy stream: first behind whatever the NULL stream (or opts.stream) still has to write into them
+    toFile(fileName, opts = {}) { addon.copyAfter(opts.stream); addon.devSaveFile(fileName, opts.byteOffset || 0, this.ptr, this.length, opts.chunkWords || 0); }
 }
 function isDev(b) { return b instanceof DevBuffer; }
+const NO_BAD = 0xFFFFFFFFFFFFFFFFn;
+function copyAfter(stream) { addon.copyAfter(stream); }      // copies enqueued from now on start after the work now on the stream (default: NULL)
+function copyFence(stream) { addon.copyFence(stream); }      // work enqueued on the stream from now on starts after the copies so far
+function copySync() { addon.copySync(); }
+
+// A chunked host container with pilcom BigBuffer's surface {length, getElement, setElement, slice(a,b) -> BigUint64Array, set(arr, off)}:
+// one typed array cannot hold more than require("buffer").kMaxLength bytes (2 GB on Node 12), a witness has 13 GB.
+// chunkWords defaults to the largest power of two the running Node allows.
+function maxChunkWords() { return 2 ** Math.floor(Math.log2(Math.floor(require("buffer").kMaxLength / 8))); }
+class ChunkedBuffer {
+    constructor(nWords, chunkWords, allocChunk = (n) => new BigUint64Array(n)) {
+        this.length = nWords;
+        this.chunkWords = chunkWords || maxChunkWords();
+        this.chunks = [];
+        for (let o = 0; o < nWords; o += this.chunkWords) this.chunks.push(allocChunk(Math.min(this.chunkWords, nWords - o)));
+    }
+    getElement(i) { return this.chunks[Math.floor(i / this.chunkWords)][i % this.chunkWords]; }
+    setElement(i, v) { this.chunks[Math.floor(i / this.chunkWords)][i % this.chunkWords] = BigInt(v); }
+    slice(a = 0, b = this.length) {
+        if (a < 0) a += this.length;
+        if (b < 0) b += this.length;
+        b = Math.min(b, this.length);
+        const out = new BigUint64Array(Math.max(0, b - a));
+        for (let o = a; o < b;) {
+            const k = Math.floor(o / this.chunkWords), at = o % this.chunkWords, m = Math.min(b - o, this.chunkWords - at);
+            out.set(this.chunks[k].subarray(at, at + m), o - a);
+            o += m;
+        }
+        return out;
+    }
+    set(arr, off = 0) {
+        if (!isFlat(arr)) arr = arr.slice(0, arr.length);
+        if (off + arr.length > this.length) throw new RangeError("offset is out of bounds");
+        for (let o = 0; o < arr.length;) {
+            const k = Math.floor((off + o) / this.chunkWords), at = (off + o) % this.chunkWords, m = Math.min(arr.length - o, this.chunkWords - at);
+            this.chunks[k].set(arr.subarray(o, o + m), at);
+            o += m;
+        }
+    }
+}
+// The same container on pinned host memory (pil2gl_host_alloc): what uploadAsync / downloadAsync / DevBuffer.fromHost take.  The
+// reference's writeToBigBuffer(buff) (witnessCalculator.js:198-214) fills it unchanged -- it only calls setElement.  The memory goes
+// back when the chunks are collected, or at free().  Zero-filled like a BigBuffer unless zero = false (pinned memory comes as it is; a
+// buffer that is about to be overwritten whole need not pay for the pass).
+class PinnedBuffer extends ChunkedBuffer {
+    constructor(nWords, chunkWords, zero = true) { super(nWords, chunkWords, (n) => { const c = addon.hostAlloc(n); if (zero) c.fill(0n); return c; }); }
+    free() { for (const c of this.chunks) addon.hostFree(c); this.chunks = []; this.length = 0; }
+}
+function eachPinned(pinned, fn) {
+    if (!(pinned instanceof PinnedBuffer)) throw new TypeError("expected a PinnedBuffer (pageable containers go through upload() / DevBuffer.from())");
+    let o = 0;
+    for (const c of pinned.chunks) { fn(c, o); o += c.length; }
+}
 
 // Containers: BigUint64Array, or anything with pilcom.BigBuffer's surface {length, slice(a,b) -> BigUint64Array, set(arr, off)}
 // (used by the reference at fft_p.js:28-29,89,116; merklehash_p.js:70; stark_gen_helpers.js:104-137).
@@ -56,4 +134,4 @@ function staged(src, nIn, dst, nOut, fn) {
     }
 }
 
-module.exports = { addon, isFlat, isDev, DevBuffer, upload, download, staged, CHUNK };
+module.exports = { addon, isFlat, isDev, DevBuffer, PinnedBuffer, ChunkedBuffer, copyAfter, copyFence, copySync, upload, download, staged, CHUNK };

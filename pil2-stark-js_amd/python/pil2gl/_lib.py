@@ -62,6 +62,18 @@ SIGNATURES = {
     "pil2gl_square": (_U64, [_U64]),
     "pil2gl_dev_download": (_I, [vp, vp, _U64]),
     "pil2gl_sync": (_I, [vp]),
+    "pil2gl_host_alloc": (_I, [_U64, C.POINTER(vp)]),
+    "pil2gl_host_free": (_I, [vp]),
+    "pil2gl_host_register": (_I, [vp, _U64]),
+    "pil2gl_host_unregister": (_I, [vp]),
+    "pil2gl_dev_upload_async": (_I, [vp, vp, _U64]),
+    "pil2gl_dev_download_async": (_I, [vp, vp, _U64]),
+    "pil2gl_copy_after": (_I, [vp]),
+    "pil2gl_copy_fence": (_I, [vp]),
+    "pil2gl_copy_sync": (_I, []),
+    "pil2gl_land_rows_dev": (_I, [vp, _U64, vp, _U64, _U64, C.POINTER(_U64), vp]),
+    "pil2gl_dev_load_file": (_I, [C.c_char_p, _U64, _U64, _U64, vp, _U64, _U64, C.POINTER(_U64)]),
+    "pil2gl_dev_save_file": (_I, [C.c_char_p, _U64, vp, _U64, _U64]),
     "pil2gl_interpolate": (_I, [vp, _U64, _U32, vp, _U32]),
     "pil2gl_interpolate_dev": (_I, [vp, _U64, _U32, vp, _U32, vp]),
     "pil2gl_interpolate_cosets_dev": (_I, [vp, _U64, _U32, vp, _U32, _U32, _U32, vp]),

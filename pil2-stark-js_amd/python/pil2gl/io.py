@@ -2,6 +2,9 @@
 
   load_pols / save_pols   <-> witnessCalculator.js:145-196 (`.commit` / `.const`: raw little-endian u64, row-major n x nCols,
                               no header) streamed through a bounded host buffer (a 107 GB trace never sits in host RAM)
+  load_pols_dev / save_pols_dev  the same files through the C ABI's own loader (pil2gl_dev_load_file / _save_file: two pinned
+                              chunks, asynchronous copies on the library's copy stream, the landing pass that checks every word
+                              is canonical and pads rows as writeToBigBuffer(buff, nCols) does, witnessCalculator.js:198-214)
   MerkleHash.writeToFile / readFromFile (pil2gl/__init__.py, pil2gl/bn128.py) <-> `.consttree` (merklehash_p.js:228-278)
   proof2zkin / zkin_json  <-> src/proof2zkin.js:1-75 and the stringification of main_prover.js:141-148
 """
@@ -45,6 +48,33 @@ def save_pols(buf, fileName):
                 flat[o:o + CHUNK_WORDS].cpu().numpy().view(np.uint64).astype("<u8", copy=False).tofile(f)
         else:
             np.ascontiguousarray(buf, dtype=np.uint64).reshape(-1).astype("<u8", copy=False).tofile(f)
+
+
+def load_pols_dev(fileName, n, nCols, dst_cols=None, check=True, chunk_words=0, byte_offset=0):
+    """-> torch int64 tensor of n * dst_cols words on the current device, filled by pil2gl_dev_load_file (dst_cols > nCols: every
+    row zero-padded to dst_cols).  check: raise ValueError naming the file, the word index and the value when a word is >= p."""
+    import ctypes as C
+    from . import _lib
+    dst_cols = nCols if dst_cols is None else dst_cols
+    out = torch.empty(n * dst_cols, dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()))
+    bad = C.c_uint64(0)
+    _lib.call("pil2gl_copy_after", C.c_void_p(torch.cuda.current_stream().cuda_stream))    # the allocator may hand out memory the stream still reads
+    _lib.call("pil2gl_dev_load_file", str(fileName).encode(), byte_offset, n, nCols, out.data_ptr(), dst_cols, chunk_words,
+              C.byref(bad) if check else None)
+    if check and bad.value != 0xFFFFFFFFFFFFFFFF:
+        r, c = divmod(bad.value, nCols)
+        v = int(out[r * dst_cols + c].item()) & 0xFFFFFFFFFFFFFFFF
+        raise ValueError("%s: word %d (row %d, column %d) is %d, not a canonical field element" % (fileName, bad.value, r, c, v))
+    return out
+
+
+def save_pols_dev(buf, fileName, chunk_words=0, byte_offset=0):
+    """the words of a contiguous device tensor to fileName through pil2gl_dev_save_file (the file ends after them)"""
+    from . import _lib
+    flat = buf.reshape(-1)
+    assert flat.is_cuda and flat.is_contiguous() and flat.element_size() == 8
+    torch.cuda.current_stream().synchronize()           # the words are read on the library's copy stream
+    _lib.call("pil2gl_dev_save_file", str(fileName).encode(), byte_offset, flat.data_ptr(), flat.numel(), chunk_words)
 
 
 def proof2zkin(p, starkInfo):
