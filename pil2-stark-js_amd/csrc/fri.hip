@@ -422,6 +422,11 @@ int pil2gl_compute_q_split_brev_dev(const uint64_t *qq1, uint32_t nBits, uint32_
     HIP_TRY(hipStreamSynchronize(as_stream(stream)));
     return PIL2GL_OK;
 }
+// (xi0, xi1, xi2) with xi1 = xi2 = 0 and (xi0 / 7)^(2^nBitsExt) = 1: the point is 7 w_E^k for some row k (no extension element outside the
+// base field solves x^E = 1).  Shared by the table, which refuses such a point, and by LEv, which must not reach the table with one.
+static bool base_point_is_a_row(u64 xi0, u64 xi1, u64 xi2, u32 nBitsExt) {
+    return xi1 == 0 && xi2 == 0 && h_pow(h_mul(xi0, h_inv(7)), 1ull << nBitsExt) == 1;
+}
 int pil2gl_x_div_x_sub_xi_dev(uint32_t nBitsExt, const uint64_t xi[3], uint64_t nOpen, uint64_t iOpen, uint64_t *out, void *stream) {
     return pil2gl_x_div_x_sub_xi_cosets_dev(nBitsExt, 0, xi, nOpen, iOpen, 0, 1, out, stream);
 }
@@ -438,6 +443,10 @@ int pil2gl_x_div_x_sub_xi_cosets_dev(uint32_t nBitsExt, uint32_t extBits, const 
     u32 ccLog = 0; while ((1u << ccLog) < cosetCount) ccLog++;
     const u64 GP = 0xFFFFFFFF00000001ull;
     const u64 xi0 = xi[0] % GP, b = h_sub(0, xi[1] % GP), c = h_sub(0, xi[2] % GP);
+    // xi = x_k for a row k of the table: that row's denominator is zero and the reference throws "Division by zero" (f3g.js:175 through
+    // F.batchInverse, stark_gen_helpers.js:316).  The kernel has no zero guard -- a zero norm would zero all the rows its lane inverts
+    // together -- so the call is refused here, whichever cosets were asked for.  Only base-field points can be rows: x_k is one.
+    if (base_point_is_a_row(xi0, b, c, nBitsExt)) return fail(PIL2GL_EINVAL, "xi is a point of the 2^%u-row coset 7<w>: x / (x - xi) divides by zero at that row", nBitsExt);
     const u64 bb = h_mul(b, b), cc = h_mul(c, c), bc = h_mul(b, c);
     XDivConst K;
     K.xi0 = xi0; K.b = b; K.c = c; K.c2 = h_add(c, c); K.bc2 = h_add(bc, bc);
@@ -457,6 +466,8 @@ int pil2gl_x_div_x_sub_xi_cosets_dev(uint32_t nBitsExt, uint32_t extBits, const 
 // i.e. the batched-inversion kernel of the FRI table at the point 7 xi over the N rows, times one extension constant: one sweep that
 // writes N triples instead of an N x 3 transform (2^24 rows: 0.5 ms against 2.8).  Same values, exactly (field arithmetic).
 // PIL2GL_LEV_NTT=1 keeps the transform (A/B runs, tests).
+// The closed form has a pole where xi^N = 1, i.e. at the N base-field roots of unity xi = w^j (0 / 0: the constant is zero and the table's
+// row j divides by zero); there the sum itself is the unit vector at row j, and the transform below computes it.
 __global__ void e3_scale_kernel(u64 *__restrict__ v, u64 n, E3 c) {
     const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) st3(v + 3 * k, e3_mul(ld3(v + 3 * k), c));
@@ -465,8 +476,8 @@ int pil2gl_build_lev_dev(uint32_t nBits, const uint64_t xi[3], uint64_t *lev, vo
     P2_TRY(ensure_init());
     if (!xi || !lev || nBits > PIL2GL_MAX_NTT_BITS) return fail(PIL2GL_EINVAL, "bad LEv arguments");
     static const bool viaNtt = getenv("PIL2GL_LEV_NTT") && atoi(getenv("PIL2GL_LEV_NTT"));
-    if (!viaNtt && nBits > 0) {
-        const u64 GP = 0xFFFFFFFF00000001ull;
+    const u64 GP = 0xFFFFFFFF00000001ull;
+    if (!viaNtt && nBits > 0 && !base_point_is_a_row(h_mul(7, xi[0] % GP), xi[1] % GP, xi[2] % GP, nBits)) {
         u64 z[3] = { xi[0] % GP, xi[1] % GP, xi[2] % GP }, zN[3] = { z[0], z[1], z[2] };
         for (u32 b = 0; b < nBits; b++) h_e3_mul(zN, zN, zN);                                  // xi^N
         const u64 invN = h_inv((1ull << nBits) % GP);

@@ -241,6 +241,7 @@ def test_bad_arguments_are_refused_before_any_launch(gl):
     d = torch.zeros(4096, dtype=torch.int64, device="cuda")
     ok = d.data_ptr()
     ch = np.zeros(3, np.uint64)
+    onCoset = np.array([7 * pow(gl._root_of_unity(6), 5, P) % P, 0, 0], dtype=np.uint64)     # x_5 of the 64-point coset: x / (x - xi) divides by zero there
     bad = [("pil2gl_fft_dev", (None, 1, 4, ok, None)), ("pil2gl_fft_dev", (ok, 1, 31, ok, None)), ("pil2gl_fft_dev", (ok, 1, 4, None, None)),
            ("pil2gl_interpolate_cosets_dev", (ok, 1, 4, ok, 6, 3, 2, None)),                 # cosets [3, 5) of 4
            ("pil2gl_interpolate_cosets_dev", (ok, 1, 4, ok, 3, 0, 1, None)),                 # nBitsExt < nBits
@@ -258,6 +259,8 @@ def test_bad_arguments_are_refused_before_any_launch(gl):
            ("pil2gl_compute_q_split_dev", (None, 4, 5, 3, 2, ok, None)),
            ("pil2gl_x_div_x_sub_xi_cosets_dev", (6, 2, gl._ptr(ch), 2, 2, 0, 1, ok, None)),   # iOpen >= nOpen
            ("pil2gl_x_div_x_sub_xi_cosets_dev", (6, 2, gl._ptr(ch), 2, 0, 3, 2, ok, None)),   # cosets [3, 5) of 4
+           ("pil2gl_x_div_x_sub_xi_dev", (6, gl._ptr(onCoset), 2, 0, ok, None)),             # the reference throws "Division by zero"
+           ("pil2gl_x_div_x_sub_xi_cosets_dev", (6, 2, gl._ptr(onCoset), 2, 1, 0, 1, ok, None)),
            ("pil2gl_rows_dot_ext_dev", (None, 8, 8, gl._ptr(ch), 1, ok, 0, None)),
            ("pil2gl_gprod_dev", (ok, 2, ok, 1, 8, ok, None)), ("pil2gl_gprod_dev", (None, 1, ok, 1, 8, ok, None)),
            ("pil2gl_dev_upload", (None, gl._ptr(ch), 3))]
