@@ -371,6 +371,22 @@ int pil2gl_debug_jit_compile(const glx_program *prog, const glx_ctx *ctx, uint64
 /* host-only: the program as pil2gl_eval_program_dev optimises it for this context, Horner fusion included: outInfo[0] = temporary
  * slots (what the choice between the compiled kernel and the two interpreter forms reads), [1] = ops, [2] = fused Horner terms */
 int pil2gl_debug_plan_program(const glx_program *prog, const glx_ctx *ctx, uint32_t *outInfo);
+/* host-only, no device: the kernel launches fft / ifft / interpolate / the extension from coefficients make for 2^nBits rows x nPols
+ * columns (the two extensions: onto cosetCount of the 2^(nBitsExt - nBits) cosets, 0 = all; fft / ifft ignore both), as the
+ * transforms plan them under the environment's test hooks (PIL2GL_NTT_KMAX, PIL2GL_NTT_GENERIC, PIL2GL_LDE_WIDEFWD).
+ * Writes *nLaunches records of PIL2GL_PLAN_LAUNCH_WORDS words to out (room for maxLaunches; 64 always suffice), in launch order:
+ *   [0] kind: 0 inverse DIF pass, 1 forward DIF pass, 2 DIT pass, 3 mid kernel (csrc/ntt.hip)   [1] lo, [2] k: index bits [lo, lo+k)
+ *   [3] columns per slot group, [4] slot groups, [5] column chunks   [6] workgroup x (tile slots), [7] workgroup y
+ *   [8] fixed-geometry instance: 0 (any-geometry), 15 or 16 slots   [9] mid kernel: rows per lane of the instance (passes: 0)
+ *   [10] LDS bytes   [11] workgroups   [12] scatters to bit-reversed rows   [13] stores canonical values
+ * A call of 2^0 rows (a copy / a broadcast) or of no columns has no launches. */
+#define PIL2GL_PLAN_FFT 0
+#define PIL2GL_PLAN_IFFT 1
+#define PIL2GL_PLAN_INTERPOLATE 2
+#define PIL2GL_PLAN_EXTEND_COEFS 3
+#define PIL2GL_PLAN_LAUNCH_WORDS 14
+int pil2gl_debug_plan_transform(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount,
+                                uint32_t *out, uint32_t maxLaunches, uint32_t *nLaunches);
 /* the two hand-written Goldilocks products on n pairs of arbitrary u64 operands (host pointers): x[i] = a*b by the exact form
  * the transform kernels use (gl_field.cuh mul_lazy_x), pb[i] = a*b by the flagged form of the S-boxes (mul_lazy_b), both canonical;
  * flag[i] != 0 where the flagged form asks to be recomputed (its last subtraction borrowed: probability ~2^-32 on random operands) */

@@ -20,6 +20,10 @@
 //    passes run in place.  Extended row i = 8k+j is coset point 7*w_E^(8k+j): natural order.
 //  * Rows are contiguous in memory, so a tile row is one contiguous segment of Wc*8 bytes
 //    (or several adjacent rows when C is small): every global access is a coalesced segment.
+//  * The host side plans first and launches second: plan_ntt / plan_lde turn (rows, columns, cosets) into a short list of launches
+//    (kernel instance, tile geometry, grid, LDS) without touching a device, ntt_launch / lde_launch run the list, and
+//    pil2gl_debug_plan_transform shows it to the tests.  Three environment switches, read once per call, are test hooks that reach
+//    pass sizes and kernel families the default plan does not: PIL2GL_NTT_KMAX, PIL2GL_NTT_GENERIC, PIL2GL_LDE_WIDEFWD.
 #include "common.h"
 #include "gl_field.cuh"
 #include "gl_fermat.cuh"
@@ -28,14 +32,6 @@
 
 #ifndef NTT_MUL
 #define NTT_MUL(a, b) mul_lazy_x(a, b)   // the twiddle products of the tile kernels: the 16-instruction exact carry-out form (A/B: -DNTT_MUL=mul_lazy, 22 compiler instructions: 208.5 vs 201.5 ms per config-3 interpolate)
-#endif
-// experiments only (tools/lde_two_sweep.sh): larger workgroups for the any-geometry instances, so that 10-stage tiles (1024 rows x 16
-// slots, 128+ KB of LDS, one workgroup per CU) still put four waves on a SIMD
-#ifndef NTT_MAXTHREADS
-#define NTT_MAXTHREADS 256
-#endif
-#ifndef LDE_MAXTHREADS
-#define LDE_MAXTHREADS 512
 #endif
 using namespace gl;
 
@@ -146,6 +142,8 @@ __device__ __forceinline__ u32 xcd_local_block() {
     return b < (per << 3) ? (b & 7) * per + (b >> 3) : b;
 }
 
+constexpr unsigned PASS_THREADS = 256, MID_THREADS = 512;      // workgroup budgets of ntt_pass_kernel / lde_mid_kernel: the planner sizes tiles by them
+
 struct PassParams {
     const u64 *src; u64 *dst;
     const u64 *tw;                  // pow256 table of the transform's 2^32-th root (forward or inverse)
@@ -161,10 +159,12 @@ struct PassParams {
 };
 
 // KC = 0: any geometry; KC = 8: the geometry of the wide matrices (8 stages, SC = 15 or 16 column slots x 16 sub-transform lanes,
-// one slot group: 16 slots for rows of 128 bytes and more in 16-column chunks, 15 for the 100-column matrices whose seven
-// chunks are 15 wide), with every stride, LDS offset and twiddle index a compile-time constant
+// one slot group), with every stride, LDS offset and twiddle index a compile-time constant.  16 slots: rows of 128 bytes and more, cut
+// into 16-column chunks with a ragged last one (100 columns: 16 x 6 + 4).  15 slots: a 15-column matrix, whose rows are under 128
+// bytes and take 7-stage passes, so no default plan reaches SC = 15 (enumerated over 2^0..2^30 rows x 1..200 columns, tests/golden/
+// transform_plans.txt.gz); PIL2GL_NTT_KMAX=9 or 10 does, e.g. fft of 2^8 x 15 (one pass) and interpolate of 2^16 x 15 (DIT pass).
 template <bool INV, bool DIT, int KC, int SC = 16>
-__global__ void __launch_bounds__(KC ? 256 : NTT_MAXTHREADS) ntt_pass_kernel(PassParams P) {
+__global__ void __launch_bounds__(PASS_THREADS) ntt_pass_kernel(PassParams P) {
     extern __shared__ u64 lds[];
     const u32 k = KC ? KC : P.k, K = 1u << k, S = KC ? SC : blockDim.x, by = KC ? 16 : blockDim.y;
     const u32 x = threadIdx.x, y = threadIdx.y, tid = y * S + x, nth = S * by;
@@ -248,9 +248,10 @@ struct LdeParams {
 
 // Finishes the iNTT on bits [0,k), scales by the coset factors and starts the forward NTT (see header).
 // SC = 0: any geometry; SC > 0: 8 stages, SC column slots x 16 sub-transform lanes, one slot group (EPT = 16) -- the geometry
-// of the wide matrices, with compile-time strides
+// of the wide matrices, with compile-time strides: 16 slots for 16 columns and more, 15 for a 15-column matrix of more than 2^8 rows
+// (the mid kernel takes 8 stages there even though the passes around it take 7)
 template <int EPT, int SC>
-__global__ void __launch_bounds__(SC ? 512 : LDE_MAXTHREADS) lde_mid_kernel(LdeParams P) {
+__global__ void __launch_bounds__(MID_THREADS) lde_mid_kernel(LdeParams P) {
     extern __shared__ u64 lds[];
     const u32 k = SC ? 8 : P.k, K = 1u << k, S = SC ? SC : blockDim.x, by = SC ? 16 : blockDim.y;
     const u32 x = threadIdx.x, y = threadIdx.y, tid = y * S + x, nth = S * by;
@@ -267,7 +268,7 @@ __global__ void __launch_bounds__(SC ? 512 : LDE_MAXTHREADS) lde_mid_kernel(LdeP
     const u64 g = (u64)gt * (SC ? 1 : P.G) + gi;    // index of this slot's 2^k-row block
     const u64 base = g * K * P.C + c;
 
-    u64 coef[EPT];                                  // EPT >= K / by rows per lane: all loads in flight while the tables are built
+    u64 coef[EPT];                                  // EPT >= K / by rows per lane (2, 4, 8 or 16): all loads in flight while the tables are built
 #pragma unroll
     for (int i = 0; i < EPT; i++) { const u32 t = y + i * by; coef[i] = (valid && t < K) ? P.src[base + (u64)t * P.C] : 0; }
     for (u32 j = tid; j < K; j += nth) { TWi[j] = P.twKi[j << (10 - k)]; TWf[j] = P.twKf[j << (10 - k)]; }
@@ -325,9 +326,26 @@ __global__ void broadcast_row_kernel(const u64 *src, u64 *dst, u64 C, u64 rows) 
 }
 
 // ---------------------------------------------------------------- host-side planning
+// plan_ntt / plan_lde decide every launch of a transform as plain values, without touching a device; ntt_launch / lde_launch
+// run what they planned.  pil2gl_debug_plan_transform shows the same plan to the tests.
 using namespace pil2gl;
 
-u32 env_u32(const char *name, u32 dflt) { const char *s = getenv(name); return s ? (u32)atoi(s) : dflt; }
+constexpr u32 TILE_WORDS = 4096;       // u64 words of a tile in LDS (32 KiB), beside its twiddle / scale tables
+
+// test hooks: reach pass sizes and kernel families the default plan does not.  Read once per call, here only.
+struct PlanOptions {
+    u32 kmax;           // PIL2GL_NTT_KMAX: stages per pass (1..10) instead of the 8 / 7 of pick_kmax; 0 = not set
+    bool generic;       // PIL2GL_NTT_GENERIC=1: the any-geometry instances where the fixed-geometry ones would run
+    bool wideFwd;       // PIL2GL_LDE_WIDEFWD=0: the forward passes of a narrow interpolate keep the narrow matrix's 7 stages
+};
+PlanOptions plan_options() {
+    PlanOptions o = {0, false, true};
+    if (const char *s = getenv("PIL2GL_NTT_KMAX")) o.kmax = std::min<u32>(10, std::max<u32>(1, (u32)atoi(s)));
+    if (const char *s = getenv("PIL2GL_NTT_GENERIC")) o.generic = atoi(s) != 0;
+    if (const char *s = getenv("PIL2GL_LDE_WIDEFWD")) o.wideFwd = atoi(s) != 0;
+    return o;
+}
+
 u32 pow2floor(u64 v) { u32 r = 1; while ((u64)r * 2 <= v) r *= 2; return r; }
 
 struct Geom { u32 Wc, nbT, nColChunks, S, by; };
@@ -342,11 +360,10 @@ Geom make_geom(u32 k, u64 C, u64 totalGroups, u32 maxElems, u32 nThreads) {
     } else {
         u32 chunks = (u32)((C + smax - 1) / smax);
         g.Wc = (u32)((C + chunks - 1) / chunks);
-        // 8-stage tiles have fixed-geometry kernels for 15 and 16 slots only: chunks of 16 with a ragged last chunk beat evenly cut chunks
-        // on the any-geometry kernels (81 columns: 16 x 5 + 1 instead of 14 x 5 + 11: -11 %), and 16 beats 15 where both give the same
-        // number of chunks (100 columns, 16 x 6 + 4 against 15 x 6 + 10: 194.7 against 198.1 ms per config-3 interpolate, four same-box
-        // pairs; other widths +-1 %: profiles/r05_lde_chunks_15_16.txt).  PIL2GL_NTT_WC15=1: 15 where it fits, as rounds 2-4 had it.
-        if (k == 8 && smax == 16 && !env_u32("PIL2GL_NTT_EVEN_CHUNKS", 0)) g.Wc = ((C + 14) / 15 == chunks && env_u32("PIL2GL_NTT_WC15", 0)) ? 15 : 16;
+        // 8-stage tiles have fixed-geometry kernels: chunks of 16 with a ragged last chunk beat evenly cut chunks on the any-geometry
+        // kernels (81 columns: 16 x 5 + 1 instead of 14 x 5 + 11: -11 %), and 16 beats 15 where both give the same number of chunks
+        // (100 columns, 16 x 6 + 4 against 15 x 6 + 10: 194.7 against 198.1 ms per config-3 interpolate; profiles/r05_lde_chunks_15_16.txt)
+        if (k == 8 && smax == 16) g.Wc = 16;
         g.nbT = 1;
         g.nColChunks = (u32)((C + g.Wc - 1) / g.Wc);
     }
@@ -356,82 +373,196 @@ Geom make_geom(u32 k, u64 C, u64 totalGroups, u32 maxElems, u32 nThreads) {
     return g;
 }
 
+// The fixed-geometry rule: a tile of 8 stages, 15 or 16 slots x 16 sub-transform lanes, one slot group runs the instances whose
+// strides are compile-time constants.  -> the slot count, or 0 for the any-geometry instances.
+// One slot group (nbT == 1) makes S == Wc, so the chunk width needs no test of its own; and an 8-stage tile has 16 sub-transforms per
+// column, so by = min(threads / S, 16) is 16 at 15 or 16 slots under either thread budget (256 / 16 = 16, 512 / 16 = 32): the pass
+// kernels, the mid kernel and the planners' probes all get the same answer from the same geometry.  With 4096-word tiles that is
+// 16 slots for 16 columns and more (chunks of 16) and 15 slots for 15 columns; narrower matrices pack several slot groups.
+u32 fixed_slots(u32 k, const Geom &g, const PlanOptions &o) {
+    return !o.generic && k == 8 && g.nbT == 1 && g.by == 16 && (g.S == 15 || g.S == 16) ? g.S : 0;
+}
+// would an 8-stage tile of a 2^n x C matrix (n > 8) run a fixed-geometry instance?
+bool fixed_at_8(u32 n, u64 C, const PlanOptions &o) { return fixed_slots(8, make_geom(8, C, 1ull << (n - 8), TILE_WORDS, PASS_THREADS), o) != 0; }
+
 // stages per pass: a tile row is S*8 contiguous bytes and S <= 256 / 2^(k-4), so 8 stages keep 128-byte segments for
 // wide matrices; narrow ones (rows under 128 bytes) take 7 so that adjacent rows fill the segment
-u32 pick_kmax(u64 C) {
-    u32 dflt = C * 8 >= 128 ? 8 : 7;
-    return std::min<u32>(10, std::max<u32>(1, env_u32("PIL2GL_NTT_KMAX", dflt)));
-}
+u32 pick_kmax(u64 C, const PlanOptions &o) { return o.kmax ? o.kmax : C * 8 >= 128 ? 8 : 7; }
 
-int set_lds(const void *fn, size_t bytes) {
-    if (bytes > 160 * 1024) return fail(PIL2GL_EINVAL, "tile needs %zu bytes of LDS (>160 KiB)", bytes);
-    if (bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+enum LaunchKind : u32 { PASS_INV_DIF = 0, PASS_FWD_DIF = 1, PASS_DIT = 2, MID = 3 };
+// one kernel launch of a transform
+struct Launch {
+    u32 kind;
+    u32 lo, k;              // the launch works on index bits [lo, lo+k)
+    Geom g;
+    u32 fixedSlots;         // 0: any-geometry instance; 15 / 16: the fixed-geometry instance of that many slots
+    u32 ept;                // mid: the rows-per-lane instance (lde_mid_kernel<EPT, ..>); passes: 0
+    u32 ldsBytes, blocks;
+    u32 scatter, canonOut;  // passes: PassParams of the same names; mid: canonOut = no pass follows
+};
+constexpr int MAX_LAUNCHES = 64;           // 2 x 30 one-stage passes and the mid kernel at most
+struct Plan { Launch l[MAX_LAUNCHES]; int n = 0; };
+
+constexpr size_t MAX_LDS_BYTES = 160 * 1024;
+int check_launch(const Launch &L, u64 blocks) {
+    if (blocks > 0x7fffffffull) return fail(PIL2GL_EINVAL, "grid too large");
+    if (L.ldsBytes > MAX_LDS_BYTES) return fail(PIL2GL_EINVAL, "tile needs %u bytes of LDS (>160 KiB)", L.ldsBytes);
     return PIL2GL_OK;
 }
 
 // One pass over index bits [lo, lo+k) of a 2^n x C matrix.
-int launch_pass(const u64 *src, u64 *dst, u64 C, u32 n, u32 lo, u32 k, bool dit, bool inverse, u64 scale, bool scatter, bool canonOut, hipStream_t st) {
-    PassParams P;
-    P.src = src; P.dst = dst; P.canonOut = canonOut;
-    P.tw = inverse ? tables().powWi : tables().powW;
-    P.twK = inverse ? tables().tw1024i : tables().tw1024;
-    P.C = C; P.scale = scale; P.k = k; P.logM = lo + k; P.hasTw = lo > 0; P.dit = dit; P.n = n; P.scatter = scatter;
-    u64 totalGroups;
-    u32 nHi;
-    if (lo > 0) { P.tStride = (C << lo); P.gStride = C; P.hiStride = (C << (lo + k)); totalGroups = 1ull << lo; nHi = 1u << (n - lo - k); }
-    else { P.tStride = C; P.gStride = (C << k); P.hiStride = 0; totalGroups = 1ull << (n - k); nHi = 1; }
-    Geom g = make_geom(k, C, totalGroups, env_u32("PIL2GL_NTT_TILE", 4096), std::min<u32>(NTT_MAXTHREADS, env_u32("PIL2GL_NTT_THREADS", 256)));
-    P.Wc = g.Wc; P.nbT = g.nbT; P.nColChunks = g.nColChunks; P.nGroupTiles = (u32)(totalGroups / g.nbT);
-    u64 K = 1ull << k;
-    const bool fixedGeom = k == 8 && (g.S == 16 || g.S == 15) && g.by == 16 && g.nbT == 1 && g.Wc == g.S && !env_u32("PIL2GL_NTT_GENERIC", 0);
-    size_t ldsBytes = 8 * ((size_t)g.S * (fixedGeom ? K + K / 16 : K) + K + (P.hasTw ? (size_t)g.nbT * K : 0));
-    u64 blocks = (u64)nHi * P.nGroupTiles * P.nColChunks;
-    if (blocks > 0x7fffffffull) return fail(PIL2GL_EINVAL, "grid too large");
-    if (dit && inverse) return fail(PIL2GL_EINVAL, "no inverse decimation-in-time pass");
-#define PASS_CASE(INV_, DIT_)                                                                                     \
-    { if (fixedGeom && g.S == 16) {                                                                               \
-          P2_TRY(set_lds((const void *)ntt_pass_kernel<INV_, DIT_, 8, 16>, ldsBytes));                               \
-          hipLaunchKernelGGL((ntt_pass_kernel<INV_, DIT_, 8, 16>), dim3((unsigned)blocks), dim3(16, 16), ldsBytes, st, P); \
-      } else if (fixedGeom) {                                                                                      \
-          P2_TRY(set_lds((const void *)ntt_pass_kernel<INV_, DIT_, 8, 15>, ldsBytes));                               \
-          hipLaunchKernelGGL((ntt_pass_kernel<INV_, DIT_, 8, 15>), dim3((unsigned)blocks), dim3(15, 16), ldsBytes, st, P); \
-      } else {                                                                                                     \
-          P2_TRY(set_lds((const void *)ntt_pass_kernel<INV_, DIT_, 0>, ldsBytes));                                   \
-          hipLaunchKernelGGL((ntt_pass_kernel<INV_, DIT_, 0>), dim3((unsigned)blocks), dim3(g.S, g.by), ldsBytes, st, P); } }
-    if (dit) PASS_CASE(false, true) else if (inverse) PASS_CASE(true, false) else PASS_CASE(false, false)
-#undef PASS_CASE
-    KERNEL_CHECK();
-    return PIL2GL_OK;
+int plan_pass(Plan &p, u32 kind, u64 C, u32 n, u32 lo, u32 k, bool scatter, bool canonOut, const PlanOptions &o) {
+    Launch &L = p.l[p.n++];
+    L.kind = kind; L.lo = lo; L.k = k; L.ept = 0; L.scatter = scatter; L.canonOut = canonOut;
+    const u64 totalGroups = lo > 0 ? 1ull << lo : 1ull << (n - k), nHi = lo > 0 ? 1ull << (n - lo - k) : 1, K = 1ull << k;
+    L.g = make_geom(k, C, totalGroups, TILE_WORDS, PASS_THREADS);
+    L.fixedSlots = fixed_slots(k, L.g, o);
+    // tile (one spare row per 16 in the fixed geometry) + tile twiddles + the inter-pass twiddles of every slot group
+    L.ldsBytes = (u32)(8 * ((size_t)L.g.S * (L.fixedSlots ? K + K / 16 : K) + K + (lo > 0 ? (size_t)L.g.nbT * K : 0)));
+    const u64 blocks = nHi * (totalGroups / L.g.nbT) * L.g.nColChunks;
+    L.blocks = (u32)blocks;
+    return check_launch(L, blocks);
 }
 
 // split `bits` into ceil(bits/kmax) nearly equal passes
 int split_bits(u32 bits, u32 kmax, u32 *ks) {
     if (bits == 0) return 0;
-    if (const char *e = getenv("PIL2GL_NTT_SPLIT")) {          // experiments: "8,8,2" is taken when it adds up to `bits`
-        u32 tot = 0; int np = 0; u32 tmp[32];
-        for (const char *q = e; *q && np < 32;) { tmp[np] = (u32)atoi(q); tot += tmp[np++]; while (*q && *q != ',') q++; if (*q) q++; }
-        if (tot == bits) { for (int i = 0; i < np; i++) ks[i] = tmp[i]; return np; }
-    }
     u32 np = (bits + kmax - 1) / kmax, base = bits / np, extra = bits % np;
     for (u32 i = 0; i < np; i++) ks[i] = base + (i < extra ? 1 : 0);
     return (int)np;
 }
 
-// passes of a standalone transform.  Where the 8-bit pass has its fixed-geometry kernel (tiles of 15 / 16 slots) as many passes as possible take
-// 8 bits and ONE takes the remainder, if that is at least 4 bits: 2^20 x 100 in 8,8,4 instead of 7,7,6 -17 %, 2^22 in 8,8,6 instead of 8,7,7 -5 %;
-// a remainder of 1..3 bits (a whole sweep for almost no arithmetic) stays balanced: 2^26 in 8,8,8,2 loses 8 % (profiles/r05_lde_mid8_planner.txt)
-int plan_passes(u32 n, u32 kmax, u64 C, u32 *ks) {
-    const u32 r = n & 7;
-    if (kmax == 8 && n > 16 && (r == 0 || r >= 4) && !getenv("PIL2GL_NTT_SPLIT") && !env_u32("PIL2GL_NTT_GENERIC", 0) && !env_u32("PIL2GL_NTT_BALANCED", 0)) {
-        const Geom g = make_geom(8, C, 1ull << (n - 8), env_u32("PIL2GL_NTT_TILE", 4096), std::min<u32>(NTT_MAXTHREADS, env_u32("PIL2GL_NTT_THREADS", 256)));
-        if ((g.S == 15 || g.S == 16) && g.by == 16 && g.nbT == 1 && g.Wc == g.S) {
-            int np = 0;
-            for (u32 i = 0; i < n / 8; i++) ks[np++] = 8;
-            if (r) ks[np++] = r;
-            return np;
-        }
+// fft / ifft of a 2^n x C matrix: decimation in frequency from the top bits down; the last pass scatters to natural order.
+// Where the 8-bit pass has its fixed-geometry kernel as many passes as possible take 8 bits and ONE takes the remainder, if that is at
+// least 4 bits: 2^20 x 100 in 8,8,4 instead of 7,7,6 -17 %, 2^22 in 8,8,6 instead of 8,7,7 -5 %; a remainder of 1..3 bits (a whole sweep
+// for almost no arithmetic) stays balanced: 2^26 in 8,8,8,2 loses 8 % (profiles/r05_lde_mid8_planner.txt)
+int plan_ntt(u32 n, u64 C, bool inverse, const PlanOptions &o, Plan &p) {
+    p.n = 0;
+    if (C == 0 || n == 0) return PIL2GL_OK;         // (n = 0: a copy)
+    const u32 kmax = pick_kmax(C, o), r = n & 7;
+    u32 ks[32];
+    int np = 0;
+    if (kmax == 8 && n > 16 && (r == 0 || r >= 4) && fixed_at_8(n, C, o)) {
+        for (u32 i = 0; i < n / 8; i++) ks[np++] = 8;
+        if (r) ks[np++] = r;
+    } else np = split_bits(n, kmax, ks);
+    u32 lo = n;
+    for (int i = 0; i < np; i++) {
+        lo -= ks[i];
+        P2_TRY(plan_pass(p, inverse ? PASS_INV_DIF : PASS_FWD_DIF, C, n, lo, ks[i], i == np - 1, i == np - 1, o));
     }
-    return split_bits(n, kmax, ks);
+    return PIL2GL_OK;
+}
+
+// interpolate / extend of a 2^n x C matrix onto cosetCount of the 2^extBits cosets (0: all of them); coefIn: the input holds
+// coefficients already (row bitrev(m) = coefficient m), so no inverse stage runs.
+//  1. iNTT, decimation in frequency, bits [kf, n) from the top down
+//  2. mid kernel: the last kf iNTT stages + coset scaling + the first kf NTT stages
+//  3. the remaining forward stages, decimation in time, bits [kf, n) from the bottom up, on dst viewed as N x (C * cosets)
+int plan_lde(u32 n, u64 C, u32 extBits, u32 cosetCount, bool coefIn, const PlanOptions &o, Plan &p) {
+    p.n = 0;
+    if (C == 0 || n == 0) return PIL2GL_OK;         // (n = 0: a broadcast)
+    if (cosetCount == 0) cosetCount = 1u << extBits;
+    // a narrow matrix (rows under 128 bytes) whose extension is wide takes 8-stage passes on that side
+    const u32 kmax = pick_kmax(C, o), kmaxF = o.wideFwd ? std::max(kmax, pick_kmax(C * cosetCount, o)) : kmax;
+    const u32 nfp = (n + kmaxF - 1) / kmaxF;
+    u32 kf = (n + nfp - 1) / nfp;       // bits done by the mid kernel (both directions)
+    // The balanced split gives the mid kernel 6 or 7 bits whenever n is not 8 * passes (n = 17..21, 25..29): its fixed-geometry form
+    // (coefficients in registers over the cosets) is worth more than balance -- 8-17 % of an interpolate at 2^17..2^28 rows x 16 / 32 /
+    // 64 / 100 columns, full extensions and single cosets alike (profiles/r05_lde_mid8_planner.txt); widths whose tiles are not 15 or
+    // 16 slots keep the balanced split (20 columns lose 2-4 % with 8)
+    if (kf < 8 && n > 8 && kmaxF == 8 && fixed_at_8(n, C, o)) kf = 8;
+    u32 ks[32];
+    if (!coefIn) {
+        const int np = split_bits(n - kf, kmax, ks);
+        u32 lo = n;
+        for (int i = 0; i < np; i++) { lo -= ks[i]; P2_TRY(plan_pass(p, PASS_INV_DIF, C, n, lo, ks[i], false, false, o)); }
+    }
+    {
+        Launch &L = p.l[p.n++];
+        L.kind = MID; L.lo = 0; L.k = kf; L.scatter = 0; L.canonOut = n > kf ? 0 : 1;
+        const u64 totalGroups = 1ull << (n - kf), K = 1ull << kf;
+        // LDS = tile (S*K, one spare row per 16 in the fixed geometry) + two tile twiddle tables (K) + coset scale tables (2*G*K); narrow
+        // matrices (small C => many slot groups per tile) are dominated by the scale tables: halve the tile until it fits 96 KiB
+        for (u32 words = TILE_WORDS;; words /= 2) {
+            L.g = make_geom(kf, C, totalGroups, words, MID_THREADS);
+            L.fixedSlots = fixed_slots(kf, L.g, o);
+            L.ldsBytes = (u32)(8 * ((size_t)L.g.S * (L.fixedSlots ? K + K / 16 : K) + 2 * K + 2 * (size_t)L.g.nbT * K));
+            if (L.ldsBytes <= 96 * 1024 || L.g.nbT == 1) break;
+        }
+        // rows per lane: K / by = 2^(stages of the widest register step) = 2, 4, 8 or 16 -- by always reaches the sub-transform count,
+        // as 512 threads cover it at every tile the LDS holds
+        const u32 need = (u32)((K + L.g.by - 1) / L.g.by);
+        L.ept = L.fixedSlots ? 16 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 16;
+        if (need > 16) return fail(PIL2GL_EINVAL, "lde tile too tall for the thread block (need %u rows per thread)", need);
+        const u64 blocks = (totalGroups / L.g.nbT) * L.g.nColChunks;
+        L.blocks = (u32)blocks;
+        P2_TRY(check_launch(L, blocks));
+    }
+    const int np = split_bits(n - kf, kmaxF, ks);
+    u32 lo = kf;
+    for (int i = 0; i < np; i++) { P2_TRY(plan_pass(p, PASS_DIT, C * cosetCount, n, lo, ks[i], false, i == np - 1, o)); lo += ks[i]; }
+    return PIL2GL_OK;
+}
+
+// ---------------------------------------------------------------- launching a plan
+int set_lds(const void *fn, size_t bytes) {
+    if (bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return PIL2GL_OK;
+}
+
+// a planned pass on a 2^n x C matrix; scale: 0, or the factor every output takes (1/N of an inverse transform)
+int launch_pass(const Launch &L, const u64 *src, u64 *dst, u64 C, u32 n, u64 scale, hipStream_t st) {
+    const bool inverse = L.kind == PASS_INV_DIF;
+    const u32 lo = L.lo, k = L.k;
+    PassParams P;
+    P.src = src; P.dst = dst; P.canonOut = L.canonOut;
+    P.tw = inverse ? tables().powWi : tables().powW;
+    P.twK = inverse ? tables().tw1024i : tables().tw1024;
+    P.C = C; P.scale = scale; P.k = k; P.logM = lo + k; P.hasTw = lo > 0; P.dit = L.kind == PASS_DIT; P.n = n; P.scatter = L.scatter;
+    u64 totalGroups;
+    if (lo > 0) { P.tStride = (C << lo); P.gStride = C; P.hiStride = (C << (lo + k)); totalGroups = 1ull << lo; }
+    else { P.tStride = C; P.gStride = (C << k); P.hiStride = 0; totalGroups = 1ull << (n - k); }
+    P.Wc = L.g.Wc; P.nbT = L.g.nbT; P.nColChunks = L.g.nColChunks; P.nGroupTiles = (u32)(totalGroups / L.g.nbT);
+    const dim3 grid(L.blocks), block(L.g.S, L.g.by);
+#define PASS_CASE(INV_, DIT_)                                                                             \
+    switch (L.fixedSlots) {                                                                               \
+    case 16: P2_TRY(set_lds((const void *)ntt_pass_kernel<INV_, DIT_, 8, 16>, L.ldsBytes));                \
+             hipLaunchKernelGGL((ntt_pass_kernel<INV_, DIT_, 8, 16>), grid, block, L.ldsBytes, st, P); break; \
+    case 15: P2_TRY(set_lds((const void *)ntt_pass_kernel<INV_, DIT_, 8, 15>, L.ldsBytes));                \
+             hipLaunchKernelGGL((ntt_pass_kernel<INV_, DIT_, 8, 15>), grid, block, L.ldsBytes, st, P); break; \
+    default: P2_TRY(set_lds((const void *)ntt_pass_kernel<INV_, DIT_, 0>, L.ldsBytes));                    \
+             hipLaunchKernelGGL((ntt_pass_kernel<INV_, DIT_, 0>), grid, block, L.ldsBytes, st, P); }
+    switch (L.kind) {
+    case PASS_DIT: PASS_CASE(false, true) break;
+    case PASS_INV_DIF: PASS_CASE(true, false) break;
+    default: PASS_CASE(false, false)
+    }
+#undef PASS_CASE
+    KERNEL_CHECK();
+    return PIL2GL_OK;
+}
+
+int launch_mid(const Launch &L, LdeParams &P, hipStream_t st) {
+    P.k = L.k; P.canonOut = L.canonOut; P.Wc = L.g.Wc; P.G = L.g.nbT; P.nColChunks = L.g.nColChunks;
+    const dim3 grid(L.blocks), block(L.g.S, L.g.by);
+#define LDE_CASE(E_)                                                                              \
+    if (!L.fixedSlots && L.ept == E_) {                                                           \
+        P2_TRY(set_lds((const void *)lde_mid_kernel<E_, 0>, L.ldsBytes));                          \
+        hipLaunchKernelGGL((lde_mid_kernel<E_, 0>), grid, block, L.ldsBytes, st, P);               \
+    } else
+#define LDE_FIXED(S_)                                                                             \
+    if (L.fixedSlots == S_) {                                                                     \
+        P2_TRY(set_lds((const void *)lde_mid_kernel<16, S_>, L.ldsBytes));                         \
+        hipLaunchKernelGGL((lde_mid_kernel<16, S_>), grid, block, L.ldsBytes, st, P);              \
+    } else
+    LDE_FIXED(15) LDE_FIXED(16)
+    LDE_CASE(2) LDE_CASE(4) LDE_CASE(8) LDE_CASE(16)
+    { return fail(PIL2GL_EINVAL, "no lde_mid_kernel instance of %u rows per lane", L.ept); }
+#undef LDE_CASE
+#undef LDE_FIXED
+    KERNEL_CHECK();
+    return PIL2GL_OK;
 }
 
 }  // namespace
@@ -440,120 +571,44 @@ namespace pil2gl {
 
 int ntt_launch(const u64 *src, u64 C, u32 n, u64 *dst, bool inverse, hipStream_t st) {
     if (C == 0) return PIL2GL_OK;
-    u64 N = 1ull << n;
     if (n == 0) {
         if (src != dst) HIP_TRY(hipMemcpyAsync(dst, src, C * 8, hipMemcpyDeviceToDevice, st));
         return PIL2GL_OK;
     }
-    u32 kmax = pick_kmax(C);
-    u32 ks[32];
-    int np = plan_passes(n, kmax, C, ks);
-    u64 scale = inverse ? h_inv(N % 0xFFFFFFFF00000001ull) : 0;
-    if (np == 1) return launch_pass(src, dst, C, n, 0, n, false, inverse, scale, true, true, st);
-    u64 *tmp;
-    P2_TRY(scratch(0, N * C, &tmp));
-    u32 lo = n;
-    for (int i = 0; i < np; i++) {
-        lo -= ks[i];
-        const u64 *in = i == 0 ? src : tmp;
-        u64 *out = i == np - 1 ? dst : tmp;
-        P2_TRY(launch_pass(in, out, C, n, lo, ks[i], false, inverse, i == 0 ? scale : 0, i == np - 1, i == np - 1, st));
-    }
+    Plan p;
+    P2_TRY(plan_ntt(n, C, inverse, plan_options(), p));
+    const u64 N = 1ull << n, scale = inverse ? h_inv(N % 0xFFFFFFFF00000001ull) : 0;
+    u64 *tmp = nullptr;                             // src -> tmp, in place there, -> dst
+    if (p.n > 1) P2_TRY(scratch(0, N * C, &tmp));
+    for (int i = 0; i < p.n; i++) P2_TRY(launch_pass(p.l[i], i == 0 ? src : tmp, i == p.n - 1 ? dst : tmp, C, n, i == 0 ? scale : 0, st));
     return PIL2GL_OK;
 }
 
 int lde_launch(const u64 *src, u64 C, u32 n, u64 *dst, u32 nExt, hipStream_t st, u32 cosetBegin, u32 cosetCount, u64 *work, bool unitShift, bool coefIn) {
     if (C == 0) return PIL2GL_OK;
-    u32 eb = nExt - n;
+    const u32 eb = nExt - n;
     if (cosetCount == 0) { cosetBegin = 0; cosetCount = 1u << eb; }
-    u64 N = 1ull << n, E = 1ull << nExt;
     if (n == 0) {                       // constant polynomial: every coset point evaluates to it
-        (void)E;
         broadcast_row_kernel<<<(unsigned)(((u64)cosetCount * C + 255) / 256), 256, 0, st>>>(src, dst, C, cosetCount);
         KERNEL_CHECK();
         return PIL2GL_OK;
     }
-    // the forward passes run on dst viewed as N x (C * cosets): a narrow matrix (rows under 128 bytes) that becomes wide there takes
-    // 8-stage passes on that side (PIL2GL_LDE_WIDEFWD=0: the narrow matrix's 7 everywhere, as before)
-    u32 kmax = pick_kmax(C);
-    const u32 kmaxF = env_u32("PIL2GL_LDE_WIDEFWD", 1) ? std::max(kmax, pick_kmax(C * cosetCount)) : kmax;
-    u32 nfp = (n + kmaxF - 1) / kmaxF;
-    u32 kf = (n + nfp - 1) / nfp;       // bits done by the mid kernel (both directions)
-    // The balanced split gives the mid kernel 6 or 7 bits whenever n is not 8 * passes (n = 17..21, 25..29): its fixed-geometry form
-    // (8 bits, 15 / 16 slots, coefficients in registers over the cosets) is worth more than balance -- 8-17 % of an interpolate at
-    // 2^17..2^28 rows x 16 / 32 / 64 / 100 columns, full extensions and single cosets alike (profiles/r05_lde_mid8_planner.txt);
-    // widths whose tiles are not 15 or 16 slots keep the balanced split (20 columns lose 2-4 % with 8).  PIL2GL_LDE_KF: experiments.
-    if (kf < 8 && n > 8 && kmaxF == 8 && !env_u32("PIL2GL_NTT_GENERIC", 0)) {
-        const Geom g8 = make_geom(8, C, 1ull << (n - 8), env_u32("PIL2GL_LDE_TILE", 4096), std::min<u32>(LDE_MAXTHREADS, env_u32("PIL2GL_LDE_THREADS", 512)));
-        if ((g8.S == 15 || g8.S == 16) && g8.by == 16 && g8.nbT == 1) kf = 8;
-    }
-    if (const char *e = getenv("PIL2GL_LDE_KF")) { const u32 f = (u32)atoi(e); kf = f ? std::min(f, n) : (n + nfp - 1) / nfp; }      // 0: the balanced split
-    // 1. iNTT, decimation in frequency, bits [kf, n) from the top down: src -> tmp, then in place
-    const u64 *coef = src;
-    if (n > kf && !coefIn) {
-        u32 ks[32];
-        int np = split_bits(n - kf, kmax, ks);
-        u64 *tmp = work;                            // caller's workspace (may be src itself: every pass is in place)
-        if (!tmp) P2_TRY(scratch(0, N * C, &tmp));
-        u32 lo = n;
-        for (int i = 0; i < np; i++) {
-            lo -= ks[i];
-            P2_TRY(launch_pass(i == 0 ? src : tmp, tmp, C, n, lo, ks[i], false, true, 0, false, false, st));
-        }
-        coef = tmp;
-    }
-    // 2. mid kernel: last kf iNTT stages + coset scaling + first kf NTT stages, tmp -> dst
-    {
-        LdeParams P;
-        P.src = coef; P.dst = dst; P.twi = tables().powWi; P.twf = tables().powW; P.twKi = tables().tw1024i; P.twKf = tables().tw1024; P.pow7 = unitShift ? nullptr : tables().pow7;
-        P.C = C; P.ninv = coefIn ? 1 : h_inv(N % 0xFFFFFFFF00000001ull); P.n = n; P.k = kf; P.extBits = eb; P.coefIn = coefIn ? 1 : 0;
-        P.cosetBegin = cosetBegin; P.cosetCount = cosetCount; P.canonOut = n > kf ? 0 : 1;
-        u64 totalGroups = 1ull << (n - kf);
-        u32 nThreads = std::min<u32>(LDE_MAXTHREADS, env_u32("PIL2GL_LDE_THREADS", 512));
-        // LDS = tile (S*K) + two local twiddle tables (K) + coset scale tables (2*G*K); narrow matrices
-        // (small C => many row groups per tile) are dominated by the scale tables, so shrink until it fits
-        u64 K = 1ull << kf;
-        u32 maxElems = env_u32("PIL2GL_LDE_TILE", 4096);
-        Geom g = make_geom(kf, C, totalGroups, maxElems, nThreads);
-        size_t ldsBytes = 8 * ((size_t)g.S * K + 2 * K + 2 * (size_t)g.nbT * K);
-        while (ldsBytes > 96 * 1024 && g.nbT > 1) {
-            maxElems /= 2;
-            g = make_geom(kf, C, totalGroups, maxElems, nThreads);
-            ldsBytes = 8 * ((size_t)g.S * K + 2 * K + 2 * (size_t)g.nbT * K);
-        }
-        P.Wc = g.Wc; P.G = g.nbT; P.nColChunks = g.nColChunks;
-        const bool fixedGeom = kf == 8 && (g.S == 15 || g.S == 16) && g.by == 16 && g.nbT == 1 && !env_u32("PIL2GL_NTT_GENERIC", 0);
-        if (fixedGeom) ldsBytes += 8 * (size_t)g.S * (K / 16);
-        u32 need = (u32)((K + g.by - 1) / g.by);
-        u64 blocks = (totalGroups / g.nbT) * g.nColChunks;
-        if (blocks > 0x7fffffffull) return fail(PIL2GL_EINVAL, "grid too large");
-        dim3 grid((unsigned)blocks), block(g.S, g.by);
-#define LDE_CASE(E_)                                                                              \
-        if (need <= E_) {                                                                         \
-            P2_TRY(set_lds((const void *)lde_mid_kernel<E_, 0>, ldsBytes));                        \
-            hipLaunchKernelGGL((lde_mid_kernel<E_, 0>), grid, block, ldsBytes, st, P);             \
-        } else
-#define LDE_FIXED(S_)                                                                             \
-        if (fixedGeom && g.S == S_) {                                                             \
-            P2_TRY(set_lds((const void *)lde_mid_kernel<16, S_>, ldsBytes));                       \
-            hipLaunchKernelGGL((lde_mid_kernel<16, S_>), grid, block, ldsBytes, st, P);            \
-        } else
-        LDE_FIXED(15) LDE_FIXED(16)
-        LDE_CASE(1) LDE_CASE(2) LDE_CASE(4) LDE_CASE(8) LDE_CASE(16) LDE_CASE(32) LDE_CASE(64)
-        { return fail(PIL2GL_EINVAL, "lde tile too tall for the thread block (need %u rows per thread)", need); }
-#undef LDE_CASE
-#undef LDE_FIXED
-        KERNEL_CHECK();
-    }
-    // 3. remaining forward stages, decimation in time, bits [kf, n) from the bottom up, in place on
-    //    dst viewed as N x (C * 2^eb)
-    if (n > kf) {
-        u32 ks[32];
-        int np = split_bits(n - kf, kmaxF, ks);
-        u32 lo = kf;
-        for (int i = 0; i < np; i++) {
-            P2_TRY(launch_pass(dst, dst, C * cosetCount, n, lo, ks[i], true, false, 0, false, i == np - 1, st));
-            lo += ks[i];
+    Plan p;
+    P2_TRY(plan_lde(n, C, eb, cosetCount, coefIn, plan_options(), p));
+    const u64 N = 1ull << n;
+    const u64 *coef = src;              // what the mid kernel reads
+    u64 *tmp = work;                    // the inverse passes: src -> tmp, then in place (the caller's workspace may be src itself)
+    if (p.l[0].kind == PASS_INV_DIF && !tmp) P2_TRY(scratch(0, N * C, &tmp));
+    for (int i = 0; i < p.n; i++) {
+        const Launch &L = p.l[i];
+        if (L.kind == PASS_INV_DIF) { P2_TRY(launch_pass(L, coef, tmp, C, n, 0, st)); coef = tmp; }
+        else if (L.kind == PASS_DIT) P2_TRY(launch_pass(L, dst, dst, C * cosetCount, n, 0, st));
+        else {
+            LdeParams P;
+            P.src = coef; P.dst = dst; P.twi = tables().powWi; P.twf = tables().powW; P.twKi = tables().tw1024i; P.twKf = tables().tw1024; P.pow7 = unitShift ? nullptr : tables().pow7;
+            P.C = C; P.ninv = coefIn ? 1 : h_inv(N % 0xFFFFFFFF00000001ull); P.n = n; P.extBits = eb; P.coefIn = coefIn ? 1 : 0;
+            P.cosetBegin = cosetBegin; P.cosetCount = cosetCount;
+            P2_TRY(launch_mid(L, P, st));
         }
     }
     return PIL2GL_OK;
@@ -622,6 +677,26 @@ static int check_coset_args(const void *src, const void *dst, uint32_t nBits, ui
 }
 
 extern "C" {
+
+// test hook (host only, no device): the launches ntt_launch / lde_launch make for this call, under the environment's test hooks
+int pil2gl_debug_plan_transform(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount,
+                                uint32_t *out, uint32_t maxLaunches, uint32_t *nLaunches) {
+    if (!nLaunches || (!out && maxLaunches)) return fail(PIL2GL_EINVAL, "null argument");
+    if (op > PIL2GL_PLAN_EXTEND_COEFS) return fail(PIL2GL_EINVAL, "unknown transform %u", op);
+    if (nBits > PIL2GL_MAX_NTT_BITS || nBitsExt < nBits || nBitsExt - nBits > 31) return fail(PIL2GL_EINVAL, "nBits %u, nBitsExt %u", nBits, nBitsExt);
+    Plan p;
+    if (op <= PIL2GL_PLAN_IFFT) P2_TRY(plan_ntt(nBits, nPols, op == PIL2GL_PLAN_IFFT, plan_options(), p));
+    else P2_TRY(plan_lde(nBits, nPols, nBitsExt - nBits, cosetCount, op == PIL2GL_PLAN_EXTEND_COEFS, plan_options(), p));
+    *nLaunches = (uint32_t)p.n;
+    if ((uint32_t)p.n > maxLaunches) return fail(PIL2GL_EINVAL, "%d launches, room for %u", p.n, maxLaunches);
+    for (int i = 0; i < p.n; i++) {
+        const Launch &L = p.l[i];
+        const uint32_t r[PIL2GL_PLAN_LAUNCH_WORDS] = {L.kind, L.lo, L.k, L.g.Wc, L.g.nbT, L.g.nColChunks, L.g.S, L.g.by, L.fixedSlots, L.ept,
+                                                      L.ldsBytes, L.blocks, L.scatter, L.canonOut};
+        for (int j = 0; j < PIL2GL_PLAN_LAUNCH_WORDS; j++) out[i * PIL2GL_PLAN_LAUNCH_WORDS + j] = r[j];
+    }
+    return PIL2GL_OK;
+}
 
 int pil2gl_interpolate_dev(const uint64_t *src, uint64_t nPols, uint32_t nBits, uint64_t *dst, uint32_t nBitsExt, void *stream) {
     P2_TRY(ensure_init());

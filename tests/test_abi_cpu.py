@@ -71,6 +71,71 @@ def test_no_cpu_fallback_without_gpu():
         pil2gl.buildMerkleHash(False).merkelize(a, 1, 8)
 
 
+_PLAN_HOOKS = {"-": {}, "G1": {"PIL2GL_NTT_GENERIC": "1"}, "W0": {"PIL2GL_LDE_WIDEFWD": "0"},
+               "K4": {"PIL2GL_NTT_KMAX": "4"}, "K6": {"PIL2GL_NTT_KMAX": "6"}, "K9": {"PIL2GL_NTT_KMAX": "9"}, "K10": {"PIL2GL_NTT_KMAX": "10"}}
+
+
+def test_transform_plans_are_the_recorded_ones(monkeypatch):
+    """every launch of fft / ifft / interpolate / the extension from coefficients -- kernel instance, tile geometry, workgroup, grid, LDS
+    bytes, flags -- equals the table in tests/golden/transform_plans.txt.gz, one line per call: `hooks op nBits columns extBits cosets :
+    launch ; launch ...` (fields of a launch: include/pil2gl.h, pil2gl_debug_plan_transform; cosets 0 = the whole extension).
+    The table was recorded from the code BEFORE plan_ntt / plan_lde existed, whose launch sites wrote their parameters instead of
+    launching: 2^0..2^18, 2^20, 2^21, 2^24, 2^27, 2^30 rows x 20 widths from 1 to 200 columns x extensions by 0..3 bits and slices of 1..3
+    cosets of 8, with the test hooks unset and at each value the tests use.  Equal plans are equal kernels, grids and LDS: a change of
+    the planner that means to move a launch updates the table with it and says so."""
+    import gzip
+    import transform_plan as tp
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "transform_plans.txt.gz"), "rt") as f:
+        lines = f.read().splitlines()
+    assert len(lines) == 7 * 24 * 20 * (2 + 2 * 7)
+    seen, hooks = set(), None
+    for ln in lines:
+        head, want = ln.split(" :")
+        hook, op, nb, c, eb, cc = head.split()
+        if hook != hooks:
+            for k in ("PIL2GL_NTT_KMAX", "PIL2GL_NTT_GENERIC", "PIL2GL_LDE_WIDEFWD"):
+                monkeypatch.delenv(k, raising=False)
+            for k, v in _PLAN_HOOKS[hook].items():
+                monkeypatch.setenv(k, v)
+            hooks = hook
+        seen.add(head)
+        assert tp.line(tp.plan(op, int(nb), int(c), int(eb), int(cc))) == want.strip(), head
+    assert len(seen) == len(lines) and {h.split()[0] for h in seen} == set(_PLAN_HOOKS)
+
+
+def test_transform_plan_reaches_what_the_gpu_tests_claim(monkeypatch):
+    """the kernel families and pass sizes the GPU tests name, from the host-only plan: which shapes run fixed-geometry instances, that
+    no default plan takes a 15-slot PASS instance (rows of 15 columns are under 128 bytes: 7-stage passes) while PIL2GL_NTT_KMAX=9
+    does, and that the mid kernel only ever needs 2, 4, 8 or 16 rows per lane"""
+    import gzip
+    import transform_plan as tp
+    for k in ("PIL2GL_NTT_KMAX", "PIL2GL_NTT_GENERIC", "PIL2GL_LDE_WIDEFWD"):
+        monkeypatch.delenv(k, raising=False)
+    assert [(l.kind, l.k, l.fixed) for l in tp.plan("interpolate", 17, 100, 1)] == [("i", 5, 0), ("i", 4, 0), ("m", 8, 16), ("d", 5, 0), ("d", 4, 0)]
+    assert [(l.kind, l.k, l.fixed) for l in tp.plan("interpolate", 14, 15, 3)] == [("i", 6, 0), ("m", 8, 15), ("d", 6, 0)]
+    assert [(l.k, l.fixed, l.scatter, l.canon) for l in tp.plan("fft", 20, 100)] == [(8, 16, 0, 0), (8, 16, 0, 0), (4, 0, 1, 1)]
+    assert tp.plan("fft", 0, 5) == [] and tp.plan("interpolate", 9, 0, 1) == []
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "transform_plans.txt.gz"), "rt") as f:
+        table = [ln.split(" :") for ln in f.read().splitlines()]
+    ept, pass15 = set(), set()
+    for head, launches in table:
+        for l in filter(None, launches.strip().split(" ; ")):
+            v = l.split()
+            if v[0] == "m":
+                ept.add(int(v[9]))
+            elif v[8] == "15":
+                pass15.add(head.split()[0])
+    assert ept == {2, 4, 8, 16} and pass15 == {"K9", "K10"}
+    monkeypatch.setenv("PIL2GL_NTT_KMAX", "9")
+    assert [(l.kind, l.k, l.fixed) for l in tp.plan("fft", 8, 15)] == [("f", 8, 15)]
+    assert [(l.kind, l.k, l.fixed) for l in tp.plan("interpolate", 16, 15, 0)] == [("i", 8, 15), ("m", 8, 15), ("d", 8, 15)]
+    lib = _lib.load()
+    n = C.c_uint32()
+    assert lib.pil2gl_debug_plan_transform(0, 31, 1, 31, 0, None, 0, C.byref(n)) != 0       # beyond the largest domain
+    assert lib.pil2gl_debug_plan_transform(2, 9, 1, 8, 0, None, 0, C.byref(n)) != 0         # nBitsExt < nBits
+    assert lib.pil2gl_debug_plan_transform(4, 9, 1, 9, 0, None, 0, C.byref(n)) != 0         # no such transform
+
+
 def test_tmp_compaction_preserves_program(oracle):
     """host-side live-range renumbering of temporaries (expr.hip) must not change what the program computes"""
     import sys

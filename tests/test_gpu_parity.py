@@ -97,12 +97,20 @@ def test_interpolate(gl, oracle, nBits, nPols, extBits):
 @pytest.mark.parametrize("nBits,nPols,extBits", [(16, 30, 3), (16, 32, 1), (17, 100, 1)])
 def test_ntt_fixed_geometry_kernels(gl, oracle, nBits, nPols, extBits, monkeypatch):
     """wide matrices with 8-stage passes run kernel instances whose strides are compile-time constants (ntt_pass_kernel<.., 8>,
-    lde_mid_kernel<16, 15|16>): the oracle's result, and bit-for-bit what the any-geometry instances give"""
+    lde_mid_kernel<16, 15|16>): the oracle's result, and bit-for-bit what the any-geometry instances give.  That the two settings run
+    the two families is read from the host-only plan: fixed-geometry instances with the hook unset, none with PIL2GL_NTT_GENERIC=1"""
+    import transform_plan as tp
+    ops = ("interpolate", "fft", "ifft")
+    monkeypatch.delenv("PIL2GL_NTT_GENERIC", raising=False)
+    unset = [tp.plan(op, nBits, nPols, extBits) for op in ops]
+    tp.check_hooks({"PIL2GL_NTT_GENERIC": "0"}, ops, nBits, nPols, extBits)
     rng = np.random.default_rng(nBits * 100 + nPols)
     a = rand_field(rng, ((1 << nBits), nPols))
     want = oracle.interpolate(a, nBits, nBits + extBits)
     for generic in ("0", "1"):
         monkeypatch.setenv("PIL2GL_NTT_GENERIC", generic)
+        tp.check_hooks({"PIL2GL_NTT_GENERIC": generic}, ops, nBits, nPols, extBits)
+        assert generic == "1" or [tp.plan(op, nBits, nPols, extBits) for op in ops] == unset
         out = np.zeros(((1 << (nBits + extBits)), nPols), np.uint64)
         gl.interpolate(a, nPols, nBits, out, nBits + extBits)
         assert np.array_equal(out, want), generic
@@ -520,6 +528,7 @@ def test_transcript_list_absorption(gl, oracle):
 def test_ntt_random_shapes_and_pass_splits(gl, oracle, monkeypatch):
     """interpolate / fft / ifft on random shapes with the pass planner forced to every split it can take (PIL2GL_NTT_KMAX:
     passes of up to 4, 6, 9, 10 stages besides the default 8 / 7), i.e. every register-step chunking of gl_fermat.cuh"""
+    import transform_plan as tp
     rng = np.random.default_rng(2024)
     n_cases = 0
     while n_cases < 40:
@@ -529,6 +538,7 @@ def test_ntt_random_shapes_and_pass_splits(gl, oracle, monkeypatch):
         kmax = rng.choice(["", "4", "6", "9", "10"])
         if kmax:
             monkeypatch.setenv("PIL2GL_NTT_KMAX", str(kmax))
+            tp.check_hooks({"PIL2GL_NTT_KMAX": str(kmax)}, ("interpolate", "fft", "ifft"), nb, C, eb)     # the largest planned pass is the forced split's
         else:
             monkeypatch.delenv("PIL2GL_NTT_KMAX", raising=False)
         a = rand_field(rng, ((1 << nb), C))
@@ -1471,9 +1481,11 @@ def test_quotient_pieces_extended_from_their_coefficients(gl, oracle, nb, eb, qD
 def test_narrow_interpolate_with_wide_forward_passes(gl, oracle, wide, monkeypatch):
     """a matrix whose rows are under 128 bytes takes 7-stage passes, but its extension viewed as N x (C * cosets) is wide: the forward passes
     then take 8 stages (PIL2GL_LDE_WIDEFWD, default on; 17-26 % on narrow interpolates at 2^24 rows) -- same values either way"""
+    import transform_plan as tp
     monkeypatch.setenv("PIL2GL_LDE_WIDEFWD", wide)
     rng = np.random.default_rng(77)
     for nb, C, eb in [(15, 2, 3), (17, 6, 3), (16, 8, 2), (18, 3, 1), (14, 12, 4), (16, 1, 3)]:
+        tp.check_hooks({"PIL2GL_LDE_WIDEFWD": wide}, ("interpolate",), nb, C, eb)       # the forward side within 8 stages with "1", within 7 with "0"
         a = rand_field(rng, (1 << nb, C))
         out = np.zeros((1 << (nb + eb), C), np.uint64)
         gl.interpolate(a, C, nb, out, nb + eb)

@@ -148,22 +148,45 @@ _GENERIC = {"GENERIC": [{"PIL2GL_NTT_GENERIC": g} for g in ("0", "1")]}
 _KMAX = {"KMAX": [{}] + [{"PIL2GL_NTT_KMAX": k} for k in ("4", "6", "9", "10")]}
 _WIDEFWD = {"WIDEFWD": [{"PIL2GL_LDE_WIDEFWD": w} for w in ("1", "0")]}
 _NTT_CASES += [(nb, C, _GENERIC) for nb, C in ((16, 30), (16, 32), (17, 100))]
-_NTT_CASES += [(nb, C, _KMAX) for nb, C in ((10, 3), (12, 17), (13, 100))]
+# (9, 3): PIL2GL_NTT_KMAX=9 reaches a 9-stage tile exactly; (8, 15) and (16, 15): with 9 or 10 a 15-column matrix takes 8-stage passes, the
+# only way to the 15-slot fixed-geometry pass instances (rows of 15 columns are under 128 bytes: 7-stage passes by default)
+_NTT_CASES += [(nb, C, _KMAX) for nb, C in ((10, 3), (12, 17), (13, 100), (9, 3), (8, 15), (16, 15))]
 
 
 def _case_id(c):
     return "-".join(str(x) for x in c[:-1]) + "".join("-" + k for k in c[-1])
 
 
-def _envs(monkeypatch, switch):
+def _envs(monkeypatch, switch, ops=(), shape=()):
     """the settings a case runs under, one after the other on the same host-side construction: {} = the defaults, else the values of
-    one switch"""
+    one switch.  What the switch is there to reach -- a kernel family, a pass size -- is asserted on the host-only plan of `ops` at
+    `shape` (transform_plan.check_hooks) before the case runs under it."""
+    import transform_plan as tp
     for env in (next(iter(switch.values())) if switch else [{}]):
         for k in ("PIL2GL_NTT_KMAX", "PIL2GL_NTT_GENERIC", "PIL2GL_LDE_WIDEFWD"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
+        tp.check_hooks(env, ops, *shape)
         yield tuple(env.items())
+
+
+def test_the_kmax_cases_reach_every_forced_pass_size(monkeypatch):
+    """the planner balances its passes, so PIL2GL_NTT_KMAX=K yields a K-stage tile only where K divides the index bits (or covers them): for
+    each K the cases force, some fft case and some interpolate case plans exactly K stages; and the 15-column cases reach the 15-slot
+    fixed-geometry pass kernels, forward DIF, inverse DIF and DIT"""
+    import transform_plan as tp
+    monkeypatch.delenv("PIL2GL_NTT_GENERIC", raising=False)
+    inst = set()
+    for env in _KMAX["KMAX"][1:]:
+        K = int(env["PIL2GL_NTT_KMAX"])
+        monkeypatch.setenv("PIL2GL_NTT_KMAX", str(K))
+        assert any(max(l.k for l in tp.plan("fft", nb, C)) == K for nb, C, e in _NTT_CASES if e is _KMAX), K
+        assert any(max(l.k for l in tp.plan("interpolate", nb, C, eb)) == K for nb, C, eb, e in _LDE_CASES if e is _KMAX), K
+        for op, shape in [(op, (nb, C)) for nb, C, e in _NTT_CASES if e is _KMAX for op in ("fft", "ifft")] + \
+                         [("interpolate", (nb, C, eb)) for nb, C, eb, e in _LDE_CASES if e is _KMAX]:
+            inst |= {l.kind for l in tp.plan(op, *shape) if l.fixed == 15 and l.kind != "m"}
+    assert inst == {"f", "i", "d"}
 
 
 @pytest.mark.parametrize("nBits,C,env", _NTT_CASES, ids=[_case_id(c) for c in _NTT_CASES])
@@ -175,7 +198,7 @@ def test_fft_ifft_chosen_outputs(gl, oracle, monkeypatch, nBits, C, env):
     for name, fn, inverse_image in (("fft", gl.fft, oracle.ifft_cols), ("ifft", gl.ifft, oracle.fft_cols)):
         src = inverse_image(Y, nBits)
         assert (src < _P).all()                     # every kernel relies on canonical inputs
-        for e in _envs(monkeypatch, env):
+        for e in _envs(monkeypatch, env, (name,), (nBits, C)):
             out = np.full_like(Y, 0xDEADBEEF)
             fn(src, C, nBits, out)
             _same(out, Y, (name, "out of place", e))
@@ -208,7 +231,7 @@ _LDE_CASES = [(1, 1, 1, {}), (3, 3, 2, {}), (7, 1, 3, {}), (7, 15, 3, {}), (8, 1
               (10, 3, 3, {}), (12, 17, 2, {}), (13, 16, 0, {}), (14, 100, 1, {}), (14, 15, 3, {}),
               (21, 1, 1, {})]
 _LDE_CASES += [(nb, C, eb, _GENERIC) for nb, C, eb in ((16, 30, 3), (16, 32, 1), (17, 100, 1))]
-_LDE_CASES += [(nb, C, eb, _KMAX) for nb, C, eb in ((10, 3, 1), (12, 17, 2), (13, 100, 1))]
+_LDE_CASES += [(nb, C, eb, _KMAX) for nb, C, eb in ((10, 3, 1), (12, 17, 2), (13, 100, 1), (9, 3, 1), (16, 15, 0))]
 _LDE_CASES += [(nb, C, eb, _WIDEFWD) for nb, C, eb in ((15, 2, 3), (16, 8, 2), (16, 1, 3))]
 
 
@@ -226,7 +249,7 @@ def test_interpolate_chosen_coset(gl, oracle, monkeypatch, nb, C, eb, env):
         slices = {(j, 1), (0, nc)}
         if nc >= 2:
             slices |= {((j & ~1), 2), ((j + 1) % nc, 1)}                            # a slice that holds j beside another coset, one that does not
-        for e in _envs(monkeypatch, env):
+        for e in _envs(monkeypatch, env, ("interpolate",), (nb, C, eb)):
             out = np.full((E, C), 0xDEADBEEF, np.uint64)
             gl.interpolate(trace, C, nb, out, nb + eb)
             assert np.array_equal(out.reshape(n, nc, C)[:, j], V), ("interpolate", j, e)
@@ -267,7 +290,7 @@ def test_unshifted_and_coefficient_extensions_chosen_coset(gl, oracle, monkeypat
         slices = {(j, 1), (0, nc)}
         if nc >= 2:
             slices |= {((j & ~1), 2), ((j + 1) % nc, 1)}
-        for e in _envs(monkeypatch, env):
+        for e in _envs(monkeypatch, env, ("interpolate", "extend_coefs"), (nb, C, eb)):
             cb_ = _dev(c[br])                       # row bitrev(m) = coefficient m
             out = torch.full((C << (nb + eb),), 0xDEADBEEF, dtype=torch.int64, device="cuda")
             _lib.call("pil2gl_extend_coefs_brev_dev", gl._ptr(cb_), C, nb, gl._ptr(out), nb + eb, None)
@@ -389,7 +412,7 @@ def test_cancellation_and_magnitude_columns(gl, oracle, monkeypatch, nb, eb, env
     a = _structured(nb, nb * 7 + eb)
     C = a.shape[1]
     wf, wi, we = oracle.fft_cols(a, nb), oracle.ifft_cols(a, nb), oracle.interpolate(a, nb, nb + eb)
-    for e in _envs(monkeypatch, env):
+    for e in _envs(monkeypatch, env, ("fft", "ifft", "interpolate"), (nb, C, eb)):
         out = np.zeros_like(a)
         gl.fft(a, C, nb, out); _same(out, wf, ("fft", e))
         gl.ifft(a, C, nb, out); _same(out, wi, ("ifft", e))

@@ -1,4 +1,4 @@
-"""interpolateCosets (a rank's share of an extension) timed under the planner's environment switches (PIL2GL_NTT_KMAX, PIL2GL_NTT_TILE):
+"""interpolateCosets (a rank's share of an extension) timed, under the planner's test hook PIL2GL_NTT_KMAX if it is set:
 NBITS, NCOLS, COSETS (count, from coset 0), EXT (3)"""
 import os, sys
 import torch
@@ -24,5 +24,5 @@ for o in range(0, dst.numel(), 1 << 28):
     d = dst[o:o + (1 << 28)]
     w = torch.arange(o, o + d.numel(), dtype=torch.int64, device="cuda")
     s0 += int(d.sum()); s1 += int((d * (2 * w + 1)).sum())
-print("KMAX %s TILE %s: 2^%d x %d, %d of %d cosets: %.2f ms   checksum %016x %016x" % (os.environ.get("PIL2GL_NTT_KMAX", "-"), os.environ.get("PIL2GL_NTT_TILE", "-"), nBits, C, cc, 1 << eb, t,
-                                                                                       s0 & (2**64 - 1), s1 & (2**64 - 1)), flush=True)
+print("KMAX %s: 2^%d x %d, %d of %d cosets: %.2f ms   checksum %016x %016x" % (os.environ.get("PIL2GL_NTT_KMAX", "-"), nBits, C, cc, 1 << eb, t,
+                                                                              s0 & (2**64 - 1), s1 & (2**64 - 1)), flush=True)

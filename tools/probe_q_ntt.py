@@ -1,5 +1,5 @@
 """computeQStark's transforms at config 3 (2^24 -> 2^27, qDim 3, qDeg 2), piece by piece: the padded form (q_split + fft of 2^27 x 6) against the
-coefficient form (q_split_brev + extend_coefs_brev), and narrow interpolates with 7- and 8-stage forward passes.  gpurun -- python tools/probe_q_ntt.py"""
+coefficient form (q_split_brev + extend_coefs_brev), and narrow interpolates with 7- and 8-stage forward passes (PIL2GL_LDE_WIDEFWD)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "pil2-stark-js_amd", "python"))
