@@ -31,7 +31,7 @@
  *    stage host-side tables in a scratch slot the next call reuses:
  *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi / cols_dot_ext /
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
- *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], build_lev (small host tables),
+ *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, build_lev (small host tables),
  *      h1h2, synth_fibonacci, group_proof / group_proofs and bn128_group_proof (openings copied to host memory),
  *      land_rows with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
@@ -238,6 +238,21 @@ int pil2gl_build_frame_zerofier_dev(uint32_t nBits, uint32_t nBitsExt, uint64_t 
 int pil2gl_compute_q_split_dev(const uint64_t *qq1, uint32_t nBits, uint32_t nBitsExt, uint32_t qDim, uint32_t qDeg, uint64_t *qq2, void *stream);
 /* the same pieces as the 2^nBits-row coefficient matrix alone, row bitrev(i) = coefficient i: coefBrev[bitrev(i)][p*qDim+k] = qq1[p*N+i][k] * (7^-N)^p */
 int pil2gl_compute_q_split_brev_dev(const uint64_t *qq1, uint32_t nBits, uint32_t nBitsExt, uint32_t qDim, uint32_t qDeg, uint64_t *coefBrev, void *stream);
+/* The quotient stage in one call (stark_gen_helpers.js:168-208): the constraint program, ifft, the split above and
+ * pil2gl_extend_coefs_brev_dev; dstExt = 2^nBitsExt x (qDim*qDeg), the quotient stage's extended matrix.
+ * ctx is the "ext" context of pil2gl_eval_program_dev (nBits = nBitsExt, primeShift = nBitsExt - nBits, every section a 2^nBitsExt-row
+ * matrix); qSection is the section the program writes (width qDim): its ptr is ignored and may be NULL, the values live in the
+ * library's scratch.  The program runs on the extended rows k * 2^s only, s = nBitsExt - nBits - ceil(log2 qDeg): deg Q < qDeg * N, so
+ * those 2^(nBitsExt - s) values fix Q, and their inverse transform equals the first 2^(nBitsExt - s) rows of the full one word for word.
+ * The evaluator sees a context of 2^(nBitsExt - s) rows whose sections have a row pitch of width * 2^s (same choice of kernel, same
+ * optimiser); s = 0 is the full domain.  PIL2GL_EINVAL, before anything is launched or written: qDeg * 2^nBits > 2^nBitsExt, a program
+ * that writes another section, a row offset that leaves the rows k * 2^s (none does when primeShift = nBitsExt - nBits).
+ * For a SATISFIED AIR the result equals the full-domain sequence bit for bit.  For a witness that breaks a constraint Q has
+ * coefficients above qDeg * N: the full-domain sequence drops them, this call folds them onto the low ones -- different matrices,
+ * and neither proof verifies.  Constraint checking (calculateExps with debug) stays on the full domain.
+ * Blocks like eval_program and compute_q_split_brev, whose host tables it stages; the extension is only enqueued. */
+int pil2gl_compute_q_stark_dev(const glx_program *prog, const glx_ctx *ctx, uint32_t qSection, uint32_t nBits, uint32_t nBitsExt,
+                               uint32_t qDim, uint32_t qDeg, uint64_t *dstExt, void *stream);
 /* computeFRIStark xDivXSubXi  stark_gen_helpers.js:293-322: out[3*(k*nOpen+iOpen)+c] = (x_k / (x_k - xi))_c, x_k = 7 w_E^k.
  * A base-field xi = (7 w_E^k, 0, 0) is a row of the table: the reference throws "Division by zero" there (F.batchInverse), and
  * both forms return PIL2GL_EINVAL before anything is launched or written, whichever cosets are asked for. */

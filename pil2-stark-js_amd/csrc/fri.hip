@@ -422,6 +422,49 @@ int pil2gl_compute_q_split_brev_dev(const uint64_t *qq1, uint32_t nBits, uint32_
     HIP_TRY(hipStreamSynchronize(as_stream(stream)));
     return PIL2GL_OK;
 }
+// The whole quotient stage (stark_gen_helpers.js:168-208): constraint program, inverse transform, split, extension of the pieces.
+// Q has degree < qDeg * N <= M = 2^m, m = nBits + ceil(log2 qDeg), so its values on the M extended rows k * 2^s, s = nBitsExt - m --
+// the coset 7 <w_E^(2^s)> = 7 <w_M> -- fix it: the size-M inverse transform of those values is c_j 7^j, j < M, word for word the first M
+// rows of the size-2^nBitsExt inverse transform of all the values, and the split reads no row beyond qDeg * N.  So the program runs on
+// that sub-domain only.  To the evaluator the sub-domain is an ordinary context: 2^m rows, a source section's row pitch width * 2^s
+// given as its width (column offsets stay below the true width), row offsets prime << (primeShift - s), the destination a compact
+// 2^m x qDim scratch.  s = 0 is the full domain through the same code.
+// (Holds for a satisfied AIR.  A witness that breaks a constraint gives Q coefficients above qDeg * N; the full-domain path drops them,
+// this one folds them onto the low ones: two different proofs, neither of which verifies.)
+int pil2gl_compute_q_stark_dev(const glx_program *prog, const glx_ctx *ctx, uint32_t qSection, uint32_t nBits, uint32_t nBitsExt,
+                               uint32_t qDim, uint32_t qDeg, uint64_t *dstExt, void *stream) {
+    P2_TRY(ensure_init());
+    if (!prog || !ctx || !dstExt || (prog->nOps && !prog->ops) || (ctx->nSections && !ctx->sections)) return fail(PIL2GL_EINVAL, "null argument");
+    if (nBitsExt < nBits || nBitsExt > PIL2GL_MAX_NTT_BITS || !qDim || !qDeg || ((u64)qDeg << nBits) > (1ull << nBitsExt)) return fail(PIL2GL_EINVAL, "bad q stage arguments");
+    if (ctx->nBits != nBitsExt) return fail(PIL2GL_EINVAL, "the context has 2^%u rows, the extended domain 2^%u", ctx->nBits, nBitsExt);
+    if (qSection >= ctx->nSections || ctx->sections[qSection].width != qDim) return fail(PIL2GL_EINVAL, "section %u is not a destination of %u columns", qSection, qDim);
+    u32 m = nBits;
+    while ((1ull << m) < ((u64)qDeg << nBits)) m++;
+    const u32 s = nBitsExt - m;
+    for (u32 k = 0; k < prog->nOps; k++) {
+        const glx_op &o = prog->ops[k];
+        if (o.dest.kind == GLX_SEC && o.dest.section != qSection) return fail(PIL2GL_EINVAL, "op %u writes section %u, not the quotient's", k, o.dest.section);
+        for (int t = 0; t < 3; t++) {                   // a row offset must stay inside the sub-domain: prime << primeShift a multiple of 2^s
+            const glx_ref &r = t < 2 ? o.src[t] : o.dest;
+            if (r.kind == GLX_SEC && r.prime != 0 && ctx->primeShift < s && !(t == 1 && o.op == GLX_OP_COPY))
+                return fail(PIL2GL_EINVAL, "op %u: row offset %d << %u leaves the rows k * 2^%u", k, r.prime, ctx->primeShift, s);
+        }
+    }
+    for (u32 i = 0; i < ctx->nSections; i++) if (i != qSection && (ctx->sections[i].width << s) >> 32) return fail(PIL2GL_EINVAL, "section %u too wide", i);
+    const u64 M = 1ull << m, W = (u64)qDim * qDeg;
+    u64 *q, *coef;
+    P2_TRY(scratch(14, M * qDim, &q));
+    P2_TRY(scratch(15, W << nBits, &coef));
+    std::vector<glx_section> secs(ctx->sections, ctx->sections + ctx->nSections);
+    for (u32 i = 0; i < ctx->nSections; i++) secs[i].width <<= s;
+    secs[qSection].ptr = q; secs[qSection].width = qDim;
+    glx_ctx sub = *ctx;
+    sub.nBits = m; sub.primeShift = ctx->primeShift < s ? 0 : ctx->primeShift - s; sub.sections = secs.data();
+    P2_TRY(pil2gl_eval_program_dev(prog, &sub, stream));
+    P2_TRY(ntt_launch(q, qDim, m, q, true, as_stream(stream)));
+    P2_TRY(pil2gl_compute_q_split_brev_dev(q, nBits, nBitsExt, qDim, qDeg, coef, stream));
+    return lde_launch(coef, W, nBits, dstExt, nBitsExt, as_stream(stream), 0, 0, nullptr, true, true);
+}
 // (xi0, xi1, xi2) with xi1 = xi2 = 0 and (xi0 / 7)^(2^nBitsExt) = 1: the point is 7 w_E^k for some row k (no extension element outside the
 // base field solves x^E = 1).  Shared by the table, which refuses such a point, and by LEv, which must not reach the table with one.
 static bool base_point_is_a_row(u64 xi0, u64 xi1, u64 xi2, u32 nBitsExt) {
