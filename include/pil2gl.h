@@ -32,9 +32,13 @@
  *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi / cols_dot_ext /
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
  *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, build_lev (small host tables),
- *      h1h2, synth_fibonacci, group_proof / group_proofs and bn128_group_proof (openings copied to host memory),
+ *      h1h2, synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
  *      land_rows with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
+ *    So do the host-pointer verifier calls roots_from_group_proofs and bn128_roots_from_group_proofs (roots copied to host memory).
+ *    bn128_group_proof[s]_dev take no stream: their copies and their gather kernel run on the NULL stream, which orders them after work
+ *    on BLOCKING streams only (the NULL stream itself, streams created with hipStreamDefault).  A tree built on a stream created
+ *    hipStreamNonBlocking is not ordered against them: synchronise that stream first (pil2gl_sync).
  *    A whole config-3 proof keeps the GPU busy 99.3 % of its wall time with these.
  *  - Every function returns 0 on success, a negative PIL2GL_E* code otherwise;
  *    pil2gl_last_error() describes the failure (the reference throws Error /
@@ -358,6 +362,20 @@ int pil2gl_bn128_group_proof_dev(const uint64_t *elems, const uint64_t *nodes, u
  * nIdx x levels x arity field elements (4 words each, normal form), *nLevels = levels. */
 int pil2gl_bn128_group_proofs_dev(const uint64_t *elems, const uint64_t *nodes, uint64_t width, uint64_t height, uint32_t arity,
                                   const uint64_t *hostIdxs, uint32_t nIdx, uint64_t *hostVals, uint64_t *hostSiblings, uint32_t *nLevels);
+/* verifier side: MerkleHash.calculateRootFromGroupProof  merklehash_bn128_p.js:184-232 with LinearHashBN.hash (linearhash.bn128.js:13-59)
+ * for a batch of nIdx openings of one tree shape, all host pointers: hostVals nIdx x width Goldilocks words, hostSiblings nIdx x levels x
+ * arity field elements (4 words each), hostRoots[q] = the root the path of leaf hostIdxs[q] leads to, normal form; verifyGroupProof
+ * :234-237 is the comparison with the root.  Per opening: 3 words packed per element (the last may hold 1 or 2), no element -> 0, one ->
+ * itself, else the sponge over chunks of `arity` (a short last chunk at t = nLast+1, or zero-padded when custom); per level the group of
+ * `arity` siblings with position idx & (arity-1) replaced by the running value (what the proof holds there is not read), state 0, then
+ * idx >>= log2(arity).  levels = 0 returns the leaf value.  Sibling words are any value < 2^256, reduced mod r (:218).
+ * siblingsMontgomery = 1: the sibling words are in Montgomery form, as tree.nodes holds them (pil2gl_bn128_convert of what
+ * pil2gl_bn128_group_proofs_dev returns, or a level's nodes read directly), so a prover can check openings against its own tree without
+ * leaving that form; 0: normal form, as the group-proof entries above write them and as a proof carries them.
+ * One launch for the whole batch, a wave per opening (csrc/bn128.hip bn_path_roots_kernel); blocks until the roots are on the host.
+ * PIL2GL_EINVAL: arity not in {2,4,8,16}, levels > 40, a null buffer that would be read with nIdx > 0; nIdx = 0 is PIL2GL_OK. */
+int pil2gl_bn128_roots_from_group_proofs(const uint64_t *hostVals, const uint64_t *hostSiblings, uint64_t width, uint32_t levels, uint32_t arity,
+                                         int custom, int siblingsMontgomery, const uint64_t *hostIdxs, uint32_t nIdx, uint64_t *hostRoots /* nIdx x 4 */);
 /* n elements between normal and Montgomery form (F.e / F.toObject); the host form is plain host arithmetic */
 int pil2gl_bn128_convert(const uint64_t *in, uint64_t n, int toMontgomery, uint64_t *out);
 int pil2gl_bn128_convert_dev(const uint64_t *in, uint64_t n, int toMontgomery, uint64_t *out, void *stream);
@@ -386,6 +404,9 @@ int pil2gl_debug_jit_compile(const glx_program *prog, const glx_ctx *ctx, uint64
 /* host-only: the program as pil2gl_eval_program_dev optimises it for this context, Horner fusion included: outInfo[0] = temporary
  * slots (what the choice between the compiled kernel and the two interpreter forms reads), [1] = ops, [2] = fused Horner terms */
 int pil2gl_debug_plan_program(const glx_program *prog, const glx_ctx *ctx, uint32_t *outInfo);
+/* host-only: how many times this process has launched the one-launch BN128 path kernel (pil2gl_bn128_roots_from_group_proofs); the tests
+ * assert that a batch of openings went through it, once, and not through a permutation call per chunk and level */
+uint64_t pil2gl_debug_bn128_path_launches(void);
 /* host-only, no device: the kernel launches fft / ifft / interpolate / the extension from coefficients make for 2^nBits rows x nPols
  * columns (the two extensions: onto cosetCount of the 2^(nBitsExt - nBits) cosets, 0 = all; fft / ifft ignore both), as the
  * transforms plan them under the environment's test hooks (PIL2GL_NTT_KMAX, PIL2GL_NTT_GENERIC, PIL2GL_LDE_WIDEFWD).

@@ -378,6 +378,27 @@ FN(Bn128MerkelizeDev) { // (devElems, width, height, arity, custom, devNodes)
     Args a(env, info); uint64_t el = a.u64(0), w = a.u64(1), h = a.u64(2), arity = a.u64(3); int custom = (int)a.u64(4); uint64_t nodes = a.u64(5); if (!a.ok) return nullptr;
     P2(env, pil2gl_bn128_merkelize_dev((const uint64_t *)(uintptr_t)el, w, h, (uint32_t)arity, custom, (uint64_t *)(uintptr_t)nodes, a.stream(6))); return mk_undefined(env);
 }
+static uint32_t bn128_levels(uint64_t h, uint64_t arity) { uint32_t nl = 0; if (arity >= 2) for (uint64_t n = h; n > 1; n = (n - 1) / arity + 1) nl++; return nl; }
+FN(Bn128GroupProofDev) {  // (devElems, devNodes, width, height, arity, idx, vals BigUint64Array(width), siblings BigUint64Array(levels*arity*4) normal form) -> nLevels
+    Args a(env, info); uint64_t el = a.u64(0), nodes = a.u64(1), w = a.u64(2), h = a.u64(3), arity = a.u64(4), idx = a.u64(5);
+    uint64_t *vals = a.arr(6, w), *sib = a.arr(7, 4ull * arity * bn128_levels(h, arity)); if (!a.ok) return nullptr;
+    uint32_t nl = 0;
+    P2(env, pil2gl_bn128_group_proof_dev((const uint64_t *)(uintptr_t)el, (const uint64_t *)(uintptr_t)nodes, w, h, (uint32_t)arity, idx, vals, sib, &nl));
+    napi_value v; napi_create_uint32(env, nl, &v); return v;
+}
+FN(Bn128GroupProofsDev) { // (devElems, devNodes, width, height, arity, idxs BigUint64Array(n), vals BigUint64Array(n*width), siblings BigUint64Array(n*levels*arity*4)) -> nLevels: one gather
+    Args a(env, info); uint64_t el = a.u64(0), nodes = a.u64(1), w = a.u64(2), h = a.u64(3), arity = a.u64(4);
+    uint64_t n = 0; uint64_t *idxs = a.arr(5, 1, &n); if (!a.ok) return nullptr;
+    uint64_t *vals = a.arr(6, n * w), *sib = a.arr(7, n * 4ull * arity * bn128_levels(h, arity)); if (!a.ok) return nullptr;
+    uint32_t nl = 0;
+    P2(env, pil2gl_bn128_group_proofs_dev((const uint64_t *)(uintptr_t)el, (const uint64_t *)(uintptr_t)nodes, w, h, (uint32_t)arity, idxs, (uint32_t)n, vals, sib, &nl));
+    napi_value v; napi_create_uint32(env, nl, &v); return v;
+}
+FN(Bn128RootsFromGroupProofs) {  // (vals BigUint64Array(n*width), siblings BigUint64Array(n*levels*arity*4), width, levels, arity, custom, siblingsMontgomery, idxs BigUint64Array(n), n, roots BigUint64Array(4n))
+    Args a(env, info); uint64_t w = a.u64(2), lv = a.u64(3), arity = a.u64(4), n = a.u64(8); int custom = (int)a.u64(5), mont = (int)a.u64(6);
+    uint64_t *vals = a.arr(0, n * w), *sib = a.arr(1, n * lv * arity * 4), *idx = a.arr(7, n), *roots = a.arr(9, 4 * n); if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_roots_from_group_proofs(vals, sib, w, (uint32_t)lv, (uint32_t)arity, custom, mont, idx, (uint32_t)n, roots)); return mk_undefined(env);
+}
 FN(Bn128Convert) {   // (in BigUint64Array(4n), n, toMontgomery, out)
     Args a(env, info); uint64_t n = a.u64(1); int toM = (int)a.u64(2);
     uint64_t *in = a.arr(0, 4 * n), *out = a.arr(3, 4 * n); if (!a.ok) return nullptr;
@@ -467,7 +488,8 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "merkleNumNodes", MerkleNumNodes }, { "merkelize", Merkelize }, { "merkelizeDev", MerkelizeDev }, { "groupProofDev", GroupProofDev }, { "groupProofsDev", GroupProofsDev },
         { "rootsFromGroupProofs", RootsFromGroupProofs }, { "spongeAbsorb", SpongeAbsorb },
         { "bn128Poseidon", Bn128Poseidon }, { "bn128SpongeAbsorb", Bn128SpongeAbsorb }, { "bn128LinearHashRows", Bn128LinearHashRows }, { "bn128MerkleNumNodes", Bn128MerkleNumNodes },
-        { "bn128Merkelize", Bn128Merkelize }, { "bn128MerkelizeDev", Bn128MerkelizeDev }, { "bn128Convert", Bn128Convert },
+        { "bn128Merkelize", Bn128Merkelize }, { "bn128MerkelizeDev", Bn128MerkelizeDev }, { "bn128GroupProofDev", Bn128GroupProofDev }, { "bn128GroupProofsDev", Bn128GroupProofsDev },
+        { "bn128RootsFromGroupProofs", Bn128RootsFromGroupProofs }, { "bn128Convert", Bn128Convert },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

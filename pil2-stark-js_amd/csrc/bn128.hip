@@ -1138,6 +1138,56 @@ __global__ void __launch_bounds__(BN_THREADS) __attribute__((amdgpu_waves_per_eu
 // in and out.  Measured at t = 17: 3.1 ms per permutation for a call per block, 0.76 ms with one lane per row (issue-bound
 // on its 17 multiply-accumulates per round; requesting operands a term ahead changes nothing), 0.49 ms with the row split.
 constexpr int CHAIN_SUB = 3;
+// One permutation of that form, a device function so that a kernel can run permutations of DIFFERENT widths one after the other (a Merkle
+// path: the sponge's full chunks, its short last chunk, the levels): lane (l, sub) of the CHAIN_SUB*t active ones enters and leaves with
+// state element l in x (Montgomery form); A supplies Cd, M and rp of width t.  sh: 17*8 words, part: CHAIN_SUB*17*17 words of the wave's LDS.
+__device__ __forceinline__ void chain_perm(u32 (&x)[8], const PermArgs &A, int t, int l, int sub, bool act, lds_u32 sh, lds_u32 part) {
+    const int nRounds = N_ROUNDS_F + A.rp;
+    for (int r = 0; r < nRounds; r++) {
+        u32 c[8];
+        load_const(A.Cd, (size_t)r * t + l, c);
+        bn::fr_add(x, c);
+        const bool full = r < N_ROUNDS_F / 2 || r >= N_ROUNDS_F / 2 + A.rp;
+        if (full || l == 0) pow5(x);
+        if (act && sub == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) sh[l * 8 + i] = x[i];
+        }
+        __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0): this wave's LDS writes have landed
+        __builtin_amdgcn_wave_barrier();
+        u32 acc[17];
+#pragma unroll
+        for (int i = 0; i < 17; i++) acc[i] = 0;
+        for (int j = sub; j < t; j += CHAIN_SUB) {
+            u32 y[8], m[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) y[i] = sh[j * 8 + i];
+            load_const(A.M, (size_t)l * t + j, m);
+            bn::mac17(acc, y, m);
+        }
+        if (act) {
+#pragma unroll
+            for (int i = 0; i < 17; i++) part[(sub * 17 + l) * 17 + i] = acc[i];
+        }
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
+        // every copy adds the three partial sums (together at most t products: they fit the 17 limbs as one row did)
+#pragma unroll
+        for (int i = 0; i < 17; i++) acc[i] = part[l * 17 + i];
+#pragma unroll
+        for (int q = 1; q < CHAIN_SUB; q++) {
+            u64 cy = 0;
+#pragma unroll
+            for (int i = 0; i < 17; i++) {
+                const u64 v = (u64)acc[i] + part[(q * 17 + l) * 17 + i] + cy;
+                acc[i] = (u32)v; cy = v >> 32;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        bn::redc17(x, acc);
+    }
+}
+
 // One workgroup (one wave) per chain: chain g reads nBlocks*nIn elements at blocks + g*nBlocks*nIn*4, state element 0 from
 // init + 4g (zero if init is null), and writes its first nOut outputs at out + g*nOut*4 -- with nBlocks = 1 this is a batch of
 // independent permutations, the faster form while there are fewer of them than SIMDs to give a whole wave each.
@@ -1165,52 +1215,9 @@ __global__ void __launch_bounds__(64) bn_sponge_chain_kernel(const u64 *__restri
         } else bn::fr_mul(x, v, r2);
     };
     if (l == 0) load_mont(init ? init : zero4);
-    const int nRounds = N_ROUNDS_F + A.rp;
     for (u64 b = 0; b < nBlocks; b++) {
         if (l > 0) load_mont(blocks + (b * nIn + (l - 1)) * 4);
-        for (int r = 0; r < nRounds; r++) {
-            u32 c[8];
-            load_const(A.Cd, (size_t)r * t + l, c);
-            bn::fr_add(x, c);
-            const bool full = r < N_ROUNDS_F / 2 || r >= N_ROUNDS_F / 2 + A.rp;
-            if (full || l == 0) pow5(x);
-            if (act && sub == 0) {
-#pragma unroll
-                for (int i = 0; i < 8; i++) sh[l * 8 + i] = x[i];
-            }
-            __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0): this wave's LDS writes have landed
-            __builtin_amdgcn_wave_barrier();
-            u32 acc[17];
-#pragma unroll
-            for (int i = 0; i < 17; i++) acc[i] = 0;
-            for (int j = sub; j < t; j += CHAIN_SUB) {
-                u32 y[8], m[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) y[i] = sh[j * 8 + i];
-                load_const(A.M, (size_t)l * t + j, m);
-                bn::mac17(acc, y, m);
-            }
-            if (act) {
-#pragma unroll
-                for (int i = 0; i < 17; i++) part[(sub * 17 + l) * 17 + i] = acc[i];
-            }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_wave_barrier();
-            // every copy adds the three partial sums (together at most t products: they fit the 17 limbs as one row did)
-#pragma unroll
-            for (int i = 0; i < 17; i++) acc[i] = part[l * 17 + i];
-#pragma unroll
-            for (int q = 1; q < CHAIN_SUB; q++) {
-                u64 cy = 0;
-#pragma unroll
-                for (int i = 0; i < 17; i++) {
-                    const u64 v = (u64)acc[i] + part[(q * 17 + l) * 17 + i] + cy;
-                    acc[i] = (u32)v; cy = v >> 32;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-            bn::redc17(x, acc);
-        }
+        chain_perm(x, A, t, l, sub, act, (lds_u32)sh, (lds_u32)part);
     }
     if (!act || sub != 0 || l >= nOut) return;
     u32 one[8] = { 1, 0, 0, 0, 0, 0, 0, 0 }, o[8];
@@ -1220,6 +1227,83 @@ __global__ void __launch_bounds__(64) bn_sponge_chain_kernel(const u64 *__restri
     } else bn::fr_mul(o, x, one);                    // out of Montgomery form
 #pragma unroll
     for (int q = 0; q < 4; q++) out[l * 4 + q] = (u64)o[2 * q] | ((u64)o[2 * q + 1] << 32);
+}
+
+// MerkleHash.calculateRootFromGroupProof (merklehash_bn128_p.js:184-232, LinearHashBN.hash linearhash.bn128.js:13-59) for a batch of openings,
+// the whole path of one opening in one wave: a verifier's batch is queries x trees, fewer chains than the chip has SIMDs, and every
+// permutation of a path waits for the one before it -- the shape of the chain kernel above, with the width changing from step to step.
+// Steps: the sponge over the row's elements (3 Goldilocks words packed per element; full chunks at t = arity+1 carrying output 0 as state
+// element 0, a short last chunk at t = nLast+1 through `last`, or zero-padded when custom), then one permutation per level at t = arity+1
+// over the level's siblings with the running value at position idx & (arity-1) (whatever the proof holds there is not read) and state 0.
+// Between two steps the running value is lane 0's x (lane 0 is (l, sub) = (0, 0) at every width), read by every lane as a wave-uniform value.
+// vals: nIdx x width words; sib: nIdx x levels x arity x 4 words, normal form (any value < 2^256: reduced by the conversion) or, sibMont,
+// Montgomery words as tree.nodes holds them; roots: nIdx x 4 words, normal form.
+__global__ void __launch_bounds__(64) bn_path_roots_kernel(const u64 *__restrict__ vals, const u64 *__restrict__ sib, const u64 *__restrict__ idxs,
+                                                          u64 width, int levels, int arity, int abits, int custom, int sibMont,
+                                                          PermArgs full, PermArgs last, u64 *__restrict__ roots) {
+    __shared__ u32 sh[17 * 8];
+    __shared__ u32 part[CHAIN_SUB * 17 * 17];
+    const int lane = threadIdx.x;
+    vals += (u64)blockIdx.x * width;
+    sib += (u64)blockIdx.x * (u64)levels * arity * 4;
+    u64 pos = idxs[blockIdx.x];
+    u32 r2[8], x[8];
+    const u32 one[8] = { 1, 0, 0, 0, 0, 0, 0, 0 };
+#pragma unroll
+    for (int i = 0; i < 8; i++) { r2[i] = bn::r2_limb(i); x[i] = 0; }
+    const u64 nEl = (width + 2) / 3;
+    auto load_elem = [&](u64 e) {                    // linearhash.bn128.js:27-38: x + y 2^64 + z 2^128 (< r: the % is the identity), to Montgomery form
+        u32 v[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+        for (int q = 0; q < 3; q++) { const u64 k = 3 * e + q; if (k < width) { const u64 w = vals[k]; v[2 * q] = (u32)w; v[2 * q + 1] = (u32)(w >> 32); } }
+        bn::fr_mul(x, v, r2);
+    };
+    if (nEl == 1) load_elem(0);                      // :41: one element is its own hash (none: 0)
+    const int nChunks = nEl < 2 ? 0 : (int)((nEl + (u64)arity - 1) / (u64)arity);
+    for (int s = 0; s < nChunks + levels; s++) {
+        u32 run[8];                                  // the value so far: the sponge's state element 0, a level's own child
+#pragma unroll
+        for (int i = 0; i < 8; i++) run[i] = (u32)__builtin_amdgcn_readlane((int)x[i], 0);
+        const bool level = s >= nChunks;
+        const u64 e0 = (u64)s * arity;
+        const int n = level || nEl - e0 >= (u64)arity ? arity : (int)(nEl - e0);
+        const bool shortLast = n < arity && !custom;
+        const int t = shortLast ? n + 1 : arity + 1;
+        const bool act = lane < CHAIN_SUB * t;
+        const int sub = act ? lane / t : 0, l = act ? lane - sub * t : 0;
+        const int cur = (int)(pos & (u64)(arity - 1));
+#pragma unroll
+        for (int i = 0; i < 8; i++) x[i] = 0;        // a level's state element 0; the zero padding of a custom last chunk
+        if (!level) {
+            if (l == 0) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) x[i] = run[i];
+            } else if (l - 1 < n) load_elem(e0 + (u64)(l - 1));
+        } else if (l > 0) {
+            if (l - 1 == cur) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) x[i] = run[i];
+            } else {
+                const u64 *w = sib + ((u64)(s - nChunks) * arity + (u64)(l - 1)) * 4;
+                u32 v[8], m[8];
+#pragma unroll
+                for (int q = 0; q < 4; q++) { v[2 * q] = (u32)w[q]; v[2 * q + 1] = (u32)(w[q] >> 32); }
+                bn::fr_mul(m, v, r2);                // v 2^256 mod r, canonical for every v < 2^256 (merklehash_bn128_p.js:218: % R)
+                if (sibMont) bn::fr_mul(x, m, one);  // v was the Montgomery word already: back to it, reduced
+                else {
+#pragma unroll
+                    for (int i = 0; i < 8; i++) x[i] = m[i];
+                }
+            }
+        }
+        if (level) pos >>= abits;
+        if (shortLast) chain_perm(x, last, t, l, sub, act, (lds_u32)sh, (lds_u32)part);
+        else chain_perm(x, full, t, l, sub, act, (lds_u32)sh, (lds_u32)part);
+    }
+    if (lane != 0) return;
+    u32 o[8];
+    bn::fr_mul(o, x, one);                           // out of Montgomery form
+#pragma unroll
+    for (int q = 0; q < 4; q++) roots[(u64)blockIdx.x * 4 + q] = (u64)o[2 * q] | ((u64)o[2 * q + 1] << 32);
 }
 
 // Montgomery <-> normal form of n elements (frm_toMontgomery / F.toObject)
@@ -1449,6 +1533,45 @@ int pil2gl_bn128_group_proofs_dev(const uint64_t *elems, const uint64_t *nodes, 
     }
     *nLevels = L.levels;
     return PIL2GL_OK;
+}
+
+// calculateRootFromGroupProof (merklehash_bn128_p.js:184-232) for a batch of openings of one tree shape: one copy in, ONE launch (a wave per
+// opening walks its whole path: bn_path_roots_kernel), one copy out
+static uint64_t g_path_launches = 0;
+uint64_t pil2gl_debug_bn128_path_launches(void) { return g_path_launches; }
+
+int pil2gl_bn128_roots_from_group_proofs(const uint64_t *hostVals, const uint64_t *hostSiblings, uint64_t width, uint32_t levels, uint32_t arity, int custom,
+                                         int siblingsMontgomery, const uint64_t *hostIdxs, uint32_t nIdx, uint64_t *hostRoots) {
+    P2_TRY(ensure_init());
+    P2_TRY(check_arity(arity));
+    if (levels > 40) return fail(PIL2GL_EINVAL, "too many levels");
+    if (!nIdx) return PIL2GL_OK;
+    if (!hostIdxs || !hostRoots || (width && !hostVals) || (levels && !hostSiblings)) return fail(PIL2GL_EINVAL, "null buffer");
+    uint32_t nbits = 0; while ((1u << nbits) < arity) nbits++;
+    const Params *pf, *pl;
+    P2_TRY(get_params((int)arity + 1, &pf));
+    pl = pf;
+    const uint64_t nEl = (width + 2) / 3, nLast = nEl % arity;
+    if (nEl > 1 && !custom && nLast) P2_TRY(get_params((int)nLast + 1, &pl));
+    const u64 nV = (u64)nIdx * width, nS = (u64)nIdx * levels * arity * 4, nO = (u64)nIdx * 4;
+    u64 *d = nullptr; bool owned = false;
+    P2_TRY(stage_acquire(nV + nS + nIdx + nO, &d, &owned));
+    u64 *dSib = d + nV, *dIdx = dSib + nS, *dRoots = dIdx + nIdx;
+    int rc = PIL2GL_OK;
+    hipError_t e = nV ? hipMemcpy(d, hostVals, nV * 8, hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess && nS) e = hipMemcpy(dSib, hostSiblings, nS * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dIdx, hostIdxs, (u64)nIdx * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D");
+    if (rc == PIL2GL_OK) {
+        bn_path_roots_kernel<<<nIdx, 64>>>(d, dSib, dIdx, width, (int)levels, (int)arity, (int)nbits, custom ? 1 : 0, siblingsMontgomery ? 1 : 0,
+                                           perm_args(pf), perm_args(pl), dRoots);
+        g_path_launches++;
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(hostRoots, dRoots, nO * 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "bn_path_roots_kernel");
+    }
+    stage_release(d, owned);
+    return rc;
 }
 
 // ---- host-pointer forms ----

@@ -2,10 +2,12 @@
 // merkelize / getElement / getGroupProof / calculateRootFromGroupProof / verifyGroupProof / eqRoot / root /
 // writeToFile / readFromFile (merklehash_bn128_p.js:10-285).  tree.nodes is a BigUint64Array of Montgomery-form field
 // elements (4 words each) laid out as the reference's (:31-45, :89-101); roots and siblings are BigInt in normal form.
+// Handed a DevBuffer, merkelize builds the tree next to its leaves and leaves it in HBM (tree.nodes is a DevBuffer too), as the
+// Goldilocks module does: openings are then one device call per tree (getGroupProofs), the root is the only node that is downloaded.
 // The reference obtains its permutation from circomlibjs / wasmcurves; here it is libpil2gl's (csrc/bn128.hip).
 "use strict";
 const fs = require("fs");
-const { addon, isFlat, DevBuffer, upload } = require("./native.js");
+const { addon, isFlat, isDev, DevBuffer, upload } = require("./native.js");
 
 const R = 21888242871839275222246405745257275088548364400416034343698204186575808495617n;
 const M64 = 0xFFFFFFFFFFFFFFFFn;
@@ -84,6 +86,11 @@ class MerkleHash {
     _getNNodes(n) { return addon.bn128MerkleNumNodes(n, this.arity); }      // merklehash_bn128_p.js:31-45
 
     async merkelize(buff, width, height) {
+        if (isDev(buff)) {          // resident: the tree is built next to its leaves and stays there
+            const nodes = new DevBuffer(this._getNNodes(height) * 4);
+            addon.bn128MerkelizeDev(buff.ptr, width, height, this.arity, this.custom ? 1 : 0, nodes.ptr);
+            return { elements: buff, nodes, width, height };
+        }
         const tree = { elements: buff, nodes: new BigUint64Array(this._getNNodes(height) * 4), width, height };
         if (isFlat(buff)) {
             addon.bn128Merkelize(buff, width, height, this.arity, this.custom ? 1 : 0, tree.nodes);
@@ -108,8 +115,21 @@ class MerkleHash {
         return isFlat(e) ? e[tree.width * idx + subIdx] : e.getElement(tree.width * idx + subIdx);
     }
 
+    _nLevels(height) { let nl = 0; for (let n = height; n > 1; n = Math.floor((n - 1) / this.arity) + 1) nl++; return nl; }
+    // siblings: nLevels x arity field elements (4 words each, normal form) from word offset o -> the reference's array of levels
+    _levels(sib, o, nl) {
+        const mp = [];
+        for (let l = 0; l < nl; l++) { const g = []; for (let i = 0; i < this.arity; i++) g.push(fromWords(sib, o / 4 + l * this.arity + i)); mp.push(g); }
+        return mp;
+    }
+
     getGroupProof(tree, idx) {          // merklehash_bn128_p.js:142-182
         if ((idx < 0) || (idx >= tree.height)) throw new Error("Out of range");
+        if (isDev(tree.elements) && isDev(tree.nodes)) {        // only the opened row and its groups cross PCIe
+            const nl = this._nLevels(tree.height), vals = new BigUint64Array(Math.max(1, tree.width)), sib = new BigUint64Array(Math.max(1, nl * this.arity * 4));
+            addon.bn128GroupProofDev(tree.elements.ptr, tree.nodes.ptr, tree.width, tree.height, this.arity, idx, vals, sib);
+            return [Array.from(vals.subarray(0, tree.width)), this._levels(sib, 0, nl)];
+        }
         const v = new Array(tree.width);
         for (let i = 0; i < tree.width; i++) v[i] = this.getElement(tree, idx, i);
         const nBitsArity = Math.ceil(Math.log2(this.arity));
@@ -125,6 +145,17 @@ class MerkleHash {
         return [v, mp];
     }
 
+    // getGroupProof for every query of a tree (fri.js:83-105 opens each tree at all query rows): for a device-resident tree one gather
+    // kernel and one copy back; host trees one by one.  Same values as getGroupProof: siblings in normal form, nodes beyond a level's count 0.
+    getGroupProofs(tree, idxs) {
+        if (!(isDev(tree.elements) && isDev(tree.nodes)) || idxs.length === 0) return idxs.map((i) => this.getGroupProof(tree, i));
+        for (const idx of idxs) if ((idx < 0) || (idx >= tree.height)) throw new Error("Out of range");
+        const nl = this._nLevels(tree.height), w = tree.width, per = nl * this.arity * 4, n = idxs.length;
+        const vals = new BigUint64Array(Math.max(1, n * w)), sib = new BigUint64Array(Math.max(1, n * per));
+        addon.bn128GroupProofsDev(tree.elements.ptr, tree.nodes.ptr, w, tree.height, this.arity, BigUint64Array.from(idxs, BigInt), vals, sib);
+        return idxs.map((_, q) => [Array.from(vals.subarray(q * w, (q + 1) * w)), this._levels(sib, q * per, nl)]);
+    }
+
     calculateRootFromGroupProof(mp, idx, vals) {    // merklehash_bn128_p.js:184-232
         let value = this.lh.hash(vals);
         const nBitsArity = Math.ceil(Math.log2(this.arity));
@@ -138,44 +169,29 @@ class MerkleHash {
         return value;
     }
 
-    // batch form for the verifier's loops over queries: every sponge chunk and every level is one batched permutation call
-    // over all the openings (one BN254 permutation alone has the latency of a wave of them)
+    // batch form for the verifier's loops over queries (stark_verify.js:165-178, fri.js:140): proofs = [[vals, siblings], ...] of one tree ->
+    // their roots; packing, leaf sponge and every level of every opening in ONE device call (a wave per opening walks its whole path)
     calculateRootsFromGroupProofs(proofs, idxs) {
         const n = proofs.length;
         if (n === 0) return [];
-        const batch = (rows, init) => {         // rows: n x nIn BigInt -> n outputs
-            const nIn = rows[0].length, out = new BigUint64Array(4 * n);
-            addon.bn128Poseidon(toWords([].concat(...rows)), init ? toWords(init) : null, n, nIn, 1, out);
-            const res = [];
-            for (let q = 0; q < n; q++) res.push(fromWords(out, q));
-            return res;
-        };
-        const els = proofs.map(([vals]) => {
-            const flat = [];
-            for (const v of vals) { if (Array.isArray(v)) for (const x of v) flat.push(BigInt(x)); else flat.push(BigInt(v)); }
-            const e = [];
-            for (let i = 0; i < flat.length; i += 3) { let acc = 0n; for (let k = 0; k < 3 && i + k < flat.length; k++) acc += flat[i + k] << BigInt(64 * k); e.push(acc % R); }
-            return e;
-        });
-        const nEl = els[0].length, nl = proofs[0][1].length;
-        if (els.some((e) => e.length !== nEl) || proofs.some((p) => p[1].length !== nl)) throw new Error("openings of different shapes in one batch");
-        let value;
-        if (nEl === 0) value = els.map(() => 0n);
-        else if (nEl === 1) value = els.map((e) => e[0]);
-        else {
-            value = els.map(() => 0n);
-            for (let i = 0; i < nEl; i += this.arity) {
-                let chunks = els.map((e) => e.slice(i, i + this.arity));
-                if (chunks[0].length < this.arity && this.custom) chunks = chunks.map((c) => c.concat(new Array(this.arity - c.length).fill(0n)));
-                value = batch(chunks, value);
+        const flatten = (vals) => { const f = []; for (const v of vals) { if (Array.isArray(v)) for (const x of v) f.push(BigInt(x)); else f.push(BigInt(v)); } return f; };
+        const first = flatten(proofs[0][0]), width = first.length, nl = proofs[0][1].length, a = this.arity, per = nl * a * 4;
+        const vals = new BigUint64Array(Math.max(1, n * width)), sib = new BigUint64Array(Math.max(1, n * per)), ii = new BigUint64Array(n), roots = new BigUint64Array(4 * n);
+        for (let q = 0; q < n; q++) {
+            const f = q === 0 ? first : flatten(proofs[q][0]), mp = proofs[q][1];
+            if (f.length !== width || mp.length !== nl || mp.some((g) => g.length !== a)) throw new Error("openings of different shapes in one batch");
+            for (let i = 0; i < width; i++) vals[q * width + i] = f[i];
+            for (let l = 0; l < nl; l++) for (let i = 0; i < a; i++) {
+                let v = BigInt(mp[l][i]); if (v < 0n || v >> 256n) { v %= R; if (v < 0n) v += R; }        // below 2^256 the library reduces
+                const o = q * per + (l * a + i) * 4;
+                for (let k = 0; k < 4; k++) sib[o + k] = (v >> BigInt(64 * k)) & M64;
             }
+            ii[q] = BigInt(idxs[q]);
         }
-        const nBitsArity = Math.ceil(Math.log2(this.arity)), pos = idxs.map((i) => Number(i));
-        for (let o = 0; o < nl; o++) {
-            const groups = proofs.map(([, mp], q) => { const g = mp[o].map((x) => BigInt(x)); g[pos[q] & (this.arity - 1)] = value[q]; pos[q] = pos[q] >> nBitsArity; return g; });
-            value = batch(groups, null);
-        }
-        return value;
+        addon.bn128RootsFromGroupProofs(vals, sib, width, nl, a, this.custom ? 1 : 0, 0, ii, n, roots);
+        const out = [];
+        for (let q = 0; q < n; q++) out.push(fromWords(roots, q));
+        return out;
     }
     verifyGroupProofs(root, proofs, idxs) { return this.calculateRootsFromGroupProofs(proofs, idxs).every((r) => this.eqRoot(r, root)); }
 
@@ -185,9 +201,15 @@ class MerkleHash {
         return this.eqRoot(this.calculateRootFromGroupProof(mp, idx, groupElements), root);
     }
 
-    root(tree) { return fromMontgomery(tree.nodes.slice(tree.nodes.length - 4))[0]; }
+    root(tree) { return fromMontgomery(tree.nodes.slice(tree.nodes.length - 4))[0]; }     // resident: the last 4 words are all that is downloaded
 
     async writeToFile(tree, fileName) {     // merklehash_bn128_p.js:243-263
+        if (isDev(tree.elements) && isDev(tree.nodes)) {        // resident: HBM -> file through the library's pinned chunks, nothing on the JS heap
+            await fs.promises.writeFile(fileName, new Uint8Array(BigUint64Array.from([BigInt(tree.width), BigInt(tree.height)]).buffer));
+            tree.elements.view(0, tree.width * tree.height).toFile(fileName, { byteOffset: 16 });
+            tree.nodes.toFile(fileName, { byteOffset: 16 + 8 * tree.width * tree.height });
+            return;
+        }
         const fd = await fs.promises.open(fileName, "w+");
         await fd.write(new Uint8Array(BigUint64Array.from([BigInt(tree.width), BigInt(tree.height)]).buffer));
         const el = tree.elements;

@@ -23,6 +23,18 @@ def _words(vals):
     return a
 
 
+def _words256(vals):
+    """the words of values < 2^256 as they are (the library reduces them mod r); anything else is reduced here first"""
+    a = np.zeros((len(vals), 4), np.uint64)
+    for i, v in enumerate(vals):
+        v = int(v)
+        if not 0 <= v < (1 << 256):
+            v %= R
+        for k in range(4):
+            a[i, k] = (v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF
+    return a
+
+
 def _ints(words):
     w = np.asarray(words, dtype=np.uint64).reshape(-1, 4)
     return [sum(int(x) << (64 * k) for k, x in enumerate(r)) for r in w]
@@ -177,9 +189,8 @@ class MerkleHashBN128:
         return value
 
     def calculateRootsFromGroupProofs(self, proofs, idxs):
-        """calculateRootFromGroupProof for a batch of openings [(vals, siblings), ...] of one tree: every sponge chunk and
-        every tree level is ONE batched permutation call over all the openings (a single BN254 permutation has the
-        latency of a whole wave of them)"""
+        """calculateRootFromGroupProof for a batch of openings [(vals, siblings), ...] of one tree: packing, leaf sponge and every
+        level of every opening in ONE launch (pil2gl_bn128_roots_from_group_proofs: a wave per opening walks its whole path)"""
         if not proofs:
             return []
         flat = []
@@ -190,30 +201,16 @@ class MerkleHashBN128:
             flat.append(f)
         if len({len(f) for f in flat}) != 1 or len({len(mp) for _, mp in proofs}) != 1:
             raise Pil2glError("openings of different shapes in one batch")
-        els = [[sum(x << (64 * k) for k, x in enumerate(f[i:i + 3])) % R for i in range(0, len(f), 3)] for f in flat]
-        n_el = len(els[0])
-        if n_el == 0:
-            value = [0] * len(proofs)
-        elif n_el == 1:
-            value = [e[0] for e in els]
-        else:                                                   # linearhash.bn128.js:46-57, all openings per chunk
-            value = [0] * len(proofs)
-            for i in range(0, n_el, self.arity):
-                chunks = [e[i:i + self.arity] for e in els]
-                if len(chunks[0]) < self.arity and self.custom:
-                    chunks = [c + [0] * (self.arity - len(c)) for c in chunks]
-                value = [r[0] for r in poseidon_batch(chunks, value, 1)]
-        nbits = (self.arity - 1).bit_length()
-        pos = [int(i) for i in idxs]
-        for level in range(len(proofs[0][1])):                  # merklehash_bn128_p.js:207-231
-            groups = []
-            for q, (_, mp) in enumerate(proofs):
-                g = [int(s_) % R for s_ in mp[level]]
-                g[pos[q] & (self.arity - 1)] = value[q]
-                groups.append(g)
-                pos[q] >>= nbits
-            value = [r[0] for r in poseidon_batch(groups, None, 1)]
-        return value
+        n, width, levels, a = len(proofs), len(flat[0]), len(proofs[0][1]), self.arity
+        if any(len(g) != a for _, mp in proofs for g in mp):
+            raise Pil2glError("a level's group must hold `arity` siblings")
+        vals = np.array(flat, dtype=np.uint64).reshape(n, width)
+        sib = _words256([s_ for _, mp in proofs for g in mp for s_ in g])
+        ii = np.array([int(i) for i in idxs], dtype=np.uint64)
+        roots = np.zeros((n, 4), np.uint64)
+        call("pil2gl_bn128_roots_from_group_proofs", _ptr(vals) if width else None, _ptr(sib) if levels else None, width, levels, a,
+             int(self.custom), 0, _ptr(ii), n, _ptr(roots))
+        return _ints(roots)
 
     def verifyGroupProofs(self, root, proofs, idxs):
         return all(self.eqRoot(r, root) for r in self.calculateRootsFromGroupProofs(proofs, idxs))
