@@ -44,7 +44,8 @@
  *    pil2gl_last_error() describes the failure (the reference throws Error /
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
- *    point fails with PIL2GL_ENODEV.
+ *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
+ *    square, the jit_cache_ and precompile_ calls, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -314,6 +315,48 @@ int pil2gl_cols_dot_ext_range_dev(const uint64_t *const *bufs, const uint64_t *s
 /* callCalculateExps / calculateExps: run the op-list on every row of the domain.  Section pointers in
  * ctx are DEVICE pointers; prog/ctx structs themselves are host memory (copied at launch). */
 int pil2gl_eval_program_dev(const glx_program *prog, const glx_ctx *ctx, void *stream);
+/* ---- compile at setup, prove many times: code objects of the evaluator's run-time compiled kernels kept on disk (csrc/expr.hip) ----
+ * Long programs on large domains run through a kernel hiprtc builds from the optimised op-list: 0.7 to 38 s for the programs of
+ * LAB_NOTES.md 13, against 0.94 s for a whole config-3 proof.  The generated source holds no pointer, no scalar value and no row
+ * count -- only the optimised op-list, the section widths, the row offsets and the form of its products -- so it is known at setup
+ * and is the same for every proof.  With a cache directory set, the evaluator looks there before it compiles and stores what it
+ * compiled; with none set (the default) nothing anywhere behaves differently.
+ * ALL FOUR CALLS BELOW ARE HOST ONLY: they need no device, never initialise one, and run on a build host (the target is then gfx950).
+ *
+ * jit_cache_set_dir: NULL or "" switches the disk cache off.  Otherwise the directory is created (mode 0700) if missing; one that
+ *   cannot be created or written is PIL2GL_EINVAL and the earlier setting stays.  Resets the counters.  Before the first call the
+ *   setting is the environment variable PIL2GL_JIT_CACHE_DIR, read once at first use (unset: off).
+ *   THE DIRECTORY HOLDS CODE THAT WILL RUN ON THE GPU: keep it private to the user who proves.  A file is only used when it belongs
+ *   to geteuid(), is writable by nobody else, and passes the checks below; the library does not defend against that same user.
+ * jit_cache_stats: counters since the library was loaded or the last set_dir --
+ *   [0] kernels found in memory  [1] found on disk  [2] compiled  [3] files written  [4] files rejected  [5] writes that failed
+ *   [6] total compile ms  [7] total ms spent looking on disk (open, read, compare, checksum)
+ * One file per kernel, <dir>/<32 hex digits>.p2gl, the digits a 128-bit hash of: cache-format version, arch, the options handed to
+ * hiprtcCompileProgram, hiprtcVersion, the source text.  Little-endian layout:
+ *   0 magic "P2GLJIT\0"  8 u32 format version (1)  12 u32 header bytes = 64 + archLen + optsLen  16 u32 hiprtc major  20 u32 hiprtc minor
+ *   24 u32 archLen  28 u32 optsLen  32 u64 srcLen  40 u64 codeLen  48 u64[2] checksum of the code bytes
+ *   64 arch, options joined by '\n', the full source text, the code object
+ * On a lookup every header field and the stored source must EQUAL what would be compiled now, the lengths must add up to the file's
+ * size and the checksum must match; anything else counts as rejected, the kernel is compiled and the file replaced -- bytes that
+ * fail a check never reach the module loader.  Files are written under a temporary name in the same directory and renamed, mode
+ * 0600; a write that fails is counted and otherwise ignored (the evaluation succeeds, pil2gl_last_error is untouched).
+ * Size: the source is about 25 KB of field arithmetic plus about 90 bytes per op, the code object 20-265 KB: 50 KB to 0.9 MB a kernel
+ *   (119 KB for the 666-op constraint program of the bench AIR, 871 KB for a 200-slot FRI program).
+ * Nothing is evicted: a directory serves one setup; delete it to start over.  pil2gl_shutdown forgets loaded modules, not files. */
+int pil2gl_jit_cache_set_dir(const char *dir);
+int pil2gl_jit_cache_stats(uint64_t out[8]);
+/* Optimises the program for this context exactly as pil2gl_eval_program_dev does and applies the same choice of kernel (the compiled
+ * one for >= 64 ops on >= 2^16 rows with <= 200 temporaries, PIL2GL_EXPR_JIT overriding); if the compiled kernel would run, makes sure
+ * its code object is in the cache directory, compiling if need be.  Section pointers are not read and may be NULL; widths, nBits,
+ * primeShift and the scalar pool must be what the later evaluation passes (equal scalars merge: placeholders must be pairwise
+ * distinct where the real values will be -- js/prover_helpers.js precompileExps and pil2gl.stark.precompile see to that).
+ * outInfo: [0] 0 interpreter / 1 compiled kernel  [1] 0 nothing to do / 1 compiled now / 2 already on disk  [2] code bytes  [3] temporaries.
+ * PIL2GL_EINVAL with no cache directory set. */
+int pil2gl_precompile_program(const glx_program *prog, const glx_ctx *ctx, uint32_t outInfo[4]);
+/* the same for the program of pil2gl_compute_q_stark_dev, in the sub-domain context that call evaluates it in (one builder for both);
+ * arguments and refusals as there, outInfo as above */
+int pil2gl_precompile_q_stark(const glx_program *prog, const glx_ctx *ctx, uint32_t qSection, uint32_t nBits, uint32_t nBitsExt,
+                              uint32_t qDim, uint32_t qDeg, uint32_t outInfo[4]);
 /* calculateExps with debug = true (prover_helpers.js:46-70: a constraint evaluated on the rows [first, last) of its boundary, stopping
  * at the first row whose value is not zero): after the constraint's program has written its value to a column of `dim` (1 or 3) words
  * per row, *hostRow = the smallest such row (UINT64_MAX if the constraint holds on the whole range) and hostVal[0..dim) its value.

@@ -450,6 +450,45 @@ FN(EvalProgramDev) {
     P2(env, pil2gl_eval_program_dev(&prog, &ctx, nullptr)); return mk_undefined(env);
 }
 
+// ---- compile at setup, prove many times (host only: none of the three touches a device) ----
+FN(JitCacheSetDir) { // (dir | null | undefined)
+    Args a(env, info);
+    if (a.is_nullish(0)) { P2(env, pil2gl_jit_cache_set_dir(nullptr)); return mk_undefined(env); }
+    size_t n = 0;
+    if (napi_get_value_string_utf8(env, a.argv[0], nullptr, 0, &n) != napi_ok) { a.fail("expected a directory name"); return nullptr; }
+    std::string dir(n + 1, 0);
+    napi_get_value_string_utf8(env, a.argv[0], &dir[0], n + 1, &n);
+    P2(env, pil2gl_jit_cache_set_dir(dir.c_str())); return mk_undefined(env);
+}
+FN(JitCacheStats) {  // -> { memoryHits, diskHits, compiles, diskWrites, rejected, failedWrites, compileMs, diskLoadMs }
+    static const char *names[8] = { "memoryHits", "diskHits", "compiles", "diskWrites", "rejected", "failedWrites", "compileMs", "diskLoadMs" };
+    uint64_t st[8];
+    P2(env, pil2gl_jit_cache_stats(st));
+    napi_value o, v; NAPI_CALL(env, napi_create_object(env, &o));
+    for (int k = 0; k < 8; k++) { NAPI_CALL(env, napi_create_double(env, (double)st[k], &v)); NAPI_CALL(env, napi_set_named_property(env, o, names[k], v)); }
+    return o;
+}
+// (opsBuf, nOps, nTmp, nBits, primeShift, sectionWidths BigUint64Array, scalars BigUint64Array) -> { routed, origin, codeBytes, slots }
+FN(PrecompileProgram) {
+    Args a(env, info); uint64_t nOps = a.u64(1), nTmp = a.u64(2), nBits = a.u64(3), ps = a.u64(4);
+    uint64_t nSec = 0, nSc = 0;
+    uint64_t *ops = a.arr(0, nOps * (sizeof(glx_op) / 8)), *widths = a.arr(5, 0, &nSec), *scal = a.arr(6, 0, &nSc);
+    if (!a.ok) return nullptr;
+    std::vector<glx_section> secs(nSec);
+    for (uint64_t i = 0; i < nSec; i++) { secs[i].ptr = nullptr; secs[i].width = widths[i]; }
+    glx_program prog = { (uint32_t)nOps, (uint32_t)nTmp, (const glx_op *)ops };
+    glx_ctx ctx = { (uint32_t)nBits, (uint32_t)ps, (uint32_t)nSec, (uint32_t)nSc, secs.data(), scal };
+    uint32_t out[4];
+    P2(env, pil2gl_precompile_program(&prog, &ctx, out));
+    static const char *origin[3] = { "none", "compiled", "disk" };
+    napi_value o, v; NAPI_CALL(env, napi_create_object(env, &o));
+    NAPI_CALL(env, napi_create_string_utf8(env, out[0] ? "jit" : "interp", NAPI_AUTO_LENGTH, &v)); NAPI_CALL(env, napi_set_named_property(env, o, "routed", v));
+    NAPI_CALL(env, napi_create_string_utf8(env, origin[out[1] < 3 ? out[1] : 0], NAPI_AUTO_LENGTH, &v)); NAPI_CALL(env, napi_set_named_property(env, o, "origin", v));
+    NAPI_CALL(env, napi_create_uint32(env, out[2], &v)); NAPI_CALL(env, napi_set_named_property(env, o, "codeBytes", v));
+    NAPI_CALL(env, napi_create_uint32(env, out[3], &v)); NAPI_CALL(env, napi_set_named_property(env, o, "slots", v));
+    return o;
+}
+
 // (devCol, dim, first, last) -> [row, v0, v1, v2] as BigInt, row = 2^64-1 when the column is zero on [first, last)
 FN(FirstNonzeroRowDev) {
     Args a(env, info); uint64_t col = a.u64(0), dim = a.u64(1), first = a.u64(2), last = a.u64(3);
@@ -495,7 +534,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },
         { "rowsDotExtDev", RowsDotExtDev }, { "rowsDotExtMultiDev", RowsDotExtMultiDev }, { "friCombineDev", FriCombineDev }, { "colsDotExtDev", ColsDotExtDev }, { "colsDotExtMultiDev", ColsDotExtMultiDev }, { "synthFibonacciDev", SynthFibonacciDev },
         { "friFoldDev", FriFoldDev }, { "friTransposeDev", FriTransposeDev },
-        { "friFold", FriFold }, { "friVerifyFold", FriVerifyFold }, { "friTranspose", FriTranspose }, { "evalProgramDev", EvalProgramDev }, { "firstNonzeroRowDev", FirstNonzeroRowDev },
+        { "friFold", FriFold }, { "friVerifyFold", FriVerifyFold }, { "friTranspose", FriTranspose }, { "evalProgramDev", EvalProgramDev }, { "jitCacheSetDir", JitCacheSetDir }, { "jitCacheStats", JitCacheStats }, { "precompileProgram", PrecompileProgram }, { "firstNonzeroRowDev", FirstNonzeroRowDev },
         { "fftBlockDev", FftBlockDev }, { "interpolatePrepareBlockDev", InterpolatePrepareBlockDev },
     };
     for (auto &f : fns) {

@@ -405,7 +405,7 @@ struct JitArgs {            // kernel argument block (by value)
     const u64 *scalars; const u32 *limbs; u64 *sec[GLX_MAX_SECTIONS]; u32 nBits; u32 pad_;
 };
 struct JitEntry { hipModule_t mod; hipFunction_t fn; };
-static std::map<std::string, JitEntry> g_jit_cache;       // modules of the device the library is initialised on (cleared by pil2gl_shutdown)
+static std::map<std::string, JitEntry> g_jit_cache;       // modules of the device the library is initialised on (cleared by pil2gl_shutdown; the disk cache below is not)
 namespace pil2gl {
 void jit_clear() {
     std::lock_guard<std::recursive_mutex> lk(runtime_lock());
@@ -544,15 +544,20 @@ static std::string jit_arch() {
     return "gfx950";
 }
 
+// what hiprtcCompileProgram is handed besides the source; part of the key of a stored code object
+static std::vector<std::string> jit_options(const std::string &arch) {
+    return { "--offload-arch=" + arch, "-O3", "-ffp-contract=off" };
+}
 static int jit_build(const std::string &src, std::vector<char> &code) {
     if (const char *dump = getenv("PIL2GL_EXPR_DUMP")) {        // debugging aid: the generated kernel's source, last program compiled
         if (FILE *f = fopen(dump, "w")) { fwrite(src.data(), 1, src.size(), f); fclose(f); }
     }
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), "pil2gl_expr.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return fail(PIL2GL_EHIP, "hiprtcCreateProgram failed");
-    const std::string arch = "--offload-arch=" + jit_arch();
-    const char *opts[] = { arch.c_str(), "-O3", "-ffp-contract=off" };
-    hiprtcResult rc = hiprtcCompileProgram(prog, 3, opts);
+    const std::vector<std::string> optStr = jit_options(jit_arch());
+    std::vector<const char *> opts;
+    for (const std::string &o : optStr) opts.push_back(o.c_str());
+    hiprtcResult rc = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
     if (rc != HIPRTC_SUCCESS) {
         size_t n = 0; hiprtcGetProgramLogSize(prog, &n);
         std::string log(n, 0); if (n) hiprtcGetProgramLog(prog, &log[0]);
@@ -564,17 +569,227 @@ static int jit_build(const std::string &src, std::vector<char> &code) {
     hiprtcDestroyProgram(&prog);
     return PIL2GL_OK;
 }
+
+// ---- code objects kept on disk ----------------------------------------------------------------------------------------------
+// A prover that starts again, or the next rank of eight, would pay the compile again: seconds to tens of seconds for a source
+// that was fully known at setup.  With a cache directory set (pil2gl_jit_cache_set_dir / PIL2GL_JIT_CACHE_DIR) jit_get looks
+// for the code object on disk before it compiles, and stores what it compiled.  One file per kernel, <dir>/<key>.p2gl; the key
+// is a 128-bit hash of everything that decides the code object (cache-format version, arch, options, hiprtc version, source).
+// The key only names the file: a file is used when its header and its stored source EQUAL what would be compiled now, its
+// lengths add up to its size, the checksum of its code bytes matches and it belongs to this user.  Anything else is set aside
+// (counted as rejected), the kernel compiled and the file replaced.  Layout (little-endian), include/pil2gl.h repeats it:
+//   0 magic "P2GLJIT\0"   8 u32 format version   12 u32 header bytes (64 + archLen + optsLen)   16 u32 hiprtc major   20 u32 hiprtc minor
+//   24 u32 archLen   28 u32 optsLen   32 u64 srcLen   40 u64 codeLen   48 u64[2] checksum of the code bytes (jit_hash128)
+//   64 arch, options (joined by '\n'), source, code object
+// The source is most of a file: about 25 KB of field arithmetic shared by every kernel plus ~90 bytes per op, next to a code
+// object of 20-265 KB -- 50 KB to 0.9 MB per kernel (119 KB for the 666-op constraint program of the bench AIR, 871 KB for a 200-slot FRI program).  Nothing is ever evicted.
+#include <errno.h>
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include <chrono>
+
+#define JIT_FILE_VERSION 1u
+static const char kJitMagic[8] = { 'P', '2', 'G', 'L', 'J', 'I', 'T', 0 };
+enum { JS_MEM_HITS, JS_DISK_HITS, JS_COMPILES, JS_DISK_WRITES, JS_REJECTED, JS_FAILED_WRITES, JS_COMPILE_NS, JS_LOAD_NS };
+static u64 g_jit_stats[8];
+static std::string g_jit_dir;           // empty: no disk cache
+static bool g_jit_dir_init = false;
+
+// The project's own 128-bit hash (file names and the checksum of the code bytes; nothing relies on it against an adversary -- the
+// stored source is compared in full): two 64-bit lanes absorb the little-endian words, each through its own rotate-multiply, a
+// short tail is zero-padded, the length starts both lanes, and the lanes are mixed into each other before a final avalanche.
+static inline u64 rotl64(u64 x, int r) { return (x << r) | (x >> (64 - r)); }
+static inline u64 avalanche64(u64 x) { x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33; return x; }
+static void jit_hash128(const void *data, size_t n, u64 out[2]) {
+    const unsigned char *p = (const unsigned char *)data;
+    u64 a = 0x9E3779B97F4A7C15ull ^ (u64)n, b = 0xC2B2AE3D27D4EB4Full + (u64)n;
+    for (size_t i = 0; i < n; i += 8) {
+        u64 w = 0;
+        const size_t m = n - i < 8 ? n - i : 8;
+        for (size_t k = 0; k < m; k++) w |= (u64)p[i + k] << (8 * k);
+        a = rotl64(a ^ w, 27) * 0x87C37B91114253D5ull + 0x52DCE729ull;
+        b = rotl64(b + w, 31) * 0x4CF5AD432745937Full ^ (a >> 29);
+    }
+    a += b; b += a;
+    a = avalanche64(a); b = avalanche64(b ^ rotl64(a, 17));
+    out[0] = a + b; out[1] = b;
+}
+
+struct JitIdent { std::string arch, opts; int rtcMajor, rtcMinor; };
+static JitIdent jit_ident() {
+    JitIdent id; id.arch = jit_arch(); id.rtcMajor = id.rtcMinor = 0;
+    for (const std::string &o : jit_options(id.arch)) { if (!id.opts.empty()) id.opts += '\n'; id.opts += o; }
+    (void)hiprtcVersion(&id.rtcMajor, &id.rtcMinor);
+    return id;
+}
+static std::string jit_key(const JitIdent &id, const std::string &src) {
+    std::string all = "p2gl-jit " + std::to_string(JIT_FILE_VERSION) + "\n" + id.arch + "\n" + id.opts + "\n" + std::to_string(id.rtcMajor) + "." + std::to_string(id.rtcMinor) + "\n";
+    all += src;
+    u64 h[2]; jit_hash128(all.data(), all.size(), h);
+    char hex[33]; snprintf(hex, sizeof hex, "%016llx%016llx", (unsigned long long)h[0], (unsigned long long)h[1]);
+    return hex;
+}
+static void put_u32(std::string &s, u32 v) { for (int k = 0; k < 4; k++) s += (char)(v >> (8 * k)); }
+static void put_u64(std::string &s, u64 v) { for (int k = 0; k < 8; k++) s += (char)(v >> (8 * k)); }
+static u64 get_le(const unsigned char *p, int n) { u64 v = 0; for (int k = 0; k < n; k++) v |= (u64)p[k] << (8 * k); return v; }
+
+// "" on success, else why the directory cannot serve (nothing is changed then)
+static std::string jit_dir_apply(const char *dir) {
+    if (!dir || !dir[0]) { g_jit_dir.clear(); return ""; }
+    if (mkdir(dir, 0700) != 0 && errno != EEXIST) return std::string("cannot create ") + dir + ": " + strerror(errno);
+    struct stat st;
+    if (stat(dir, &st) != 0 || !S_ISDIR(st.st_mode)) return std::string(dir) + " is not a directory";
+    if (access(dir, R_OK | W_OK | X_OK) != 0) return std::string(dir) + " cannot be written: " + strerror(errno);
+    g_jit_dir = dir;
+    return "";
+}
+static void jit_dir_init() {            // under runtime_lock()
+    if (g_jit_dir_init) return;
+    g_jit_dir_init = true;
+    const std::string why = jit_dir_apply(getenv("PIL2GL_JIT_CACHE_DIR"));
+    if (!why.empty()) fprintf(stderr, "pil2gl: PIL2GL_JIT_CACHE_DIR ignored (%s)\n", why.c_str());
+}
+static u64 now_ns() { return (u64)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// 1: `code` holds the stored code object; 0: no file; -1: a file that fails a check (it never reaches the module loader)
+static int jit_disk_load(const std::string &path, const JitIdent &id, const std::string &src, std::vector<char> &code) {
+    const int fd = open(path.c_str(), O_RDONLY | O_NOFOLLOW | O_CLOEXEC);
+    if (fd < 0) return errno == ENOENT ? 0 : -1;
+    struct stat st;
+    std::vector<unsigned char> f;
+    bool ok = fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_uid == geteuid() && (st.st_mode & 022) == 0 && st.st_size >= 64 && st.st_size < ((off_t)1 << 31);
+    if (ok) {
+        f.resize((size_t)st.st_size);
+        size_t got = 0;
+        while (got < f.size()) { const ssize_t r = read(fd, f.data() + got, f.size() - got); if (r <= 0) break; got += (size_t)r; }
+        char extra;
+        ok = got == f.size() && read(fd, &extra, 1) == 0;          // and the file did not grow under us
+    }
+    close(fd);
+    if (!ok) return -1;
+    if (memcmp(f.data(), kJitMagic, 8) != 0 || get_le(&f[8], 4) != JIT_FILE_VERSION) return -1;
+    const u64 hdr = get_le(&f[12], 4), aLen = get_le(&f[24], 4), oLen = get_le(&f[28], 4), sLen = get_le(&f[32], 8), cLen = get_le(&f[40], 8);
+    if ((int)get_le(&f[16], 4) != id.rtcMajor || (int)get_le(&f[20], 4) != id.rtcMinor) return -1;
+    if (aLen != id.arch.size() || oLen != id.opts.size() || sLen != src.size() || hdr != 64 + aLen + oLen || cLen == 0) return -1;
+    if (cLen > f.size() || hdr + sLen + cLen != f.size()) return -1;       // (the other three lengths are equal to ours: no overflow)
+    if (memcmp(&f[64], id.arch.data(), aLen) != 0 || memcmp(&f[64 + aLen], id.opts.data(), oLen) != 0 || memcmp(&f[hdr], src.data(), sLen) != 0) return -1;
+    u64 sum[2]; jit_hash128(&f[hdr + sLen], cLen, sum);
+    if (sum[0] != get_le(&f[48], 8) || sum[1] != get_le(&f[56], 8)) return -1;
+    code.assign((const char *)&f[hdr + sLen], (const char *)&f[hdr + sLen] + cLen);
+    return 1;
+}
+// temporary name in the same directory, then rename(): a reader sees the old file, no file or the whole new one.  Never touches pil2gl_last_error.
+static bool jit_disk_store(const std::string &path, const JitIdent &id, const std::string &src, const std::vector<char> &code) {
+    std::string h(kJitMagic, 8);
+    u64 sum[2]; jit_hash128(code.data(), code.size(), sum);
+    put_u32(h, JIT_FILE_VERSION); put_u32(h, (u32)(64 + id.arch.size() + id.opts.size())); put_u32(h, (u32)id.rtcMajor); put_u32(h, (u32)id.rtcMinor);
+    put_u32(h, (u32)id.arch.size()); put_u32(h, (u32)id.opts.size()); put_u64(h, src.size()); put_u64(h, code.size()); put_u64(h, sum[0]); put_u64(h, sum[1]);
+    h += id.arch; h += id.opts;
+    static unsigned serial = 0;
+    const std::string tmp = path + ".tmp." + std::to_string((long)getpid()) + "." + std::to_string(serial++);
+    const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_EXCL | O_NOFOLLOW | O_CLOEXEC, 0600);
+    if (fd < 0) return false;
+    bool ok = true;
+    const struct { const char *p; size_t n; } parts[3] = { { h.data(), h.size() }, { src.data(), src.size() }, { code.data(), code.size() } };
+    for (int k = 0; k < 3 && ok; k++)
+        for (size_t put = 0; put < parts[k].n && ok;) { const ssize_t w = write(fd, parts[k].p + put, parts[k].n - put); if (w <= 0) ok = false; else put += (size_t)w; }
+    ok = fchmod(fd, 0600) == 0 && ok;                               // whatever the umask made of it
+    ok = close(fd) == 0 && ok;
+    if (ok && rename(tmp.c_str(), path.c_str()) != 0) ok = false;
+    if (!ok) (void)unlink(tmp.c_str());
+    return ok;
+}
+// the code object of `src`: from the disk cache when it holds a sound copy, else compiled now (and stored, when a directory is set).
+// origin: 1 compiled now, 2 already on disk.  Under runtime_lock().
+static int jit_code(const std::string &src, std::vector<char> &code, u32 *origin) {
+    jit_dir_init();
+    JitIdent id; std::string path;
+    if (!g_jit_dir.empty()) {
+        const u64 t0 = now_ns();
+        id = jit_ident();
+        path = g_jit_dir + "/" + jit_key(id, src) + ".p2gl";
+        const int r = jit_disk_load(path, id, src, code);
+        g_jit_stats[JS_LOAD_NS] += now_ns() - t0;
+        if (r == 1) { g_jit_stats[JS_DISK_HITS]++; if (origin) *origin = 2; return PIL2GL_OK; }
+        if (r < 0) g_jit_stats[JS_REJECTED]++;
+    }
+    const u64 t0 = now_ns();
+    P2_TRY(jit_build(src, code));
+    g_jit_stats[JS_COMPILES]++; g_jit_stats[JS_COMPILE_NS] += now_ns() - t0;
+    if (origin) *origin = 1;
+    if (!g_jit_dir.empty()) g_jit_stats[jit_disk_store(path, id, src, code) ? JS_DISK_WRITES : JS_FAILED_WRITES]++;
+    return PIL2GL_OK;
+}
 static int jit_get(const std::string &src, hipFunction_t *fn) {
     std::lock_guard<std::recursive_mutex> lk(runtime_lock());
     auto it = g_jit_cache.find(src);
-    if (it != g_jit_cache.end()) { *fn = it->second.fn; return PIL2GL_OK; }
+    if (it != g_jit_cache.end()) { g_jit_stats[JS_MEM_HITS]++; *fn = it->second.fn; return PIL2GL_OK; }
     std::vector<char> code;
-    P2_TRY(jit_build(src, code));
+    P2_TRY(jit_code(src, code, nullptr));
     JitEntry e;
     HIP_TRY(hipModuleLoadData(&e.mod, code.data()));
     HIP_TRY(hipModuleGetFunction(&e.fn, e.mod, "jit_eval"));
     g_jit_cache.emplace(src, e);
     *fn = e.fn;
+    return PIL2GL_OK;
+}
+extern "C" int pil2gl_jit_cache_set_dir(const char *dir) {
+    std::lock_guard<std::recursive_mutex> lk(runtime_lock());
+    const std::string why = jit_dir_apply(dir);
+    if (!why.empty()) return fail(PIL2GL_EINVAL, "jit cache directory: %s", why.c_str());
+    g_jit_dir_init = true;                                          // an explicit choice outranks the environment
+    memset(g_jit_stats, 0, sizeof g_jit_stats);
+    return PIL2GL_OK;
+}
+extern "C" int pil2gl_jit_cache_stats(uint64_t out[8]) {
+    if (!out) return fail(PIL2GL_EINVAL, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(runtime_lock());
+    for (int k = 0; k < 8; k++) out[k] = k >= JS_COMPILE_NS ? (g_jit_stats[k] + 500000) / 1000000 : g_jit_stats[k];
+    return PIL2GL_OK;
+}
+
+// Which kernel a program takes, in one place: the run-time compiled one for long programs on large domains (PIL2GL_EXPR_JIT=1 forces it,
+// =0 disables it) whose temporaries fit its registers, else an interpreter form.  pil2gl_eval_program_dev and pil2gl_precompile_program
+// both ask here (tests/evalpath.py restates it).
+static bool jit_routed(size_t nOps, u32 nBits, u32 nSlots) {
+    const char *e = getenv("PIL2GL_EXPR_JIT");
+    const bool want = e ? atoi(e) != 0 : (nOps >= 64 && nBits >= 16);
+    return want && nSlots <= 200;
+}
+// the optimised program of a context as the evaluator runs it, with the context checks that need no device
+static int plan_program(const glx_program *prog, const glx_ctx *ctx, std::vector<IOp> &ops, u32 &nSlots, std::vector<u32> &limbPool) {
+    P2_TRY(compile_program(prog, ctx, ops, nSlots, limbPool, getenv("PIL2GL_EXPR_NOFUSE") == nullptr));
+    if (ctx->nSections > GLX_MAX_SECTIONS) return fail(PIL2GL_EINVAL, "too many sections (%u > %d)", ctx->nSections, GLX_MAX_SECTIONS);
+    for (size_t k = 0; k < ops.size(); k++)
+        for (int s = 0; s < 3; s++) {
+            const glx_ref &r = s < 2 ? ops[k].src[s] : ops[k].dest;
+            const int64_t off = (int64_t)r.prime * ((int64_t)1 << ctx->primeShift);
+            if (off != (int64_t)(int32_t)off) return fail(PIL2GL_EINVAL, "row offset overflow in op %zu", k);
+        }
+    for (u32 i = 0; i < ctx->nSections; i++) if (ctx->sections[i].width >> 32) return fail(PIL2GL_EINVAL, "section %u too wide", i);
+    return PIL2GL_OK;
+}
+
+// Setup-time half of the disk cache (host only: no device is initialised, section pointers are not read).  The program is optimised
+// and routed exactly as pil2gl_eval_program_dev will; if the compiled kernel would run, its code object is put into the cache
+// directory unless a sound copy is there.  outInfo: [0] 0 interpreter / 1 compiled kernel, [1] 0 nothing done / 1 compiled now /
+// 2 already on disk, [2] code bytes, [3] temporary slots.
+extern "C" int pil2gl_precompile_program(const glx_program *prog, const glx_ctx *ctx, uint32_t outInfo[4]) {
+    if (!prog || !ctx || !outInfo || (prog->nOps && !prog->ops) || (ctx->nSections && !ctx->sections)) return fail(PIL2GL_EINVAL, "null argument");
+    if (ctx->nBits > 31) return fail(PIL2GL_EINVAL, "domain too large");
+    std::lock_guard<std::recursive_mutex> lk(runtime_lock());
+    jit_dir_init();
+    if (g_jit_dir.empty()) return fail(PIL2GL_EINVAL, "no jit cache directory set (pil2gl_jit_cache_set_dir / PIL2GL_JIT_CACHE_DIR)");
+    outInfo[0] = outInfo[1] = outInfo[2] = outInfo[3] = 0;
+    if (prog->nOps == 0) return PIL2GL_OK;
+    std::vector<IOp> ops; std::vector<u32> limbPool; u32 nSlots = 0;
+    P2_TRY(plan_program(prog, ctx, ops, nSlots, limbPool));
+    outInfo[3] = nSlots;
+    if (!jit_routed(ops.size(), ctx->nBits, nSlots)) return PIL2GL_OK;
+    std::vector<char> code; u32 origin = 0;
+    P2_TRY(jit_code(jit_source(ops, nSlots, ctx), code, &origin));
+    outInfo[0] = 1; outInfo[1] = origin; outInfo[2] = (uint32_t)code.size();
     return PIL2GL_OK;
 }
 
@@ -608,15 +823,12 @@ extern "C" int pil2gl_eval_program_dev(const glx_program *prog, const glx_ctx *c
     if (prog->nOps == 0) return PIL2GL_OK;
     hipStream_t st = as_stream(stream);
     std::vector<IOp> ops; std::vector<u32> limbPool; u32 nSlots = 0;
-    P2_TRY(compile_program(prog, ctx, ops, nSlots, limbPool, getenv("PIL2GL_EXPR_NOFUSE") == nullptr));
-
-    if (ctx->nSections > GLX_MAX_SECTIONS) return fail(PIL2GL_EINVAL, "too many sections (%u > %d)", ctx->nSections, GLX_MAX_SECTIONS);
+    P2_TRY(plan_program(prog, ctx, ops, nSlots, limbPool));
     // device form of the program (scratch slot 4): ops, then the scalar pool
     std::vector<DevOp> dops(ops.size());
     for (size_t k = 0; k < ops.size(); k++) {
         auto cv = [&](const glx_ref &r) { DevRef d; d.kind_dim = (u32)r.kind | ((u32)r.dim << 8); d.section = r.section; d.rowOff = (int32_t)((int64_t)r.prime * ((int64_t)1 << ctx->primeShift)); d.index = r.index; return d; };
         dops[k].op = ops[k].op; dops[k].aux = ops[k].aux; dops[k].dest = cv(ops[k].dest); dops[k].src[0] = cv(ops[k].src[0]); dops[k].src[1] = cv(ops[k].src[1]);
-        for (int s = 0; s < 3; s++) { const glx_ref &r = s < 2 ? ops[k].src[s] : ops[k].dest; if ((int64_t)r.prime * ((int64_t)1 << ctx->primeShift) != (int64_t)(int32_t)((int64_t)r.prime * ((int64_t)1 << ctx->primeShift))) return fail(PIL2GL_EINVAL, "row offset overflow in op %zu", k); }
     }
     const u64 opsWords = ((u64)dops.size() * sizeof(DevOp) + 7) / 8, limbWords = (limbPool.size() * 4 + 7) / 8;
     u64 *d;
@@ -630,12 +842,9 @@ extern "C" int pil2gl_eval_program_dev(const glx_program *prog, const glx_ctx *c
     c.limbs = (const u32 *)(d + opsWords + ctx->nScalars + 1);
     c.nBits = ctx->nBits;
     for (u32 i = 0; i < GLX_MAX_SECTIONS; i++) { c.secPtr[i] = i < ctx->nSections ? ctx->sections[i].ptr : nullptr; c.secWidth[i] = i < ctx->nSections ? (u32)ctx->sections[i].width : 0; }
-    for (u32 i = 0; i < ctx->nSections; i++) if (ctx->sections[i].width >> 32) return fail(PIL2GL_EINVAL, "section %u too wide", i);
     const u64 nRows = 1ull << ctx->nBits;
-    {   // run-time compiled path for long programs on large domains (PIL2GL_EXPR_JIT=1 forces it, =0 disables it)
-        const char *e = getenv("PIL2GL_EXPR_JIT");
-        const bool want = e ? atoi(e) != 0 : (ops.size() >= 64 && ctx->nBits >= 16);
-        if (want && nSlots <= 200) {
+    {   // run-time compiled path for long programs on large domains
+        if (jit_routed(ops.size(), ctx->nBits, nSlots)) {
             hipFunction_t fn;
             if (jit_get(jit_source(ops, nSlots, ctx), &fn) != PIL2GL_OK) {
                 static bool warned = false;

@@ -431,14 +431,16 @@ int pil2gl_compute_q_split_brev_dev(const uint64_t *qq1, uint32_t nBits, uint32_
 // 2^m x qDim scratch.  s = 0 is the full domain through the same code.
 // (Holds for a satisfied AIR.  A witness that breaks a constraint gives Q coefficients above qDeg * N; the full-domain path drops them,
 // this one folds them onto the low ones: two different proofs, neither of which verifies.)
-int pil2gl_compute_q_stark_dev(const glx_program *prog, const glx_ctx *ctx, uint32_t qSection, uint32_t nBits, uint32_t nBitsExt,
-                               uint32_t qDim, uint32_t qDeg, uint64_t *dstExt, void *stream) {
-    P2_TRY(ensure_init());
-    if (!prog || !ctx || !dstExt || (prog->nOps && !prog->ops) || (ctx->nSections && !ctx->sections)) return fail(PIL2GL_EINVAL, "null argument");
+// The sub-domain context of the quotient stage, after its argument checks (host only).  secs / sub: the context the evaluator is handed;
+// the destination's pointer is left null for the caller to fill in.  m: the sub-domain has 2^m rows.  One builder, so that what is
+// compiled ahead of time (pil2gl_precompile_q_stark) is what the stage runs.
+static int q_stark_context(const glx_program *prog, const glx_ctx *ctx, uint32_t qSection, uint32_t nBits, uint32_t nBitsExt, uint32_t qDim, uint32_t qDeg,
+                           std::vector<glx_section> &secs, glx_ctx &sub, u32 &m) {
+    if (!prog || !ctx || (prog->nOps && !prog->ops) || (ctx->nSections && !ctx->sections)) return fail(PIL2GL_EINVAL, "null argument");
     if (nBitsExt < nBits || nBitsExt > PIL2GL_MAX_NTT_BITS || !qDim || !qDeg || ((u64)qDeg << nBits) > (1ull << nBitsExt)) return fail(PIL2GL_EINVAL, "bad q stage arguments");
     if (ctx->nBits != nBitsExt) return fail(PIL2GL_EINVAL, "the context has 2^%u rows, the extended domain 2^%u", ctx->nBits, nBitsExt);
     if (qSection >= ctx->nSections || ctx->sections[qSection].width != qDim) return fail(PIL2GL_EINVAL, "section %u is not a destination of %u columns", qSection, qDim);
-    u32 m = nBits;
+    m = nBits;
     while ((1ull << m) < ((u64)qDeg << nBits)) m++;
     const u32 s = nBitsExt - m;
     for (u32 k = 0; k < prog->nOps; k++) {
@@ -451,19 +453,35 @@ int pil2gl_compute_q_stark_dev(const glx_program *prog, const glx_ctx *ctx, uint
         }
     }
     for (u32 i = 0; i < ctx->nSections; i++) if (i != qSection && (ctx->sections[i].width << s) >> 32) return fail(PIL2GL_EINVAL, "section %u too wide", i);
+    secs.assign(ctx->sections, ctx->sections + ctx->nSections);
+    for (u32 i = 0; i < ctx->nSections; i++) secs[i].width <<= s;
+    secs[qSection].ptr = nullptr; secs[qSection].width = qDim;
+    sub = *ctx;
+    sub.nBits = m; sub.primeShift = ctx->primeShift < s ? 0 : ctx->primeShift - s; sub.sections = secs.data();
+    return PIL2GL_OK;
+}
+int pil2gl_compute_q_stark_dev(const glx_program *prog, const glx_ctx *ctx, uint32_t qSection, uint32_t nBits, uint32_t nBitsExt,
+                               uint32_t qDim, uint32_t qDeg, uint64_t *dstExt, void *stream) {
+    P2_TRY(ensure_init());
+    if (!dstExt) return fail(PIL2GL_EINVAL, "null argument");
+    std::vector<glx_section> secs; glx_ctx sub; u32 m = 0;
+    P2_TRY(q_stark_context(prog, ctx, qSection, nBits, nBitsExt, qDim, qDeg, secs, sub, m));
     const u64 M = 1ull << m, W = (u64)qDim * qDeg;
     u64 *q, *coef;
     P2_TRY(scratch(14, M * qDim, &q));
     P2_TRY(scratch(15, W << nBits, &coef));
-    std::vector<glx_section> secs(ctx->sections, ctx->sections + ctx->nSections);
-    for (u32 i = 0; i < ctx->nSections; i++) secs[i].width <<= s;
-    secs[qSection].ptr = q; secs[qSection].width = qDim;
-    glx_ctx sub = *ctx;
-    sub.nBits = m; sub.primeShift = ctx->primeShift < s ? 0 : ctx->primeShift - s; sub.sections = secs.data();
+    secs[qSection].ptr = q;
     P2_TRY(pil2gl_eval_program_dev(prog, &sub, stream));
     P2_TRY(ntt_launch(q, qDim, m, q, true, as_stream(stream)));
     P2_TRY(pil2gl_compute_q_split_brev_dev(q, nBits, nBitsExt, qDim, qDeg, coef, stream));
     return lde_launch(coef, W, nBits, dstExt, nBitsExt, as_stream(stream), 0, 0, nullptr, true, true);
+}
+// pil2gl_precompile_program for the program of the quotient stage, in the sub-domain context the stage evaluates it in (host only)
+int pil2gl_precompile_q_stark(const glx_program *prog, const glx_ctx *ctx, uint32_t qSection, uint32_t nBits, uint32_t nBitsExt,
+                              uint32_t qDim, uint32_t qDeg, uint32_t outInfo[4]) {
+    std::vector<glx_section> secs; glx_ctx sub; u32 m = 0;
+    P2_TRY(q_stark_context(prog, ctx, qSection, nBits, nBitsExt, qDim, qDeg, secs, sub, m));
+    return pil2gl_precompile_program(prog, &sub, outInfo);
 }
 // (xi0, xi1, xi2) with xi1 = xi2 = 0 and (xi0 / 7)^(2^nBitsExt) = 1: the point is 7 w_E^k for some row k (no extension element outside the
 // base field solves x^E = 1).  Shared by the table, which refuses such a point, and by LEv, which must not reach the table with one.

@@ -134,4 +134,19 @@ function staged(src, nIn, dst, nOut, fn) {
     }
 }
 
-module.exports = { addon, isFlat, isDev, DevBuffer, PinnedBuffer, ChunkedBuffer, copyAfter, copyFence, copySync, upload, download, staged, CHUNK };
+// Compile at setup, prove many times (include/pil2gl.h, "code objects ... kept on disk"); none of the three needs a device.
+// jitCacheSetDir(dir): where the evaluator's run-time compiled kernels are kept between processes; null / "" = nowhere, the default
+// unless PIL2GL_JIT_CACHE_DIR is set.  The directory holds code that will run on the GPU: keep it private to the user.
+function jitCacheSetDir(dir) { addon.jitCacheSetDir(dir ? String(dir) : null); }
+// -> { memoryHits, diskHits, compiles, diskWrites, rejected, failedWrites, compileMs, diskLoadMs } since load or the last jitCacheSetDir
+function jitCacheStats() { return addon.jitCacheStats(); }
+// (ops, nOps, nTmp as prover_helpers.encode writes them; widths: columns of every section; nScalars: the scalar pool, or how many
+// words it will hold -- then pairwise distinct placeholders stand in) -> { routed: "jit" | "interp", origin: "none" | "compiled" | "disk", codeBytes, slots }
+function precompileProgram(ops, nOps, nTmp, nBits, primeShift, widths, nScalars) {
+    const w = widths instanceof BigUint64Array ? widths : BigUint64Array.from(Array.from(widths, (x) => BigInt(x)));
+    let sc = nScalars;
+    if (!(sc instanceof BigUint64Array)) { sc = new BigUint64Array(Math.max(1, Number(nScalars))); for (let i = 0; i < sc.length; i++) sc[i] = 0x9E3779B97F4A7C15n * BigInt(i + 1) % 0xFFFFFFFF00000001n; }
+    return addon.precompileProgram(ops, nOps, nTmp, nBits, primeShift, w, sc);
+}
+module.exports = { addon, isFlat, isDev, DevBuffer, PinnedBuffer, ChunkedBuffer, copyAfter, copyFence, copySync, upload, download, staged, CHUNK,
+    jitCacheSetDir, jitCacheStats, precompileProgram };

@@ -5,7 +5,7 @@
 // ctx buffers (const_n, cm{s}_n/_ext, x_n/x_ext, Zi_ext, xDivXSubXi_ext, q_ext, f_ext) may be BigUint64Array or
 // BigBuffer-like; referenced sections are staged to the device, destinations copied back.
 "use strict";
-const { addon, isDev, upload, download } = require("./native.js");
+const { addon, isDev, upload, download, precompileProgram } = require("./native.js");
 const P = 0xFFFFFFFF00000001n;
 const OP = { add: 0, sub: 1, mul: 2, copy: 3 };
 const TMP = 0, SEC = 1, SCALAR = 2;
@@ -242,5 +242,34 @@ module.exports.setPol = function setPol(ctx, idPol, pol, dom, options) {
 
 module.exports.callCalculateExps = async function callCalculateExps(stage, code, dom, ctx, parallelExec, useThreads, debug, global = false) {
     module.exports.calculateExps(ctx, code, dom, debug, false, global);                            // prover_helpers.js:23-29 (no worker pool here)
+};
+// Setup-time half of `compile once, prove many times` (native.js jitCacheSetDir): encodes `code` as a later
+// callCalculateExps(stage, code, dom, ctx, ...) of a proof will and hands it to pil2gl_precompile_program, so that the proving process
+// finds the compiled kernel in the cache directory.  No device is needed.  ctx needs pilInfo, nBits, nBitsExt and extendBits; publics,
+// challenges, evals and subproof values are read from ctx where it has them and stood in for by placeholders where it has none.  The
+// evaluator merges EQUAL scalars and nothing else of their values reaches the kernel, so every placeholder differs from every other
+// and from the constants a program writes down: the kernel is the one any proof's values lead to (unless two of them coincide).
+// -> { routed: "jit" | "interp", origin: "none" | "compiled" | "disk", codeBytes, slots }
+function later(real, tag, dim, depth = 1) {
+    return new Proxy(real || [], {
+        get(t, k) {
+            if (typeof k !== "string" || !/^[0-9]+$/.test(k)) return t[k];
+            if (depth > 1) return later(t[k], tag + "/" + k, dim, depth - 1);
+            if (t[k] !== undefined && t[k] !== null) return t[k];
+            const h = require("crypto").createHash("sha256").update("pil2gl placeholder " + tag + "/" + k).digest();
+            const v = [0, 8, 16].map((o) => h.readBigUInt64LE(o) % P);
+            return dim === 3 ? v : v[0];
+        },
+    });
+}
+module.exports.precompileExps = function precompileExps(ctx, code, dom, global = false) {
+    const shadow = Object.create(ctx);
+    shadow.publics = later(ctx.publics, "public", 1);
+    shadow.challenges = later(ctx.challenges, "challenge", 3, 2);
+    shadow.evals = later(ctx.evals, "eval", 3);
+    shadow.subproofValues = later(ctx.subproofValues, "subproofValue", 1, global ? 2 : 1);
+    const enc = encode(code.code, dom, shadow, !!global);
+    return precompileProgram(enc.ops, enc.nOps, enc.nTmp, dom === "n" ? ctx.nBits : ctx.nBitsExt, dom === "n" ? 0 : ctx.extendBits,
+        enc.sections.map((s) => s.width), enc.scalars);
 };
 module.exports.encode = encode;

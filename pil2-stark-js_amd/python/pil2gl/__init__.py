@@ -70,6 +70,62 @@ def device_info():
     return name.value.decode(), cus.value, mem.value
 
 
+# ----------------------------------------------------------------------------- compile at setup, prove many times
+JIT_CACHE_STATS = ("memoryHits", "diskHits", "compiles", "diskWrites", "rejected", "failedWrites", "compileMs", "diskLoadMs")
+PRECOMPILE_ORIGIN = ("none", "compiled", "disk")
+
+
+def jit_cache_set_dir(path):
+    """pil2gl_jit_cache_set_dir: where the evaluator's run-time compiled kernels are kept between processes (None or "": nowhere, the
+    default unless PIL2GL_JIT_CACHE_DIR is set).  The directory holds code that will run on the GPU: keep it private to the user.
+    Host only; resets the counters."""
+    call("pil2gl_jit_cache_set_dir", None if not path else str(path).encode())
+
+
+def jit_cache_stats():
+    """pil2gl_jit_cache_stats as a dict (JIT_CACHE_STATS), since the library was loaded or the last jit_cache_set_dir.  Host only."""
+    out = (C.c_uint64 * 8)()
+    call("pil2gl_jit_cache_stats", out)
+    return dict(zip(JIT_CACHE_STATS, (int(v) for v in out)))
+
+
+def _precompile_info(info):
+    return {"routed": "jit" if info[0] else "interp", "origin": PRECOMPILE_ORIGIN[info[1]], "codeBytes": int(info[2]), "slots": int(info[3])}
+
+
+def precompile_program(ops, n_tmp, widths, scalars, n_bits, prime_shift):
+    """pil2gl_precompile_program: the program (ops as stark.encode_code writes them) in the context of sections `widths` columns wide,
+    2^n_bits rows, row offsets prime << prime_shift: if the evaluator would run it through its compiled kernel, that kernel's code
+    object is in the cache directory when this returns.  No device is needed or touched.  The scalar pool matters only through which
+    of its entries are EQUAL (they merge): placeholders must be pairwise distinct where the proof's values will be.
+    -> {"routed": "jit" | "interp", "origin": "none" | "compiled" | "disk", "codeBytes", "slots"}"""
+    from .stark import make_c_program
+    prog = make_c_program(ops, n_tmp)
+    cs = (_lib.GlxSection * len(widths))()
+    for i, w in enumerate(widths):
+        cs[i].ptr = None; cs[i].width = int(w)
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+    ctx = _lib.GlxCtx(n_bits, prime_shift, len(widths), scalars.size, cs, scalars.ctypes.data_as(_lib.u64p))
+    info = (C.c_uint32 * 4)()
+    call("pil2gl_precompile_program", C.byref(prog), C.byref(ctx), info)
+    return _precompile_info(info)
+
+
+def precompile_q_stark(ops, n_tmp, widths, scalars, q_section, n_bits, n_bits_ext, q_dim, q_deg):
+    """pil2gl_precompile_q_stark: the same for the quotient stage's program, whose context the library derives itself (the rows
+    k * 2^s of the extended domain: pil2gl_compute_q_stark_dev); arguments as stark.GpuBackend.q_stark's, widths in place of buffers"""
+    from .stark import make_c_program
+    prog = make_c_program(ops, n_tmp)
+    cs = (_lib.GlxSection * len(widths))()
+    for i, w in enumerate(widths):
+        cs[i].ptr = None; cs[i].width = int(w)
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+    ctx = _lib.GlxCtx(n_bits_ext, n_bits_ext - n_bits, len(widths), scalars.size, cs, scalars.ctypes.data_as(_lib.u64p))
+    info = (C.c_uint32 * 4)()
+    call("pil2gl_precompile_q_stark", C.byref(prog), C.byref(ctx), q_section, n_bits, n_bits_ext, q_dim, q_deg, info)
+    return _precompile_info(info)
+
+
 # ----------------------------------------------------------------------------- fft_p.js
 def _check_len(buf, n, what):
     if buf is not None and int(np.prod(buf.shape)) < n:

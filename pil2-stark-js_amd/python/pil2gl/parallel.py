@@ -702,7 +702,9 @@ def stark_gen_sharded(be, cm1_n, setup, info, exprs, publics, group=None, rehear
     trees: what a domain beyond one device's memory needs).  overwrite_trace: the last witness stage's trace buffer doubles as its
     LDE's coefficient workspace and is destroyed (config 5: 107 GB trace + 107 GB slice per GPU, no room for a third buffer).
     samples: {"rows": [local rows]} -> receives those rows of the rank's slices (cm1_ext, const_ext, x_ext, Zi_ext, q_ext): the
-    full-size rehearsal test checks them against closed forms."""
+    full-size rehearsal test checks them against closed forms.
+    stark.precompile does not enumerate this function's programs (per-rank slices are other contexts, so other kernels): with a
+    cache directory set each rank stores what it compiles and finds it again at its next start, but nothing is built ahead of time."""
     from . import stark as S
     import time
     t_last = [time.perf_counter()]
