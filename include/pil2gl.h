@@ -29,9 +29,9 @@
  *    stream (or order it against the stream given) and return.
  *    The following _dev calls BLOCK until their work on the stream has finished, because they hand a result to the host or
  *    stage host-side tables in a scratch slot the next call reuses:
- *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi / cols_dot_ext /
+ *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi[_step] / cols_dot_ext /
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
- *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, build_lev (small host tables),
+ *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, compute_fri_pol, build_lev (small host tables),
  *      h1h2, synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
  *      land_rows with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
@@ -287,6 +287,11 @@ int pil2gl_rows_dot_ext_dev(const uint64_t *buf, uint64_t width, uint64_t nRows,
  * two sweeps of two; matrices left with under 32 columns, and PIL2GL_ROWS_DOT_MFMA=0, on the vector kernels.  nOut: 1..4. */
 int pil2gl_rows_dot_ext_multi_dev(const uint64_t *const *bufs, const uint64_t *widths, uint32_t nBufs, uint64_t nRows,
                                   const uint64_t *const *hostCoefs, uint32_t nOut, uint64_t *acc, int accumulate, void *stream);
+/* the same sums over every 2^rowStepBits-th row: acc[r][o] (+)= sum_k sum_c bufs[k][r << rowStepBits][c] * hostCoefs[k][o][c], r < nRows,
+ * acc dense (nRows x nOut x 3).  With rowStepBits = nBitsExt - nBits these are the rows of an extended matrix that lie on the coset
+ * 7 <w_N>.  Same kernels and the same choice among them as the dense call (its rowStepBits = 0 case); rowStepBits: 0..20. */
+int pil2gl_rows_dot_ext_multi_step_dev(const uint64_t *const *bufs, const uint64_t *widths, uint32_t nBufs, uint64_t nRows, uint32_t rowStepBits,
+                                       const uint64_t *const *hostCoefs, uint32_t nOut, uint64_t *acc, int accumulate, void *stream);
 /* f[r] = Horner in vf1 over the openings of (acc[r][o] - K_o) * xDivXSubXi[r][o]   (friPolinomial.js:38-50);
  * hostK: nOpen x 3 (K_o = sum_j ev_j vf2^(n_o - j)). */
 int pil2gl_fri_combine_dev(const uint64_t *acc, const uint64_t *hostK, const uint64_t vf1[3], const uint64_t *xDivXSubXi,
@@ -297,6 +302,23 @@ int pil2gl_fri_combine_dev(const uint64_t *acc, const uint64_t *hostK, const uin
  * evMap -- with a previous-row opening ([-1, 0, 1]) that is 0, 1, -1, not the order of openingPoints. */
 int pil2gl_fri_combine_order_dev(const uint64_t *acc, const uint64_t *hostK, const uint64_t vf1[3], const uint64_t *xDivXSubXi,
                                  uint32_t nOpen, const uint32_t *order, uint64_t nRows, uint64_t *f, void *stream);
+/* The whole FRI polynomial (computeFRIStark, stark_gen_helpers.js:275-335) from the extended matrices, in one call:
+ *     F(x) = Horner in vf1, in `order`, of  (sum_k sum_c bufs[k][x][c] * hostCoefs[k][o][c] - K_o) * x / (x - xi_o),   o < nOpen,
+ * on all 2^nBitsExt rows of fExt (x 3).  bufs[k]: device 2^nBitsExt x widths[k]; hostCoefs[k]: nOpen x widths[k] x 3; hostK: nOpen x 3;
+ * xis: nOpen x 3 (host); order: as in pil2gl_fri_combine_order_dev.
+ * PRECONDITION: every column is a polynomial of degree < 2^nBits and K_o is built from the TRUE evaluations of those same columns at xi_o
+ * (K_o = sum_c col_c(xi_o) * coef[o][c]).  Then each bracket vanishes at xi_o and F has degree < 2^nBits -- for any witness, satisfied
+ * or not -- so F is fixed by its values on the extended rows k << (nBitsExt - nBits), the coset 7 <w_N>.  The call computes x / (x - xi),
+ * the row sums and the combination on those 2^nBits rows only and extends the result (inverse transform, zero padding, plain forward
+ * transform: one unshifted extension).  Exact field arithmetic, canonical words: fExt equals, word for word, what
+ * x_div_x_sub_xi -> rows_dot_ext_multi -> fri_combine_order give on every row.  With any other K the two differ (F is then no polynomial
+ * of that degree); the three entries above remain for that case.  nBitsExt == nBits is the full-domain sequence itself.
+ * PIL2GL_EINVAL, before anything is launched or written: a base-field xi_o that is a row of the 2^nBitsExt-row domain (the rule of
+ * pil2gl_x_div_x_sub_xi_dev, applied although only every 2^(nBitsExt - nBits)-th row is visited), nBitsExt < nBits, nOpen outside 1..4,
+ * an order that is no permutation.  Blocks like rows_dot_ext_multi and fri_combine_order (host-side weights); the extension is only enqueued. */
+int pil2gl_compute_fri_pol_dev(const uint64_t *const *bufs, const uint64_t *widths, uint32_t nBufs, const uint64_t *const *hostCoefs, uint32_t nOpen,
+                               const uint64_t *hostK, const uint64_t vf1[3], const uint32_t *order, const uint64_t *xis,
+                               uint32_t nBits, uint32_t nBitsExt, uint64_t *fExt, void *stream);
 /* hostOut[l][c] = sum_k buf[k*rowStep][c] * levs[l][k]   (stark_gen_helpers.js:250-264 for every column of a buffer
  * and every opening at once; hostOut: nLev x width x 3, levs[l]: device nRows x 3). */
 int pil2gl_cols_dot_ext_dev(const uint64_t *buf, uint64_t width, uint64_t nRows, uint64_t rowStep, const uint64_t *const *levs,

@@ -45,6 +45,7 @@ struct RowsDotParams {
     u32 nOut;
     u64 *acc;                   // [nRows][nOut][3]
     u32 accumulate;
+    u64 rowPitch;               // words from one row of the sum to the next: stride << rowStepBits (row r of the sum is matrix row r << rowStepBits).  Addresses only: the weights are indexed with stride
 };
 
 // lanes <-> rows; the 64 x CW tile of a wave is staged through LDS with coalesced row-segment loads
@@ -74,9 +75,9 @@ __global__ void __launch_bounds__(256) rows_dot_kernel(RowsDotParams P) {
     const u32 lr = lane >> 4, lc = lane & 15;
     auto fetch = [&](u64 c0) {
         const u32 cw = (u32)min((u64)CW, P.width - c0);
-        u64 off = (row0 + lr) * P.stride + P.col0 + c0 + lc;
+        u64 off = (row0 + lr) * P.rowPitch + P.col0 + c0 + lc;
         asm volatile("" : "+v"(off));
-        const u64 step = 4 * P.stride;
+        const u64 step = 4 * P.rowPitch;
 #pragma unroll
         for (u32 i = 0; i < CW; i++) {
             const u64 gr = row0 + lr + 4 * i;
@@ -156,7 +157,7 @@ __global__ void __launch_bounds__(256) rows_dot_stream_kernel(RowsDotParams P, u
             for (u32 i = 0; i < NB; i++) {
                 const bool in = u0 + 256 * i + tid < total;
                 at[i] = in ? r * LD + c : 0xFFFFFFFFu;
-                v[i] = (in && row0 + r < P.nRows) ? P.buf[(row0 + r) * P.stride + P.col0 + c0 + c] : 0;
+                v[i] = (in && row0 + r < P.nRows) ? P.buf[(row0 + r) * P.rowPitch + P.col0 + c0 + c] : 0;
                 c += dr; r += dq;
                 if (c >= w) { c -= w; r++; }
             }
@@ -239,7 +240,7 @@ constexpr u32 MF_MAXSEG = 4;
 struct RowsDotMfmaParams {
     // the K dimension is the concatenation of up to MF_MAXSEG matrices with the same rows (a stage's matrices side by side):
     // segment k holds segW[k] (even) columns and starts at 16-byte unit segU0[k] of the staged row
-    const u64 *segBuf[MF_MAXSEG]; u32 segW[MF_MAXSEG], segPitch[MF_MAXSEG], segU0[MF_MAXSEG], nSeg;      // segBuf: the window's first column; segPitch: words per matrix row
+    const u64 *segBuf[MF_MAXSEG]; u32 segW[MF_MAXSEG], segPitch[MF_MAXSEG], segU0[MF_MAXSEG], nSeg;      // segBuf: the window's first column; segPitch: words from one row of the sum to the next (the matrix's row length << rowStepBits)
     u64 nRows; u32 width, nOut;         // width: all segments together
     const v4i *atab;            // [kSteps][NT][64 lanes]: 16 digit bytes per lane
     const u64 *bias;            // [3*nOut] canonical
@@ -439,13 +440,13 @@ using namespace pil2gl;
 // host side of rows_dot_mfma_kernel: signed base-256 digits of the weights laid out as the MFMA's A operand, the constant per output.
 // Segment k: nRows x widths[k] matrix bufs[k] with weights hostCoefs[k] ([nOut][widths[k]][3]); out = sum over all segments' columns.
 // a segment of the staged row: columns [col0, col0 + width) of an nRows x pitch matrix, with the weights of those columns
-struct MfSeg { const u64 *buf; u64 pitch, col0, width; const u64 *coef; };     // coef: [nOut][pitch][3], the whole matrix's
+struct MfSeg { const u64 *buf; u64 pitch, col0, width; const u64 *coef; u64 rowPitch; };     // coef: [nOut][pitch][3], the whole matrix's; rowPitch: pitch << rowStepBits, words between the rows read
 static u64 mf_padded(const MfSeg *segs, u32 n) { u64 t = 0; for (u32 k = 0; k < n; k++) t += segs[k].width + (segs[k].width & 1); return t; }
 static bool rows_dot_mfma_fits(const MfSeg *segs, u32 nSeg, u32 nOut) {
     const char *sw = getenv("PIL2GL_ROWS_DOT_MFMA");
     if ((sw && sw[0] == '0') || nOut < 1 || nOut > 2 || nSeg < 1 || nSeg > MF_MAXSEG) return false;
     for (u32 k = 0; k < nSeg; k++)
-        if (segs[k].width == 0 || ((uintptr_t)segs[k].buf & 7) || (segs[k].pitch >> 31)) return false;
+        if (segs[k].width == 0 || ((uintptr_t)segs[k].buf & 7) || (segs[k].rowPitch >> 31)) return false;
     const u64 total = mf_padded(segs, nSeg);                    // an odd segment is staged with a zero word after each row
     if (total < 32 || total > MF_MAXW) return false;
     // the kernel keeps a 64-row tile and the digit planes in up to ~144 KB of LDS: only where a workgroup may have that much
@@ -467,7 +468,7 @@ static int launch_rows_dot_mfma(const MfSeg *segs, u32 nBufs, u64 nRows, u32 nOu
     const u32 nO = 3 * nOut;
     const u64 winWidth = mf_padded(segs, nBufs);                // columns of the staged row: every segment rounded up to an even count
     bool odd = false;                                           // rows of some segment start on 8-byte boundaries only
-    for (u32 k = 0; k < nBufs; k++) odd |= ((segs[k].width | segs[k].pitch | segs[k].col0) & 1) != 0 || ((uintptr_t)segs[k].buf & 15);
+    for (u32 k = 0; k < nBufs; k++) odd |= ((segs[k].width | segs[k].rowPitch | segs[k].col0) & 1) != 0 || ((uintptr_t)segs[k].buf & 15);
     std::vector<signed char> dig((size_t)winWidth * nO * 9, 0);
     std::vector<u64> bias(nO);
     unsigned __int128 k128 = 0, offs = 0;
@@ -519,7 +520,7 @@ static int launch_rows_dot_mfma(const MfSeg *segs, u32 nBufs, u64 nRows, u32 nOu
     RowsDotMfmaParams P;
     u32 u0 = 0;
     for (u32 k = 0; k < MF_MAXSEG; k++) {
-        P.segBuf[k] = k < nBufs ? segs[k].buf + segs[k].col0 : nullptr; P.segW[k] = k < nBufs ? (u32)segs[k].width : 0; P.segPitch[k] = k < nBufs ? (u32)segs[k].pitch : 0; P.segU0[k] = u0;
+        P.segBuf[k] = k < nBufs ? segs[k].buf + segs[k].col0 : nullptr; P.segW[k] = k < nBufs ? (u32)segs[k].width : 0; P.segPitch[k] = k < nBufs ? (u32)segs[k].rowPitch : 0; P.segU0[k] = u0;
         if (k < nBufs) u0 += (u32)((segs[k].width + 1) / 2);
     }
     P.nSeg = nBufs; P.nRows = nRows; P.width = (u32)winWidth; P.nOut = nOut; P.atab = (const v4i *)d; P.bias = d + atWords;
@@ -540,7 +541,7 @@ static int launch_rows_dot_mfma(const MfSeg *segs, u32 nBufs, u64 nRows, u32 nOu
 }
 
 // the vector-ALU kernels (whole-row streaming tiles / column tiles): any shape
-static int rows_dot_ext_plain(const uint64_t *buf, uint64_t width, uint64_t nRows, const uint64_t *hostCoef, uint32_t nOut,
+static int rows_dot_ext_plain(const uint64_t *buf, uint64_t width, uint64_t nRows, uint32_t rowStepBits, const uint64_t *hostCoef, uint32_t nOut,
                               uint64_t *acc, int accumulate, void *stream) {
     hipStream_t st = as_stream(stream);
     const u64 nC = (u64)nOut * width * 3;
@@ -558,7 +559,7 @@ static int rows_dot_ext_plain(const uint64_t *buf, uint64_t width, uint64_t nRow
     const char *sw = getenv("PIL2GL_ROWS_DOT_STREAM");
     const bool stream_ok = !(sw && sw[0] == '0');
     for (u64 col0 = 0; col0 < width; col0 += 1024) {
-        RowsDotParams P = { buf, std::min<u64>(1024, width - col0), nRows, width, col0, (const u32 *)d, nOut, acc, (u32)(accumulate != 0 || col0 != 0) };
+        RowsDotParams P = { buf, std::min<u64>(1024, width - col0), nRows, width, col0, (const u32 *)d, nOut, acc, (u32)(accumulate != 0 || col0 != 0), width << rowStepBits };
         if (stream_ok && P.width >= 32) {               // long rows: whole-row streaming tiles
             const u32 nch = (u32)((P.width + STREAM_CW_MAX - 1) / STREAM_CW_MAX), cw = (u32)((P.width + nch - 1) / nch), LD = cw | 1;
             const size_t lds = 8 * std::max<size_t>((size_t)64 * LD, (size_t)nOut * 18 * 64);
@@ -594,7 +595,7 @@ static int rows_dot_ext_plain(const uint64_t *buf, uint64_t width, uint64_t nRow
 // column windows, windows and narrow matrices are packed (largest first) into launches of at most MF_MAXSEG segments and MF_MAXW columns,
 // each launch after the first accumulating.  Matrices left in a launch of under 32 columns go to rows_dot_ext_dev one by one.
 // -> false: not for the matrix cores (more than two outputs, PIL2GL_ROWS_DOT_MFMA=0, no wide launch at all)
-static bool rows_dot_mfma_plan(const uint64_t *const *bufs, const uint64_t *widths, const uint64_t *const *hostCoefs, u32 nBufs, u32 nOut,
+static bool rows_dot_mfma_plan(const uint64_t *const *bufs, const uint64_t *widths, const uint64_t *const *hostCoefs, u32 nBufs, u32 nOut, u32 rowStepBits,
                                std::vector<std::vector<MfSeg>> &launches, std::vector<u32> &leftovers) {
     std::vector<MfSeg> wins;
     for (u32 k = 0; k < nBufs; k++) {
@@ -602,7 +603,7 @@ static bool rows_dot_mfma_plan(const uint64_t *const *bufs, const uint64_t *widt
         if (W == 0) continue;
         const u64 n = (W + (W & 1) + MF_MAXW - 1) / MF_MAXW;
         u64 per = (W + n - 1) / n; per += per & 1;
-        for (u64 c0 = 0; c0 < W; c0 += per) wins.push_back({ bufs[k], W, c0, std::min<u64>(per, W - c0), hostCoefs[k] });
+        for (u64 c0 = 0; c0 < W; c0 += per) wins.push_back({ bufs[k], W, c0, std::min<u64>(per, W - c0), hostCoefs[k], W << rowStepBits });
     }
     std::stable_sort(wins.begin(), wins.end(), [](const MfSeg &a, const MfSeg &b) { return a.width > b.width; });
     std::vector<u64> fill;
@@ -641,15 +642,23 @@ int pil2gl_rows_dot_ext_dev(const uint64_t *buf, uint64_t width, uint64_t nRows,
 
 int pil2gl_rows_dot_ext_multi_dev(const uint64_t *const *bufs, const uint64_t *widths, uint32_t nBufs, uint64_t nRows,
                                   const uint64_t *const *hostCoefs, uint32_t nOut, uint64_t *acc, int accumulate, void *stream) {
+    return pil2gl_rows_dot_ext_multi_step_dev(bufs, widths, nBufs, nRows, 0, hostCoefs, nOut, acc, accumulate, stream);
+}
+// row r of the sums is row r << rowStepBits of every matrix (the rows k * 2^eb of an extended matrix: one coset); acc stays dense.  The step
+// only lengthens the kernels' row pitch: same launches, same paths as the dense call, which is the step-0 case
+int pil2gl_rows_dot_ext_multi_step_dev(const uint64_t *const *bufs, const uint64_t *widths, uint32_t nBufs, uint64_t nRows, uint32_t rowStepBits,
+                                       const uint64_t *const *hostCoefs, uint32_t nOut, uint64_t *acc, int accumulate, void *stream) {
     P2_TRY(ensure_init());
     if (!bufs || !widths || !hostCoefs || !acc || nBufs == 0) return fail(PIL2GL_EINVAL, "null buffer");
     for (uint32_t k = 0; k < nBufs; k++) if (!bufs[k] || !hostCoefs[k]) return fail(PIL2GL_EINVAL, "null buffer");
     if (nOut < 1 || nOut > 4) return fail(PIL2GL_EINVAL, "nOut must be 1..4");
+    if (rowStepBits > 20) return fail(PIL2GL_EINVAL, "rowStepBits must be 0..20");
+    for (uint32_t k = 0; k < nBufs; k++) if (widths[k] >> 40) return fail(PIL2GL_EINVAL, "matrix too wide");
     if (nRows == 0) return PIL2GL_OK;
     std::vector<std::vector<MfSeg>> launches;
     std::vector<u32> leftovers;
     bool acc1 = accumulate != 0;
-    if (rows_dot_mfma_plan(bufs, widths, hostCoefs, nBufs, nOut, launches, leftovers)) {
+    if (rows_dot_mfma_plan(bufs, widths, hostCoefs, nBufs, nOut, rowStepBits, launches, leftovers)) {
         // the kernel produces one or two outputs per launch: three or four opening points take two sweeps of the same launches
         // (outputs 0-1, then 2-3: HBM-bound passes against one vector-ALU-bound pass), writing their own words of the caller's rows
         for (u32 o0 = 0; o0 < nOut; o0 += 2) {
@@ -662,12 +671,12 @@ int pil2gl_rows_dot_ext_multi_dev(const uint64_t *const *bufs, const uint64_t *w
             }
         }
         acc1 = true;
-        for (u32 k : leftovers) P2_TRY(rows_dot_ext_plain(bufs[k], widths[k], nRows, hostCoefs[k], nOut, acc, 1, stream));
+        for (u32 k : leftovers) P2_TRY(rows_dot_ext_plain(bufs[k], widths[k], nRows, rowStepBits, hostCoefs[k], nOut, acc, 1, stream));
         return PIL2GL_OK;
     }
     for (uint32_t k = 0; k < nBufs; k++) {
         if (widths[k] == 0) continue;
-        P2_TRY(rows_dot_ext_plain(bufs[k], widths[k], nRows, hostCoefs[k], nOut, acc, acc1 ? 1 : 0, stream)); acc1 = true;
+        P2_TRY(rows_dot_ext_plain(bufs[k], widths[k], nRows, rowStepBits, hostCoefs[k], nOut, acc, acc1 ? 1 : 0, stream)); acc1 = true;
     }
     return PIL2GL_OK;
 }

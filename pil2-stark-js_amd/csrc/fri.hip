@@ -522,6 +522,43 @@ int pil2gl_x_div_x_sub_xi_cosets_dev(uint32_t nBitsExt, uint32_t extBits, const 
     KERNEL_CHECK();
     return PIL2GL_OK;
 }
+// The whole FRI polynomial (stark_gen_helpers.js:275-335).  Every column has degree < N and K_o holds the columns' own evaluations at xi_o,
+// so each bracket of  F(x) = sum_o (sum_c coef[o][c] col_c(x) - K_o) x / (x - xi_o)  vanishes at xi_o and deg F < N, whatever the witness:
+// F is fixed by its values on the extended rows k << eb, the coset 7 <w_N>.  Those N values are G(w_N^k) for G(x) = F(7 x); the unshifted
+// extension of G (inverse passes, no coset scaling, forward passes onto every coset w_E^j <w_N>) is G(w_E^i) = F(7 w_E^i): f_ext, the same
+// canonical words the full-domain sequence writes.  One lde_launch: the inverse passes leave bit-reversed rows that the mid kernel reads as
+// they are, so there is no natural-order coefficient matrix, no reorder and no second read of it.
+// Scratch: 14 (x / (x - xi), N x 3 nOpen) and 15 (the row sums, the same size) are the quotient stage's slots -- that stage is over when
+// this one runs, and at config 3 they already have the size -- and 1 (the N x 3 values) is the FRI fold's, which runs after.
+int pil2gl_compute_fri_pol_dev(const uint64_t *const *bufs, const uint64_t *widths, uint32_t nBufs, const uint64_t *const *hostCoefs, uint32_t nOpen,
+                               const uint64_t *hostK, const uint64_t vf1[3], const uint32_t *order, const uint64_t *xis,
+                               uint32_t nBits, uint32_t nBitsExt, uint64_t *fExt, void *stream) {
+    P2_TRY(ensure_init());
+    if (!bufs || !widths || !hostCoefs || !hostK || !vf1 || !order || !xis || !fExt || nBufs == 0) return fail(PIL2GL_EINVAL, "null argument");
+    for (u32 k = 0; k < nBufs; k++) if (!bufs[k] || !hostCoefs[k]) return fail(PIL2GL_EINVAL, "null buffer");
+    if (nBitsExt < nBits || nBitsExt > PIL2GL_MAX_NTT_BITS) return fail(PIL2GL_EINVAL, "bad domain sizes (nBits %u, nBitsExt %u)", nBits, nBitsExt);
+    if (nOpen < 1 || nOpen > 4) return fail(PIL2GL_EINVAL, "nOpen must be 1..4");
+    u32 seen = 0;
+    for (u32 k = 0; k < nOpen; k++) {
+        if (order[k] >= nOpen || (seen >> order[k] & 1)) return fail(PIL2GL_EINVAL, "order must be a permutation of the openings");
+        seen |= 1u << order[k];
+    }
+    const u64 GP = 0xFFFFFFFF00000001ull;
+    for (u32 o = 0; o < nOpen; o++)     // the rule of the full table, although only the rows k << eb are visited: the same inputs are refused as before
+        if (base_point_is_a_row(xis[3 * o] % GP, xis[3 * o + 1] % GP, xis[3 * o + 2] % GP, nBitsExt))
+            return fail(PIL2GL_EINVAL, "xi of opening %u is a point of the 2^%u-row coset 7<w>: x / (x - xi) divides by zero at that row", o, nBitsExt);
+    const u32 eb = nBitsExt - nBits;
+    const u64 N = 1ull << nBits;
+    u64 *xdiv, *acc, *f = fExt;
+    P2_TRY(scratch(14, N * 3 * nOpen, &xdiv));
+    P2_TRY(scratch(15, N * 3 * nOpen, &acc));
+    if (eb) P2_TRY(scratch(1, N * 3, &f));
+    for (u32 o = 0; o < nOpen; o++) P2_TRY(pil2gl_x_div_x_sub_xi_cosets_dev(nBitsExt, eb, xis + 3 * o, nOpen, o, 0, 1, xdiv, stream));
+    P2_TRY(pil2gl_rows_dot_ext_multi_step_dev(bufs, widths, nBufs, N, eb, hostCoefs, nOpen, acc, 0, stream));
+    P2_TRY(pil2gl_fri_combine_order_dev(acc, hostK, vf1, xdiv, nOpen, order, N, f, stream));
+    if (!eb) return PIL2GL_OK;
+    return lde_launch(f, 3, nBits, fExt, nBitsExt, as_stream(stream), 0, 0, nullptr, true);
+}
 // LEv = F.ifft of (xi^k)_{k<N} (stark_gen_helpers.js:216-231).  The inverse transform of a geometric sequence has a closed form,
 //     LEv[j] = (1/N) sum_k (xi w^-j)^k = (1 - xi^N) / N * w^j / (w^j - xi) = (1 - xi^N) / N * x_j / (x_j - 7 xi),   x_j = 7 w^j,
 // i.e. the batched-inversion kernel of the FRI table at the point 7 xi over the N rows, times one extension constant: one sweep that

@@ -120,8 +120,10 @@ SIGNATURES = {
     "pil2gl_compute_evals_dev": (_I, [C.POINTER(EvalDesc), _U32, _U32, _U32, C.POINTER(vp), _U32, vp, vp]),
     "pil2gl_rows_dot_ext_dev": (_I, [vp, _U64, _U64, vp, _U32, vp, _I, vp]),
     "pil2gl_rows_dot_ext_multi_dev": (_I, [vp, vp, _U32, _U64, vp, _U32, vp, _I, vp]),
+    "pil2gl_rows_dot_ext_multi_step_dev": (_I, [vp, vp, _U32, _U64, _U32, vp, _U32, vp, _I, vp]),
     "pil2gl_fri_combine_dev": (_I, [vp, vp, vp, vp, _U32, _U64, vp, vp]),
     "pil2gl_fri_combine_order_dev": (_I, [vp, vp, vp, vp, _U32, vp, _U64, vp, vp]),
+    "pil2gl_compute_fri_pol_dev": (_I, [vp, vp, _U32, vp, _U32, vp, vp, vp, vp, _U32, _U32, vp, vp]),
     "pil2gl_cols_dot_ext_dev": (_I, [vp, _U64, _U64, _U64, C.POINTER(vp), _U32, vp, vp]),
     "pil2gl_cols_dot_ext_multi_dev": (_I, [vp, vp, _U32, _U64, _U64, vp, _U32, vp, vp]),
     "pil2gl_cols_dot_ext_range_dev": (_I, [vp, vp, vp, vp, _U32, _U64, _U64, vp, _U32, vp, vp]),
