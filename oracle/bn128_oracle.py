@@ -16,6 +16,8 @@ merklehash_bn128_p.js:4-5,12,290-292 and merklehash_bn128_worker.js:55-95,138.  
 Pinned end to end by a proof the reference itself wrote: test/final/verifier.proof.zkin.json (arity 4, t=5 and the
 generated t=4), tests/test_bn128_oracle.py.
 """
+from operator import mul
+
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617     # BN254 scalar field
 N_ROUNDS_F = 8
 N_ROUNDS_P = [56, 57, 56, 60, 60, 63, 64, 63, 60, 66, 60, 65, 70, 60, 64, 68]        # poseidon.circom:8, t = 2..17
@@ -83,6 +85,90 @@ def poseidon(inputs, init_state=0, n_out=1):
             st[0] = pow(st[0], 5, R)
         st = [sum(M[i][j] * st[j] for j in range(t)) % R for i in range(t)]
     return st[:n_out]
+
+
+# ---- round access and the inverse permutation (tests/bn128_chosen.py: states chosen in the middle of the permutation).
+#      The S-box is a bijection (gcd(5, R-1) = 1) and M is invertible, so every round runs backwards.
+SBOX_INV = pow(5, -1, R - 1)                                                         # (x^5)^SBOX_INV = x
+_MINV = {}
+
+
+def matrix_inverse(t):
+    """M^-1 mod R for width t (Gauss-Jordan), cached"""
+    if t not in _MINV:
+        M = poseidon_constants(t)[1]
+        A = [list(row) + [int(i == k) for k in range(t)] for i, row in enumerate(M)]
+        for c in range(t):
+            piv = next(r for r in range(c, t) if A[r][c])
+            A[c], A[piv] = A[piv], A[c]
+            iv = pow(A[c][c], R - 2, R)
+            A[c] = [v * iv % R for v in A[c]]
+            for r in range(t):
+                if r != c and A[r][c]:
+                    f = A[r][c]
+                    A[r] = [(x - f * y) % R for x, y in zip(A[r], A[c])]
+        _MINV[t] = [row[t:] for row in A]
+    return _MINV[t]
+
+
+def is_full_round(t, r):
+    return r < N_ROUNDS_F // 2 or r >= N_ROUNDS_F // 2 + N_ROUNDS_P[t - 2]
+
+
+def _check_round(t, r, u):
+    n_rounds = N_ROUNDS_F + N_ROUNDS_P[t - 2]
+    if not 0 <= r <= n_rounds or len(u) != t:
+        raise ValueError("round %d / %d values for width %d" % (r, len(u), t))
+    return n_rounds
+
+
+def poseidon_from_round(t, r, u):
+    """u: the state of width t as it enters the S-box of round r (round r's constants added) -> the permutation's final state.
+    r = RF + rp: u is the final state itself."""
+    n_rounds = _check_round(t, r, u)
+    C, M = poseidon_constants(t)
+    st = [int(a) % R for a in u]
+    for q in range(r, n_rounds):
+        if q > r:
+            st = [(a + C[t * q + j]) % R for j, a in enumerate(st)]
+        if is_full_round(t, q):
+            st = [pow(a, 5, R) for a in st]
+        else:
+            st[0] = pow(st[0], 5, R)
+        st = [sum(map(mul, row, st)) % R for row in M]
+    return st
+
+
+def poseidon_preimage(t, r, u):
+    """u as in poseidon_from_round -> the permutation's input state: element 0 is the initState, the rest the inputs"""
+    n_rounds = _check_round(t, r, u)
+    C = poseidon_constants(t)[0]
+    Mi = matrix_inverse(t)
+    st = [int(a) % R for a in u]
+    for q in range(r, -1, -1):                    # st: the S-box input of round q (q = n_rounds: the output of the last linear layer)
+        if q < n_rounds:
+            st = [(a - C[t * q + j]) % R for j, a in enumerate(st)]
+        if q == 0:
+            break
+        st = [sum(map(mul, row, st)) % R for row in Mi]
+        if is_full_round(t, q - 1):
+            st = [pow(a, SBOX_INV, R) for a in st]
+        else:
+            st[0] = pow(st[0], SBOX_INV, R)
+    return st
+
+
+def poseidon_sbox_input(t, r, y):
+    """y: the state as it LEAVES the S-box of round r (the operand of that round's linear layer) -> the u of the two functions above:
+    the fifth root of every element in a full round, of element 0 alone in a partial one (the others pass the S-box unchanged)"""
+    n_rounds = _check_round(t, r, y)
+    if r == n_rounds:
+        raise ValueError("no S-box after the last round")
+    u = [int(a) % R for a in y]
+    if is_full_round(t, r):
+        return [pow(a, SBOX_INV, R) for a in u]
+    u[0] = pow(u[0], SBOX_INV, R)
+    return u
 
 
 def linear_hash_worker(vals, arity, custom):
