@@ -5,13 +5,13 @@
 // (circomlibjs@0.1.7 buildPoseidonWasm `poseidon`, wasmcurves@0.1.5 F1m `frm_toMontgomery`; neither is under the
 // reference tree).  The permutation follows the in-tree statement circuits.bn128/custom/poseidon.circom:6-45
 // (t = nInputs+1, RF = 8, RP = N_ROUNDS_P[t-2], x^5, dense round constants and MDS); its parameters are produced on the
-// host by the published Poseidon parameter generation (Grain LFSR) and agree with every constant set the reference holds
+// host (bn_params.cpp) by the published Poseidon parameter generation (Grain LFSR) and agree with every constant set the reference holds
 // (tests/test_bn128_oracle.py pins the same generator; tests/test_gpu_bn128.py compares this one with it).
 //
 // One pipeline per width (bn_perm), one permutation per lane, the linear layers on the matrix cores (bn_mfma.cuh) and the S-box in radix
 // 2^29 (bn_field29.cuh):
 //   t = 2..4    perm_small: round by round as poseidon.circom states it, state and tiles in registers;
-//   t = 5..16   the partial rounds in the sparse form (derivation below, next to derive_sparse(): 2t-1 products per round instead of t^2),
+//   t = 5..16   the partial rounds in the sparse form (derivation: bn_params.cpp, next to derive_sparse(): 2t-1 products per round instead of t^2),
 //               four to a block on the matrix cores (partial_rounds_mfma), the rp % 4 rounds left over on the vector ALU (partial_rounds);
 //   t = 17      the same phases in ONE function body (the arity-16 trees).
 // Between the layers the state is a lazy representative (< 2^255) in LDS as [element][limb][lane] for the lower elements and in private
@@ -19,6 +19,8 @@
 // Few permutations (<= WAVE_PER_PERM_MAX) run the circuit's dense statement instead, a wave each (bn_sponge_chain_kernel).
 // Nodes are stored as the reference stores them: 4 little-endian u64 words of the Montgomery form.
 #include "common.h"
+#include "bn_consts.h"
+#include "bn_params.h"
 #include "bn_field.cuh"
 #include "bn_mfma.cuh"
 #include "bn_field29.cuh"
@@ -33,12 +35,7 @@ using bn::u32;
 
 namespace {
 
-// State elements kept in LDS (the rest in private memory: "Where the state lives" below): 10 = 20 KB per wave, two waves per SIMD.  With the
-// batch in which the partial rounds fetch the others' operands (partial_rounds_mfma_impl::rows: a batch of four leaves the registers for the
-// accumulators) it shapes the order of the tile stream the host writes (mfma_partial_tables).
-constexpr int BN_LDS_ELEMS = 10;
-constexpr int BN_HI_BATCH = 4;
-constexpr int BN_SMALL_T = 4;                        // widths up to this run the permutation round by round with the state and the layer's tiles in registers (perm_small)
+using namespace bnc;                               // BN_LDS_ELEMS, BN_HI_BATCH, BN_SMALL_T, the round numbers, MFMA_AHEAD: shared with the host parameter builder
 constexpr int BN_BLOCK = 64;                         // lanes of a wave = permutations a wave carries
 // Waves per workgroup.  Every wave works alone on its own 64 permutations and its own LDS slice; what the waves of a workgroup share is
 // TIME: a barrier at the start of every matrix phase (dense layer, rows on y, column update) keeps them on the same operand tiles, so that
@@ -48,79 +45,9 @@ constexpr int BN_THREADS = BN_BLOCK * BN_WG_WAVES;
 // Up to this many permutations in one call run a wave each (bn_sponge_chain_kernel): a lane each would leave them at the latency of one wave
 // working alone (~3 ms at t = 17); a wave each runs them in ~0.5 ms while the SIMDs outnumber them
 constexpr long WAVE_PER_PERM_MAX = 2048;
-constexpr int N_ROUNDS_F = 8;
-const int N_ROUNDS_P[16] = { 56, 57, 56, 60, 60, 63, 64, 63, 60, 66, 60, 65, 70, 60, 64, 68 };   // poseidon.circom:8
 
-// ------------------------------------------------------------------------------------------ host 256-bit arithmetic
-struct U256 { u64 w[4]; };
-const U256 HR = { { 0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull } };
-const U256 HR2 = { { 0x1bb8e645ae216da7ull, 0x53fe3ab1e35c59e3ull, 0x8c49833d53bb8085ull, 0x0216d0b17f4e44a5ull } };
-const u64 HN0 = 0xc2e1f593efffffffull;
-typedef unsigned __int128 u128;
-
-bool h_ge(const U256 &a, const U256 &b) { for (int i = 3; i >= 0; i--) if (a.w[i] != b.w[i]) return a.w[i] > b.w[i]; return true; }
-U256 h_sub(const U256 &a, const U256 &b) { U256 r; u64 br = 0; for (int i = 0; i < 4; i++) { u128 d = (u128)a.w[i] - b.w[i] - br; r.w[i] = (u64)d; br = (u64)(d >> 64) & 1; } return r; }
-U256 h_addmod(const U256 &a, const U256 &b) {
-    U256 r; u64 c = 0;
-    for (int i = 0; i < 4; i++) { u128 s = (u128)a.w[i] + b.w[i] + c; r.w[i] = (u64)s; c = (u64)(s >> 64); }
-    if (c || h_ge(r, HR)) r = h_sub(r, HR);
-    return r;
-}
-U256 h_addraw(const U256 &a, const U256 &b) { U256 r; u64 c = 0; for (int i = 0; i < 4; i++) { u128 s = (u128)a.w[i] + b.w[i] + c; r.w[i] = (u64)s; c = (u64)(s >> 64); } return r; }
-U256 h_mont(const U256 &a, const U256 &b) {           // a*b/2^256 mod r
-    u64 t[6] = { 0, 0, 0, 0, 0, 0 };
-    for (int i = 0; i < 4; i++) {
-        u64 c = 0;
-        for (int j = 0; j < 4; j++) { u128 x = (u128)a.w[j] * b.w[i] + t[j] + c; t[j] = (u64)x; c = (u64)(x >> 64); }
-        u128 x = (u128)t[4] + c; t[4] = (u64)x; t[5] = (u64)(x >> 64);
-        u64 m = t[0] * HN0;
-        c = (u64)(((u128)m * HR.w[0] + t[0]) >> 64);
-        for (int j = 1; j < 4; j++) { u128 y = (u128)m * HR.w[j] + t[j] + c; t[j - 1] = (u64)y; c = (u64)(y >> 64); }
-        x = (u128)t[4] + c; t[3] = (u64)x; t[4] = t[5] + (u64)(x >> 64);
-    }
-    U256 r = { { t[0], t[1], t[2], t[3] } };
-    if (t[4] || h_ge(r, HR)) r = h_sub(r, HR);
-    return r;
-}
-U256 h_submod(const U256 &a, const U256 &b) { return h_ge(a, b) ? h_sub(a, b) : h_sub(h_addraw(a, HR), b); }   // a, b < r < 2^254
-bool h_is_zero(const U256 &a) { return !(a.w[0] | a.w[1] | a.w[2] | a.w[3]); }
-U256 h_to_mont(const U256 &a) { return h_mont(a, HR2); }
-U256 h_from_mont(const U256 &a) { U256 one = { { 1, 0, 0, 0 } }; return h_mont(a, one); }
-U256 h_inv_mont(const U256 &a) {                      // a^(r-2), Montgomery in and out
-    U256 e = HR; e.w[0] -= 2;
-    U256 acc = h_to_mont(U256{ { 1, 0, 0, 0 } });
-    for (int i = 255; i >= 0; i--) {
-        acc = h_mont(acc, acc);
-        if ((e.w[i / 64] >> (i % 64)) & 1) acc = h_mont(acc, a);
-    }
-    return acc;
-}
-
-// ------------------------------------------------------------------------------------------ Poseidon parameters
-// Grain LFSR parameter stream of the Poseidon paper's reference generator: 80-bit register initialised with
-// field=1 (2 bits), sbox=0 (4), n=254 (12), t (12), RF (10), RP (10), thirty ones; 160 warm-up steps; output bits are
-// self-shrunk (a 1 passes the next bit, a 0 drops it); field elements = 254 bits MSB first, rejected when >= r (round
-// constants) or reduced mod r (the 2t Cauchy points); M[i][j] = 1/(x_i + y_j).
-struct Grain {
-    uint8_t b[80]; int p = 0;
-    int step() { int nb = b[(p + 62) % 80] ^ b[(p + 51) % 80] ^ b[(p + 38) % 80] ^ b[(p + 23) % 80] ^ b[(p + 13) % 80] ^ b[p]; b[p] = (uint8_t)nb; p = (p + 1) % 80; return nb; }
-    int next() { int nb = step(); while (!nb) { step(); nb = step(); } return step(); }
-    U256 rnd() { U256 v = { { 0, 0, 0, 0 } }; for (int i = 0; i < 254; i++) { for (int k = 3; k > 0; k--) v.w[k] = (v.w[k] << 1) | (v.w[k - 1] >> 63); v.w[0] = (v.w[0] << 1) | (u64)next(); } return v; }
-    Grain(int t, int rp) {
-        int n = 0;
-        auto put = [&](unsigned v, int w) { for (int i = w - 1; i >= 0; i--) b[n++] = (v >> i) & 1; };
-        put(1, 2); put(0, 4); put(254, 12); put((unsigned)t, 12); put(N_ROUNDS_F, 10); put((unsigned)rp, 10);
-        while (n < 80) b[n++] = 1;
-        for (int i = 0; i < 160; i++) step();
-    }
-};
-
-// device tables of one state width t, Montgomery form, 8 limbs per element, one allocation:
-//   C8[8][t]  constants of the 4+4 full rounds (the first of the second half also carries what the partial rounds pushed out)
-//   M[t][t]   dense MDS;  S[RP] scalar constants;  V[RP][t-1], W[RP][t-1] sparse rows / columns
-//   Cd[(8+RP)][t] the original constants (the dense statement of the chain kernel, perm_small's first round)
-//   Mt / Dt   the dense layer and D = diag(1, Mhat^RP) as matrix-core operand tiles (bn_mfma.cuh), MK / DK their per-row constants;
-//   Pt        the tile stream of the blocked partial rounds, KR / KU its row constants (mfma_partial_tables)
+// device tables of one state width t (their construction and layout: bn_params.h), three allocations: the elements in Montgomery form, 8 limbs each,
+// the matrix-core operand tiles and the row constants
 struct Params { int t = 0, rp = 0; u32 *base = nullptr, *C8, *M, *S, *V, *W, *Cd; u32 m00[8];
                 const bnm::v4i *Mt = nullptr, *Dt = nullptr, *Pt = nullptr; const u32 *MK = nullptr, *DK = nullptr, *KR = nullptr, *KU = nullptr;
                 const bnm::v4i *Mt0 = nullptr; const u32 *MK0 = nullptr, *C0p = nullptr;        // the first layer for inputs S-boxed as plain integers (plain_sbox_store)
@@ -128,282 +55,35 @@ struct Params { int t = 0, rp = 0; u32 *base = nullptr, *C8, *M, *S, *V, *W, *Cd
 Params g_params[18];
 std::mutex g_mu;
 
-typedef std::vector<U256> Vec;
-Vec mat_vec(const Vec &A, const Vec &x, int n) {        // A (n x n) * x
-    Vec y((size_t)n);
-    for (int i = 0; i < n; i++) { U256 a = { { 0, 0, 0, 0 } }; for (int j = 0; j < n; j++) a = h_addmod(a, h_mont(A[(size_t)i * n + j], x[j])); y[i] = a; }
-    return y;
-}
-int mat_inv(Vec &A, int n) {                             // Gauss-Jordan in place (Montgomery form)
-    const U256 one = h_to_mont(U256{ { 1, 0, 0, 0 } });
-    Vec I((size_t)n * n, U256{ { 0, 0, 0, 0 } });
-    for (int i = 0; i < n; i++) I[(size_t)i * n + i] = one;
-    for (int c = 0; c < n; c++) {
-        int p = c;
-        while (p < n && h_is_zero(A[(size_t)p * n + c])) p++;
-        if (p == n) return fail(PIL2GL_EINVAL, "singular MDS sub-matrix");
-        if (p != c) for (int j = 0; j < n; j++) { std::swap(A[(size_t)p * n + j], A[(size_t)c * n + j]); std::swap(I[(size_t)p * n + j], I[(size_t)c * n + j]); }
-        const U256 iv = h_inv_mont(A[(size_t)c * n + c]);
-        for (int j = 0; j < n; j++) { A[(size_t)c * n + j] = h_mont(A[(size_t)c * n + j], iv); I[(size_t)c * n + j] = h_mont(I[(size_t)c * n + j], iv); }
-        for (int r = 0; r < n; r++) {
-            if (r == c || h_is_zero(A[(size_t)r * n + c])) continue;
-            const U256 f = A[(size_t)r * n + c];
-            for (int j = 0; j < n; j++) {
-                A[(size_t)r * n + j] = h_submod(A[(size_t)r * n + j], h_mont(f, A[(size_t)c * n + j]));
-                I[(size_t)r * n + j] = h_submod(I[(size_t)r * n + j], h_mont(f, I[(size_t)c * n + j]));
-            }
-        }
-    }
-    A = I;
-    return PIL2GL_OK;
-}
-
-// Sparse form of the RP partial rounds.  Dense statement: x_{k+1} = M * sigma(x_k + c_k), sigma = x^5 on element 0 only.
-//  (1) constants: with e_0 = c_0, s_k = e_k[0], e_{k+1} = c_{k+1} + M*(0, e_k[1:]), the sequence y_{k+1} = M*sigma'(y_k + s_k e0)
-//      satisfies x_k + c_k = y_k + e_k; what is left, f = M*(0, e_{RP-1}[1:]), joins the next full round's constants.
-//  (2) matrices: M = [[m00, v],[w, Mh]].  With D_k = diag(1, Mh^k), M*D_k = D_{k+1} * [[m00, v*Mh^k],[Mh^-(k+1) w, I]], and
-//      D_k commutes with sigma', so y_k = D_k u_k with u_{k+1} = [[m00, V_k],[W_k, I]] * sigma'(u_k): 2t-1 products;
-//      one dense multiplication by D_RP = diag(1, Mh^RP) closes the sequence.
-int derive_sparse(int t, int rp, const Vec &C, const Vec &M, Vec &C8, Vec &D, Vec &S, Vec &V, Vec &W) {
-    const int n = t - 1;
-    const U256 zero = { { 0, 0, 0, 0 } };
-    Vec Mh((size_t)n * n), v((size_t)n), w((size_t)n);
-    for (int i = 0; i < n; i++) { v[i] = M[(size_t)1 + i]; w[i] = M[(size_t)(i + 1) * t]; for (int j = 0; j < n; j++) Mh[(size_t)i * n + j] = M[(size_t)(i + 1) * t + 1 + j]; }
-    Vec Mhi = Mh;
-    P2_TRY(mat_inv(Mhi, n));
-    S.resize((size_t)rp); V.resize((size_t)rp * n); W.resize((size_t)rp * n); C8.resize((size_t)8 * t);
-    Vec e(C.begin() + (size_t)4 * t, C.begin() + (size_t)5 * t), f;
-    for (int k = 0; k < rp; k++) {
-        S[k] = e[0];
-        Vec et = e; et[0] = zero;
-        Vec Me = mat_vec(M, et, t);
-        if (k + 1 < rp) for (int j = 0; j < t; j++) e[j] = h_addmod(C[(size_t)(5 + k) * t + j], Me[j]);
-        else f = Me;
-    }
-    Vec vk = v, wk = mat_vec(Mhi, w, n);
-    for (int k = 0; k < rp; k++) {
-        for (int j = 0; j < n; j++) { V[(size_t)k * n + j] = vk[j]; W[(size_t)k * n + j] = wk[j]; }
-        Vec nv((size_t)n);
-        for (int j = 0; j < n; j++) { U256 a = zero; for (int i = 0; i < n; i++) a = h_addmod(a, h_mont(vk[i], Mh[(size_t)i * n + j])); nv[j] = a; }
-        vk = nv;
-        wk = mat_vec(Mhi, wk, n);
-    }
-    D.assign((size_t)n * n, zero);
-    const U256 one = h_to_mont(U256{ { 1, 0, 0, 0 } });
-    for (int i = 0; i < n; i++) D[(size_t)i * n + i] = one;
-    for (int k = 0; k < rp; k++) {
-        Vec nd((size_t)n * n);
-        for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) { U256 a = zero; for (int q = 0; q < n; q++) a = h_addmod(a, h_mont(Mh[(size_t)i * n + q], D[(size_t)q * n + j])); nd[(size_t)i * n + j] = a; }
-        D = nd;
-    }
-    for (int r = 0; r < 4; r++) for (int j = 0; j < t; j++) {
-        C8[(size_t)r * t + j] = C[(size_t)r * t + j];
-        C8[(size_t)(4 + r) * t + j] = r == 0 ? h_addmod(C[(size_t)(4 + rp) * t + j], f[j]) : C[(size_t)(4 + rp + r) * t + j];
-    }
-    return PIL2GL_OK;
-}
-
-// Operand tiles and row constants for the matrix cores (layout and derivation: bn_mfma.cuh).
-struct MfmaConsts {
-    U256 P[32];                                      // 2^(8b+32) mod r, plain
-    U256 off;                                        // sum_k ACC_BIAS 256^k mod r
-    MfmaConsts() {
-        U256 v = { { 1, 0, 0, 0 } };
-        for (int e = 0; e < 32; e++) v = h_addmod(v, v);
-        for (int b = 0; b < 32; b++) { P[b] = v; for (int e = 0; e < 8; e++) v = h_addmod(v, v); }
-        off = U256{ { 0, 0, 0, 0 } };
-        v = U256{ { (u64)bnm::ACC_BIAS, 0, 0, 0 } };
-        for (int k = 0; k < 32; k++) { off = h_addmod(off, v); for (int e = 0; e < 8; e++) v = h_addmod(v, v); }
-    }
-};
-// one tile (1 KB, lane order) of the coefficient a0 (Montgomery form); tot += the sum of its 32 constants.  sboxed: the operand this tile
-// multiplies comes straight out of the S-box, i.e. (bn_field29.cuh) carries a factor 2^-20: the coefficient takes it back
-void mfma_tile(const MfmaConsts &mc, const U256 &a0, int8_t *tile, U256 &tot, bool sboxed, const U256 *extra = nullptr) {
-    U256 a = sboxed ? h_mont(a0, h_to_mont(U256{ { 1ull << 20, 0, 0, 0 } })) : a0;
-    if (extra) a = h_mont(a, *extra);                // (a further factor in Montgomery form: the plain-input first layer)
-    for (int b = 0; b < 32; b++) {
-        const U256 c = h_mont(a, mc.P[b]);           // a 2^(8b+32) mod r as a plain integer
-        tot = h_addmod(tot, c);
-        int d[32], carry = 0;
-        for (int k = 0; k < 32; k++) {
-            int v = (int)((c.w[k / 8] >> (8 * (k % 8))) & 255) + carry;
-            carry = v >= 128;
-            d[k] = carry ? v - 256 : v;
-        }                                             // c < 2^254: the top digit takes the last carry
-        const int g = b / 16, sl = b % 16;
-        for (int m = 0; m < 32; m++) {
-            const int pos = 16 * ((m / 4) % 2) + 4 * (m / 8) + m % 4;
-            tile[(size_t)(g * 32 + m) * 16 + sl] = (int8_t)d[pos];
-        }
-    }
-}
-// the row constant: (128 tot - nAcc sum_k ACC_BIAS 256^k) / 2^32 + fold mod r   (nAcc accumulations started at the bias make up the row)
-U256 mfma_row_const(const MfmaConsts &mc, U256 tot, int nAcc, const U256 &fold) {
-    const U256 inv32 = { { 0, 0, 0, 1ull << 32 } };  // 2^224: h_mont(a, 2^224) = a / 2^32
-    for (int e = 0; e < 7; e++) tot = h_addmod(tot, tot);
-    for (int e = 0; e < nAcc; e++) tot = h_submod(tot, mc.off);
-    return h_addmod(h_mont(tot, inv32), fold);
-}
-// A: rows x cols entries in Montgomery form.  tiles: rows*cols KB; K: rows plain integers mod r (callers add what follows the layer).
-// colFactor: columns >= 1 carry this further factor (Montgomery form)
-void mfma_layer_tables(const Vec &A, int rows, int cols, std::vector<int8_t> &tiles, Vec &K, bool sboxed, const U256 *colFactor = nullptr) {
-    const MfmaConsts mc;
-    const U256 zero = { { 0, 0, 0, 0 } };
-    tiles.assign((size_t)rows * cols * 1024, 0);
-    K.resize((size_t)rows);
-    for (int i = 0; i < rows; i++) {
-        U256 tot = zero;
-        for (int j = 0; j < cols; j++) mfma_tile(mc, A[(size_t)i * cols + j], tiles.data() + ((size_t)i * cols + j) * 1024, tot, sboxed, j >= 1 ? colFactor : nullptr);
-        K[i] = mfma_row_const(mc, tot, 1, zero);
-    }
-}
-// The partial rounds four to a block, blocks two to a SUPER-BLOCK (partial_rounds_mfma): the tile stream in the order the kernel consumes it and
-// the row constants.  Block b (rounds k0 = 4b .. k0+3), z_i = the S-box output of round k0+i, y = elements 1..n at the start of b's SUPER-BLOCK:
-//   x0 after round k0+i = m00 z_i + sum_j V[k0+i][j] y_j + sum_{i'<i} (V[k0+i] . W[k0+i']) z_i'  [+ for the second block of a super-block the same
-//   cross terms with the four z of the first];   y_j after the super-block = y_j + sum over its rounds of W[k][j] z_k  (one column update per 8 rounds).
-// Stream per block, in two passes (rows 0-1, then rows 2-3): n x 2 tiles V[k0+i][j] (j outer), second block: 2 x 4 tiles (V[k0+i] . W[k0-4+s]);  then the block's own
-// cross terms, round i = 0..3: i + 1 tiles (z_0 .. z_i of the block; the last is m00).  Per super-block after its blocks: n x (1 + 8) tiles (1, W[k][j]; four zero tiles when
-// the super-block has one block).
-// KR[k]: round k's row constant with S[k+1] folded in while round k+1 is one of these; KU[sb][j]: the column constants.
-void mfma_partial_tables(int t, int rp, const Vec &S, const Vec &V, const Vec &W, const U256 &m00, std::vector<int8_t> &tiles, Vec &KR, Vec &KU) {
-    const MfmaConsts mc;
-    const U256 zero = { { 0, 0, 0, 0 } }, one = h_to_mont(U256{ { 1, 0, 0, 0 } });
-    const int n = t - 1, nb = rp / 4, nsb = (nb + 1) / 2;
-    tiles.assign(((size_t)nb * (4 * n + 10) + (size_t)nsb * 9 * n + (size_t)(nb / 2) * 16) * 1024, 0);      // per block its rows and rounds, per super-block the columns (1 + 8 tiles each), 16 more for a second block's rows
-    KR.assign((size_t)nb * 4, zero); KU.assign((size_t)nsb * n, zero);
-    auto dot = [&](int ka, int kb) { U256 c = zero; for (int j = 0; j < n; j++) c = h_addmod(c, h_mont(V[(size_t)ka * n + j], W[(size_t)kb * n + j])); return c; };
-    int8_t *tp = tiles.data();
-    for (int sb = 0; sb < nsb; sb++) {
-        const int halves = nb - 2 * sb >= 2 ? 2 : 1;
-        for (int h = 0; h < halves; h++) {
-            const int k0 = 4 * (2 * sb + h);
-            U256 tot[4] = { zero, zero, zero, zero };
-            // the kernel takes the rows two at a time (partial_rounds_mfma_impl::rows): the first pass walks the columns in order, the second starts with the last
-            // batch of the columns that live in private memory (still in its registers), then the first batch, then the columns in LDS
-            const int nlo = n + 1 <= BN_LDS_ELEMS ? n : BN_LDS_ELEMS - 1, nhi = n - nlo, hb2 = nhi < BN_HI_BATCH ? nhi : BN_HI_BATCH, spl = nhi - hb2;
-            for (int pass = 0; pass < 2; pass++) {
-                std::vector<int> order;
-                if (pass == 0) for (int j = 0; j < n; j++) order.push_back(j);
-                else {
-                    for (int q = spl; q < nhi; q++) order.push_back(nlo + q);
-                    for (int q = 0; q < spl; q++) order.push_back(nlo + q);
-                    for (int j = 0; j < nlo; j++) order.push_back(j);
-                }
-                for (int j : order) for (int i = 2 * pass; i < 2 * pass + 2; i++, tp += 1024) mfma_tile(mc, V[(size_t)(k0 + i) * n + j], tp, tot[i], false);
-                if (h == 1) for (int i = 2 * pass; i < 2 * pass + 2; i++) for (int s = 0; s < 4; s++, tp += 1024) mfma_tile(mc, dot(k0 + i, k0 - 4 + s), tp, tot[i], true);
-            }
-            for (int i = 0; i < 4; i++) {
-                for (int ip = 0; ip <= i; ip++, tp += 1024)                                    // round i: its i + 1 cross terms, z_0 .. z_i of the block
-                    mfma_tile(mc, ip < i ? dot(k0 + i, k0 + ip) : m00, tp, tot[i], true);      // a z: the S-box's output
-                KR[(size_t)k0 + i] = mfma_row_const(mc, tot[i], 2, k0 + i + 1 < 4 * nb ? S[(size_t)k0 + i + 1] : zero);
-            }
-        }
-        for (int j = 0; j < n; j++) {
-            U256 tu = zero;
-            mfma_tile(mc, one, tp, tu, false); tp += 1024;
-            if (halves == 1) tp += 4 * 1024;       // (zero tiles where the kernel multiplies the absent first block's operands: one form of the column)
-            for (int s = 0; s < 4 * halves; s++, tp += 1024) mfma_tile(mc, W[(size_t)(8 * sb + s) * n + j], tp, tu, true);
-            KU[(size_t)sb * n + j] = mfma_row_const(mc, tu, 1, zero);
-        }
-    }
-}
-
 int get_params(int t, const Params **out) {
     if (t < 2 || t > 17) return fail(PIL2GL_EINVAL, "BN128 Poseidon takes 1..16 inputs (t=%d)", t);
     std::lock_guard<std::mutex> lk(g_mu);
     Params &P = g_params[t];
     if (!P.t) {
-        const int rp = N_ROUNDS_P[t - 2], nC = (N_ROUNDS_F + rp) * t, n = t - 1;
-        Grain g(t, rp);
-        Vec C((size_t)nC), M((size_t)t * t), xy((size_t)2 * t);
-        for (int i = 0; i < nC; i++) { U256 v = g.rnd(); while (h_ge(v, HR)) v = g.rnd(); C[i] = h_to_mont(v); }
-        for (int i = 0; i < 2 * t; i++) { U256 v = g.rnd(); while (h_ge(v, HR)) v = h_sub(v, HR); xy[i] = h_to_mont(v); }
-        for (int i = 0; i < t; i++) for (int j = 0; j < t; j++) M[(size_t)i * t + j] = h_inv_mont(h_addmod(xy[i], xy[t + j]));
-        Vec C8, D, S, V, W;
-        P2_TRY(derive_sparse(t, rp, C, M, C8, D, S, V, W));
-        Vec all;
-        auto put = [&](const Vec &x) { size_t o = all.size(); all.insert(all.end(), x.begin(), x.end()); return o; };
-        const size_t oC8 = put(C8), oM = put(M), oS = put(S), oV = put(V), oW = put(W), oCd = put(C);
-        u32 *d = nullptr;
-        HIP_TRY(hipMalloc((void **)&d, all.size() * 32));
-        HIP_TRY(hipMemcpy(d, all.data(), all.size() * 32, hipMemcpyHostToDevice));
-        P.base = d; P.C8 = d + oC8 * 8; P.M = d + oM * 8; P.S = d + oS * 8; P.V = d + oV * 8; P.W = d + oW * 8; P.Cd = d + oCd * 8;
-        memcpy(P.m00, M[0].w, 32);
-        {
-            std::vector<int8_t> tm, td, tpr, tm0; Vec km0, km, kd, kr, ku, km0p, c0p;
-            mfma_layer_tables(M, t, t, tm, km0, true);     // every dense layer follows an S-box layer
-            // The first layer once more for inputs that went through the S-box as PLAIN integers (leaf kernel: v + c instead of (v + c) 2^256 mod r,
-            // no conversion product): bn29::pow5 then returns the state form's value times 2^-1280 (five missing factors 2^256), which columns 1..t-1 of
-            // this copy take back.  c0p: the first round's constants as plain integers.
-            {
-                U256 f = { { 1, 0, 0, 0 } };
-                for (int e = 0; e < 1280; e++) f = h_addmod(f, f);
-                const U256 fm = h_to_mont(f);
-                mfma_layer_tables(M, t, t, tm0, km0p, true, &fm);
-                c0p.resize((size_t)t);
-                for (int i = 0; i < t; i++) c0p[i] = h_mont(C8[i], U256{ { 1, 0, 0, 0 } });
-            }
-            mfma_layer_tables(D, n, n, td, kd, false);    // the closing layer reads the columns the blocks left
-            mfma_partial_tables(t, rp, S, V, W, M[0], tpr, kr, ku);
-            // What follows a layer is added by its row constants (the values in between are lazy representatives, no other addition
-            // is left): the next full round's constants C8; after the fourth full round S[0] on element 0; after the closing layer
-            // C8[4] on elements 1..n -- element 0 gets C8[4][0] from the last partial round's row when that round is one of the
-            // blocked ones (rp % 4 == 0), from the vector code otherwise.  MK: one set per dense layer of the permutation, 8 x t.
-            km.resize((size_t)8 * t);
-            for (int inst = 0; inst < 8; inst++) for (int i = 0; i < t; i++) {
-                U256 f = { { 0, 0, 0, 0 } };
-                if (inst == 3) { if (i == 0) f = S[0]; }
-                else if (inst < 7) f = C8[(size_t)(inst + 1) * t + i];
-                km[(size_t)inst * t + i] = h_addmod(km0[i], f);
-            }
-            for (int i = 0; i < t; i++) km0p[i] = h_addmod(km0p[i], C8[(size_t)t + i]);
-            for (int i = 0; i < n; i++) kd[i] = h_addmod(kd[i], C8[(size_t)4 * t + 1 + i]);
-            if (rp % 4 == 0 && rp >= 4) kr[(size_t)rp - 1] = h_addmod(kr[(size_t)rp - 1], C8[(size_t)4 * t]);
-            // Small widths (t <= BN_SMALL_T): poseidon.circom:22-44 as written, every round one t x t layer of the SAME matrix -- two tile sets (after a full
-            // round every column comes out of the S-box, after a partial round only column 0) that stay in registers, and one row constant per round and row
-            // (the layer's own + the next round's constants).  No tile stream, no sparse blocks: a width-3 permutation is a chain of 65 short rounds whose
-            // latency, not its work, was the cost (perm_small).
-            std::vector<int8_t> ts; Vec sk;
-            if (t <= BN_SMALL_T) {
-                const MfmaConsts mc;
-                const U256 zero = { { 0, 0, 0, 0 } };
-                const int R = N_ROUNDS_F + rp;
-                ts.assign((size_t)2 * t * t * 1024, 0);
-                Vec kset[2]; kset[0].resize((size_t)t); kset[1].resize((size_t)t);
-                for (int set = 0; set < 2; set++)
-                    for (int i = 0; i < t; i++) {
-                        U256 tot = zero;
-                        for (int j = 0; j < t; j++) mfma_tile(mc, M[(size_t)i * t + j], ts.data() + ((size_t)(set * t + i) * t + j) * 1024, tot, set == 0 || j == 0);
-                        kset[set][i] = mfma_row_const(mc, tot, 1, zero);
-                    }
-                sk.resize((size_t)R * t);
-                for (int r = 0; r < R; r++) {
-                    const bool full = r < N_ROUNDS_F / 2 || r >= N_ROUNDS_F / 2 + rp;
-                    for (int i = 0; i < t; i++) sk[(size_t)r * t + i] = h_addmod(kset[full ? 0 : 1][i], r + 1 < R ? C[(size_t)(r + 1) * t + i] : zero);
-                }
-            }
-            const size_t spare = 16 * 1024;          // the tiles the read-ahead touches past the end of a table (MFMA_AHEAD)
-            int8_t *dt = nullptr; u32 *dk = nullptr;
-            HIP_TRY(hipMalloc((void **)&dt, tm.size() + td.size() + tpr.size() + tm0.size() + ts.size() + 5 * spare));
-            HIP_TRY(hipMemset(dt, 0, tm.size() + td.size() + tpr.size() + tm0.size() + ts.size() + 5 * spare));
-            if (!ts.empty()) HIP_TRY(hipMemcpy(dt + tm.size() + td.size() + tpr.size() + tm0.size() + 4 * spare, ts.data(), ts.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(dt + tm.size() + td.size() + tpr.size() + 3 * spare, tm0.data(), tm0.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(dt, tm.data(), tm.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(dt + tm.size() + spare, td.data(), td.size(), hipMemcpyHostToDevice));
-            if (!tpr.empty()) HIP_TRY(hipMemcpy(dt + tm.size() + td.size() + 2 * spare, tpr.data(), tpr.size(), hipMemcpyHostToDevice));
-            Vec kall;
-            kall.insert(kall.end(), km.begin(), km.end()); kall.insert(kall.end(), kd.begin(), kd.end());
-            kall.insert(kall.end(), kr.begin(), kr.end()); kall.insert(kall.end(), ku.begin(), ku.end());
-            kall.insert(kall.end(), km0p.begin(), km0p.end()); kall.insert(kall.end(), c0p.begin(), c0p.end());
-            kall.insert(kall.end(), sk.begin(), sk.end());
-            HIP_TRY(hipMalloc((void **)&dk, kall.size() * 32));
-            HIP_TRY(hipMemcpy(dk, kall.data(), kall.size() * 32, hipMemcpyHostToDevice));
-            P.Mt = (const bnm::v4i *)dt; P.Dt = (const bnm::v4i *)(dt + tm.size() + spare); P.Pt = (const bnm::v4i *)(dt + tm.size() + td.size() + 2 * spare);
-            P.MK = dk; P.DK = dk + km.size() * 8; P.KR = P.DK + kd.size() * 8; P.KU = P.KR + kr.size() * 8;
-            P.Mt0 = (const bnm::v4i *)(dt + tm.size() + td.size() + tpr.size() + 3 * spare); P.MK0 = P.KU + ku.size() * 8; P.C0p = P.MK0 + km0p.size() * 8;
-            if (!ts.empty()) { P.St = (const bnm::v4i *)(dt + tm.size() + td.size() + tpr.size() + tm0.size() + 4 * spare); P.SK = P.C0p + c0p.size() * 8; }
+        bnp::BnHostParams H;
+        if (const int rc = bnp::bn_build_params(t, H)) return fail(rc, "%s", H.error.c_str());
+        const void *src[3] = { H.elems.data(), H.tiles.data(), H.consts.data() };
+        const size_t bytes[3] = { H.elems.size() * 32, H.tiles.size(), H.consts.size() * 32 };
+        void *d[3] = { nullptr, nullptr, nullptr };
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < 3 && e == hipSuccess; k++) {
+            e = hipMalloc(&d[k], bytes[k]);
+            if (e == hipSuccess) e = hipMemcpy(d[k], src[k], bytes[k], hipMemcpyHostToDevice);
         }
-        P.rp = rp; P.t = t;
+        if (e != hipSuccess) {                       // P.t stays 0: a later call tries again
+            for (int k = 0; k < 3; k++) if (d[k]) (void)hipFree(d[k]);
+            return hip_fail(e, "BN128 parameter upload");
+        }
+        u32 *el = (u32 *)d[0];
+        const int8_t *tl = (const int8_t *)d[1];
+        const u32 *kc = (const u32 *)d[2];
+        auto tile = [&](size_t o) { return (const bnm::v4i *)(tl + o * 1024); };
+        P.base = el; P.C8 = el + H.C8 * 8; P.M = el + H.M * 8; P.S = el + H.S * 8; P.V = el + H.V * 8; P.W = el + H.W * 8; P.Cd = el + H.Cd * 8;
+        memcpy(P.m00, H.elems[H.m00].w, 32);
+        P.Mt = tile(H.Mt); P.Dt = tile(H.Dt); P.Pt = tile(H.Pt); P.Mt0 = tile(H.Mt0);
+        P.MK = kc + H.MK * 8; P.DK = kc + H.DK * 8; P.KR = kc + H.KR * 8; P.KU = kc + H.KU * 8; P.MK0 = kc + H.MK0 * 8; P.C0p = kc + H.C0p * 8;
+        if (H.St != bnp::BN_ABSENT) { P.St = tile(H.St); P.SK = kc + H.SK * 8; }
+        P.rp = H.rp; P.t = t;
     }
     *out = &P;
     return PIL2GL_OK;
@@ -520,8 +200,7 @@ __device__ __noinline__ void canon_state(const St st, int t) {
 // A dense layer on the matrix cores (bn_mfma.cuh): the N operand pairs are made once and stay in registers, a row is N pairs of
 // MFMAs and one short finish; no 32x32 product of the state is left.  The operand tiles come from the L2 as ONE linear stream
 // (row after row, tile after tile) read MFMA_AHEAD tiles ahead of their use -- a load per tile and lane, the oldest awaited
-// alone -- so the table carries MFMA_AHEAD spare tiles after its last one.
-constexpr int MFMA_AHEAD = 8;
+// alone -- so the table carries spare tiles after its last one (MFMA_AHEAD and BN_SPARE_TILES: bn_consts.h, the host writes them).
 // with the S-box in the row loop the ring is shorter: the S-box needs some of its registers (4 / 6 / 8 tiles 27.15 / 26.9 / 26.9 ms)
 constexpr int MFMA_AHEAD_SBOX = 6;
 // SBOX: the NEXT round's S-box is applied to every finished row before it is stored (its constant came with the row): the separate S-box pass over
@@ -630,6 +309,7 @@ __device__ __noinline__ void partial_rounds(const St st, const PermArgs &A, int 
 // y_j + sum_k W z_k (1 + 8 pairs and one finish each -- the costliest phase, hence every eight rounds, not four).  No 32x32 product is left
 // but the S-box's.  The tiles are ONE linear stream in consumption order, read PR_AHEAD tiles ahead.
 constexpr int PR_AHEAD = 4;                          // (deeper read-ahead measured nothing; the registers go to the rows' accumulators and operand batches)
+static_assert(BN_SPARE_TILES >= MFMA_AHEAD && BN_SPARE_TILES >= MFMA_AHEAD_SBOX && BN_SPARE_TILES >= PR_AHEAD, "the spare tiles after a table cover the deepest read-ahead");
 struct TileStream {
     bnm::gtile p;
     bnm::v4i q[PR_AHEAD];
@@ -1486,8 +1166,8 @@ int pil2gl_bn128_group_proof_dev(const uint64_t *elems, const uint64_t *nodes, u
         offset += nextN * arity; n = nextN; id >>= nbits; lv++;
     }
     for (size_t k = 0; k < mont.size() / 4; k++) {
-        U256 v = { { mont[4 * k], mont[4 * k + 1], mont[4 * k + 2], mont[4 * k + 3] } };
-        v = h_from_mont(v);
+        bnp::U256 v = { { mont[4 * k], mont[4 * k + 1], mont[4 * k + 2], mont[4 * k + 3] } };
+        v = bnp::h_from_mont(v);
         memcpy(hostSiblings + 4 * k, v.w, 32);
     }
     *nLevels = lv;
@@ -1514,7 +1194,7 @@ int pil2gl_bn128_group_proofs_dev(const uint64_t *elems, const uint64_t *nodes, 
     }
     const u64 stride = width + (u64)L.levels * arity * 4;
     u64 *d;
-    P2_TRY(scratch(6, (u64)nIdx * (stride + 1), &d));
+    P2_TRY(scratch(SCR_GROUP_PROOFS, (u64)nIdx * (stride + 1), &d));
     u64 *dIdx = d + (u64)nIdx * stride;
     HIP_TRY(hipMemcpy(dIdx, hostIdxs, (u64)nIdx * 8, hipMemcpyHostToDevice));
     bn_group_proofs_kernel<<<nIdx, 64>>>(elems, nodes, width, (int)arity, (int)nbits, dIdx, L, d);
@@ -1526,8 +1206,8 @@ int pil2gl_bn128_group_proofs_dev(const uint64_t *elems, const uint64_t *nodes, 
         if (width) memcpy(hostVals + (u64)q * width, h.data() + (u64)q * stride, width * 8);
         for (u64 k = 0; k < per / 4; k++) {
             const u64 *w = h.data() + (u64)q * stride + width + 4 * k;
-            U256 v = { { w[0], w[1], w[2], w[3] } };
-            v = h_from_mont(v);
+            bnp::U256 v = { { w[0], w[1], w[2], w[3] } };
+            v = bnp::h_from_mont(v);
             memcpy(hostSiblings + (u64)q * per + 4 * k, v.w, 32);
         }
     }
@@ -1554,24 +1234,15 @@ int pil2gl_bn128_roots_from_group_proofs(const uint64_t *hostVals, const uint64_
     const uint64_t nEl = (width + 2) / 3, nLast = nEl % arity;
     if (nEl > 1 && !custom && nLast) P2_TRY(get_params((int)nLast + 1, &pl));
     const u64 nV = (u64)nIdx * width, nS = (u64)nIdx * levels * arity * 4, nO = (u64)nIdx * 4;
-    u64 *d = nullptr; bool owned = false;
-    P2_TRY(stage_acquire(nV + nS + nIdx + nO, &d, &owned));
-    u64 *dSib = d + nV, *dIdx = dSib + nS, *dRoots = dIdx + nIdx;
-    int rc = PIL2GL_OK;
-    hipError_t e = nV ? hipMemcpy(d, hostVals, nV * 8, hipMemcpyHostToDevice) : hipSuccess;
-    if (e == hipSuccess && nS) e = hipMemcpy(dSib, hostSiblings, nS * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dIdx, hostIdxs, (u64)nIdx * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D");
-    if (rc == PIL2GL_OK) {
-        bn_path_roots_kernel<<<nIdx, 64>>>(d, dSib, dIdx, width, (int)levels, (int)arity, (int)nbits, custom ? 1 : 0, siblingsMontgomery ? 1 : 0,
-                                           perm_args(pf), perm_args(pl), dRoots);
-        g_path_launches++;
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(hostRoots, dRoots, nO * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "bn_path_roots_kernel");
-    }
-    stage_release(d, owned);
-    return rc;
+    Stage s(nV + nS + nIdx + nO);
+    const u64 *dVals = s.put(hostVals, nV), *dSib = s.put(hostSiblings, nS), *dIdx = s.put(hostIdxs, nIdx);
+    u64 *dRoots = s.take(nO);
+    P2_TRY(s.rc());
+    bn_path_roots_kernel<<<nIdx, 64>>>(dVals, dSib, dIdx, width, (int)levels, (int)arity, (int)nbits, custom ? 1 : 0, siblingsMontgomery ? 1 : 0,
+                                       perm_args(pf), perm_args(pl), dRoots);
+    g_path_launches++;
+    KERNEL_CHECK();
+    return s.get(hostRoots, dRoots, nO);
 }
 
 // ---- host-pointer forms ----
@@ -1579,18 +1250,13 @@ int pil2gl_bn128_poseidon(const uint64_t *in, const uint64_t *init, uint64_t cou
     P2_TRY(ensure_init());
     if (count == 0) return PIL2GL_OK;
     if (!in || !out) return fail(PIL2GL_EINVAL, "null buffer");
-    u64 *d = nullptr;
     const u64 nI = count * nIn * 4, nS = init ? count * 4 : 0, nO = count * nOut * 4;
-    bool owned = false;
-    P2_TRY(stage_acquire(nI + nS + nO, &d, &owned));
-    int rc = PIL2GL_OK;
-    hipError_t e = hipMemcpy(d, in, nI * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nS) e = hipMemcpy(d + nI, init, nS * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D");
-    if (rc == PIL2GL_OK) rc = pil2gl_bn128_poseidon_dev(d, nS ? d + nI : nullptr, count, nIn, nOut, d + nI + nS, nullptr);
-    if (rc == PIL2GL_OK) { e = hipMemcpy(out, d + nI + nS, nO * 8, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H"); }
-    stage_release(d, owned);
-    return rc;
+    Stage s(nI + nS + nO);
+    const u64 *dIn = s.put(in, nI), *dInit = s.put(init, nS);
+    u64 *dOut = s.take(nO);
+    P2_TRY(s.rc());
+    P2_TRY(pil2gl_bn128_poseidon_dev(dIn, dInit, count, nIn, nOut, dOut, nullptr));
+    return s.get(out, dOut, nO);
 }
 
 // transcript.bn128.js:56-66 for a list: nBlocks full blocks of nIn elements absorbed one after the other; state element 0
@@ -1603,20 +1269,13 @@ int pil2gl_bn128_sponge_absorb(const uint64_t *hostBlocks, uint64_t nBlocks, uin
     const Params *pf;
     P2_TRY(get_params((int)nIn + 1, &pf));
     const u64 nB = nBlocks * nIn * 4, nO = (u64)(nIn + 1) * 4;
-    u64 *d = nullptr; bool owned = false;
-    P2_TRY(stage_acquire(nB + 4 + nO, &d, &owned));
-    int rc = PIL2GL_OK;
-    hipError_t e = hipMemcpy(d, hostBlocks, nB * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + nB, hostInit, 32, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D");
-    if (rc == PIL2GL_OK) {
-        bn_sponge_chain_kernel<<<1, 64>>>(d, nBlocks, (int)nIn, d + nB, perm_args(pf), (int)nIn + 1, 0, d + nB + 4);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(hostOut, d + nB + 4, nO * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "bn_sponge_chain_kernel");
-    }
-    stage_release(d, owned);
-    return rc;
+    Stage s(nB + 4 + nO);
+    const u64 *dBlocks = s.put(hostBlocks, nB), *dInit = s.put(hostInit, 4);
+    u64 *dOut = s.take(nO);
+    P2_TRY(s.rc());
+    bn_sponge_chain_kernel<<<1, 64>>>(dBlocks, nBlocks, (int)nIn, dInit, perm_args(pf), (int)nIn + 1, 0, dOut);
+    KERNEL_CHECK();
+    return s.get(hostOut, dOut, nO);
 }
 
 int pil2gl_bn128_merkelize(const uint64_t *elems, uint64_t width, uint64_t height, uint32_t arity, int custom, uint64_t *nodes) {
@@ -1624,39 +1283,31 @@ int pil2gl_bn128_merkelize(const uint64_t *elems, uint64_t width, uint64_t heigh
     if (height == 0) return fail(PIL2GL_EINVAL, "height must be > 0");
     P2_TRY(check_arity(arity));
     const u64 nE = width * height, nN = pil2gl_bn128_merkle_num_nodes(height, arity) * 4;
-    u64 *d = nullptr;
-    bool owned = false;
-    P2_TRY(stage_acquire(nE + nN, &d, &owned));
-    int rc = PIL2GL_OK;
-    hipError_t e = nE ? hipMemcpy(d, elems, nE * 8, hipMemcpyHostToDevice) : hipSuccess;
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D");
-    if (rc == PIL2GL_OK) rc = pil2gl_bn128_merkelize_dev(d, width, height, arity, custom, d + nE, nullptr);
-    if (rc == PIL2GL_OK) { e = hipMemcpy(nodes, d + nE, nN * 8, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H"); }
-    stage_release(d, owned);
-    return rc;
+    Stage s(nE + nN);
+    const u64 *dElems = s.put(elems, nE);
+    u64 *dNodes = s.take(nN);
+    P2_TRY(s.rc());
+    P2_TRY(pil2gl_bn128_merkelize_dev(dElems, width, height, arity, custom, dNodes, nullptr));
+    return s.get(nodes, dNodes, nN);
 }
 
 int pil2gl_bn128_linear_hash_rows(const uint64_t *in, uint64_t width, uint64_t height, uint32_t arity, int custom, uint64_t *out) {
     P2_TRY(ensure_init());
     if (height == 0) return PIL2GL_OK;
     const u64 nE = width * height, nO = height * 4;
-    u64 *d = nullptr;
-    bool owned = false;
-    P2_TRY(stage_acquire(nE + nO, &d, &owned));
-    int rc = PIL2GL_OK;
-    hipError_t e = nE ? hipMemcpy(d, in, nE * 8, hipMemcpyHostToDevice) : hipSuccess;
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D");
-    if (rc == PIL2GL_OK) rc = pil2gl_bn128_linear_hash_rows_dev(d, width, height, arity, custom, d + nE, nullptr);
-    if (rc == PIL2GL_OK) { e = hipMemcpy(out, d + nE, nO * 8, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H"); }
-    stage_release(d, owned);
-    return rc;
+    Stage s(nE + nO);
+    const u64 *dIn = s.put(in, nE);
+    u64 *dOut = s.take(nO);
+    P2_TRY(s.rc());
+    P2_TRY(pil2gl_bn128_linear_hash_rows_dev(dIn, width, height, arity, custom, dOut, nullptr));
+    return s.get(out, dOut, nO);
 }
 
 int pil2gl_bn128_convert(const uint64_t *in, uint64_t n, int toMontgomery, uint64_t *out) {     // host-only arithmetic (a few values: roots, proofs)
     if (n && (!in || !out)) return fail(PIL2GL_EINVAL, "null buffer");
     for (uint64_t k = 0; k < n; k++) {
-        U256 v = { { in[4 * k], in[4 * k + 1], in[4 * k + 2], in[4 * k + 3] } };
-        v = toMontgomery ? h_to_mont(v) : h_from_mont(v);
+        bnp::U256 v = { { in[4 * k], in[4 * k + 1], in[4 * k + 2], in[4 * k + 3] } };
+        v = toMontgomery ? bnp::h_to_mont(v) : bnp::h_from_mont(v);
         memcpy(out + 4 * k, v.w, 32);
     }
     return PIL2GL_OK;

@@ -9,7 +9,7 @@
 //
 // The Montgomery radix is 2^261 here, not the 2^256 of the state: M(a, b) = a b / 2^261.  x^5 through two squarings and a product comes
 // out as X^5 / 2^1044 for a state value X = x 2^256, i.e. the state form of x^5 times 2^-20.  The constant 2^20 is multiplied into the
-// tiles of the linear layer that reads the S-box's output (bn128.hip: mfma_tile's `sboxed` operands), so nothing is paid for it.
+// tiles of the linear layer that reads the S-box's output (bn_params.cpp: mfma_tile's `sboxed` operands), so nothing is paid for it.
 // Operands are lazy representatives below 0.9 * 2^256 (eight 32-bit words in, eight out); results are below 2^252 + r.
 #pragma once
 #include <stdint.h>

@@ -25,6 +25,7 @@
 //     and the high half of ITS row, which it finishes alone.
 #pragma once
 #include "bn_field.cuh"
+#include "bn_consts.h"
 
 namespace bnm {
 
@@ -34,7 +35,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef const v4i __attribute__((address_space(1))) *gtile;
 
-constexpr int ACC_BIAS = 1 << 30;         // 2.0f's bit pattern: an inline constant of the matrix instruction (its C operand), no register set-up per accumulator
+using bnc::ACC_BIAS;                      // the accumulators' start value (the host's row constants take it back)
 
 // the operands of both tiles from the lane's own eight limbs
 // (the swaps go through the builtin: hipcc pads a vector write against the swap that reads it -- two wait states -- itself;

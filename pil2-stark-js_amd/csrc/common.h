@@ -47,14 +47,48 @@ struct Tables {
 };
 const Tables &tables();
 
-// scratch (grown on demand, kept across calls) ------------------------------------------
-int scratch(u32 slot, u64 nWords, u64 **out);
+// scratch (grown on demand, kept across calls): one slot per owner, so that no two buffers that are live at once share one
+enum ScratchSlot : u32 {
+    SCR_NTT_TMP = 0,          // ntt.hip: the second buffer of a transform of more than one pass
+    SCR_FRI_COEF = 1,         // fri.hip: a fold's coefficients (fri_fold, fri_verify_fold); the FRI polynomial on its coset before the extension
+    SCR_FRI_TABLE = 2,        // fri.hip upload_small: the small host-made table of one helper call (zerofiers, shifts, Lagrange powers)
+    SCR_EVALS = 3,            // fri.hip compute_evals: the blocks' partial sums
+    SCR_EXPR_PROGRAM = 4,     // expr.hip: the device form of a program (ops, scalar pool, limbs)
+    SCR_EXPR_TMP = 5,         // expr.hip: the interpreter's temporaries when they do not fit LDS
+    SCR_GROUP_PROOFS = 6,     // merkle.hip, bn128.hip: the openings group_proofs gathers / roots_from_group_proofs walks -- shared: none of them calls another
+    SCR_DOT = 7,              // dot.hip: tables and partial sums of the extension-weighted sums
+    SCR_HINT_TMP = 8,         // hints.hip: the running sums / products' per-element work
+    SCR_HINT_TOTALS = 9,      // hints.hip: their blocks' totals
+    SCR_HINT_WORK = 10,       // hints.hip h1h2: hash table, counts, starts, totals
+    SCR_STAGE = 11,           // Stage below: device copies of the small host-pointer calls
+    SCR_HOST_NTT_IN = 12,     // ntt.hip host_wrap: device copies of the host-pointer transforms (a size policy of its own, documented there)
+    SCR_HOST_NTT_OUT = 13,
+    SCR_Q_A = 14,             // fri.hip: the quotient stage (q, then its coefficients in SCR_Q_B) and the FRI polynomial (x / (x - xi) tables, accumulators)
+    SCR_Q_B = 15,
+    SCR_CLOCK_PROBE = 16,     // merkle.hip pil2gl_selftest_clock
+    N_SCRATCH
+};
+int scratch(ScratchSlot slot, u64 nWords, u64 **out);
 
-// device staging for the host-pointer entry points: small requests (<= 16 MB) come from a persistent slot -- a hipMalloc /
-// hipFree pair per call costs a device synchronisation each, which dominated the transcript's single permutations --
-// larger ones are allocated and released per call.  stage_release() frees only what stage_acquire() allocated.
-int stage_acquire(u64 nWords, u64 **out, bool *owned);
-void stage_release(u64 *p, bool owned);
+// Device staging for the host-pointer entry points: reserves nWords, hands out consecutive sub-ranges (filled from host memory or left for
+// the kernels to write), copies results back and releases on scope exit.  Small requests (<= 16 MB) come from a persistent slot -- a
+// hipMalloc / hipFree pair per call costs a device synchronisation each, which dominated the transcript's single permutations -- larger ones
+// are allocated and released per call.  The first failure (initialisation, allocation, a copy) stays in rc(); after it put / take return
+// nullptr and get returns it.
+class Stage {
+public:
+    explicit Stage(u64 nWords);                       // includes ensure_init()
+    ~Stage();
+    Stage(const Stage &) = delete; Stage &operator=(const Stage &) = delete;
+    int rc() const { return rc_; }
+    u64 *take(u64 n);                                 // the next n words, as they are
+    const u64 *put(const u64 *host, u64 n);           // the next n words, copied from host; n == 0: nullptr (an absent input)
+    int get(u64 *host, const u64 *dev, u64 n);        // device -> host
+private:
+    u64 *d_ = nullptr, used_ = 0, cap_ = 0;
+    bool owned_ = false;
+    int rc_;
+};
 
 hipStream_t as_stream(void *s);
 

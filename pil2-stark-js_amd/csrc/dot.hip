@@ -514,7 +514,7 @@ static int launch_rows_dot_mfma(const MfSeg *segs, u32 nBufs, u64 nRows, u32 nOu
             }
     u64 *d;
     const size_t atWords = (atab.size() + 7) / 8;
-    P2_TRY(scratch(7, atWords + nO + 2, &d));
+    P2_TRY(scratch(SCR_DOT, atWords + nO + 2, &d));
     HIP_TRY(hipMemcpyAsync(d, atab.data(), atab.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d + atWords, bias.data(), nO * 8, hipMemcpyHostToDevice, st));
     RowsDotMfmaParams P;
@@ -551,7 +551,7 @@ static int rows_dot_ext_plain(const uint64_t *buf, uint64_t width, uint64_t nRow
         limbs[3 * i] = (u32)v & LIMB_MASK; limbs[3 * i + 1] = (u32)(v >> LIMB_BITS) & LIMB_MASK; limbs[3 * i + 2] = (u32)(v >> (2 * LIMB_BITS));
     }
     u64 *d;
-    P2_TRY(scratch(7, (limbs.size() * 4 + 7) / 8 + 1, &d));
+    P2_TRY(scratch(SCR_DOT, (limbs.size() * 4 + 7) / 8 + 1, &d));
     HIP_TRY(hipMemcpyAsync(d, limbs.data(), limbs.size() * 4, hipMemcpyHostToDevice, st));
     const unsigned blocks = (unsigned)((nRows + 255) / 256);
     // a lane's six partial sums take one term below 2^54 per column and are folded once per launch: windows of at most
@@ -698,7 +698,7 @@ int pil2gl_fri_combine_order_dev(const uint64_t *acc, const uint64_t *hostK, con
     hipStream_t st = as_stream(stream);
     std::vector<u64> k(hostK, hostK + 3ull * nOpen);
     u64 *d;
-    P2_TRY(scratch(7, 16, &d));
+    P2_TRY(scratch(SCR_DOT, 16, &d));
     HIP_TRY(hipMemcpyAsync(d, k.data(), k.size() * 8, hipMemcpyHostToDevice, st));
     E3 v = { { vf1[0], vf1[1], vf1[2] } };
     fri_combine_kernel<<<nblk(nRows), 256, 0, st>>>(acc, d, v, xDivXSubXi, nOpen, ord, nRows, f);
@@ -739,7 +739,7 @@ int pil2gl_cols_dot_ext_range_dev(const uint64_t *const *bufs, const uint64_t *s
     const u64 nChunks = (nRows + rpc - 1) / rpc, n = (u64)nLev * width * 3;
     u64 *d;
     const u64 nGroups = std::min<u64>(64, nChunks), per = (nChunks + nGroups - 1) / nGroups;
-    P2_TRY(scratch(7, ((u64)nLev * nRows * 9 * 4 + 7) / 8 + nChunks * n + nGroups * n + n + 1, &d));
+    P2_TRY(scratch(SCR_DOT, ((u64)nLev * nRows * 9 * 4 + 7) / 8 + nChunks * n + nGroups * n + n + 1, &d));
     u32 *limbs = (u32 *)d;
     u64 *partial = d + ((u64)nLev * nRows * 9 * 4 + 7) / 8, *part2 = partial + nChunks * n, *res = part2 + nGroups * n;
     for (u32 l = 0; l < nLev; l++) limbs_kernel<<<nblk(nRows * 3), 256, 0, st>>>(levs[l], nRows * 3, limbs + (u64)l * nRows * 9);

@@ -832,7 +832,7 @@ extern "C" int pil2gl_eval_program_dev(const glx_program *prog, const glx_ctx *c
     }
     const u64 opsWords = ((u64)dops.size() * sizeof(DevOp) + 7) / 8, limbWords = (limbPool.size() * 4 + 7) / 8;
     u64 *d;
-    P2_TRY(scratch(4, opsWords + ctx->nScalars + limbWords + 2, &d));
+    P2_TRY(scratch(SCR_EXPR_PROGRAM, opsWords + ctx->nScalars + limbWords + 2, &d));
     HIP_TRY(hipMemcpyAsync(d, dops.data(), dops.size() * sizeof(DevOp), hipMemcpyHostToDevice, st));
     if (ctx->nScalars) HIP_TRY(hipMemcpyAsync(d + opsWords, ctx->scalars, (u64)ctx->nScalars * 8, hipMemcpyHostToDevice, st));
     if (!limbPool.empty()) HIP_TRY(hipMemcpyAsync(d + opsWords + ctx->nScalars + 1, limbPool.data(), limbPool.size() * 4, hipMemcpyHostToDevice, st));
@@ -882,7 +882,7 @@ interpreter:
         const u32 threads = 256;
         const u64 blocks = std::min<u64>((nRows + threads - 1) / threads, 256ull * 8);
         u64 *gtmp;
-        P2_TRY(scratch(5, (u64)slots * 3 * blocks * threads, &gtmp));
+        P2_TRY(scratch(SCR_EXPR_TMP, (u64)slots * 3 * blocks * threads, &gtmp));
         eval_kernel<false><<<(unsigned)blocks, threads, 0, st>>>(c, gtmp);
     }
     KERNEL_CHECK();
@@ -914,7 +914,7 @@ extern "C" int pil2gl_first_nonzero_row_dev(const uint64_t *col, uint32_t dim, u
     if (blocks > 0x7fffffffull) return fail(PIL2GL_EINVAL, "grid too large");
     hipStream_t st = as_stream(stream);
     u64 *d;
-    P2_TRY(scratch(4, 1, &d));
+    P2_TRY(scratch(SCR_EXPR_PROGRAM, 1, &d));
     HIP_TRY(hipMemsetAsync(d, 0xff, 8, st));
     first_nonzero_kernel<<<(unsigned)blocks, 256, 0, st>>>(col, dim, first, last, (unsigned long long *)d);
     KERNEL_CHECK();

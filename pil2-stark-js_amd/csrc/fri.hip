@@ -234,7 +234,7 @@ int pil2gl_fri_fold_dev(const uint64_t *pol, uint32_t polBits, uint32_t outBits,
     hipStream_t st = as_stream(stream);
     const u64 n = 1ull << polBits;
     u64 *coef;
-    P2_TRY(scratch(1, 3 * n, &coef));
+    P2_TRY(scratch(SCR_FRI_COEF, 3 * n, &coef));
     // group iNTT (fri.js:51-55): pol is an nX x (pol2N*3) row-major matrix, transform along its rows' index
     P2_TRY(ntt_launch(pol, 3ull << outBits, polBits - outBits, coef, true, st));
     E3 ch = { { challenge[0], challenge[1], challenge[2] } };
@@ -255,7 +255,7 @@ int pil2gl_fri_verify_fold_dev(const uint64_t *groups, uint32_t foldBits, uint32
     const u64 *coef = groups;
     if (foldBits > 0) {
         u64 *c;
-        P2_TRY(scratch(1, 3 * nX * nQueries, &c));
+        P2_TRY(scratch(SCR_FRI_COEF, 3 * nX * nQueries, &c));
         P2_TRY(ntt_launch(groups, 3ull * nQueries, foldBits, c, true, st));
         coef = c;
     }
@@ -274,24 +274,14 @@ int pil2gl_fri_transpose_dev(const uint64_t *pol, uint32_t polBits, uint32_t tra
     return PIL2GL_OK;
 }
 
-static int host3(const uint64_t *in, u64 nIn, uint64_t *out, u64 nOut, int (*fn)(const u64 *, u64 *, void *), void *arg) {
-    P2_TRY(ensure_init());
-    u64 *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, (nIn + nOut + 1) * 8));
-    int rc = PIL2GL_OK;
-    hipError_t e = hipMemcpy(d, in, nIn * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D");
-    if (rc == PIL2GL_OK) rc = fn(d, d + nIn, arg);
-    if (rc == PIL2GL_OK) { e = hipMemcpy(out, d + nIn, nOut * 8, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H"); }
-    (void)hipFree(d);
-    return rc;
-}
-struct FoldArgs { u32 polBits, outBits; u64 shiftInv; const u64 *ch; };
 int pil2gl_fri_fold(const uint64_t *pol, uint32_t polBits, uint32_t outBits, uint64_t shiftInv, const uint64_t challenge[3], uint64_t *out) {
     if (outBits > polBits || polBits > PIL2GL_MAX_NTT_BITS) return fail(PIL2GL_EINVAL, "Invalid polynomial size");
-    FoldArgs a = { polBits, outBits, shiftInv, challenge };
-    return host3(pol, 3ull << polBits, out, 3ull << outBits,
-                 [](const u64 *i, u64 *o, void *p) { FoldArgs *a = (FoldArgs *)p; return pil2gl_fri_fold_dev(i, a->polBits, a->outBits, a->shiftInv, a->ch, o, nullptr); }, &a);
+    Stage s((3ull << polBits) + (3ull << outBits));
+    const u64 *dPol = s.put(pol, 3ull << polBits);
+    u64 *dOut = s.take(3ull << outBits);
+    P2_TRY(s.rc());
+    P2_TRY(pil2gl_fri_fold_dev(dPol, polBits, outBits, shiftInv, challenge, dOut, nullptr));
+    return s.get(out, dOut, 3ull << outBits);
 }
 int pil2gl_fri_verify_fold(const uint64_t *groups, uint32_t foldBits, uint32_t nQueries, const uint64_t *sinv,
                            const uint64_t challenge[3], uint64_t *out) {
@@ -299,22 +289,21 @@ int pil2gl_fri_verify_fold(const uint64_t *groups, uint32_t foldBits, uint32_t n
     if (!groups || !sinv || !out || !challenge) return fail(PIL2GL_EINVAL, "null buffer");
     if (foldBits > 20 || nQueries == 0) return fail(PIL2GL_EINVAL, "Invalid group size or query count");
     const u64 nG = (3ull << foldBits) * nQueries;
-    u64 *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, (nG + 4ull * nQueries) * 8));
-    int rc = PIL2GL_OK;
-    hipError_t e = hipMemcpy(d, groups, nG * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + nG, sinv, nQueries * 8ull, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D");
-    if (rc == PIL2GL_OK) rc = pil2gl_fri_verify_fold_dev(d, foldBits, nQueries, d + nG, challenge, d + nG + nQueries, nullptr);
-    if (rc == PIL2GL_OK) { e = hipMemcpy(out, d + nG + nQueries, 3ull * nQueries * 8, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H"); }
-    (void)hipFree(d);
-    return rc;
+    Stage s(nG + 4ull * nQueries);
+    const u64 *dGroups = s.put(groups, nG), *dSinv = s.put(sinv, nQueries);
+    u64 *dOut = s.take(3ull * nQueries);
+    P2_TRY(s.rc());
+    P2_TRY(pil2gl_fri_verify_fold_dev(dGroups, foldBits, nQueries, dSinv, challenge, dOut, nullptr));
+    return s.get(out, dOut, 3ull * nQueries);
 }
 int pil2gl_fri_transpose(const uint64_t *pol, uint32_t polBits, uint32_t transposeBits, uint64_t *out) {
     if (transposeBits > polBits || polBits > 31) return fail(PIL2GL_EINVAL, "Invalid polynomial size");
-    u32 a[2] = { polBits, transposeBits };
-    return host3(pol, 3ull << polBits, out, 3ull << polBits,
-                 [](const u64 *i, u64 *o, void *p) { u32 *a = (u32 *)p; return pil2gl_fri_transpose_dev(i, a[0], a[1], o, nullptr); }, a);
+    Stage s(6ull << polBits);
+    const u64 *dPol = s.put(pol, 3ull << polBits);
+    u64 *dOut = s.take(3ull << polBits);
+    P2_TRY(s.rc());
+    P2_TRY(pil2gl_fri_transpose_dev(dPol, polBits, transposeBits, dOut, nullptr));
+    return s.get(out, dOut, 3ull << polBits);
 }
 
 // ---- STARK step helpers ----
@@ -353,7 +342,7 @@ static void zh_table(u32 nBits, u32 nBitsExt, std::vector<u64> &zh, bool inverte
     zh.resize(1ull << eb);
     for (u64 i = 0; i < zh.size(); i++) { u64 z = h_sub(h_mul(sn, w), 1); zh[i] = inverted ? h_inv(z) : z; w = h_mul(w, we); }
 }
-static int upload_small(const std::vector<u64> &h, u32 slot, u64 **d, hipStream_t st) {
+static int upload_small(const std::vector<u64> &h, ScratchSlot slot, u64 **d, hipStream_t st) {
     P2_TRY(scratch(slot, h.size() ? h.size() : 1, d));
     // pageable-host async copies are staged by the runtime before returning, so `h` may go out of scope
     HIP_TRY(hipMemcpyAsync(*d, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
@@ -365,10 +354,10 @@ int pil2gl_build_zhinv_dev(uint32_t nBits, uint32_t nBitsExt, uint64_t *out, voi
     if (nBitsExt < nBits || nBitsExt > 31 || nBitsExt - nBits > 20) return fail(PIL2GL_EINVAL, "bad domain sizes");
     if (!out) return fail(PIL2GL_EINVAL, "null buffer");
     std::vector<u64> zh; zh_table(nBits, nBitsExt, zh, true);
-    u64 *d; P2_TRY(upload_small(zh, 2, &d, as_stream(stream)));
+    u64 *d; P2_TRY(upload_small(zh, SCR_FRI_TABLE, &d, as_stream(stream)));
     periodic_kernel<<<nblk(1ull << nBitsExt), 256, 0, as_stream(stream)>>>(d, zh.size(), 1ull << nBitsExt, out);
     KERNEL_CHECK();
-    HIP_TRY(hipStreamSynchronize(as_stream(stream)));       // scratch slot 2 is reused by the next helper call
+    HIP_TRY(hipStreamSynchronize(as_stream(stream)));       // SCR_FRI_TABLE is reused by the next helper call
     return PIL2GL_OK;
 }
 int pil2gl_build_one_row_zerofier_inv_dev(uint32_t nBits, uint32_t nBitsExt, uint64_t rowIndex, uint64_t *out, void *stream) {
@@ -376,7 +365,7 @@ int pil2gl_build_one_row_zerofier_inv_dev(uint32_t nBits, uint32_t nBitsExt, uin
     if (nBitsExt < nBits || nBitsExt > 31 || nBitsExt - nBits > 20) return fail(PIL2GL_EINVAL, "bad domain sizes");
     if (!out) return fail(PIL2GL_EINVAL, "null buffer");
     std::vector<u64> zh; zh_table(nBits, nBitsExt, zh, false);
-    u64 *d; P2_TRY(upload_small(zh, 2, &d, as_stream(stream)));
+    u64 *d; P2_TRY(upload_small(zh, SCR_FRI_TABLE, &d, as_stream(stream)));
     u64 root = h_pow(h_root(nBits), rowIndex);
     one_row_zerofier_kernel<<<nblk(((1ull << nBitsExt) + 7) / 8), 256, 0, as_stream(stream)>>>(nBitsExt, root, d, zh.size(), tables().powW, out);
     KERNEL_CHECK();
@@ -390,7 +379,7 @@ int pil2gl_build_frame_zerofier_dev(uint32_t nBits, uint32_t nBitsExt, uint64_t 
     u64 w = h_root(nBits), N = 1ull << nBits;
     for (u64 i = 0; i < offsetMin; i++) roots.push_back(h_pow(w, i));
     for (u64 i = 0; i < offsetMax; i++) roots.push_back(h_pow(w, N - i - 1));
-    u64 *d; P2_TRY(upload_small(roots, 2, &d, as_stream(stream)));
+    u64 *d; P2_TRY(upload_small(roots, SCR_FRI_TABLE, &d, as_stream(stream)));
     frame_zerofier_kernel<<<nblk(1ull << nBitsExt), 256, 0, as_stream(stream)>>>(nBitsExt, d, (u32)roots.size(), tables().powW, out);
     KERNEL_CHECK();
     HIP_TRY(hipStreamSynchronize(as_stream(stream)));
@@ -403,7 +392,7 @@ int pil2gl_compute_q_split_dev(const uint64_t *qq1, uint32_t nBits, uint32_t nBi
     std::vector<u64> sp(qDeg);
     u64 shiftIn = h_pow(h_inv(7), 1ull << nBits), cur = 1;
     for (u32 p = 0; p < qDeg; p++) { sp[p] = cur; cur = h_mul(cur, shiftIn); }
-    u64 *d; P2_TRY(upload_small(sp, 2, &d, as_stream(stream)));
+    u64 *d; P2_TRY(upload_small(sp, SCR_FRI_TABLE, &d, as_stream(stream)));
     q_split_kernel<<<nblk(((u64)qDim * qDeg) << nBitsExt), 256, 0, as_stream(stream)>>>(qq1, nBits, nBitsExt, qDim, qDeg, d, qq2);
     KERNEL_CHECK();
     HIP_TRY(hipStreamSynchronize(as_stream(stream)));
@@ -416,7 +405,7 @@ int pil2gl_compute_q_split_brev_dev(const uint64_t *qq1, uint32_t nBits, uint32_
     std::vector<u64> sp(qDeg);
     u64 shiftIn = h_pow(h_inv(7), 1ull << nBits), cur = 1;
     for (u32 p = 0; p < qDeg; p++) { sp[p] = cur; cur = h_mul(cur, shiftIn); }
-    u64 *d; P2_TRY(upload_small(sp, 2, &d, as_stream(stream)));
+    u64 *d; P2_TRY(upload_small(sp, SCR_FRI_TABLE, &d, as_stream(stream)));
     q_split_brev_kernel<<<nblk(((u64)qDim * qDeg) << nBits), 256, 0, as_stream(stream)>>>(qq1, nBits, qDim, qDeg, d, coefBrev);
     KERNEL_CHECK();
     HIP_TRY(hipStreamSynchronize(as_stream(stream)));
@@ -468,8 +457,8 @@ int pil2gl_compute_q_stark_dev(const glx_program *prog, const glx_ctx *ctx, uint
     P2_TRY(q_stark_context(prog, ctx, qSection, nBits, nBitsExt, qDim, qDeg, secs, sub, m));
     const u64 M = 1ull << m, W = (u64)qDim * qDeg;
     u64 *q, *coef;
-    P2_TRY(scratch(14, M * qDim, &q));
-    P2_TRY(scratch(15, W << nBits, &coef));
+    P2_TRY(scratch(SCR_Q_A, M * qDim, &q));
+    P2_TRY(scratch(SCR_Q_B, W << nBits, &coef));
     secs[qSection].ptr = q;
     P2_TRY(pil2gl_eval_program_dev(prog, &sub, stream));
     P2_TRY(ntt_launch(q, qDim, m, q, true, as_stream(stream)));
@@ -550,9 +539,9 @@ int pil2gl_compute_fri_pol_dev(const uint64_t *const *bufs, const uint64_t *widt
     const u32 eb = nBitsExt - nBits;
     const u64 N = 1ull << nBits;
     u64 *xdiv, *acc, *f = fExt;
-    P2_TRY(scratch(14, N * 3 * nOpen, &xdiv));
-    P2_TRY(scratch(15, N * 3 * nOpen, &acc));
-    if (eb) P2_TRY(scratch(1, N * 3, &f));
+    P2_TRY(scratch(SCR_Q_A, N * 3 * nOpen, &xdiv));
+    P2_TRY(scratch(SCR_Q_B, N * 3 * nOpen, &acc));
+    if (eb) P2_TRY(scratch(SCR_FRI_COEF, N * 3, &f));
     for (u32 o = 0; o < nOpen; o++) P2_TRY(pil2gl_x_div_x_sub_xi_cosets_dev(nBitsExt, eb, xis + 3 * o, nOpen, o, 0, 1, xdiv, stream));
     P2_TRY(pil2gl_rows_dot_ext_multi_step_dev(bufs, widths, nBufs, N, eb, hostCoefs, nOpen, acc, 0, stream));
     P2_TRY(pil2gl_fri_combine_order_dev(acc, hostK, vf1, xdiv, nOpen, order, N, f, stream));
@@ -590,7 +579,7 @@ int pil2gl_build_lev_dev(uint32_t nBits, const uint64_t xi[3], uint64_t *lev, vo
     std::vector<u64> xp(3 * (nBits ? nBits : 1));
     u64 cur[3] = { xi[0], xi[1], xi[2] };
     for (u32 b = 0; b < nBits; b++) { xp[3 * b] = cur[0]; xp[3 * b + 1] = cur[1]; xp[3 * b + 2] = cur[2]; h_e3_mul(cur, cur, cur); }
-    u64 *d; P2_TRY(upload_small(xp, 2, &d, as_stream(stream)));
+    u64 *d; P2_TRY(upload_small(xp, SCR_FRI_TABLE, &d, as_stream(stream)));
     lev_pow_kernel<<<nblk(1ull << nBits), 256, 0, as_stream(stream)>>>(nBits, d, lev);
     KERNEL_CHECK();
     P2_TRY(ntt_launch(lev, 3, nBits, lev, true, as_stream(stream)));       // F.ifft on triples: component-wise
@@ -605,7 +594,7 @@ int pil2gl_compute_evals_dev(const pil2gl_eval_desc *descs, uint32_t nEvals, uin
     hipStream_t st = as_stream(stream);
     const u32 nBlocks = (u32)std::min<u64>(256, ((1ull << nBits) + 255) / 256);
     u64 *partial, *res;
-    P2_TRY(scratch(3, (u64)nEvals * nBlocks * 3 + (u64)nEvals * 3, &partial));
+    P2_TRY(scratch(SCR_EVALS, (u64)nEvals * nBlocks * 3 + (u64)nEvals * 3, &partial));
     res = partial + (u64)nEvals * nBlocks * 3;
     for (u32 e = 0; e < nEvals; e++) {
         if (descs[e].levIndex >= nLevs || (descs[e].dim != 1 && descs[e].dim != 3)) return fail(PIL2GL_EINVAL, "bad eval descriptor %u", e);
@@ -623,7 +612,7 @@ int pil2gl_synth_fibonacci_dev(uint32_t nBits, uint32_t nPairs, const uint64_t *
     P2_TRY(ensure_init());
     if (!hostInit || !cm || nBits > 31 || nPairs == 0) return fail(PIL2GL_EINVAL, "bad synthetic trace arguments");
     std::vector<u64> h(hostInit, hostInit + 2ull * nPairs);
-    u64 *d; P2_TRY(upload_small(h, 2, &d, as_stream(stream)));
+    u64 *d; P2_TRY(upload_small(h, SCR_FRI_TABLE, &d, as_stream(stream)));
     synth_fibonacci_kernel<<<nblk(nPairs, 64), 64, 0, as_stream(stream)>>>(nBits, nPairs, d, cm);
     KERNEL_CHECK();
     HIP_TRY(hipStreamSynchronize(as_stream(stream)));

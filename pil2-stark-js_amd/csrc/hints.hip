@@ -123,8 +123,8 @@ int run_hint(const u64 *num, u32 dimNum, const u64 *den, u32 dimDen, u64 n, u64 
     const u64 nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
     if (nb > 0x7fffffffull) return fail(PIL2GL_EINVAL, "grid too large");
     u64 *tmp, *totals;
-    P2_TRY(scratch(8, n * 3, &tmp));
-    P2_TRY(scratch(9, nb * 3, &totals));
+    P2_TRY(scratch(SCR_HINT_TMP, n * 3, &tmp));
+    P2_TRY(scratch(SCR_HINT_TOTALS, nb * 3, &totals));
     hint_scan1<PROD><<<(unsigned)nb, SCAN_THREADS, 0, st>>>(num, dimNum, den, dimDen, n, tmp, totals);
     KERNEL_CHECK();
     hint_scan2<PROD><<<1, SCAN_THREADS, 0, st>>>(totals, nb);
@@ -247,7 +247,7 @@ extern "C" int pil2gl_h1h2_dev(const uint64_t *f, const uint64_t *t, uint64_t n,
     u64 cap = 2; while (cap < 2 * n) cap <<= 1;
     const u64 nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
     u64 *ws;                                             // table[cap] | cnt[n] | start[n] | totals[nb] | missing[1]
-    P2_TRY(scratch(10, cap + 2 * n + nb + 1, &ws));
+    P2_TRY(scratch(SCR_HINT_WORK, cap + 2 * n + nb + 1, &ws));
     unsigned long long *table = (unsigned long long *)ws, *cnt = table + cap;
     u64 *start = ws + cap + n, *totals = start + n;
     unsigned long long *missing = (unsigned long long *)(totals + nb);

@@ -408,7 +408,7 @@ int pil2gl_group_proofs_dev(const uint64_t *elems, const uint64_t *nodes, uint64
     for (u32 i = 0; i < nIdx; i++) if (hostIdxs[i] >= height) return fail(PIL2GL_EINVAL, "Out of range");     // merklehash_p.js:143
     const u64 stride = width + 4ull * lv;
     u64 *d;
-    P2_TRY(scratch(6, (u64)nIdx * (stride + 1), &d));
+    P2_TRY(scratch(SCR_GROUP_PROOFS, (u64)nIdx * (stride + 1), &d));
     u64 *dIdx = d + (u64)nIdx * stride;
     HIP_TRY(hipMemcpy(dIdx, hostIdxs, (u64)nIdx * 8, hipMemcpyHostToDevice));
     group_proofs_kernel<<<nIdx, 64>>>(elems, nodes, width, height, dIdx, lv, d);
@@ -434,7 +434,7 @@ int pil2gl_roots_from_group_proofs(const uint64_t *hostProofs, uint64_t width, u
         h[nv + ns + q] = hostIdxs[q];
     }
     u64 *d;
-    P2_TRY(scratch(6, nv + ns + nIdx + 8ull * nIdx + 1, &d));
+    P2_TRY(scratch(SCR_GROUP_PROOFS, nv + ns + nIdx + 8ull * nIdx + 1, &d));
     u64 *dVals = d, *dSib = d + nv, *dIdx = dSib + ns, *dLeaf = dIdx + nIdx, *dRoots = dLeaf + 4ull * nIdx;
     HIP_TRY(hipMemcpy(d, h.data(), (nv + ns + nIdx) * 8, hipMemcpyHostToDevice));
     P2_TRY(pil2gl_linear_hash_rows_dev(dVals, width, nIdx, splitLinearHash, dLeaf, nullptr));
@@ -449,86 +449,69 @@ int pil2gl_sponge_absorb(const uint64_t *hostBlocks, uint64_t nBlocks, const uin
     P2_TRY(ensure_init());
     if (!hostBlocks || !hostCap || !hostOut12) return fail(PIL2GL_EINVAL, "null buffer");
     if (nBlocks == 0) return fail(PIL2GL_EINVAL, "nothing to absorb");
-    u64 *d; bool owned;
-    P2_TRY(stage_acquire(8 * nBlocks + 4 + 12, &d, &owned));
-    int rc = PIL2GL_OK;
-    hipError_t e = hipMemcpy(d, hostBlocks, 8 * nBlocks * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + 8 * nBlocks, hostCap, 32, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D");
-    if (rc == PIL2GL_OK) {
-        sponge_chain_kernel<<<1, 64>>>(d, nBlocks, d + 8 * nBlocks, d + 8 * nBlocks + 4);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(hostOut12, d + 8 * nBlocks + 4, 96, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "sponge_chain_kernel");
-    }
-    stage_release(d, owned);
-    return rc;
+    Stage s(8 * nBlocks + 4 + 12);
+    const u64 *dBlocks = s.put(hostBlocks, 8 * nBlocks), *dCap = s.put(hostCap, 4);
+    u64 *dOut = s.take(12);
+    P2_TRY(s.rc());
+    sponge_chain_kernel<<<1, 64>>>(dBlocks, nBlocks, dCap, dOut);
+    KERNEL_CHECK();
+    return s.get(hostOut12, dOut, 12);
 }
 
 // ---- host-pointer forms ----
-static int with_dev(const uint64_t *hIn, u64 nIn, const uint64_t *hIn2, u64 nIn2, uint64_t *hOut, u64 nOut,
-                    int (*fn)(const u64 *, const u64 *, u64 *, void *), void *arg) {
-    P2_TRY(ensure_init());
-    u64 *d = nullptr; bool owned = false;
-    P2_TRY(stage_acquire(nIn + nIn2 + nOut, &d, &owned));
-    int rc = PIL2GL_OK;
-    hipError_t e = hipSuccess;
-    if (nIn) e = hipMemcpy(d, hIn, nIn * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nIn2) e = hipMemcpy(d + nIn, hIn2, nIn2 * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D");
-    if (rc == PIL2GL_OK) rc = fn(d, nIn2 ? d + nIn : nullptr, d + nIn + nIn2, arg);
-    if (rc == PIL2GL_OK && nOut) { e = hipMemcpy(hOut, d + nIn + nIn2, nOut * 8, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H"); }
-    stage_release(d, owned);
-    return rc;
-}
-struct LhArgs { u64 width, height; int split; };
-struct PsArgs { u64 count; u32 nOut; };
-
 int pil2gl_linear_hash_rows(const uint64_t *in, uint64_t width, uint64_t height, int split, uint64_t *out) {
-    LhArgs a = { width, height, split };
-    return with_dev(in, width * height, nullptr, 0, out, height * 4,
-                    [](const u64 *i, const u64 *, u64 *o, void *p) { LhArgs *a = (LhArgs *)p; return pil2gl_linear_hash_rows_dev(i, a->width, a->height, a->split, o, nullptr); }, &a);
+    Stage s(width * height + height * 4);
+    const u64 *dIn = s.put(in, width * height);
+    u64 *dOut = s.take(height * 4);
+    P2_TRY(s.rc());
+    P2_TRY(pil2gl_linear_hash_rows_dev(dIn, width, height, split, dOut, nullptr));
+    return s.get(out, dOut, height * 4);
 }
 int pil2gl_merkelize_level(const uint64_t *in, uint64_t nOps, uint64_t *out) {
-    return with_dev(in, nOps * 8, nullptr, 0, out, nOps * 4,
-                    [](const u64 *i, const u64 *, u64 *o, void *p) { return pil2gl_merkelize_level_dev(i, *(u64 *)p, o, nullptr); }, &nOps);
+    Stage s(nOps * 12);
+    const u64 *dIn = s.put(in, nOps * 8);
+    u64 *dOut = s.take(nOps * 4);
+    P2_TRY(s.rc());
+    P2_TRY(pil2gl_merkelize_level_dev(dIn, nOps, dOut, nullptr));
+    return s.get(out, dOut, nOps * 4);
 }
 int pil2gl_poseidon(const uint64_t *in, const uint64_t *cap, uint64_t count, uint32_t nOut, uint64_t *out) {
     if (nOut < 1 || nOut > 12) return fail(PIL2GL_EINVAL, "nOut must be 1..12");
-    PsArgs a = { count, nOut };
-    return with_dev(in, count * 8, cap, cap ? count * 4 : 0, out, count * nOut,
-                    [](const u64 *i, const u64 *c, u64 *o, void *p) { PsArgs *a = (PsArgs *)p; return pil2gl_poseidon_dev(i, c, a->count, a->nOut, o, nullptr); }, &a);
+    const u64 nCap = cap ? count * 4 : 0;
+    Stage s(count * 8 + nCap + count * nOut);
+    const u64 *dIn = s.put(in, count * 8), *dCap = s.put(cap, nCap);
+    u64 *dOut = s.take(count * nOut);
+    P2_TRY(s.rc());
+    P2_TRY(pil2gl_poseidon_dev(dIn, dCap, count, nOut, dOut, nullptr));
+    return s.get(out, dOut, count * nOut);
 }
-struct MdsArgs { u64 n; u32 layers; int mfma; };
 int pil2gl_selftest_mds(const uint64_t *states, uint64_t n, uint32_t layers, int mfma, uint64_t *out) {
     if (n == 0) return PIL2GL_OK;
-    MdsArgs a = { n, layers, mfma };
-    return with_dev(states, n * 12, nullptr, 0, out, n * 12,
-                    [](const u64 *i, const u64 *, u64 *o, void *p) {
-                        MdsArgs *a = (MdsArgs *)p;
-                        mds_selftest_kernel<<<(unsigned)((a->n + 255) / 256), 256>>>(i, a->n, a->layers, a->mfma, o);
-                        KERNEL_CHECK();
-                        return (int)PIL2GL_OK;
-                    }, &a);
+    Stage s(n * 24);
+    const u64 *dIn = s.put(states, n * 12);
+    u64 *dOut = s.take(n * 12);
+    P2_TRY(s.rc());
+    mds_selftest_kernel<<<(unsigned)((n + 255) / 256), 256>>>(dIn, n, layers, mfma, dOut);
+    KERNEL_CHECK();
+    return s.get(out, dOut, n * 12);
 }
 int pil2gl_selftest_poseidon(const uint64_t *states, uint64_t n, int what, uint64_t *out) {
     if (n == 0) return PIL2GL_OK;
     if (what < 0 || what > 4) return fail(PIL2GL_EINVAL, "what must be 0..4");
-    MdsArgs a = { n, 0, what };
-    return with_dev(states, n * 12, nullptr, 0, out, n * 12,
-                    [](const u64 *i, const u64 *, u64 *o, void *p) {
-                        MdsArgs *a = (MdsArgs *)p;
-                        poseidon_selftest_kernel<<<(unsigned)((a->n + 255) / 256), 256>>>(i, a->n, a->mfma, o);
-                        KERNEL_CHECK();
-                        return (int)PIL2GL_OK;
-                    }, &a);
+    Stage s(n * 24);
+    const u64 *dIn = s.put(states, n * 12);
+    u64 *dOut = s.take(n * 12);
+    P2_TRY(s.rc());
+    poseidon_selftest_kernel<<<(unsigned)((n + 255) / 256), 256>>>(dIn, n, what, dOut);
+    KERNEL_CHECK();
+    return s.get(out, dOut, n * 12);
 }
 int pil2gl_selftest_clock(uint32_t iters, double *mhz /* [3]: median, 5th and 95th percentile over the workgroups */) {
     P2_TRY(ensure_init());
     if (!mhz || iters == 0 || iters > 4096) return fail(PIL2GL_EINVAL, "iters must be 1..4096");
     const unsigned blocks = 256 * 4 * 8;                        // eight rounds of four workgroups per CU
     u64 *d;
-    P2_TRY(scratch(5, (u64)blocks * 256 + 2ull * blocks, &d));
+    P2_TRY(scratch(SCR_CLOCK_PROBE, (u64)blocks * 256 + 2ull * blocks, &d));
     clock_probe_kernel<<<blocks, 256>>>(d, (int)iters, d + (u64)blocks * 256);
     KERNEL_CHECK();
     std::vector<u64> h(2 * blocks);
@@ -542,9 +525,13 @@ int pil2gl_selftest_clock(uint32_t iters, double *mhz /* [3]: median, 5th and 95
 }
 int pil2gl_merkelize(const uint64_t *elems, uint64_t width, uint64_t height, int split, uint64_t *nodes) {
     if (height == 0) return fail(PIL2GL_EINVAL, "height must be > 0");
-    LhArgs a = { width, height, split };
-    return with_dev(elems, width * height, nullptr, 0, nodes, pil2gl_merkle_num_nodes(height),
-                    [](const u64 *i, const u64 *, u64 *o, void *p) { LhArgs *a = (LhArgs *)p; return pil2gl_merkelize_dev(i, a->width, a->height, a->split, o, nullptr); }, &a);
+    const u64 nN = pil2gl_merkle_num_nodes(height);
+    Stage s(width * height + nN);
+    const u64 *dElems = s.put(elems, width * height);
+    u64 *dNodes = s.take(nN);
+    P2_TRY(s.rc());
+    P2_TRY(pil2gl_merkelize_dev(dElems, width, height, split, dNodes, nullptr));
+    return s.get(nodes, dNodes, nN);
 }
 
 }  // extern "C"

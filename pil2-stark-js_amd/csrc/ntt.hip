@@ -579,7 +579,7 @@ int ntt_launch(const u64 *src, u64 C, u32 n, u64 *dst, bool inverse, hipStream_t
     P2_TRY(plan_ntt(n, C, inverse, plan_options(), p));
     const u64 N = 1ull << n, scale = inverse ? h_inv(N % 0xFFFFFFFF00000001ull) : 0;
     u64 *tmp = nullptr;                             // src -> tmp, in place there, -> dst
-    if (p.n > 1) P2_TRY(scratch(0, N * C, &tmp));
+    if (p.n > 1) P2_TRY(scratch(SCR_NTT_TMP, N * C, &tmp));
     for (int i = 0; i < p.n; i++) P2_TRY(launch_pass(p.l[i], i == 0 ? src : tmp, i == p.n - 1 ? dst : tmp, C, n, i == 0 ? scale : 0, st));
     return PIL2GL_OK;
 }
@@ -598,7 +598,7 @@ int lde_launch(const u64 *src, u64 C, u32 n, u64 *dst, u32 nExt, hipStream_t st,
     const u64 N = 1ull << n;
     const u64 *coef = src;              // what the mid kernel reads
     u64 *tmp = work;                    // the inverse passes: src -> tmp, then in place (the caller's workspace may be src itself)
-    if (p.l[0].kind == PASS_INV_DIF && !tmp) P2_TRY(scratch(0, N * C, &tmp));
+    if (p.l[0].kind == PASS_INV_DIF && !tmp) P2_TRY(scratch(SCR_NTT_TMP, N * C, &tmp));
     for (int i = 0; i < p.n; i++) {
         const Launch &L = p.l[i];
         if (L.kind == PASS_INV_DIF) { P2_TRY(launch_pass(L, coef, tmp, C, n, 0, st)); coef = tmp; }
@@ -760,9 +760,9 @@ static int host_wrap(const uint64_t *src, uint64_t nPols, uint32_t nBits, uint64
     const uint64_t keepWords = 1ull << 27;
     const bool keepIn = nIn <= keepWords, keepOut = nOut <= keepWords;
     uint64_t *dIn = nullptr, *dOut = nullptr;
-    if (keepIn) P2_TRY(scratch(12, nIn, &dIn)); else HIP_TRY(hipMalloc((void **)&dIn, nIn * 8));
+    if (keepIn) P2_TRY(scratch(SCR_HOST_NTT_IN, nIn, &dIn)); else HIP_TRY(hipMalloc((void **)&dIn, nIn * 8));
     int rc = PIL2GL_OK;
-    if (keepOut) rc = scratch(13, nOut, &dOut);
+    if (keepOut) rc = scratch(SCR_HOST_NTT_OUT, nOut, &dOut);
     else { hipError_t e = hipMalloc((void **)&dOut, nOut * 8); if (e != hipSuccess) rc = hip_fail(e, "hipMalloc(dst)"); }
     hipError_t e = hipSuccess;
     if (rc == PIL2GL_OK) { e = hipMemcpy(dIn, src, nIn * 8, hipMemcpyHostToDevice); if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy H2D"); }

@@ -13,7 +13,6 @@ static bool g_ready = false;
 static int g_device = -1;
 static Tables g_tables = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
 static u64 *g_tables_mem = nullptr;
-static const u32 N_SCRATCH = 16;      // 12, 13: device copies of the host-pointer NTT entry points (ntt.hip host_wrap); 14, 15: the quotient stage (fri.hip)
 static u64 *g_scratch[N_SCRATCH] = { nullptr };
 static u64 g_scratch_words[N_SCRATCH] = { 0 };
 
@@ -78,7 +77,7 @@ int ensure_init() {
 // concurrent calls.
 std::recursive_mutex &runtime_lock() { static std::recursive_mutex m; return m; }
 
-int scratch(u32 slot, u64 nWords, u64 **out) {
+int scratch(ScratchSlot slot, u64 nWords, u64 **out) {
     std::lock_guard<std::recursive_mutex> lk(runtime_lock());
     if (slot >= N_SCRATCH) return fail(PIL2GL_EINVAL, "bad scratch slot");
     if (g_scratch_words[slot] < nWords) {
@@ -90,13 +89,31 @@ int scratch(u32 slot, u64 nWords, u64 **out) {
     return PIL2GL_OK;
 }
 
-int stage_acquire(u64 nWords, u64 **out, bool *owned) {
-    if (nWords <= (2ull << 20)) { *owned = false; return scratch(11, nWords + 1, out); }
-    *owned = true;
-    HIP_TRY(hipMalloc((void **)out, (nWords + 1) * 8));
-    return PIL2GL_OK;
+Stage::Stage(u64 nWords) : cap_(nWords) {
+    rc_ = ensure_init();
+    if (rc_ != PIL2GL_OK) return;
+    if (nWords <= (2ull << 20)) { rc_ = scratch(SCR_STAGE, nWords + 1, &d_); return; }
+    hipError_t e = hipMalloc((void **)&d_, (nWords + 1) * 8);
+    if (e != hipSuccess) { d_ = nullptr; rc_ = hip_fail(e, "hipMalloc (staging)"); }
+    else owned_ = true;
 }
-void stage_release(u64 *p, bool owned) { if (owned && p) (void)hipFree(p); }
+Stage::~Stage() { if (owned_) (void)hipFree(d_); }
+u64 *Stage::take(u64 n) {
+    if (rc_ != PIL2GL_OK) return nullptr;
+    if (n > cap_ - used_) { rc_ = fail(PIL2GL_EINVAL, "staging buffer too small"); return nullptr; }
+    u64 *p = d_ + used_;
+    used_ += n;
+    return p;
+}
+const u64 *Stage::put(const u64 *host, u64 n) {
+    u64 *p = n ? take(n) : nullptr;
+    if (p) { hipError_t e = hipMemcpy(p, host, n * 8, hipMemcpyHostToDevice); if (e != hipSuccess) { rc_ = hip_fail(e, "hipMemcpy H2D"); return nullptr; } }
+    return p;
+}
+int Stage::get(u64 *host, const u64 *dev, u64 n) {
+    if (rc_ == PIL2GL_OK && n) { hipError_t e = hipMemcpy(host, dev, n * 8, hipMemcpyDeviceToHost); if (e != hipSuccess) rc_ = hip_fail(e, "hipMemcpy D2H"); }
+    return rc_;
+}
 
 }  // namespace pil2gl
 

@@ -99,7 +99,7 @@ if __name__ == "__main__":
 
 # ------------------------------------------------------------------ the partial rounds, four to a block, rows as digit products
 def derive_sparse(t):
-    """bn128.hip::derive_sparse on plain integers: (C8[8][t], D[(t-1)^2], S[rp], V[rp][t-1], W[rp][t-1], m00)"""
+    """csrc/bn_params.cpp derive_sparse on plain integers: (C8[8][t], D[(t-1)^2], S[rp], V[rp][t-1], W[rp][t-1], m00)"""
     C, M = O.poseidon_constants(t)
     rp, n = O.N_ROUNDS_P[t - 2], t - 1
     Mh = [[M[i + 1][j + 1] for j in range(n)] for i in range(n)]
@@ -143,12 +143,35 @@ def derive_sparse(t):
     return C8, D, S, V, W, M[0][0], M
 
 
+def tile_values(a):
+    """the 32 plain integers one operand tile spells for the plain coefficient a: a 2^(8b+32) mod r, b < 32"""
+    return [a * pow(256, b, R) * (1 << 32) % R for b in range(32)]
+
+
+def row_const(coefs, n_acc=1, fold=0):
+    """the row constant of a row of plain coefficients gathered in n_acc accumulations; fold: a Montgomery-form constant added to the row"""
+    tot = sum(sum(tile_values(a)) for a in coefs)
+    return ((128 * tot - n_acc * OFF) * pow(1 << 32, -1, R) + fold) % R
+
+
 def row_tables(coefs, n_acc=1, fold=0):
-    """one row: plain coefficients, one per operand -> (digits[j][b][k], K); fold: a Montgomery-form constant added to the row"""
-    dig = [[signed_digits(a * pow(256, b, R) * (1 << 32) % R) for b in range(32)] for a in coefs]
-    tot = sum(a * pow(256, b, R) * (1 << 32) % R for a in coefs for b in range(32))
-    K = ((128 * tot - n_acc * OFF) * pow(1 << 32, -1, R) + fold) % R
-    return dig, K
+    """one row: plain coefficients, one per operand -> (digits[j][b][k], K)"""
+    return [[signed_digits(c) for c in tile_values(a)] for a in coefs], row_const(coefs, n_acc, fold)
+
+
+def decode_tile(tile):
+    """one 1 KB operand tile in the lane order the host writes (csrc/bn_params.cpp mfma_tile: digit pos(m) of block b is byte
+    ((b // 16) * 32 + m) * 16 + b % 16, pos(m) = 16 ((m / 4) % 2) + 4 (m / 8) + m % 4) -> the 32 integers its signed base-256 digits spell"""
+    assert len(tile) == 1024
+    out = []
+    for b in range(32):
+        g, sl = divmod(b, 16)
+        c = 0
+        for m in range(32):
+            d = tile[(g * 32 + m) * 16 + sl]
+            c += (d - 256 if d >= 128 else d) << (8 * (16 * ((m // 4) % 2) + 4 * (m // 8) + m % 4))
+        out.append(c)
+    return out
 
 
 def row_positions(dig, x):
