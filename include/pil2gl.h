@@ -445,6 +445,37 @@ int pil2gl_bn128_roots_from_group_proofs(const uint64_t *hostVals, const uint64_
 int pil2gl_bn128_convert(const uint64_t *in, uint64_t n, int toMontgomery, uint64_t *out);
 int pil2gl_bn128_convert_dev(const uint64_t *in, uint64_t n, int toMontgomery, uint64_t *out, void *stream);
 
+/* ---- BN254 Fr transforms: src/helpers/fft/fft_p.bn128.js, fft_worker.bn128.js (csrc/bn_ntt.hip) ----------------------------------
+ * The multi-column NTT the fflonk prover runs over its committed polynomials (fflonk_prover_helpers.js:312,334, fflonk_setup.js:42).
+ * An element is 4 little-endian u64 words of a * 2^256 mod r, MONTGOMERY form in and out (the bytes ffjavascript's Fr keeps in its
+ * buffers, and the form of tree.nodes above).  Inputs must be canonical (< r); they are not validated.  Row-major: element (row j,
+ * polynomial i) at word (j*nPols + i)*4 (test/fft_p.bn128.test.js:28).  Roots of unity are ffjavascript's Fr.w[]: w[28] =
+ * 5^((r-1)/2^28), w[k] = w[k+1]^2.  nBits <= nBitsExt <= 28, else PIL2GL_EINVAL; nBits = 0 copies the row.  Argument errors are
+ * reported before any device call; the compute entries return PIL2GL_ENODEV without a device.  The _dev forms take device pointers
+ * (16-byte aligned) and only enqueue on the caller's stream; the others take host pointers and stage through device copies.
+ * Two exceptions to "only enqueue", both on FIRST use: the twiddle tables of a size and direction are allocated and uploaded with a
+ * synchronous copy, and the working buffer of a transform of more than 2^10 rows is (re)allocated, with a device synchronise, when it
+ * has to grow -- make one call of the largest size before capturing a stream into a graph.  That working buffer is one per process, as
+ * every scratch buffer of this library is (one caller at a time, any stream): two transforms of more than 2^10 rows must not be in flight
+ * on different streams at once. */
+/* fft(buffSrc, nPols, nBits, buffDst, Fr)  fft_p.bn128.js:178-223: dst[j] = sum_k src[k] w[nBits]^(jk), natural order in and out; dst may be src */
+int pil2gl_bn128_fft(const uint64_t *src, uint64_t nPols, uint32_t nBits, uint64_t *dst);
+/* ifft(...)  fft_p.bn128.js:58-71,178-223 (invBitReverse): dst[k] = 1/n sum_j src[j] w[nBits]^(-jk); dst may be src */
+int pil2gl_bn128_ifft(const uint64_t *src, uint64_t nPols, uint32_t nBits, uint64_t *dst);
+/* interpolate(buffSrc, nPols, nBits, buffDstCoefs, buffDst, nBitsExt, Fr)  fft_p.bn128.js:225-285: dstCoefs (2^nBits rows; may be NULL)
+ * = ifft(src), scaled by 1/n (:265-266); dst (2^nBitsExt rows) = fft of the coefficients padded with zero rows.  NO coset shift
+ * (fft_worker.bn128.js:15-22 never advances its factor).  dst and dstCoefs must not overlap each other or src. */
+int pil2gl_bn128_interpolate(const uint64_t *src, uint64_t nPols, uint32_t nBits, uint64_t *dstCoefs, uint64_t *dst, uint32_t nBitsExt);
+int pil2gl_bn128_fft_dev(const uint64_t *src, uint64_t nPols, uint32_t nBits, uint64_t *dst, void *stream);
+int pil2gl_bn128_ifft_dev(const uint64_t *src, uint64_t nPols, uint32_t nBits, uint64_t *dst, void *stream);
+int pil2gl_bn128_interpolate_dev(const uint64_t *src, uint64_t nPols, uint32_t nBits, uint64_t *dstCoefs, uint64_t *dst, uint32_t nBitsExt, void *stream);
+/* host-only, no device: the sweeps over global memory a transform of 2^nBits rows makes (the replacement of fft_p.bn128.js:200-221's
+ * block loop): *nSweeps of them, layersPerSweep[i] butterfly layers in sweep i (room entries available; 3 always suffice), summing to
+ * nBits.  A sweep of K layers keeps 2^K rows x min(nPols, tile_bytes / 32 >> K) columns in LDS; pil2gl_debug_bn128_fft_tile_bytes is that
+ * limit.  nBits = 0 has no sweep; nBits > 28 is PIL2GL_EINVAL. */
+int pil2gl_debug_bn128_fft_plan(uint32_t nBits, uint32_t *layersPerSweep, uint32_t room, uint32_t *nSweeps);
+uint32_t pil2gl_debug_bn128_fft_tile_bytes(void);
+
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):
  * cm is 2^nBits x (2*nPairs) row-major (l1_k, l2_k), hostInit = 2*nPairs canonical start values (host pointer). */

@@ -186,6 +186,36 @@ FN(IfftDev) {
     P2(env, pil2gl_ifft_dev((const uint64_t *)(uintptr_t)s, nPols, (uint32_t)nBits, (uint64_t *)(uintptr_t)d, a.stream(4))); return mk_undefined(env);
 }
 
+// ---- BN254 Fr transforms (fft_p.bn128.js:178-285): 4 words per element, Montgomery form ----
+static napi_value bn128_fft_common(napi_env env, napi_callback_info info, bool inverse) {      // (src, nPols, nBits, dst)
+    Args a(env, info); uint64_t nPols = a.u64(1); uint32_t nBits = (uint32_t)a.u64(2);
+    if (nBits > 40) a.fail("bad size");
+    uint64_t *s = a.arr(0, a.ok ? (nPols << nBits) * 4 : 0), *d = a.arr(3, a.ok ? (nPols << nBits) * 4 : 0); if (!a.ok) return nullptr;
+    P2(env, inverse ? pil2gl_bn128_ifft(s, nPols, nBits, d) : pil2gl_bn128_fft(s, nPols, nBits, d)); return mk_undefined(env);
+}
+FN(Bn128Fft) { return bn128_fft_common(env, info, false); }
+FN(Bn128Ifft) { return bn128_fft_common(env, info, true); }
+FN(Bn128Interpolate) {   // (src, nPols, nBits, dstCoefs | null, dst, nBitsExt)  fft_p.bn128.js:225
+    Args a(env, info); uint64_t nPols = a.u64(1); uint32_t nBits = (uint32_t)a.u64(2), nBitsExt = (uint32_t)a.u64(5);
+    if (nBits > 40 || nBitsExt > 40) a.fail("bad size");
+    uint64_t *s = a.arr(0, a.ok ? (nPols << nBits) * 4 : 0), *c = a.is_nullish(3) ? nullptr : a.arr(3, a.ok ? (nPols << nBits) * 4 : 0);
+    uint64_t *d = a.arr(4, a.ok ? (nPols << nBitsExt) * 4 : 0); if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_interpolate(s, nPols, nBits, c, d, nBitsExt)); return mk_undefined(env);
+}
+FN(Bn128FftDev) {        // (dSrc, nPols, nBits, dDst[, stream])
+    Args a(env, info); uint64_t *s = DP(0); uint64_t nPols = a.u64(1), nBits = a.u64(2); uint64_t *d = DP(3); if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_fft_dev(s, nPols, (uint32_t)nBits, d, a.stream(4))); return mk_undefined(env);
+}
+FN(Bn128IfftDev) {
+    Args a(env, info); uint64_t *s = DP(0); uint64_t nPols = a.u64(1), nBits = a.u64(2); uint64_t *d = DP(3); if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_ifft_dev(s, nPols, (uint32_t)nBits, d, a.stream(4))); return mk_undefined(env);
+}
+FN(Bn128InterpolateDev) { // (dSrc, nPols, nBits, dDstCoefs | null, dDst, nBitsExt[, stream])
+    Args a(env, info); uint64_t *s = DP(0); uint64_t nPols = a.u64(1), nBits = a.u64(2); uint64_t *c = a.is_nullish(3) ? nullptr : DP(3); uint64_t *d = DP(4); uint64_t nBitsExt = a.u64(5);
+    if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_interpolate_dev(s, nPols, (uint32_t)nBits, c, d, (uint32_t)nBitsExt, a.stream(6))); return mk_undefined(env);
+}
+
 // ---- hashing ----
 FN(Poseidon) {       // (in BigUint64Array(8*count), cap BigUint64Array(4*count)|null, count, nOut, out)
     Args a(env, info); uint64_t count = a.u64(2); uint32_t nOut = (uint32_t)a.u64(3);
@@ -529,6 +559,8 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128Poseidon", Bn128Poseidon }, { "bn128SpongeAbsorb", Bn128SpongeAbsorb }, { "bn128LinearHashRows", Bn128LinearHashRows }, { "bn128MerkleNumNodes", Bn128MerkleNumNodes },
         { "bn128Merkelize", Bn128Merkelize }, { "bn128MerkelizeDev", Bn128MerkelizeDev }, { "bn128GroupProofDev", Bn128GroupProofDev }, { "bn128GroupProofsDev", Bn128GroupProofsDev },
         { "bn128RootsFromGroupProofs", Bn128RootsFromGroupProofs }, { "bn128Convert", Bn128Convert },
+        { "bn128Fft", Bn128Fft }, { "bn128Ifft", Bn128Ifft }, { "bn128Interpolate", Bn128Interpolate },
+        { "bn128FftDev", Bn128FftDev }, { "bn128IfftDev", Bn128IfftDev }, { "bn128InterpolateDev", Bn128InterpolateDev },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

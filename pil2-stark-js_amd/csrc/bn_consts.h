@@ -18,4 +18,11 @@ constexpr int ACC_BIAS = 1 << 30;                    // 2.0f's bit pattern: an i
 constexpr int MFMA_AHEAD = 8;
 constexpr int BN_SPARE_TILES = 2 * MFMA_AHEAD;
 
+// The Fr transforms (bn_ntt.hip; their planning and root tables: bn_params.cpp).  A sweep keeps a tile of 2^K rows x a group of columns in LDS,
+// 32 bytes per element: 2048 elements = 64 KiB, two workgroups per CU.  K <= 10: the table of tile twiddles holds the 512 powers of w[10].
+constexpr unsigned BN_NTT_MAX_BITS = 28;             // Fr.s: r - 1 = 2^28 * odd
+constexpr unsigned BN_NTT_KMAX = 10;
+constexpr unsigned BN_NTT_TILE_ELEMS = 2048;
+constexpr unsigned BN_NTT_MAX_SWEEPS = (BN_NTT_MAX_BITS + BN_NTT_KMAX - 1) / BN_NTT_KMAX;
+
 }  // namespace bnc

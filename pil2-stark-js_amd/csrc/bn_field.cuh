@@ -89,6 +89,26 @@ __device__ __forceinline__ void fr_add(u32 a[8], const u32 b[8]) {
     for (int i = 0; i < 8; i++) a[i] = t[i];
 }
 
+// a = a - b mod r   (a, b < r): the borrow of the eight-limb difference becomes a mask and r AND the mask is added back.  Plain C++: the
+// transforms' butterflies (bn_ntt.hip) spend one of these per product, and hipcc turns both chains into v_sub_co / v_addc_co on its own
+__device__ __forceinline__ void fr_sub(u32 a[8], const u32 b[8]) {
+    u32 borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const u64 d = (u64)a[i] - b[i] - borrow;
+        a[i] = (u32)d;
+        borrow = (u32)(d >> 63);
+    }
+    const u32 mask = 0u - borrow;
+    u32 carry = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const u64 s = (u64)a[i] + (r_limb(i) & mask) + carry;
+        a[i] = (u32)s;
+        carry = (u32)(s >> 32);
+    }
+}
+
 // (lo, hi) += x * y      /     (lo, hi) += x
 __device__ __forceinline__ void acc_mad(u64 &lo, u32 &hi, u32 x, u32 y) {
     asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc" : "+v"(lo), "+v"(hi) : "v"(x), "v"(y) : "vcc");

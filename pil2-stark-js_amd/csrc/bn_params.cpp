@@ -349,4 +349,39 @@ int bn_build_params(int t, BnHostParams &out) {
     return PIL2GL_OK;
 }
 
+// ------------------------------------------------------------------------------------------ the Fr transforms
+U256 bn_mont_mul(const U256 &a, const U256 &b) { return h_mont(a, b); }
+
+void bn_powers(const U256 &g, size_t n, U256 *out) {
+    U256 acc = h_to_mont(U256{ { 1, 0, 0, 0 } });
+    for (size_t i = 0; i < n; i++) { out[i] = acc; acc = h_mont(acc, g); }
+}
+
+const BnNttConsts &bn_ntt_consts() {
+    static const BnNttConsts K = [] {
+        BnNttConsts c;
+        U256 e = HR; e.w[0] -= 1;                    // (r - 1) >> 28
+        for (int i = 0; i < 4; i++) e.w[i] = (e.w[i] >> BN_NTT_MAX_BITS) | (i < 3 ? e.w[i + 1] << (64 - BN_NTT_MAX_BITS) : 0);
+        const U256 one = h_to_mont(U256{ { 1, 0, 0, 0 } }), five = h_to_mont(U256{ { 5, 0, 0, 0 } });
+        U256 acc = one;
+        for (int i = 255; i >= 0; i--) {
+            acc = h_mont(acc, acc);
+            if ((e.w[i / 64] >> (i % 64)) & 1) acc = h_mont(acc, five);
+        }
+        c.w[BN_NTT_MAX_BITS] = acc;
+        for (int k = (int)BN_NTT_MAX_BITS - 1; k >= 0; k--) c.w[k] = h_mont(c.w[k + 1], c.w[k + 1]);
+        U256 p2 = one;
+        for (unsigned k = 0; k <= BN_NTT_MAX_BITS; k++) { c.wi[k] = h_inv_mont(c.w[k]); c.ninv[k] = h_inv_mont(p2); p2 = h_addmod(p2, p2); }
+        return c;
+    }();
+    return K;
+}
+
+int bn_ntt_plan(unsigned nBits, unsigned *layers) {
+    if (nBits > BN_NTT_MAX_BITS) return -1;
+    const unsigned S = (nBits + BN_NTT_KMAX - 1) / BN_NTT_KMAX;
+    for (unsigned i = 0; i < S; i++) layers[i] = nBits / S + (i < nBits % S ? 1 : 0);
+    return (int)S;
+}
+
 }  // namespace bnp

@@ -38,4 +38,17 @@ struct BnHostParams {
 // t = 2..17.  No device, no globals.  Returns 0, or PIL2GL_EINVAL with out.error set.
 int bn_build_params(int t, BnHostParams &out);
 
+// ---- the Fr transforms (bn_ntt.hip) ----
+// Roots of unity as ffjavascript's Fr.w[] has them: w[28] = 5^((r-1)/2^28) (5: the smallest quadratic non-residue), w[k] = w[k+1]^2;
+// wi[k] = 1/w[k], ninv[k] = 1/2^k.  Montgomery form, computed on first use with the host arithmetic above (nothing typed in).
+struct BnNttConsts { U256 w[29], wi[29], ninv[29]; };
+const BnNttConsts &bn_ntt_consts();
+// out[i] = g^i, i < n (Montgomery form in and out)
+void bn_powers(const U256 &g, size_t n, U256 *out);
+U256 bn_mont_mul(const U256 &a, const U256 &b);
+// The sweeps of a transform of 2^nBits rows: layers[i] butterfly layers in sweep i, as even as ceil(nBits / BN_NTT_KMAX) sweeps allow (the
+// first ones take the odd layers).  A sweep of K layers holds 2^K rows x min(nPols, BN_NTT_TILE_ELEMS >> K) columns.  Returns the number of
+// sweeps (0 for nBits = 0), -1 for nBits > BN_NTT_MAX_BITS.  layers: room for BN_NTT_MAX_SWEEPS.
+int bn_ntt_plan(unsigned nBits, unsigned *layers);
+
 }  // namespace bnp

@@ -66,6 +66,7 @@ enum ScratchSlot : u32 {
     SCR_Q_A = 14,             // fri.hip: the quotient stage (q, then its coefficients in SCR_Q_B) and the FRI polynomial (x / (x - xi) tables, accumulators)
     SCR_Q_B = 15,
     SCR_CLOCK_PROBE = 16,     // merkle.hip pil2gl_selftest_clock
+    SCR_BN_NTT_TMP = 17,      // bn_ntt.hip: the working buffer of a BN254 transform of more than one sweep
     N_SCRATCH
 };
 int scratch(ScratchSlot slot, u64 nWords, u64 **out);

@@ -9,6 +9,7 @@ module.exports = {
     copySync: require("./native.js").copySync,
     fft_p: require("./fft_p.js"),
     fft_worker: require("./fft_worker.js"),
+    fft_p_bn128: require("./fft_p_bn128.js"),
     buildMerkleHash: require("./merklehash_p.js"),
     buildPoseidon: require("./poseidon.js"),
     buildMerkleHashBN128: require("./merklehash_bn128_p.js"),

@@ -157,6 +157,14 @@ SIGNATURES = {
     "pil2gl_debug_bn128_path_launches": (_U64, []),
     "pil2gl_bn128_convert": (_I, [vp, _U64, _I, vp]),
     "pil2gl_bn128_convert_dev": (_I, [vp, _U64, _I, vp, vp]),
+    "pil2gl_bn128_fft": (_I, [vp, _U64, _U32, vp]),
+    "pil2gl_bn128_ifft": (_I, [vp, _U64, _U32, vp]),
+    "pil2gl_bn128_interpolate": (_I, [vp, _U64, _U32, vp, vp, _U32]),
+    "pil2gl_bn128_fft_dev": (_I, [vp, _U64, _U32, vp, vp]),
+    "pil2gl_bn128_ifft_dev": (_I, [vp, _U64, _U32, vp, vp]),
+    "pil2gl_bn128_interpolate_dev": (_I, [vp, _U64, _U32, vp, vp, _U32, vp]),
+    "pil2gl_debug_bn128_fft_plan": (_I, [_U32, C.POINTER(_U32), _U32, C.POINTER(_U32)]),
+    "pil2gl_debug_bn128_fft_tile_bytes": (_U32, []),
     "pil2gl_selftest_field": (_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_ext": (_I, [vp, vp, _U64, vp, vp]),
     "pil2gl_selftest_products": (_I, [vp, vp, _U64, vp, vp, vp]),

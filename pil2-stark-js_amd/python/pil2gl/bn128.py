@@ -3,6 +3,7 @@
   LinearHashBN                    <-> src/helpers/hash/linearhash/linearhash.bn128.js:4-62
   Transcript                      <-> src/helpers/transcript/transcript.bn128.js:1-106
   poseidon(inputs, initState, nOut) <-> circomlibjs buildPoseidon() as the reference calls it
+  fft / ifft / interpolate        <-> src/helpers/fft/fft_p.bn128.js:178-285 (Montgomery words in and out)
 Field elements cross this API as Python ints in normal form (the JS modules use BigInt / F.toObject)."""
 import ctypes as C
 
@@ -77,6 +78,45 @@ def to_montgomery(vals):
     w = _words(vals); o = np.zeros_like(w)
     call("pil2gl_bn128_convert", _ptr(w), w.shape[0], 1, _ptr(o))
     return o
+
+
+def _transform(name, words, nPols, nBits, out):
+    _check_len(words, (nPols << nBits) * 4, "words")
+    if out is None:
+        out = torch.empty_like(words) if _is_dev(words) else np.empty_like(words)
+    _check_len(out, (nPols << nBits) * 4, "out")
+    if _is_dev(words):
+        call(name + "_dev", _ptr(words), nPols, nBits, _ptr(out), _stream())
+    else:
+        call(name, _ptr(words), nPols, nBits, _ptr(out))
+    return out
+
+
+def fft(words, nPols, nBits, out=None):
+    """fft_p.bn128.js:178: words = (2^nBits, nPols, 4) uint64 Montgomery words, a numpy array or a device tensor; the result (natural
+    order, Montgomery words) is a new buffer of the same kind, or `out` (which may be `words`)"""
+    return _transform("pil2gl_bn128_fft", words, nPols, nBits, out)
+
+
+def ifft(words, nPols, nBits, out=None):
+    """fft_p.bn128.js:182"""
+    return _transform("pil2gl_bn128_ifft", words, nPols, nBits, out)
+
+
+def interpolate(words, nPols, nBits, nBitsExt, coefs=True):
+    """fft_p.bn128.js:225: -> (coefficients (2^nBits, nPols, 4), evaluations on the 2^nBitsExt roots (2^nBitsExt, nPols, 4)), no coset
+    shift; coefs=False skips the first output (None in its place)"""
+    _check_len(words, (nPols << nBits) * 4, "words")
+    dev = _is_dev(words)
+    if dev:
+        ext = torch.empty((1 << nBitsExt, nPols, 4), dtype=words.dtype, device=words.device)
+        co = torch.empty((1 << nBits, nPols, 4), dtype=words.dtype, device=words.device) if coefs else None
+        call("pil2gl_bn128_interpolate_dev", _ptr(words), nPols, nBits, _ptr(co), _ptr(ext), nBitsExt, _stream())
+    else:
+        ext = np.empty((1 << nBitsExt, nPols, 4), np.uint64)
+        co = np.empty((1 << nBits, nPols, 4), np.uint64) if coefs else None
+        call("pil2gl_bn128_interpolate", _ptr(words), nPols, nBits, _ptr(co), _ptr(ext), nBitsExt)
+    return co, ext
 
 
 class LinearHashBN:
