@@ -624,30 +624,38 @@ static void load_dim(const uint64_t *p, uint64_t i, int dim, uint64_t r[3]) {
 static void store_dim(uint64_t *p, uint64_t i, int dim, const uint64_t r[3]) {
     if (dim == 3) { p[3 * i] = r[0]; p[3 * i + 1] = r[1]; p[3 * i + 2] = r[2]; } else p[i] = r[0];
 }
+/* the rows' ratios num[i] / den[i] (num one element when numOne): independent of each other, so the inversions -- nearly all of the
+ * work -- are spread over the threads; the running product / sum below stays the serial walk of the reference */
+static uint64_t *hint_ratios(const uint64_t *num, int dimNum, int numOne, const uint64_t *den, int dimDen, uint64_t n) {
+    uint64_t *r = (uint64_t *)malloc((n ? n : 1) * 24);
+#pragma omp parallel for schedule(static) num_threads(g_threads) if (n >= 4096)
+    for (uint64_t i = 0; i < n; i++) {
+        uint64_t a[3], d[3], di[3];
+        load_dim(num, numOne ? 0 : i, dimNum, a); load_dim(den, i, dimDen, d);
+        or3_inv(d, di);
+        or3_mul(a, di, r + 3 * i);
+    }
+    return r;
+}
 /* calculateZ (polutils.js:128-143): z[0] = 1, z[i] = z[i-1] * num[i-1] / den[i-1] */
 void or_gprod(const uint64_t *num, int dimNum, const uint64_t *den, int dimDen, uint64_t n, uint64_t *out) {
     int dimOut = (dimNum == 3 || dimDen == 3) ? 3 : 1;
     uint64_t z[3] = { 1, 0, 0 };
+    uint64_t *r = hint_ratios(num, dimNum, 0, den, dimDen, n);
     for (uint64_t i = 0; i < n; i++) {
         store_dim(out, i, dimOut, z);
-        uint64_t a[3], d[3], di[3], r[3];
-        load_dim(num, i, dimNum, a); load_dim(den, i, dimDen, d);
-        or3_inv(d, di);
-        or3_mul(a, di, r);
-        or3_mul(z, r, z);
+        or3_mul(z, r + 3 * i, z);
     }
+    free(r);
 }
 /* calculateS (polutils.js:145-164): s[i] = sum_{j<=i} num / den[j], num a single element */
 void or_gsum(const uint64_t *num, int dimNum, const uint64_t *den, int dimDen, uint64_t n, uint64_t *out) {
     int dimOut = (dimNum == 3 || dimDen == 3) ? 3 : 1;
-    uint64_t s[3] = { 0, 0, 0 }, a[3];
-    load_dim(num, 0, dimNum, a);
+    uint64_t s[3] = { 0, 0, 0 };
+    uint64_t *r = hint_ratios(num, dimNum, 1, den, dimDen, n);
     for (uint64_t i = 0; i < n; i++) {
-        uint64_t d[3], di[3], r[3];
-        load_dim(den, i, dimDen, d);
-        or3_inv(d, di);
-        or3_mul(a, di, r);
-        add3(s, r, s);
+        add3(s, r + 3 * i, s);
         store_dim(out, i, dimOut, s);
     }
+    free(r);
 }
