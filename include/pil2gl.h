@@ -476,6 +476,37 @@ int pil2gl_bn128_interpolate_dev(const uint64_t *src, uint64_t nPols, uint32_t n
 int pil2gl_debug_bn128_fft_plan(uint32_t nBits, uint32_t *layersPerSweep, uint32_t room, uint32_t *nSweeps);
 uint32_t pil2gl_debug_bn128_fft_tile_bytes(void);
 
+/* ---- BN254 G1 multi-scalar multiplication: G1.toAffine(G1.multiExpAffine(bases, scalars)) (csrc/bn_msm.hip) ----------------------
+ * The commitment step of the fflonk prover (commit(..., {multiExp: true}): fflonk_prover_helpers.js:185,336, fflonk_setup.js:52):
+ * out = sum_i scalars[i] * bases[i] on y^2 = x^3 + 3 over Fq, generator (1, 2) of order r.  Byte formats are ffjavascript's:
+ *   bases    n affine points, 8 little-endian u64 each: x then y, Fq MONTGOMERY form (a * 2^256 mod q), as ptau section 2 / zkey.pTau
+ *            holds them.  Infinity is 64 zero bytes (G1.zeroAffine).  Coordinates must be canonical (< q); membership of the curve is NOT
+ *            validated.
+ *   scalars  element i is the 4 words at word 4 * i * scalarStride: a column of a row-major coefficient matrix of nPols columns commits
+ *            with scalarStride = nPols and no gather (the copy loop of fflonk_prover_helpers.js:326-331).  scalarsMontgomery != 0: Fr
+ *            Montgomery words, what pil2gl_bn128_ifft leaves (any value < 2^256, reduced mod r); 0: normal form, canonical (< r), what
+ *            multiExpAffine itself takes after Fr.batchFromMontgomery.  A normal-form scalar >= r gives an unspecified point (no fault).
+ *   out      one affine point in the format of bases; n = 0 and an empty sum give 64 zero bytes.
+ * 0 <= n <= 2^28 and 1 <= scalarStride < 2^32, else PIL2GL_EINVAL; so is a null buffer (bases / scalars only with n > 0).  Argument
+ * errors are reported before any device call; without a device the entries return PIL2GL_ENODEV (the host form with n = 0 needs none).
+ * The _dev form takes device pointers (bases and scalars 16-byte aligned, out 8-byte), only enqueues on the caller's stream and writes
+ * out on the device.  One exception, on FIRST use, as for the transforms above: the working buffer (pil2gl_debug_bn128_msm_plan's
+ * scratchBytes) is (re)allocated, with a device synchronise, when it has to grow -- make one call of the largest n before capturing a
+ * stream into a graph; it is one per process, so two MSMs must not be in flight on different streams at once.  The host form stages
+ * bases, the scalars up to the last one read, and out through device copies. */
+int pil2gl_bn128_g1_msm(const uint64_t *bases, const uint64_t *scalars, uint64_t n, uint64_t scalarStride, uint32_t scalarsMontgomery, uint64_t *out);
+int pil2gl_bn128_g1_msm_dev(const uint64_t *bases, const uint64_t *scalars, uint64_t n, uint64_t scalarStride, uint32_t scalarsMontgomery,
+                            uint64_t *out, void *stream);
+/* host-only, no device: how an MSM of n points runs.  out[0] = c, the window width in bits; [1] = nWindows = ceil(255 / c); [2] = buckets
+ * per window = 2^(c-1) (signed digits); [3] = windows whose point lists are built and accumulated per pass.  *scratchBytes = the working
+ * buffer, at most 4 * clamp(8 n, 2^19, 2^30) + 96 MiB (0 for n = 0).  n > 2^28 is PIL2GL_EINVAL. */
+int pil2gl_debug_bn128_msm_plan(uint64_t n, uint32_t *out, uint64_t *scratchBytes);
+/* host-only, no device: the signed digits the kernels split a scalar into (normal form, below 2^254) for windows of c bits, least
+ * significant first, by the code the kernels run: *nDigits = ceil(255 / c) of them (room entries available), each in
+ * [-(2^(c-1) - 1), 2^(c-1)], sum_w digits[w] 2^(c w) = scalar.  c outside 4..16, a larger scalar or too little room: PIL2GL_EINVAL
+ * (the count still comes back in the last case). */
+int pil2gl_debug_bn128_msm_digits(const uint64_t scalar[4], uint32_t c, int32_t *digits, uint32_t room, uint32_t *nDigits);
+
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):
  * cm is 2^nBits x (2*nPairs) row-major (l1_k, l2_k), hostInit = 2*nPairs canonical start values (host pointer). */

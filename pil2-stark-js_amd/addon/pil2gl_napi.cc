@@ -216,6 +216,12 @@ FN(Bn128InterpolateDev) { // (dSrc, nPols, nBits, dDstCoefs | null, dDst, nBitsE
     P2(env, pil2gl_bn128_interpolate_dev(s, nPols, (uint32_t)nBits, c, d, (uint32_t)nBitsExt, a.stream(6))); return mk_undefined(env);
 }
 
+// ---- BN254 G1 multi-scalar multiplication (G1.multiExpAffine + toAffine): device pointers, the 64 bytes written on the device ----
+FN(Bn128G1MsmDev) {      // (dBases, dScalars, n, scalarStride, scalarsMontgomery, dOut[, stream])
+    Args a(env, info); uint64_t *b = DP(0), *s = DP(1); uint64_t n = a.u64(2), stride = a.u64(3), mont = a.u64(4); uint64_t *o = DP(5); if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_g1_msm_dev(b, s, n, stride, (uint32_t)mont, o, a.stream(6))); return mk_undefined(env);
+}
+
 // ---- hashing ----
 FN(Poseidon) {       // (in BigUint64Array(8*count), cap BigUint64Array(4*count)|null, count, nOut, out)
     Args a(env, info); uint64_t count = a.u64(2); uint32_t nOut = (uint32_t)a.u64(3);
@@ -561,6 +567,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128RootsFromGroupProofs", Bn128RootsFromGroupProofs }, { "bn128Convert", Bn128Convert },
         { "bn128Fft", Bn128Fft }, { "bn128Ifft", Bn128Ifft }, { "bn128Interpolate", Bn128Interpolate },
         { "bn128FftDev", Bn128FftDev }, { "bn128IfftDev", Bn128IfftDev }, { "bn128InterpolateDev", Bn128InterpolateDev },
+        { "bn128G1MsmDev", Bn128G1MsmDev },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

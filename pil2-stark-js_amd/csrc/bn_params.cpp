@@ -1,6 +1,7 @@
 // BN254 Poseidon parameters on the host (interface and table layout: bn_params.h).
 #include "bn_params.h"
 #include "bn_consts.h"
+#include "bn_msm_recode.h"
 #include "../../include/pil2gl.h"
 #include <string.h>
 #include <algorithm>
@@ -382,6 +383,34 @@ int bn_ntt_plan(unsigned nBits, unsigned *layers) {
     const unsigned S = (nBits + BN_NTT_KMAX - 1) / BN_NTT_KMAX;
     for (unsigned i = 0; i < S; i++) layers[i] = nBits / S + (i < nBits % S ? 1 : 0);
     return (int)S;
+}
+
+// ------------------------------------------------------------------------------------------ the G1 MSM
+BnMsmPlan bn_msm_plan(uint64_t n) {
+    if (n == 0) n = 1;
+    BnMsmPlan p;
+    uint32_t lg = 0;
+    while ((n >> lg) > 1) lg++;
+    p.c = lg < bnm::MSM_MIN_C + 3 ? bnm::MSM_MIN_C : (lg - 3 > bnm::MSM_MAX_C ? bnm::MSM_MAX_C : lg - 3);
+    p.nWindows = (bnm::MSM_SCALAR_BITS + 1 + p.c - 1) / p.c;
+    p.bucketsPerWindow = 1u << (p.c - 1);
+    const uint64_t lo = 1ull << 19, hi = 1ull << 30;
+    const uint64_t room = std::min(std::max(8 * n, lo), hi) / n;         // entries / n >= 1 for n <= 2^30
+    uint32_t g = 1;
+    while (2ull * g <= room && 2 * g <= bnm::MSM_MAX_WINDOWS) g *= 2;
+    p.windowsPerPass = std::min(g, p.nWindows);
+    p.m1 = (p.bucketsPerWindow + BN_MSM_L1 - 1) / BN_MSM_L1;
+    p.m2 = (p.m1 + BN_MSM_L - 1) / BN_MSM_L;
+    auto up16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    const uint64_t nbPass = (uint64_t)p.windowsPerPass * p.bucketsPerWindow;
+    p.offHist = 0;
+    p.offCursor = up16((nbPass + 1) * 4);
+    p.offEntries = p.offCursor + up16(nbPass * 4);
+    p.offBuckets = p.offEntries + up16(n * p.windowsPerPass * 4);
+    p.offLevelA = p.offBuckets + (uint64_t)p.nWindows * p.bucketsPerWindow * 128;
+    p.offLevelB = p.offLevelA + 2ull * p.nWindows * p.m1 * 128;
+    p.scratchBytes = p.offLevelB + 2ull * p.nWindows * p.m2 * 128;
+    return p;
 }
 
 }  // namespace bnp

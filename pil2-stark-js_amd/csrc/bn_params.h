@@ -51,4 +51,22 @@ U256 bn_mont_mul(const U256 &a, const U256 &b);
 // sweeps (0 for nBits = 0), -1 for nBits > BN_NTT_MAX_BITS.  layers: room for BN_NTT_MAX_SWEEPS.
 int bn_ntt_plan(unsigned nBits, unsigned *layers);
 
+// ---- the G1 multi-scalar multiplication (bn_msm.hip) ----
+// How an MSM of n points runs (n = 0 plans as n = 1): windows of c bits (signed digits, bn_msm_recode.h), nWindows = ceil(255 / c) of them,
+// bucketsPerWindow = 2^(c-1); c = floor(log2 n) - 3 within [4, 16].  The point lists of windowsPerPass windows are built and accumulated
+// at a time: the largest power of two that keeps n * windowsPerPass list entries within clamp(8 n, 2^19, 2^30), at most nWindows.
+// The working buffer, in bytes from its start (every region 16-byte aligned):
+//   offHist     windowsPerPass * bucketsPerWindow + 1 u32: the pass's histogram, then its exclusive scan (the last entry: the total)
+//   offCursor   one u32 per bucket of the pass: where the scatter writes next
+//   offEntries  n * windowsPerPass u32: point index | sign << 31, grouped by bucket
+//   offBuckets  nWindows * bucketsPerWindow points of 128 bytes (X, Y, ZZ, ZZZ): every window's bucket sums
+//   offLevelA / offLevelB   the reduction's levels (X then Y, nWindows * m1 resp. nWindows * m2 points each), used alternately
+// scratchBytes <= 4 * clamp(8 n, 2^19, 2^30) + 96 MiB for every n <= 2^28.
+constexpr uint32_t BN_MSM_L1 = 8, BN_MSM_L = 16;     // buckets per lane in the reduction's first level / items per lane in the later ones
+struct BnMsmPlan {
+    uint32_t c, nWindows, bucketsPerWindow, windowsPerPass, m1, m2;
+    uint64_t offHist, offCursor, offEntries, offBuckets, offLevelA, offLevelB, scratchBytes;
+};
+BnMsmPlan bn_msm_plan(uint64_t n);
+
 }  // namespace bnp

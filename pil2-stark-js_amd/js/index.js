@@ -10,6 +10,7 @@ module.exports = {
     fft_p: require("./fft_p.js"),
     fft_worker: require("./fft_worker.js"),
     fft_p_bn128: require("./fft_p_bn128.js"),
+    g1_msm: require("./g1_msm.js"),
     buildMerkleHash: require("./merklehash_p.js"),
     buildPoseidon: require("./poseidon.js"),
     buildMerkleHashBN128: require("./merklehash_bn128_p.js"),

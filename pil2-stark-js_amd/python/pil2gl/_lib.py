@@ -165,6 +165,10 @@ SIGNATURES = {
     "pil2gl_bn128_interpolate_dev": (_I, [vp, _U64, _U32, vp, vp, _U32, vp]),
     "pil2gl_debug_bn128_fft_plan": (_I, [_U32, C.POINTER(_U32), _U32, C.POINTER(_U32)]),
     "pil2gl_debug_bn128_fft_tile_bytes": (_U32, []),
+    "pil2gl_bn128_g1_msm": (_I, [vp, vp, _U64, _U64, _U32, vp]),
+    "pil2gl_bn128_g1_msm_dev": (_I, [vp, vp, _U64, _U64, _U32, vp, vp]),
+    "pil2gl_debug_bn128_msm_plan": (_I, [_U64, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_debug_bn128_msm_digits": (_I, [C.POINTER(_U64), _U32, C.POINTER(C.c_int32), _U32, C.POINTER(_U32)]),
     "pil2gl_selftest_field": (_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_ext": (_I, [vp, vp, _U64, vp, vp]),
     "pil2gl_selftest_products": (_I, [vp, vp, _U64, vp, vp, vp]),

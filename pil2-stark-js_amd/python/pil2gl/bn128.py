@@ -4,6 +4,7 @@
   Transcript                      <-> src/helpers/transcript/transcript.bn128.js:1-106
   poseidon(inputs, initState, nOut) <-> circomlibjs buildPoseidon() as the reference calls it
   fft / ifft / interpolate        <-> src/helpers/fft/fft_p.bn128.js:178-285 (Montgomery words in and out)
+  g1_msm                          <-> G1.toAffine(G1.multiExpAffine(bases, scalars)) of ffjavascript, the fflonk commit
 Field elements cross this API as Python ints in normal form (the JS modules use BigInt / F.toObject)."""
 import ctypes as C
 
@@ -117,6 +118,28 @@ def interpolate(words, nPols, nBits, nBitsExt, coefs=True):
         co = np.empty((1 << nBits, nPols, 4), np.uint64) if coefs else None
         call("pil2gl_bn128_interpolate", _ptr(words), nPols, nBits, _ptr(co), _ptr(ext), nBitsExt)
     return co, ext
+
+
+def g1_msm(bases, scalars, n=None, stride=1, montgomery=True, out=None):
+    """G1.toAffine(G1.multiExpAffine(bases, scalars)): bases = n affine points of 8 uint64 words (x, y in Fq Montgomery form, infinity all
+    zero), scalars = element i at word 4*i*stride (Fr Montgomery words, or normal form with montgomery=False); numpy arrays or device
+    tensors, both of one kind.  n defaults to the number of points in bases.  -> the affine sum as 8 words of the same kind, or `out`"""
+    if _is_dev(bases) != _is_dev(scalars) or (out is not None and _is_dev(out) != _is_dev(bases)):
+        raise Pil2glError("mixing host and device buffers in one call")
+    if n is None:
+        n = int(np.prod(bases.shape)) // 8
+    if stride < 1:
+        raise Pil2glError("stride must be at least 1")
+    _check_len(bases, 8 * n, "bases")
+    _check_len(scalars, ((n - 1) * stride + 1) * 4 if n else 0, "scalars")
+    if out is None:
+        out = torch.empty(8, dtype=bases.dtype, device=bases.device) if _is_dev(bases) else np.empty(8, np.uint64)
+    _check_len(out, 8, "out")
+    if _is_dev(bases):
+        call("pil2gl_bn128_g1_msm_dev", _ptr(bases), _ptr(scalars), n, stride, 1 if montgomery else 0, _ptr(out), _stream())
+    else:
+        call("pil2gl_bn128_g1_msm", _ptr(bases), _ptr(scalars), n, stride, 1 if montgomery else 0, _ptr(out))
+    return out
 
 
 class LinearHashBN:
