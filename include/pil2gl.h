@@ -24,7 +24,7 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; land_rows with a null hostFirstBad.
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program (after staging: see there); land_rows with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
  *    The following _dev calls BLOCK until their work on the stream has finished, because they hand a result to the host or
@@ -52,6 +52,7 @@
 #pragma once
 #include <stdint.h>
 #include "pil2gl_expr.h"
+#include "pil2gl_bn_expr.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -506,6 +507,41 @@ int pil2gl_debug_bn128_msm_plan(uint64_t n, uint32_t *out, uint64_t *scratchByte
  * [-(2^(c-1) - 1), 2^(c-1)], sum_w digits[w] 2^(c w) = scalar.  c outside 4..16, a larger scalar or too little room: PIL2GL_EINVAL
  * (the count still comes back in the last case). */
 int pil2gl_debug_bn128_msm_digits(const uint64_t scalar[4], uint32_t c, int32_t *digits, uint32_t room, uint32_t *nDigits);
+
+/* ---- BN254 Fr expression evaluator: calculateExps over curve.Fr (csrc/bn_expr.hip, include/pil2gl_bn_expr.h) ----------------------
+ * The row loop the fflonk final prover runs between two commitments (src/prover/prover.js:212-219; prover_helpers.js:31-72
+ * calculateExps, :83-107 compileCode, :109-259 setRef / getRef / evalMap; fflonk_prover_worker.js:5-41): the op-list is evaluated for
+ * every row i of a domain of 2^nBits rows, an operand with row offset `prime` at row (i + prime * 2^primeShift) mod 2^nBits.  Elements
+ * are 4 little-endian u64 words, MONTGOMERY form and canonical (< r) in and out, never converted: what pil2gl_bn128_ifft leaves and
+ * what pil2gl_bn128_fft / pil2gl_bn128_g1_msm(scalarsMontgomery = 1) take.  Inputs are not validated against r.  add / sub / mul / copy
+ * on single elements; the operand classes, counted in elements, are in pil2gl_bn_expr.h.  Sections must not overlap each other.
+ * Refused with PIL2GL_EINVAL before any device call: a null program, context, op-list, section table, or the null pointer of a section
+ * or scalar pool that an op names; dim != 1; op above GLX_OP_COPY; a section, column, scalar or tmp out of range; a tmp read before it is
+ * written; a scalar as destination; more than PIL2GL_BNX_MAX_SECTIONS sections; nBits or primeShift > 28; prime * 2^primeShift beyond 32
+ * bits; a column that the program writes and also reads where any of those accesses has a non-zero row offset, or that it writes at two
+ * different offsets (the reference's serial row loop makes that order-dependent; a lane per row would make it a race).  Reading and
+ * writing one cell at offset 0 (x = x * x) is fine.  Without a device the compute entries then return PIL2GL_ENODEV.
+ * The _dev form takes device sections (16-byte aligned).  Blocking behaviour: the op-list and the scalar pool are host temporaries; they
+ * are staged with one pageable-memory copy on the caller's stream, which the runtime completes before the call returns (so it waits for
+ * earlier work on that stream), and the kernel is only ENQUEUED: the call does not wait for it, and the next call on the same stream may
+ * follow at once.  One exception, on FIRST use, as for the transforms: the working buffer (program, scalar pool, and temporaries when
+ * more than the LDS limit are live) is (re)allocated, with a device synchronise, when it has to grow.  It is one per process: two
+ * evaluations must not be in flight on different streams at once.  The host form stages the sections the program names through device
+ * copies and copies back the ones it writes. */
+int pil2gl_bn128_eval_program(const glx_program *prog, const bnx_ctx *ctx);
+int pil2gl_bn128_eval_program_dev(const glx_program *prog, const bnx_ctx *ctx, void *stream);
+/* calculateExps with debug = true over Fr (prover_helpers.js:46-70, fflonk_prover_worker.js:19-26): after a constraint's program has
+ * written its value to column `column` of a device section `width` elements wide, *hostRow = the smallest row of [first, last) whose
+ * element is not zero (all eight 32-bit words decide), hostVal[0..4) = that element (Montgomery words); UINT64_MAX and zeros if there is
+ * none.  last <= 2^28.  Blocks until the answer is on the host. */
+int pil2gl_bn128_first_nonzero_row_dev(const uint64_t *col, uint64_t width, uint64_t column, uint64_t first, uint64_t last,
+                                       uint64_t *hostRow, uint64_t *hostVal, void *stream);
+/* host-only, no device: how pil2gl_bn128_eval_program_dev would run the program, after the same checks.  outInfo[0] = temporary slots
+ * after value numbering and live-range renumbering (each distinct cell loaded once, common sub-expressions merged), [1] = ops after
+ * those passes, [2] = kernel form: 0 temporaries in LDS, 1 in the global working buffer, [3] = the LDS slot limit (form 0 up to and
+ * including it), [4] = lanes of one launch (threads * resident workgroups: a larger domain takes the grid-stride loop again),
+ * [5] = threads per workgroup. */
+int pil2gl_debug_bn128_plan_program(const glx_program *prog, const bnx_ctx *ctx, uint32_t *outInfo /* [6] */);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

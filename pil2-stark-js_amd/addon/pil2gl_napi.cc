@@ -222,6 +222,33 @@ FN(Bn128G1MsmDev) {      // (dBases, dScalars, n, scalarStride, scalarsMontgomer
     P2(env, pil2gl_bn128_g1_msm_dev(b, s, n, stride, (uint32_t)mont, o, a.stream(6))); return mk_undefined(env);
 }
 
+// ---- BN254 Fr expression evaluator (calculateExps over curve.Fr): device sections, Montgomery scalars ----
+// (opsBuf BigUint64Array = packed glx_op[], nOps, nTmp, nBits, primeShift, sectionPtrs BigUint64Array, sectionWidths BigUint64Array in elements,
+//  scalars BigUint64Array of 4 words per element[, stream])
+FN(Bn128EvalProgramDev) {
+    Args a(env, info); uint64_t nOps = a.u64(1), nTmp = a.u64(2), nBits = a.u64(3), ps = a.u64(4);
+    uint64_t nSec = 0, nSec2 = 0, nSc = 0;
+    uint64_t *ops = a.arr(0, nOps * (sizeof(glx_op) / 8)), *ptrs = a.arr(5, 0, &nSec), *widths = a.arr(6, 0, &nSec2), *scal = a.arr(7, 0, &nSc);
+    if (a.ok && nSec != nSec2) a.fail("section arrays differ in length");
+    if (a.ok && nSc % 4) a.fail("scalars must hold 4 words per element");
+    if (!a.ok) return nullptr;
+    std::vector<bnx_section> secs(nSec);
+    for (uint64_t i = 0; i < nSec; i++) { secs[i].ptr = (uint64_t *)(uintptr_t)ptrs[i]; secs[i].width = widths[i]; }
+    glx_program prog = { (uint32_t)nOps, (uint32_t)nTmp, (const glx_op *)ops };
+    bnx_ctx ctx = { (uint32_t)nBits, (uint32_t)ps, (uint32_t)nSec, (uint32_t)(nSc / 4), secs.data(), scal };
+    P2(env, pil2gl_bn128_eval_program_dev(&prog, &ctx, a.stream(8))); return mk_undefined(env);
+}
+// (devSection, width, column, first, last) -> [row, w0, w1, w2, w3] as BigInt, row = 2^64-1 when the column is zero on [first, last)
+FN(Bn128FirstNonzeroRowDev) {
+    Args a(env, info); uint64_t col = a.u64(0), width = a.u64(1), column = a.u64(2), first = a.u64(3), last = a.u64(4);
+    if (!a.ok) return nullptr;
+    uint64_t out[5] = { 0, 0, 0, 0, 0 };
+    P2(env, pil2gl_bn128_first_nonzero_row_dev((const uint64_t *)(uintptr_t)col, width, column, first, last, &out[0], &out[1], nullptr));
+    napi_value arr; NAPI_CALL(env, napi_create_array_with_length(env, 5, &arr));
+    for (uint32_t i = 0; i < 5; i++) { napi_value v; NAPI_CALL(env, napi_create_bigint_uint64(env, out[i], &v)); NAPI_CALL(env, napi_set_element(env, arr, i, v)); }
+    return arr;
+}
+
 // ---- hashing ----
 FN(Poseidon) {       // (in BigUint64Array(8*count), cap BigUint64Array(4*count)|null, count, nOut, out)
     Args a(env, info); uint64_t count = a.u64(2); uint32_t nOut = (uint32_t)a.u64(3);
@@ -567,7 +594,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128RootsFromGroupProofs", Bn128RootsFromGroupProofs }, { "bn128Convert", Bn128Convert },
         { "bn128Fft", Bn128Fft }, { "bn128Ifft", Bn128Ifft }, { "bn128Interpolate", Bn128Interpolate },
         { "bn128FftDev", Bn128FftDev }, { "bn128IfftDev", Bn128IfftDev }, { "bn128InterpolateDev", Bn128InterpolateDev },
-        { "bn128G1MsmDev", Bn128G1MsmDev },
+        { "bn128G1MsmDev", Bn128G1MsmDev }, { "bn128EvalProgramDev", Bn128EvalProgramDev }, { "bn128FirstNonzeroRowDev", Bn128FirstNonzeroRowDev },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

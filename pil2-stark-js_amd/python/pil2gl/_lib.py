@@ -36,6 +36,12 @@ class GlxCtx(C.Structure):
                 ("nScalars", C.c_uint32), ("sections", C.POINTER(GlxSection)), ("scalars", u64p)]
 
 
+class BnxCtx(C.Structure):
+    """include/pil2gl_bn_expr.h bnx_ctx; its sections are GlxSection-shaped (pointer, width in elements)"""
+    _fields_ = [("nBits", C.c_uint32), ("primeShift", C.c_uint32), ("nSections", C.c_uint32),
+                ("nScalars", C.c_uint32), ("sections", C.POINTER(GlxSection)), ("scalars", u64p)]
+
+
 class GlxProgram(C.Structure):
     _fields_ = [("nOps", C.c_uint32), ("nTmp", C.c_uint32), ("ops", C.POINTER(GlxOp))]
 
@@ -169,6 +175,10 @@ SIGNATURES = {
     "pil2gl_bn128_g1_msm_dev": (_I, [vp, vp, _U64, _U64, _U32, vp, vp]),
     "pil2gl_debug_bn128_msm_plan": (_I, [_U64, C.POINTER(_U32), C.POINTER(_U64)]),
     "pil2gl_debug_bn128_msm_digits": (_I, [C.POINTER(_U64), _U32, C.POINTER(C.c_int32), _U32, C.POINTER(_U32)]),
+    "pil2gl_bn128_eval_program": (_I, [C.POINTER(GlxProgram), C.POINTER(BnxCtx)]),
+    "pil2gl_bn128_eval_program_dev": (_I, [C.POINTER(GlxProgram), C.POINTER(BnxCtx), vp]),
+    "pil2gl_bn128_first_nonzero_row_dev": (_I, [vp, _U64, _U64, _U64, _U64, vp, vp, vp]),
+    "pil2gl_debug_bn128_plan_program": (_I, [C.POINTER(GlxProgram), C.POINTER(BnxCtx), C.POINTER(_U32)]),
     "pil2gl_selftest_field": (_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_ext": (_I, [vp, vp, _U64, vp, vp]),
     "pil2gl_selftest_products": (_I, [vp, vp, _U64, vp, vp, vp]),

@@ -5,6 +5,8 @@
   poseidon(inputs, initState, nOut) <-> circomlibjs buildPoseidon() as the reference calls it
   fft / ifft / interpolate        <-> src/helpers/fft/fft_p.bn128.js:178-285 (Montgomery words in and out)
   g1_msm                          <-> G1.toAffine(G1.multiExpAffine(bases, scalars)) of ffjavascript, the fflonk commit
+  encode_program / eval_program / first_nonzero_row
+                                  <-> src/prover/prover_helpers.js:31-259 calculateExps over ctx.F = curve.Fr (Montgomery words in and out)
 Field elements cross this API as Python ints in normal form (the JS modules use BigInt / F.toObject)."""
 import ctypes as C
 
@@ -140,6 +142,147 @@ def g1_msm(bases, scalars, n=None, stride=1, montgomery=True, out=None):
     else:
         call("pil2gl_bn128_g1_msm", _ptr(bases), _ptr(scalars), n, stride, 1 if montgomery else 0, _ptr(out))
     return out
+
+
+# ---- calculateExps over Fr: prover_helpers.js:31-72, :83-107 compileCode, :109-259 setRef / getRef / evalMap ----
+OPC = {"add": 0, "sub": 1, "mul": 2, "copy": 3}
+TMP, SEC, SCALAR = 0, 1, 2
+
+
+def encode_program(code, ctx, dom, is_global=False):
+    """The reference's `code.code` (a list of {op, dest, src[]}) as op tuples (op, dest, src0, src1) of refs (kind, dim, section, prime,
+    index), following getRef / setRef / evalMap as they run with ctx.prover === "fflonk": every element is one Fr element, so dim is 1.
+    ctx: {"pilInfo": {cmPolsMap, mapSectionsN, nConstants, boundaries}, "publics", "challenges", "subproofValues"} with the scalars as
+    Montgomery words (4 uint64 each), the form ctx.F keeps them in.  number{value} becomes F.e(value) through pil2gl_bn128_convert.
+    -> (ops, nTmp, sections, scalars): sections = [(name, width, ziIndex or None)] in the order the ops number them, name being the
+    ctx member the reference reads ("const_n", "cm1_ext", "x_n", "Zi_ext", "q_ext", ...); scalars = (nScalars, 4) uint64."""
+    info = ctx["pilInfo"]
+    sections, sec_index, words, numbers = [], {}, [], {}
+
+    def section(name, width, zi=None):
+        key = (name, zi)
+        if key not in sec_index:
+            sec_index[key] = len(sections)
+            sections.append((name, width, zi))
+        return sec_index[key]
+
+    def scalar(w):
+        w = np.asarray(w, dtype=np.uint64).reshape(4)
+        words.append(w)
+        return (SCALAR, 1, 0, 0, len(words) - 1)
+
+    def ref(r, dest):
+        t = r["type"]
+        if r.get("dim", 1) != 1:
+            raise Pil2glError("dim %s: Fr elements have dim 1" % r.get("dim"))
+        if t == "tmp":
+            return (TMP, 1, 0, 0, r["id"])
+        if t == "cm":                                           # evalMap, prover_helpers.js:220-259
+            p = info["cmPolsMap"][r["id"]]
+            st = "cm%d" % p["stage"]
+            return (SEC, 1, section(st + "_" + dom, info["mapSectionsN"][st]), r.get("prime", 0) or 0, p["stagePos"])
+        if t == "q" and dest:                                   # prover_helpers.js:115-129
+            if dom != "ext":
+                raise Pil2glError("Accessing q in domain n")
+            return (SEC, 1, section("q_ext", 1), 0, 0)
+        if dest:
+            raise Pil2glError("Invalid reference type set: " + t)
+        if t == "const":
+            return (SEC, 1, section("const_" + dom, info["nConstants"]), r.get("prime", 0) or 0, r["id"])
+        if t == "x":
+            return (SEC, 1, section("x_" + dom, 1), 0, 0)
+        if t == "Zi":                                           # prover_helpers.js:202-215
+            bs = info["boundaries"]
+            b = bs[r["boundaryId"]]
+            if b["name"] == "everyFrame":
+                zi = [k for k, o in enumerate(bs) if o["name"] == "everyFrame" and o.get("offsetMin") == b.get("offsetMin") and o.get("offsetMax") == b.get("offsetMax")]
+            elif b["name"] in ("everyRow", "firstRow", "lastRow"):
+                zi = [k for k, o in enumerate(bs) if o["name"] == b["name"]]
+            else:
+                raise Pil2glError("Invalid boundary: " + b["name"])
+            if not zi:
+                raise Pil2glError("Something went wrong")
+            return (SEC, 1, section("Zi_ext", 1, zi[0]), 0, 0)
+        if t == "number":
+            v = int(r["value"]) % R                             # F.e: a negative value is value + r
+            if v not in numbers:
+                numbers[v] = scalar(to_montgomery([v])[0])
+            return numbers[v]
+        if t == "public":
+            return scalar(ctx["publics"][r["id"]])
+        if t == "challenge":
+            return scalar(ctx["challenges"][r["stage"] - 1][r["stageId"]])
+        if t == "subproofValue":
+            return scalar(ctx["subproofValues"][r["subproofId"]][r["id"]] if is_global else ctx["subproofValues"][r["id"]])
+        raise Pil2glError("Invalid reference type get: " + t)
+
+    ops, n_tmp = [], 0
+    for c in code:
+        if c["op"] not in OPC:
+            raise Pil2glError("Invalid op:" + c["op"])
+        for r in [c["dest"]] + list(c["src"]):
+            if r["type"] == "tmp":
+                n_tmp = max(n_tmp, r["id"] + 1)
+        src = [ref(r, False) for r in c["src"]]
+        ops.append((OPC[c["op"]], ref(c["dest"], True), src[0], src[1] if c["op"] != "copy" else None))
+    return ops, n_tmp, sections, np.array(words, dtype=np.uint64).reshape(-1, 4)
+
+
+def make_context(ops, n_tmp, sections, scalars, nBits, primeShift, widths=None):
+    """-> (glx_program, bnx_ctx) for the library's entries: what eval_program builds per call, for callers that call more than once"""
+    from . import _lib
+    from .stark import make_c_program
+    prog = make_c_program(ops, n_tmp if n_tmp is not None else 1 + max([r[4] for o in ops for r in o[1:] if r is not None and r[0] == TMP], default=-1))
+    cs = (_lib.GlxSection * max(len(sections), 1))()
+    for i, b in enumerate(sections):
+        if b is not None and (len(b.shape) != 3 or b.shape[2] != 4 or b.shape[0] != 1 << nBits):
+            raise Pil2glError("section %d must have shape (2^nBits, width, 4)" % i)
+        cs[i].ptr = None if b is None else _ptr(b).value
+        cs[i].width = widths[i] if widths is not None else b.shape[1]
+    sc = np.ascontiguousarray(scalars if scalars is not None else np.zeros((0, 4)), dtype=np.uint64).reshape(-1, 4)
+    ctx = _lib.BnxCtx(nBits, primeShift, len(sections), sc.shape[0], cs, sc.ctypes.data_as(_lib.u64p) if sc.size else None)
+    ctx._keep = (cs, sc)
+    return prog, ctx
+
+
+def eval_program(code, sections, scalars, nBits, primeShift=0, nTmp=None):
+    """calculateExps(ctx, code, dom) over Fr for every row of a domain of 2^nBits rows (primeShift = 0 on "n", nBitsExt - nBits on "ext").
+    code = op tuples as encode_program returns them; sections = one buffer per section index, each (2^nBits, width, 4) uint64 Montgomery
+    words, all numpy arrays or all device tensors (then the kernel is enqueued on the current stream); scalars = (nScalars, 4) uint64
+    Montgomery words, always a numpy array.  Destination sections are written in place."""
+    live = [b for b in sections if b is not None]
+    dev = bool(live) and _is_dev(live[0])
+    if any(_is_dev(b) != dev for b in live):
+        raise Pil2glError("mixing host and device buffers in one call")
+    prog, ctx = make_context(code, nTmp, sections, scalars, nBits, primeShift)
+    if dev:
+        call("pil2gl_bn128_eval_program_dev", C.byref(prog), C.byref(ctx), _stream())
+    else:
+        call("pil2gl_bn128_eval_program", C.byref(prog), C.byref(ctx))
+
+
+def plan_program(code, widths, scalars, nBits, primeShift=0, nTmp=None):
+    """pil2gl_debug_bn128_plan_program (no device): how eval_program would run `code` on sections of these widths ->
+    {slots, ops, form (0 LDS / 1 global), ldsSlotLimit, lanesPerLaunch, threads}"""
+    fake = np.zeros(4, np.uint64)                               # a non-null pointer that is never read
+    prog, ctx = make_context(code, nTmp, [None] * len(widths), scalars, nBits, primeShift, widths)
+    for i in range(len(widths)):
+        ctx.sections[i].ptr = fake.ctypes.data
+    info = (C.c_uint32 * 6)()
+    call("pil2gl_debug_bn128_plan_program", C.byref(prog), C.byref(ctx), info)
+    return dict(zip(("slots", "ops", "form", "ldsSlotLimit", "lanesPerLaunch", "threads"), (int(v) for v in info)))
+
+
+def first_nonzero_row(section, column, first, last):
+    """calculateExps with debug = true (prover_helpers.js:46-70): section = a device tensor (rows, width, 4) whose column `column` holds a
+    constraint's values -> (row, value words) of the smallest row of [first, last) that is not zero, or None"""
+    if not _is_dev(section) or len(section.shape) != 3 or section.shape[2] != 4:
+        raise Pil2glError("section must be a device tensor of shape (rows, width, 4)")
+    if not 0 <= first <= last <= section.shape[0] or not 0 <= column < section.shape[1]:
+        raise Pil2glError("column %d, rows [%d, %d) of a section of %d rows x %d columns" % (column, first, last, section.shape[0], section.shape[1]))
+    row = C.c_uint64(); val = np.zeros(4, np.uint64)
+    call("pil2gl_bn128_first_nonzero_row_dev", _ptr(section), section.shape[1], column, first, last, C.byref(row), _ptr(val), _stream())
+    return None if row.value == 0xFFFFFFFFFFFFFFFF else (int(row.value), val)
 
 
 class LinearHashBN:
