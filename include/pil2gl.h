@@ -24,7 +24,7 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program (after staging: see there); land_rows with a null hostFirstBad.
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); land_rows with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
  *    The following _dev calls BLOCK until their work on the stream has finished, because they hand a result to the host or
@@ -542,6 +542,41 @@ int pil2gl_bn128_first_nonzero_row_dev(const uint64_t *col, uint64_t width, uint
  * including it), [4] = lanes of one launch (threads * resident workgroups: a larger domain takes the grid-stride loop again),
  * [5] = threads per workgroup. */
 int pil2gl_debug_bn128_plan_program(const glx_program *prog, const bnx_ctx *ctx, uint32_t *outInfo /* [6] */);
+
+/* ---- BN254 Fr polynomial division by x^k - beta and evaluation (csrc/bn_poly.hip) ---------------------------------------------------
+ * The long-vector field work of the fflonk prover's last two steps: Q.divZh(N, 2^extendBits) of computeQFflonk
+ * (fflonk_prover_helpers.js:147-148) and, in computeOpeningsFflonk's shplonkjs open (:212), the divisions by x^k - h^k and x - y and the
+ * evaluations of the committed polynomials at their opening points.  For a coefficient vector c[0..n), k >= 1 and a field element beta,
+ *     d[i] = c[i] + beta * d[i + k]     (d[j] = 0 for j >= n),   i.e.  d[i] = sum_{t >= 0} beta^t c[i + t k]:
+ * d[k..n) is the quotient of c by x^k - beta, quotient coefficient m at position m + k, and d[0..k) is the remainder.  k = N, beta = 1 is
+ * divZh: for a divisible polynomial the quotient, found from position N on, is the one the reference computes from the low end.  There is
+ * no "not divisible" entry: the caller runs pil2gl_bn128_first_nonzero_row_dev(dst, stride, 0, 0, k) on the remainder positions (the
+ * reference throws "Polynomial is not divisible").  k = 1, beta = z is division by x - z with d[0] = p(z); poly_eval computes only that,
+ * out[p] = sum_i c[i] points[p]^i for nPoints points, and reads src only.
+ *   Addressing  element i is the 4 words at word 4 * i * stride, for src and dst alike: a column of a row-major matrix is processed where
+ *               it lies (as g1_msm's scalarStride), and the words between a strided destination's elements are left as they are.
+ *   Aliasing    dst == src is allowed (position i depends on c[i] and on positions above it); any other overlap is not.
+ *   beta, points  HOST pointers, 4 words per element, MONTGOMERY form and canonical (a challenge comes from the host transcript).
+ *               Coefficients are Montgomery words, canonical in and out, never converted: what pil2gl_bn128_ifft leaves.
+ *   Limits      0 <= n <= 2^28, 1 <= stride < 2^32, 1 <= k <= 2^28, 1 <= nPoints <= 64; anything else, and a null buffer (src / dst only
+ *               with n > 0), is PIL2GL_EINVAL before any device call.  k >= n copies; n = 0 writes nothing, and poly_eval gives zeros.
+ *               Without a device the compute entries return PIL2GL_ENODEV (the host forms with n = 0 need none).
+ * The _dev forms take device pointers (16-byte aligned; out: nPoints elements on the device) and only ENQUEUE on the caller's stream,
+ * after staging the levels' multipliers (powers of beta computed on the host, at most 16 KiB) with one pageable-memory copy on that
+ * stream, which the runtime completes before the call returns.  One exception, on FIRST use, as for every BN254 block above: the working
+ * buffer (pil2gl_debug_bn128_poly_plan's scratchBytes; poly_eval: 16 KiB + nPoints times the rest) is (re)allocated, with a device
+ * synchronise, when it has to grow; it is one per process, so two of these calls must not be in flight on different streams at once.
+ * The host forms stage src up to its last element, and a strided dst that is not src, through device copies. */
+int pil2gl_bn128_poly_div_xk_sub(const uint64_t *src, uint64_t n, uint64_t stride, uint64_t k, const uint64_t hostBeta[4], uint64_t *dst);
+int pil2gl_bn128_poly_div_xk_sub_dev(const uint64_t *src, uint64_t n, uint64_t stride, uint64_t k, const uint64_t hostBeta[4], uint64_t *dst, void *stream);
+int pil2gl_bn128_poly_eval(const uint64_t *src, uint64_t n, uint64_t stride, const uint64_t *hostPoints, uint32_t nPoints, uint64_t *out);
+int pil2gl_bn128_poly_eval_dev(const uint64_t *src, uint64_t n, uint64_t stride, const uint64_t *hostPoints, uint32_t nPoints, uint64_t *out, void *stream);
+/* host-only, no device: how poly_div_xk_sub runs (n, k); poly_eval runs as (n, 1).  The k chains of M = ceil(n / k) links are cut into
+ * segments, a lane each.  outInfo[0] = L, links per segment; [1] = S, segments per chain (L * S * k >= n); [2] = carry levels, the times
+ * the same recurrence is applied to the segment values (0 when S = 1); [3] = threads per workgroup; [4] = the form: 0 a lane per chain
+ * (M <= 32, or k >= 2^17 lanes), 1 segmented.  *scratchBytes = the working buffer: 16 KiB of multipliers, and the segment values of all
+ * levels, below 9 MiB (none in form 0).  The carry-level count stops growing at n = 2^22.  n or k out of range: PIL2GL_EINVAL. */
+int pil2gl_debug_bn128_poly_plan(uint64_t n, uint64_t k, uint32_t *outInfo /* [5] */, uint64_t *scratchBytes);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

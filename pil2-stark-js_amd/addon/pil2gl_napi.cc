@@ -249,8 +249,21 @@ FN(Bn128FirstNonzeroRowDev) {
     return arr;
 }
 
+// ---- BN254 Fr polynomial division by x^k - beta and evaluation: device coefficients, beta / points as host Montgomery words ----
+FN(Bn128PolyDivDev) {    // (dSrc, n, stride, k, beta BigUint64Array(4), dDst[, stream])
+    Args a(env, info); uint64_t *s = DP(0); uint64_t n = a.u64(1), stride = a.u64(2), k = a.u64(3); uint64_t *beta = a.arr(4, 4); uint64_t *d = DP(5);
+    if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_poly_div_xk_sub_dev(s, n, stride, k, beta, d, a.stream(6))); return mk_undefined(env);
+}
+FN(Bn128PolyEvalDev) {   // (dSrc, n, stride, points BigUint64Array(4 * nPoints), dOut[, stream])
+    Args a(env, info); uint64_t *s = DP(0); uint64_t n = a.u64(1), stride = a.u64(2), len = 0; uint64_t *pts = a.arr(3, 4, &len); uint64_t *o = DP(4);
+    if (a.ok && (len % 4 || len / 4 > 64)) a.fail("points must hold 4 words per point, at most 64 points");
+    if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_poly_eval_dev(s, n, stride, pts, (uint32_t)(len / 4), o, a.stream(5))); return mk_undefined(env);
+}
+
 // ---- hashing ----
-FN(Poseidon) {       // (in BigUint64Array(8*count), cap BigUint64Array(4*count)|null, count, nOut, out)
+FN(Poseidon) {      // (in BigUint64Array(8*count), cap BigUint64Array(4*count)|null, count, nOut, out)
     Args a(env, info); uint64_t count = a.u64(2); uint32_t nOut = (uint32_t)a.u64(3);
     uint64_t *in = a.arr(0, 8 * count), *cap = a.is_nullish(1) ? nullptr : a.arr(1, 4 * count), *out = a.arr(4, (uint64_t)nOut * count); if (!a.ok) return nullptr;
     P2(env, pil2gl_poseidon(in, cap, count, nOut, out)); return mk_undefined(env);
@@ -595,6 +608,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128Fft", Bn128Fft }, { "bn128Ifft", Bn128Ifft }, { "bn128Interpolate", Bn128Interpolate },
         { "bn128FftDev", Bn128FftDev }, { "bn128IfftDev", Bn128IfftDev }, { "bn128InterpolateDev", Bn128InterpolateDev },
         { "bn128G1MsmDev", Bn128G1MsmDev }, { "bn128EvalProgramDev", Bn128EvalProgramDev }, { "bn128FirstNonzeroRowDev", Bn128FirstNonzeroRowDev },
+        { "bn128PolyDivDev", Bn128PolyDivDev }, { "bn128PolyEvalDev", Bn128PolyEvalDev },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

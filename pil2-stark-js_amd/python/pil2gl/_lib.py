@@ -179,7 +179,12 @@ SIGNATURES = {
     "pil2gl_bn128_eval_program_dev": (_I, [C.POINTER(GlxProgram), C.POINTER(BnxCtx), vp]),
     "pil2gl_bn128_first_nonzero_row_dev": (_I, [vp, _U64, _U64, _U64, _U64, vp, vp, vp]),
     "pil2gl_debug_bn128_plan_program": (_I, [C.POINTER(GlxProgram), C.POINTER(BnxCtx), C.POINTER(_U32)]),
-    "pil2gl_selftest_field": (_I, [vp, vp, _U64, vp, vp, vp]),
+    "pil2gl_bn128_poly_div_xk_sub": (_I, [vp, _U64, _U64, _U64, vp, vp]),
+    "pil2gl_bn128_poly_div_xk_sub_dev": (_I, [vp, _U64, _U64, _U64, vp, vp, vp]),
+    "pil2gl_bn128_poly_eval": (_I, [vp, _U64, _U64, vp, _U32, vp]),
+    "pil2gl_bn128_poly_eval_dev": (_I, [vp, _U64, _U64, vp, _U32, vp, vp]),
+    "pil2gl_debug_bn128_poly_plan": (_I, [_U64, _U64, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_selftest_field":(_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_ext": (_I, [vp, vp, _U64, vp, vp]),
     "pil2gl_selftest_products": (_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_mds": (_I, [vp, _U64, _U32, _I, vp]),

@@ -7,6 +7,7 @@
   g1_msm                          <-> G1.toAffine(G1.multiExpAffine(bases, scalars)) of ffjavascript, the fflonk commit
   encode_program / eval_program / first_nonzero_row
                                   <-> src/prover/prover_helpers.js:31-259 calculateExps over ctx.F = curve.Fr (Montgomery words in and out)
+  poly_div / poly_eval / poly_plan <-> Polynomial.divZh / divByXNSubValue / evaluate as fflonk_prover_helpers.js:147-148, :212 use them
 Field elements cross this API as Python ints in normal form (the JS modules use BigInt / F.toObject)."""
 import ctypes as C
 
@@ -283,6 +284,70 @@ def first_nonzero_row(section, column, first, last):
     row = C.c_uint64(); val = np.zeros(4, np.uint64)
     call("pil2gl_bn128_first_nonzero_row_dev", _ptr(section), section.shape[1], column, first, last, C.byref(row), _ptr(val), _stream())
     return None if row.value == 0xFFFFFFFFFFFFFFFF else (int(row.value), val)
+
+
+# ---- division by x^k - beta and evaluation: Q.divZh of computeQFflonk, the long-vector work of shplonkjs open ----
+def _host_elems(a, what, most=None):
+    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+    if a.shape[0] < 1 or (most is not None and a.shape[0] > most):
+        raise Pil2glError("%s: %d elements" % (what, a.shape[0]))
+    return a
+
+
+def poly_div(words, k, beta, n=None, stride=1, out=None):
+    """d[i] = c[i] + beta d[i + k] over the coefficients `words` (element i at word 4*i*stride, Montgomery words; a numpy array or a
+    device tensor): d[k..n) is the quotient by x^k - beta (coefficient m at m + k), d[0..k) the remainder.  beta = 4 Montgomery words
+    on the host.  n defaults to the elements `words` holds at this stride.  -> a new buffer of the same kind and shape, or `out` (which
+    may be `words`; with stride > 1 the words between its elements stay as they are, so give one)"""
+    if out is not None and _is_dev(out) != _is_dev(words):
+        raise Pil2glError("mixing host and device buffers in one call")
+    if stride < 1:
+        raise Pil2glError("stride must be at least 1")
+    total = int(np.prod(words.shape))
+    if n is None:
+        n = (total // 4 + stride - 1) // stride
+    need = ((n - 1) * stride + 1) * 4 if n else 0
+    _check_len(words, need, "words")
+    if out is None:
+        if stride != 1:
+            raise Pil2glError("a strided division writes into a matrix: pass out")
+        out = torch.empty_like(words) if _is_dev(words) else np.empty_like(words)
+    _check_len(out, need, "out")
+    b = _host_elems(beta, "beta", 1)
+    if _is_dev(words):
+        call("pil2gl_bn128_poly_div_xk_sub_dev", _ptr(words), n, stride, k, _ptr(b), _ptr(out), _stream())
+    else:
+        call("pil2gl_bn128_poly_div_xk_sub", _ptr(words), n, stride, k, _ptr(b), _ptr(out))
+    return out
+
+
+def poly_eval(words, points, n=None, stride=1):
+    """sum_i c[i] z^i for every z of `points` ((P, 4) Montgomery words on the host, 1 <= P <= 64) over the coefficients `words` (as
+    poly_div takes them; never written) -> (P, 4) Montgomery words of the same kind as `words`"""
+    if stride < 1:
+        raise Pil2glError("stride must be at least 1")
+    total = int(np.prod(words.shape))
+    if n is None:
+        n = (total // 4 + stride - 1) // stride
+    _check_len(words, ((n - 1) * stride + 1) * 4 if n else 0, "words")
+    z = _host_elems(points, "points", 64)
+    if _is_dev(words):
+        out = torch.empty((z.shape[0], 4), dtype=words.dtype, device=words.device)
+        call("pil2gl_bn128_poly_eval_dev", _ptr(words), n, stride, _ptr(z), z.shape[0], _ptr(out), _stream())
+    else:
+        out = np.empty((z.shape[0], 4), np.uint64)
+        call("pil2gl_bn128_poly_eval", _ptr(words), n, stride, _ptr(z), z.shape[0], _ptr(out))
+    return out
+
+
+def poly_plan(n, k):
+    """pil2gl_debug_bn128_poly_plan (no device): how poly_div runs (n, k), and poly_eval (n, 1) ->
+    {L, S, levels, threads, form (0 a lane per chain / 1 segmented), scratchBytes}"""
+    info = (C.c_uint32 * 5)(); nbytes = C.c_uint64()
+    call("pil2gl_debug_bn128_poly_plan", n, k, info, C.byref(nbytes))
+    d = dict(zip(("L", "S", "levels", "threads", "form"), (int(v) for v in info)))
+    d["scratchBytes"] = int(nbytes.value)
+    return d
 
 
 class LinearHashBN:
