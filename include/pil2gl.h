@@ -24,7 +24,7 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); land_rows with a null hostFirstBad.
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod and bn128_gsum; land_rows with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
  *    The following _dev calls BLOCK until their work on the stream has finished, because they hand a result to the host or
@@ -577,6 +577,50 @@ int pil2gl_bn128_poly_eval_dev(const uint64_t *src, uint64_t n, uint64_t stride,
  * (M <= 32, or k >= 2^17 lanes), 1 segmented.  *scratchBytes = the working buffer: 16 KiB of multipliers, and the segment values of all
  * levels, below 9 MiB (none in form 0).  The carry-level count stops growing at n = 2^22.  n or k out of range: PIL2GL_EINVAL. */
 int pil2gl_debug_bn128_poly_plan(uint64_t n, uint64_t k, uint32_t *outInfo /* [5] */, uint64_t *scratchBytes);
+
+/* ---- BN254 Fr grand product, grand sum and batch inverse: the gprod / gsum hints over curve.Fr (csrc/bn_scan.hip) -----------------
+ * What resolves the hints of a fflonk stage with a permutation, connection or lookup argument (src/prover/hints_helpers.js:92-113):
+ * calculateZ and calculateS of src/helpers/polutils.js:132-164 with F = curve.Fr, each one F.batchInverse and a serial walk of n products.
+ *     batch_inverse   dst[i] = src[i]^-1
+ *     gprod           out[0] = 1 (Montgomery form), out[i] = out[i-1] * num[i-1] / den[i-1]          (calculateZ)
+ *     gsum            out[i] = out[i-1] + num / den[i], out[0] = num / den[0]; num is ONE element      (calculateS)
+ * The `result` field of a hint is out[n-1]: the caller copies those 32 bytes, there is no entry for it.
+ *   Addressing  element i of a column is the 4 words at word 4 * i * stride, each column with a stride of its own: a column of a row-major
+ *               section is read and written where it lies, and the words between a strided destination's elements are left as they are.
+ *               Montgomery words, canonical in and out, never converted; inputs are not validated against r.
+ *   Zeros       A stated choice: the reference's Fr is ffjavascript's wasm field, which the reference tree does not carry, so what its
+ *               batchInverse makes of a zero cannot be pinned.  The convention of the Goldilocks hints above and of the MSM's Fq inversion
+ *               holds: a zero inverts to ZERO and is kept out of every running product (it spoils no other row).  In gprod a zero
+ *               denominator makes that row's ratio 0, so every later row is 0; in gsum the row adds 0.  A zero numerator is plain arithmetic.
+ *   Aliasing    A column is (pointer, stride).  batch_inverse may run in place: dst the SAME column as src.  Otherwise an output must share
+ *               no element with an input: columns whose byte ranges are apart, or columns of equal stride whose pointers differ by a
+ *               multiple of 32 bytes that is no multiple of 32 * stride bytes (two columns of one section: the ranges interleave, no
+ *               element is shared).  Ranges that meet in any other way -- different strides included -- are PIL2GL_EINVAL, a host check.
+ *   hostNum     gsum's numerator: a HOST pointer to 4 Montgomery words in both forms.
+ *   Limits      0 <= n <= 2^28, 1 <= stride < 2^32; anything else, and a null buffer with n > 0 (hostNum: always), is PIL2GL_EINVAL
+ *               before any device call.  n = 0 is PIL2GL_OK, touches nothing and needs no device.  Without a device the entries return
+ *               PIL2GL_ENODEV.
+ * The _dev forms take device pointers (16-byte aligned) and only ENQUEUE on the caller's stream; nothing is staged.  One exception, on
+ * FIRST use, as for every BN254 block above: the working buffer (pil2gl_debug_bn128_scan_plan's scratchBytes) is (re)allocated, with a
+ * device synchronise, when it has to grow; it is one per process, so two of these calls must not be in flight on different streams at
+ * once.  The host forms stage every column up to its last element (a strided destination too) through device copies. */
+int pil2gl_bn128_batch_inverse(const uint64_t *src, uint64_t srcStride, uint64_t n, uint64_t *dst, uint64_t dstStride);
+int pil2gl_bn128_batch_inverse_dev(const uint64_t *src, uint64_t srcStride, uint64_t n, uint64_t *dst, uint64_t dstStride, void *stream);
+int pil2gl_bn128_gprod(const uint64_t *num, uint64_t numStride, const uint64_t *den, uint64_t denStride, uint64_t n,
+                       uint64_t *out, uint64_t outStride);
+int pil2gl_bn128_gprod_dev(const uint64_t *num, uint64_t numStride, const uint64_t *den, uint64_t denStride, uint64_t n,
+                           uint64_t *out, uint64_t outStride, void *stream);
+int pil2gl_bn128_gsum(const uint64_t hostNum[4], const uint64_t *den, uint64_t denStride, uint64_t n, uint64_t *out, uint64_t outStride);
+int pil2gl_bn128_gsum_dev(const uint64_t hostNum[4], const uint64_t *den, uint64_t denStride, uint64_t n,
+                          uint64_t *out, uint64_t outStride, void *stream);
+/* host-only, no device: how the three run on n rows.  op: 0 batch_inverse, 1 gprod, 2 gsum, 3 batch_inverse in place.  The rows are cut
+ * into segments, a lane each; the segment totals are the same problem one level up, until a level has at most 64 items, which one lane
+ * finishes (the inversion's single Fermat ladder is there).  outInfo[0] = L, rows per segment; [1] = S, segments (L * S >= n,
+ * (S - 1) * L < n); [2] = levels (1 for n <= 64; first 2, 3, 4, 5 at n = 65, 1025, 16385, 262145; never more); [3] = threads per
+ * workgroup; [4] = segments per workgroup (a workgroup's share is L times this many rows).  *scratchBytes = the working buffer: the levels
+ * above the first, below 9 MiB, and 32 * n more for op 3 only (an inversion in place has nowhere else to keep its prefix products); 0 for
+ * n = 0.  n > 2^28 or op > 3: PIL2GL_EINVAL. */
+int pil2gl_debug_bn128_scan_plan(uint64_t n, uint32_t op, uint32_t *outInfo /* [5] */, uint64_t *scratchBytes);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

@@ -262,6 +262,23 @@ FN(Bn128PolyEvalDev) {   // (dSrc, n, stride, points BigUint64Array(4 * nPoints)
     P2(env, pil2gl_bn128_poly_eval_dev(s, n, stride, pts, (uint32_t)(len / 4), o, a.stream(5))); return mk_undefined(env);
 }
 
+// ---- BN254 Fr batch inverse, grand product and grand sum (the gprod / gsum hints over curve.Fr): device columns, each with its stride ----
+FN(Bn128BatchInverseDev) {   // (dSrc, srcStride, n, dDst, dstStride[, stream])
+    Args a(env, info); uint64_t *s = DP(0); uint64_t ss = a.u64(1), n = a.u64(2); uint64_t *d = DP(3); uint64_t ds = a.u64(4);
+    if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_batch_inverse_dev(s, ss, n, d, ds, a.stream(5))); return mk_undefined(env);
+}
+FN(Bn128GprodDev) {          // (dNum, numStride, dDen, denStride, n, dOut, outStride[, stream])
+    Args a(env, info); uint64_t *nu = DP(0); uint64_t ns = a.u64(1); uint64_t *de = DP(2); uint64_t ds = a.u64(3), n = a.u64(4); uint64_t *o = DP(5); uint64_t os = a.u64(6);
+    if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_gprod_dev(nu, ns, de, ds, n, o, os, a.stream(7))); return mk_undefined(env);
+}
+FN(Bn128GsumDev) {           // (num BigUint64Array(4), dDen, denStride, n, dOut, outStride[, stream])
+    Args a(env, info); uint64_t *nu = a.arr(0, 4); uint64_t *de = DP(1); uint64_t ds = a.u64(2), n = a.u64(3); uint64_t *o = DP(4); uint64_t os = a.u64(5);
+    if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_gsum_dev(nu, de, ds, n, o, os, a.stream(6))); return mk_undefined(env);
+}
+
 // ---- hashing ----
 FN(Poseidon) {      // (in BigUint64Array(8*count), cap BigUint64Array(4*count)|null, count, nOut, out)
     Args a(env, info); uint64_t count = a.u64(2); uint32_t nOut = (uint32_t)a.u64(3);
@@ -609,6 +626,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128FftDev", Bn128FftDev }, { "bn128IfftDev", Bn128IfftDev }, { "bn128InterpolateDev", Bn128InterpolateDev },
         { "bn128G1MsmDev", Bn128G1MsmDev }, { "bn128EvalProgramDev", Bn128EvalProgramDev }, { "bn128FirstNonzeroRowDev", Bn128FirstNonzeroRowDev },
         { "bn128PolyDivDev", Bn128PolyDivDev }, { "bn128PolyEvalDev", Bn128PolyEvalDev },
+        { "bn128BatchInverseDev", Bn128BatchInverseDev }, { "bn128GprodDev", Bn128GprodDev }, { "bn128GsumDev", Bn128GsumDev },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

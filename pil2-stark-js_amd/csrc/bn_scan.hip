@@ -1,0 +1,395 @@
+// Grand product, grand sum and batch inverse over the BN254 scalar field Fr, gfx950: what resolves the gprod / gsum hints of a fflonk
+// stage with a permutation, connection or lookup argument (src/prover/hints_helpers.js:92-113; calculateZ / calculateS of
+// src/helpers/polutils.js:132-164 with F = curve.Fr, one F.batchInverse and a serial walk of N products each).
+//
+//     batch_inverse   dst[i] = src[i]^-1
+//     gprod           z[0] = 1,  z[i] = z[i - 1] num[i - 1] / den[i - 1]
+//     gsum            s[i] = s[i - 1] + num / den[i],  s[0] = num / den[0]          (num: ONE element, on the host)
+//
+// Elements are 32 bytes of Montgomery words, canonical in and out, moved as two 16-byte halves; element i of a column lies at word
+// 4 i stride, so a column of a row-major section is worked on where it is (as poly_div and g1_msm take theirs).
+//
+// ZERO DENOMINATORS -- a stated choice.  The reference's Fr is ffjavascript's wasm field, which the reference tree does not vendor, so
+// what its batchInverse makes of a zero cannot be pinned from here.  This library's own convention is used (include/pil2gl.h on the
+// Goldilocks hints, fq_inv of bn_fq.cuh: 0 -> 0): a zero inverts to zero and is kept out of every running product, so it spoils no other
+// row's inverse.  In gprod the ratio of that row is then 0 and every later row is 0; in gsum the row adds 0.  A zero NUMERATOR is plain
+// arithmetic.
+//
+// Arithmetic.  One Fermat inversion is about 380 products of 328 vector instructions each (DESIGN.md section 14's count), so there is one
+// per call, on one lane, and everything else is Montgomery's trick spread over lanes.  bnscan::plan (bn_scan_plan.h) cuts the n items
+// into S segments of L, a lane per segment [s L, min((s + 1) L, n)):
+//   inversion   reduce: a lane leaves the product of its segment (zeros left out).  Those S products are the same problem one level up,
+//               inverted in place; the last level is one lane, which inverts its total with the ladder.  store: a lane walks its segment
+//               upwards writing the prefix products q[i], takes r = 1 / (its segment's product) from the level above, and walks back down:
+//               y[i] = r q[i - 1] (times the numerator for the two hints), r = r x[i].  1 + 3 products per row, + 1 with a numerator.
+//               The prefixes are kept in the destination itself (read back before each element is overwritten); an inversion in place has
+//               no such room and keeps them in the working buffer (n elements more).
+//   scan        the hints then run a prefix scan over the ratios, in place in the destination: reduce, the totals scanned one level up
+//               (inclusive), store seeded with the total before the segment.  gprod: an exclusive running product, 2 products per row;
+//               gsum: an inclusive running sum, additions only.
+// Products per row, the levels above the first adding 1/15 at most: batch_inverse 4, gsum 5, gprod 7.  A level boundary is a kernel
+// boundary; no workgroup waits for another.  The alternative of DESIGN.md section 15 (prefix and suffix products, 5 per row for gprod)
+// was not taken: it needs a second strided temporary where this needs none.
+//
+// Memory safety does not rest on n being a multiple of anything: a lane with s >= S returns, a lane walks only [s L, min((s + 1) L, n)),
+// and an empty segment leaves the identity.
+#include "common.h"
+#include "bn_field.cuh"
+#include "bn_params.h"
+#include "bn_scan_plan.h"
+
+using namespace pil2gl;
+using bn::u32;
+
+namespace {
+
+struct Elem { u32 w[8]; };
+
+enum Mode : u32 { MODE_NONE = 0, MODE_COLUMN = 1, MODE_CONST = 2 };      // what the inverses are multiplied by
+
+struct InvArgs {
+    const uint4 *x; u64 xs;                          // element i of the level at x + 2 i xs (16-byte halves)
+    uint4 *y; u64 ys;                                // its inverse (may be x)
+    uint4 *q; u64 qs;                                // the prefix products (may be y, never x)
+    const uint4 *num; u64 ns;                        // MODE_COLUMN: the numerators
+    const uint4 *vinv;                               // store: the inverses of the segment products (dense), unless this is the last level
+    uint4 *v;                                        // reduce: the segment products (dense)
+    u64 n, S; u32 L, mode;
+    Elem one, mul;                                   // 1 in Montgomery form; MODE_CONST: the numerator
+};
+struct ScanArgs {
+    uint4 *y; u64 ys;                                // scanned in place
+    const uint4 *carry;                              // store: the inclusive scan of the segment totals (dense), or null when S = 1
+    uint4 *v;                                        // reduce: the segment totals (dense)
+    u64 n, S; u32 L, exclusive;
+    Elem ident;                                      // 0, or 1 in Montgomery form
+};
+
+__device__ __forceinline__ void ld_elem(const uint4 *p, u32 x[8]) {
+    const uint4 a = p[0], b = p[1];
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+}
+__device__ __forceinline__ void st_elem(uint4 *p, const u32 x[8]) {
+    p[0] = make_uint4(x[0], x[1], x[2], x[3]); p[1] = make_uint4(x[4], x[5], x[6], x[7]);
+}
+__device__ __forceinline__ bool is_zero(const u32 x[8]) { return (x[0] | x[1] | x[2] | x[3] | x[4] | x[5] | x[6] | x[7]) == 0; }
+__device__ __forceinline__ void set(u32 x[8], const Elem &e) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) x[i] = e.w[i];
+}
+
+// a^-1 = a^(r - 2), Montgomery in and out, a != 0: 252 squarings and a product per set bit below the top one (bit 253), the exponent's
+// bits taken from r's constant limbs (r ends in ...f0000001: subtracting 2 borrows from no other limb).  One lane, once per call.
+__device__ __noinline__ void fr_inv(u32 out[8], const u32 a[8]) {
+    u32 acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) acc[i] = a[i];
+    for (int bit = 252; bit >= 0; bit--) {
+        bn::fr_mul(acc, acc, acc);
+        u32 w = 0;
+#pragma unroll
+        for (int l = 0; l < 8; l++) if ((bit >> 5) == l) w = bn::r_limb(l) - (l == 0 ? 2u : 0u);
+        if ((w >> (bit & 31)) & 1) bn::fr_mul(acc, acc, a);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) out[i] = acc[i];
+}
+
+// the segment [b, e) of lane t; false for a lane without one
+__device__ __forceinline__ bool segment(u64 n, u64 S, u32 L, u64 &t, u64 &b, u64 &e) {
+    t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= S) return false;
+    b = t * L;
+    e = b + L < n ? b + L : n;
+    return true;
+}
+
+__global__ void __launch_bounds__(bnscan::THREADS) bn_inv_reduce_kernel(InvArgs a) {
+    u64 t, b, e;
+    if (!segment(a.n, a.S, a.L, t, b, e)) return;
+    u32 acc[8], x[8];
+    set(acc, a.one);
+    const size_t step = 2 * (size_t)a.xs;
+    const uint4 *px = a.x + b * step;
+    for (u64 i = b; i < e; i++, px += step) {
+        ld_elem(px, x);
+        if (!is_zero(x)) bn::fr_mul(acc, acc, x);
+    }
+    st_elem(a.v + 2 * t, acc);
+}
+
+template <bool TOP>
+__global__ void __launch_bounds__(bnscan::THREADS) bn_inv_store_kernel(InvArgs a) {
+    u64 t, b, e;
+    if (!segment(a.n, a.S, a.L, t, b, e) || b >= e) return;
+    u32 r[8], x[8], p[8];
+    set(r, a.one);
+    const size_t xstep = 2 * (size_t)a.xs, qstep = 2 * (size_t)a.qs, ystep = 2 * (size_t)a.ys, nstep = 2 * (size_t)a.ns;
+    const uint4 *px = a.x + b * xstep;
+    uint4 *pq = a.q + b * qstep;
+    for (u64 i = b; i < e; i++, px += xstep, pq += qstep) {       // up: q[i] = the product of the segment's non-zero elements up to i
+        ld_elem(px, x);
+        if (!is_zero(x)) bn::fr_mul(r, r, x);
+        st_elem(pq, r);
+    }
+    if (TOP) fr_inv(r, r);                                        // a product of non-zero elements: never zero
+    else ld_elem(a.vinv + 2 * t, r);
+    uint4 *py = a.y + e * ystep;
+    const uint4 *pn = a.num + e * nstep;
+    for (u64 i = e; i-- > b;) {                                   // down: r = 1 / q[i]
+        px -= xstep; pq -= qstep; py -= ystep; pn -= nstep;
+        ld_elem(px, x);                                           // before y[i] is stored: y may be x
+        if (i > b) ld_elem(pq - qstep, p); else set(p, a.one);    // q[i - 1] is below everything stored so far: q may be y
+        if (is_zero(x)) {
+#pragma unroll
+            for (int l = 0; l < 8; l++) p[l] = 0;
+        } else {
+            bn::fr_mul(p, p, r);
+            bn::fr_mul(r, r, x);
+            if (a.mode == MODE_COLUMN) { ld_elem(pn, x); bn::fr_mul(p, p, x); }
+            else if (a.mode == MODE_CONST) { set(x, a.mul); bn::fr_mul(p, p, x); }
+        }
+        st_elem(py, p);
+    }
+}
+
+template <bool ADD>
+__device__ __forceinline__ void combine(u32 acc[8], const u32 x[8]) {
+    if (ADD) bn::fr_add(acc, x); else bn::fr_mul(acc, acc, x);
+}
+
+template <bool ADD>
+__global__ void __launch_bounds__(bnscan::THREADS) bn_scan_reduce_kernel(ScanArgs a) {
+    u64 t, b, e;
+    if (!segment(a.n, a.S, a.L, t, b, e)) return;
+    u32 acc[8], x[8];
+    set(acc, a.ident);
+    const size_t step = 2 * (size_t)a.ys;
+    const uint4 *py = a.y + b * step;
+    for (u64 i = b; i < e; i++, py += step) {
+        ld_elem(py, x);
+        combine<ADD>(acc, x);
+    }
+    st_elem(a.v + 2 * t, acc);
+}
+
+template <bool ADD>
+__global__ void __launch_bounds__(bnscan::THREADS) bn_scan_store_kernel(ScanArgs a) {
+    u64 t, b, e;
+    if (!segment(a.n, a.S, a.L, t, b, e)) return;
+    u32 acc[8], x[8];
+    if (a.carry && t > 0) ld_elem(a.carry + 2 * (t - 1), acc); else set(acc, a.ident);
+    const size_t step = 2 * (size_t)a.ys;
+    uint4 *py = a.y + b * step;
+    for (u64 i = b; i < e; i++, py += step) {
+        ld_elem(py, x);
+        if (a.exclusive) { st_elem(py, acc); combine<ADD>(acc, x); }
+        else { combine<ADD>(acc, x); st_elem(py, acc); }
+    }
+}
+
+Elem to_elem(const u64 w[4]) {
+    Elem e;
+    for (int i = 0; i < 4; i++) { e.w[2 * i] = (u32)w[i]; e.w[2 * i + 1] = (u32)(w[i] >> 32); }
+    return e;
+}
+Elem mont_one() { return to_elem(bnp::h_to_mont(bnp::U256{ { 1, 0, 0, 0 } }).w); }
+
+unsigned blocks(u64 lanes) { return (unsigned)((lanes + bnscan::THREADS - 1) / bnscan::THREADS); }
+
+// y[i] = mode(x[i]^-1) over the plan's levels; q: where level 0 keeps its prefixes (y, or the working buffer when y is x)
+int inverse_launch(const bnscan::Plan &p, uint4 *base, const uint4 *x, u64 xs, uint4 *y, u64 ys, uint4 *q, u64 qs,
+                   u32 mode, const uint4 *num, u64 ns, const Elem &mul, hipStream_t st) {
+    auto values = [&](u32 i) { return base + 2 * p.lv[i].off; };
+    auto args = [&](u32 i) {
+        const bnscan::Level &l = p.lv[i];
+        InvArgs a{};
+        if (i == 0) { a.x = x; a.xs = xs; a.y = y; a.ys = ys; a.q = q; a.qs = qs; a.mode = mode; a.num = num; a.ns = ns; a.mul = mul; }
+        else { a.x = values(i); a.y = values(i); a.q = values(i) + 2 * l.n; a.xs = a.ys = a.qs = 1; a.mode = MODE_NONE; }
+        a.n = l.n; a.S = l.S; a.L = l.L; a.one = mont_one();
+        return a;
+    };
+    const u32 last = p.nLevels - 1;
+    for (u32 i = 0; i < last; i++) {
+        InvArgs a = args(i);
+        a.v = values(i + 1);
+        bn_inv_reduce_kernel<<<blocks(a.S), bnscan::THREADS, 0, st>>>(a);
+        KERNEL_CHECK();
+    }
+    for (u32 i = p.nLevels; i-- > 0;) {
+        InvArgs a = args(i);
+        if (i == last) bn_inv_store_kernel<true><<<1, 64, 0, st>>>(a);
+        else { a.vinv = values(i + 1); bn_inv_store_kernel<false><<<blocks(a.S), bnscan::THREADS, 0, st>>>(a); }
+        KERNEL_CHECK();
+    }
+    return PIL2GL_OK;
+}
+
+// the running sum (inclusive) or product (exclusive, from 1) of y, in place
+template <bool ADD>
+int scan_launch(const bnscan::Plan &p, uint4 *base, uint4 *y, u64 ys, hipStream_t st) {
+    auto values = [&](u32 i) { return base + 2 * p.lv[i].off; };
+    auto args = [&](u32 i) {
+        const bnscan::Level &l = p.lv[i];
+        ScanArgs a{};
+        a.y = i ? values(i) : y; a.ys = i ? 1 : ys;
+        a.n = l.n; a.S = l.S; a.L = l.L; a.exclusive = !ADD && i == 0;
+        if (!ADD) a.ident = mont_one();
+        return a;
+    };
+    const u32 last = p.nLevels - 1;
+    for (u32 i = 0; i < last; i++) {
+        ScanArgs a = args(i);
+        a.v = values(i + 1);
+        bn_scan_reduce_kernel<ADD><<<blocks(a.S), bnscan::THREADS, 0, st>>>(a);
+        KERNEL_CHECK();
+    }
+    for (u32 i = p.nLevels; i-- > 0;) {
+        ScanArgs a = args(i);
+        a.carry = i < last ? values(i + 1) : nullptr;
+        bn_scan_store_kernel<ADD><<<blocks(a.S), bnscan::THREADS, 0, st>>>(a);
+        KERNEL_CHECK();
+    }
+    return PIL2GL_OK;
+}
+
+int run(u32 op, const u64 *num, u64 numStride, const u64 *hostNum, const u64 *den, u64 denStride, u64 n, u64 *out, u64 outStride, hipStream_t st) {
+    if (n == 0) return PIL2GL_OK;
+    const bool inPlace = op == bnscan::OP_BATCH_INVERSE && den == out;
+    const bnscan::Plan p = bnscan::plan(n, inPlace);
+    u64 *d = nullptr;
+    if (p.elems) P2_TRY(scratch(SCR_BN_SCAN, 4 * p.elems, &d));
+    uint4 *base = (uint4 *)d, *y = (uint4 *)out;
+    uint4 *q = inPlace ? base + 2 * p.q0Off : y;
+    const u32 mode = op == bnscan::OP_GPROD ? MODE_COLUMN : op == bnscan::OP_GSUM ? MODE_CONST : MODE_NONE;
+    const Elem mul = hostNum ? to_elem(hostNum) : Elem{};
+    P2_TRY(inverse_launch(p, base, (const uint4 *)den, denStride, y, outStride, q, inPlace ? 1 : outStride, mode, (const uint4 *)num, numStride, mul, st));
+    if (op == bnscan::OP_GPROD) return scan_launch<false>(p, base, y, outStride, st);
+    if (op == bnscan::OP_GSUM) return scan_launch<true>(p, base, y, outStride, st);
+    return PIL2GL_OK;
+}
+
+int check_column(const void *p, u64 n, u64 stride) {
+    if (const char *m = bnscan::check_size(n)) return fail(PIL2GL_EINVAL, "n = %llu: %s", (unsigned long long)n, m);
+    if (const char *m = bnscan::check_stride(stride)) return fail(PIL2GL_EINVAL, "stride = %llu: %s", (unsigned long long)stride, m);
+    if (n && !p) return fail(PIL2GL_EINVAL, "null buffer");
+    return PIL2GL_OK;
+}
+int check_apart(const void *in, u64 inStride, const void *out, u64 outStride, u64 n, bool sameAllowed) {
+    const bnscan::Relation r = bnscan::relation((uintptr_t)in, inStride, (uintptr_t)out, outStride, n);
+    if (r == bnscan::OVERLAP || (r == bnscan::SAME && !sameAllowed))
+        return fail(PIL2GL_EINVAL, "the output overlaps an input (only batch_inverse may run in place, on the same pointer and stride)");
+    return PIL2GL_OK;
+}
+int check_inverse(const u64 *src, u64 srcStride, u64 n, const u64 *dst, u64 dstStride) {
+    P2_TRY(check_column(src, n, srcStride));
+    P2_TRY(check_column(dst, n, dstStride));
+    return check_apart(src, srcStride, dst, dstStride, n, true);
+}
+int check_gprod(const u64 *num, u64 numStride, const u64 *den, u64 denStride, u64 n, const u64 *out, u64 outStride) {
+    P2_TRY(check_column(num, n, numStride));
+    P2_TRY(check_column(den, n, denStride));
+    P2_TRY(check_column(out, n, outStride));
+    P2_TRY(check_apart(num, numStride, out, outStride, n, false));
+    return check_apart(den, denStride, out, outStride, n, false);
+}
+int check_gsum(const u64 *hostNum, const u64 *den, u64 denStride, u64 n, const u64 *out, u64 outStride) {
+    if (!hostNum) return fail(PIL2GL_EINVAL, "null buffer");
+    P2_TRY(check_column(den, n, denStride));
+    P2_TRY(check_column(out, n, outStride));
+    return check_apart(den, denStride, out, outStride, n, false);
+}
+int check_aligned(const void *a, const void *b, const void *c) {
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) return fail(PIL2GL_EINVAL, "device columns must be 16-byte aligned");
+    return PIL2GL_OK;
+}
+u64 span_words(u64 n, u64 stride) { return ((n - 1) * stride + 1) * 4; }     // up to the last element
+
+// the device copy of a host destination: a strided one keeps what lies between its elements, so those words travel too
+u64 *stage_out(Stage &s, const u64 *host, u64 n, u64 stride) {
+    return stride == 1 ? s.take(4 * n) : const_cast<u64 *>(s.put(host, span_words(n, stride)));
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_debug_bn128_scan_plan(uint64_t n, uint32_t op, uint32_t *outInfo, uint64_t *scratchBytes) {
+    if (!outInfo || !scratchBytes) return fail(PIL2GL_EINVAL, "null argument");
+    if (const char *m = bnscan::check_size(n)) return fail(PIL2GL_EINVAL, "n = %llu: %s", (unsigned long long)n, m);
+    if (op >= bnscan::N_OPS) return fail(PIL2GL_EINVAL, "op = %u: 0 batch_inverse, 1 gprod, 2 gsum, 3 batch_inverse in place", op);
+    const bnscan::Plan p = bnscan::plan(n, op == bnscan::OP_BATCH_INVERSE_IN_PLACE);
+    outInfo[0] = p.lv[0].L; outInfo[1] = (uint32_t)p.lv[0].S; outInfo[2] = p.nLevels; outInfo[3] = bnscan::THREADS;
+    outInfo[4] = bnscan::THREADS;                    // segments per workgroup: a lane each
+    *scratchBytes = n ? bnscan::scratch_bytes(p) : 0;
+    return PIL2GL_OK;
+}
+
+int pil2gl_bn128_batch_inverse_dev(const uint64_t *src, uint64_t srcStride, uint64_t n, uint64_t *dst, uint64_t dstStride, void *stream) {
+    P2_TRY(check_inverse(src, srcStride, n, dst, dstStride));
+    if (n == 0) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    P2_TRY(check_aligned(src, dst, nullptr));
+    return run(bnscan::OP_BATCH_INVERSE, nullptr, 0, nullptr, src, srcStride, n, dst, dstStride, as_stream(stream));
+}
+
+int pil2gl_bn128_gprod_dev(const uint64_t *num, uint64_t numStride, const uint64_t *den, uint64_t denStride, uint64_t n,
+                           uint64_t *out, uint64_t outStride, void *stream) {
+    P2_TRY(check_gprod(num, numStride, den, denStride, n, out, outStride));
+    if (n == 0) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    P2_TRY(check_aligned(num, den, out));
+    return run(bnscan::OP_GPROD, num, numStride, nullptr, den, denStride, n, out, outStride, as_stream(stream));
+}
+
+int pil2gl_bn128_gsum_dev(const uint64_t hostNum[4], const uint64_t *den, uint64_t denStride, uint64_t n,
+                          uint64_t *out, uint64_t outStride, void *stream) {
+    P2_TRY(check_gsum(hostNum, den, denStride, n, out, outStride));
+    if (n == 0) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    P2_TRY(check_aligned(den, out, nullptr));
+    return run(bnscan::OP_GSUM, nullptr, 0, hostNum, den, denStride, n, out, outStride, as_stream(stream));
+}
+
+int pil2gl_bn128_batch_inverse(const uint64_t *src, uint64_t srcStride, uint64_t n, uint64_t *dst, uint64_t dstStride) {
+    P2_TRY(check_inverse(src, srcStride, n, dst, dstStride));
+    if (n == 0) return PIL2GL_OK;
+    const bool inPlace = dst == src;                 // then the strides are equal too: anything else was refused
+    const uint64_t sw = span_words(n, srcStride), dw = span_words(n, dstStride);
+    Stage s(inPlace ? sw : sw + dw);
+    P2_TRY(s.rc());
+    const uint64_t *dSrc = s.put(src, sw);
+    uint64_t *dDst = inPlace ? const_cast<uint64_t *>(dSrc) : stage_out(s, dst, n, dstStride);
+    P2_TRY(s.rc());
+    P2_TRY(run(bnscan::OP_BATCH_INVERSE, nullptr, 0, nullptr, dSrc, srcStride, n, dDst, dstStride, 0));
+    return s.get(dst, dDst, dw);
+}
+
+int pil2gl_bn128_gprod(const uint64_t *num, uint64_t numStride, const uint64_t *den, uint64_t denStride, uint64_t n,
+                       uint64_t *out, uint64_t outStride) {
+    P2_TRY(check_gprod(num, numStride, den, denStride, n, out, outStride));
+    if (n == 0) return PIL2GL_OK;
+    const uint64_t nw = span_words(n, numStride), dw = span_words(n, denStride), ow = span_words(n, outStride);
+    Stage s(nw + dw + ow);
+    P2_TRY(s.rc());
+    const uint64_t *dNum = s.put(num, nw), *dDen = s.put(den, dw);
+    uint64_t *dOut = stage_out(s, out, n, outStride);
+    P2_TRY(s.rc());
+    P2_TRY(run(bnscan::OP_GPROD, dNum, numStride, nullptr, dDen, denStride, n, dOut, outStride, 0));
+    return s.get(out, dOut, ow);
+}
+
+int pil2gl_bn128_gsum(const uint64_t hostNum[4], const uint64_t *den, uint64_t denStride, uint64_t n, uint64_t *out, uint64_t outStride) {
+    P2_TRY(check_gsum(hostNum, den, denStride, n, out, outStride));
+    if (n == 0) return PIL2GL_OK;
+    const uint64_t dw = span_words(n, denStride), ow = span_words(n, outStride);
+    Stage s(dw + ow);
+    P2_TRY(s.rc());
+    const uint64_t *dDen = s.put(den, dw);
+    uint64_t *dOut = stage_out(s, out, n, outStride);
+    P2_TRY(s.rc());
+    P2_TRY(run(bnscan::OP_GSUM, nullptr, 0, hostNum, dDen, denStride, n, dOut, outStride, 0));
+    return s.get(out, dOut, ow);
+}
+
+}  // extern "C"

@@ -70,6 +70,7 @@ enum ScratchSlot : u32 {
     SCR_BN_MSM = 18,          // bn_msm.hip: histogram, cursors, point lists, buckets and reduction levels of a G1 MSM (layout: bnp::bn_msm_plan)
     SCR_BN_EXPR = 19,         // bn_expr.hip: the first-non-zero search's cell, the device form of a program (ops, scalar pool), the temporaries that do not fit LDS
     SCR_BN_POLY = 20,         // bn_poly.hip: the levels' multipliers, then the segment values of every level and point (layout: bnpoly::plan)
+    SCR_BN_SCAN = 21,         // bn_scan.hip: the levels' segment totals and prefixes, then the level-0 prefixes of an inversion in place (layout: bnscan::plan)
     N_SCRATCH
 };
 int scratch(ScratchSlot slot, u64 nWords, u64 **out);

@@ -1,0 +1,95 @@
+// Drop-ins for calculateZ, calculateS (src/helpers/polutils.js:132-164) and F.batchInverse with F = curve.Fr, the field a fflonk stage
+// resolves its gprod / gsum hints over (src/prover/hints_helpers.js:92-113), computed by libpil2gl on the MI355X (csrc/bn_scan.hip).
+//   calculateZ(F, num, den)   z[0] = 1, z[i] = z[i-1] num[i-1] / den[i-1]
+//   calculateS(F, num, den)   s[i] = s[i-1] + num / den[i], num ONE element
+//   batchInverse(F, a)        a[i]^-1
+// Array forms: arrays of Uint8Array(32), Fr Montgomery bytes (what curve.Fr keeps), in and out; `F` is accepted and ignored.  They are
+// packed, staged through device copies and unpacked, as js/polutils.js does for Goldilocks.
+// Resident forms (calculateZDev, calculateSDev, batchInverseDev): a column is { buf: DevBuffer, stride = 1, offset = 0 }, element i at
+// element offset + i * stride of buf (a section of prover_helpers_bn128.js: stride = its width, offset = the column).  Nothing is staged;
+// the result is written into the `out` column and `out` is returned.  The hint's `result` field is element n - 1: lastElement(out, n).
+// A zero denominator inverts to zero and stays out of every running product (include/pil2gl.h): its ratio is 0.
+"use strict";
+const { addon, isDev } = require("./native.js");
+
+function pack(col, what) {
+    const a = new BigUint64Array(4 * col.length);
+    const bytes = new Uint8Array(a.buffer);
+    for (let i = 0; i < col.length; i++) {
+        const e = col[i];
+        if (!(e instanceof Uint8Array) || e.byteLength !== 32) throw new Error("polutils_bn128: " + what + "[" + i + "] must be a Uint8Array of 32 bytes");
+        bytes.set(e, 32 * i);
+    }
+    return a;
+}
+function unpack(a) {
+    const n = a.length / 4, out = new Array(n);
+    for (let i = 0; i < n; i++) out[i] = new Uint8Array(a.buffer.slice(a.byteOffset + 32 * i, a.byteOffset + 32 * i + 32));
+    return out;
+}
+// fn(device addresses of the inputs, device address of the n-element result) -> the result as an array of Uint8Array(32)
+function onDevice(arrays, n, fn) {
+    const ptrs = [];
+    try {
+        for (const a of arrays) { const d = addon.devAlloc(Math.max(1, a.length)); ptrs.push(d); if (a.length) addon.devUpload(d, 0, a); }
+        const dOut = addon.devAlloc(Math.max(1, 4 * n)); ptrs.push(dOut);
+        fn(ptrs.slice(0, arrays.length), dOut);
+        const r = new BigUint64Array(4 * n);
+        if (n) addon.devDownload(r, dOut, 0);                    // a synchronous copy: ordered after the kernels
+        return unpack(r);
+    } finally { for (const d of ptrs) addon.devFree(d); }
+}
+
+async function calculateZ(F, num, den) {
+    const n = den.length;
+    if (num.length !== n) throw new Error("polutils_bn128: num and den must have the same length");
+    return onDevice([pack(num, "num"), pack(den, "den")], n, ([dn, dd], dz) => addon.bn128GprodDev(dn, 1, dd, 1, n, dz, 1));
+}
+async function calculateS(F, num, den) {
+    const n = den.length, c = pack([num], "num");
+    return onDevice([pack(den, "den")], n, ([dd], ds) => addon.bn128GsumDev(c, dd, 1, n, ds, 1));
+}
+function batchInverse(F, a) {
+    const n = a.length;
+    return onDevice([pack(a, "a")], n, ([da], di) => addon.bn128BatchInverseDev(da, 1, n, di, 1));
+}
+
+// ---- resident columns ----
+function column(c, n, what) {
+    if (!c || !isDev(c.buf)) throw new Error("polutils_bn128: " + what + " must be { buf: DevBuffer, stride, offset }");
+    const stride = c.stride === undefined ? 1 : c.stride, offset = c.offset === undefined ? 0 : c.offset;
+    if (!Number.isInteger(stride) || stride < 1 || !Number.isInteger(offset) || offset < 0) throw new Error("polutils_bn128: bad stride or offset of " + what);
+    const words = n ? 4 * (offset + (n - 1) * stride + 1) : 0;
+    if (c.buf.length < words) throw new Error("polutils_bn128: " + what + " holds " + c.buf.length + " words, needs " + words);
+    return { ptr: c.buf.addr(4 * offset), stride };
+}
+function rows(n) {
+    if (!Number.isInteger(n) || n < 0) throw new Error("polutils_bn128: bad row count");
+    return n;
+}
+function calculateZDev(num, den, n, out, stream) {
+    const a = column(num, rows(n), "num"), b = column(den, n, "den"), o = column(out, n, "out");
+    addon.bn128GprodDev(a.ptr, a.stride, b.ptr, b.stride, n, o.ptr, o.stride, stream);
+    return out;
+}
+function calculateSDev(num, den, n, out, stream) {
+    if (!(num instanceof Uint8Array) || num.byteLength !== 32) throw new Error("polutils_bn128: num must be a Uint8Array of 32 bytes");
+    const b = column(den, rows(n), "den"), o = column(out, n, "out");
+    addon.bn128GsumDev(pack([num], "num"), b.ptr, b.stride, n, o.ptr, o.stride, stream);
+    return out;
+}
+// out may be the same column as src (in place)
+function batchInverseDev(src, n, out, stream) {
+    const a = column(src, rows(n), "src"), o = column(out, n, "out");
+    addon.bn128BatchInverseDev(a.ptr, a.stride, n, o.ptr, o.stride, stream);
+    return out;
+}
+// the `result` field of a hint: element n - 1 of its column, as Montgomery bytes
+function lastElement(col, n) {
+    const c = column(col, rows(n), "the column");
+    if (n < 1) throw new Error("polutils_bn128: an empty column has no last element");
+    const off = 4 * ((col.offset || 0) + (n - 1) * c.stride);
+    return new Uint8Array(col.buf.slice(off, off + 4).buffer);
+}
+
+module.exports = { calculateZ, calculateS, batchInverse, calculateZDev, calculateSDev, batchInverseDev, lastElement };

@@ -8,6 +8,9 @@
   encode_program / eval_program / first_nonzero_row
                                   <-> src/prover/prover_helpers.js:31-259 calculateExps over ctx.F = curve.Fr (Montgomery words in and out)
   poly_div / poly_eval / poly_plan <-> Polynomial.divZh / divByXNSubValue / evaluate as fflonk_prover_helpers.js:147-148, :212 use them
+  batch_inverse / gprod / gsum / scan_plan
+                                  <-> F.batchInverse, calculateZ, calculateS of src/helpers/polutils.js:132-164 over curve.Fr, as
+                                      hints_helpers.js:92-113 resolves gprod / gsum hints (Montgomery words in and out)
 Field elements cross this API as Python ints in normal form (the JS modules use BigInt / F.toObject)."""
 import ctypes as C
 
@@ -346,6 +349,88 @@ def poly_plan(n, k):
     info = (C.c_uint32 * 5)(); nbytes = C.c_uint64()
     call("pil2gl_debug_bn128_poly_plan", n, k, info, C.byref(nbytes))
     d = dict(zip(("L", "S", "levels", "threads", "form"), (int(v) for v in info)))
+    d["scratchBytes"] = int(nbytes.value)
+    return d
+
+
+# ---- gprod / gsum hints over Fr: calculateZ, calculateS and F.batchInverse (polutils.js:132-164, hints_helpers.js:92-113) ----
+SCAN_OPS = {"batch_inverse": 0, "gprod": 1, "gsum": 2, "batch_inverse_in_place": 3}
+
+
+def _column(buf, n, stride, what):
+    """-> the rows of a column: n, or what `buf` holds at this stride; checks the stride and the length"""
+    if stride < 1:
+        raise Pil2glError("stride must be at least 1")
+    if n is None:
+        n = (int(np.prod(buf.shape)) // 4 + stride - 1) // stride
+    _check_len(buf, ((n - 1) * stride + 1) * 4 if n else 0, what)
+    return n
+
+
+def _scan_out(like, n, stride, out):
+    if out is None:
+        if stride != 1:
+            raise Pil2glError("a strided result is written into a matrix: pass out")
+        out = torch.empty((n, 4), dtype=like.dtype, device=like.device) if _is_dev(like) else np.empty((n, 4), np.uint64)
+    _column(out, n, stride, "out")
+    return out
+
+
+def batch_inverse(words, n=None, stride=1, out=None, out_stride=None):
+    """F.batchInverse: out[i] = words[i]^-1, a zero giving zero (element i at word 4*i*stride, Montgomery words; a numpy array or a device
+    tensor).  n defaults to the elements `words` holds at this stride.  -> a new buffer of the same kind, or `out` (element i at word
+    4*i*out_stride, out_stride defaulting to stride; `out` may be `words` itself at the same stride, and nothing else that overlaps it)"""
+    if out is not None and _is_dev(out) != _is_dev(words):
+        raise Pil2glError("mixing host and device buffers in one call")
+    n = _column(words, n, stride, "words")
+    out_stride = stride if out_stride is None else out_stride
+    out = _scan_out(words, n, out_stride, out)
+    if _is_dev(words):
+        call("pil2gl_bn128_batch_inverse_dev", _ptr(words), stride, n, _ptr(out), out_stride, _stream())
+    else:
+        call("pil2gl_bn128_batch_inverse", _ptr(words), stride, n, _ptr(out), out_stride)
+    return out
+
+
+def gprod(num, den, n=None, num_stride=1, den_stride=1, out=None, out_stride=1):
+    """calculateZ(F, num, den): out[0] = 1, out[i] = out[i-1] num[i-1] / den[i-1] (Montgomery words; columns as batch_inverse takes them,
+    each with its own stride; numpy arrays or device tensors, all of one kind).  A zero denominator makes its ratio 0.  n defaults to the
+    elements `den` holds.  -> a new buffer of the same kind, or `out` (which must not overlap num or den); out[n-1] is the hint's result"""
+    if _is_dev(num) != _is_dev(den) or (out is not None and _is_dev(out) != _is_dev(den)):
+        raise Pil2glError("mixing host and device buffers in one call")
+    n = _column(den, n, den_stride, "den")
+    _column(num, n, num_stride, "num")
+    out = _scan_out(den, n, out_stride, out)
+    if _is_dev(den):
+        call("pil2gl_bn128_gprod_dev", _ptr(num), num_stride, _ptr(den), den_stride, n, _ptr(out), out_stride, _stream())
+    else:
+        call("pil2gl_bn128_gprod", _ptr(num), num_stride, _ptr(den), den_stride, n, _ptr(out), out_stride)
+    return out
+
+
+def gsum(num_elem, den, n=None, den_stride=1, out=None, out_stride=1):
+    """calculateS(F, num, den): out[i] = out[i-1] + num / den[i] with num ONE element, 4 Montgomery words on the host; den and out as
+    gprod takes them.  A zero denominator adds 0."""
+    if _is_dev(num_elem):
+        raise Pil2glError("num_elem is one element on the host")
+    if out is not None and _is_dev(out) != _is_dev(den):
+        raise Pil2glError("mixing host and device buffers in one call")
+    n = _column(den, n, den_stride, "den")
+    out = _scan_out(den, n, out_stride, out)
+    e = _host_elems(num_elem, "num_elem", 1)
+    if _is_dev(den):
+        call("pil2gl_bn128_gsum_dev", _ptr(e), _ptr(den), den_stride, n, _ptr(out), out_stride, _stream())
+    else:
+        call("pil2gl_bn128_gsum", _ptr(e), _ptr(den), den_stride, n, _ptr(out), out_stride)
+    return out
+
+
+def scan_plan(n, op="gprod"):
+    """pil2gl_debug_bn128_scan_plan (no device): how batch_inverse / gprod / gsum run n rows (op: a key of SCAN_OPS or its number) ->
+    {L rows per segment, S segments, levels, threads, segsPerWorkgroup, scratchBytes}"""
+    info = (C.c_uint32 * 5)(); nbytes = C.c_uint64()
+    call("pil2gl_debug_bn128_scan_plan", n, SCAN_OPS.get(op, op), info, C.byref(nbytes))
+    d = dict(zip(("L", "S", "levels", "threads", "segsPerWorkgroup"), (int(v) for v in info)))
     d["scratchBytes"] = int(nbytes.value)
     return d
 
