@@ -32,7 +32,7 @@
  *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi[_step] / cols_dot_ext /
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
  *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, compute_fri_pol, build_lev (small host tables),
- *      h1h2, synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
+ *      h1h2 and bn128_h1h2 (the missing row comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
  *      land_rows with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
  *    So do the host-pointer verifier calls roots_from_group_proofs and bn128_roots_from_group_proofs (roots copied to host memory).
@@ -621,6 +621,41 @@ int pil2gl_bn128_gsum_dev(const uint64_t hostNum[4], const uint64_t *den, uint64
  * above the first, below 9 MiB, and 32 * n more for op 3 only (an inversion in place has nowhere else to keep its prefix products); 0 for
  * n = 0.  n > 2^28 or op > 3: PIL2GL_EINVAL. */
 int pil2gl_debug_bn128_scan_plan(uint64_t n, uint32_t op, uint32_t *outInfo /* [5] */, uint64_t *scratchBytes);
+
+/* ---- BN254 Fr plookup hint: calculateH1H2 over curve.Fr (csrc/bn_h1h2.hip) ---------------------------------------------------------
+ * The last branch of resolveHint (src/prover/hints_helpers.js:115-121): calculateH1H2(F, f, t) of src/helpers/polutils.js:105-130, which
+ * uses no field arithmetic.  f and t have n elements each.  Two elements are the same value exactly when their 32 bytes are equal (the
+ * reference keys an object by the bytes).  With last(v) the largest i with t[i] = v, and cnt[i] = #{j : f[j] = t[i]} if i = last(t[i])
+ * and 0 otherwise, the merged sequence s is t[0] repeated 1 + cnt[0] times, then t[1] repeated 1 + cnt[1] times, and so on: 2 n
+ * elements; h1[i] = s[2i], h2[i] = s[2i+1].  (t = [a, b, a], f = [a, a, b]: s = a, b, b, a, a, a; h1 = [a, b, a], h2 = [b, a, a] -- the
+ * counts of a duplicated value go to its LAST occurrence.)  The result does not depend on the order in which atomics land.
+ *   Missing     If some f[j] is not in t the call returns PIL2GL_EINVAL with the message "Number not included: w:<j>", j the lowest such
+ *               index, also stored through missingRow (which may be NULL, and holds UINT64_MAX on success and on every other refusal).
+ *               Then no word of h1 or h2 has been written: the step that writes them is launched only after the check.
+ *   Addressing  element i of a column is the 4 words at word 4 * i * stride, f, t, h1 and h2 each with a stride of its own; the words
+ *               between a strided output's elements are left as they are.  Montgomery words as curve.Fr keeps them, expected canonical,
+ *               not validated, never converted.
+ *   Aliasing    An output must share no element with an input or with the other output, by the rule of the scan block above: byte ranges
+ *               apart, or two columns of one section (equal strides, pointers a multiple of 32 bytes apart that is no multiple of
+ *               32 * stride).  Any other overlap -- the same column included -- is PIL2GL_EINVAL, a host check.  f and t may be anything.
+ *   Limits      0 <= n <= 2^28, 1 <= stride < 2^32; anything else, and a null buffer with n > 0, is PIL2GL_EINVAL before any device
+ *               call.  n = 0 is PIL2GL_OK, touches nothing (missingRow aside) and needs no device.  Without a device: PIL2GL_ENODEV.
+ * The _dev form takes device pointers (16-byte aligned; anything else is PIL2GL_EINVAL, also before any device call), enqueues on the
+ * caller's stream and BLOCKS for the 8-byte readback of the missing cell; what writes h1 and h2 is enqueued after it and not waited
+ * for.  As for every BN254 block above, the working buffer
+ * (pil2gl_debug_bn128_h1h2_plan's scratchBytes) is (re)allocated, with a device synchronise, when it has to grow; it is one per process,
+ * so two of these calls must not be in flight on different streams at once.  All of it is cleared or written by every call.  The host
+ * form stages every column up to its last element (strided outputs too) through device copies. */
+int pil2gl_bn128_h1h2(const uint64_t *f, uint64_t fStride, const uint64_t *t, uint64_t tStride, uint64_t n,
+                      uint64_t *h1, uint64_t h1Stride, uint64_t *h2, uint64_t h2Stride, uint64_t *missingRow);
+int pil2gl_bn128_h1h2_dev(const uint64_t *f, uint64_t fStride, const uint64_t *t, uint64_t tStride, uint64_t n,
+                          uint64_t *h1, uint64_t h1Stride, uint64_t *h2, uint64_t h2Stride, uint64_t *missingRow, void *stream);
+/* host-only, no device: how the hint runs on n rows.  outInfo[0] = the table's capacity in 4-byte slots, the power of two with
+ * 2 n <= capacity < 4 n (2 for n <= 1); [1] = threads per workgroup; [2] = the scan chunk: groups (rows of t) per workgroup of the local
+ * scan; [3] = that scan's workgroups, ceil(n / chunk); [4] = output rows per workgroup of the expand step; [5] = its workgroups.
+ * *scratchBytes = the working buffer (table, counts / group starts, chunk totals, missing cell): below 20 n + n / 512 + 64 bytes for
+ * every n, 3 GiB + 512 KiB + 16 bytes at n = 2^28; 0 for n = 0.  n > 2^28: PIL2GL_EINVAL. */
+int pil2gl_debug_bn128_h1h2_plan(uint64_t n, uint32_t *outInfo /* [6] */, uint64_t *scratchBytes);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

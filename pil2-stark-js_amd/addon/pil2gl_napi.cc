@@ -278,6 +278,17 @@ FN(Bn128GsumDev) {           // (num BigUint64Array(4), dDen, denStride, n, dOut
     if (!a.ok) return nullptr;
     P2(env, pil2gl_bn128_gsum_dev(nu, de, ds, n, o, os, a.stream(6))); return mk_undefined(env);
 }
+// the plookup hint over curve.Fr (calculateH1H2).  A value of f that is not in t is no exception here: the row comes back, and
+// js/polutils_bn128.js throws the reference's full message, which needs the element
+FN(Bn128H1h2Dev) {           // (dF, fStride, dT, tStride, n, dH1, h1Stride, dH2, h2Stride[, stream]) -> undefined, or the lowest missing row as a BigInt
+    Args a(env, info); uint64_t *f = DP(0); uint64_t fs = a.u64(1); uint64_t *t = DP(2); uint64_t ts = a.u64(3), n = a.u64(4);
+    uint64_t *h1 = DP(5); uint64_t s1 = a.u64(6); uint64_t *h2 = DP(7); uint64_t s2 = a.u64(8);
+    if (!a.ok) return nullptr;
+    uint64_t miss = UINT64_MAX;
+    const int rc = pil2gl_bn128_h1h2_dev(f, fs, t, ts, n, h1, s1, h2, s2, &miss, a.stream(9));
+    if (rc == PIL2GL_EINVAL && miss != UINT64_MAX) return mk_bigint(env, miss);
+    P2(env, rc); return mk_undefined(env);
+}
 
 // ---- hashing ----
 FN(Poseidon) {      // (in BigUint64Array(8*count), cap BigUint64Array(4*count)|null, count, nOut, out)
@@ -627,6 +638,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128G1MsmDev", Bn128G1MsmDev }, { "bn128EvalProgramDev", Bn128EvalProgramDev }, { "bn128FirstNonzeroRowDev", Bn128FirstNonzeroRowDev },
         { "bn128PolyDivDev", Bn128PolyDivDev }, { "bn128PolyEvalDev", Bn128PolyEvalDev },
         { "bn128BatchInverseDev", Bn128BatchInverseDev }, { "bn128GprodDev", Bn128GprodDev }, { "bn128GsumDev", Bn128GsumDev },
+        { "bn128H1h2Dev", Bn128H1h2Dev },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

@@ -3,11 +3,15 @@
 //   calculateZ(F, num, den)   z[0] = 1, z[i] = z[i-1] num[i-1] / den[i-1]
 //   calculateS(F, num, den)   s[i] = s[i-1] + num / den[i], num ONE element
 //   batchInverse(F, a)        a[i]^-1
+//   calculateH1H2(F, f, t)    [h1, h2] of polutils.js:105-130, the h1h2 hint (hints_helpers.js:115-121; csrc/bn_h1h2.hip): elements are
+//                             compared as their 32 bytes; a value of f that t lacks throws the reference's message
 // Array forms: arrays of Uint8Array(32), Fr Montgomery bytes (what curve.Fr keeps), in and out; `F` is accepted and ignored.  They are
 // packed, staged through device copies and unpacked, as js/polutils.js does for Goldilocks.
 // Resident forms (calculateZDev, calculateSDev, batchInverseDev): a column is { buf: DevBuffer, stride = 1, offset = 0 }, element i at
 // element offset + i * stride of buf (a section of prover_helpers_bn128.js: stride = its width, offset = the column).  Nothing is staged;
 // the result is written into the `out` column and `out` is returned.  The hint's `result` field is element n - 1: lastElement(out, n).
+// calculateH1H2Dev(f, t, n, h1, h2, stream) writes two columns and returns [h1, h2]; h1 and h2 may be two columns of one section, and
+// overlap nothing otherwise.
 // A zero denominator inverts to zero and stays out of every running product (include/pil2gl.h): its ratio is 0.
 "use strict";
 const { addon, isDev } = require("./native.js");
@@ -54,6 +58,30 @@ function batchInverse(F, a) {
     return onDevice([pack(a, "a")], n, ([da], di) => addon.bn128BatchInverseDev(da, 1, n, di, 1));
 }
 
+// the reference's message for a value t lacks (polutils.js:115): the row, and the element as F.toString gives it -- the decimal normal form of
+// the Montgomery bytes
+const FR = 21888242871839275222246405745257275088548364400416034343698204186575808495617n;
+const R_INV = 9915499612839321149637521777990102151350674507940716049588462388200839649614n;       // (2^256)^-1 mod r
+function decimal(e) {
+    let v = 0n;
+    for (let i = 31; i >= 0; i--) v = (v << 8n) | BigInt(e[i]);
+    return (v * R_INV % FR).toString();
+}
+function notIncluded(row, e) { return new Error("Number not included: w:" + row + ", value:" + decimal(e)); }
+
+function calculateH1H2(F, f, t) {
+    const n = t.length;
+    if (f.length !== n) throw new Error("polutils_bn128: f and t must have the same length");
+    const ptrs = [];
+    try {
+        for (const a of [pack(f, "f"), pack(t, "t")]) { const d = addon.devAlloc(Math.max(1, a.length)); ptrs.push(d); if (a.length) addon.devUpload(d, 0, a); }
+        for (let k = 0; k < 2; k++) ptrs.push(addon.devAlloc(Math.max(1, 4 * n)));
+        const miss = addon.bn128H1h2Dev(ptrs[0], 1, ptrs[1], 1, n, ptrs[2], 1, ptrs[3], 1);
+        if (miss !== undefined) throw notIncluded(miss, f[Number(miss)]);
+        return [2, 3].map((k) => { const r = new BigUint64Array(4 * n); if (n) addon.devDownload(r, ptrs[k], 0); return unpack(r); });
+    } finally { for (const d of ptrs) addon.devFree(d); }
+}
+
 // ---- resident columns ----
 function column(c, n, what) {
     if (!c || !isDev(c.buf)) throw new Error("polutils_bn128: " + what + " must be { buf: DevBuffer, stride, offset }");
@@ -84,6 +112,15 @@ function batchInverseDev(src, n, out, stream) {
     addon.bn128BatchInverseDev(a.ptr, a.stride, n, o.ptr, o.stride, stream);
     return out;
 }
+function calculateH1H2Dev(f, t, n, h1, h2, stream) {
+    const a = column(f, rows(n), "f"), b = column(t, n, "t"), o1 = column(h1, n, "h1"), o2 = column(h2, n, "h2");
+    const miss = addon.bn128H1h2Dev(a.ptr, a.stride, b.ptr, b.stride, n, o1.ptr, o1.stride, o2.ptr, o2.stride, stream);
+    if (miss !== undefined) {                                     // the message carries the value: download that one element
+        const off = 4 * ((f.offset || 0) + Number(miss) * a.stride);
+        throw notIncluded(miss, new Uint8Array(f.buf.slice(off, off + 4).buffer));
+    }
+    return [h1, h2];
+}
 // the `result` field of a hint: element n - 1 of its column, as Montgomery bytes
 function lastElement(col, n) {
     const c = column(col, rows(n), "the column");
@@ -92,4 +129,4 @@ function lastElement(col, n) {
     return new Uint8Array(col.buf.slice(off, off + 4).buffer);
 }
 
-module.exports = { calculateZ, calculateS, batchInverse, calculateZDev, calculateSDev, batchInverseDev, lastElement };
+module.exports = { calculateZ, calculateS, batchInverse, calculateH1H2, calculateZDev, calculateSDev, batchInverseDev, calculateH1H2Dev, lastElement };

@@ -191,6 +191,9 @@ SIGNATURES = {
     "pil2gl_bn128_gsum": (_I, [vp, vp, _U64, _U64, vp, _U64]),
     "pil2gl_bn128_gsum_dev": (_I, [vp, vp, _U64, _U64, vp, _U64, vp]),
     "pil2gl_debug_bn128_scan_plan": (_I, [_U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_bn128_h1h2": (_I, [vp, _U64, vp, _U64, _U64, vp, _U64, vp, _U64, C.POINTER(_U64)]),
+    "pil2gl_bn128_h1h2_dev": (_I, [vp, _U64, vp, _U64, _U64, vp, _U64, vp, _U64, C.POINTER(_U64), vp]),
+    "pil2gl_debug_bn128_h1h2_plan": (_I, [_U64, C.POINTER(_U32), C.POINTER(_U64)]),
     "pil2gl_selftest_field":(_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_ext": (_I, [vp, vp, _U64, vp, vp]),
     "pil2gl_selftest_products": (_I, [vp, vp, _U64, vp, vp, vp]),

@@ -11,6 +11,7 @@
   batch_inverse / gprod / gsum / scan_plan
                                   <-> F.batchInverse, calculateZ, calculateS of src/helpers/polutils.js:132-164 over curve.Fr, as
                                       hints_helpers.js:92-113 resolves gprod / gsum hints (Montgomery words in and out)
+  h1h2 / h1h2_plan                <-> calculateH1H2 of src/helpers/polutils.js:105-130 over curve.Fr, the h1h2 hint (hints_helpers.js:115-121)
 Field elements cross this API as Python ints in normal form (the JS modules use BigInt / F.toObject)."""
 import ctypes as C
 
@@ -431,6 +432,43 @@ def scan_plan(n, op="gprod"):
     info = (C.c_uint32 * 5)(); nbytes = C.c_uint64()
     call("pil2gl_debug_bn128_scan_plan", n, SCAN_OPS.get(op, op), info, C.byref(nbytes))
     d = dict(zip(("L", "S", "levels", "threads", "segsPerWorkgroup"), (int(v) for v in info)))
+    d["scratchBytes"] = int(nbytes.value)
+    return d
+
+
+# ---- the plookup hint over Fr: calculateH1H2 (polutils.js:105-130, hints_helpers.js:115-121) ----
+def h1h2(f, t, n=None, f_stride=1, t_stride=1, h1=None, h1_stride=1, h2=None, h2_stride=1):
+    """calculateH1H2(F, f, t): the multiset f merged into t -- t[i] repeated 1 + cnt[i] times, the counts of a duplicated value at its LAST
+    occurrence -- and read as h1[i] = s[2i], h2[i] = s[2i+1].  Elements are compared as their 32 bytes (Montgomery words, never converted);
+    columns as gprod takes them, each with its own stride; numpy arrays or device tensors, all of one kind.  n defaults to the elements
+    `t` holds.  -> (h1, h2): new buffers of the same kind, or the ones passed (which must overlap nothing but as columns of one section).
+    A value of f that is not in t raises Pil2glError with "Number not included: w:<lowest such row>"; the outputs are untouched then."""
+    kinds = {_is_dev(b) for b in (f, t, h1, h2) if b is not None}
+    if len(kinds) != 1:
+        raise Pil2glError("mixing host and device buffers in one call")
+    n = _column(t, n, t_stride, "t")
+    _column(f, n, f_stride, "f")
+    h1 = _scan_out(t, n, h1_stride, h1)
+    h2 = _scan_out(t, n, h2_stride, h2)
+    miss = C.c_uint64()
+    args = (_ptr(f), f_stride, _ptr(t), t_stride, n, _ptr(h1), h1_stride, _ptr(h2), h2_stride, C.byref(miss))
+    try:
+        if _is_dev(t):
+            call("pil2gl_bn128_h1h2_dev", *args, _stream())
+        else:
+            call("pil2gl_bn128_h1h2", *args)
+    except Pil2glError as e:
+        e.missing_row = None if miss.value == (1 << 64) - 1 else int(miss.value)      # the library's missingRow
+        raise
+    return h1, h2
+
+
+def h1h2_plan(n):
+    """pil2gl_debug_bn128_h1h2_plan (no device): how h1h2 runs n rows -> {capacity (table slots), threads, scanChunk (groups per
+    workgroup of the local scan), scanBlocks, expandRows (output rows per workgroup of the expand step), expandBlocks, scratchBytes}"""
+    info = (C.c_uint32 * 6)(); nbytes = C.c_uint64()
+    call("pil2gl_debug_bn128_h1h2_plan", n, info, C.byref(nbytes))
+    d = dict(zip(("capacity", "threads", "scanChunk", "scanBlocks", "expandRows", "expandBlocks"), (int(v) for v in info)))
     d["scratchBytes"] = int(nbytes.value)
     return d
 
