@@ -142,6 +142,16 @@ __device__ __forceinline__ u32 xcd_local_block() {
     return b < (per << 3) ? (b & 7) * per + (b >> 3) : b;
 }
 
+// Two adjacent column slots of one tile row.  The 16-slot fixed-geometry kernels move a tile between HBM and LDS in these: lane
+// tid owns slots 2*px, 2*px+1 (px = tid & 7) of the eight tile rows r + 32*i (r = tid >> 3), so a 128-byte row piece is 8 lanes x 16
+// bytes, a row's inter-pass twiddle is read once for two elements, and everything that tells the eight rows apart is a constant:
+// an immediate offset in LDS (34 padded rows), a workgroup-uniform 64-bit step in HBM.  A matrix row of an odd column count starts on
+// 8 bytes, so the HBM side claims no more; the ragged last lane of such a row (one valid column) moves 8 bytes.
+struct Pair { u64 a, b; };
+typedef Pair __attribute__((aligned(16))) PairL;       // in LDS: tile rows are 128 bytes
+constexpr u32 PAIR_ROWS = 8, PAIR_LDS_STEP = 34 * 8;     // rows per lane; pairs between them in a padded tile (32 rows + 2 spare)
+__host__ __device__ constexpr u32 brev3(u32 i) { return ((i & 1) << 2) | (i & 2) | ((i >> 2) & 1); }
+
 constexpr unsigned PASS_THREADS = 256, MID_THREADS = 512;      // workgroup budgets of ntt_pass_kernel / lde_mid_kernel: the planner sizes tiles by them
 
 struct PassParams {
@@ -184,12 +194,33 @@ __global__ void __launch_bounds__(PASS_THREADS) ntt_pass_kernel(PassParams P) {
     const u64 g = P.scatter ? (u64)gi * P.nGroupTiles + gt : (u64)gt * P.nbT + gi;
     const u64 base = (u64)hi * P.hiStride + g * P.gStride + c;
 
+    // 16 slots: pairs of slots (see Pair); g = gt and gi = 0 here (one slot group)
+    constexpr bool WIDE = KC == 8 && SC == 16;
+    const u32 px = tid & 7, r = tid >> 3;
+    const u64 c0 = (u64)cc * 16 + 2 * px;
+    const bool v1 = c0 < P.C, v2 = c0 + 1 < P.C;
+    const u64 base0 = (u64)hi * P.hiStride + g * P.gStride + c0 + (u64)r * P.tStride, rs = P.tStride * 32;
+    Pair vin2[PAIR_ROWS];
+
     // the first LOADB rows of this lane are requested before the tables are built, so that their latency overlaps it;
     // all loads of a batch are in flight together (one load per iteration would serialise the HBM latency)
     constexpr u32 LOADB = 16;
     u64 vin[LOADB];
+    if constexpr (WIDE) {
 #pragma unroll
-    for (u32 i = 0; i < LOADB; i++) { const u32 t = y + i * by; vin[i] = (valid && t < K) ? P.src[base + (u64)t * P.tStride] : 0; }
+        for (u32 i = 0; i < PAIR_ROWS; i++) vin2[i] = {0, 0};
+        const u64 *sp = P.src + base0;
+        if (v2) {
+#pragma unroll
+            for (u32 i = 0; i < PAIR_ROWS; i++) vin2[i] = *reinterpret_cast<const Pair *>(sp + i * rs);
+        } else if (v1) {
+#pragma unroll
+            for (u32 i = 0; i < PAIR_ROWS; i++) vin2[i].a = sp[i * rs];
+        }
+    } else {
+#pragma unroll
+        for (u32 i = 0; i < LOADB; i++) { const u32 t = y + i * by; vin[i] = (valid && t < K) ? P.src[base + (u64)t * P.tStride] : 0; }
+    }
     for (u32 j = tid; j < K; j += nth) TW[j] = P.twK[j << (10 - k)];
     if (P.hasTw) {
         for (u32 idx = tid; idx < (KC ? 1 : P.nbT) * K; idx += nth) {
@@ -200,20 +231,35 @@ __global__ void __launch_bounds__(PASS_THREADS) ntt_pass_kernel(PassParams P) {
         }
     }
     __syncthreads();
-    for (u32 t0 = y;;) {
+    PairL *trow = reinterpret_cast<PairL *>(tile) + (r + (r >> 4)) * 8 + px;       // tile row r + 32*i: PAIR_LDS_STEP * i further
+    if constexpr (WIDE) {
+        if (DIT && P.hasTw) {
 #pragma unroll
-        for (u32 i = 0; i < LOADB; i++) {
-            const u32 t = t0 + i * by;
-            if (t < K) {
-                u64 v = vin[i];
-                if (DIT && P.hasTw) v = NTT_MUL(v, TWO[gi * K + t]);
-                tile[TROW(t) * S + x] = v;
+            for (u32 i = 0; i < PAIR_ROWS; i++) {
+                const u64 w = TWO[r + 32 * i];
+                PairL o; o.a = NTT_MUL(vin2[i].a, w); o.b = NTT_MUL(vin2[i].b, w);
+                trow[i * PAIR_LDS_STEP] = o;
             }
-        }
-        t0 += LOADB * by;
-        if (t0 >= K) break;
+        } else {
 #pragma unroll
-        for (u32 i = 0; i < LOADB; i++) { const u32 t = t0 + i * by; vin[i] = (valid && t < K) ? P.src[base + (u64)t * P.tStride] : 0; }
+            for (u32 i = 0; i < PAIR_ROWS; i++) { PairL o; o.a = vin2[i].a; o.b = vin2[i].b; trow[i * PAIR_LDS_STEP] = o; }
+        }
+    } else {
+        for (u32 t0 = y;;) {
+#pragma unroll
+            for (u32 i = 0; i < LOADB; i++) {
+                const u32 t = t0 + i * by;
+                if (t < K) {
+                    u64 v = vin[i];
+                    if (DIT && P.hasTw) v = NTT_MUL(v, TWO[gi * K + t]);
+                    tile[TROW(t) * S + x] = v;
+                }
+            }
+            t0 += LOADB * by;
+            if (t0 >= K) break;
+#pragma unroll
+            for (u32 i = 0; i < LOADB; i++) { const u32 t = t0 + i * by; vin[i] = (valid && t < K) ? P.src[base + (u64)t * P.tStride] : 0; }
+        }
     }
     __syncthreads();
     if constexpr (KC == 8) {
@@ -222,14 +268,47 @@ __global__ void __launch_bounds__(PASS_THREADS) ntt_pass_kernel(PassParams P) {
     } else {
         if (DIT) dit_stages<INV>(tile, TW, k, S, x, y, by); else dif_stages<INV>(tile, TW, k, S, x, y, by);
     }
-    if (!valid) return;
-    for (u32 t = y; t < K; t += by) {
-        u64 v = tile[TROW(t) * S + x];
-        if (P.hasTw && !DIT) v = P.canonOut ? mul(v, TWO[gi * K + t]) : NTT_MUL(v, TWO[gi * K + t]);
-        else if (!P.hasTw && P.scale) v = mul(v, P.scale);
-        else if (P.canonOut) v = canon(v);
-        u64 addr = P.scatter ? (u64)bitrev32((u32)(g * K + t), P.n) * P.C + c : base + (u64)t * P.tStride;
-        P.dst[addr] = v;
+    if constexpr (WIDE) {
+        if (!v1) return;
+        // row i of this lane: words dp + ord(i) * os, ord = i, or its 3-bit reversal where the pass scatters (tile row bits 5..7 are
+        // the lowest three of the reversed index above the tile's own: bitrev_n(g*2^8 + r + 32 i) = bitrev_n(g*2^8 + r) + (brev3(i) << (n - 8)))
+        u64 *dp = P.dst + base0;
+        u64 os = rs;
+        if (P.scatter) { dp = P.dst + (u64)bitrev32((u32)(g * K + r), P.n) * P.C + c0; os = P.C << (P.n - 8); }
+        // what a value takes on its way out is the same for the whole launch: one loop per case, nothing decided per element
+        auto put = [&](auto xf) {
+            if (v2) {
+#pragma unroll
+                for (u32 i = 0; i < PAIR_ROWS; i++) {
+                    Pair v; { const PairL l = trow[i * PAIR_LDS_STEP]; v.a = l.a; v.b = l.b; }
+                    xf(v, i);
+                    *reinterpret_cast<Pair *>(dp + (P.scatter ? brev3(i) : i) * os) = v;
+                }
+            } else {
+#pragma unroll
+                for (u32 i = 0; i < PAIR_ROWS; i++) {
+                    Pair v; v.a = reinterpret_cast<const u64 *>(trow + i * PAIR_LDS_STEP)[0]; v.b = 0;
+                    xf(v, i);
+                    dp[(P.scatter ? brev3(i) : i) * os] = v.a;
+                }
+            }
+        };
+        if (P.hasTw && !DIT) {
+            if (P.canonOut) put([&](Pair &v, u32 i) { const u64 w = TWO[r + 32 * i]; v.a = mul(v.a, w); v.b = mul(v.b, w); });
+            else put([&](Pair &v, u32 i) { const u64 w = TWO[r + 32 * i]; v.a = NTT_MUL(v.a, w); v.b = NTT_MUL(v.b, w); });
+        } else if (!P.hasTw && P.scale) put([&](Pair &v, u32) { v.a = mul(v.a, P.scale); v.b = mul(v.b, P.scale); });
+        else if (P.canonOut) put([&](Pair &v, u32) { v.a = canon(v.a); v.b = canon(v.b); });
+        else put([&](Pair &, u32) {});
+    } else {
+        if (!valid) return;
+        for (u32 t = y; t < K; t += by) {
+            u64 v = tile[TROW(t) * S + x];
+            if (P.hasTw && !DIT) v = P.canonOut ? mul(v, TWO[gi * K + t]) : NTT_MUL(v, TWO[gi * K + t]);
+            else if (!P.hasTw && P.scale) v = mul(v, P.scale);
+            else if (P.canonOut) v = canon(v);
+            u64 addr = P.scatter ? (u64)bitrev32((u32)(g * K + t), P.n) * P.C + c : base + (u64)t * P.tStride;
+            P.dst[addr] = v;
+        }
     }
 #undef TROW
 }
@@ -268,9 +347,31 @@ __global__ void __launch_bounds__(MID_THREADS) lde_mid_kernel(LdeParams P) {
     const u64 g = (u64)gt * (SC ? 1 : P.G) + gi;    // index of this slot's 2^k-row block
     const u64 base = g * K * P.C + c;
 
+    // 16 slots: pairs of slots (see Pair), the lane's eight pairs of coefficients in registers over the cosets
+    constexpr bool WIDE = SC == 16;
+    const u32 px = tid & 7, r = tid >> 3;
+    const u64 c0 = (u64)cc * 16 + 2 * px;
+    const bool v1 = c0 < P.C, v2 = c0 + 1 < P.C;
+    Pair coef2[PAIR_ROWS];
+    PairL *trow = reinterpret_cast<PairL *>(tile) + (r + (r >> 4)) * 8 + px;       // tile row r + 32*i: PAIR_LDS_STEP * i further
+
     u64 coef[EPT];                                  // EPT >= K / by rows per lane (2, 4, 8 or 16): all loads in flight while the tables are built
+    if constexpr (WIDE) {
 #pragma unroll
-    for (int i = 0; i < EPT; i++) { const u32 t = y + i * by; coef[i] = (valid && t < K) ? P.src[base + (u64)t * P.C] : 0; }
+        for (u32 i = 0; i < PAIR_ROWS; i++) coef2[i] = {0, 0};
+        const u64 *sp = P.src + (g * K + r) * P.C + c0;
+        const u64 rs = P.C * 32;
+        if (v2) {
+#pragma unroll
+            for (u32 i = 0; i < PAIR_ROWS; i++) coef2[i] = *reinterpret_cast<const Pair *>(sp + i * rs);
+        } else if (v1) {
+#pragma unroll
+            for (u32 i = 0; i < PAIR_ROWS; i++) coef2[i].a = sp[i * rs];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < EPT; i++) { const u32 t = y + i * by; coef[i] = (valid && t < K) ? P.src[base + (u64)t * P.C] : 0; }
+    }
     for (u32 j = tid; j < K; j += nth) { TWi[j] = P.twKi[j << (10 - k)]; TWf[j] = P.twKf[j << (10 - k)]; }
     for (u32 idx = tid; idx < P.G * K; idx += nth) {
         u32 pos = (gt * P.G + (idx >> k)) * K + (idx & (K - 1));
@@ -281,17 +382,58 @@ __global__ void __launch_bounds__(MID_THREADS) lde_mid_kernel(LdeParams P) {
         Sc[idx] = s0;
     }
     if (!P.coefIn) {                                // (uniform for the launch)
+        if constexpr (WIDE) {
 #pragma unroll
-        for (int i = 0; i < EPT; i++) { const u32 t = y + i * by; if (t < K) tile[(y + i * rowStep) * S + x] = coef[i]; }
+            for (u32 i = 0; i < PAIR_ROWS; i++) { PairL o; o.a = coef2[i].a; o.b = coef2[i].b; trow[i * PAIR_LDS_STEP] = o; }
+        } else {
+#pragma unroll
+            for (int i = 0; i < EPT; i++) { const u32 t = y + i * by; if (t < K) tile[(y + i * rowStep) * S + x] = coef[i]; }
+        }
         __syncthreads();
         if constexpr (SC != 0) { dif_step<4, true, true>(tile, TWi, 8, 8, SC, x, y, 16); dif_step<4, true, true>(tile, TWi, 8, 4, SC, x, y, 16); }
         else dif_stages<true>(tile, TWi, k, S, x, y, by);
+        if constexpr (WIDE) {
 #pragma unroll
-        for (int i = 0; i < EPT; i++) { u32 t = y + i * by; coef[i] = t < K ? tile[(y + i * rowStep) * S + x] : 0; }
+            for (u32 i = 0; i < PAIR_ROWS; i++) { const PairL l = trow[i * PAIR_LDS_STEP]; coef2[i].a = l.a; coef2[i].b = l.b; }
+        } else {
+#pragma unroll
+            for (int i = 0; i < EPT; i++) { u32 t = y + i * by; coef[i] = t < K ? tile[(y + i * rowStep) * S + x] : 0; }
+        }
     }
     __syncthreads();
     const u32 nCosets = P.cosetCount;
     for (u32 j = 0; j < nCosets; j++) {
+        if constexpr (WIDE) {
+            // (the offsets are made opaque for the reason given below; the eight rows are then a uniform step apart)
+            u64 dstOff = ((g * K + r) * P.cosetCount + j) * P.C + c0;
+            u32 pairOff = (r + (r >> 4)) * 8 + px, scOff = r;
+            asm volatile("" : "+v"(dstOff), "+v"(pairOff), "+v"(scOff));
+            const u64 dstStep = (u64)32 * P.cosetCount * P.C;
+            PairL *tp = reinterpret_cast<PairL *>(tile) + pairOff;
+#pragma unroll
+            for (u32 i = 0; i < PAIR_ROWS; i++) {
+                const u64 sc = Sc[scOff + 32 * i];
+                PairL o; o.a = NTT_MUL(coef2[i].a, sc); o.b = NTT_MUL(coef2[i].b, sc);
+                tp[i * PAIR_LDS_STEP] = o;
+            }
+            __syncthreads();
+            dit_step<4, false, true>(tile, TWf, 8, 0, 4, SC, x, y, 16); dit_step<4, false, true>(tile, TWf, 8, 4, 0, SC, x, y, 16);
+            asm volatile("" : "+v"(dstOff), "+v"(pairOff));
+            tp = reinterpret_cast<PairL *>(tile) + pairOff;
+            u64 *dp = P.dst + dstOff;
+            if (v2) {
+                if (P.canonOut) {
+#pragma unroll
+                    for (u32 i = 0; i < PAIR_ROWS; i++) { const PairL l = tp[i * PAIR_LDS_STEP]; Pair v; v.a = canon(l.a); v.b = canon(l.b); *reinterpret_cast<Pair *>(dp + i * dstStep) = v; }
+                } else {
+#pragma unroll
+                    for (u32 i = 0; i < PAIR_ROWS; i++) { const PairL l = tp[i * PAIR_LDS_STEP]; Pair v; v.a = l.a; v.b = l.b; *reinterpret_cast<Pair *>(dp + i * dstStep) = v; }
+                }
+            } else if (v1) {
+#pragma unroll
+                for (u32 i = 0; i < PAIR_ROWS; i++) { const u64 v = reinterpret_cast<const u64 *>(tp + i * PAIR_LDS_STEP)[0]; dp[i * dstStep] = P.canonOut ? canon(v) : v; }
+            }
+        } else {
         // the per-row offsets do not depend on j: left alone the compiler computes them all once and keeps ~4 registers per
         // row alive across the loop; the opaque copies make it redo the few additions in every coset instead
         u64 dstOff = ((g * K + y) * P.cosetCount + j) * P.C + c;
@@ -310,6 +452,7 @@ __global__ void __launch_bounds__(MID_THREADS) lde_mid_kernel(LdeParams P) {
                 u32 t = y + i * by;
                 if (t < K) { const u64 v = tile[tileOff + i * rowStep * S]; P.dst[dstOff + i * dstStep] = P.canonOut ? canon(v) : v; }
             }
+        }
         }
         for (u32 idx = tid; idx < P.G * K; idx += nth) Sc[idx] = mul(Sc[idx], Uc[idx]);
         __syncthreads();
