@@ -578,6 +578,40 @@ int pil2gl_bn128_poly_eval_dev(const uint64_t *src, uint64_t n, uint64_t stride,
  * levels, below 9 MiB (none in form 0).  The carry-level count stops growing at n = 2^22.  n or k out of range: PIL2GL_EINVAL. */
 int pil2gl_debug_bn128_poly_plan(uint64_t n, uint64_t k, uint32_t *outInfo /* [5] */, uint64_t *scratchBytes);
 
+/* ---- BN254 Fr products with a sparse polynomial, scaled sums and the degree (csrc/bn_polymul.hip) -----------------------------------
+ * What shplonkjs open (computeOpeningsFflonk, fflonk_prover_helpers.js:212) does on its longest vectors between the evaluations and the
+ * divisions of the block above: the Polynomial class's add, sub, mulScalar, byXSubValue, byXNSubValue and degree, which build
+ * W = sum_i alpha^i (f_i - r_i) Z_{T\S_i} and L = sum_i alpha^i Z_{T\S_i}(y) (f_i - r_i(y)) - Z_T(y) W.  One form covers the first five:
+ *     acc[i] <- s * acc[i] + sum_{j < t} m[j] * src[i - e[j]]     for 0 <= i < nAcc,   src[x] = 0 for x < 0 or x >= nSrc,
+ * the product of src by M(x) = sum_j m[j] x^e[j] added to the scaled accumulator.  add / sub: t = 1, m = 1 / r - 1, s = 1.  mulScalar:
+ * t = 1, s = NULL, acc the same column as src.  byXSubValue(v): {(-v, 0), (1, 1)}; byXNSubValue(n, v): {(-v, 0), (1, n)}.  A zerofier
+ * prod_j (x^k_j - beta_j) multiplied out on the host is ONE call instead of one per factor, and W += alpha^i Z f_i is one call.
+ * poly_degree stores the largest i whose 32 bytes are not all zero, or UINT64_MAX for the zero polynomial and for n = 0.
+ *   Addressing  element i of a column is the 4 words at word 4 * i * stride, acc and src each with a stride of its own; the words between a
+ *               strided acc's elements are left as they are.  Montgomery words, canonical in and out, never converted, not validated.
+ *   hostScale   a HOST pointer to 4 Montgomery words, or NULL: then acc is written and NEVER READ (it may hold anything).
+ *   hostCoefs, hostExps   HOST pointers: t elements of 4 Montgomery words, and t exponents, strictly increasing.  Zero coefficients are
+ *               dropped on the host; the kernel sees the compacted list.
+ *   Aliasing    acc must share no element with src, by the rule of the scan block below (byte ranges apart, or two columns of one section).
+ *               One exception: with t = 1 and e[0] = 0 the operation is elementwise and acc may be the SAME column as src.  A shifted
+ *               product in place is refused: the caller alternates two buffers, as the reference's byXSubValue does with its new buffer.
+ *   Limits      0 <= nAcc, nSrc <= 2^28, 1 <= stride < 2^32, 1 <= t <= 64, e[t-1] <= 2^28, and nSrc > 0 implies nSrc + e[t-1] <= nAcc (a
+ *               product is never truncated); anything else, and a null buffer with a non-zero count (hostCoefs, hostExps, degree: always),
+ *               is PIL2GL_EINVAL before any device call.  nAcc = 0 is PIL2GL_OK and needs no device; nSrc = 0 only scales, or zero-fills
+ *               with hostScale NULL.  Without a device the entries return PIL2GL_ENODEV.
+ * The _dev forms take device pointers (16-byte aligned; anything else is PIL2GL_EINVAL, also before any device call).  poly_fma_dev only
+ * ENQUEUES one kernel on the caller's stream: the term list travels as kernel arguments, there is no copy, no readback and no working
+ * buffer.  poly_degree_dev enqueues and BLOCKS for the 8-byte readback, as pil2gl_bn128_first_nonzero_row_dev does.  The host forms
+ * stage every column up to its last element through device copies (columns whose ranges meet as one range). */
+int pil2gl_bn128_poly_fma(uint64_t *acc, uint64_t nAcc, uint64_t accStride, const uint64_t *hostScale /* [4] or NULL */,
+                          const uint64_t *src, uint64_t nSrc, uint64_t srcStride,
+                          const uint64_t *hostCoefs /* [4 t] */, const uint64_t *hostExps /* [t] */, uint32_t t);
+int pil2gl_bn128_poly_fma_dev(uint64_t *acc, uint64_t nAcc, uint64_t accStride, const uint64_t *hostScale /* [4] or NULL */,
+                              const uint64_t *src, uint64_t nSrc, uint64_t srcStride,
+                              const uint64_t *hostCoefs /* [4 t] */, const uint64_t *hostExps /* [t] */, uint32_t t, void *stream);
+int pil2gl_bn128_poly_degree(const uint64_t *src, uint64_t n, uint64_t stride, uint64_t *degree);
+int pil2gl_bn128_poly_degree_dev(const uint64_t *src, uint64_t n, uint64_t stride, uint64_t *degree, void *stream);
+
 /* ---- BN254 Fr grand product, grand sum and batch inverse: the gprod / gsum hints over curve.Fr (csrc/bn_scan.hip) -----------------
  * What resolves the hints of a fflonk stage with a permutation, connection or lookup argument (src/prover/hints_helpers.js:92-113):
  * calculateZ and calculateS of src/helpers/polutils.js:132-164 with F = curve.Fr, each one F.batchInverse and a serial walk of n products.

@@ -262,6 +262,21 @@ FN(Bn128PolyEvalDev) {   // (dSrc, n, stride, points BigUint64Array(4 * nPoints)
     P2(env, pil2gl_bn128_poly_eval_dev(s, n, stride, pts, (uint32_t)(len / 4), o, a.stream(5))); return mk_undefined(env);
 }
 
+// ---- BN254 Fr products with a sparse polynomial, scaled sums and the degree (shplonkjs open): device columns, host scale / terms ----
+FN(Bn128PolyFmaDev) {    // (dAcc, nAcc, accStride, scale BigUint64Array(4) | null, dSrc, nSrc, srcStride, coefs BigUint64Array(4 t), exps BigUint64Array(t)[, stream])
+    Args a(env, info); uint64_t *acc = DP(0); uint64_t nAcc = a.u64(1), as = a.u64(2); uint64_t *scale = a.is_nullish(3) ? nullptr : a.arr(3, 4);
+    uint64_t *src = DP(4); uint64_t nSrc = a.u64(5), ss = a.u64(6), nc = 0, ne = 0; uint64_t *coefs = a.arr(7, 0, &nc), *exps = a.arr(8, 0, &ne);
+    if (a.ok && (nc != 4 * ne || ne > 0xFFFFFFFFull)) a.fail("coefs must hold 4 words per exponent");
+    if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_poly_fma_dev(acc, nAcc, as, scale, src, nSrc, ss, coefs, exps, (uint32_t)ne, a.stream(9))); return mk_undefined(env);
+}
+FN(Bn128PolyDegreeDev) { // (dSrc, n, stride[, stream]) -> the degree as a BigInt, 2^64-1 for the zero polynomial
+    Args a(env, info); uint64_t *s = DP(0); uint64_t n = a.u64(1), stride = a.u64(2);
+    if (!a.ok) return nullptr;
+    uint64_t deg = UINT64_MAX;
+    P2(env, pil2gl_bn128_poly_degree_dev(s, n, stride, &deg, a.stream(3))); return mk_bigint(env, deg);
+}
+
 // ---- BN254 Fr batch inverse, grand product and grand sum (the gprod / gsum hints over curve.Fr): device columns, each with its stride ----
 FN(Bn128BatchInverseDev) {   // (dSrc, srcStride, n, dDst, dstStride[, stream])
     Args a(env, info); uint64_t *s = DP(0); uint64_t ss = a.u64(1), n = a.u64(2); uint64_t *d = DP(3); uint64_t ds = a.u64(4);
@@ -637,6 +652,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128FftDev", Bn128FftDev }, { "bn128IfftDev", Bn128IfftDev }, { "bn128InterpolateDev", Bn128InterpolateDev },
         { "bn128G1MsmDev", Bn128G1MsmDev }, { "bn128EvalProgramDev", Bn128EvalProgramDev }, { "bn128FirstNonzeroRowDev", Bn128FirstNonzeroRowDev },
         { "bn128PolyDivDev", Bn128PolyDivDev }, { "bn128PolyEvalDev", Bn128PolyEvalDev },
+        { "bn128PolyFmaDev", Bn128PolyFmaDev }, { "bn128PolyDegreeDev", Bn128PolyDegreeDev },
         { "bn128BatchInverseDev", Bn128BatchInverseDev }, { "bn128GprodDev", Bn128GprodDev }, { "bn128GsumDev", Bn128GsumDev },
         { "bn128H1h2Dev", Bn128H1h2Dev },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },

@@ -184,6 +184,10 @@ SIGNATURES = {
     "pil2gl_bn128_poly_eval": (_I, [vp, _U64, _U64, vp, _U32, vp]),
     "pil2gl_bn128_poly_eval_dev": (_I, [vp, _U64, _U64, vp, _U32, vp, vp]),
     "pil2gl_debug_bn128_poly_plan": (_I, [_U64, _U64, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_bn128_poly_fma": (_I, [vp, _U64, _U64, vp, vp, _U64, _U64, vp, vp, _U32]),
+    "pil2gl_bn128_poly_fma_dev": (_I, [vp, _U64, _U64, vp, vp, _U64, _U64, vp, vp, _U32, vp]),
+    "pil2gl_bn128_poly_degree": (_I, [vp, _U64, _U64, C.POINTER(_U64)]),
+    "pil2gl_bn128_poly_degree_dev": (_I, [vp, _U64, _U64, C.POINTER(_U64), vp]),
     "pil2gl_bn128_batch_inverse": (_I, [vp, _U64, _U64, vp, _U64]),
     "pil2gl_bn128_batch_inverse_dev": (_I, [vp, _U64, _U64, vp, _U64, vp]),
     "pil2gl_bn128_gprod": (_I, [vp, _U64, vp, _U64, _U64, vp, _U64]),

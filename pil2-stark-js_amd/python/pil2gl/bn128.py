@@ -8,6 +8,7 @@
   encode_program / eval_program / first_nonzero_row
                                   <-> src/prover/prover_helpers.js:31-259 calculateExps over ctx.F = curve.Fr (Montgomery words in and out)
   poly_div / poly_eval / poly_plan <-> Polynomial.divZh / divByXNSubValue / evaluate as fflonk_prover_helpers.js:147-148, :212 use them
+  poly_fma / poly_degree          <-> Polynomial.add / sub / mulScalar / byXSubValue / byXNSubValue / degree as shplonkjs open (:212) uses them
   batch_inverse / gprod / gsum / scan_plan
                                   <-> F.batchInverse, calculateZ, calculateS of src/helpers/polutils.js:132-164 over curve.Fr, as
                                       hints_helpers.js:92-113 resolves gprod / gsum hints (Montgomery words in and out)
@@ -352,6 +353,46 @@ def poly_plan(n, k):
     d = dict(zip(("L", "S", "levels", "threads", "form"), (int(v) for v in info)))
     d["scratchBytes"] = int(nbytes.value)
     return d
+
+
+# ---- products with a sparse polynomial, scaled sums, degree: Polynomial.add / sub / mulScalar / byXSubValue / byXNSubValue / degree ----
+def poly_fma(acc, src, coefs, exps, scale=None, *, n_acc, n_src, acc_stride=1, src_stride=1):
+    """acc[i] <- scale acc[i] + sum_j coefs[j] src[i - exps[j]] for i < n_acc, src zero outside [0, n_src): the product of src by the
+    sparse polynomial sum_j coefs[j] x^exps[j], added to the scaled accumulator (shplonkjs open, fflonk_prover_helpers.js:212).  acc and
+    src are columns (element i at word 4*i*stride, Montgomery words; numpy arrays or device tensors of one kind; src may be None with
+    n_src = 0); coefs = (t, 4) Montgomery words and exps = t strictly increasing exponents, 1 <= t <= 64, on the host; scale = 4
+    Montgomery words on the host, or None: then acc is written and never read.  n_src + exps[-1] <= n_acc.  acc must share no element
+    with src, except as the same column when exps == [0].  -> acc"""
+    if src is not None and _is_dev(acc) != _is_dev(src):
+        raise Pil2glError("mixing host and device buffers in one call")
+    if acc_stride < 1 or src_stride < 1:
+        raise Pil2glError("stride must be at least 1")
+    _check_len(acc, ((n_acc - 1) * acc_stride + 1) * 4 if n_acc else 0, "acc")
+    if src is None and n_src:
+        raise Pil2glError("src is None with n_src = %d" % n_src)
+    _check_len(src, ((n_src - 1) * src_stride + 1) * 4 if n_src else 0, "src")
+    m = np.ascontiguousarray(coefs, dtype=np.uint64).reshape(-1, 4)
+    e = np.ascontiguousarray(exps, dtype=np.uint64).reshape(-1)
+    if m.shape[0] != e.shape[0]:
+        raise Pil2glError("%d coefficients for %d exponents" % (m.shape[0], e.shape[0]))
+    s = None if scale is None else _host_elems(scale, "scale", 1)
+    args = (_ptr(acc), n_acc, acc_stride, _ptr(s), _ptr(src), n_src, src_stride, _ptr(m), _ptr(e), e.shape[0])
+    if _is_dev(acc):
+        call("pil2gl_bn128_poly_fma_dev", *args, _stream())
+    else:
+        call("pil2gl_bn128_poly_fma", *args)
+    return acc
+
+
+def poly_degree(words, n=None, stride=1):
+    """Polynomial.degree: the largest i whose element (at word 4*i*stride) is not zero, or None for the zero polynomial and for n = 0"""
+    n = _column(words, n, stride, "words")
+    d = C.c_uint64()
+    if _is_dev(words):
+        call("pil2gl_bn128_poly_degree_dev", _ptr(words), n, stride, C.byref(d), _stream())
+    else:
+        call("pil2gl_bn128_poly_degree", _ptr(words), n, stride, C.byref(d))
+    return None if d.value == (1 << 64) - 1 else int(d.value)
 
 
 # ---- gprod / gsum hints over Fr: calculateZ, calculateS and F.batchInverse (polutils.js:132-164, hints_helpers.js:92-113) ----
