@@ -1,0 +1,23 @@
+// A BN254 element between memory and registers, gfx950: 32 bytes travel as two 16-byte halves and are worked on as eight 32-bit limbs
+// (bn_field.cuh, bn_fq.cuh).  The one copy of that move for every unit that takes elements from global memory; bn_ntt.hip's LDS tile
+// accessors and bn_expr.hip's typed temporaries are indexed differently and stay where they are.
+#pragma once
+#include "bn_field.cuh"
+
+namespace bn {
+
+__device__ __forceinline__ void unpack(const uint4 &a, const uint4 &b, u32 x[8]) {
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+}
+__device__ __forceinline__ void ld_elem(const uint4 *p, u32 x[8]) {
+    const uint4 a = p[0], b = p[1];
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+}
+__device__ __forceinline__ void st_elem(uint4 *p, const u32 x[8]) {
+    p[0] = make_uint4(x[0], x[1], x[2], x[3]); p[1] = make_uint4(x[4], x[5], x[6], x[7]);
+}
+// all eight 32-bit words decide
+__device__ __forceinline__ bool is_zero(const u32 x[8]) { return (x[0] | x[1] | x[2] | x[3] | x[4] | x[5] | x[6] | x[7]) == 0; }
+__device__ __forceinline__ bool is_zero(const uint4 &a, const uint4 &b) { return ((a.x | a.y | a.z | a.w) | (b.x | b.y | b.z | b.w)) == 0; }
+
+}  // namespace bn

@@ -11,7 +11,7 @@
 // 256, 128 or 64 lanes, in a global working buffer (SCR_BN_EXPR) otherwise.  bnx::geometry (bn_expr_plan.h) decides, and
 // pil2gl_debug_bn128_plan_program reports what it decided.
 #include "common.h"
-#include "bn_field.cuh"
+#include "bn_elem.cuh"
 #include "bn_expr_plan.h"
 #include <vector>
 #include <string.h>
@@ -33,9 +33,6 @@ struct DevCtx {
 
 constexpr u64 HEADER_WORDS = 8;                      // SCR_BN_EXPR starts with the first-non-zero search's cell
 
-__device__ __forceinline__ void unpack(const uint4 &a, const uint4 &b, u32 x[8]) {
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-}
 // element (row + rowOff) mod 2^nBits, column index of a section   (prover_helpers.js:220-233)
 __device__ __forceinline__ uint4 *cell(const DevRef &r, const DevCtx &c, u64 row) {
     const u64 rr = (row + (u64)(int64_t)r.rowOff) & ((1ull << c.nBits) - 1);
@@ -57,8 +54,7 @@ __device__ __forceinline__ void load_ref(const DevRef &r, const DevCtx &c, u64 r
         return;
     }
     const uint4 *p = r.kind == GLX_SCALAR ? c.scalars + 2 * (size_t)r.index : cell(r, c, row);
-    const uint4 a = p[0], b = p[1];
-    unpack(a, b, x);
+    bn::ld_elem(p, x);
 }
 
 template <bool LDS_TMP>
@@ -81,8 +77,7 @@ __global__ void __launch_bounds__(256) bn_eval_kernel(DevCtx c, uint4 *gtmp) {
                 const size_t e = (size_t)(2 * op.dest.index) * stride;
                 T[e] = (v4u){ a[0], a[1], a[2], a[3] }; T[e + stride] = (v4u){ a[4], a[5], a[6], a[7] };
             } else {
-                uint4 *q = cell(op.dest, c, row);
-                q[0] = make_uint4(a[0], a[1], a[2], a[3]); q[1] = make_uint4(a[4], a[5], a[6], a[7]);
+                bn::st_elem(cell(op.dest, c, row), a);
             }
         }
     }
@@ -95,7 +90,7 @@ __global__ void __launch_bounds__(256) bn_first_nonzero_kernel(const uint4 *__re
     bool nz = false;
     if (r < last) {
         const uint4 a = col[2 * r * width], b = col[2 * r * width + 1];
-        nz = ((a.x | a.y | a.z | a.w) | (b.x | b.y | b.z | b.w)) != 0;        // all eight 32-bit words decide
+        nz = !bn::is_zero(a, b);
     }
     const u64 mask = __ballot(nz);
     if (mask && (threadIdx.x & 63) == 0) atomicMin(best, (unsigned long long)(r + __builtin_ctzll(mask)));

@@ -24,7 +24,7 @@
 //
 // Every probe loop runs at most `cap` times whatever the data; the table has at least 2 n slots for at most n values, so an empty slot
 // ends every unsuccessful probe long before.  Memory safety rests on no multiple: a lane with i >= n returns or idles at the barriers.
-#include "common.h"
+#include "bn_column_stage.h"
 #include "bn_h1h2_plan.h"
 
 using namespace pil2gl;
@@ -217,24 +217,18 @@ int run(const Cols &c, hipStream_t st, u64 *missing) {
     return PIL2GL_OK;
 }
 
-int check_column(const void *p, u64 n, u64 stride, const char *what) {
-    if (const char *m = bnh1h2::check_stride(stride)) return fail(PIL2GL_EINVAL, "%s stride = %llu: %s", what, (unsigned long long)stride, m);
-    if (n && !p) return fail(PIL2GL_EINVAL, "null buffer (%s)", what);
-    return PIL2GL_OK;
-}
 int check(const Cols &c) {
-    if (const char *m = bnh1h2::check_size(c.n)) return fail(PIL2GL_EINVAL, "n = %llu: %s", (unsigned long long)c.n, m);
     P2_TRY(check_column(c.f, c.n, c.fs, "f"));
     P2_TRY(check_column(c.t, c.n, c.ts, "t"));
     P2_TRY(check_column(c.h1, c.n, c.h1s, "h1"));
     P2_TRY(check_column(c.h2, c.n, c.h2s, "h2"));
-    const bool ok = bnh1h2::apart(c.f, c.fs, c.h1, c.h1s, c.n) && bnh1h2::apart(c.t, c.ts, c.h1, c.h1s, c.n) &&
-                    bnh1h2::apart(c.f, c.fs, c.h2, c.h2s, c.n) && bnh1h2::apart(c.t, c.ts, c.h2, c.h2s, c.n) &&
-                    bnh1h2::apart(c.h1, c.h1s, c.h2, c.h2s, c.n);
+    // an output against an input or the other output: they must share no element (bn_column.h: apart, or two columns of one section)
+    auto apart = [&](const void *a, u64 as, const void *b, u64 bs) { return bncol::relation((uintptr_t)a, as, (uintptr_t)b, bs, c.n) == bncol::APART; };
+    const bool ok = apart(c.f, c.fs, c.h1, c.h1s) && apart(c.t, c.ts, c.h1, c.h1s) && apart(c.f, c.fs, c.h2, c.h2s) &&
+                    apart(c.t, c.ts, c.h2, c.h2s) && apart(c.h1, c.h1s, c.h2, c.h2s);
     if (!ok) return fail(PIL2GL_EINVAL, "an output overlaps an input or the other output (only columns of one section may interleave)");
     return PIL2GL_OK;
 }
-u64 span_words(u64 n, u64 stride) { return ((n - 1) * stride + 1) * 4; }     // up to the last element
 
 }  // namespace
 
@@ -242,7 +236,7 @@ extern "C" {
 
 int pil2gl_debug_bn128_h1h2_plan(uint64_t n, uint32_t *outInfo, uint64_t *scratchBytes) {
     if (!outInfo || !scratchBytes) return fail(PIL2GL_EINVAL, "null argument");
-    if (const char *m = bnh1h2::check_size(n)) return fail(PIL2GL_EINVAL, "n = %llu: %s", (unsigned long long)n, m);
+    if (const char *m = bncol::check_size(n)) return fail(PIL2GL_EINVAL, "n = %llu: %s", (unsigned long long)n, m);
     const bnh1h2::Plan p = bnh1h2::plan(n);
     outInfo[0] = (uint32_t)p.cap; outInfo[1] = THREADS; outInfo[2] = SCAN_CHUNK; outInfo[3] = p.scanBlocks;
     outInfo[4] = EXPAND_ROWS; outInfo[5] = p.expandBlocks;
@@ -257,7 +251,7 @@ int pil2gl_bn128_h1h2_dev(const uint64_t *f, uint64_t fStride, const uint64_t *t
     const Cols c{ f, fStride, t, tStride, n, h1, h1Stride, h2, h2Stride };
     P2_TRY(check(c));
     if (n == 0) return PIL2GL_OK;
-    if (((uintptr_t)f | (uintptr_t)t | (uintptr_t)h1 | (uintptr_t)h2) & 15) return fail(PIL2GL_EINVAL, "device columns must be 16-byte aligned");
+    P2_TRY(check_aligned16({ f, t, h1, h2 }));
     P2_TRY(ensure_init());
     const int rc = run(c, as_stream(stream), &miss);
     if (missingRow) *missingRow = miss;
@@ -271,32 +265,15 @@ int pil2gl_bn128_h1h2(const uint64_t *f, uint64_t fStride, const uint64_t *t, ui
     const Cols c{ f, fStride, t, tStride, n, h1, h1Stride, h2, h2Stride };
     P2_TRY(check(c));
     if (n == 0) return PIL2GL_OK;
-    // every column up to its last element; a strided output keeps what lies between its elements, so those words travel too.  Two
-    // output columns of one section are ONE staged range, so that neither copy back undoes the other
-    const uint64_t fw = span_words(n, fStride), tw = span_words(n, tStride), w1 = span_words(n, h1Stride), w2 = span_words(n, h2Stride);
-    const uintptr_t a1 = (uintptr_t)h1, a2 = (uintptr_t)h2, e1 = a1 + 8 * w1, e2 = a2 + 8 * w2;      // as integers, like bnscan::relation
-    const bool together = !(e1 <= a2 || e2 <= a1);                           // the outputs' ranges meet: columns of one section
-    uint64_t *lo = a1 < a2 ? h1 : h2;
-    const uint64_t ow = together ? ((e1 > e2 ? e1 : e2) - (a1 < a2 ? a1 : a2)) / 8 : 0;
-    const uint64_t off1 = (a1 - (uintptr_t)lo) / 8, off2 = (a2 - (uintptr_t)lo) / 8;                   // together: where each column starts in the range
-    Stage s(fw + tw + (together ? ow : w1 + w2));
+    // two outputs of one section are one staged range, so that neither copy back undoes the other (bn_column.h)
+    const bncol::Col cols[4] = { { (uintptr_t)f, n, fStride, true, false }, { (uintptr_t)t, n, tStride, true, false },
+                                 { (uintptr_t)h1, n, h1Stride, false, true }, { (uintptr_t)h2, n, h2Stride, false, true } };
+    ColumnStage s(cols, 4);
     P2_TRY(s.rc());
-    const uint64_t *dF = s.put(f, fw), *dT = s.put(t, tw);
-    uint64_t *d1, *d2;
-    if (together) {
-        uint64_t *dO = const_cast<uint64_t *>(s.put(lo, ow));
-        d1 = dO ? dO + off1 : nullptr; d2 = dO ? dO + off2 : nullptr;
-    } else {
-        d1 = h1Stride == 1 ? s.take(w1) : const_cast<uint64_t *>(s.put(h1, w1));
-        d2 = h2Stride == 1 ? s.take(w2) : const_cast<uint64_t *>(s.put(h2, w2));
-    }
-    P2_TRY(s.rc());
-    const int rc = run(Cols{ dF, fStride, dT, tStride, n, d1, h1Stride, d2, h2Stride }, 0, &miss);
+    const int rc = run(Cols{ s.dev(0), fStride, s.dev(1), tStride, n, s.dev(2), h1Stride, s.dev(3), h2Stride }, 0, &miss);
     if (missingRow) *missingRow = miss;
     P2_TRY(rc);
-    if (together) return s.get(lo, off1 ? d2 : d1, ow);
-    P2_TRY(s.get(h1, d1, w1));
-    return s.get(h2, d2, w2);
+    return s.copy_back();
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Host-only half of the BN254 Fr plookup hint (bn_h1h2.hip): the one place that decides the table capacity, the launches' geometry and
-// the layout of the working buffer from n, and that refuses what the entries refuse.  No HIP header: it builds with the plain C++
-// compiler (tests/bn_h1h2_dump.cpp runs it under the sanitizers).
+// the layout of the working buffer from n.  No HIP header: it builds with the plain C++ compiler (tests/bn_h1h2_dump.cpp runs it under
+// the sanitizers).  What the entries refuse about a column is bn_column.h's.
 //
 // The working buffer, in 32-bit words, every part starting on a multiple of 4 words (16 bytes):
 //   table    cap slots, cap the power of two with 2 n <= cap < 4 n (n = 1: 2): an index into t, or EMPTY
@@ -13,11 +13,9 @@
 // would take 8 GiB.
 #pragma once
 #include <stdint.h>
-#include "bn_scan_plan.h"                            // the limits on n and stride, and the relation of two columns: one rule for every Fr hint
 
 namespace bnh1h2 {
 
-constexpr uint64_t MAX_N = bnscan::MAX_N;            // 2^28
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 constexpr uint32_t THREADS = 256;
 constexpr uint32_t SCAN_ITEMS = 8;                   // groups per lane of the local scan
@@ -51,13 +49,5 @@ inline Plan plan(uint64_t n) {
 }
 
 inline uint64_t scratch_bytes(const Plan &p) { return 4 * p.words; }
-
-// ---- the refusals, before any device call: 0, or a message for PIL2GL_EINVAL ----
-inline const char *check_size(uint64_t n) { return bnscan::check_size(n); }
-inline const char *check_stride(uint64_t stride) { return bnscan::check_stride(stride); }
-// an output against an input or the other output: they must share no element (bn_scan_plan.h: apart, or two columns of one section)
-inline bool apart(const void *a, uint64_t aStride, const void *b, uint64_t bStride, uint64_t n) {
-    return bnscan::relation((uintptr_t)a, aStride, (uintptr_t)b, bStride, n) == bnscan::APART;
-}
 
 }  // namespace bnh1h2

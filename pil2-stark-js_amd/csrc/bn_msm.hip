@@ -23,10 +23,12 @@
 #include "bn_params.h"
 #include "bn_msm_recode.h"
 #include "bn_g1.cuh"
+#include "bn_elem.cuh"
 
 using namespace pil2gl;
 using bn::u32;
 using bn::G1X;
+using bn::unpack;
 
 namespace {
 
@@ -42,9 +44,6 @@ struct PassParams {
     uint4 *buckets;                                  // the pass's first bucket
 };
 
-__device__ __forceinline__ void unpack(const uint4 &a, const uint4 &b, u32 x[8]) {
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-}
 __device__ __forceinline__ void ld_point(const uint4 *p, G1X &v) {
     unpack(p[0], p[1], v.x); unpack(p[2], p[3], v.y); unpack(p[4], p[5], v.zz); unpack(p[6], p[7], v.zzz);
 }

@@ -50,6 +50,17 @@ bool h_is_zero(const U256 &a) { return !(a.w[0] | a.w[1] | a.w[2] | a.w[3]); }
 
 U256 h_to_mont(const U256 &a) { return h_mont(a, HR2); }
 U256 h_from_mont(const U256 &a) { U256 one = { { 1, 0, 0, 0 } }; return h_mont(a, one); }
+U256 bn_mont_mul(const U256 &a, const U256 &b) { return h_mont(a, b); }
+const U256 &bn_mont_one() { static const U256 v = h_to_mont(U256{ { 1, 0, 0, 0 } }); return v; }
+const U256 &bn_mont_neg_one() { static const U256 v = h_submod(U256{ { 0, 0, 0, 0 } }, bn_mont_one()); return v; }
+U256 bn_mont_pow(U256 base, uint64_t e) {
+    U256 r = bn_mont_one();
+    for (; e; e >>= 1) {
+        if (e & 1) r = h_mont(r, base);
+        base = h_mont(base, base);
+    }
+    return r;
+}
 
 namespace {
 
@@ -351,10 +362,8 @@ int bn_build_params(int t, BnHostParams &out) {
 }
 
 // ------------------------------------------------------------------------------------------ the Fr transforms
-U256 bn_mont_mul(const U256 &a, const U256 &b) { return h_mont(a, b); }
-
 void bn_powers(const U256 &g, size_t n, U256 *out) {
-    U256 acc = h_to_mont(U256{ { 1, 0, 0, 0 } });
+    U256 acc = bn_mont_one();
     for (size_t i = 0; i < n; i++) { out[i] = acc; acc = h_mont(acc, g); }
 }
 

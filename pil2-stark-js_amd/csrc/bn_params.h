@@ -11,6 +11,12 @@ namespace bnp {
 struct U256 { uint64_t w[4]; };
 U256 h_to_mont(const U256 &a);                       // a 2^256 mod r
 U256 h_from_mont(const U256 &a);                     // a / 2^256 mod r
+U256 bn_mont_mul(const U256 &a, const U256 &b);
+const U256 &bn_mont_one();                           // 1 in Montgomery form
+const U256 &bn_mont_neg_one();                       // r - 1 in Montgomery form
+U256 bn_mont_pow(U256 base, uint64_t e);             // base^e, Montgomery form in and out
+// four 64-bit words as the eight 32-bit limbs the kernels work on
+inline void bn_limbs(const uint64_t w[4], uint32_t out[8]) { for (int i = 0; i < 4; i++) { out[2 * i] = (uint32_t)w[i]; out[2 * i + 1] = (uint32_t)(w[i] >> 32); } }
 
 constexpr size_t BN_ABSENT = (size_t)-1;             // the offset of a region this width does not have
 
@@ -45,7 +51,6 @@ struct BnNttConsts { U256 w[29], wi[29], ninv[29]; };
 const BnNttConsts &bn_ntt_consts();
 // out[i] = g^i, i < n (Montgomery form in and out)
 void bn_powers(const U256 &g, size_t n, U256 *out);
-U256 bn_mont_mul(const U256 &a, const U256 &b);
 // The sweeps of a transform of 2^nBits rows: layers[i] butterfly layers in sweep i, as even as ceil(nBits / BN_NTT_KMAX) sweeps allow (the
 // first ones take the odd layers).  A sweep of K layers holds 2^K rows x min(nPols, BN_NTT_TILE_ELEMS >> K) columns.  Returns the number of
 // sweeps (0 for nBits = 0), -1 for nBits > BN_NTT_MAX_BITS.  layers: room for BN_NTT_MAX_SWEEPS.

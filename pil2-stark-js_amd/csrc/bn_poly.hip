@@ -29,13 +29,15 @@
 //
 // Memory safety does not rest on n, k and L dividing each other: a lane's links are [s L, min((s + 1) L, links of chain j)), every
 // element index is j + m k with m below the chain's link count, and a carry is read only for s + 1 < S.
-#include "common.h"
-#include "bn_field.cuh"
+#include "bn_column_stage.h"
+#include "bn_elem.cuh"
 #include "bn_params.h"
 #include "bn_poly_plan.h"
 
 using namespace pil2gl;
 using bn::u32;
+using bn::unpack;
+using bn::st_elem;
 
 namespace {
 
@@ -48,13 +50,6 @@ struct LevelArgs {
     u64 srcPitch, dstPitch;                          // per point (grid.y), in 16-byte halves
     u32 betaPitch;                                   // per point, in elements
 };
-
-__device__ __forceinline__ void unpack(const uint4 &a, const uint4 &b, u32 x[8]) {
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-}
-__device__ __forceinline__ void st_elem(uint4 *p, const u32 x[8]) {
-    p[0] = make_uint4(x[0], x[1], x[2], x[3]); p[1] = make_uint4(x[4], x[5], x[6], x[7]);
-}
 
 // STORE = false: reduce (dst[t] = the segment's value, dense).  STORE = true: every link of the segment to dst, same addressing as src.
 template <bool STORE>
@@ -101,16 +96,6 @@ __global__ void __launch_bounds__(bnpoly::THREADS) bn_poly_kernel(LevelArgs a) {
     if (!STORE) st_elem(dst + 2 * t, x);
 }
 
-// base^e in Montgomery form
-bnp::U256 h_pow(bnp::U256 base, u64 e) {
-    bnp::U256 r = bnp::h_to_mont(bnp::U256{ { 1, 0, 0, 0 } });
-    for (; e; e >>= 1) {
-        if (e & 1) r = bnp::bn_mont_mul(r, base);
-        base = bnp::bn_mont_mul(base, base);
-    }
-    return r;
-}
-
 // the multipliers of every level for nPoints values of beta, [point][level] at the head of the working buffer
 void level_powers(const bnpoly::Plan &p, const u64 *hostBeta, u32 nPoints, bnp::U256 *out) {
     for (u32 q = 0; q < nPoints; q++) {
@@ -118,7 +103,7 @@ void level_powers(const bnpoly::Plan &p, const u64 *hostBeta, u32 nPoints, bnp::
         for (int i = 0; i < 4; i++) b.w[i] = hostBeta[4 * q + i];
         for (u32 i = 0; i < p.nLevels; i++) {
             out[(size_t)q * bnpoly::MAX_LEVELS + i] = b;
-            if (i + 1 < p.nLevels) b = h_pow(b, p.lv[i].L);
+            if (i + 1 < p.nLevels) b = bnp::bn_mont_pow(b, p.lv[i].L);
         }
     }
 }
@@ -193,20 +178,14 @@ int eval_launch(const u64 *src, u64 n, u64 stride, const u64 *hostPoints, u32 nP
     return PIL2GL_OK;
 }
 
-int check_common(const void *src, u64 n, u64 stride) {
-    if (n > bnpoly::MAX_N) return fail(PIL2GL_EINVAL, "n = %llu: at most 2^28 coefficients", (unsigned long long)n);
-    if (stride == 0 || stride >> 32) return fail(PIL2GL_EINVAL, "stride = %llu: 1 <= stride < 2^32", (unsigned long long)stride);
-    if (n && !src) return fail(PIL2GL_EINVAL, "null buffer");
-    return PIL2GL_OK;
-}
 int check_div(const u64 *src, u64 n, u64 stride, u64 k, const u64 *hostBeta, const u64 *dst) {
-    P2_TRY(check_common(src, n, stride));
-    if (k == 0 || k > bnpoly::MAX_N) return fail(PIL2GL_EINVAL, "k = %llu: 1 <= k <= 2^28", (unsigned long long)k);
+    P2_TRY(check_column(src, n, stride, "src"));
+    if (k == 0 || k > bncol::MAX_N) return fail(PIL2GL_EINVAL, "k = %llu: 1 <= k <= 2^28", (unsigned long long)k);
     if (!hostBeta || (n && !dst)) return fail(PIL2GL_EINVAL, "null buffer");
     return PIL2GL_OK;
 }
 int check_eval(const u64 *src, u64 n, u64 stride, const u64 *hostPoints, u32 nPoints, const u64 *out) {
-    P2_TRY(check_common(src, n, stride));
+    P2_TRY(check_column(src, n, stride, "src"));
     if (nPoints == 0 || nPoints > bnpoly::MAX_POINTS) return fail(PIL2GL_EINVAL, "nPoints = %u: 1 <= nPoints <= %u", nPoints, bnpoly::MAX_POINTS);
     if (!hostPoints || !out) return fail(PIL2GL_EINVAL, "null buffer");
     return PIL2GL_OK;
@@ -218,8 +197,8 @@ extern "C" {
 
 int pil2gl_debug_bn128_poly_plan(uint64_t n, uint64_t k, uint32_t *outInfo, uint64_t *scratchBytes) {
     if (!outInfo || !scratchBytes) return fail(PIL2GL_EINVAL, "null argument");
-    if (n > bnpoly::MAX_N) return fail(PIL2GL_EINVAL, "n = %llu: at most 2^28 coefficients", (unsigned long long)n);
-    if (k == 0 || k > bnpoly::MAX_N) return fail(PIL2GL_EINVAL, "k = %llu: 1 <= k <= 2^28", (unsigned long long)k);
+    if (const char *m = bncol::check_size(n)) return fail(PIL2GL_EINVAL, "n = %llu: %s", (unsigned long long)n, m);
+    if (k == 0 || k > bncol::MAX_N) return fail(PIL2GL_EINVAL, "k = %llu: 1 <= k <= 2^28", (unsigned long long)k);
     const bnpoly::Plan p = bnpoly::plan(n, k);
     outInfo[0] = p.lv[0].L; outInfo[1] = (uint32_t)p.lv[0].S; outInfo[2] = p.nLevels - 1; outInfo[3] = bnpoly::THREADS;
     outInfo[4] = p.lv[0].S > 1 ? 1 : 0;
@@ -230,43 +209,37 @@ int pil2gl_debug_bn128_poly_plan(uint64_t n, uint64_t k, uint32_t *outInfo, uint
 int pil2gl_bn128_poly_div_xk_sub_dev(const uint64_t *src, uint64_t n, uint64_t stride, uint64_t k, const uint64_t hostBeta[4], uint64_t *dst, void *stream) {
     P2_TRY(check_div(src, n, stride, k, hostBeta, dst));
     P2_TRY(ensure_init());
-    if (((uintptr_t)src | (uintptr_t)dst) & 15) return fail(PIL2GL_EINVAL, "src and dst must be 16-byte aligned");
+    P2_TRY(check_aligned16({ src, dst }));
     return div_launch(src, n, stride, k, hostBeta, dst, as_stream(stream));
 }
 
 int pil2gl_bn128_poly_div_xk_sub(const uint64_t *src, uint64_t n, uint64_t stride, uint64_t k, const uint64_t hostBeta[4], uint64_t *dst) {
     P2_TRY(check_div(src, n, stride, k, hostBeta, dst));
     if (n == 0) return PIL2GL_OK;
-    const uint64_t words = ((n - 1) * stride + 1) * 4;                     // up to the last element
-    const bool inPlace = dst == src;
-    Stage s(inPlace ? words : 2 * words);
+    const bncol::Col cols[2] = { { (uintptr_t)src, n, stride, true, false }, { (uintptr_t)dst, n, stride, false, true } };
+    ColumnStage s(cols, 2);                          // dst == src: one copy serves both (bn_column.h)
     P2_TRY(s.rc());
-    const uint64_t *dSrc = s.put(src, words);
-    // a strided destination keeps what lies between its elements: those words travel too
-    uint64_t *dDst = inPlace ? const_cast<uint64_t *>(dSrc) : stride == 1 ? s.take(words) : const_cast<uint64_t *>(s.put(dst, words));
-    P2_TRY(s.rc());
-    P2_TRY(div_launch(dSrc, n, stride, k, hostBeta, dDst, 0));
-    return s.get(dst, dDst, words);
+    P2_TRY(div_launch(s.dev(0), n, stride, k, hostBeta, s.dev(1), 0));
+    return s.copy_back();
 }
 
 int pil2gl_bn128_poly_eval_dev(const uint64_t *src, uint64_t n, uint64_t stride, const uint64_t *hostPoints, uint32_t nPoints, uint64_t *out, void *stream) {
     P2_TRY(check_eval(src, n, stride, hostPoints, nPoints, out));
     P2_TRY(ensure_init());
-    if (((uintptr_t)src | (uintptr_t)out) & 15) return fail(PIL2GL_EINVAL, "src and out must be 16-byte aligned");
+    P2_TRY(check_aligned16({ src, out }));
     return eval_launch(src, n, stride, hostPoints, nPoints, out, as_stream(stream));
 }
 
 int pil2gl_bn128_poly_eval(const uint64_t *src, uint64_t n, uint64_t stride, const uint64_t *hostPoints, uint32_t nPoints, uint64_t *out) {
     P2_TRY(check_eval(src, n, stride, hostPoints, nPoints, out));
     if (n == 0) { for (uint32_t i = 0; i < 4 * nPoints; i++) out[i] = 0; return PIL2GL_OK; }
-    const uint64_t words = ((n - 1) * stride + 1) * 4;
-    Stage s(words + 4ull * nPoints);
+    const bncol::Col col{ (uintptr_t)src, n, stride, true, false };
+    ColumnStage s(&col, 1, 4ull * nPoints);          // the results are nPoints elements, no column
     P2_TRY(s.rc());
-    const uint64_t *dSrc = s.put(src, words);
-    uint64_t *dOut = s.take(4ull * nPoints);
+    uint64_t *dOut = s.stage().take(4ull * nPoints);
     P2_TRY(s.rc());
-    P2_TRY(eval_launch(dSrc, n, stride, hostPoints, nPoints, dOut, 0));
-    return s.get(out, dOut, 4ull * nPoints);
+    P2_TRY(eval_launch(s.dev(0), n, stride, hostPoints, nPoints, dOut, 0));
+    return s.stage().get(out, dOut, 4ull * nPoints);
 }
 
 }  // extern "C"

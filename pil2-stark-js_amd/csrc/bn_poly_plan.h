@@ -14,7 +14,6 @@
 
 namespace bnpoly {
 
-constexpr uint64_t MAX_N = 1ull << 28;
 constexpr uint32_t MAX_POINTS = 64;                  // evaluation points per call
 constexpr uint32_t THREADS = 256;
 constexpr uint32_t SEG_MIN = 32;                     // a chain this short is not cut; a cut one has at most ceil(M / 32) segments (L > 16)

@@ -22,19 +22,18 @@
 // Aliasing: a lane writes acc[i] only and reads acc[i] and src[i - e[j]].  With t = 1, e[0] = 0 those are the same index, so acc may be
 // the same column as src; in every other case a lane would read what another lane writes, and the entries refuse any shared element.
 // Memory safety rests on the range tests alone: i < nAcc, 0 <= i - e[j] < nSrc.
-#include "common.h"
-#include "bn_field.cuh"
+#include "bn_column_stage.h"
+#include "bn_elem.cuh"
 #include "bn_params.h"
-#include "bn_scan_plan.h"                            // the limits on n and stride, and the relation of two columns: one rule for every Fr block
 
 using namespace pil2gl;
 using bn::u32;
+using bn::unpack;
 
 namespace {
 
 constexpr u32 THREADS = 256;
 constexpr u32 MAX_TERMS = 64;
-constexpr u64 MAX_N = bnscan::MAX_N;                 // 2^28
 
 enum Scale : u32 { SCALE_NONE = 0, SCALE_ONE = 1, SCALE_MUL = 2 };      // acc never read / kept as loaded / multiplied by s
 
@@ -48,10 +47,6 @@ struct FmaArgs {
     Term term[MAX_TERMS];
 };
 static_assert(sizeof(FmaArgs) <= 4096, "the term list travels as kernel arguments");
-
-__device__ __forceinline__ void unpack(const uint4 &a, const uint4 &b, u32 x[8]) {
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-}
 
 __global__ void __launch_bounds__(THREADS) bn_poly_fma_kernel(FmaArgs a) {
     const u64 i = (u64)blockIdx.x * THREADS + threadIdx.x;
@@ -83,7 +78,7 @@ __global__ void __launch_bounds__(THREADS) bn_poly_fma_kernel(FmaArgs a) {
             bn::fr_add(x, y);
         }
     }
-    pa[0] = make_uint4(x[0], x[1], x[2], x[3]); pa[1] = make_uint4(x[4], x[5], x[6], x[7]);
+    bn::st_elem(pa, x);
 }
 
 // *best = max over the non-zero elements of (index + 1); the caller clears it to 0.  Lanes run over the column FROM THE TOP (lane g of
@@ -99,7 +94,7 @@ __global__ void __launch_bounds__(THREADS) bn_poly_degree_kernel(const uint4 *__
     if (g < n) {
         const u64 i = n - 1 - g;
         const uint4 a = col[2 * i * stride], b = col[2 * i * stride + 1];
-        nz = ((a.x | a.y | a.z | a.w) | (b.x | b.y | b.z | b.w)) != 0;        // all eight 32-bit words decide
+        nz = !bn::is_zero(a, b);
     }
     const u64 mask = __ballot(nz);
     if (mask && g == g0) atomicMax(best, (unsigned long long)(n - g0 - __builtin_ctzll(mask)));      // the lowest lane set is the highest element
@@ -113,53 +108,20 @@ struct Call {
 
 bool words_eq(const u64 *a, const bnp::U256 &b) { return a[0] == b.w[0] && a[1] == b.w[1] && a[2] == b.w[2] && a[3] == b.w[3]; }
 bool words_zero(const u64 *a) { return (a[0] | a[1] | a[2] | a[3]) == 0; }
-void to_limbs(const u64 *w, u32 out[8]) { for (int l = 0; l < 4; l++) { out[2 * l] = (u32)w[l]; out[2 * l + 1] = (u32)(w[l] >> 32); } }
-
-// 1 and r - 1 in Montgomery form (bn_params.cpp's arithmetic; r - 1 = -1, and -(1 R) = r - (R mod r))
-const bnp::U256 &mont_one() { static const bnp::U256 v = bnp::h_to_mont(bnp::U256{ { 1, 0, 0, 0 } }); return v; }
-const bnp::U256 &mont_minus_one() {
-    static const bnp::U256 v = [] {
-        const u64 r[4] = { 0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull };
-        const bnp::U256 &one = mont_one();
-        bnp::U256 d; u64 borrow = 0;
-        for (int l = 0; l < 4; l++) {
-            const u64 x = r[l] - one.w[l], y = x - borrow;
-            borrow = (r[l] < one.w[l]) | (x < borrow);
-            d.w[l] = y;
-        }
-        return d;
-    }();
-    return v;
-}
-
-// the relation of acc (nAcc elements) and src (nSrc elements) by bn_scan_plan.h's rule: byte ranges that do not meet are apart whatever
-// the strides; ranges that meet are judged by bnscan::relation, whose verdict on meeting ranges (the same column, two columns of one
-// section, anything else) does not depend on the count
-bnscan::Relation relation(const Call &c) {
-    if (c.nAcc == 0 || c.nSrc == 0) return bnscan::APART;
-    const uintptr_t a = (uintptr_t)c.acc, b = (uintptr_t)c.src;
-    const u64 aLen = 32 * ((c.nAcc - 1) * c.accStride + 1), bLen = 32 * ((c.nSrc - 1) * c.srcStride + 1);
-    if (a + aLen <= b || b + bLen <= a) return bnscan::APART;
-    return bnscan::relation(a, c.accStride, b, c.srcStride, c.nAcc);
-}
 
 int check(const Call &c) {
-    if (const char *m = bnscan::check_size(c.nAcc)) return fail(PIL2GL_EINVAL, "nAcc = %llu: %s", (unsigned long long)c.nAcc, m);
-    if (const char *m = bnscan::check_size(c.nSrc)) return fail(PIL2GL_EINVAL, "nSrc = %llu: %s", (unsigned long long)c.nSrc, m);
-    if (const char *m = bnscan::check_stride(c.accStride)) return fail(PIL2GL_EINVAL, "acc stride = %llu: %s", (unsigned long long)c.accStride, m);
-    if (const char *m = bnscan::check_stride(c.srcStride)) return fail(PIL2GL_EINVAL, "src stride = %llu: %s", (unsigned long long)c.srcStride, m);
+    P2_TRY(check_column(c.acc, c.nAcc, c.accStride, "acc"));
+    P2_TRY(check_column(c.src, c.nSrc, c.srcStride, "src"));
     if (c.t == 0 || c.t > MAX_TERMS) return fail(PIL2GL_EINVAL, "t = %u: 1 <= t <= %u terms", c.t, MAX_TERMS);
     if (!c.coefs || !c.exps) return fail(PIL2GL_EINVAL, "null buffer (hostCoefs / hostExps)");
     for (u32 j = 1; j < c.t; j++)
         if (c.exps[j] <= c.exps[j - 1]) return fail(PIL2GL_EINVAL, "exponents must be strictly increasing (e[%u] = %llu after %llu)", j, (unsigned long long)c.exps[j], (unsigned long long)c.exps[j - 1]);
     const u64 eMax = c.exps[c.t - 1];
-    if (eMax > MAX_N) return fail(PIL2GL_EINVAL, "exponent %llu: at most 2^28", (unsigned long long)eMax);
+    if (eMax > bncol::MAX_N) return fail(PIL2GL_EINVAL, "exponent %llu: at most 2^28", (unsigned long long)eMax);
     if (c.nSrc && c.nSrc + eMax > c.nAcc)
         return fail(PIL2GL_EINVAL, "the product has %llu + %llu coefficients, acc holds %llu: nothing is truncated", (unsigned long long)c.nSrc, (unsigned long long)eMax, (unsigned long long)c.nAcc);
-    if (c.nAcc && !c.acc) return fail(PIL2GL_EINVAL, "null buffer (acc)");
-    if (c.nSrc && !c.src) return fail(PIL2GL_EINVAL, "null buffer (src)");
-    const bnscan::Relation rel = relation(c);
-    if (rel == bnscan::OVERLAP || (rel == bnscan::SAME && !(c.t == 1 && c.exps[0] == 0)))
+    const bncol::Relation rel = bncol::relation((uintptr_t)c.acc, c.accStride, c.nAcc, (uintptr_t)c.src, c.srcStride, c.nSrc);
+    if (rel == bncol::OVERLAP || (rel == bncol::SAME && !(c.t == 1 && c.exps[0] == 0)))
         return fail(PIL2GL_EINVAL, "acc overlaps src (only columns of one section may interleave; the same column only with t = 1, e = 0)");
     return PIL2GL_OK;
 }
@@ -170,16 +132,16 @@ int fma_launch(const Call &c, hipStream_t st) {
     a.acc = (uint4 *)c.acc; a.src = (const uint4 *)c.src;
     a.nAcc = c.nAcc; a.nSrc = c.nSrc; a.accStride = c.accStride; a.srcStride = c.srcStride;
     if (c.scale) {
-        a.scale = words_eq(c.scale, mont_one()) ? SCALE_ONE : SCALE_MUL;
-        to_limbs(c.scale, a.s);
+        a.scale = words_eq(c.scale, bnp::bn_mont_one()) ? SCALE_ONE : SCALE_MUL;
+        bnp::bn_limbs(c.scale, a.s);
     }
     if (c.nSrc)
         for (u32 j = 0; j < c.t; j++) {              // zero coefficients are dropped here
             const u64 *m = c.coefs + 4 * j;
             if (words_zero(m)) continue;
-            if (words_eq(m, mont_one())) a.oneMask |= 1ull << a.t;
-            else if (words_eq(m, mont_minus_one())) a.negMask |= 1ull << a.t;
-            to_limbs(m, a.term[a.t].m);
+            if (words_eq(m, bnp::bn_mont_one())) a.oneMask |= 1ull << a.t;
+            else if (words_eq(m, bnp::bn_mont_neg_one())) a.negMask |= 1ull << a.t;
+            bnp::bn_limbs(m, a.term[a.t].m);
             a.term[a.t].e = c.exps[j];
             a.t++;
         }
@@ -190,10 +152,7 @@ int fma_launch(const Call &c, hipStream_t st) {
 
 int check_degree(const u64 *src, u64 n, u64 stride, const u64 *degree) {
     if (!degree) return fail(PIL2GL_EINVAL, "null buffer (degree)");
-    if (const char *m = bnscan::check_size(n)) return fail(PIL2GL_EINVAL, "n = %llu: %s", (unsigned long long)n, m);
-    if (const char *m = bnscan::check_stride(stride)) return fail(PIL2GL_EINVAL, "stride = %llu: %s", (unsigned long long)stride, m);
-    if (n && !src) return fail(PIL2GL_EINVAL, "null buffer (src)");
-    return PIL2GL_OK;
+    return check_column(src, n, stride, "src");
 }
 
 // blocks for the 8-byte readback
@@ -210,8 +169,6 @@ int degree_run(const u64 *src, u64 n, u64 stride, u64 *degree, hipStream_t st) {
     return PIL2GL_OK;
 }
 
-u64 span_words(u64 n, u64 stride) { return n ? ((n - 1) * stride + 1) * 4 : 0; }      // up to the last element
-
 }  // namespace
 
 extern "C" {
@@ -222,7 +179,7 @@ int pil2gl_bn128_poly_fma_dev(uint64_t *acc, uint64_t nAcc, uint64_t accStride, 
     const Call c{ acc, nAcc, accStride, hostScale, src, nSrc, srcStride, hostCoefs, hostExps, t };
     P2_TRY(check(c));
     if (nAcc == 0) return PIL2GL_OK;
-    if (((uintptr_t)acc | (uintptr_t)src) & 15) return fail(PIL2GL_EINVAL, "device columns must be 16-byte aligned");
+    P2_TRY(check_aligned16({ acc, src }));
     P2_TRY(ensure_init());
     return fma_launch(c, as_stream(stream));
 }
@@ -233,36 +190,20 @@ int pil2gl_bn128_poly_fma(uint64_t *acc, uint64_t nAcc, uint64_t accStride, cons
     Call c{ acc, nAcc, accStride, hostScale, src, nSrc, srcStride, hostCoefs, hostExps, t };
     P2_TRY(check(c));
     if (nAcc == 0) return PIL2GL_OK;
-    // every column up to its last element; a strided acc keeps what lies between its elements, so those words travel too.  Columns whose
-    // ranges meet (the same column, two columns of one section) are ONE staged range
-    const uint64_t aw = span_words(nAcc, accStride), sw = span_words(nSrc, srcStride);
-    const uintptr_t a0 = (uintptr_t)acc, s0 = (uintptr_t)src, a1 = a0 + 8 * aw, s1 = s0 + 8 * sw;
-    const bool together = nSrc && !(a1 <= s0 || s1 <= a0);
-    if (together) {
-        const uintptr_t lo = a0 < s0 ? a0 : s0, hi = a1 > s1 ? a1 : s1;
-        const uint64_t w = (hi - lo) / 8;
-        Stage s(w);
-        P2_TRY(s.rc());
-        uint64_t *d = const_cast<uint64_t *>(s.put((const uint64_t *)lo, w));
-        P2_TRY(s.rc());
-        c.acc = d + (a0 - lo) / 8; c.src = d + (s0 - lo) / 8;
-        P2_TRY(fma_launch(c, 0));
-        return s.get(acc, c.acc, aw);
-    }
-    Stage s(aw + sw);
+    // without a scale acc is written and never read; acc and src of one section, or the same column, are one staged range (bn_column.h)
+    const bncol::Col cols[2] = { { (uintptr_t)acc, nAcc, accStride, hostScale != nullptr, true }, { (uintptr_t)src, nSrc, srcStride, true, false } };
+    ColumnStage s(cols, 2);
     P2_TRY(s.rc());
-    c.src = s.put(src, sw);
-    c.acc = !hostScale && accStride == 1 ? s.take(aw) : const_cast<uint64_t *>(s.put(acc, aw));
-    P2_TRY(s.rc());
+    c.acc = s.dev(0); c.src = s.dev(1);
     P2_TRY(fma_launch(c, 0));
-    return s.get(acc, c.acc, aw);
+    return s.copy_back();
 }
 
 int pil2gl_bn128_poly_degree_dev(const uint64_t *src, uint64_t n, uint64_t stride, uint64_t *degree, void *stream) {
     P2_TRY(check_degree(src, n, stride, degree));
     *degree = ~0ull;
     if (n == 0) return PIL2GL_OK;
-    if ((uintptr_t)src & 15) return fail(PIL2GL_EINVAL, "the column must be 16-byte aligned");
+    P2_TRY(check_aligned16({ src }));
     P2_TRY(ensure_init());
     return degree_run(src, n, stride, degree, as_stream(stream));
 }
@@ -271,12 +212,10 @@ int pil2gl_bn128_poly_degree(const uint64_t *src, uint64_t n, uint64_t stride, u
     P2_TRY(check_degree(src, n, stride, degree));
     *degree = ~0ull;
     if (n == 0) return PIL2GL_OK;
-    const uint64_t words = span_words(n, stride);
-    Stage s(words);
+    const bncol::Col col{ (uintptr_t)src, n, stride, true, false };
+    ColumnStage s(&col, 1);
     P2_TRY(s.rc());
-    const uint64_t *d = s.put(src, words);
-    P2_TRY(s.rc());
-    return degree_run(d, n, stride, degree, 0);
+    return degree_run(s.dev(0), n, stride, degree, 0);
 }
 
 }  // extern "C"

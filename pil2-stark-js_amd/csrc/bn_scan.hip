@@ -33,13 +33,16 @@
 //
 // Memory safety does not rest on n being a multiple of anything: a lane with s >= S returns, a lane walks only [s L, min((s + 1) L, n)),
 // and an empty segment leaves the identity.
-#include "common.h"
-#include "bn_field.cuh"
+#include "bn_column_stage.h"
+#include "bn_elem.cuh"
 #include "bn_params.h"
 #include "bn_scan_plan.h"
 
 using namespace pil2gl;
 using bn::u32;
+using bn::ld_elem;
+using bn::st_elem;
+using bn::is_zero;
 
 namespace {
 
@@ -65,14 +68,6 @@ struct ScanArgs {
     Elem ident;                                      // 0, or 1 in Montgomery form
 };
 
-__device__ __forceinline__ void ld_elem(const uint4 *p, u32 x[8]) {
-    const uint4 a = p[0], b = p[1];
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-}
-__device__ __forceinline__ void st_elem(uint4 *p, const u32 x[8]) {
-    p[0] = make_uint4(x[0], x[1], x[2], x[3]); p[1] = make_uint4(x[4], x[5], x[6], x[7]);
-}
-__device__ __forceinline__ bool is_zero(const u32 x[8]) { return (x[0] | x[1] | x[2] | x[3] | x[4] | x[5] | x[6] | x[7]) == 0; }
 __device__ __forceinline__ void set(u32 x[8], const Elem &e) {
 #pragma unroll
     for (int i = 0; i < 8; i++) x[i] = e.w[i];
@@ -188,13 +183,6 @@ __global__ void __launch_bounds__(bnscan::THREADS) bn_scan_store_kernel(ScanArgs
     }
 }
 
-Elem to_elem(const u64 w[4]) {
-    Elem e;
-    for (int i = 0; i < 4; i++) { e.w[2 * i] = (u32)w[i]; e.w[2 * i + 1] = (u32)(w[i] >> 32); }
-    return e;
-}
-Elem mont_one() { return to_elem(bnp::h_to_mont(bnp::U256{ { 1, 0, 0, 0 } }).w); }
-
 unsigned blocks(u64 lanes) { return (unsigned)((lanes + bnscan::THREADS - 1) / bnscan::THREADS); }
 
 // y[i] = mode(x[i]^-1) over the plan's levels; q: where level 0 keeps its prefixes (y, or the working buffer when y is x)
@@ -206,7 +194,7 @@ int inverse_launch(const bnscan::Plan &p, uint4 *base, const uint4 *x, u64 xs, u
         InvArgs a{};
         if (i == 0) { a.x = x; a.xs = xs; a.y = y; a.ys = ys; a.q = q; a.qs = qs; a.mode = mode; a.num = num; a.ns = ns; a.mul = mul; }
         else { a.x = values(i); a.y = values(i); a.q = values(i) + 2 * l.n; a.xs = a.ys = a.qs = 1; a.mode = MODE_NONE; }
-        a.n = l.n; a.S = l.S; a.L = l.L; a.one = mont_one();
+        a.n = l.n; a.S = l.S; a.L = l.L; bnp::bn_limbs(bnp::bn_mont_one().w, a.one.w);
         return a;
     };
     const u32 last = p.nLevels - 1;
@@ -234,7 +222,7 @@ int scan_launch(const bnscan::Plan &p, uint4 *base, uint4 *y, u64 ys, hipStream_
         ScanArgs a{};
         a.y = i ? values(i) : y; a.ys = i ? 1 : ys;
         a.n = l.n; a.S = l.S; a.L = l.L; a.exclusive = !ADD && i == 0;
-        if (!ADD) a.ident = mont_one();
+        if (!ADD) bnp::bn_limbs(bnp::bn_mont_one().w, a.ident.w);
         return a;
     };
     const u32 last = p.nLevels - 1;
@@ -262,52 +250,46 @@ int run(u32 op, const u64 *num, u64 numStride, const u64 *hostNum, const u64 *de
     uint4 *base = (uint4 *)d, *y = (uint4 *)out;
     uint4 *q = inPlace ? base + 2 * p.q0Off : y;
     const u32 mode = op == bnscan::OP_GPROD ? MODE_COLUMN : op == bnscan::OP_GSUM ? MODE_CONST : MODE_NONE;
-    const Elem mul = hostNum ? to_elem(hostNum) : Elem{};
+    Elem mul{};
+    if (hostNum) bnp::bn_limbs(hostNum, mul.w);
     P2_TRY(inverse_launch(p, base, (const uint4 *)den, denStride, y, outStride, q, inPlace ? 1 : outStride, mode, (const uint4 *)num, numStride, mul, st));
     if (op == bnscan::OP_GPROD) return scan_launch<false>(p, base, y, outStride, st);
     if (op == bnscan::OP_GSUM) return scan_launch<true>(p, base, y, outStride, st);
     return PIL2GL_OK;
 }
 
-int check_column(const void *p, u64 n, u64 stride) {
-    if (const char *m = bnscan::check_size(n)) return fail(PIL2GL_EINVAL, "n = %llu: %s", (unsigned long long)n, m);
-    if (const char *m = bnscan::check_stride(stride)) return fail(PIL2GL_EINVAL, "stride = %llu: %s", (unsigned long long)stride, m);
-    if (n && !p) return fail(PIL2GL_EINVAL, "null buffer");
-    return PIL2GL_OK;
-}
 int check_apart(const void *in, u64 inStride, const void *out, u64 outStride, u64 n, bool sameAllowed) {
-    const bnscan::Relation r = bnscan::relation((uintptr_t)in, inStride, (uintptr_t)out, outStride, n);
-    if (r == bnscan::OVERLAP || (r == bnscan::SAME && !sameAllowed))
+    const bncol::Relation r = bncol::relation((uintptr_t)in, inStride, (uintptr_t)out, outStride, n);
+    if (r == bncol::OVERLAP || (r == bncol::SAME && !sameAllowed))
         return fail(PIL2GL_EINVAL, "the output overlaps an input (only batch_inverse may run in place, on the same pointer and stride)");
     return PIL2GL_OK;
 }
 int check_inverse(const u64 *src, u64 srcStride, u64 n, const u64 *dst, u64 dstStride) {
-    P2_TRY(check_column(src, n, srcStride));
-    P2_TRY(check_column(dst, n, dstStride));
+    P2_TRY(check_column(src, n, srcStride, "src"));
+    P2_TRY(check_column(dst, n, dstStride, "dst"));
     return check_apart(src, srcStride, dst, dstStride, n, true);
 }
 int check_gprod(const u64 *num, u64 numStride, const u64 *den, u64 denStride, u64 n, const u64 *out, u64 outStride) {
-    P2_TRY(check_column(num, n, numStride));
-    P2_TRY(check_column(den, n, denStride));
-    P2_TRY(check_column(out, n, outStride));
+    P2_TRY(check_column(num, n, numStride, "num"));
+    P2_TRY(check_column(den, n, denStride, "den"));
+    P2_TRY(check_column(out, n, outStride, "out"));
     P2_TRY(check_apart(num, numStride, out, outStride, n, false));
     return check_apart(den, denStride, out, outStride, n, false);
 }
 int check_gsum(const u64 *hostNum, const u64 *den, u64 denStride, u64 n, const u64 *out, u64 outStride) {
     if (!hostNum) return fail(PIL2GL_EINVAL, "null buffer");
-    P2_TRY(check_column(den, n, denStride));
-    P2_TRY(check_column(out, n, outStride));
+    P2_TRY(check_column(den, n, denStride, "den"));
+    P2_TRY(check_column(out, n, outStride, "out"));
     return check_apart(den, denStride, out, outStride, n, false);
 }
-int check_aligned(const void *a, const void *b, const void *c) {
-    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) return fail(PIL2GL_EINVAL, "device columns must be 16-byte aligned");
-    return PIL2GL_OK;
-}
-u64 span_words(u64 n, u64 stride) { return ((n - 1) * stride + 1) * 4; }     // up to the last element
-
-// the device copy of a host destination: a strided one keeps what lies between its elements, so those words travel too
-u64 *stage_out(Stage &s, const u64 *host, u64 n, u64 stride) {
-    return stride == 1 ? s.take(4 * n) : const_cast<u64 *>(s.put(host, span_words(n, stride)));
+// the host-pointer forms: the columns staged by the one rule (bn_column.h), the operator, the written column copied back
+int run_host(u32 op, const u64 *num, u64 numStride, const u64 *hostNum, const u64 *den, u64 denStride, u64 n, u64 *out, u64 outStride) {
+    const bncol::Col cols[3] = { { (uintptr_t)den, n, denStride, true, false }, { (uintptr_t)out, n, outStride, false, true },
+                                 { (uintptr_t)num, num ? n : 0, numStride, true, false } };
+    ColumnStage s(cols, 3);
+    P2_TRY(s.rc());
+    P2_TRY(run(op, s.dev(2), numStride, hostNum, s.dev(0), denStride, n, s.dev(1), outStride, 0));
+    return s.copy_back();
 }
 
 }  // namespace
@@ -316,7 +298,7 @@ extern "C" {
 
 int pil2gl_debug_bn128_scan_plan(uint64_t n, uint32_t op, uint32_t *outInfo, uint64_t *scratchBytes) {
     if (!outInfo || !scratchBytes) return fail(PIL2GL_EINVAL, "null argument");
-    if (const char *m = bnscan::check_size(n)) return fail(PIL2GL_EINVAL, "n = %llu: %s", (unsigned long long)n, m);
+    if (const char *m = bncol::check_size(n)) return fail(PIL2GL_EINVAL, "n = %llu: %s", (unsigned long long)n, m);
     if (op >= bnscan::N_OPS) return fail(PIL2GL_EINVAL, "op = %u: 0 batch_inverse, 1 gprod, 2 gsum, 3 batch_inverse in place", op);
     const bnscan::Plan p = bnscan::plan(n, op == bnscan::OP_BATCH_INVERSE_IN_PLACE);
     outInfo[0] = p.lv[0].L; outInfo[1] = (uint32_t)p.lv[0].S; outInfo[2] = p.nLevels; outInfo[3] = bnscan::THREADS;
@@ -329,7 +311,7 @@ int pil2gl_bn128_batch_inverse_dev(const uint64_t *src, uint64_t srcStride, uint
     P2_TRY(check_inverse(src, srcStride, n, dst, dstStride));
     if (n == 0) return PIL2GL_OK;
     P2_TRY(ensure_init());
-    P2_TRY(check_aligned(src, dst, nullptr));
+    P2_TRY(check_aligned16({ src, dst }));
     return run(bnscan::OP_BATCH_INVERSE, nullptr, 0, nullptr, src, srcStride, n, dst, dstStride, as_stream(stream));
 }
 
@@ -338,7 +320,7 @@ int pil2gl_bn128_gprod_dev(const uint64_t *num, uint64_t numStride, const uint64
     P2_TRY(check_gprod(num, numStride, den, denStride, n, out, outStride));
     if (n == 0) return PIL2GL_OK;
     P2_TRY(ensure_init());
-    P2_TRY(check_aligned(num, den, out));
+    P2_TRY(check_aligned16({ num, den, out }));
     return run(bnscan::OP_GPROD, num, numStride, nullptr, den, denStride, n, out, outStride, as_stream(stream));
 }
 
@@ -347,49 +329,27 @@ int pil2gl_bn128_gsum_dev(const uint64_t hostNum[4], const uint64_t *den, uint64
     P2_TRY(check_gsum(hostNum, den, denStride, n, out, outStride));
     if (n == 0) return PIL2GL_OK;
     P2_TRY(ensure_init());
-    P2_TRY(check_aligned(den, out, nullptr));
+    P2_TRY(check_aligned16({ den, out }));
     return run(bnscan::OP_GSUM, nullptr, 0, hostNum, den, denStride, n, out, outStride, as_stream(stream));
 }
 
 int pil2gl_bn128_batch_inverse(const uint64_t *src, uint64_t srcStride, uint64_t n, uint64_t *dst, uint64_t dstStride) {
     P2_TRY(check_inverse(src, srcStride, n, dst, dstStride));
     if (n == 0) return PIL2GL_OK;
-    const bool inPlace = dst == src;                 // then the strides are equal too: anything else was refused
-    const uint64_t sw = span_words(n, srcStride), dw = span_words(n, dstStride);
-    Stage s(inPlace ? sw : sw + dw);
-    P2_TRY(s.rc());
-    const uint64_t *dSrc = s.put(src, sw);
-    uint64_t *dDst = inPlace ? const_cast<uint64_t *>(dSrc) : stage_out(s, dst, n, dstStride);
-    P2_TRY(s.rc());
-    P2_TRY(run(bnscan::OP_BATCH_INVERSE, nullptr, 0, nullptr, dSrc, srcStride, n, dDst, dstStride, 0));
-    return s.get(dst, dDst, dw);
+    return run_host(bnscan::OP_BATCH_INVERSE, nullptr, 0, nullptr, src, srcStride, n, dst, dstStride);
 }
 
 int pil2gl_bn128_gprod(const uint64_t *num, uint64_t numStride, const uint64_t *den, uint64_t denStride, uint64_t n,
                        uint64_t *out, uint64_t outStride) {
     P2_TRY(check_gprod(num, numStride, den, denStride, n, out, outStride));
     if (n == 0) return PIL2GL_OK;
-    const uint64_t nw = span_words(n, numStride), dw = span_words(n, denStride), ow = span_words(n, outStride);
-    Stage s(nw + dw + ow);
-    P2_TRY(s.rc());
-    const uint64_t *dNum = s.put(num, nw), *dDen = s.put(den, dw);
-    uint64_t *dOut = stage_out(s, out, n, outStride);
-    P2_TRY(s.rc());
-    P2_TRY(run(bnscan::OP_GPROD, dNum, numStride, nullptr, dDen, denStride, n, dOut, outStride, 0));
-    return s.get(out, dOut, ow);
+    return run_host(bnscan::OP_GPROD, num, numStride, nullptr, den, denStride, n, out, outStride);
 }
 
 int pil2gl_bn128_gsum(const uint64_t hostNum[4], const uint64_t *den, uint64_t denStride, uint64_t n, uint64_t *out, uint64_t outStride) {
     P2_TRY(check_gsum(hostNum, den, denStride, n, out, outStride));
     if (n == 0) return PIL2GL_OK;
-    const uint64_t dw = span_words(n, denStride), ow = span_words(n, outStride);
-    Stage s(dw + ow);
-    P2_TRY(s.rc());
-    const uint64_t *dDen = s.put(den, dw);
-    uint64_t *dOut = stage_out(s, out, n, outStride);
-    P2_TRY(s.rc());
-    P2_TRY(run(bnscan::OP_GSUM, nullptr, 0, hostNum, dDen, denStride, n, dOut, outStride, 0));
-    return s.get(out, dOut, ow);
+    return run_host(bnscan::OP_GSUM, nullptr, 0, hostNum, den, denStride, n, out, outStride);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Host-only half of the BN254 Fr grand product, grand sum and batch inverse (bn_scan.hip): the one place that decides the segment length,
-// the segments, the levels and the working buffer from n, and that refuses what the entries refuse.  No HIP header: it builds with the
-// plain C++ compiler (tests/bn_scan_dump.cpp runs it under the sanitizers).
+// the segments, the levels and the working buffer from n.  No HIP header: it builds with the plain C++ compiler (tests/bn_scan_dump.cpp
+// runs it under the sanitizers).  What the entries refuse about a column is bn_column.h's.
 //
 // Both halves of every operator -- Montgomery's batch inversion and the running product / sum -- are the same shape: a vector of n items
 // is cut into S segments of L items, a lane per segment; the S segment totals are the same problem one level up, until a level has at
@@ -17,7 +17,6 @@
 
 namespace bnscan {
 
-constexpr uint64_t MAX_N = 1ull << 28;
 constexpr uint32_t THREADS = 256;
 constexpr uint32_t SEG_MIN = 16;                     // a cut level has at most ceil(n / 16) segments (L >= 16 unless LANES binds: then longer)
 constexpr uint32_t TOP_MAX = 64;                     // a level this short is one lane's
@@ -62,30 +61,5 @@ inline Plan plan(uint64_t n, bool inPlace) {
 }
 
 inline uint64_t scratch_bytes(const Plan &p) { return 32 * p.elems; }
-
-// ---- the refusals, before any device call ----
-// 0, or a message for PIL2GL_EINVAL
-inline const char *check_size(uint64_t n) { return n > MAX_N ? "n: at most 2^28 rows" : nullptr; }
-inline const char *check_stride(uint64_t stride) { return stride == 0 || stride >> 32 ? "stride: 1 <= stride < 2^32" : nullptr; }
-
-// A column is (ptr, stride): element i is the 32 bytes at ptr + 32 i stride.  Two columns of n elements:
-//   the same column (same ptr, same stride)                                     -> SAME   (allowed only where the operator says so)
-//   byte ranges [ptr, ptr + 32 ((n - 1) stride + 1)) apart                       -> APART
-//   equal strides, ptrs a multiple of 32 bytes apart but not of 32 stride bytes  -> APART  (two columns of one row-major section interleave:
-//                                                                                          their ranges meet, no element does)
-//   anything else                                                               -> OVERLAP (different strides whose ranges meet are refused
-//                                                                                          without looking for a common element)
-enum Relation { APART = 0, SAME = 1, OVERLAP = 2 };
-inline Relation relation(uintptr_t a, uint64_t aStride, uintptr_t b, uint64_t bStride, uint64_t n) {
-    if (n == 0) return APART;
-    if (a == b && aStride == bStride) return SAME;
-    const uint64_t aLen = 32 * ((n - 1) * aStride + 1), bLen = 32 * ((n - 1) * bStride + 1);
-    if (a + aLen <= b || b + bLen <= a) return APART;
-    if (aStride == bStride) {
-        const uint64_t d = a > b ? a - b : b - a;
-        if (d % 32 == 0 && d % (32 * aStride) != 0) return APART;
-    }
-    return OVERLAP;
-}
 
 }  // namespace bnscan

@@ -299,6 +299,16 @@ def _host_elems(a, what, most=None):
     return a
 
 
+def _column(buf, n, stride, what):
+    """-> the rows of a column: n, or what `buf` holds at this stride; checks the stride and the length"""
+    if stride < 1:
+        raise Pil2glError("stride must be at least 1")
+    if n is None:
+        n = (int(np.prod(buf.shape)) // 4 + stride - 1) // stride
+    _check_len(buf, ((n - 1) * stride + 1) * 4 if n else 0, what)
+    return n
+
+
 def poly_div(words, k, beta, n=None, stride=1, out=None):
     """d[i] = c[i] + beta d[i + k] over the coefficients `words` (element i at word 4*i*stride, Montgomery words; a numpy array or a
     device tensor): d[k..n) is the quotient by x^k - beta (coefficient m at m + k), d[0..k) the remainder.  beta = 4 Montgomery words
@@ -306,18 +316,12 @@ def poly_div(words, k, beta, n=None, stride=1, out=None):
     may be `words`; with stride > 1 the words between its elements stay as they are, so give one)"""
     if out is not None and _is_dev(out) != _is_dev(words):
         raise Pil2glError("mixing host and device buffers in one call")
-    if stride < 1:
-        raise Pil2glError("stride must be at least 1")
-    total = int(np.prod(words.shape))
-    if n is None:
-        n = (total // 4 + stride - 1) // stride
-    need = ((n - 1) * stride + 1) * 4 if n else 0
-    _check_len(words, need, "words")
+    n = _column(words, n, stride, "words")
     if out is None:
         if stride != 1:
             raise Pil2glError("a strided division writes into a matrix: pass out")
         out = torch.empty_like(words) if _is_dev(words) else np.empty_like(words)
-    _check_len(out, need, "out")
+    _column(out, n, stride, "out")
     b = _host_elems(beta, "beta", 1)
     if _is_dev(words):
         call("pil2gl_bn128_poly_div_xk_sub_dev", _ptr(words), n, stride, k, _ptr(b), _ptr(out), _stream())
@@ -329,12 +333,7 @@ def poly_div(words, k, beta, n=None, stride=1, out=None):
 def poly_eval(words, points, n=None, stride=1):
     """sum_i c[i] z^i for every z of `points` ((P, 4) Montgomery words on the host, 1 <= P <= 64) over the coefficients `words` (as
     poly_div takes them; never written) -> (P, 4) Montgomery words of the same kind as `words`"""
-    if stride < 1:
-        raise Pil2glError("stride must be at least 1")
-    total = int(np.prod(words.shape))
-    if n is None:
-        n = (total // 4 + stride - 1) // stride
-    _check_len(words, ((n - 1) * stride + 1) * 4 if n else 0, "words")
+    n = _column(words, n, stride, "words")
     z = _host_elems(points, "points", 64)
     if _is_dev(words):
         out = torch.empty((z.shape[0], 4), dtype=words.dtype, device=words.device)
@@ -365,12 +364,10 @@ def poly_fma(acc, src, coefs, exps, scale=None, *, n_acc, n_src, acc_stride=1, s
     with src, except as the same column when exps == [0].  -> acc"""
     if src is not None and _is_dev(acc) != _is_dev(src):
         raise Pil2glError("mixing host and device buffers in one call")
-    if acc_stride < 1 or src_stride < 1:
-        raise Pil2glError("stride must be at least 1")
-    _check_len(acc, ((n_acc - 1) * acc_stride + 1) * 4 if n_acc else 0, "acc")
+    _column(acc, n_acc, acc_stride, "acc")
     if src is None and n_src:
         raise Pil2glError("src is None with n_src = %d" % n_src)
-    _check_len(src, ((n_src - 1) * src_stride + 1) * 4 if n_src else 0, "src")
+    _column(src, n_src, src_stride, "src")
     m = np.ascontiguousarray(coefs, dtype=np.uint64).reshape(-1, 4)
     e = np.ascontiguousarray(exps, dtype=np.uint64).reshape(-1)
     if m.shape[0] != e.shape[0]:
@@ -399,17 +396,8 @@ def poly_degree(words, n=None, stride=1):
 SCAN_OPS = {"batch_inverse": 0, "gprod": 1, "gsum": 2, "batch_inverse_in_place": 3}
 
 
-def _column(buf, n, stride, what):
-    """-> the rows of a column: n, or what `buf` holds at this stride; checks the stride and the length"""
-    if stride < 1:
-        raise Pil2glError("stride must be at least 1")
-    if n is None:
-        n = (int(np.prod(buf.shape)) // 4 + stride - 1) // stride
-    _check_len(buf, ((n - 1) * stride + 1) * 4 if n else 0, what)
-    return n
-
-
-def _scan_out(like, n, stride, out):
+def _out_column(like, n, stride, out):
+    """-> `out` checked as a column of n rows, or a new dense one of the kind of `like`"""
     if out is None:
         if stride != 1:
             raise Pil2glError("a strided result is written into a matrix: pass out")
@@ -426,7 +414,7 @@ def batch_inverse(words, n=None, stride=1, out=None, out_stride=None):
         raise Pil2glError("mixing host and device buffers in one call")
     n = _column(words, n, stride, "words")
     out_stride = stride if out_stride is None else out_stride
-    out = _scan_out(words, n, out_stride, out)
+    out = _out_column(words, n, out_stride, out)
     if _is_dev(words):
         call("pil2gl_bn128_batch_inverse_dev", _ptr(words), stride, n, _ptr(out), out_stride, _stream())
     else:
@@ -442,7 +430,7 @@ def gprod(num, den, n=None, num_stride=1, den_stride=1, out=None, out_stride=1):
         raise Pil2glError("mixing host and device buffers in one call")
     n = _column(den, n, den_stride, "den")
     _column(num, n, num_stride, "num")
-    out = _scan_out(den, n, out_stride, out)
+    out = _out_column(den, n, out_stride, out)
     if _is_dev(den):
         call("pil2gl_bn128_gprod_dev", _ptr(num), num_stride, _ptr(den), den_stride, n, _ptr(out), out_stride, _stream())
     else:
@@ -458,7 +446,7 @@ def gsum(num_elem, den, n=None, den_stride=1, out=None, out_stride=1):
     if out is not None and _is_dev(out) != _is_dev(den):
         raise Pil2glError("mixing host and device buffers in one call")
     n = _column(den, n, den_stride, "den")
-    out = _scan_out(den, n, out_stride, out)
+    out = _out_column(den, n, out_stride, out)
     e = _host_elems(num_elem, "num_elem", 1)
     if _is_dev(den):
         call("pil2gl_bn128_gsum_dev", _ptr(e), _ptr(den), den_stride, n, _ptr(out), out_stride, _stream())
@@ -489,8 +477,8 @@ def h1h2(f, t, n=None, f_stride=1, t_stride=1, h1=None, h1_stride=1, h2=None, h2
         raise Pil2glError("mixing host and device buffers in one call")
     n = _column(t, n, t_stride, "t")
     _column(f, n, f_stride, "f")
-    h1 = _scan_out(t, n, h1_stride, h1)
-    h2 = _scan_out(t, n, h2_stride, h2)
+    h1 = _out_column(t, n, h1_stride, h1)
+    h2 = _out_column(t, n, h2_stride, h2)
     miss = C.c_uint64()
     args = (_ptr(f), f_stride, _ptr(t), t_stride, n, _ptr(h1), h1_stride, _ptr(h2), h2_stride, C.byref(miss))
     try:

@@ -5,6 +5,7 @@
 // and the verdicts of the output rule on a few chosen pairs.  Exits non-zero on a broken invariant.
 #include <stdio.h>
 #include "bn_h1h2_plan.h"
+#include "bn_column.h"
 
 static int bad(const char *what, uint64_t n) { fprintf(stderr, "n = %llu: %s\n", (unsigned long long)n, what); return 1; }
 
@@ -28,18 +29,19 @@ int main() {
     int rc = 0;
     for (uint64_t n = 1; n <= (1u << 14); n++) rc |= dump(n);
     for (uint32_t k = 15; k <= 28; k++)
-        for (uint64_t n = (1ull << k) - 1; n <= (1ull << k) + 1 && n <= bnh1h2::MAX_N; n++) rc |= dump(n);
-    // an output against another column: 1 when they share no element by the rule
-    char *a = (char *)(uintptr_t)(1 << 20);
-    printf("apart same %d\n", bnh1h2::apart(a, 3, a, 3, 100));
-    printf("apart same-pointer-other-stride %d\n", bnh1h2::apart(a, 3, a, 2, 100));
-    printf("apart interleaved %d\n", bnh1h2::apart(a, 5, a + 32 * 2, 5, 100));
-    printf("apart shifted-rows %d\n", bnh1h2::apart(a, 3, a + 32 * 6, 3, 100));
-    printf("apart misaligned %d\n", bnh1h2::apart(a, 3, a + 8, 3, 100));
-    printf("apart disjoint %d\n", bnh1h2::apart(a, 3, a + 32 * (99 * 3 + 1), 3, 100));
-    printf("apart other-strides %d\n", bnh1h2::apart(a, 3, a + 32, 5, 100));
-    printf("apart empty %d\n", bnh1h2::apart(a, 1, a, 1, 0));
-    printf("refusals %d %d %d %d %d\n", bnh1h2::check_size(bnh1h2::MAX_N) == nullptr, bnh1h2::check_size(bnh1h2::MAX_N + 1) != nullptr,
-           bnh1h2::check_stride(0) != nullptr, bnh1h2::check_stride(1ull << 32) != nullptr, bnh1h2::check_stride(0xFFFFFFFFull) == nullptr);
+        for (uint64_t n = (1ull << k) - 1; n <= (1ull << k) + 1 && n <= bncol::MAX_N; n++) rc |= dump(n);
+    // an output against another column: 1 when they share no element by the rule (bn_column.h)
+    const uintptr_t a = 1 << 20;
+    auto apart = [](uintptr_t x, uint64_t xStride, uintptr_t y, uint64_t yStride, uint64_t n) { return bncol::relation(x, xStride, y, yStride, n) == bncol::APART; };
+    printf("apart same %d\n", apart(a, 3, a, 3, 100));
+    printf("apart same-pointer-other-stride %d\n", apart(a, 3, a, 2, 100));
+    printf("apart interleaved %d\n", apart(a, 5, a + 32 * 2, 5, 100));
+    printf("apart shifted-rows %d\n", apart(a, 3, a + 32 * 6, 3, 100));
+    printf("apart misaligned %d\n", apart(a, 3, a + 8, 3, 100));
+    printf("apart disjoint %d\n", apart(a, 3, a + 32 * (99 * 3 + 1), 3, 100));
+    printf("apart other-strides %d\n", apart(a, 3, a + 32, 5, 100));
+    printf("apart empty %d\n", apart(a, 1, a, 1, 0));
+    printf("refusals %d %d %d %d %d\n", bncol::check_size(bncol::MAX_N) == nullptr, bncol::check_size(bncol::MAX_N + 1) != nullptr,
+           bncol::check_stride(0) != nullptr, bncol::check_stride(1ull << 32) != nullptr, bncol::check_stride(0xFFFFFFFFull) == nullptr);
     return rc;
 }

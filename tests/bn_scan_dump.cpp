@@ -5,6 +5,7 @@
 // and the verdicts of the column relation on a few chosen pairs.  Exits non-zero on a broken invariant.
 #include <stdio.h>
 #include "bn_scan_plan.h"
+#include "bn_column.h"
 
 static int bad(const char *what, uint64_t n) { fprintf(stderr, "n = %llu: %s\n", (unsigned long long)n, what); return 1; }
 
@@ -34,20 +35,20 @@ int main() {
     int rc = 0;
     for (uint64_t n = 1; n <= (1u << 14); n++) rc |= dump(n, false);
     for (uint32_t k = 1; k <= 28; k++)
-        for (uint64_t n = (1ull << k) - 1; n <= (1ull << k) + 1 && n <= bnscan::MAX_N; n++) { rc |= dump(n, false); rc |= dump(n, true); }
-    // the column relation: 0 apart, 1 same, 2 overlap
+        for (uint64_t n = (1ull << k) - 1; n <= (1ull << k) + 1 && n <= bncol::MAX_N; n++) { rc |= dump(n, false); rc |= dump(n, true); }
+    // the column relation (bn_column.h): 0 apart, 1 same, 2 overlap
     const uintptr_t a = 1 << 20;
-    printf("relation same %d\n", bnscan::relation(a, 3, a, 3, 100));
-    printf("relation same-pointer-other-stride %d\n", bnscan::relation(a, 3, a, 2, 100));
-    printf("relation interleaved %d\n", bnscan::relation(a, 3, a + 32, 3, 100));
-    printf("relation interleaved-later-row %d\n", bnscan::relation(a, 3, a + 32 * 7, 3, 100));
-    printf("relation shifted-rows %d\n", bnscan::relation(a, 3, a + 32 * 6, 3, 100));
-    printf("relation misaligned %d\n", bnscan::relation(a, 3, a + 8, 3, 100));
-    printf("relation apart %d\n", bnscan::relation(a, 3, a + 32 * (99 * 3 + 1), 3, 100));
-    printf("relation touching %d\n", bnscan::relation(a, 3, a + 32 * (99 * 3 + 1) - 8, 3, 100));
-    printf("relation other-strides %d\n", bnscan::relation(a, 3, a + 32, 5, 100));
-    printf("relation empty %d\n", bnscan::relation(a, 1, a, 2, 0));
-    printf("refusals %d %d %d %d %d\n", bnscan::check_size(bnscan::MAX_N) == nullptr, bnscan::check_size(bnscan::MAX_N + 1) != nullptr,
-           bnscan::check_stride(0) != nullptr, bnscan::check_stride(1ull << 32) != nullptr, bnscan::check_stride(0xFFFFFFFFull) == nullptr);
+    printf("relation same %d\n", bncol::relation(a, 3, a, 3, 100));
+    printf("relation same-pointer-other-stride %d\n", bncol::relation(a, 3, a, 2, 100));
+    printf("relation interleaved %d\n", bncol::relation(a, 3, a + 32, 3, 100));
+    printf("relation interleaved-later-row %d\n", bncol::relation(a, 3, a + 32 * 7, 3, 100));
+    printf("relation shifted-rows %d\n", bncol::relation(a, 3, a + 32 * 6, 3, 100));
+    printf("relation misaligned %d\n", bncol::relation(a, 3, a + 8, 3, 100));
+    printf("relation apart %d\n", bncol::relation(a, 3, a + 32 * (99 * 3 + 1), 3, 100));
+    printf("relation touching %d\n", bncol::relation(a, 3, a + 32 * (99 * 3 + 1) - 8, 3, 100));
+    printf("relation other-strides %d\n", bncol::relation(a, 3, a + 32, 5, 100));
+    printf("relation empty %d\n", bncol::relation(a, 1, a, 2, 0));
+    printf("refusals %d %d %d %d %d\n", bncol::check_size(bncol::MAX_N) == nullptr, bncol::check_size(bncol::MAX_N + 1) != nullptr,
+           bncol::check_stride(0) != nullptr, bncol::check_stride(1ull << 32) != nullptr, bncol::check_stride(0xFFFFFFFFull) == nullptr);
     return rc;
 }

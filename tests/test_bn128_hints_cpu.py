@@ -262,3 +262,33 @@ def test_planner_header_under_the_sanitizers(tmp_path, lib):
     assert verdicts == {"same": "1", "same-pointer-other-stride": "2", "interleaved": "0", "interleaved-later-row": "0", "shifted-rows": "2",
                         "misaligned": "2", "apart": "0", "touching": "2", "other-strides": "2", "empty": "0"}
     assert [l for l in lines if l.startswith("refusals")] == ["refusals 1 1 1 1 1"]
+
+
+# ---- the staging decision of the host-pointer entries (bn_column.h) under the sanitizers, in a program of its own -------------------------
+# n = 100 rows unless the case says otherwise; a range is "+<bytes from the section's start> words up down", a column "<range> +<word>"
+STAGING = """\
+stage apart words=800 | range +0 words=400 up=1 down=0 range +65536 words=400 up=0 down=1 | col 0 +0 col 1 +0
+stage apart-strided-output words=2384 | range +0 words=1192 up=1 down=0 range +65536 words=1192 up=1 down=1 | col 0 +0 col 1 +0
+stage same-stride-1 words=400 | range +0 words=400 up=1 down=1 | col 0 +0 col 0 +0
+stage same-stride-3 words=1192 | range +0 words=1192 up=1 down=1 | col 0 +0 col 0 +0
+stage outputs-at-0-and-1 words=1596 | range +65536 words=400 up=1 down=0 range +0 words=1196 up=1 down=1 | col 0 +0 col 1 +0 col 1 +4
+stage outputs-at-2-and-0 words=1600 | range +65536 words=400 up=1 down=0 range +0 words=1200 up=1 down=1 | col 0 +0 col 1 +8 col 1 +0
+stage output-among-inputs words=1196 | range +0 words=1196 up=1 down=1 | col 0 +0 col 0 +4
+stage three-of-one-section words=780 | range +0 words=780 up=1 down=1 | col 0 +4 col 0 +8 col 0 +0
+stage touching words=1592 | range +0 words=1192 up=1 down=0 range +9536 words=400 up=0 down=1 | col 0 +0 col 1 +0
+stage empty-beside words=400 | range +0 words=400 up=0 down=1 | col - +0 col 0 +0
+stage one-row words=8 | range +0 words=4 up=1 down=0 range +32 words=4 up=1 down=1 | col 0 +0 col 1 +0
+stage one-row-in-place words=4 | range +0 words=4 up=1 down=1 | col 0 +0 col 0 +0
+stage counts-acc-first words=1192 | range +0 words=1192 up=1 down=1 | col 0 +0 col 0 +4
+stage counts-src-first words=1196 | range +0 words=1196 up=1 down=1 | col 0 +4 col 0 +0
+stage inputs-of-one-section words=2784 | range +0 words=1192 up=1 down=0 range +32 words=1192 up=1 down=0 range +65536 words=400 up=0 down=1 | col 0 +0 col 1 +0 col 2 +0
+"""
+
+
+def test_staging_decision_under_the_sanitizers(tmp_path):
+    exe = str(tmp_path / "bn_column_dump")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "bn_column_dump.cpp"), "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stderr == "", "sanitizer report or a broken invariant:\n" + run.stderr[-4000:]
+    assert run.stdout == STAGING

@@ -224,6 +224,20 @@ def test_strided_columns_and_two_columns_of_one_section(bn, on_device):
         bn.h1h2(df, dt, n=n, f_stride=3, h1=ds[4:], h1_stride=w, h2=ds[4:], h2_stride=w)
 
 
+def test_h2_below_h1_in_one_section_on_the_host(bn):
+    n, w = 300, 3
+    t = distinct(n, 63)
+    f = drawn(t, 64)
+    want = ref.h1h2(f, t)
+    wf, wt = href.words(f).reshape(-1), href.words(t).reshape(-1)
+    s = np.full(n * w * 4, SENTINEL, np.uint64)
+    bn.h1h2(wf.copy(), wt.copy(), n=n, h1=s[8:], h1_stride=w, h2=s, h2_stride=w)      # h2 column 0, h1 column 2, host pointers
+    got = s.reshape(n, w, 4)
+    differs(got[:, 2], href.words(want[0]), "h1, column 2")
+    differs(got[:, 0], href.words(want[1]), "h2, column 0")
+    assert (got[:, 1] == SENTINEL).all()
+
+
 # ---- 7. missing ----------------------------------------------------------------------------------------------------------------------------
 def test_missing_value(bn):
     from pil2gl import Pil2glError

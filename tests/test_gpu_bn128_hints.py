@@ -266,6 +266,19 @@ def test_host_pointer_forms_equal_the_device_forms(bn):
     assert np.array_equal(bn.batch_inverse(w, out=w).reshape(-1, 4), ref.mont_words(ref.batch_inverse(den)))     # in place on the host
 
 
+def test_gprod_on_the_host_into_a_column_of_the_inputs_section(bn):
+    n, w = 65, 3                                                  # the smallest two-level plan
+    assert bn.scan_plan(n, "gprod")["levels"] == 2 and bn.scan_plan(n - 1, "gprod")["levels"] == 1
+    num, den = columns(n, 11)
+    sec = ref.words(ref.rand_elems(n * w, 12)).reshape(n, w, 4)
+    sec[:, 0], sec[:, 1] = ref.mont_words(num), ref.mont_words(den)
+    s = sec.reshape(-1).copy()
+    bn.gprod(s, s[4:], n=n, num_stride=w, den_stride=w, out=s[8:], out_stride=w)     # columns 0 and 1 into column 2, host pointers
+    got = s.reshape(n, w, 4)
+    differs(got[:, 2], ref.mont_words(ref.gprod(num, den)), "column 2")
+    assert np.array_equal(got[:, :2], sec[:, :2])
+
+
 def test_no_rows(bn):
     d = dev(ref.mont_words([7]))
     bn.batch_inverse(d, n=0, out=d)
