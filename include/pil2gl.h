@@ -734,6 +734,23 @@ uint64_t pil2gl_debug_bn128_path_launches(void);
 #define PIL2GL_PLAN_LAUNCH_WORDS 14
 int pil2gl_debug_plan_transform(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount,
                                 uint32_t *out, uint32_t maxLaunches, uint32_t *nLaunches);
+/* host-only, no device: how the launches of the same call (same arguments, same order) are dealt to workgroups.  A workgroup of a 16-slot
+ * fixed-geometry instance owns one row tile and a run of up to W consecutive column chunks of it; every other instance has W = 1.
+ * Per launch PIL2GL_PLAN_GRID_WORDS words:
+ *   [0] workgroups launched   [1] W   [2] row tiles   [3] row tiles per outer index (hi)   [4] column chunks
+ * so that [11] of pil2gl_debug_plan_transform, the tiles of the launch, is [2] x [4], and [0] = [2] x ceil([4] / [1]). */
+#define PIL2GL_PLAN_GRID_WORDS 5
+int pil2gl_debug_plan_transform_grid(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount,
+                                     uint32_t *out, uint32_t maxLaunches, uint32_t *nLaunches);
+/* the walk itself, from the function the kernels run: for workgroups [firstBlock, firstBlock + count) of launch number `launch` of that
+ * call and steps s < W, out[((b - firstBlock) * W + s) * 3 + 0..2] = outer index hi, row tile gt within it, column chunk cc of the tile
+ * the workgroup works on in step s; 0xffffffff thrice where it has no such step */
+int pil2gl_debug_transform_walk(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount, uint32_t launch,
+                                uint32_t firstBlock, uint32_t count, uint32_t *out);
+/* every workgroup and step of that launch through the same function: counts[0] = tiles (hi, gt, cc) reached exactly once, [1] = tiles
+ * never reached, [2] = visits beyond a tile's first or outside the launch */
+int pil2gl_debug_transform_walk_cover(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount, uint32_t launch,
+                                      uint64_t *counts);
 /* the two hand-written Goldilocks products on n pairs of arbitrary u64 operands (host pointers): x[i] = a*b by the exact form
  * the transform kernels use (gl_field.cuh mul_lazy_x), pb[i] = a*b by the flagged form of the S-boxes (mul_lazy_b), both canonical;
  * flag[i] != 0 where the flagged form asks to be recomputed (its last subtraction borrowed: probability ~2^-32 on random operands) */

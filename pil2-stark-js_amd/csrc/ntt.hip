@@ -9,7 +9,8 @@
 //    x S column slots in LDS, runs the k stages there as register steps of up to four stages (16-row
 //    sub-transforms in Z/(2^96+1), see below), and applies the inter-pass twiddle w_(2^(lo+k))^(b*j)
 //    from a per-tile LDS table that is shared by all columns of the tile.  All passes are in place.
-//    Workgroups are numbered so that the column chunks of one row block run on one XCD (one L2).
+//    Workgroups are numbered so that the column chunks of one row block run on one XCD (one L2); in the 16-slot pass kernels a
+//    workgroup takes a run of consecutive chunks of its row tile and builds the tables once (walk_at).
 //  * Forward/inverse transforms run decimation-in-frequency (natural in -> bit-reversed out);
 //    the last pass scatters rows to their bit-reversed index so the caller sees natural order.
 //  * interpolate (LDE) never reorders anything: iNTT as DIF leaves coefficient m at row
@@ -137,10 +138,26 @@ __device__ __forceinline__ void dit_stages(u64 *tile, const u64 *TW, u32 k, u32 
 // neighbours in memory -- the column chunks of the same rows, whose row segments share cache lines when the row length is
 // not a multiple of 128 bytes -- are consecutive logical indices; this maps consecutive logical indices to one XCD, so the
 // second half of a straddled line is found (reads) or completed (writes) in the same L2.
-__device__ __forceinline__ u32 xcd_local_block() {
-    const u32 b = blockIdx.x, per = gridDim.x >> 3;
+__host__ __device__ constexpr u32 xcd_local_block(u32 b, u32 grid) {
+    const u32 per = grid >> 3;
     return b < (per << 3) ? (b & 7) * per + (b >> 3) : b;
 }
+
+// The chunk walk: which tile of the launch workgroup `block` (of `grid`) works on in its step `step`.  A launch is nHi x nGroupTiles row
+// tiles x nColChunks column chunks; a workgroup owns ONE row tile (hi, gt) and a run of up to W consecutive chunks of it, a last shorter
+// run taking what W leaves over, so that whatever depends on the row tile alone -- the twiddle and scale tables -- is built once per W
+// chunks.  The runs of a row tile are consecutive logical indices: one XCD.  -> false where the workgroup has no such step (step 0
+// always exists).  W = 1 is one tile per workgroup, the chunk index varying fastest.  The kernels and the host's account of a launch
+// (pil2gl_debug_transform_walk) both go through this one function.
+__host__ __device__ constexpr bool walk_at(u32 block, u32 grid, u32 step, u32 W, u32 nColChunks, u32 nGroupTiles, u32 &hi, u32 &gt, u32 &cc) {
+    const u32 b = xcd_local_block(block, grid), runs = (nColChunks + W - 1) / W, rowTile = b / runs;
+    hi = rowTile / nGroupTiles;
+    gt = rowTile - hi * nGroupTiles;
+    cc = (b - rowTile * runs) * W + step;
+    return step < W && cc < nColChunks;
+}
+// its workgroups: ceil(nColChunks / W) runs per row tile
+__host__ __device__ constexpr u64 walk_grid(u64 rowTiles, u32 W, u32 nColChunks) { return rowTiles * ((nColChunks + W - 1) / W); }
 
 // Two adjacent column slots of one tile row.  The 16-slot fixed-geometry kernels move a tile between HBM and LDS in these: lane
 // tid owns slots 2*px, 2*px+1 (px = tid & 7) of the eight tile rows r + 32*i (r = tid >> 3), so a 128-byte row piece is 8 lanes x 16
@@ -164,6 +181,7 @@ struct PassParams {
     u32 k, logM, hasTw, dit;
     u32 Wc, nbT;                    // tile slots S = nbT*Wc : nbT adjacent groups x Wc columns
     u32 nColChunks, nGroupTiles;
+    u32 walk;                       // column chunks a workgroup walks (walk_at's W; 1 outside the 16-slot instances)
     u32 n, scatter;                 // scatter: store row bitrev_n(g*2^k + t) (lo = 0 pass of a natural-order transform)
     u32 canonOut;                   // 1: this pass writes a transform's result (canonical values); 0: the next pass takes any representative
 };
@@ -173,66 +191,57 @@ struct PassParams {
 // into 16-column chunks with a ragged last one (100 columns: 16 x 6 + 4).  15 slots: a 15-column matrix, whose rows are under 128
 // bytes and take 7-stage passes, so no default plan reaches SC = 15 (enumerated over 2^0..2^30 rows x 1..200 columns, tests/golden/
 // transform_plans.txt.gz); PIL2GL_NTT_KMAX=9 or 10 does, e.g. fft of 2^8 x 15 (one pass) and interpolate of 2^16 x 15 (DIT pass).
-template <bool INV, bool DIT, int KC, int SC = 16>
-__global__ void __launch_bounds__(PASS_THREADS) ntt_pass_kernel(PassParams P) {
-    extern __shared__ u64 lds[];
-    const u32 k = KC ? KC : P.k, K = 1u << k, S = KC ? SC : blockDim.x, by = KC ? 16 : blockDim.y;
-    const u32 x = threadIdx.x, y = threadIdx.y, tid = y * S + x, nth = S * by;
-    constexpr bool PAD = KC != 0;                   // one spare tile row per 16 (see dif_step)
-    const u32 tileRows = PAD ? K + (K >> 4) : K;
-    u64 *tile = lds, *TW = tile + (size_t)S * tileRows, *TWO = TW + K;
-#define TROW(t_) (PAD ? (t_) + ((t_) >> 4) : (t_))
-
-    u32 bid = xcd_local_block();
-    const u32 cc = bid % P.nColChunks; bid /= P.nColChunks;
-    const u32 gt = bid % P.nGroupTiles;
-    const u32 hi = bid / P.nGroupTiles;
-    const u32 gi = KC ? 0 : x / P.Wc, ci = x - gi * P.Wc;
-    const u64 c = (u64)cc * P.Wc + ci;
-    const bool valid = c < P.C;
-    // slot groups: adjacent blocks; in the scattering pass blocks nGroupTiles apart, whose bit-reversed rows are adjacent
-    const u64 g = P.scatter ? (u64)gi * P.nGroupTiles + gt : (u64)gt * P.nbT + gi;
-    const u64 base = (u64)hi * P.hiStride + g * P.gStride + c;
-
-    // 16 slots: pairs of slots (see Pair); g = gt and gi = 0 here (one slot group)
-    constexpr bool WIDE = KC == 8 && SC == 16;
+// The 16-slot fixed-geometry pass (8 stages, 16 column slots x 16 sub-transform lanes, one slot group: g = gt): the workgroup builds the
+// tables of its row tile once and walks its column chunks (walk_at): load, tile write, stages, store, next chunk.  The tile moves in
+// slot pairs (see Pair).  Only the first chunk's loads overlap anything of the workgroup's own (the tables): issuing chunk c+1's before
+// chunk c's store costs 33 registers (147 / 153 / 156 against 114 / 121 / 124: a wave per SIMD), and the three other workgroups of
+// the CU cover the latency.
+template <bool INV, bool DIT>
+__device__ __forceinline__ void pass_walk16(const PassParams &P, u64 *lds) {
+    constexpr u32 K = 256, S = 16;
+    const u32 x = threadIdx.x, y = threadIdx.y, tid = y * S + x;
+    u64 *tile = lds, *TW = tile + S * (K + K / 16), *TWO = TW + K;
+    u32 hi, gt, cc;
+    walk_at(blockIdx.x, gridDim.x, 0, P.walk, P.nColChunks, P.nGroupTiles, hi, gt, cc);
     const u32 px = tid & 7, r = tid >> 3;
-    const u64 c0 = (u64)cc * 16 + 2 * px;
-    const bool v1 = c0 < P.C, v2 = c0 + 1 < P.C;
-    const u64 base0 = (u64)hi * P.hiStride + g * P.gStride + c0 + (u64)r * P.tStride, rs = P.tStride * 32;
-    Pair vin2[PAIR_ROWS];
+    // the lane's first row at slot pair px of chunk 0, in and out; a chunk is 16 words further, the lane's eight rows are rs / os apart
+    const u64 in0 = (u64)hi * P.hiStride + (u64)gt * P.gStride + (u64)r * P.tStride + 2 * px, rs = P.tStride * 32;
+    // row i of this lane goes to out0 + ord(i) * os, ord = i, or its 3-bit reversal where the pass scatters (tile row bits 5..7 are
+    // the lowest three of the reversed index above the tile's own: bitrev_n(g*2^8 + r + 32 i) = bitrev_n(g*2^8 + r) + (brev3(i) << (n - 8)))
+    u64 out0 = in0, os = rs;
+    if (P.scatter) { out0 = (u64)bitrev32(gt * K + r, P.n) * P.C + 2 * px; os = P.C << (P.n - 8); }
 
-    // the first LOADB rows of this lane are requested before the tables are built, so that their latency overlaps it;
-    // all loads of a batch are in flight together (one load per iteration would serialise the HBM latency)
-    constexpr u32 LOADB = 16;
-    u64 vin[LOADB];
-    if constexpr (WIDE) {
+    Pair vin2[PAIR_ROWS];
+    // all eight loads of a chunk are in flight together; the ragged last lane of an odd-width row has one column, lanes beyond it none
+    auto load = [&](u32 chunk) {
+        const u64 c0 = (u64)chunk * 16 + 2 * px;
+        // (the offset is made opaque: left alone the compiler works out the eight row addresses of every chunk once, ahead of the
+        // loop, and keeps them in registers through the stages; this way it redoes the eight additions per chunk)
+        u64 off = in0 + (u64)chunk * 16;
+        asm volatile("" : "+v"(off));
+        const u64 *sp = P.src + off;
 #pragma unroll
         for (u32 i = 0; i < PAIR_ROWS; i++) vin2[i] = {0, 0};
-        const u64 *sp = P.src + base0;
-        if (v2) {
+        if (c0 + 1 < P.C) {
 #pragma unroll
             for (u32 i = 0; i < PAIR_ROWS; i++) vin2[i] = *reinterpret_cast<const Pair *>(sp + i * rs);
-        } else if (v1) {
+        } else if (c0 < P.C) {
 #pragma unroll
             for (u32 i = 0; i < PAIR_ROWS; i++) vin2[i].a = sp[i * rs];
         }
-    } else {
-#pragma unroll
-        for (u32 i = 0; i < LOADB; i++) { const u32 t = y + i * by; vin[i] = (valid && t < K) ? P.src[base + (u64)t * P.tStride] : 0; }
-    }
-    for (u32 j = tid; j < K; j += nth) TW[j] = P.twK[j << (10 - k)];
+    };
+    load(cc);                                       // the first chunk's latency overlaps the tables
+    TW[tid] = P.twK[tid << 2];
     if (P.hasTw) {
-        for (u32 idx = tid; idx < (KC ? 1 : P.nbT) * K; idx += nth) {
-            u32 b = gt * (KC ? 1 : P.nbT) + (idx >> k);
-            u64 v = root_pow(P.tw, P.logM, b * bitrev32(idx & (K - 1), k));
-            if (P.scale) v = mul(v, P.scale);
-            TWO[idx] = v;
-        }
+        u64 v = root_pow(P.tw, P.logM, gt * bitrev32(tid, 8));
+        if (P.scale) v = mul(v, P.scale);
+        TWO[tid] = v;
     }
     __syncthreads();
     PairL *trow = reinterpret_cast<PairL *>(tile) + (r + (r >> 4)) * 8 + px;       // tile row r + 32*i: PAIR_LDS_STEP * i further
-    if constexpr (WIDE) {
+    for (u32 step = 0;;) {
+        // (a lane reads back and rewrites only its own pairs of the tile, so no barrier stands between one chunk's store and the next
+        // chunk's tile write; the stages end in one)
         if (DIT && P.hasTw) {
 #pragma unroll
             for (u32 i = 0; i < PAIR_ROWS; i++) {
@@ -244,37 +253,17 @@ __global__ void __launch_bounds__(PASS_THREADS) ntt_pass_kernel(PassParams P) {
 #pragma unroll
             for (u32 i = 0; i < PAIR_ROWS; i++) { PairL o; o.a = vin2[i].a; o.b = vin2[i].b; trow[i * PAIR_LDS_STEP] = o; }
         }
-    } else {
-        for (u32 t0 = y;;) {
-#pragma unroll
-            for (u32 i = 0; i < LOADB; i++) {
-                const u32 t = t0 + i * by;
-                if (t < K) {
-                    u64 v = vin[i];
-                    if (DIT && P.hasTw) v = NTT_MUL(v, TWO[gi * K + t]);
-                    tile[TROW(t) * S + x] = v;
-                }
-            }
-            t0 += LOADB * by;
-            if (t0 >= K) break;
-#pragma unroll
-            for (u32 i = 0; i < LOADB; i++) { const u32 t = t0 + i * by; vin[i] = (valid && t < K) ? P.src[base + (u64)t * P.tStride] : 0; }
-        }
-    }
-    __syncthreads();
-    if constexpr (KC == 8) {
-        if (DIT) { dit_step<4, INV, true>(tile, TW, 8, 0, 4, SC, x, y, 16); dit_step<4, INV, true>(tile, TW, 8, 4, 0, SC, x, y, 16); }
-        else { dif_step<4, INV, true>(tile, TW, 8, 8, SC, x, y, 16); dif_step<4, INV, true>(tile, TW, 8, 4, SC, x, y, 16); }
-    } else {
-        if (DIT) dit_stages<INV>(tile, TW, k, S, x, y, by); else dif_stages<INV>(tile, TW, k, S, x, y, by);
-    }
-    if constexpr (WIDE) {
-        if (!v1) return;
-        // row i of this lane: words dp + ord(i) * os, ord = i, or its 3-bit reversal where the pass scatters (tile row bits 5..7 are
-        // the lowest three of the reversed index above the tile's own: bitrev_n(g*2^8 + r + 32 i) = bitrev_n(g*2^8 + r) + (brev3(i) << (n - 8)))
-        u64 *dp = P.dst + base0;
-        u64 os = rs;
-        if (P.scatter) { dp = P.dst + (u64)bitrev32((u32)(g * K + r), P.n) * P.C + c0; os = P.C << (P.n - 8); }
+        __syncthreads();
+        if (DIT) { dit_step<4, INV, true>(tile, TW, 8, 0, 4, S, x, y, 16); dit_step<4, INV, true>(tile, TW, 8, 4, 0, S, x, y, 16); }
+        else { dif_step<4, INV, true>(tile, TW, 8, 8, S, x, y, 16); dif_step<4, INV, true>(tile, TW, 8, 4, S, x, y, 16); }
+
+        const u64 c0 = (u64)cc * 16 + 2 * px;
+        const bool v1 = c0 < P.C, v2 = c0 + 1 < P.C;
+        u64 outOff = out0 + (u64)cc * 16;            // (opaque for the same reason)
+        asm volatile("" : "+v"(outOff));
+        u64 *dp = P.dst + outOff;
+        u32 h2, g2, ccNext;
+        const bool more = walk_at(blockIdx.x, gridDim.x, ++step, P.walk, P.nColChunks, P.nGroupTiles, h2, g2, ccNext);
         // what a value takes on its way out is the same for the whole launch: one loop per case, nothing decided per element
         auto put = [&](auto xf) {
             if (v2) {
@@ -284,7 +273,7 @@ __global__ void __launch_bounds__(PASS_THREADS) ntt_pass_kernel(PassParams P) {
                     xf(v, i);
                     *reinterpret_cast<Pair *>(dp + (P.scatter ? brev3(i) : i) * os) = v;
                 }
-            } else {
+            } else if (v1) {
 #pragma unroll
                 for (u32 i = 0; i < PAIR_ROWS; i++) {
                     Pair v; v.a = reinterpret_cast<const u64 *>(trow + i * PAIR_LDS_STEP)[0]; v.b = 0;
@@ -299,16 +288,78 @@ __global__ void __launch_bounds__(PASS_THREADS) ntt_pass_kernel(PassParams P) {
         } else if (!P.hasTw && P.scale) put([&](Pair &v, u32) { v.a = mul(v.a, P.scale); v.b = mul(v.b, P.scale); });
         else if (P.canonOut) put([&](Pair &v, u32) { v.a = canon(v.a); v.b = canon(v.b); });
         else put([&](Pair &, u32) {});
-    } else {
-        if (!valid) return;
-        for (u32 t = y; t < K; t += by) {
-            u64 v = tile[TROW(t) * S + x];
-            if (P.hasTw && !DIT) v = P.canonOut ? mul(v, TWO[gi * K + t]) : NTT_MUL(v, TWO[gi * K + t]);
-            else if (!P.hasTw && P.scale) v = mul(v, P.scale);
-            else if (P.canonOut) v = canon(v);
-            u64 addr = P.scatter ? (u64)bitrev32((u32)(g * K + t), P.n) * P.C + c : base + (u64)t * P.tStride;
-            P.dst[addr] = v;
+        if (!more) break;
+        cc = ccNext;
+        load(cc);
+    }
+}
+
+template <bool INV, bool DIT, int KC, int SC = 16>
+__global__ void __launch_bounds__(PASS_THREADS) ntt_pass_kernel(PassParams P) {
+    extern __shared__ u64 lds[];
+    if constexpr (KC == 8 && SC == 16) { pass_walk16<INV, DIT>(P, lds); return; }
+    const u32 k = KC ? KC : P.k, K = 1u << k, S = KC ? SC : blockDim.x, by = KC ? 16 : blockDim.y;
+    const u32 x = threadIdx.x, y = threadIdx.y, tid = y * S + x, nth = S * by;
+    constexpr bool PAD = KC != 0;                   // one spare tile row per 16 (see dif_step)
+    const u32 tileRows = PAD ? K + (K >> 4) : K;
+    u64 *tile = lds, *TW = tile + (size_t)S * tileRows, *TWO = TW + K;
+#define TROW(t_) (PAD ? (t_) + ((t_) >> 4) : (t_))
+
+    u32 hi, gt, cc;                                 // one tile per workgroup
+    walk_at(blockIdx.x, gridDim.x, 0, 1, P.nColChunks, P.nGroupTiles, hi, gt, cc);
+    const u32 gi = KC ? 0 : x / P.Wc, ci = x - gi * P.Wc;
+    const u64 c = (u64)cc * P.Wc + ci;
+    const bool valid = c < P.C;
+    // slot groups: adjacent blocks; in the scattering pass blocks nGroupTiles apart, whose bit-reversed rows are adjacent
+    const u64 g = P.scatter ? (u64)gi * P.nGroupTiles + gt : (u64)gt * P.nbT + gi;
+    const u64 base = (u64)hi * P.hiStride + g * P.gStride + c;
+
+    // the first LOADB rows of this lane are requested before the tables are built, so that their latency overlaps it;
+    // all loads of a batch are in flight together (one load per iteration would serialise the HBM latency)
+    constexpr u32 LOADB = 16;
+    u64 vin[LOADB];
+#pragma unroll
+    for (u32 i = 0; i < LOADB; i++) { const u32 t = y + i * by; vin[i] = (valid && t < K) ? P.src[base + (u64)t * P.tStride] : 0; }
+    for (u32 j = tid; j < K; j += nth) TW[j] = P.twK[j << (10 - k)];
+    if (P.hasTw) {
+        for (u32 idx = tid; idx < (KC ? 1 : P.nbT) * K; idx += nth) {
+            u32 b = gt * (KC ? 1 : P.nbT) + (idx >> k);
+            u64 v = root_pow(P.tw, P.logM, b * bitrev32(idx & (K - 1), k));
+            if (P.scale) v = mul(v, P.scale);
+            TWO[idx] = v;
         }
+    }
+    __syncthreads();
+    for (u32 t0 = y;;) {
+#pragma unroll
+        for (u32 i = 0; i < LOADB; i++) {
+            const u32 t = t0 + i * by;
+            if (t < K) {
+                u64 v = vin[i];
+                if (DIT && P.hasTw) v = NTT_MUL(v, TWO[gi * K + t]);
+                tile[TROW(t) * S + x] = v;
+            }
+        }
+        t0 += LOADB * by;
+        if (t0 >= K) break;
+#pragma unroll
+        for (u32 i = 0; i < LOADB; i++) { const u32 t = t0 + i * by; vin[i] = (valid && t < K) ? P.src[base + (u64)t * P.tStride] : 0; }
+    }
+    __syncthreads();
+    if constexpr (KC == 8) {
+        if (DIT) { dit_step<4, INV, true>(tile, TW, 8, 0, 4, SC, x, y, 16); dit_step<4, INV, true>(tile, TW, 8, 4, 0, SC, x, y, 16); }
+        else { dif_step<4, INV, true>(tile, TW, 8, 8, SC, x, y, 16); dif_step<4, INV, true>(tile, TW, 8, 4, SC, x, y, 16); }
+    } else {
+        if (DIT) dit_stages<INV>(tile, TW, k, S, x, y, by); else dif_stages<INV>(tile, TW, k, S, x, y, by);
+    }
+    if (!valid) return;
+    for (u32 t = y; t < K; t += by) {
+        u64 v = tile[TROW(t) * S + x];
+        if (P.hasTw && !DIT) v = P.canonOut ? mul(v, TWO[gi * K + t]) : NTT_MUL(v, TWO[gi * K + t]);
+        else if (!P.hasTw && P.scale) v = mul(v, P.scale);
+        else if (P.canonOut) v = canon(v);
+        u64 addr = P.scatter ? (u64)bitrev32((u32)(g * K + t), P.n) * P.C + c : base + (u64)t * P.tStride;
+        P.dst[addr] = v;
     }
 #undef TROW
 }
@@ -323,6 +374,7 @@ struct LdeParams {
     u32 cosetBegin, cosetCount;     // this call produces cosets [cosetBegin, cosetBegin+cosetCount) of the 2^extBits (multi-GPU: one slice per rank)
     u32 coefIn;                     // 1: src already holds COEFFICIENTS, coefficient m at row bitrev_n(m) (what the inverse passes + the stages below leave): no inverse stages here
     u32 Wc, G, nColChunks;
+    u32 nTiles;                     // row tiles of the launch
 };
 
 // Finishes the iNTT on bits [0,k), scales by the coset factors and starts the forward NTT (see header).
@@ -338,9 +390,8 @@ __global__ void __launch_bounds__(MID_THREADS) lde_mid_kernel(LdeParams P) {
     const u32 tileRows = PAD ? K + (K >> 4) : K, rowStep = PAD ? by + 1 : by;      // rows y + i*by -> y + i*(by+1) when padded (by = 16)
     u64 *tile = lds, *TWi = tile + (size_t)S * tileRows, *TWf = TWi + K, *Sc = TWf + K, *Uc = Sc + (size_t)P.G * K;
 
-    u32 bid = xcd_local_block();
-    const u32 cc = bid % P.nColChunks;
-    const u32 gt = bid / P.nColChunks;
+    u32 hi, gt, cc;                                 // one tile per workgroup (hi = 0: the row blocks of the mid kernel are one run of tiles)
+    walk_at(blockIdx.x, gridDim.x, 0, 1, P.nColChunks, P.nTiles, hi, gt, cc);
     const u32 gi = SC ? 0 : x / P.Wc, ci = x - gi * P.Wc;
     const u64 c = (u64)cc * P.Wc + ci;
     const bool valid = c < P.C;
@@ -540,7 +591,9 @@ struct Launch {
     Geom g;
     u32 fixedSlots;         // 0: any-geometry instance; 15 / 16: the fixed-geometry instance of that many slots
     u32 ept;                // mid: the rows-per-lane instance (lde_mid_kernel<EPT, ..>); passes: 0
-    u32 ldsBytes, blocks;
+    u32 ldsBytes, blocks;   // blocks: the tiles of the launch, row tiles x column chunks
+    u32 groupTiles;         // row tiles per outer index (passes above bit 0: 2^lo / slot groups; else all of them)
+    u32 walk, grid;         // a workgroup walks up to `walk` column chunks of its row tile (walk_at): `grid` workgroups take the `blocks` tiles
     u32 scatter, canonOut;  // passes: PassParams of the same names; mid: canonOut = no pass follows
 };
 constexpr int MAX_LAUNCHES = 64;           // 2 x 30 one-stage passes and the mid kernel at most
@@ -551,6 +604,25 @@ int check_launch(const Launch &L, u64 blocks) {
     if (blocks > 0x7fffffffull) return fail(PIL2GL_EINVAL, "grid too large");
     if (L.ldsBytes > MAX_LDS_BYTES) return fail(PIL2GL_EINVAL, "tile needs %u bytes of LDS (>160 KiB)", L.ldsBytes);
     return PIL2GL_OK;
+}
+
+// How many column chunks a workgroup of the launch walks.  The 16-slot fixed-geometry instances build their per-row-tile tables once per
+// workgroup, so the longer the run the less of that work is repeated; but the chip wants several workgroups per CU slot, so a launch
+// that has 4 x 256 tiles keeps at least that many workgroups: with R = ceil(1024 / rowTiles) runs wanted per row tile, W =
+// floor(nColChunks / R) leaves at least R (2^24 rows: R = 1, a workgroup takes its whole row of chunks, 7 of 100 columns and 50 of 800).
+// Where that comes to one chunk, two are taken if the grid still holds 1024 or never could (a launch that cannot fill the chip is a few
+// microseconds either way).  The mid kernel and every other instance keep one tile per workgroup (the mid kernel's tables serve eight
+// cosets already, and walking costs it 18 registers: 182, a wave per SIMD).
+constexpr u32 WALK_MIN_GRID = 4 * 256;
+void plan_walk(Launch &L, u64 rowTiles) {
+    const u32 nc = L.g.nColChunks;
+    L.walk = 1;
+    if (L.fixedSlots == 16 && L.kind != MID) {
+        const u64 R = (WALK_MIN_GRID + rowTiles - 1) / rowTiles;
+        if (R <= nc) L.walk = (u32)(nc / R);
+        if (L.walk == 1 && nc >= 2 && (rowTiles * nc < WALK_MIN_GRID || walk_grid(rowTiles, 2, nc) >= WALK_MIN_GRID)) L.walk = 2;
+    }
+    L.grid = (u32)walk_grid(rowTiles, L.walk, nc);
 }
 
 // One pass over index bits [lo, lo+k) of a 2^n x C matrix.
@@ -564,6 +636,8 @@ int plan_pass(Plan &p, u32 kind, u64 C, u32 n, u32 lo, u32 k, bool scatter, bool
     L.ldsBytes = (u32)(8 * ((size_t)L.g.S * (L.fixedSlots ? K + K / 16 : K) + K + (lo > 0 ? (size_t)L.g.nbT * K : 0)));
     const u64 blocks = nHi * (totalGroups / L.g.nbT) * L.g.nColChunks;
     L.blocks = (u32)blocks;
+    L.groupTiles = (u32)(totalGroups / L.g.nbT);
+    plan_walk(L, nHi * L.groupTiles);
     return check_launch(L, blocks);
 }
 
@@ -640,6 +714,8 @@ int plan_lde(u32 n, u64 C, u32 extBits, u32 cosetCount, bool coefIn, const PlanO
         if (need > 16) return fail(PIL2GL_EINVAL, "lde tile too tall for the thread block (need %u rows per thread)", need);
         const u64 blocks = (totalGroups / L.g.nbT) * L.g.nColChunks;
         L.blocks = (u32)blocks;
+        L.groupTiles = (u32)(totalGroups / L.g.nbT);
+        plan_walk(L, L.groupTiles);
         P2_TRY(check_launch(L, blocks));
     }
     const int np = split_bits(n - kf, kmaxF, ks);
@@ -663,11 +739,10 @@ int launch_pass(const Launch &L, const u64 *src, u64 *dst, u64 C, u32 n, u64 sca
     P.tw = inverse ? tables().powWi : tables().powW;
     P.twK = inverse ? tables().tw1024i : tables().tw1024;
     P.C = C; P.scale = scale; P.k = k; P.logM = lo + k; P.hasTw = lo > 0; P.dit = L.kind == PASS_DIT; P.n = n; P.scatter = L.scatter;
-    u64 totalGroups;
-    if (lo > 0) { P.tStride = (C << lo); P.gStride = C; P.hiStride = (C << (lo + k)); totalGroups = 1ull << lo; }
-    else { P.tStride = C; P.gStride = (C << k); P.hiStride = 0; totalGroups = 1ull << (n - k); }
-    P.Wc = L.g.Wc; P.nbT = L.g.nbT; P.nColChunks = L.g.nColChunks; P.nGroupTiles = (u32)(totalGroups / L.g.nbT);
-    const dim3 grid(L.blocks), block(L.g.S, L.g.by);
+    if (lo > 0) { P.tStride = (C << lo); P.gStride = C; P.hiStride = (C << (lo + k)); }
+    else { P.tStride = C; P.gStride = (C << k); P.hiStride = 0; }
+    P.Wc = L.g.Wc; P.nbT = L.g.nbT; P.nColChunks = L.g.nColChunks; P.nGroupTiles = L.groupTiles; P.walk = L.walk;
+    const dim3 grid(L.grid), block(L.g.S, L.g.by);
 #define PASS_CASE(INV_, DIT_)                                                                             \
     switch (L.fixedSlots) {                                                                               \
     case 16: P2_TRY(set_lds((const void *)ntt_pass_kernel<INV_, DIT_, 8, 16>, L.ldsBytes));                \
@@ -688,7 +763,8 @@ int launch_pass(const Launch &L, const u64 *src, u64 *dst, u64 C, u32 n, u64 sca
 
 int launch_mid(const Launch &L, LdeParams &P, hipStream_t st) {
     P.k = L.k; P.canonOut = L.canonOut; P.Wc = L.g.Wc; P.G = L.g.nbT; P.nColChunks = L.g.nColChunks;
-    const dim3 grid(L.blocks), block(L.g.S, L.g.by);
+    P.nTiles = L.groupTiles;
+    const dim3 grid(L.grid), block(L.g.S, L.g.by);
 #define LDE_CASE(E_)                                                                              \
     if (!L.fixedSlots && L.ept == E_) {                                                           \
         P2_TRY(set_lds((const void *)lde_mid_kernel<E_, 0>, L.ldsBytes));                          \
@@ -821,15 +897,27 @@ static int check_coset_args(const void *src, const void *dst, uint32_t nBits, ui
 
 extern "C" {
 
-// test hook (host only, no device): the launches ntt_launch / lde_launch make for this call, under the environment's test hooks
+// test hooks (host only, no device): the launches ntt_launch / lde_launch make for this call, under the environment's test hooks, and how
+// those launches walk their column chunks
+namespace {
+int plan_for_debug(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount, Plan &p) {
+    if (op > PIL2GL_PLAN_EXTEND_COEFS) return fail(PIL2GL_EINVAL, "unknown transform %u", op);
+    if (nBits > PIL2GL_MAX_NTT_BITS || nBitsExt < nBits || nBitsExt - nBits > 31) return fail(PIL2GL_EINVAL, "nBits %u, nBitsExt %u", nBits, nBitsExt);
+    if (op <= PIL2GL_PLAN_IFFT) return plan_ntt(nBits, nPols, op == PIL2GL_PLAN_IFFT, plan_options(), p);
+    return plan_lde(nBits, nPols, nBitsExt - nBits, cosetCount, op == PIL2GL_PLAN_EXTEND_COEFS, plan_options(), p);
+}
+struct WalkShape { u32 grid, walk, rowTiles, nGroupTiles, nColChunks; };
+// what launch_pass / launch_mid hand walk_at for this launch
+WalkShape walk_shape(const Launch &L) {
+    return {L.grid, L.walk, L.blocks / L.g.nColChunks, L.groupTiles, L.g.nColChunks};
+}
+}  // namespace
+
 int pil2gl_debug_plan_transform(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount,
                                 uint32_t *out, uint32_t maxLaunches, uint32_t *nLaunches) {
     if (!nLaunches || (!out && maxLaunches)) return fail(PIL2GL_EINVAL, "null argument");
-    if (op > PIL2GL_PLAN_EXTEND_COEFS) return fail(PIL2GL_EINVAL, "unknown transform %u", op);
-    if (nBits > PIL2GL_MAX_NTT_BITS || nBitsExt < nBits || nBitsExt - nBits > 31) return fail(PIL2GL_EINVAL, "nBits %u, nBitsExt %u", nBits, nBitsExt);
     Plan p;
-    if (op <= PIL2GL_PLAN_IFFT) P2_TRY(plan_ntt(nBits, nPols, op == PIL2GL_PLAN_IFFT, plan_options(), p));
-    else P2_TRY(plan_lde(nBits, nPols, nBitsExt - nBits, cosetCount, op == PIL2GL_PLAN_EXTEND_COEFS, plan_options(), p));
+    P2_TRY(plan_for_debug(op, nBits, nPols, nBitsExt, cosetCount, p));
     *nLaunches = (uint32_t)p.n;
     if ((uint32_t)p.n > maxLaunches) return fail(PIL2GL_EINVAL, "%d launches, room for %u", p.n, maxLaunches);
     for (int i = 0; i < p.n; i++) {
@@ -838,6 +926,62 @@ int pil2gl_debug_plan_transform(uint32_t op, uint32_t nBits, uint64_t nPols, uin
                                                       L.ldsBytes, L.blocks, L.scatter, L.canonOut};
         for (int j = 0; j < PIL2GL_PLAN_LAUNCH_WORDS; j++) out[i * PIL2GL_PLAN_LAUNCH_WORDS + j] = r[j];
     }
+    return PIL2GL_OK;
+}
+
+int pil2gl_debug_plan_transform_grid(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount,
+                                     uint32_t *out, uint32_t maxLaunches, uint32_t *nLaunches) {
+    if (!nLaunches || (!out && maxLaunches)) return fail(PIL2GL_EINVAL, "null argument");
+    Plan p;
+    P2_TRY(plan_for_debug(op, nBits, nPols, nBitsExt, cosetCount, p));
+    *nLaunches = (uint32_t)p.n;
+    if ((uint32_t)p.n > maxLaunches) return fail(PIL2GL_EINVAL, "%d launches, room for %u", p.n, maxLaunches);
+    for (int i = 0; i < p.n; i++) {
+        const WalkShape w = walk_shape(p.l[i]);
+        const uint32_t r[PIL2GL_PLAN_GRID_WORDS] = {w.grid, w.walk, w.rowTiles, w.nGroupTiles, w.nColChunks};
+        for (int j = 0; j < PIL2GL_PLAN_GRID_WORDS; j++) out[i * PIL2GL_PLAN_GRID_WORDS + j] = r[j];
+    }
+    return PIL2GL_OK;
+}
+
+int pil2gl_debug_transform_walk(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount, uint32_t launch,
+                                uint32_t firstBlock, uint32_t count, uint32_t *out) {
+    if (!out) return fail(PIL2GL_EINVAL, "null argument");
+    Plan p;
+    P2_TRY(plan_for_debug(op, nBits, nPols, nBitsExt, cosetCount, p));
+    if (launch >= (uint32_t)p.n) return fail(PIL2GL_EINVAL, "launch %u of %d", launch, p.n);
+    const WalkShape w = walk_shape(p.l[launch]);
+    if ((uint64_t)firstBlock + count > w.grid) return fail(PIL2GL_EINVAL, "workgroups [%u, +%u) of %u", firstBlock, count, w.grid);
+    for (uint32_t b = 0; b < count; b++)
+        for (uint32_t s = 0; s < w.walk; s++) {
+            uint32_t *o = out + ((size_t)b * w.walk + s) * 3;
+            if (!walk_at(firstBlock + b, w.grid, s, w.walk, w.nColChunks, w.nGroupTiles, o[0], o[1], o[2])) o[0] = o[1] = o[2] = 0xffffffffu;
+        }
+    return PIL2GL_OK;
+}
+
+int pil2gl_debug_transform_walk_cover(uint32_t op, uint32_t nBits, uint64_t nPols, uint32_t nBitsExt, uint32_t cosetCount, uint32_t launch,
+                                      uint64_t *counts) {
+    if (!counts) return fail(PIL2GL_EINVAL, "null argument");
+    Plan p;
+    P2_TRY(plan_for_debug(op, nBits, nPols, nBitsExt, cosetCount, p));
+    if (launch >= (uint32_t)p.n) return fail(PIL2GL_EINVAL, "launch %u of %d", launch, p.n);
+    const Launch &L = p.l[launch];
+    const WalkShape w = walk_shape(L);
+    uint64_t *seen = (uint64_t *)calloc(((size_t)L.blocks + 63) / 64, 8);
+    if (!seen) return fail(PIL2GL_EINVAL, "out of memory");
+    uint64_t once = 0, extra = 0;
+    for (uint32_t b = 0; b < w.grid; b++) {
+        uint32_t hi, gt, cc;
+        for (uint32_t s = 0; walk_at(b, w.grid, s, w.walk, w.nColChunks, w.nGroupTiles, hi, gt, cc); s++) {
+            const uint64_t rowTile = (uint64_t)hi * w.nGroupTiles + gt, cell = rowTile * w.nColChunks + cc;
+            if (gt >= w.nGroupTiles || rowTile >= w.rowTiles || (seen[cell >> 6] >> (cell & 63) & 1)) { extra++; continue; }
+            seen[cell >> 6] |= 1ull << (cell & 63);
+            once++;
+        }
+    }
+    free(seen);
+    counts[0] = once; counts[1] = L.blocks - once; counts[2] = extra;
     return PIL2GL_OK;
 }
 

@@ -146,6 +146,9 @@ SIGNATURES = {
     "pil2gl_debug_jit_compile": (_I, [C.POINTER(GlxProgram), C.POINTER(GlxCtx), C.POINTER(_U64), C.POINTER(_U32)]),
     "pil2gl_debug_plan_program": (_I, [C.POINTER(GlxProgram), C.POINTER(GlxCtx), C.POINTER(_U32)]),
     "pil2gl_debug_plan_transform": (_I, [_U32, _U32, _U64, _U32, _U32, C.POINTER(_U32), _U32, C.POINTER(_U32)]),
+    "pil2gl_debug_plan_transform_grid": (_I, [_U32, _U32, _U64, _U32, _U32, C.POINTER(_U32), _U32, C.POINTER(_U32)]),
+    "pil2gl_debug_transform_walk": (_I, [_U32, _U32, _U64, _U32, _U32, _U32, _U32, _U32, vp]),
+    "pil2gl_debug_transform_walk_cover": (_I, [_U32, _U32, _U64, _U32, _U32, _U32, C.POINTER(_U64)]),
     "pil2gl_gprod_dev": (_I, [vp, _U32, vp, _U32, _U64, vp, vp]),
     "pil2gl_gsum_dev": (_I, [vp, _U32, vp, _U32, _U64, vp, vp]),
     "pil2gl_h1h2_dev": (_I, [vp, vp, _U64, _U32, vp, vp, vp]),
