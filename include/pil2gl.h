@@ -500,8 +500,40 @@ int pil2gl_bn128_g1_msm_dev(const uint64_t *bases, const uint64_t *scalars, uint
                             uint64_t *out, void *stream);
 /* host-only, no device: how an MSM of n points runs.  out[0] = c, the window width in bits; [1] = nWindows = ceil(255 / c); [2] = buckets
  * per window = 2^(c-1) (signed digits); [3] = windows whose point lists are built and accumulated per pass.  *scratchBytes = the working
- * buffer, at most 4 * clamp(8 n, 2^19, 2^30) + 96 MiB (0 for n = 0).  n > 2^28 is PIL2GL_EINVAL. */
+ * buffer, at most 4 * clamp(8 n, 2^19, 2^30) + 96 MiB (0 for n = 0).  n > 2^28 is PIL2GL_EINVAL.  The batch of one polynomial. */
 int pil2gl_debug_bn128_msm_plan(uint64_t n, uint32_t *out, uint64_t *scratchBytes);
+/* ---- BN254 G1 stage commit: K packed polynomials over the same bases in one call (csrc/bn_msm.hip, csrc/bn_msm_batch.h) -----------
+ * What fflonk's commit(stage, ...) computes for a stage (extendAndCommit, fflonk_prover_helpers.js:303-336; computeQFflonk's commit,
+ * :185; fflonk_setup.js:52) straight from the row-major coefficient matrix pil2gl_bn128_ifft left: no packed copy of the polynomials is
+ * built.  Packed polynomial k is fflonk's CPolynomial f_k(X) = sum_j X^j p_j(X^m): it has n_k = m_k * rows_k coefficients; coefficient
+ * i sits in slot j = i mod m_k and row t = i div m_k, and is 0 when the slot is empty, else element
+ * polys[k].first + t * rowStride + slot (elements of 4 words).  Polynomial k's m_k slots are the next m_k entries of `slots`, each a
+ * column index below rowStride or PIL2GL_G1_EMPTY_SLOT.  out[8 k ..] = toAffine(sum_i coef_k[i] * bases[i]) in the format above, all
+ * zero for the empty sum; every polynomial indexes bases from 0.  m = 1 with one slot is the strided MSM above; rowStride = 1, m = 1 and
+ * different `first` commits pieces of one coefficient vector.  Formats of bases and scalars, scalarsMontgomery, the alignment of the
+ * _dev form, its enqueue-only behaviour and the shared working buffer (pil2gl_debug_bn128_msm_batch_plan's scratchBytes) are those of
+ * pil2gl_bn128_g1_msm.
+ * Refused with PIL2GL_EINVAL before any device call, nothing written: K outside 1..16; m_k outside 1..64; sum m_k > 256;
+ * n_k > nBases; sum n_k > 2^28; rowStride outside 1..2^32-1; first >= 2^58; a slot that is neither the marker nor below rowStride; a
+ * null polys, slots or out, null bases with a point, null scalars with a slot in use.  rows_k = 0 is legal (the zero point); a batch
+ * without any point needs no device in the host form.  The host form stages the bases up to the largest n_k, the scalars up to the last
+ * element any descriptor reaches, and out through device copies; neither form can check how far bases and scalars extend. */
+#define PIL2GL_G1_EMPTY_SLOT 0xFFFFFFFFu
+typedef struct { uint64_t first, rows; uint32_t m, reserved; } pil2gl_g1_poly;
+int pil2gl_bn128_g1_commit(const uint64_t *bases, uint64_t nBases, const uint64_t *scalars, uint64_t rowStride, uint32_t scalarsMontgomery,
+                           const pil2gl_g1_poly *polys, uint32_t K, const uint32_t *slots, uint64_t *out);
+int pil2gl_bn128_g1_commit_dev(const uint64_t *bases, uint64_t nBases, const uint64_t *scalars, uint64_t rowStride, uint32_t scalarsMontgomery,
+                               const pil2gl_g1_poly *polys, uint32_t K, const uint32_t *slots, uint64_t *out, void *stream);
+/* host-only, no device: how a batch of K MSMs of counts[k] points runs: out[0..3] as pil2gl_debug_bn128_msm_plan's, one window width for
+ * the batch (from the largest count, lowered while K * out[1] * out[2] bucket points exceed 9 * 2^19) and out[3] windows per pass (from the
+ * total count, K * out[3] * out[2] <= 2^18 histogram cells).  *scratchBytes = the working buffer, at most
+ * 4 * clamp(8 N, 2^19, 2^30) + 96 MiB * min(K, 9), N the total count (0 for N = 0).  K = 1 equals pil2gl_debug_bn128_msm_plan.
+ * K outside 1..16 or N > 2^28 is PIL2GL_EINVAL. */
+int pil2gl_debug_bn128_msm_batch_plan(uint32_t K, const uint64_t *counts, uint32_t *out, uint64_t *scratchBytes);
+/* host-only, no device: where point lane `lane` of a batch (described as for pil2gl_bn128_g1_commit) lies, by the code the kernels run:
+ * out[0] = k, out[1] = i, out[2] = 1 and out[3] = the scalar's element offset, or out[2] = out[3] = 0 for an empty slot.  A lane at or
+ * past sum n_k and every descriptor the commit refuses (n_k is checked against 2^28 only) is PIL2GL_EINVAL. */
+int pil2gl_debug_bn128_commit_locate(const pil2gl_g1_poly *polys, uint32_t K, const uint32_t *slots, uint64_t rowStride, uint64_t lane, uint64_t out[4]);
 /* host-only, no device: the signed digits the kernels split a scalar into (normal form, below 2^254) for windows of c bits, least
  * significant first, by the code the kernels run: *nDigits = ceil(255 / c) of them (room entries available), each in
  * [-(2^(c-1) - 1), 2^(c-1)], sum_w digits[w] 2^(c w) = scalar.  c outside 4..16, a larger scalar or too little room: PIL2GL_EINVAL

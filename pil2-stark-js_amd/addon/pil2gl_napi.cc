@@ -222,6 +222,30 @@ FN(Bn128G1MsmDev) {      // (dBases, dScalars, n, scalarStride, scalarsMontgomer
     P2(env, pil2gl_bn128_g1_msm_dev(b, s, n, stride, (uint32_t)mont, o, a.stream(6))); return mk_undefined(env);
 }
 
+// K packed polynomials over the same bases, K * 8 words written on the device
+// (dBases, nBases, dScalars, rowStride, scalarsMontgomery, polys BigUint64Array of (first, rows, m) per polynomial, slots BigUint64Array of one
+//  column index or 0xFFFFFFFF per slot, dOut[, stream])
+FN(Bn128G1CommitDev) {
+    Args a(env, info); uint64_t *b = DP(0); uint64_t nBases = a.u64(1); uint64_t *s = DP(2); uint64_t stride = a.u64(3), mont = a.u64(4);
+    uint64_t nDesc = 0, nSlots = 0;
+    uint64_t *desc = a.arr(5, 0, &nDesc), *slotWords = a.arr(6, 0, &nSlots); uint64_t *o = DP(7);
+    if (a.ok && (nDesc % 3 || nDesc > 3 * 64)) a.fail("polys must hold (first, rows, m) per polynomial");
+    if (a.ok && nSlots > 4096) a.fail("too many slots");
+    if (!a.ok) return nullptr;
+    std::vector<pil2gl_g1_poly> polys(nDesc / 3 + 1);
+    std::vector<uint32_t> slots(nSlots + 1);
+    uint64_t need = 0;
+    for (uint64_t k = 0; k < nDesc / 3; k++) {
+        polys[k].first = desc[3 * k]; polys[k].rows = desc[3 * k + 1]; polys[k].reserved = 0;
+        polys[k].m = desc[3 * k + 2] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)desc[3 * k + 2];
+        need += polys[k].m;
+    }
+    if (need > nSlots) { a.fail("slots hold fewer entries than the polynomials name"); return nullptr; }
+    for (uint64_t j = 0; j < nSlots; j++) slots[j] = slotWords[j] > 0xFFFFFFFFull ? 0xFFFFFFFEu : (uint32_t)slotWords[j];      // too large: refused by the library as a column
+    P2(env, pil2gl_bn128_g1_commit_dev(b, nBases, s, stride, (uint32_t)mont, polys.data(), (uint32_t)(nDesc / 3), slots.data(), o, a.stream(8)));
+    return mk_undefined(env);
+}
+
 // ---- BN254 Fr expression evaluator (calculateExps over curve.Fr): device sections, Montgomery scalars ----
 // (opsBuf BigUint64Array = packed glx_op[], nOps, nTmp, nBits, primeShift, sectionPtrs BigUint64Array, sectionWidths BigUint64Array in elements,
 //  scalars BigUint64Array of 4 words per element[, stream])
@@ -650,7 +674,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128RootsFromGroupProofs", Bn128RootsFromGroupProofs }, { "bn128Convert", Bn128Convert },
         { "bn128Fft", Bn128Fft }, { "bn128Ifft", Bn128Ifft }, { "bn128Interpolate", Bn128Interpolate },
         { "bn128FftDev", Bn128FftDev }, { "bn128IfftDev", Bn128IfftDev }, { "bn128InterpolateDev", Bn128InterpolateDev },
-        { "bn128G1MsmDev", Bn128G1MsmDev }, { "bn128EvalProgramDev", Bn128EvalProgramDev }, { "bn128FirstNonzeroRowDev", Bn128FirstNonzeroRowDev },
+        { "bn128G1MsmDev", Bn128G1MsmDev }, { "bn128G1CommitDev", Bn128G1CommitDev }, { "bn128EvalProgramDev", Bn128EvalProgramDev }, { "bn128FirstNonzeroRowDev", Bn128FirstNonzeroRowDev },
         { "bn128PolyDivDev", Bn128PolyDivDev }, { "bn128PolyEvalDev", Bn128PolyEvalDev },
         { "bn128PolyFmaDev", Bn128PolyFmaDev }, { "bn128PolyDegreeDev", Bn128PolyDegreeDev },
         { "bn128BatchInverseDev", Bn128BatchInverseDev }, { "bn128GprodDev", Bn128GprodDev }, { "bn128GsumDev", Bn128GsumDev },

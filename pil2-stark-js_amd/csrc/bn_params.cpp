@@ -395,30 +395,36 @@ int bn_ntt_plan(unsigned nBits, unsigned *layers) {
 }
 
 // ------------------------------------------------------------------------------------------ the G1 MSM
-BnMsmPlan bn_msm_plan(uint64_t n) {
-    if (n == 0) n = 1;
+BnMsmPlan bn_msm_batch_plan(uint32_t K, const uint64_t *counts) {
+    uint64_t N = 0, nMax = 1;
+    for (uint32_t k = 0; k < K; k++) { N += counts[k]; nMax = std::max(nMax, counts[k]); }
+    if (N == 0) N = 1;
+    if (K == 0) K = 1;
     BnMsmPlan p;
     uint32_t lg = 0;
-    while ((n >> lg) > 1) lg++;
+    while ((nMax >> lg) > 1) lg++;
     p.c = lg < bnm::MSM_MIN_C + 3 ? bnm::MSM_MIN_C : (lg - 3 > bnm::MSM_MAX_C ? bnm::MSM_MAX_C : lg - 3);
-    p.nWindows = (bnm::MSM_SCALAR_BITS + 1 + p.c - 1) / p.c;
+    auto windows = [](uint32_t c) { return (bnm::MSM_SCALAR_BITS + 1 + c - 1) / c; };
+    while (p.c > bnm::MSM_MIN_C && (uint64_t)K * windows(p.c) << (p.c - 1) > BN_MSM_BUCKET_BUDGET) p.c--;
+    p.nWindows = windows(p.c);
     p.bucketsPerWindow = 1u << (p.c - 1);
     const uint64_t lo = 1ull << 19, hi = 1ull << 30;
-    const uint64_t room = std::min(std::max(8 * n, lo), hi) / n;         // entries / n >= 1 for n <= 2^30
+    const uint64_t room = std::min(std::max(8 * N, lo), hi) / N;         // entries / N >= 1 for N <= 2^30
+    auto cells = [&](uint32_t g) { return (uint64_t)K * std::min(g, p.nWindows) * p.bucketsPerWindow; };
     uint32_t g = 1;
-    while (2ull * g <= room && 2 * g <= bnm::MSM_MAX_WINDOWS) g *= 2;
+    while (2ull * g <= room && 2 * g <= bnm::MSM_MAX_WINDOWS && cells(2 * g) <= BN_MSM_PASS_CELLS) g *= 2;
     p.windowsPerPass = std::min(g, p.nWindows);
     p.m1 = (p.bucketsPerWindow + BN_MSM_L1 - 1) / BN_MSM_L1;
     p.m2 = (p.m1 + BN_MSM_L - 1) / BN_MSM_L;
     auto up16 = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint64_t nbPass = (uint64_t)p.windowsPerPass * p.bucketsPerWindow;
+    const uint64_t nbPass = cells(p.windowsPerPass), items = (uint64_t)K * p.nWindows;
     p.offHist = 0;
     p.offCursor = up16((nbPass + 1) * 4);
     p.offEntries = p.offCursor + up16(nbPass * 4);
-    p.offBuckets = p.offEntries + up16(n * p.windowsPerPass * 4);
-    p.offLevelA = p.offBuckets + (uint64_t)p.nWindows * p.bucketsPerWindow * 128;
-    p.offLevelB = p.offLevelA + 2ull * p.nWindows * p.m1 * 128;
-    p.scratchBytes = p.offLevelB + 2ull * p.nWindows * p.m2 * 128;
+    p.offBuckets = p.offEntries + up16(N * p.windowsPerPass * 4);
+    p.offLevelA = p.offBuckets + items * p.bucketsPerWindow * 128;
+    p.offLevelB = p.offLevelA + 2 * items * p.m1 * 128;
+    p.scratchBytes = p.offLevelB + 2 * items * p.m2 * 128;
     return p;
 }
 

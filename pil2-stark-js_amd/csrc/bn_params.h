@@ -57,21 +57,30 @@ void bn_powers(const U256 &g, size_t n, U256 *out);
 int bn_ntt_plan(unsigned nBits, unsigned *layers);
 
 // ---- the G1 multi-scalar multiplication (bn_msm.hip) ----
-// How an MSM of n points runs (n = 0 plans as n = 1): windows of c bits (signed digits, bn_msm_recode.h), nWindows = ceil(255 / c) of them,
-// bucketsPerWindow = 2^(c-1); c = floor(log2 n) - 3 within [4, 16].  The point lists of windowsPerPass windows are built and accumulated
-// at a time: the largest power of two that keeps n * windowsPerPass list entries within clamp(8 n, 2^19, 2^30), at most nWindows.
-// The working buffer, in bytes from its start (every region 16-byte aligned):
-//   offHist     windowsPerPass * bucketsPerWindow + 1 u32: the pass's histogram, then its exclusive scan (the last entry: the total)
+// How a batch of K MSMs over the same bases runs, polynomial k of counts[k] points (K = 1 is the single MSM; a batch without points plans
+// as one point): windows of c bits (signed digits, bn_msm_recode.h), nWindows = ceil(255 / c) of them, bucketsPerWindow = 2^(c-1), one c
+// for the batch: floor(log2 max_k counts[k]) - 3 within [4, 16], lowered while K * nWindows * bucketsPerWindow bucket points exceed
+// BN_MSM_BUCKET_BUDGET = 9 * 2^19 (never for K = 1: 16 windows of 2^15 buckets are 2^19; only from 16 to 15, for K >= 10: sixteen
+// polynomials fit at c = 15.  The budget is this large on purpose: the widths below 15 have a top window of few scalar bits -- c = 14
+// keeps 2 of them -- so that a few buckets take a quarter of a polynomial's points each, one lane adding them one after the other).  The point lists of windowsPerPass windows of every
+// polynomial are built and accumulated at a time: the largest power of two that keeps N * windowsPerPass list entries, N = sum_k
+// counts[k], within clamp(8 N, 2^19, 2^30) and K * windowsPerPass * bucketsPerWindow histogram cells within BN_MSM_PASS_CELLS (what
+// the one-workgroup scan is given; K = 1 never reaches it), at most nWindows.
+// The working buffer, in bytes from its start (every region 16-byte aligned); window w of polynomial k is item w * K + k throughout:
+//   offHist     K * windowsPerPass * bucketsPerWindow + 1 u32: the pass's histogram, then its exclusive scan (the last entry: the total)
 //   offCursor   one u32 per bucket of the pass: where the scatter writes next
-//   offEntries  n * windowsPerPass u32: point index | sign << 31, grouped by bucket
-//   offBuckets  nWindows * bucketsPerWindow points of 128 bytes (X, Y, ZZ, ZZZ): every window's bucket sums
-//   offLevelA / offLevelB   the reduction's levels (X then Y, nWindows * m1 resp. nWindows * m2 points each), used alternately
-// scratchBytes <= 4 * clamp(8 n, 2^19, 2^30) + 96 MiB for every n <= 2^28.
+//   offEntries  N * windowsPerPass u32: point index within its polynomial | sign << 31, grouped by bucket
+//   offBuckets  K * nWindows * bucketsPerWindow points of 128 bytes (X, Y, ZZ, ZZZ): every window's bucket sums
+//   offLevelA / offLevelB   the reduction's levels (X then Y, K * nWindows * m1 resp. K * nWindows * m2 points each), used alternately
+// scratchBytes <= 4 * clamp(8 N, 2^19, 2^30) + 96 MiB * min(K, 9) for every K <= 16 and N <= 2^28: the lists, then 2 MiB of histogram
+// and cursors, and buckets and levels of at most min(K, 9) * 2^19 bucket points at 128 * (1 + 2/8 + 2/128) bytes and a little.
 constexpr uint32_t BN_MSM_L1 = 8, BN_MSM_L = 16;     // buckets per lane in the reduction's first level / items per lane in the later ones
+constexpr uint64_t BN_MSM_BUCKET_BUDGET = 9ull << 19, BN_MSM_PASS_CELLS = 1ull << 18;
 struct BnMsmPlan {
     uint32_t c, nWindows, bucketsPerWindow, windowsPerPass, m1, m2;
     uint64_t offHist, offCursor, offEntries, offBuckets, offLevelA, offLevelB, scratchBytes;
 };
-BnMsmPlan bn_msm_plan(uint64_t n);
+BnMsmPlan bn_msm_batch_plan(uint32_t K, const uint64_t *counts);
+inline BnMsmPlan bn_msm_plan(uint64_t n) { return bn_msm_batch_plan(1, &n); }
 
 }  // namespace bnp

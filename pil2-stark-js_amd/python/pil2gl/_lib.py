@@ -51,6 +51,11 @@ class EvalDesc(C.Structure):
                 ("dim", C.c_uint32), ("levIndex", C.c_uint32)]
 
 
+class G1Poly(C.Structure):
+    """include/pil2gl.h pil2gl_g1_poly: one packed polynomial of a G1 commit batch"""
+    _fields_ = [("first", C.c_uint64), ("rows", C.c_uint64), ("m", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # name -> (restype, argtypes); pointers that may be host or device are c_void_p
 _U64, _U32, _I = C.c_uint64, C.c_uint32, C.c_int
 SIGNATURES = {
@@ -177,6 +182,10 @@ SIGNATURES = {
     "pil2gl_bn128_g1_msm": (_I, [vp, vp, _U64, _U64, _U32, vp]),
     "pil2gl_bn128_g1_msm_dev": (_I, [vp, vp, _U64, _U64, _U32, vp, vp]),
     "pil2gl_debug_bn128_msm_plan": (_I, [_U64, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_bn128_g1_commit": (_I, [vp, _U64, vp, _U64, _U32, C.POINTER(G1Poly), _U32, C.POINTER(_U32), vp]),
+    "pil2gl_bn128_g1_commit_dev": (_I, [vp, _U64, vp, _U64, _U32, C.POINTER(G1Poly), _U32, C.POINTER(_U32), vp, vp]),
+    "pil2gl_debug_bn128_msm_batch_plan": (_I, [_U32, C.POINTER(_U64), C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_debug_bn128_commit_locate": (_I, [C.POINTER(G1Poly), _U32, C.POINTER(_U32), _U64, _U64, C.POINTER(_U64)]),
     "pil2gl_debug_bn128_msm_digits": (_I, [C.POINTER(_U64), _U32, C.POINTER(C.c_int32), _U32, C.POINTER(_U32)]),
     "pil2gl_bn128_eval_program": (_I, [C.POINTER(GlxProgram), C.POINTER(BnxCtx)]),
     "pil2gl_bn128_eval_program_dev": (_I, [C.POINTER(GlxProgram), C.POINTER(BnxCtx), vp]),

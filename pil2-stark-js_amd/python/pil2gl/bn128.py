@@ -5,6 +5,8 @@
   poseidon(inputs, initState, nOut) <-> circomlibjs buildPoseidon() as the reference calls it
   fft / ifft / interpolate        <-> src/helpers/fft/fft_p.bn128.js:178-285 (Montgomery words in and out)
   g1_msm                          <-> G1.toAffine(G1.multiExpAffine(bases, scalars)) of ffjavascript, the fflonk commit
+  g1_commit                       <-> the G1 points of fflonk's commit(stage, ...): several packed polynomials (CPolynomial) in one call,
+                                      read as columns of the coefficient matrix ifft left
   encode_program / eval_program / first_nonzero_row
                                   <-> src/prover/prover_helpers.js:31-259 calculateExps over ctx.F = curve.Fr (Montgomery words in and out)
   poly_div / poly_eval / poly_plan <-> Polynomial.divZh / divByXNSubValue / evaluate as fflonk_prover_helpers.js:147-148, :212 use them
@@ -18,7 +20,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import Pil2glError, load, call
+from ._lib import Pil2glError, G1Poly, load, call
 from . import _is_dev, _ptr, _stream, _check_len, _to_host, torch
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -147,6 +149,46 @@ def g1_msm(bases, scalars, n=None, stride=1, montgomery=True, out=None):
         call("pil2gl_bn128_g1_msm_dev", _ptr(bases), _ptr(scalars), n, stride, 1 if montgomery else 0, _ptr(out), _stream())
     else:
         call("pil2gl_bn128_g1_msm", _ptr(bases), _ptr(scalars), n, stride, 1 if montgomery else 0, _ptr(out))
+    return out
+
+
+EMPTY_SLOT = 0xFFFFFFFF
+
+
+def g1_commit(bases, scalars, polys, row_stride, montgomery=True, out=None):
+    """The commitments of K packed polynomials over the same bases in one call.  scalars = a row-major matrix of Fr elements (4 words
+    each), row_stride elements per row; polys = [(first, rows, slots)]: polynomial k has len(slots) * rows coefficients, coefficient i is
+    the element first + (i div m) * row_stride + slots[i mod m], or 0 where that slot is None (fflonk's CPolynomial).  numpy arrays or
+    device tensors, all of one kind.  -> (K, 8) words of the same kind, or `out`: toAffine(sum_i coef_k[i] * bases[i]) per polynomial"""
+    if _is_dev(bases) != _is_dev(scalars) or (out is not None and _is_dev(out) != _is_dev(bases)):
+        raise Pil2glError("mixing host and device buffers in one call")
+    K = len(polys)
+    descs, flat, extent, n_max = (G1Poly * max(K, 1))(), [], 0, 0
+    for k, (first, rows, slots) in enumerate(polys):
+        first, rows = int(first), int(rows)
+        if first < 0 or rows < 0:
+            raise Pil2glError("polynomial %d: negative first or rows" % k)
+        descs[k].first, descs[k].rows, descs[k].m = first, rows, len(slots)
+        cols = [int(c) for c in slots if c is not None]
+        if any(c < 0 or c >= EMPTY_SLOT for c in cols):
+            raise Pil2glError("polynomial %d: bad column index" % k)
+        flat += [EMPTY_SLOT if c is None else int(c) for c in slots]
+        n_max = max(n_max, rows * len(slots))
+        if rows and cols:
+            extent = max(extent, first + (rows - 1) * int(row_stride) + max(cols) + 1)
+    n_bases = int(np.prod(bases.shape)) // 8
+    if n_max > n_bases:
+        raise Pil2glError("a polynomial of %d coefficients, bases hold %d points" % (n_max, n_bases))
+    _check_len(scalars, 4 * extent, "scalars")         # the C entry cannot know how far the buffers extend
+    c_slots = (C.c_uint32 * max(len(flat), 1))(*flat)
+    if out is None:
+        out = torch.empty((K, 8), dtype=bases.dtype, device=bases.device) if _is_dev(bases) else np.empty((K, 8), np.uint64)
+    _check_len(out, 8 * K, "out")
+    args = [_ptr(bases), n_bases, _ptr(scalars), int(row_stride), 1 if montgomery else 0, descs, K, c_slots, _ptr(out)]
+    if _is_dev(bases):
+        call("pil2gl_bn128_g1_commit_dev", *args, _stream())
+    else:
+        call("pil2gl_bn128_g1_commit", *args)
     return out
 
 
