@@ -13,26 +13,7 @@
 // { byteLength, slice(a, b) -> Uint8Array }, staged in 256 MB pieces.  Returns a Promise of the 64-byte affine point as a Uint8Array.
 "use strict";
 const { addon, isDev } = require("./native.js");
-
-const CHUNK_BYTES = 1 << 28;
-
-function asWords(u8) {       // a BigUint64Array over the same bytes where alignment allows, over a copy otherwise
-    if (u8.byteOffset % 8 === 0) return new BigUint64Array(u8.buffer, u8.byteOffset, u8.byteLength / 8);
-    const c = new Uint8Array(u8.byteLength); c.set(u8);
-    return new BigUint64Array(c.buffer);
-}
-function byteLength(buf) { return isDev(buf) ? buf.length * 8 : buf.byteLength; }
-
-// a host buffer's first `bytes` bytes on the device (freed by the caller through `owned`); a DevBuffer as it is
-function resident(buf, bytes, owned) {
-    if (isDev(buf)) return buf.ptr;
-    const p = addon.devAlloc(Math.max(1, bytes / 8)); owned.push(p);
-    for (let o = 0; o < bytes; o += CHUNK_BYTES) {
-        const e = Math.min(bytes, o + CHUNK_BYTES);
-        addon.devUpload(p, o / 8, asWords(buf instanceof Uint8Array ? buf.subarray(o, e) : buf.slice(o, e)));
-    }
-    return p;
-}
+const { byteLength, scope, input, output } = require("./bn128_stage.js").native();
 
 async function multiExpAffine(bases, scalars, options = {}) {
     const stride = options.stride === undefined ? 1 : options.stride;
@@ -43,17 +24,10 @@ async function multiExpAffine(bases, scalars, options = {}) {
     const scalarBytes = n ? ((n - 1) * stride + 1) * 32 : 0;
     if (byteLength(bases) < n * 64) throw new Error("g1_msm: bases hold " + byteLength(bases) + " bytes, need " + n * 64);
     if (byteLength(scalars) < scalarBytes) throw new Error("g1_msm: scalars hold " + byteLength(scalars) + " bytes, need " + scalarBytes);
-    const owned = [];
-    try {
-        const dBases = resident(bases, n * 64, owned), dScalars = resident(scalars, scalarBytes, owned);
-        const dOut = addon.devAlloc(8); owned.push(dOut);
-        addon.bn128G1MsmDev(dBases, dScalars, n, stride, montgomery ? 1 : 0, dOut);
-        const out = new BigUint64Array(8);
-        addon.devDownload(out, dOut, 0);                 // a synchronous copy: ordered after the kernels
-        return new Uint8Array(out.buffer);
-    } finally {
-        for (const p of owned) addon.devFree(p);
-    }
+    const out = new Uint8Array(64);
+    scope([input(bases, n * 64), input(scalars, scalarBytes), output(out, 64)],
+        ([dBases, dScalars, dOut]) => addon.bn128G1MsmDev(dBases, dScalars, n, stride, montgomery ? 1 : 0, dOut));
+    return out;
 }
 
 const EMPTY_SLOT = 0xFFFFFFFF;
@@ -81,17 +55,10 @@ async function multiExpPacked(bases, coefs, polys, options = {}) {
     });
     if (byteLength(bases) < nMax * 64) throw new Error("g1_msm: bases hold " + byteLength(bases) + " bytes, need " + nMax * 64);
     if (byteLength(coefs) < extent * 32) throw new Error("g1_msm: coefs hold " + byteLength(coefs) + " bytes, need " + extent * 32);
-    const owned = [];
-    try {
-        const dBases = resident(bases, nMax * 64, owned), dCoefs = resident(coefs, extent * 32, owned);
-        const dOut = addon.devAlloc(8 * K); owned.push(dOut);
-        addon.bn128G1CommitDev(dBases, isDev(bases) ? Math.floor(byteLength(bases) / 64) : nMax, dCoefs, stride, montgomery ? 1 : 0, desc, BigUint64Array.from(slots), dOut);
-        const out = new BigUint64Array(8 * K);
-        addon.devDownload(out, dOut, 0);                 // one synchronous copy for all K points: ordered after the kernels
-        return polys.map((_, k) => new Uint8Array(out.buffer, 64 * k, 64));
-    } finally {
-        for (const p of owned) addon.devFree(p);
-    }
+    const out = new Uint8Array(64 * K);                  // all K points come back in one copy
+    scope([input(bases, nMax * 64), input(coefs, extent * 32), output(out, 64 * K)], ([dBases, dCoefs, dOut]) =>
+        addon.bn128G1CommitDev(dBases, isDev(bases) ? Math.floor(byteLength(bases) / 64) : nMax, dCoefs, stride, montgomery ? 1 : 0, desc, BigUint64Array.from(slots), dOut));
+    return polys.map((_, k) => out.subarray(64 * k, 64 * k + 64));
 }
 
 module.exports.multiExpAffine = multiExpAffine;

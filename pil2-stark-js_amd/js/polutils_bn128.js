@@ -15,6 +15,7 @@
 // A zero denominator inverts to zero and stays out of every running product (include/pil2gl.h): its ratio is 0.
 "use strict";
 const { addon, isDev } = require("./native.js");
+const { scope, input, output } = require("./bn128_stage.js").native();
 
 function pack(col, what) {
     const a = new BigUint64Array(4 * col.length);
@@ -26,36 +27,25 @@ function pack(col, what) {
     }
     return a;
 }
-function unpack(a) {
-    const n = a.length / 4, out = new Array(n);
-    for (let i = 0; i < n; i++) out[i] = new Uint8Array(a.buffer.slice(a.byteOffset + 32 * i, a.byteOffset + 32 * i + 32));
-    return out;
-}
-// fn(device addresses of the inputs, device address of the n-element result) -> the result as an array of Uint8Array(32)
-function onDevice(arrays, n, fn) {
-    const ptrs = [];
-    try {
-        for (const a of arrays) { const d = addon.devAlloc(Math.max(1, a.length)); ptrs.push(d); if (a.length) addon.devUpload(d, 0, a); }
-        const dOut = addon.devAlloc(Math.max(1, 4 * n)); ptrs.push(dOut);
-        fn(ptrs.slice(0, arrays.length), dOut);
-        const r = new BigUint64Array(4 * n);
-        if (n) addon.devDownload(r, dOut, 0);                    // a synchronous copy: ordered after the kernels
-        return unpack(r);
-    } finally { for (const d of ptrs) addon.devFree(d); }
+// fn([device addresses of the inputs, then of nOut results of n elements]) -> the results, each an array of Uint8Array(32)
+function onDevice(arrays, n, nOut, fn) {
+    const outs = Array.from({ length: nOut }, () => new Uint8Array(32 * n));
+    scope(arrays.map((a) => input(new Uint8Array(a.buffer), a.byteLength)).concat(outs.map((o) => output(o, o.length))), fn);
+    return outs.map((o) => Array.from({ length: n }, (_, i) => o.slice(32 * i, 32 * i + 32)));
 }
 
 async function calculateZ(F, num, den) {
     const n = den.length;
     if (num.length !== n) throw new Error("polutils_bn128: num and den must have the same length");
-    return onDevice([pack(num, "num"), pack(den, "den")], n, ([dn, dd], dz) => addon.bn128GprodDev(dn, 1, dd, 1, n, dz, 1));
+    return onDevice([pack(num, "num"), pack(den, "den")], n, 1, ([dn, dd, dz]) => addon.bn128GprodDev(dn, 1, dd, 1, n, dz, 1))[0];
 }
 async function calculateS(F, num, den) {
     const n = den.length, c = pack([num], "num");
-    return onDevice([pack(den, "den")], n, ([dd], ds) => addon.bn128GsumDev(c, dd, 1, n, ds, 1));
+    return onDevice([pack(den, "den")], n, 1, ([dd, ds]) => addon.bn128GsumDev(c, dd, 1, n, ds, 1))[0];
 }
 function batchInverse(F, a) {
     const n = a.length;
-    return onDevice([pack(a, "a")], n, ([da], di) => addon.bn128BatchInverseDev(da, 1, n, di, 1));
+    return onDevice([pack(a, "a")], n, 1, ([da, di]) => addon.bn128BatchInverseDev(da, 1, n, di, 1))[0];
 }
 
 // the reference's message for a value t lacks (polutils.js:115): the row, and the element as F.toString gives it -- the decimal normal form of
@@ -72,14 +62,10 @@ function notIncluded(row, e) { return new Error("Number not included: w:" + row 
 function calculateH1H2(F, f, t) {
     const n = t.length;
     if (f.length !== n) throw new Error("polutils_bn128: f and t must have the same length");
-    const ptrs = [];
-    try {
-        for (const a of [pack(f, "f"), pack(t, "t")]) { const d = addon.devAlloc(Math.max(1, a.length)); ptrs.push(d); if (a.length) addon.devUpload(d, 0, a); }
-        for (let k = 0; k < 2; k++) ptrs.push(addon.devAlloc(Math.max(1, 4 * n)));
-        const miss = addon.bn128H1h2Dev(ptrs[0], 1, ptrs[1], 1, n, ptrs[2], 1, ptrs[3], 1);
+    return onDevice([pack(f, "f"), pack(t, "t")], n, 2, ([df, dt, d1, d2]) => {
+        const miss = addon.bn128H1h2Dev(df, 1, dt, 1, n, d1, 1, d2, 1);
         if (miss !== undefined) throw notIncluded(miss, f[Number(miss)]);
-        return [2, 3].map((k) => { const r = new BigUint64Array(4 * n); if (n) addon.devDownload(r, ptrs[k], 0); return unpack(r); });
-    } finally { for (const d of ptrs) addon.devFree(d); }
+    });
 }
 
 // ---- resident columns ----

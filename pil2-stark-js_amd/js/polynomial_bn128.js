@@ -18,17 +18,11 @@
 //   a shifted product is never in place: the result goes to a second buffer (as the reference's byXSubValue fills a new BigBuffer),
 //   which must hold src's coefficients + the largest exponent
 "use strict";
-const { addon, isDev } = require("./native.js");
+const { addon } = require("./native.js");
+const { byteLength, scope, input, output, inout, asWords } = require("./bn128_stage.js").native();
 
-const CHUNK_BYTES = 1 << 28;
 const NONE = 0xFFFFFFFFFFFFFFFFn;
 
-function asWords(u8) {       // a BigUint64Array over the same bytes where alignment allows, over a copy otherwise
-    if (u8.byteOffset % 8 === 0) return new BigUint64Array(u8.buffer, u8.byteOffset, u8.byteLength / 8);
-    const c = new Uint8Array(u8.byteLength); c.set(u8);
-    return new BigUint64Array(c.buffer);
-}
-function byteLength(buf) { return isDev(buf) ? buf.length * 8 : buf.byteLength; }
 function elem(u8, what) {
     if (!(u8 instanceof Uint8Array) || u8.byteLength !== 32) throw new Error("polynomial_bn128: " + what + " must be a Uint8Array of 32 bytes");
     return asWords(u8);
@@ -42,33 +36,12 @@ function shape(buf, opts) {
     if (byteLength(buf) < bytes) throw new Error("polynomial_bn128: the buffer holds " + byteLength(buf) + " bytes, needs " + bytes);
     return { n, stride, bytes };
 }
-// fn(device address of the coefficients); a staged buffer is uploaded first and, with writeBack, downloaded into buf afterwards
-function withResident(buf, bytes, writeBack, fn) {
-    if (isDev(buf)) return fn(buf.ptr);
-    const p = addon.devAlloc(Math.max(1, bytes / 8));
-    try {
-        for (let o = 0; o < bytes; o += CHUNK_BYTES) {
-            const e = Math.min(bytes, o + CHUNK_BYTES);
-            addon.devUpload(p, o / 8, asWords(buf instanceof Uint8Array ? buf.subarray(o, e) : buf.slice(o, e)));
-        }
-        const res = fn(p);
-        for (let o = 0; writeBack && o < bytes; o += CHUNK_BYTES) {
-            const t = new BigUint64Array((Math.min(bytes, o + CHUNK_BYTES) - o) / 8);
-            addon.devDownload(t, p, o / 8);                  // a synchronous copy: ordered after the kernels
-            buf.set(new Uint8Array(t.buffer), o);
-        }
-        return res;
-    } finally {
-        addon.devFree(p);
-    }
-}
-
 // buf <- d, in place; returns buf
 function divByXNSubValue(buf, k, beta, opts = {}) {
     const { n, stride, bytes } = shape(buf, opts);
     if (!Number.isInteger(k) || k < 1) throw new Error("polynomial_bn128: k must be a positive integer");
     const b = elem(beta, "beta");
-    withResident(buf, bytes, true, (p) => addon.bn128PolyDivDev(p, n, stride, k, b, p));
+    scope([inout(buf, bytes)], ([p]) => addon.bn128PolyDivDev(p, n, stride, k, b, p));
     return buf;
 }
 
@@ -80,7 +53,7 @@ function divZh(buf, domainSize, opts = {}) {
     const one = new BigUint64Array(4);
     new Uint8Array(one.buffer).set(ONE_MONT);
     let row = NONE;
-    withResident(buf, bytes, true, (p) => {
+    scope([inout(buf, bytes)], ([p]) => {
         addon.bn128PolyDivDev(p, n, stride, domainSize, one, p);
         row = addon.bn128FirstNonzeroRowDev(p, stride, 0, 0, Math.min(domainSize, n))[0];
     });
@@ -94,15 +67,9 @@ function evaluate(buf, points, opts = {}) {
     if (!Array.isArray(points) || points.length < 1 || points.length > 64) throw new Error("polynomial_bn128: 1 to 64 points per call");
     const z = new BigUint64Array(4 * points.length);
     points.forEach((pt, i) => z.set(elem(pt, "a point"), 4 * i));
-    const dOut = addon.devAlloc(z.length);
-    try {
-        withResident(buf, bytes, false, (p) => addon.bn128PolyEvalDev(p, n, stride, z, dOut));
-        const out = new BigUint64Array(z.length);
-        addon.devDownload(out, dOut, 0);                     // a synchronous copy: ordered after the kernels
-        return points.map((_, i) => new Uint8Array(out.buffer.slice(32 * i, 32 * i + 32)));
-    } finally {
-        addon.devFree(dOut);
-    }
+    const out = new Uint8Array(32 * points.length);
+    scope([input(buf, bytes), output(out, out.length)], ([p, dOut]) => addon.bn128PolyEvalDev(p, n, stride, z, dOut));
+    return points.map((_, i) => out.slice(32 * i, 32 * i + 32));
 }
 
 // 1 in Montgomery form: 2^256 mod r, little-endian
@@ -171,9 +138,9 @@ function fma(acc, src, terms, opts = {}) {
     const { coefs, exps } = packTerms(terms);
     const scale = opts.scale === undefined || opts.scale === null ? null : elem(opts.scale, "scale");
     const run = (pa, ps) => addon.bn128PolyFmaDev(pa, a.n, a.stride, scale, ps, s.n, s.stride, coefs, exps);
-    if (src === acc) withResident(acc, Math.max(a.bytes, s.bytes), true, (p) => run(p, p));
-    else if (s.n === 0) withResident(acc, a.bytes, true, (pa) => run(pa, 0n));
-    else withResident(src, s.bytes, false, (ps) => withResident(acc, a.bytes, true, (pa) => run(pa, ps)));
+    const bufs = [inout(acc, a.bytes)];                      // acc === src is one copy; no src, or an empty one, is address 0
+    if (src === acc || s.n) bufs.push(input(src, s.bytes));
+    scope(bufs, ([pa, ps = 0n]) => run(pa, ps));
     return acc;
 }
 
@@ -205,7 +172,7 @@ function elem8(u8) { elem(u8, "value"); return u8; }
 function degree(buf, opts = {}) {
     const { n, stride, bytes } = shape(buf, opts);
     if (n === 0) return -1;
-    const d = withResident(buf, bytes, false, (p) => addon.bn128PolyDegreeDev(p, n, stride));
+    const d = scope([input(buf, bytes)], ([p]) => addon.bn128PolyDegreeDev(p, n, stride));
     return d === NONE ? -1 : Number(d);
 }
 

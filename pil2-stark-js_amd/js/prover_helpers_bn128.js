@@ -10,6 +10,7 @@
 // No arithmetic happens here.
 "use strict";
 const { addon, isDev, DevBuffer } = require("./native.js");
+const { asWords } = require("./bn128_stage.js");
 const OP = { add: 0, sub: 1, mul: 2, copy: 3 };
 const TMP = 0, SEC = 1, SCALAR = 2;
 const R = 21888242871839275222246405745257275088548364400416034343698204186575808495617n;
@@ -24,8 +25,7 @@ function fe(ctx, value) {          // F.e(value) as 4 words
 }
 function words(u8) {
     if (!(u8 instanceof Uint8Array) || u8.length !== 32) throw new Error("prover_helpers_bn128: a scalar must be a Uint8Array of 32 bytes");
-    const c = new Uint8Array(32); c.set(u8);
-    return new BigUint64Array(c.buffer);
+    return asWords(u8);
 }
 
 function encode(code, dom, ctx, global) {

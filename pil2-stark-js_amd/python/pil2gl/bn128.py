@@ -21,26 +21,17 @@ import ctypes as C
 import numpy as np
 
 from ._lib import Pil2glError, G1Poly, load, call
-from . import _is_dev, _ptr, _stream, _check_len, _to_host, torch
+from . import _is_dev, _ptr, _stream, _check_len, _same_side, _to_host, torch
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
 
-def _words(vals):
-    a = np.zeros((len(vals), 4), np.uint64)
-    for i, v in enumerate(vals):
-        v = int(v) % R
-        for k in range(4):
-            a[i, k] = (v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF
-    return a
-
-
-def _words256(vals):
-    """the words of values < 2^256 as they are (the library reduces them mod r); anything else is reduced here first"""
+def _words(vals, keep256=False):
+    """the 4 words of every value reduced mod r; keep256 leaves values < 2^256 as they are (the library reduces them mod r)"""
     a = np.zeros((len(vals), 4), np.uint64)
     for i, v in enumerate(vals):
         v = int(v)
-        if not 0 <= v < (1 << 256):
+        if not (keep256 and 0 <= v < (1 << 256)):
             v %= R
         for k in range(4):
             a[i, k] = (v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF
@@ -50,6 +41,21 @@ def _words256(vals):
 def _ints(words):
     w = np.asarray(words, dtype=np.uint64).reshape(-1, 4)
     return [sum(int(x) << (64 * k) for k, x in enumerate(r)) for r in w]
+
+
+def _dispatch(name, buf, *args):
+    """the library's entry `name` over host buffers, or its `_dev` twin on the current stream where `buf` is a device tensor"""
+    if _is_dev(buf):
+        call(name + "_dev", *args, _stream())
+    else:
+        call(name, *args)
+
+
+def _new_like(like, shape):
+    """a new buffer of this shape and of the kind of `like`: a tensor next to it, or a numpy array of words"""
+    if _is_dev(like):
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    return np.empty(shape, np.uint64)
 
 
 def poseidon(inputs, initState=0, nOut=1):
@@ -92,14 +98,12 @@ def to_montgomery(vals):
 
 
 def _transform(name, words, nPols, nBits, out):
+    _same_side(words, out)
     _check_len(words, (nPols << nBits) * 4, "words")
     if out is None:
-        out = torch.empty_like(words) if _is_dev(words) else np.empty_like(words)
+        out = _new_like(words, words.shape)
     _check_len(out, (nPols << nBits) * 4, "out")
-    if _is_dev(words):
-        call(name + "_dev", _ptr(words), nPols, nBits, _ptr(out), _stream())
-    else:
-        call(name, _ptr(words), nPols, nBits, _ptr(out))
+    _dispatch(name, words, _ptr(words), nPols, nBits, _ptr(out))
     return out
 
 
@@ -118,15 +122,9 @@ def interpolate(words, nPols, nBits, nBitsExt, coefs=True):
     """fft_p.bn128.js:225: -> (coefficients (2^nBits, nPols, 4), evaluations on the 2^nBitsExt roots (2^nBitsExt, nPols, 4)), no coset
     shift; coefs=False skips the first output (None in its place)"""
     _check_len(words, (nPols << nBits) * 4, "words")
-    dev = _is_dev(words)
-    if dev:
-        ext = torch.empty((1 << nBitsExt, nPols, 4), dtype=words.dtype, device=words.device)
-        co = torch.empty((1 << nBits, nPols, 4), dtype=words.dtype, device=words.device) if coefs else None
-        call("pil2gl_bn128_interpolate_dev", _ptr(words), nPols, nBits, _ptr(co), _ptr(ext), nBitsExt, _stream())
-    else:
-        ext = np.empty((1 << nBitsExt, nPols, 4), np.uint64)
-        co = np.empty((1 << nBits, nPols, 4), np.uint64) if coefs else None
-        call("pil2gl_bn128_interpolate", _ptr(words), nPols, nBits, _ptr(co), _ptr(ext), nBitsExt)
+    ext = _new_like(words, (1 << nBitsExt, nPols, 4))
+    co = _new_like(words, (1 << nBits, nPols, 4)) if coefs else None
+    _dispatch("pil2gl_bn128_interpolate", words, _ptr(words), nPols, nBits, _ptr(co), _ptr(ext), nBitsExt)
     return co, ext
 
 
@@ -134,8 +132,7 @@ def g1_msm(bases, scalars, n=None, stride=1, montgomery=True, out=None):
     """G1.toAffine(G1.multiExpAffine(bases, scalars)): bases = n affine points of 8 uint64 words (x, y in Fq Montgomery form, infinity all
     zero), scalars = element i at word 4*i*stride (Fr Montgomery words, or normal form with montgomery=False); numpy arrays or device
     tensors, both of one kind.  n defaults to the number of points in bases.  -> the affine sum as 8 words of the same kind, or `out`"""
-    if _is_dev(bases) != _is_dev(scalars) or (out is not None and _is_dev(out) != _is_dev(bases)):
-        raise Pil2glError("mixing host and device buffers in one call")
+    _same_side(bases, scalars, out)
     if n is None:
         n = int(np.prod(bases.shape)) // 8
     if stride < 1:
@@ -143,12 +140,9 @@ def g1_msm(bases, scalars, n=None, stride=1, montgomery=True, out=None):
     _check_len(bases, 8 * n, "bases")
     _check_len(scalars, ((n - 1) * stride + 1) * 4 if n else 0, "scalars")
     if out is None:
-        out = torch.empty(8, dtype=bases.dtype, device=bases.device) if _is_dev(bases) else np.empty(8, np.uint64)
+        out = _new_like(bases, 8)
     _check_len(out, 8, "out")
-    if _is_dev(bases):
-        call("pil2gl_bn128_g1_msm_dev", _ptr(bases), _ptr(scalars), n, stride, 1 if montgomery else 0, _ptr(out), _stream())
-    else:
-        call("pil2gl_bn128_g1_msm", _ptr(bases), _ptr(scalars), n, stride, 1 if montgomery else 0, _ptr(out))
+    _dispatch("pil2gl_bn128_g1_msm", bases, _ptr(bases), _ptr(scalars), n, stride, 1 if montgomery else 0, _ptr(out))
     return out
 
 
@@ -160,8 +154,7 @@ def g1_commit(bases, scalars, polys, row_stride, montgomery=True, out=None):
     each), row_stride elements per row; polys = [(first, rows, slots)]: polynomial k has len(slots) * rows coefficients, coefficient i is
     the element first + (i div m) * row_stride + slots[i mod m], or 0 where that slot is None (fflonk's CPolynomial).  numpy arrays or
     device tensors, all of one kind.  -> (K, 8) words of the same kind, or `out`: toAffine(sum_i coef_k[i] * bases[i]) per polynomial"""
-    if _is_dev(bases) != _is_dev(scalars) or (out is not None and _is_dev(out) != _is_dev(bases)):
-        raise Pil2glError("mixing host and device buffers in one call")
+    _same_side(bases, scalars, out)
     K = len(polys)
     descs, flat, extent, n_max = (G1Poly * max(K, 1))(), [], 0, 0
     for k, (first, rows, slots) in enumerate(polys):
@@ -182,13 +175,10 @@ def g1_commit(bases, scalars, polys, row_stride, montgomery=True, out=None):
     _check_len(scalars, 4 * extent, "scalars")         # the C entry cannot know how far the buffers extend
     c_slots = (C.c_uint32 * max(len(flat), 1))(*flat)
     if out is None:
-        out = torch.empty((K, 8), dtype=bases.dtype, device=bases.device) if _is_dev(bases) else np.empty((K, 8), np.uint64)
+        out = _new_like(bases, (K, 8))
     _check_len(out, 8 * K, "out")
-    args = [_ptr(bases), n_bases, _ptr(scalars), int(row_stride), 1 if montgomery else 0, descs, K, c_slots, _ptr(out)]
-    if _is_dev(bases):
-        call("pil2gl_bn128_g1_commit_dev", *args, _stream())
-    else:
-        call("pil2gl_bn128_g1_commit", *args)
+    _dispatch("pil2gl_bn128_g1_commit", bases,
+              _ptr(bases), n_bases, _ptr(scalars), int(row_stride), 1 if montgomery else 0, descs, K, c_slots, _ptr(out))
     return out
 
 
@@ -298,15 +288,9 @@ def eval_program(code, sections, scalars, nBits, primeShift=0, nTmp=None):
     code = op tuples as encode_program returns them; sections = one buffer per section index, each (2^nBits, width, 4) uint64 Montgomery
     words, all numpy arrays or all device tensors (then the kernel is enqueued on the current stream); scalars = (nScalars, 4) uint64
     Montgomery words, always a numpy array.  Destination sections are written in place."""
-    live = [b for b in sections if b is not None]
-    dev = bool(live) and _is_dev(live[0])
-    if any(_is_dev(b) != dev for b in live):
-        raise Pil2glError("mixing host and device buffers in one call")
+    _same_side(*sections)
     prog, ctx = make_context(code, nTmp, sections, scalars, nBits, primeShift)
-    if dev:
-        call("pil2gl_bn128_eval_program_dev", C.byref(prog), C.byref(ctx), _stream())
-    else:
-        call("pil2gl_bn128_eval_program", C.byref(prog), C.byref(ctx))
+    _dispatch("pil2gl_bn128_eval_program", next((b for b in sections if b is not None), None), C.byref(prog), C.byref(ctx))
 
 
 def plan_program(code, widths, scalars, nBits, primeShift=0, nTmp=None):
@@ -356,19 +340,15 @@ def poly_div(words, k, beta, n=None, stride=1, out=None):
     device tensor): d[k..n) is the quotient by x^k - beta (coefficient m at m + k), d[0..k) the remainder.  beta = 4 Montgomery words
     on the host.  n defaults to the elements `words` holds at this stride.  -> a new buffer of the same kind and shape, or `out` (which
     may be `words`; with stride > 1 the words between its elements stay as they are, so give one)"""
-    if out is not None and _is_dev(out) != _is_dev(words):
-        raise Pil2glError("mixing host and device buffers in one call")
+    _same_side(words, out)
     n = _column(words, n, stride, "words")
     if out is None:
         if stride != 1:
             raise Pil2glError("a strided division writes into a matrix: pass out")
-        out = torch.empty_like(words) if _is_dev(words) else np.empty_like(words)
+        out = _new_like(words, words.shape)
     _column(out, n, stride, "out")
     b = _host_elems(beta, "beta", 1)
-    if _is_dev(words):
-        call("pil2gl_bn128_poly_div_xk_sub_dev", _ptr(words), n, stride, k, _ptr(b), _ptr(out), _stream())
-    else:
-        call("pil2gl_bn128_poly_div_xk_sub", _ptr(words), n, stride, k, _ptr(b), _ptr(out))
+    _dispatch("pil2gl_bn128_poly_div_xk_sub", words, _ptr(words), n, stride, k, _ptr(b), _ptr(out))
     return out
 
 
@@ -377,12 +357,8 @@ def poly_eval(words, points, n=None, stride=1):
     poly_div takes them; never written) -> (P, 4) Montgomery words of the same kind as `words`"""
     n = _column(words, n, stride, "words")
     z = _host_elems(points, "points", 64)
-    if _is_dev(words):
-        out = torch.empty((z.shape[0], 4), dtype=words.dtype, device=words.device)
-        call("pil2gl_bn128_poly_eval_dev", _ptr(words), n, stride, _ptr(z), z.shape[0], _ptr(out), _stream())
-    else:
-        out = np.empty((z.shape[0], 4), np.uint64)
-        call("pil2gl_bn128_poly_eval", _ptr(words), n, stride, _ptr(z), z.shape[0], _ptr(out))
+    out = _new_like(words, (z.shape[0], 4))
+    _dispatch("pil2gl_bn128_poly_eval", words, _ptr(words), n, stride, _ptr(z), z.shape[0], _ptr(out))
     return out
 
 
@@ -404,8 +380,7 @@ def poly_fma(acc, src, coefs, exps, scale=None, *, n_acc, n_src, acc_stride=1, s
     n_src = 0); coefs = (t, 4) Montgomery words and exps = t strictly increasing exponents, 1 <= t <= 64, on the host; scale = 4
     Montgomery words on the host, or None: then acc is written and never read.  n_src + exps[-1] <= n_acc.  acc must share no element
     with src, except as the same column when exps == [0].  -> acc"""
-    if src is not None and _is_dev(acc) != _is_dev(src):
-        raise Pil2glError("mixing host and device buffers in one call")
+    _same_side(acc, src)
     _column(acc, n_acc, acc_stride, "acc")
     if src is None and n_src:
         raise Pil2glError("src is None with n_src = %d" % n_src)
@@ -415,11 +390,8 @@ def poly_fma(acc, src, coefs, exps, scale=None, *, n_acc, n_src, acc_stride=1, s
     if m.shape[0] != e.shape[0]:
         raise Pil2glError("%d coefficients for %d exponents" % (m.shape[0], e.shape[0]))
     s = None if scale is None else _host_elems(scale, "scale", 1)
-    args = (_ptr(acc), n_acc, acc_stride, _ptr(s), _ptr(src), n_src, src_stride, _ptr(m), _ptr(e), e.shape[0])
-    if _is_dev(acc):
-        call("pil2gl_bn128_poly_fma_dev", *args, _stream())
-    else:
-        call("pil2gl_bn128_poly_fma", *args)
+    _dispatch("pil2gl_bn128_poly_fma", acc,
+              _ptr(acc), n_acc, acc_stride, _ptr(s), _ptr(src), n_src, src_stride, _ptr(m), _ptr(e), e.shape[0])
     return acc
 
 
@@ -427,10 +399,7 @@ def poly_degree(words, n=None, stride=1):
     """Polynomial.degree: the largest i whose element (at word 4*i*stride) is not zero, or None for the zero polynomial and for n = 0"""
     n = _column(words, n, stride, "words")
     d = C.c_uint64()
-    if _is_dev(words):
-        call("pil2gl_bn128_poly_degree_dev", _ptr(words), n, stride, C.byref(d), _stream())
-    else:
-        call("pil2gl_bn128_poly_degree", _ptr(words), n, stride, C.byref(d))
+    _dispatch("pil2gl_bn128_poly_degree", words, _ptr(words), n, stride, C.byref(d))
     return None if d.value == (1 << 64) - 1 else int(d.value)
 
 
@@ -443,7 +412,7 @@ def _out_column(like, n, stride, out):
     if out is None:
         if stride != 1:
             raise Pil2glError("a strided result is written into a matrix: pass out")
-        out = torch.empty((n, 4), dtype=like.dtype, device=like.device) if _is_dev(like) else np.empty((n, 4), np.uint64)
+        out = _new_like(like, (n, 4))
     _column(out, n, stride, "out")
     return out
 
@@ -452,15 +421,11 @@ def batch_inverse(words, n=None, stride=1, out=None, out_stride=None):
     """F.batchInverse: out[i] = words[i]^-1, a zero giving zero (element i at word 4*i*stride, Montgomery words; a numpy array or a device
     tensor).  n defaults to the elements `words` holds at this stride.  -> a new buffer of the same kind, or `out` (element i at word
     4*i*out_stride, out_stride defaulting to stride; `out` may be `words` itself at the same stride, and nothing else that overlaps it)"""
-    if out is not None and _is_dev(out) != _is_dev(words):
-        raise Pil2glError("mixing host and device buffers in one call")
+    _same_side(words, out)
     n = _column(words, n, stride, "words")
     out_stride = stride if out_stride is None else out_stride
     out = _out_column(words, n, out_stride, out)
-    if _is_dev(words):
-        call("pil2gl_bn128_batch_inverse_dev", _ptr(words), stride, n, _ptr(out), out_stride, _stream())
-    else:
-        call("pil2gl_bn128_batch_inverse", _ptr(words), stride, n, _ptr(out), out_stride)
+    _dispatch("pil2gl_bn128_batch_inverse", words, _ptr(words), stride, n, _ptr(out), out_stride)
     return out
 
 
@@ -468,15 +433,11 @@ def gprod(num, den, n=None, num_stride=1, den_stride=1, out=None, out_stride=1):
     """calculateZ(F, num, den): out[0] = 1, out[i] = out[i-1] num[i-1] / den[i-1] (Montgomery words; columns as batch_inverse takes them,
     each with its own stride; numpy arrays or device tensors, all of one kind).  A zero denominator makes its ratio 0.  n defaults to the
     elements `den` holds.  -> a new buffer of the same kind, or `out` (which must not overlap num or den); out[n-1] is the hint's result"""
-    if _is_dev(num) != _is_dev(den) or (out is not None and _is_dev(out) != _is_dev(den)):
-        raise Pil2glError("mixing host and device buffers in one call")
+    _same_side(num, den, out)
     n = _column(den, n, den_stride, "den")
     _column(num, n, num_stride, "num")
     out = _out_column(den, n, out_stride, out)
-    if _is_dev(den):
-        call("pil2gl_bn128_gprod_dev", _ptr(num), num_stride, _ptr(den), den_stride, n, _ptr(out), out_stride, _stream())
-    else:
-        call("pil2gl_bn128_gprod", _ptr(num), num_stride, _ptr(den), den_stride, n, _ptr(out), out_stride)
+    _dispatch("pil2gl_bn128_gprod", den, _ptr(num), num_stride, _ptr(den), den_stride, n, _ptr(out), out_stride)
     return out
 
 
@@ -485,15 +446,11 @@ def gsum(num_elem, den, n=None, den_stride=1, out=None, out_stride=1):
     gprod takes them.  A zero denominator adds 0."""
     if _is_dev(num_elem):
         raise Pil2glError("num_elem is one element on the host")
-    if out is not None and _is_dev(out) != _is_dev(den):
-        raise Pil2glError("mixing host and device buffers in one call")
+    _same_side(den, out)
     n = _column(den, n, den_stride, "den")
     out = _out_column(den, n, out_stride, out)
     e = _host_elems(num_elem, "num_elem", 1)
-    if _is_dev(den):
-        call("pil2gl_bn128_gsum_dev", _ptr(e), _ptr(den), den_stride, n, _ptr(out), out_stride, _stream())
-    else:
-        call("pil2gl_bn128_gsum", _ptr(e), _ptr(den), den_stride, n, _ptr(out), out_stride)
+    _dispatch("pil2gl_bn128_gsum", den, _ptr(e), _ptr(den), den_stride, n, _ptr(out), out_stride)
     return out
 
 
@@ -514,9 +471,7 @@ def h1h2(f, t, n=None, f_stride=1, t_stride=1, h1=None, h1_stride=1, h2=None, h2
     columns as gprod takes them, each with its own stride; numpy arrays or device tensors, all of one kind.  n defaults to the elements
     `t` holds.  -> (h1, h2): new buffers of the same kind, or the ones passed (which must overlap nothing but as columns of one section).
     A value of f that is not in t raises Pil2glError with "Number not included: w:<lowest such row>"; the outputs are untouched then."""
-    kinds = {_is_dev(b) for b in (f, t, h1, h2) if b is not None}
-    if len(kinds) != 1:
-        raise Pil2glError("mixing host and device buffers in one call")
+    _same_side(f, t, h1, h2)
     n = _column(t, n, t_stride, "t")
     _column(f, n, f_stride, "f")
     h1 = _out_column(t, n, h1_stride, h1)
@@ -524,10 +479,7 @@ def h1h2(f, t, n=None, f_stride=1, t_stride=1, h1=None, h1_stride=1, h2=None, h2
     miss = C.c_uint64()
     args = (_ptr(f), f_stride, _ptr(t), t_stride, n, _ptr(h1), h1_stride, _ptr(h2), h2_stride, C.byref(miss))
     try:
-        if _is_dev(t):
-            call("pil2gl_bn128_h1h2_dev", *args, _stream())
-        else:
-            call("pil2gl_bn128_h1h2", *args)
+        _dispatch("pil2gl_bn128_h1h2", t, *args)
     except Pil2glError as e:
         e.missing_row = None if miss.value == (1 << 64) - 1 else int(miss.value)      # the library's missingRow
         raise
@@ -589,12 +541,8 @@ class MerkleHashBN128:
             raise Pil2glError("height must be > 0")
         _check_len(buff, width * height, "buff")
         n_words = self._getNNodes(height) * 4
-        if _is_dev(buff):
-            nodes = torch.empty(n_words, dtype=torch.int64, device=buff.device)
-            call("pil2gl_bn128_merkelize_dev", _ptr(buff), width, height, self.arity, int(self.custom), _ptr(nodes), _stream())
-        else:
-            nodes = np.zeros(n_words, np.uint64)
-            call("pil2gl_bn128_merkelize", _ptr(buff), width, height, self.arity, int(self.custom), _ptr(nodes))
+        nodes = torch.empty(n_words, dtype=torch.int64, device=buff.device) if _is_dev(buff) else np.zeros(n_words, np.uint64)
+        _dispatch("pil2gl_bn128_merkelize", buff, _ptr(buff), width, height, self.arity, int(self.custom), _ptr(nodes))
         return {"elements": buff, "nodes": nodes, "width": width, "height": height}
 
     def root(self, tree):
@@ -670,7 +618,7 @@ class MerkleHashBN128:
         if any(len(g) != a for _, mp in proofs for g in mp):
             raise Pil2glError("a level's group must hold `arity` siblings")
         vals = np.array(flat, dtype=np.uint64).reshape(n, width)
-        sib = _words256([s_ for _, mp in proofs for g in mp for s_ in g])
+        sib = _words([s_ for _, mp in proofs for g in mp for s_ in g], keep256=True)
         ii = np.array([int(i) for i in idxs], dtype=np.uint64)
         roots = np.zeros((n, 4), np.uint64)
         call("pil2gl_bn128_roots_from_group_proofs", _ptr(vals) if width else None, _ptr(sib) if levels else None, width, levels, a,

@@ -1,11 +1,13 @@
 // The BN254 Fr drop-in (pil2-stark-js_amd/js/fft_p_bn128.js) against expected bytes a Python checker wrote: every case of the job runs
 // over a Uint8Array, over a chunked object with ffjavascript BigBuffer's surface (4096-byte chunks: staging crosses them) and over
-// DevBuffers.  usage: node fft_bn128_parity.js <job.json>; exits non-zero on the first difference.
+// DevBuffers.  Then staging in several pieces: 3 columns of 64 rows (6144 bytes) with the piece size lowered to 1024 bytes give the bytes
+// the same calls give in one piece.  usage: node fft_bn128_parity.js <job.json>; exits non-zero on the first difference.
 "use strict";
 const fs = require("fs");
 const path = require("path");
 const m = require(path.join(__dirname, "..", "..", "pil2-stark-js_amd", "js", "index.js"));
 const { fft, ifft, interpolate } = m.fft_p_bn128;
+const stage = require(path.join(__dirname, "..", "..", "pil2-stark-js_amd", "js", "bn128_stage.js"));
 const Fr = { n8: 32 };
 
 class Chunked {              // { byteLength, slice(a, b) -> Uint8Array, set(arr, off) } over 4096-byte pieces
@@ -30,6 +32,28 @@ function check(what, got, wantHex) {
     const want = Buffer.from(wantHex, "hex");
     if (got.length !== want.length) throw new Error(what + ": " + got.length + " bytes, expected " + want.length);
     for (let i = 0; i < want.length; i++) if (got[i] !== want[i]) throw new Error(what + ": byte " + i + " (element " + Math.floor(i / 32) + ") differs");
+}
+
+// fft out of place and in place (buffDst === buffSrc), interpolate with buffDstCoefs given, over Uint8Arrays -> every buffer the calls touch
+async function stagedRuns(input, nPols, nBits, nBitsExt) {
+    const src = Uint8Array.from(input), dst = new Uint8Array(input.length), inPlace = Uint8Array.from(input);
+    const coefs = new Uint8Array(input.length), ext = new Uint8Array(nPols * 2 ** nBitsExt * 32);
+    await fft(src, nPols, nBits, dst, Fr);
+    await fft(inPlace, nPols, nBits, inPlace, Fr);
+    await interpolate(src, nPols, nBits, coefs, ext, nBitsExt, Fr);
+    return { src, dst, inPlace, coefs, ext };
+}
+async function piecewise(job) {
+    const nPols = 3, nBits = 6, bytes = nPols * 2 ** nBits * 32;
+    const input = Buffer.from(job.cases[job.cases.length - 1].input, "hex").subarray(0, bytes);       // any run of field elements serves
+    if (input.length !== bytes) throw new Error("the last case holds fewer than " + bytes + " bytes");
+    const one = await stagedRuns(input, nPols, nBits, nBits + 1);
+    const was = stage.setPieceBytes(1024);
+    let many;
+    try { many = await stagedRuns(input, nPols, nBits, nBits + 1); } finally { stage.setPieceBytes(was); }
+    for (const k of Object.keys(one)) check("1024-byte pieces: " + k, many[k], Buffer.from(one[k]).toString("hex"));
+    check("1024-byte pieces: in place and out of place agree", many.inPlace, Buffer.from(one.dst).toString("hex"));
+    check("1024-byte pieces: source untouched", many.src, Buffer.from(input).toString("hex"));
 }
 
 async function main() {
@@ -61,6 +85,7 @@ async function main() {
             n++;
         }
     }
+    await piecewise(job);
     let threw = false;
     try { await fft(new Uint8Array(64), 1, 1, new Uint8Array(64), { n8: 8 }); } catch (e) { threw = true; }
     if (!threw) throw new Error("a field with n8 != 32 was accepted");
