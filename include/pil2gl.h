@@ -24,7 +24,8 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod and bn128_gsum; land_rows with a null hostFirstBad.
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod and bn128_gsum; land_rows with a null hostFirstBad;
+ *      wtns_adds and bn128_wtns_adds, wtns_gather and bn128_wtns_gather with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
  *    The following _dev calls BLOCK until their work on the stream has finished, because they hand a result to the host or
@@ -33,7 +34,7 @@
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
  *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, compute_fri_pol, build_lev (small host tables),
  *      h1h2 and bn128_h1h2 (the missing row comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
- *      land_rows with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
+ *      land_rows, wtns_gather and bn128_wtns_gather with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
  *    So do the host-pointer verifier calls roots_from_group_proofs and bn128_roots_from_group_proofs (roots copied to host memory).
  *    bn128_group_proof[s]_dev take no stream: their copies and their gather kernel run on the NULL stream, which orders them after work
@@ -45,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -722,6 +723,60 @@ int pil2gl_bn128_h1h2_dev(const uint64_t *f, uint64_t fStride, const uint64_t *t
  * *scratchBytes = the working buffer (table, counts / group starts, chunk totals, missing cell): below 20 n + n / 512 + 64 bytes for
  * every n, 3 GiB + 512 KiB + 16 bytes at n = 2^28; 0 for n = 0.  n > 2^28: PIL2GL_EINVAL. */
 int pil2gl_debug_bn128_h1h2_plan(uint64_t n, uint32_t *outInfo /* [6] */, uint64_t *scratchBytes);
+
+/* ---- recursion witness: the additions and the sMap gather of the *_exec step (csrc/wtns_exec.hip, csrc/wtns_plan.h) ---------------
+ * compressorExec (src/compressor/compressor_exec.js:5-32) over Goldilocks and the loop of src/final/main_final_exec.js:50-67 over the
+ * BN254 scalar field Fr (also test/plonk2pil/main_plonkexec.js) turn the circom witness w into the N x nCols trace:
+ *   additions   for i = 0 .. nAdds - 1 in order: w[nWitness + i] = w[a_i] ca_i + w[b_i] cb_i in the field; a_i, b_i may name an earlier
+ *               addition.  An operand >= nWitness + i is PIL2GL_EINVAL naming i (the reference would read `undefined`).
+ *   gather      dst[i dstCols + j] = (s = sMap[i nCols + j]) ? w[s] : 0 for j < nCols, and 0 for nCols <= j < dstCols (the widening rule
+ *               of land_rows above).  Index 0 means zero, not w[0].  nRows (the file's nSMap) rows are written.
+ * An element is one u64 (Goldilocks) or four u64 (Fr); nW = nWitness + nAdds must stay below 2^32 (the reference's sMap is Uint32Array,
+ * compressor18_setup.js:62).  Goldilocks: witness and coefficient words in [p, 2^64) count as their value mod p; outputs are canonical.
+ * Fr: w holds NORMAL-form values, 32 bytes little-endian (what circom's calculator and a .wtns hold); the coefficients are Montgomery
+ * words, as the exec file's section 4 holds them (final/exec_helpers.js:150-165); any 256-bit pattern counts as its value mod r; the
+ * additions leave normal-form canonical values in w; the trace is written in Montgomery form when toMontgomery is non-zero (what
+ * writeToBigBufferFr, src/prover/prover.js:27, leaves in cm1_n and fft_p_bn128 reads) and in normal form otherwise, canonical either way.
+ *
+ * pil2gl_wtns_adds_plan: host-only, no device.  Addition i has its operands at hostAddIdx[idxStride i], [idxStride i + 1] and its two
+ * coefficients, coefWords (1 or 4) words each, at hostCoef[coefStride i ..] -- a compressor .exec: addsBuff, 4, addsBuff + 2, 4; a final
+ * .exec: section 3, 2, section 4, 8.  level(i) = 0 when both operands are below nWitness, else 1 + the highest level among its operands
+ * that are additions.  With every output NULL the call validates and returns *nLevels.  Otherwise outLevelStart (levelCap >= nLevels + 1
+ * entries) and outAdds (4 nAdds words) receive the additions sorted by level, stable within a level, as (a, b, dst = nWitness + i, i),
+ * level l being records [outLevelStart[l], outLevelStart[l + 1]); outCoef (2 coefWords nAdds words, may be NULL) the coefficients
+ * permuted alike.  The device runs ONE LAUNCH PER LEVEL: a chain of depth D costs D launches (r1cs2plonk.js:49-67 reduces a linear
+ * combination through a queue, so depth grows like log2 of the longest combination).
+ * pil2gl_[bn128_]wtns_adds_dev: w (device, nW elements, the first nWitness filled), adds / coefs (device, the plan's outAdds / outCoef,
+ * 16-byte aligned), hostLevelStart (HOST, checked: starts at 0, ascends, ends at nAdds).  Enqueues only.  A record whose a or b is >= nW or
+ * whose dst is outside [nWitness, nW) writes nothing.  w overlapping a table is PIL2GL_EINVAL.
+ * pil2gl_[bn128_]wtns_gather_dev: sMap32 = device, nRows x nCols 32-bit indices.  An index >= nW writes zero; with hostFirstBad the call
+ * BLOCKS and reports the smallest flat cell index i nCols + j holding one, UINT64_MAX when clean (as land_rows); with NULL it only enqueues.
+ * dstCols < nCols, nW >= 2^32, dst overlapping w or sMap: PIL2GL_EINVAL.  w and dst 8-byte (Fr: 16-byte) aligned.
+ * pil2gl_[bn128_]wtns_exec: host pointers; plan, stage, compute, copy out.  The u64 tables as the files hold them: Goldilocks hostAddIdx
+ * = the records (a, b, ca, cb) and hostAddCoef = hostAddIdx + 2 (strides 4); Fr hostAddIdx = 2 nAdds indices, hostAddCoef = 2 nAdds
+ * elements.  hostSMap64 = nRows x nCols u64; a value >= nW is PIL2GL_EINVAL naming the cell.  hostDst = nRows x nCols elements.
+ * Every refusal comes before the first device call; without a device the compute calls return PIL2GL_ENODEV.  nAdds = 0 and an empty
+ * trace are PIL2GL_OK. */
+int pil2gl_wtns_adds_plan(const uint64_t *hostAddIdx, uint64_t idxStride, uint64_t nAdds, uint64_t nWitness, const uint64_t *hostCoef,
+                          uint64_t coefStride, uint32_t coefWords, uint32_t *outAdds, uint64_t *outCoef, uint32_t *outLevelStart,
+                          uint32_t levelCap, uint32_t *nLevels);
+int pil2gl_wtns_adds_dev(uint64_t *w, uint64_t nWitness, const uint32_t *adds, const uint64_t *coefs, uint64_t nAdds,
+                         const uint32_t *hostLevelStart, uint32_t nLevels, void *stream);
+int pil2gl_bn128_wtns_adds_dev(uint64_t *w, uint64_t nWitness, const uint32_t *adds, const uint64_t *coefs, uint64_t nAdds,
+                               const uint32_t *hostLevelStart, uint32_t nLevels, void *stream);
+int pil2gl_wtns_gather_dev(const uint64_t *w, uint64_t nW, const uint32_t *sMap32, uint64_t nRows, uint64_t nCols, uint64_t *dst,
+                           uint64_t dstCols, uint64_t *hostFirstBad, void *stream);
+int pil2gl_bn128_wtns_gather_dev(const uint64_t *w, uint64_t nW, const uint32_t *sMap32, uint64_t nRows, uint64_t nCols, uint64_t *dst,
+                                 uint64_t dstCols, int toMontgomery, uint64_t *hostFirstBad, void *stream);
+int pil2gl_wtns_exec(const uint64_t *hostW, uint64_t nWitness, const uint64_t *hostAddIdx, const uint64_t *hostAddCoef, uint64_t nAdds,
+                     const uint64_t *hostSMap64, uint64_t nRows, uint64_t nCols, uint64_t *hostDst);
+int pil2gl_bn128_wtns_exec(const uint64_t *hostW, uint64_t nWitness, const uint64_t *hostAddIdx, const uint64_t *hostAddCoef, uint64_t nAdds,
+                           const uint64_t *hostSMap64, uint64_t nRows, uint64_t nCols, uint64_t *hostDst, int toMontgomery);
+/* host-only, no device: how the additions run.  outInfo[0] = levels, [1] = kernel launches of the additions (one per level), [2] = the
+ * widest level, [3] = threads per workgroup, [4] = workgroups of the widest level's launch; outWidths[l] = additions of level l for
+ * l < widthCap (may be NULL).  Refuses what pil2gl_wtns_adds_plan refuses. */
+int pil2gl_debug_wtns_plan(const uint64_t *hostAddIdx, uint64_t idxStride, uint64_t nAdds, uint64_t nWitness, uint32_t *outInfo /* [5] */,
+                           uint32_t *outWidths, uint32_t widthCap);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

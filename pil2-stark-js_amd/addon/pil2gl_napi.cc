@@ -495,6 +495,61 @@ FN(H1H2Dev) {          // (dF, dT, n, dim, dH1, dH2)  polutils.js:105-126
     P2(env, pil2gl_h1h2_dev(f, t, n, dim, h1, h2, a.stream(6))); return mk_undefined(env);
 }
 
+// ---- recursion witness: the additions and the sMap gather of the *_exec step (csrc/wtns_exec.hip; js/witness_exec.js) ----
+static napi_value mk_words(napi_env env, size_t nWords, uint64_t **data) {      // a new BigUint64Array
+    napi_value ab, ta; void *p = nullptr;
+    if (napi_create_arraybuffer(env, nWords * 8, &p, &ab) != napi_ok || napi_create_typedarray(env, napi_biguint64_array, nWords, ab, 0, &ta) != napi_ok) {
+        napi_throw_error(env, nullptr, "cannot allocate a BigUint64Array of this length"); return nullptr; }
+    *data = (uint64_t *)p;
+    return ta;
+}
+// (addIdx, idxOffset, idxStride, nAdds, nWitness, coef, coefOffset, coefStride, coefWords) -> { nLevels, adds, coefs, levelStart }: the plan's
+// 32-bit records and level table packed into BigUint64Arrays (two records' halves / two entries a word), ready for a DevBuffer
+FN(WtnsAddsPlan) {
+    Args a(env, info); uint64_t idxLen = 0, coefLen = 0;
+    uint64_t *idx = a.arr(0, 0, &idxLen); uint64_t io = a.u64(1), is = a.u64(2), nAdds = a.u64(3), nWitness = a.u64(4);
+    uint64_t *coef = a.arr(5, 0, &coefLen); uint64_t co = a.u64(6), cs = a.u64(7); uint32_t cw = (uint32_t)a.u64(8);
+    if (!a.ok) return nullptr;
+    if (nAdds && (is < 2 || io + (nAdds - 1) * is + 2 > idxLen || (cw != 1 && cw != 4) || co + (nAdds - 1) * cs + 2 * cw > coefLen)) {
+        napi_throw_type_error(env, nullptr, "wtnsAddsPlan: the tables are shorter than nAdds additions"); return nullptr; }
+    uint32_t nLevels = 0;
+    P2(env, pil2gl_wtns_adds_plan(idx + io, is, nAdds, nWitness, nullptr, 0, cw, nullptr, nullptr, nullptr, 0, &nLevels));
+    uint64_t *recs, *coefs, *starts;
+    napi_value vr = mk_words(env, 2 * nAdds, &recs), vc = mk_words(env, 2 * cw * nAdds, &coefs), vs = mk_words(env, (nLevels + 2) / 2, &starts);
+    if (!vr || !vc || !vs) return nullptr;
+    starts[(nLevels + 2) / 2 - 1] = 0;
+    P2(env, pil2gl_wtns_adds_plan(idx + io, is, nAdds, nWitness, coef + co, cs, cw, (uint32_t *)recs, coefs, (uint32_t *)starts, nLevels + 1, &nLevels));
+    napi_value o, v; napi_create_object(env, &o);
+    napi_create_uint32(env, nLevels, &v); napi_set_named_property(env, o, "nLevels", v);
+    napi_set_named_property(env, o, "adds", vr); napi_set_named_property(env, o, "coefs", vc); napi_set_named_property(env, o, "levelStart", vs);
+    return o;
+}
+FN(WtnsAddsDev) {          // (dW, nWitness, dAdds, dCoefs, nAdds, levelStart (the plan's packed array), nLevels, bn128[, stream])
+    Args a(env, info); uint64_t *w = DP(0); uint64_t nWitness = a.u64(1); uint64_t *adds = DP(2), *coefs = DP(3); uint64_t nAdds = a.u64(4);
+    uint64_t nLevels = a.u64(6); uint64_t *ls = a.arr(5, (nLevels + 2) / 2); bool bn = a.u64(7) != 0; if (!a.ok) return nullptr;
+    P2(env, (bn ? pil2gl_bn128_wtns_adds_dev : pil2gl_wtns_adds_dev)(w, nWitness, (const uint32_t *)adds, coefs, nAdds, (const uint32_t *)ls, (uint32_t)nLevels, a.stream(8)));
+    return mk_undefined(env);
+}
+FN(WtnsGatherDev) {        // (dW, nW, dSMap32, nRows, nCols, dDst, dstCols, bn128, toMontgomery, check[, stream]) -> first bad cell as BigInt (2^64-1: none), undefined without check
+    Args a(env, info); uint64_t *w = DP(0); uint64_t nW = a.u64(1); uint64_t *sm = DP(2); uint64_t nRows = a.u64(3), nCols = a.u64(4); uint64_t *d = DP(5);
+    uint64_t dc = a.u64(6); bool bn = a.u64(7) != 0; int mont = a.u64(8) != 0; bool check = a.u64(9) != 0; if (!a.ok) return nullptr;
+    uint64_t bad = ~0ull;
+    if (bn) P2(env, pil2gl_bn128_wtns_gather_dev(w, nW, (const uint32_t *)sm, nRows, nCols, d, dc, mont, check ? &bad : nullptr, a.stream(10)));
+    else P2(env, pil2gl_wtns_gather_dev(w, nW, (const uint32_t *)sm, nRows, nCols, d, dc, check ? &bad : nullptr, a.stream(10)));
+    return check ? mk_bigint(env, bad) : mk_undefined(env);
+}
+FN(WtnsExec) {             // (w, nWitness, addsBuff (a, b, ca, cb), nAdds, sMap, nRows, nCols, dst)   compressor_exec.js:17-29
+    Args a(env, info); uint64_t nWitness = a.u64(1), nAdds = a.u64(3), nRows = a.u64(5), nCols = a.u64(6);
+    uint64_t *w = a.arr(0, nWitness), *adds = a.arr(2, 4 * nAdds), *sm = a.arr(4, nRows * nCols), *d = a.arr(7, nRows * nCols); if (!a.ok) return nullptr;
+    P2(env, pil2gl_wtns_exec(w, nWitness, adds, adds + 2, nAdds, sm, nRows, nCols, d)); return mk_undefined(env);
+}
+FN(Bn128WtnsExec) {        // (w, nWitness, addsIdx, addsCoef, nAdds, sMap, nRows, nCols, dst, toMontgomery)   main_final_exec.js:55-67
+    Args a(env, info); uint64_t nWitness = a.u64(1), nAdds = a.u64(4), nRows = a.u64(6), nCols = a.u64(7);
+    uint64_t *w = a.arr(0, 4 * nWitness), *idx = a.arr(2, 2 * nAdds), *coef = a.arr(3, 8 * nAdds), *sm = a.arr(5, nRows * nCols), *d = a.arr(8, 4 * nRows * nCols);
+    int mont = a.u64(9) != 0; if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_wtns_exec(w, nWitness, idx, coef, nAdds, sm, nRows, nCols, d, mont)); return mk_undefined(env);
+}
+
 // ---- BN128 Merkle commitment (merklehash_bn128_p.js / merklehash_bn128_worker.js) ----
 FN(Bn128Poseidon) {  // (in BigUint64Array(4*nIn*count) normal form, init BigUint64Array(4*count)|null, count, nIn, nOut, out(4*nOut*count))
     Args a(env, info); uint64_t count = a.u64(2), nIn = a.u64(3), nOut = a.u64(4);
@@ -679,6 +734,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128PolyFmaDev", Bn128PolyFmaDev }, { "bn128PolyDegreeDev", Bn128PolyDegreeDev },
         { "bn128BatchInverseDev", Bn128BatchInverseDev }, { "bn128GprodDev", Bn128GprodDev }, { "bn128GsumDev", Bn128GsumDev },
         { "bn128H1h2Dev", Bn128H1h2Dev },
+        { "wtnsAddsPlan", WtnsAddsPlan }, { "wtnsAddsDev", WtnsAddsDev }, { "wtnsGatherDev", WtnsGatherDev }, { "wtnsExec", WtnsExec }, { "bn128WtnsExec", Bn128WtnsExec },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

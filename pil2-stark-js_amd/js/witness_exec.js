@@ -1,0 +1,135 @@
+// The recursion witness on the device: the `*_exec` step of the reference with the witness in place of the wasm (the witness calculator
+// is third-party and stays the caller's).  Names and shapes follow src/compressor/compressor_exec.js and src/final/exec_helpers.js /
+// main_final_exec.js:50-67; the additions and the sMap gather run in csrc/wtns_exec.hip.
+//   readExecFile(execFile, nCols)            compressor .exec (flat u64)  -> { nAdds, nSMap, addsBuff, sMapBuff }
+//   readExecFile(Fr, execFile, nCols)        final .exec (binfile "exec") -> { nAdds, nSMap, addsBigInt, addsFr, sMap }; addsFr = the 2 nAdds
+//                                            coefficients as section 4 holds them, Montgomery bytes (the reference turns them into BigInts)
+//   readWtns(file)                           .wtns (binfile "wtns")       -> { n8, prime, nWitness, w: Uint8Array, normal form }
+//   compressorExec(F, pil, w, exec)          w: BigUint64Array | BigInt[] -> cmPols-shaped { Compressor: { a: [nCols][N] BigInt }, trace }
+//   finalExec(w, exec, nCols, opts)          w: Uint8Array of 32-byte normal-form values -> the N x nCols trace as bytes, Montgomery form
+//                                            unless opts.montgomery === false (what writeToBigBufferFr leaves in cm1_n)
+//   prepareExec(exec, nCols, nWitness)       once per setup -> { adds, coefs, sMap, levelStart, ... } with the tables as DevBuffers
+//   execDev(prepared, wDev, dst, opts)       per proof: wDev = DevBuffer of nW elements whose first nWitness hold the witness; dst = DevBuffer
+//                                            of nRows x (opts.dstCols || nCols) elements, made when absent; opts.check: throw on a bad index
+// Node 12: no optional chaining.
+"use strict";
+const fs = require("fs");
+const { addon, DevBuffer, isDev } = require("./native.js");
+const stage = require("./bn128_stage.js");
+
+function short(file, found, expected) { return new Error(file + ": " + found + " bytes found, " + expected + " expected"); }
+function readAt(fd, file, size, at, n) {
+    if (at + n > size) throw short(file, size, at + n);
+    const b = new Uint8Array(n);
+    let got = 0;
+    while (got < n) { const k = fs.readSync(fd, b, got, n - got, at + got); if (k <= 0) throw short(file, at + got, at + n); got += k; }
+    return b;
+}
+const u32 = (b, o) => new DataView(b.buffer, b.byteOffset, b.byteLength).getUint32(o, true);
+const u64n = (b, o) => Number(new DataView(b.buffer, b.byteOffset, b.byteLength).getBigUint64(o, true));
+
+// the minimal iden3 binfile reader: 4-byte type, u32 version, u32 section count, then (u32 id, u64 size, payload) until the file ends
+function withSections(file, type, fn) {
+    const fd = fs.openSync(file, "r");
+    try {
+        const size = fs.fstatSync(fd).size;
+        const head = readAt(fd, file, size, 0, 12);
+        if (Buffer.from(head.subarray(0, 4)).toString("latin1") !== type) throw new Error(file + ": not a " + type + " file");
+        const version = u32(head, 4), count = u32(head, 8), secs = {};
+        for (let at = 12, k = 0; at < size && k < count; k++) {
+            const h = readAt(fd, file, size, at, 12), n = u64n(h, 4);
+            if (at + 12 + n > size) throw short(file, size, at + 12 + n);
+            secs[u32(h, 0)] = { at: at + 12, n };
+            at += 12 + n;
+        }
+        const section = (id, bytes) => {
+            if (!secs[id]) throw new Error(file + ": no section " + id);
+            if (secs[id].n < bytes) throw short(file, size, size + bytes - secs[id].n);
+            return readAt(fd, file, size, secs[id].at, bytes);
+        };
+        return fn(version, section);
+    } finally { fs.closeSync(fd); }
+}
+
+function readCompressorExec(file, nCols) {
+    const fd = fs.openSync(file, "r");
+    try {
+        const size = fs.fstatSync(fd).size;
+        const h = readAt(fd, file, size, 0, 16), nAdds = u64n(h, 0), nSMap = u64n(h, 8);
+        const want = 8 * (2 + 4 * nAdds + nSMap * nCols);
+        if (size < want) throw short(file, size, want);
+        const addsBuff = stage.asWords(readAt(fd, file, size, 16, 32 * nAdds));
+        const sMapBuff = stage.asWords(readAt(fd, file, size, 16 + 32 * nAdds, 8 * nSMap * nCols));
+        return { nAdds, nSMap, addsBuff, sMapBuff };
+    } finally { fs.closeSync(fd); }
+}
+function readFinalExec(file, nCols) {
+    return withSections(file, "exec", (version, section) => {
+        if (version !== 1) throw new Error(file + ": exec version " + version + ", 1 expected");
+        const info = section(2, 16), nAdds = u64n(info, 0), nSMap = u64n(info, 8);
+        return { nAdds, nSMap, addsBigInt: stage.asWords(section(3, 16 * nAdds)), addsFr: section(4, 64 * nAdds), sMap: stage.asWords(section(5, 8 * nSMap * nCols)) };
+    });
+}
+// both of the reference's shapes: (execFile, nCols) and (F, execFile, nCols[, logger])
+async function readExecFile(a, b, c) {
+    return typeof a === "string" ? readCompressorExec(a, b) : readFinalExec(b, c);
+}
+function readWtns(file) {
+    return withSections(file, "wtns", (version, section) => {
+        const n8 = u32(section(1, 4), 0), head = section(1, 8 + n8), nWitness = u32(head, 4 + n8);
+        let prime = 0n;
+        for (let i = n8 - 1; i >= 0; i--) prime = (prime << 8n) | BigInt(head[4 + i]);
+        return { n8, prime, nWitness, w: section(2, nWitness * n8) };
+    });
+}
+
+const isFinal = (exec) => exec.addsFr !== undefined;
+function words(x) { return x instanceof BigUint64Array ? x : x instanceof Uint8Array ? stage.asWords(x) : BigUint64Array.from(Array.from(x, (v) => BigInt(v))); }
+
+async function compressorExec(F, pil, w, exec) {
+    const refs = pil.references, N = Object.values(refs)[0].polDeg;
+    const a = refs["Compressor.a"], nCols = a && a.len ? a.len : exec.sMapBuff.length / exec.nSMap;
+    const wW = words(w), trace = new BigUint64Array(exec.nSMap * nCols);
+    addon.wtnsExec(wW, wW.length, exec.addsBuff, exec.nAdds, exec.sMapBuff, exec.nSMap, nCols, trace);
+    const cols = [];
+    for (let j = 0; j < nCols; j++) { const col = new Array(N).fill(0n); for (let i = 0; i < exec.nSMap; i++) col[i] = trace[i * nCols + j]; cols.push(col); }
+    return { Compressor: { a: cols }, trace };
+}
+function finalExec(w, exec, nCols, opts) {
+    const wW = words(w), out = new Uint8Array(32 * exec.nSMap * nCols);
+    addon.bn128WtnsExec(wW, wW.length / 4, exec.addsBigInt, words(exec.addsFr), exec.nAdds, exec.sMap, exec.nSMap, nCols, stage.asWords(out),
+        !(opts && opts.montgomery === false));
+    return out;
+}
+
+function prepareExec(exec, nCols, nWitness) {
+    const bn128 = isFinal(exec), nAdds = exec.nAdds, nRows = exec.nSMap, nW = nWitness + nAdds;
+    const idx = bn128 ? exec.addsBigInt : exec.addsBuff, coef = bn128 ? words(exec.addsFr) : exec.addsBuff;
+    const plan = bn128 ? addon.wtnsAddsPlan(idx, 0, 2, nAdds, nWitness, coef, 0, 8, 4) : addon.wtnsAddsPlan(idx, 0, 4, nAdds, nWitness, coef, 2, 4, 1);
+    const sMap64 = bn128 ? exec.sMap : exec.sMapBuff, cells = nRows * nCols;
+    if (sMap64.length < cells) throw new Error("sMap holds " + sMap64.length + " entries, " + nRows + " x " + nCols + " expected");
+    // narrow and validate over the 32-bit halves of the file's words (little-endian: low half first): no BigInt per cell
+    const packed = new BigUint64Array(Math.ceil(cells / 2)), sMap32 = new Uint32Array(packed.buffer);
+    const halves = new Uint32Array(sMap64.buffer, sMap64.byteOffset, 2 * cells);
+    for (let k = 0; k < cells; k++) {
+        const lo = halves[2 * k];
+        if (halves[2 * k + 1] !== 0 || lo >= nW) throw new Error("sMap[" + k + "] = " + sMap64[k] + " names no signal (nWitness + nAdds = " + nW + ")");
+        sMap32[k] = lo;
+    }
+    return { bn128, nWitness, nAdds, nW, nRows, nCols, nLevels: plan.nLevels, levelStart: plan.levelStart,
+        adds: DevBuffer.from(plan.adds), coefs: DevBuffer.from(plan.coefs), sMap: DevBuffer.from(packed),
+        free() { this.adds.free(); this.coefs.free(); this.sMap.free(); } };
+}
+function execDev(p, wDev, dst, opts) {
+    opts = opts || {};
+    const wordsPer = p.bn128 ? 4 : 1, dstCols = opts.dstCols || p.nCols;
+    if (!isDev(wDev) || wDev.length < p.nW * wordsPer) throw new Error("execDev: w must be a DevBuffer of nW = " + p.nW + " elements");
+    if (!dst) dst = new DevBuffer(p.nRows * dstCols * wordsPer);
+    if (dst.length < p.nRows * dstCols * wordsPer) throw new Error("execDev: dst holds " + dst.length + " words");
+    addon.wtnsAddsDev(wDev.ptr, p.nWitness, p.adds.ptr, p.coefs.ptr, p.nAdds, p.levelStart, p.nLevels, p.bn128);
+    const bad = addon.wtnsGatherDev(wDev.ptr, p.nW, p.sMap.ptr, p.nRows, p.nCols, dst.ptr, dstCols, p.bn128, opts.montgomery !== false, !!opts.check);
+    if (opts.check && bad !== 0xFFFFFFFFFFFFFFFFn) throw new Error("sMap cell " + bad + " names no signal");
+    return dst;
+}
+
+module.exports = { readExecFile, readWtns, compressorExec, finalExec, prepareExec, execDev };

@@ -1,0 +1,242 @@
+"""The recursion witness on the device: the `*_exec` step of the reference -- compressorExec (src/compressor/compressor_exec.js:5-32)
+over Goldilocks, the loop of src/final/main_final_exec.js:50-67 over the BN254 scalar field -- through csrc/wtns_exec.hip.
+
+    exec_ = read_exec_file("c12a.exec", 12, "gl")            # or (path, nCols, "bn128") for a final .exec
+    trace = exec_gl(w, exec_)                                # host arrays in, the N x nCols trace out
+    prep = prepare(exec_)                                    # the circuit's constant tables into HBM, once
+    trace = exec_dev(prep, w_dev)                            # per proof: w_dev holds the witness in its first nWitness elements
+
+Goldilocks elements are uint64 words, Fr elements 4 words; the Fr witness is in normal form (a .wtns' values), the trace comes out in
+Montgomery form unless montgomery=False.  No arithmetic happens here: the planner, the additions and the gather are the library's.
+"""
+import ctypes as C
+import os
+import struct
+
+import numpy as np
+
+from ._lib import Pil2glError, call
+from . import _is_dev, _ptr, _stream, torch
+
+_U32P = C.POINTER(C.c_uint32)
+_WORDS = {"gl": 1, "bn128": 4}
+
+
+def _np_ptr(a):
+    return C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+
+
+def _strides(field):
+    """(idxStride, coefStride) of the tables as the files hold them"""
+    return (4, 4) if field == "gl" else (2, 8)
+
+
+def _tables(exec_):
+    """(operand table, coefficient table) as the plan reads them"""
+    if exec_["field"] == "gl":
+        adds = np.ascontiguousarray(exec_["adds"], np.uint64).reshape(-1)
+        return adds, adds[2:] if adds.size else adds
+    return np.ascontiguousarray(exec_["addsIdx"], np.uint64).reshape(-1), np.ascontiguousarray(exec_["addsCoef"], np.uint64).reshape(-1)
+
+
+def adds_plan(add_idx, n_witness, coefs=None, coef_words=1, idx_stride=2, coef_stride=None):
+    """pil2gl_wtns_adds_plan (host-only): -> {"adds": (nAdds, 4) uint32 records (a, b, dst, source position) sorted by level, "coefs": the
+    coefficients permuted alike (None without `coefs`), "levelStart": uint32[nLevels + 1], "nLevels"}"""
+    add_idx = np.ascontiguousarray(add_idx, np.uint64).reshape(-1)
+    n_adds = (add_idx.size + idx_stride - 2) // idx_stride if add_idx.size else 0
+    coef_stride = coef_stride or 2 * coef_words
+    if coefs is not None:
+        coefs = np.ascontiguousarray(coefs, np.uint64).reshape(-1)
+        if n_adds and coefs.size < (n_adds - 1) * coef_stride + 2 * coef_words:
+            raise Pil2glError("coefs holds %d words, %d additions need %d" % (coefs.size, n_adds, (n_adds - 1) * coef_stride + 2 * coef_words))
+    n = C.c_uint32()
+    call("pil2gl_wtns_adds_plan", _np_ptr(add_idx), idx_stride, n_adds, n_witness, None, 0, coef_words, None, None, None, 0, C.byref(n))
+    recs = np.zeros((n_adds, 4), np.uint32)
+    out_coef = np.zeros(2 * coef_words * n_adds, np.uint64) if coefs is not None else None
+    start = np.zeros(n.value + 1, np.uint32)
+    call("pil2gl_wtns_adds_plan", _np_ptr(add_idx), idx_stride, n_adds, n_witness, _np_ptr(coefs), coef_stride, coef_words,
+         _np_ptr(recs), _np_ptr(out_coef), _np_ptr(start), start.size, C.byref(n))
+    return {"adds": recs, "coefs": out_coef, "levelStart": start, "nLevels": n.value}
+
+
+def plan_info(add_idx, n_witness, idx_stride=2):
+    """pil2gl_debug_wtns_plan (host-only): levels, launches, the levels' widths"""
+    add_idx = np.ascontiguousarray(add_idx, np.uint64).reshape(-1)
+    n_adds = (add_idx.size + idx_stride - 2) // idx_stride if add_idx.size else 0
+    info = (C.c_uint32 * 5)()
+    call("pil2gl_debug_wtns_plan", _np_ptr(add_idx), idx_stride, n_adds, n_witness, info, None, 0)
+    widths = np.zeros(info[0], np.uint32)
+    call("pil2gl_debug_wtns_plan", _np_ptr(add_idx), idx_stride, n_adds, n_witness, info, _np_ptr(widths), widths.size)
+    return {"levels": info[0], "launches": info[1], "widest": info[2], "threads": info[3], "widestBlocks": info[4], "widths": [int(x) for x in widths]}
+
+
+def _exec_host(name, w, exec_, words, *tail):
+    w = np.ascontiguousarray(w, np.uint64).reshape(-1)
+    if w.size % words:
+        raise Pil2glError("w holds %d words, no multiple of %d" % (w.size, words))
+    idx, coef = _tables(exec_)
+    s_map = np.ascontiguousarray(exec_["sMap"], np.uint64).reshape(-1)
+    n_rows, n_cols = exec_["nSMap"], exec_["nCols"]
+    if s_map.size != n_rows * n_cols:
+        raise Pil2glError("sMap holds %d entries, %d x %d expected" % (s_map.size, n_rows, n_cols))
+    shape = (n_rows, n_cols) if words == 1 else (n_rows, n_cols, 4)
+    dst = np.zeros(shape, np.uint64)
+    call(name, _np_ptr(w), w.size // words, _np_ptr(idx), _np_ptr(coef), exec_["nAdds"], _np_ptr(s_map), n_rows, n_cols, _np_ptr(dst), *tail)
+    return dst
+
+
+def exec_gl(w, exec_):
+    """compressorExec with the witness in place of the wasm: w = uint64[nWitness] -> the (nSMap, nCols) trace, canonical"""
+    return _exec_host("pil2gl_wtns_exec", w, exec_, 1)
+
+
+def exec_bn128(w, exec_, montgomery=True):
+    """main_final_exec.js:50-67: w = (nWitness, 4) normal-form words -> the (nSMap, nCols, 4) trace, Montgomery words by default"""
+    return _exec_host("pil2gl_bn128_wtns_exec", w, exec_, 4, 1 if montgomery else 0)
+
+
+def _to_dev(a):
+    """bytes of a host table as a device tensor of whole words (the tail padded with zeros)"""
+    raw = a.tobytes()
+    raw += b"\0" * (-len(raw) % 16)
+    return torch.from_numpy(np.frombuffer(raw, np.int64).copy()).cuda()
+
+
+def prepare(exec_, n_witness=None):
+    """the circuit's constant tables into HBM, once per setup: the levelled additions, their coefficients and the sMap as 32-bit indices.
+    n_witness: the circuit's witness length (or exec_["nWitness"]).  An sMap value that names no signal is refused here, as the host form
+    refuses it."""
+    exec_ = dict(exec_, nWitness=exec_["nWitness"] if n_witness is None else n_witness)
+    field = exec_["field"]
+    words = _WORDS[field]
+    idx, coef = _tables(exec_)
+    si, sc = _strides(field)
+    n_adds, n_rows, n_cols = exec_["nAdds"], exec_["nSMap"], exec_["nCols"]
+    p = adds_plan(idx, exec_["nWitness"], coef, words, si, sc)
+    s_map = np.ascontiguousarray(exec_["sMap"], np.uint64).reshape(-1)
+    n_w = exec_["nWitness"] + n_adds
+    if s_map.size != n_rows * n_cols:
+        raise Pil2glError("sMap holds %d entries, %d x %d expected" % (s_map.size, n_rows, n_cols))
+    bad = np.flatnonzero(s_map >= n_w)
+    if bad.size:
+        raise Pil2glError("sMap[%d] = %d names no signal (nWitness + nAdds = %d)" % (bad[0], s_map[bad[0]], n_w))
+    return {"field": field, "nWitness": exec_["nWitness"], "nAdds": n_adds, "nW": n_w, "nRows": n_rows, "nCols": n_cols,
+            "adds": _to_dev(p["adds"]), "coefs": _to_dev(p["coefs"]), "sMap": _to_dev(s_map.astype(np.uint32)),
+            "levelStart": p["levelStart"], "nLevels": p["nLevels"]}
+
+
+def adds_dev(prep, w_dev):
+    """the additions in place: w_dev = device tensor of nW elements whose first nWitness hold the witness; enqueues on the current stream"""
+    name = "pil2gl_wtns_adds_dev" if prep["field"] == "gl" else "pil2gl_bn128_wtns_adds_dev"
+    if w_dev.numel() < prep["nW"] * _WORDS[prep["field"]]:
+        raise Pil2glError("w holds %d words, nW = %d elements needed" % (w_dev.numel(), prep["nW"]))
+    call(name, _ptr(w_dev), prep["nWitness"], _ptr(prep["adds"]), _ptr(prep["coefs"]), prep["nAdds"],
+         prep["levelStart"].ctypes.data_as(C.c_void_p), prep["nLevels"], _stream())
+
+
+def gather_dev(prep, w_dev, dst=None, dst_cols=None, montgomery=True, check=False, s_map=None):
+    """the fill: -> dst, a (nRows, dstCols[, 4]) device tensor (given or new); check=True blocks and returns (dst, firstBad) with
+    firstBad None when every index names a signal.  s_map: another device table of nRows x nCols 32-bit indices in place of prep's."""
+    words = _WORDS[prep["field"]]
+    dst_cols = dst_cols or prep["nCols"]
+    n = prep["nRows"] * dst_cols * words
+    if dst is None:
+        dst = torch.empty((prep["nRows"], dst_cols) + ((4,) if words == 4 else ()), dtype=w_dev.dtype, device=w_dev.device)
+    if dst.numel() < n:
+        raise Pil2glError("dst holds %d words, %d needed" % (dst.numel(), n))
+    bad = C.c_uint64()
+    args = [_ptr(w_dev), prep["nW"], _ptr(s_map if s_map is not None else prep["sMap"]), prep["nRows"], prep["nCols"], _ptr(dst), dst_cols]
+    if words == 4:
+        args.append(1 if montgomery else 0)
+    call("pil2gl_wtns_gather_dev" if words == 1 else "pil2gl_bn128_wtns_gather_dev", *args, C.byref(bad) if check else None, _stream())
+    if check:
+        return dst, (None if bad.value == 0xFFFFFFFFFFFFFFFF else bad.value)
+    return dst
+
+
+def exec_dev(prep, w_dev, dst=None, dst_cols=None, montgomery=True, check=False):
+    """per proof: the additions, then the fill, both on the current stream; the result is what interpolate / bn128.ifft read"""
+    if not _is_dev(w_dev):
+        raise Pil2glError("exec_dev takes a device tensor (exec_gl / exec_bn128 take host arrays)")
+    adds_dev(prep, w_dev)
+    return gather_dev(prep, w_dev, dst, dst_cols, montgomery, check)
+
+
+# ---- files ----
+def _short(path, found, expected):
+    return Pil2glError("%s: %d bytes found, %d expected" % (path, found, expected))
+
+
+def _sections(path, kind):
+    """the minimal iden3 binfile reader: 4-byte type, u32 version, u32 section count, then (u32 id, u64 size, payload) until the file
+    ends -> (version, {id: (offset, size)})"""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        head = f.read(12)
+        if len(head) < 12:
+            raise _short(path, size, 12)
+        if head[:4] != kind.encode():
+            raise Pil2glError("%s: type %r, %r expected" % (path, head[:4], kind))
+        version, count = struct.unpack("<II", head[4:])
+        out, at = {}, 12
+        while at < size and len(out) < count:
+            f.seek(at)
+            h = f.read(12)
+            if len(h) < 12:
+                raise _short(path, size, at + 12)
+            sid, n = struct.unpack("<IQ", h)
+            if at + 12 + n > size:
+                raise _short(path, size, at + 12 + n)
+            out[sid] = (at + 12, n)
+            at += 12 + n
+    return version, out
+
+
+def _section(path, secs, sid, expected=None):
+    if sid not in secs:
+        raise Pil2glError("%s: no section %d" % (path, sid))
+    off, n = secs[sid]
+    if expected is not None and n < expected:
+        raise _short(path, os.path.getsize(path), os.path.getsize(path) + expected - n)
+    return np.fromfile(path, np.uint8, n if expected is None else expected, offset=off)
+
+
+def read_exec_file(path, n_cols, field="gl", n_witness=None):
+    """readExecFile of compressor/exec_helpers.js:26-47 (field "gl": flat u64) or final/exec_helpers.js:14-39 (field "bn128": binfile
+    "exec") -> {"field", "nAdds", "nSMap", "nCols", "sMap", and "adds" (gl: 4 nAdds words a, b, ca, cb) or "addsIdx" + "addsCoef" (bn128:
+    2 nAdds indices, (2 nAdds, 4) Montgomery words)}.  A file shorter than its header says is refused with name, found and expected size."""
+    size = os.path.getsize(path)
+    if field == "gl":
+        if size < 16:
+            raise _short(path, size, 16)
+        n_adds, n_smap = (int(x) for x in np.fromfile(path, np.uint64, 2))
+        want = 8 * (2 + 4 * n_adds + n_smap * n_cols)
+        if size < want:
+            raise _short(path, size, want)
+        body = np.fromfile(path, np.uint64, 4 * n_adds + n_smap * n_cols, offset=16)
+        out = {"adds": body[:4 * n_adds], "sMap": body[4 * n_adds:]}
+    elif field == "bn128":
+        version, secs = _sections(path, "exec")
+        if version != 1:
+            raise Pil2glError("%s: exec version %d, 1 expected" % (path, version))
+        n_adds, n_smap = (int(x) for x in _section(path, secs, 2, 16).view(np.uint64))
+        out = {"addsIdx": _section(path, secs, 3, 16 * n_adds).view(np.uint64),
+               "addsCoef": _section(path, secs, 4, 64 * n_adds).view(np.uint64).reshape(-1, 4),
+               "sMap": _section(path, secs, 5, 8 * n_smap * n_cols).view(np.uint64)}
+    else:
+        raise Pil2glError("field is \"gl\" or \"bn128\"")
+    out.update(field=field, nAdds=n_adds, nSMap=n_smap, nCols=n_cols)
+    if n_witness is not None:
+        out["nWitness"] = n_witness
+    return out
+
+
+def read_wtns(path):
+    """a .wtns (binfile "wtns"): -> {"n8", "prime", "nWitness", "w": (nWitness, n8 / 8) uint64 words, normal form}"""
+    _, secs = _sections(path, "wtns")
+    head = _section(path, secs, 1, 4).tobytes()
+    n8 = struct.unpack("<I", head[:4])[0]
+    head = _section(path, secs, 1, 8 + n8).tobytes()
+    n = struct.unpack("<I", head[4 + n8:8 + n8])[0]
+    w = _section(path, secs, 2, n * n8).view(np.uint64).reshape(n, n8 // 8)
+    return {"n8": n8, "prime": int.from_bytes(head[4:4 + n8], "little"), "nWitness": n, "w": w}
