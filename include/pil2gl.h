@@ -25,7 +25,7 @@
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
  *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod and bn128_gsum; land_rows with a null hostFirstBad;
- *      wtns_adds and bn128_wtns_adds, wtns_gather and bn128_wtns_gather with a null hostFirstBad.
+ *      wtns_adds and bn128_wtns_adds, wtns_gather and bn128_wtns_gather with a null hostFirstBad, conn_pols and bn128_conn_pols with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
  *    The following _dev calls BLOCK until their work on the stream has finished, because they hand a result to the host or
@@ -34,7 +34,7 @@
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
  *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, compute_fri_pol, build_lev (small host tables),
  *      h1h2 and bn128_h1h2 (the missing row comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
- *      land_rows, wtns_gather and bn128_wtns_gather with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
+ *      land_rows, wtns_gather, bn128_wtns_gather, conn_pols and bn128_conn_pols with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
  *    So do the host-pointer verifier calls roots_from_group_proofs and bn128_roots_from_group_proofs (roots copied to host memory).
  *    bn128_group_proof[s]_dev take no stream: their copies and their gather kernel run on the NULL stream, which orders them after work
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -777,6 +777,54 @@ int pil2gl_bn128_wtns_exec(const uint64_t *hostW, uint64_t nWitness, const uint6
  * l < widthCap (may be NULL).  Refuses what pil2gl_wtns_adds_plan refuses. */
 int pil2gl_debug_wtns_plan(const uint64_t *hostAddIdx, uint64_t idxStride, uint64_t nAdds, uint64_t nWitness, uint32_t *outInfo /* [5] */,
                            uint32_t *outWidths, uint32_t widthCap);
+
+/* ---- connection polynomials: the constant columns S of a recursion circuit from its sMap (csrc/conn_pols.hip, csrc/conn_plan.h) ----
+ * The compressor and final setups build the copy-constraint permutation with two host loops (src/compressor/compressor12_setup.js:470-500,
+ * compressor18_setup.js:534-560, src/final/final6_setup.js:243-270, final9_setup.js:264-290, finalfflonk_setup.js:136-163 over curve.Fr,
+ * test/plonk2pil/plonksetup.js:79-105):
+ *   S[j][i] = id(i, j) = w^i ks1[j] for i < N, j < nCols, with ks1[0] = 1 and ks1[j] = ks[j - 1] (w = F.w[nBits], ks = getKs(F, nCols - 1));
+ *   for i < nRows, for j < nCols, s = sMap[j][i], s != 0: the first time s is seen its cell is remembered, every later time
+ *   connect(S[first.col], first.row, S[j], i) swaps the two values (polutils.js:166).
+ * The result has a closed form: with c_0 < c_1 < ... < c_k the cells of one signal in flat order i nCols + j, S[c_m] = id(c_{m-1}) for
+ * m >= 1 and S[c_0] = id(c_k).  A zero cell, a signal seen once and every row at or past nRows keep id of themselves.  The library sorts
+ * the cells by signal (stable, 8 bits a pass) and fills S from each cell's predecessor; the values equal the reference's, cell for cell.
+ * An element is one u64 (Goldilocks: w and ks1 words in [p, 2^64) count as their value mod p, outputs canonical) or four u64 (Fr: w, ks1
+ * and the output are MONTGOMERY words, what finalfflonk_setup.js leaves in constPols.Final.S through writeToBigBufferFr; any 256-bit pattern
+ * counts as its value mod r, outputs canonical).  w (1 element) and ks1 (nCols elements, ks1[0] included) are HOST pointers in every form
+ * and are read before the call returns; the library multiplies what it is given (getKs is pilcom's).
+ *
+ * pil2gl_conn_plan: host-only, no device.  outInfo[0] = digit passes of the sort, ceil(bits(nW - 1) / 8) (0 when no cell can name a signal);
+ * [1] = threads per workgroup; [2] = cells per workgroup of a pass; [3] = workgroups of a pass's histogram and scatter; [4] = workgroups
+ * of the histogram's scan; [5], [6] = bits of the low and high power tables (2^[5] entries a column, 2^[6] entries); [7] = kernel launches
+ * of a call, 4 + 5 passes (2 without cells).  *scratchBytes = the working buffer, a multiple of 16: with cells = nRows nCols and
+ * T = nCols 2^[5] + 2^[6], 16 + 8 elemWords T + 4 r16(4 cells) + 1024 [3] + r16(4 [4]) where r16 rounds up to 16 -- below
+ * 16 cells + cells / 4 + cells / 16384 + 8 elemWords T + 2048 bytes; 0 for nCols = 0.  PIL2GL_EINVAL: nRows nCols >= 2^32, nW >= 2^32,
+ * nRows > N, N no power of two or above 2^32, nCols > 64, elemWords not 1 or 4.
+ * pil2gl_[bn128_]conn_pols_dev: sMap32 = device, nRows x nCols 32-bit indices, row-major (what pil2gl_wtns_gather_dev reads); scratch =
+ * device, 16-byte aligned, scratchBytes >= the plan's; dst = device, element (i, j) at dst[(i dstStride + dstOffset + j) elemWords], the
+ * column contract of csrc/bn_column.h applied to nCols adjacent columns of a row-major matrix dstStride elements wide, of which only those
+ * nCols are written, N rows of them.  An index >= nW counts as zero (the cell keeps its identity); with hostFirstBad the call BLOCKS and
+ * reports the smallest flat cell i nCols + j holding one, UINT64_MAX when clean; with NULL it only enqueues.  PIL2GL_EINVAL: what the plan
+ * refuses, dstStride < dstOffset + nCols, dstStride >= 2^32, a scratch that is too small, dst overlapping sMap32 or the scratch, the
+ * scratch overlapping sMap32, a null or misaligned buffer (dst 8-byte, Fr 16-byte).  nCols = 0 is PIL2GL_OK and needs no device.
+ * pil2gl_[bn128_]conn_pols: host pointers; stage, compute, copy out N x nCols elements, row-major (hostDst[(i nCols + j) elemWords]).
+ * sMapLayout PIL2GL_CONN_SMAP_ROWS_U64: hostSMap = nRows x nCols u64, row-major (an exec file's table); PIL2GL_CONN_SMAP_COLS_U32: nCols
+ * arrays of N u32 one after the other (the setups' sMap[j][i] at hostSMap[j N + i]), of which rows below nRows are read.  A value >= nW is
+ * PIL2GL_EINVAL naming the cell.  Every refusal comes before the first device call; without a device the compute calls return
+ * PIL2GL_ENODEV. */
+#define PIL2GL_CONN_SMAP_ROWS_U64 0
+#define PIL2GL_CONN_SMAP_COLS_U32 1
+int pil2gl_conn_plan(uint64_t nRows, uint64_t nCols, uint64_t nW, uint64_t N, uint32_t elemWords, uint32_t *outInfo /* [8] */, uint64_t *scratchBytes);
+int pil2gl_conn_pols_dev(const uint32_t *sMap32, uint64_t nRows, uint64_t nCols, uint64_t nW, uint64_t N, const uint64_t *hostW, const uint64_t *hostKs1,
+                         uint64_t *dst, uint64_t dstStride, uint64_t dstOffset, uint64_t *scratch, uint64_t scratchBytes, uint64_t *hostFirstBad,
+                         void *stream);
+int pil2gl_bn128_conn_pols_dev(const uint32_t *sMap32, uint64_t nRows, uint64_t nCols, uint64_t nW, uint64_t N, const uint64_t *hostW,
+                               const uint64_t *hostKs1, uint64_t *dst, uint64_t dstStride, uint64_t dstOffset, uint64_t *scratch, uint64_t scratchBytes,
+                               uint64_t *hostFirstBad, void *stream);
+int pil2gl_conn_pols(const void *hostSMap, int sMapLayout, uint64_t nRows, uint64_t nCols, uint64_t nW, uint64_t N, const uint64_t *hostW,
+                     const uint64_t *hostKs1, uint64_t *hostDst);
+int pil2gl_bn128_conn_pols(const void *hostSMap, int sMapLayout, uint64_t nRows, uint64_t nCols, uint64_t nW, uint64_t N, const uint64_t *hostW,
+                           const uint64_t *hostKs1, uint64_t *hostDst);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

@@ -550,6 +550,40 @@ FN(Bn128WtnsExec) {        // (w, nWitness, addsIdx, addsCoef, nAdds, sMap, nRow
     P2(env, pil2gl_bn128_wtns_exec(w, nWitness, idx, coef, nAdds, sm, nRows, nCols, d, mont)); return mk_undefined(env);
 }
 
+// ---- connection polynomials: the S columns of a recursion circuit from its sMap (csrc/conn_pols.hip; js/witness_exec.js) ----
+FN(ConnPlan) {             // (nRows, nCols, nW, N, elemWords) -> { passes, threads, tile, sortBlocks, scanChunks, loBits, hiBits, launches, scratchBytes }
+    Args a(env, info); uint64_t nRows = a.u64(0), nCols = a.u64(1), nW = a.u64(2), N = a.u64(3); uint32_t ew = (uint32_t)a.u64(4); if (!a.ok) return nullptr;
+    uint32_t out[8]; uint64_t bytes = 0;
+    P2(env, pil2gl_conn_plan(nRows, nCols, nW, N, ew, out, &bytes));
+    static const char *names[8] = { "passes", "threads", "tile", "sortBlocks", "scanChunks", "loBits", "hiBits", "launches" };
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 8; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
+    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "scratchBytes", v);
+    return o;
+}
+// (dSMap32, nRows, nCols, nW, N, consts = w then ks1 (1 + nCols elements), dDst, dstStride, dstOffset, dScratch, scratchBytes, check)
+//   -> first bad cell as BigInt (2^64-1: none), undefined without check
+static napi_value conn_pols_dev(napi_env env, napi_callback_info info, uint32_t ew) {
+    Args a(env, info); uint64_t *sm = DP(0); uint64_t nRows = a.u64(1), nCols = a.u64(2), nW = a.u64(3), N = a.u64(4);
+    uint64_t *c = a.arr(5, ew * (1 + nCols)); uint64_t *d = DP(6); uint64_t stride = a.u64(7), off = a.u64(8); uint64_t *scr = DP(9);
+    uint64_t bytes = a.u64(10); bool check = a.u64(11) != 0; if (!a.ok) return nullptr;
+    uint64_t bad = ~0ull;
+    P2(env, (ew == 4 ? pil2gl_bn128_conn_pols_dev : pil2gl_conn_pols_dev)((const uint32_t *)sm, nRows, nCols, nW, N, c, c + ew, d, stride, off, scr, bytes,
+                                                                          check ? &bad : nullptr, nullptr));
+    return check ? mk_bigint(env, bad) : mk_undefined(env);
+}
+FN(ConnPolsDev) { return conn_pols_dev(env, info, 1); }
+FN(Bn128ConnPolsDev) { return conn_pols_dev(env, info, 4); }
+// (sMap words, layout (0: nRows x nCols u64; 1: nCols arrays of N u32, packed two a word), nRows, nCols, nW, N, consts, dst (N nCols elements))
+static napi_value conn_pols_host(napi_env env, napi_callback_info info, uint32_t ew) {
+    Args a(env, info); int layout = (int)a.u64(1); uint64_t nRows = a.u64(2), nCols = a.u64(3), nW = a.u64(4), N = a.u64(5);
+    uint64_t *sm = a.arr(0, layout == PIL2GL_CONN_SMAP_COLS_U32 ? (N * nCols + 1) / 2 : nRows * nCols);
+    uint64_t *c = a.arr(6, ew * (1 + nCols)), *d = a.arr(7, ew * N * nCols); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_conn_pols : pil2gl_conn_pols)(sm, layout, nRows, nCols, nW, N, c, c + ew, d)); return mk_undefined(env);
+}
+FN(ConnPols) { return conn_pols_host(env, info, 1); }
+FN(Bn128ConnPols) { return conn_pols_host(env, info, 4); }
+
 // ---- BN128 Merkle commitment (merklehash_bn128_p.js / merklehash_bn128_worker.js) ----
 FN(Bn128Poseidon) {  // (in BigUint64Array(4*nIn*count) normal form, init BigUint64Array(4*count)|null, count, nIn, nOut, out(4*nOut*count))
     Args a(env, info); uint64_t count = a.u64(2), nIn = a.u64(3), nOut = a.u64(4);
@@ -735,6 +769,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128BatchInverseDev", Bn128BatchInverseDev }, { "bn128GprodDev", Bn128GprodDev }, { "bn128GsumDev", Bn128GsumDev },
         { "bn128H1h2Dev", Bn128H1h2Dev },
         { "wtnsAddsPlan", WtnsAddsPlan }, { "wtnsAddsDev", WtnsAddsDev }, { "wtnsGatherDev", WtnsGatherDev }, { "wtnsExec", WtnsExec }, { "bn128WtnsExec", Bn128WtnsExec },
+        { "connPlan", ConnPlan }, { "connPolsDev", ConnPolsDev }, { "bn128ConnPolsDev", Bn128ConnPolsDev }, { "connPols", ConnPols }, { "bn128ConnPols", Bn128ConnPols },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

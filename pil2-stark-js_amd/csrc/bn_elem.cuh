@@ -16,6 +16,17 @@ __device__ __forceinline__ void ld_elem(const uint4 *p, u32 x[8]) {
 __device__ __forceinline__ void st_elem(uint4 *p, const u32 x[8]) {
     p[0] = make_uint4(x[0], x[1], x[2], x[3]); p[1] = make_uint4(x[4], x[5], x[6], x[7]);
 }
+// any 256-bit pattern -> its value mod r: 2^256 < 6 r
+__device__ __forceinline__ void reduce256(u32 x[8]) {
+    u32 t[9];
+#pragma unroll
+    for (int i = 0; i < 8; i++) t[i] = x[i];
+    t[8] = 0;
+#pragma unroll
+    for (int k = 0; k < 5; k++) cond_sub_r(t);
+#pragma unroll
+    for (int i = 0; i < 8; i++) x[i] = t[i];
+}
 // all eight 32-bit words decide
 __device__ __forceinline__ bool is_zero(const u32 x[8]) { return (x[0] | x[1] | x[2] | x[3] | x[4] | x[5] | x[6] | x[7]) == 0; }
 __device__ __forceinline__ bool is_zero(const uint4 &a, const uint4 &b) { return ((a.x | a.y | a.z | a.w) | (b.x | b.y | b.z | b.w)) == 0; }

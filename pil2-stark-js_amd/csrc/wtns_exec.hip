@@ -41,18 +41,6 @@ __global__ void __launch_bounds__(THREADS) wtns_adds_gl_kernel(u64 *w, u32 nWitn
     }
 }
 
-// any 256-bit pattern -> its value mod r: 2^256 < 6 r
-__device__ __forceinline__ void fr_reduce256(u32 x[8]) {
-    u32 t[9];
-#pragma unroll
-    for (int i = 0; i < 8; i++) t[i] = x[i];
-    t[8] = 0;
-#pragma unroll
-    for (int k = 0; k < 5; k++) bn::cond_sub_r(t);
-#pragma unroll
-    for (int i = 0; i < 8; i++) x[i] = t[i];
-}
-
 // w: 2 halves an element; coefs: 4 halves an addition (ca, cb)
 __global__ void __launch_bounds__(THREADS) wtns_adds_fr_kernel(uint4 *w, u32 nWitness, u32 nW, const uint4 *__restrict__ adds,
                                                                const uint4 *__restrict__ coefs, u32 count) {
@@ -62,11 +50,11 @@ __global__ void __launch_bounds__(THREADS) wtns_adds_fr_kernel(uint4 *w, u32 nWi
         u32 x[8], y[8], c[8];
         bn::ld_elem(w + 2 * (size_t)r.x, x);
         bn::ld_elem(coefs + 4 * (size_t)k, c);
-        fr_reduce256(c);
+        bn::reduce256(c);
         bn::fr_mul(x, x, c);                         // normal x Montgomery = the normal-form product, canonical
         bn::ld_elem(w + 2 * (size_t)r.y, y);
         bn::ld_elem(coefs + 4 * (size_t)k + 2, c);
-        fr_reduce256(c);
+        bn::reduce256(c);
         bn::fr_mul(y, y, c);
         bn::fr_add(x, y);
         bn::st_elem(w + 2 * (size_t)r.z, x);
@@ -132,7 +120,7 @@ __global__ void __launch_bounds__(THREADS) wtns_gather_fr_kernel(const uint4 *__
                 for (int i = 0; i < 8; i++) r2[i] = bn::r2_limb(i);
                 bn::fr_mul(x, x, r2);
             } else {
-                fr_reduce256(x);
+                bn::reduce256(x);
             }
             out = h ? make_uint4(x[4], x[5], x[6], x[7]) : make_uint4(x[0], x[1], x[2], x[3]);
         }

@@ -11,6 +11,13 @@
 //   prepareExec(exec, nCols, nWitness)       once per setup -> { adds, coefs, sMap, levelStart, ... } with the tables as DevBuffers
 //   execDev(prepared, wDev, dst, opts)       per proof: wDev = DevBuffer of nW elements whose first nWitness hold the witness; dst = DevBuffer
 //                                            of nRows x (opts.dstCols || nCols) elements, made when absent; opts.check: throw on a bad index
+//   connectionPols(F, sMap, N, ks, { w })    the setups' two S loops (compressor12_setup.js:470-500 and siblings; csrc/conn_pols.hip): sMap = the
+//                                            setups' own array of nCols Uint32Array(N), ks = getKs(F, nCols - 1), w = F.w[log2 N] unless given
+//                                            -> S[j][i]: BigInts over Goldilocks, 32-byte Montgomery Uint8Arrays over curve.Fr, so that a
+//                                            setup says constPols.Compressor.S = connectionPols(F, sMap, N, ks)
+//   connectionPolsDev(prepared, dConst, { N, ks, w, stride, offset, check })   the same from prepareExec's resident sMap into columns
+//                                            [offset, offset + nCols) of dConst, a DevBuffer of N rows of `stride` elements (made when
+//                                            absent, stride = nCols); nothing is copied to the host; check: throw on a bad index
 // Node 12: no optional chaining.
 "use strict";
 const fs = require("fs");
@@ -132,4 +139,54 @@ function execDev(p, wDev, dst, opts) {
     return dst;
 }
 
-module.exports = { readExecFile, readWtns, compressorExec, finalExec, prepareExec, execDev };
+// ---- connection polynomials ----
+const FR_ONE = (() => {       // 2^256 mod r: one in Montgomery form, as bytes
+    const v = (1n << 256n) % 21888242871839275222246405745257275088548364400416034343698204186575808495617n, b = new Uint8Array(32);
+    for (let i = 0; i < 32; i++) b[i] = Number((v >> BigInt(8 * i)) & 0xFFn);
+    return b;
+})();
+// w, then ks1 = one and the caller's nCols - 1 elements, as the library reads them
+function connConsts(bn128, nCols, w, one, ks) {
+    if (!ks || ks.length !== Math.max(nCols - 1, 0)) throw new Error("connectionPols: ks must hold nCols - 1 = " + (nCols - 1) + " elements");
+    if (w === undefined) throw new Error("connectionPols: no root of unity w");
+    const ew = bn128 ? 4 : 1, c = new BigUint64Array(ew * (1 + nCols));
+    [w, one].concat(Array.from(ks)).slice(0, 1 + nCols).forEach((v, k) => { if (bn128) c.set(stage.asWords(v), 4 * k); else c[k] = BigInt(v); });
+    return c;
+}
+function connectionPols(F, sMap, N, ks, opts) {
+    const bn128 = F.n8 === 32, ew = bn128 ? 4 : 1, nCols = sMap.length;
+    const consts = connConsts(bn128, nCols, opts && opts.w !== undefined ? opts.w : F.w[Math.log2(N)], F.one, ks);
+    const packed = new BigUint64Array(Math.ceil(nCols * N / 2)), flat = new Uint32Array(packed.buffer);
+    let top = 0;
+    for (let j = 0; j < nCols; j++) {
+        if (sMap[j].length !== N) throw new Error("connectionPols: sMap[" + j + "] holds " + sMap[j].length + " entries, N = " + N + " expected");
+        flat.set(sMap[j], j * N);
+        for (let i = 0; i < N; i++) if (sMap[j][i] > top) top = sMap[j][i];
+    }
+    const out = new BigUint64Array(ew * N * nCols);
+    (bn128 ? addon.bn128ConnPols : addon.connPols)(packed, 1, N, nCols, top + 1, N, consts, out);
+    const bytes = new Uint8Array(out.buffer), S = [];
+    for (let j = 0; j < nCols; j++) {
+        const col = new Array(N);
+        for (let i = 0; i < N; i++) col[i] = bn128 ? bytes.subarray(32 * (i * nCols + j), 32 * (i * nCols + j + 1)) : out[i * nCols + j];
+        S.push(col);
+    }
+    return S;
+}
+function connectionPolsDev(p, dConst, opts) {
+    opts = opts || {};
+    const ew = p.bn128 ? 4 : 1, N = opts.N, offset = opts.offset || 0, stride = opts.stride || p.nCols + offset;
+    const consts = connConsts(p.bn128, p.nCols, opts.w, p.bn128 ? FR_ONE : 1n, opts.ks);
+    const plan = addon.connPlan(p.nRows, p.nCols, p.nW, N, ew);
+    if (!dConst) dConst = new DevBuffer(N * stride * ew);
+    if (!isDev(dConst) || dConst.length < ((N - 1) * stride + offset + p.nCols) * ew) throw new Error("connectionPolsDev: dConst must be a DevBuffer of N = " + N + " rows of " + stride + " elements");
+    const work = new DevBuffer(plan.scratchBytes / 8);
+    try {
+        const bad = (p.bn128 ? addon.bn128ConnPolsDev : addon.connPolsDev)(p.sMap.ptr, p.nRows, p.nCols, p.nW, N, consts, dConst.ptr, stride, offset, work.ptr,
+            plan.scratchBytes, !!opts.check);
+        if (opts.check && bad !== 0xFFFFFFFFFFFFFFFFn) throw new Error("sMap cell " + bad + " names no signal");
+    } finally { work.free(); }                       // releasing device memory waits for the work enqueued on it
+    return dConst;
+}
+
+module.exports = { readExecFile, readWtns, compressorExec, finalExec, prepareExec, execDev, connectionPols, connectionPolsDev };

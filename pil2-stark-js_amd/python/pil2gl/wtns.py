@@ -8,6 +8,11 @@ over Goldilocks, the loop of src/final/main_final_exec.js:50-67 over the BN254 s
 
 Goldilocks elements are uint64 words, Fr elements 4 words; the Fr witness is in normal form (a .wtns' values), the trace comes out in
 Montgomery form unless montgomery=False.  No arithmetic happens here: the planner, the additions and the gather are the library's.
+
+The same resident sMap drives the setups' connection polynomials (csrc/conn_pols.hip), the constant columns S of the copy constraints:
+
+    S = conn_pols(s_map, n_cols, N, w, ks)                   # host arrays in, the (N, nCols) columns out
+    S = conn_pols_dev(prep, N, w, ks)                        # from what prepare() left in HBM, into a device matrix
 """
 import ctypes as C
 import os
@@ -160,6 +165,74 @@ def exec_dev(prep, w_dev, dst=None, dst_cols=None, montgomery=True, check=False)
         raise Pil2glError("exec_dev takes a device tensor (exec_gl / exec_bn128 take host arrays)")
     adds_dev(prep, w_dev)
     return gather_dev(prep, w_dev, dst, dst_cols, montgomery, check)
+
+
+# ---- connection polynomials ----
+_FR_ONE = [((1 << 256) % 21888242871839275222246405745257275088548364400416034343698204186575808495617 >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)]
+
+
+def conn_plan(n_rows, n_cols, n_w, N, field="gl"):
+    """pil2gl_conn_plan (host-only): the sort's passes, the launch geometry, the working buffer"""
+    info = (C.c_uint32 * 8)()
+    nbytes = C.c_uint64()
+    call("pil2gl_conn_plan", n_rows, n_cols, n_w, N, _WORDS[field], info, C.byref(nbytes))
+    names = ("passes", "threads", "tile", "sortBlocks", "scanChunks", "loBits", "hiBits", "launches")
+    return dict(zip(names, (int(x) for x in info)), scratchBytes=nbytes.value)
+
+
+def _conn_consts(w, ks, n_cols, words):
+    """(w, ks1) as the library reads them: ks1 = one, then the caller's n_cols - 1 elements of ks"""
+    w = np.ascontiguousarray(w, np.uint64).reshape(-1)
+    ks = np.ascontiguousarray(ks, np.uint64).reshape(-1)
+    if w.size != words or ks.size != max(n_cols - 1, 0) * words:
+        raise Pil2glError("w holds %d words and ks %d; one element and nCols - 1 = %d elements of %d words expected" % (w.size, ks.size, n_cols - 1, words))
+    one = np.array([1] if words == 1 else _FR_ONE, np.uint64)
+    return w, np.concatenate([one, ks])
+
+
+def conn_pols(s_map, n_cols, N, w, ks, field="gl", n_w=None):
+    """the setups' two S loops (compressor12_setup.js:470-500 and its five siblings): -> the (N, nCols[, 4]) columns, S[j][i] at [i, j].
+    s_map: a uint32 array of shape (nCols, N), the setups' own sMap[j][i], or the exec file's table, nRows x nCols row-major (any integer
+    type).  w = F.w[nBits] and ks = getKs(F, nCols - 1) as words: uint64 for Goldilocks, (., 4) Montgomery words for Fr, which is also
+    what comes out.  n_w: one more than the highest signal (found when absent)."""
+    words = _WORDS[field]
+    s_map = np.asarray(s_map)
+    if s_map.dtype == np.uint32 and s_map.shape == (n_cols, N):
+        layout, n_rows, s_map = 1, N, np.ascontiguousarray(s_map)
+    else:
+        s_map = np.ascontiguousarray(s_map, np.uint64).reshape(-1)
+        if n_cols == 0 or s_map.size % n_cols:
+            raise Pil2glError("sMap holds %d entries, no multiple of nCols = %d" % (s_map.size, n_cols))
+        layout, n_rows = 0, s_map.size // n_cols
+    if n_w is None:
+        n_w = int(s_map.max()) + 1 if s_map.size else 1
+    w, ks1 = _conn_consts(w, ks, n_cols, words)
+    dst = np.zeros((N, n_cols) + ((4,) if words == 4 else ()), np.uint64)
+    call("pil2gl_conn_pols" if words == 1 else "pil2gl_bn128_conn_pols", _np_ptr(s_map), layout, n_rows, n_cols, n_w, N, _np_ptr(w), _np_ptr(ks1), _np_ptr(dst))
+    return dst
+
+
+def conn_pols_dev(prep, N, w, ks, dst=None, dst_stride=None, dst_offset=0, check=False, s_map=None):
+    """the same from what prepare() returned: -> dst, a device matrix of N rows and dst_stride (default nCols) elements a row, of which
+    columns [dst_offset, dst_offset + nCols) are written -- the layout interpolate / merkelize read.  The working buffer comes from the
+    plan and lives for the call; enqueues on the current stream.  check=True blocks and returns (dst, firstBad), firstBad None when every
+    index names a signal.  s_map: another device table of nRows x nCols 32-bit indices in place of prep's."""
+    words = _WORDS[prep["field"]]
+    n_cols = prep["nCols"]
+    dst_stride = n_cols + dst_offset if dst_stride is None else dst_stride
+    plan = conn_plan(prep["nRows"], n_cols, prep["nW"], N, prep["field"])
+    w, ks1 = _conn_consts(w, ks, n_cols, words)
+    if dst is None:
+        dst = torch.empty((N, dst_stride) + ((4,) if words == 4 else ()), dtype=torch.int64, device=prep["sMap"].device)
+    if dst.numel() < ((N - 1) * dst_stride + dst_offset + n_cols) * words:
+        raise Pil2glError("dst holds %d words, %d rows of stride %d need more" % (dst.numel(), N, dst_stride))
+    work = torch.empty(max(plan["scratchBytes"] // 8, 2), dtype=torch.int64, device=prep["sMap"].device)
+    bad = C.c_uint64()
+    call("pil2gl_conn_pols_dev" if words == 1 else "pil2gl_bn128_conn_pols_dev", _ptr(s_map if s_map is not None else prep["sMap"]), prep["nRows"], n_cols,
+         prep["nW"], N, _np_ptr(w), _np_ptr(ks1), _ptr(dst), dst_stride, dst_offset, _ptr(work), plan["scratchBytes"], C.byref(bad) if check else None, _stream())
+    if check:
+        return dst, (None if bad.value == 0xFFFFFFFFFFFFFFFF else bad.value)
+    return dst
 
 
 # ---- files ----
