@@ -27,6 +27,24 @@ __device__ __forceinline__ void reduce256(u32 x[8]) {
 #pragma unroll
     for (int i = 0; i < 8; i++) x[i] = t[i];
 }
+// R^2 mod r: fr_mul by it takes a normal-form value to its Montgomery word
+__device__ __forceinline__ void ld_r2(u32 r2[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) r2[i] = r2_limb(i);
+}
+// base^e by square and multiply, Montgomery in and out
+__device__ __forceinline__ void fr_pow(u32 out[8], const u32 base[8], u64 e) {
+    u32 b[8], one[8] = { 1, 0, 0, 0, 0, 0, 0, 0 }, r2[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) b[i] = base[i];
+    ld_r2(r2);
+    fr_mul(out, r2, one);                            // R^2 / R: one
+    while (e) {
+        if (e & 1) fr_mul(out, out, b);
+        fr_mul(b, b, b);
+        e >>= 1;
+    }
+}
 // all eight 32-bit words decide
 __device__ __forceinline__ bool is_zero(const u32 x[8]) { return (x[0] | x[1] | x[2] | x[3] | x[4] | x[5] | x[6] | x[7]) == 0; }
 __device__ __forceinline__ bool is_zero(const uint4 &a, const uint4 &b) { return ((a.x | a.y | a.z | a.w) | (b.x | b.y | b.z | b.w)) == 0; }

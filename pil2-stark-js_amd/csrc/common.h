@@ -73,6 +73,7 @@ enum ScratchSlot : u32 {
     SCR_BN_SCAN = 21,         // bn_scan.hip: the levels' segment totals and prefixes, then the level-0 prefixes of an inversion in place (layout: bnscan::plan)
     SCR_BN_H1H2 = 22,         // bn_h1h2.hip: hash table, counts / group starts, chunk totals, the missing cell (layout: bnh1h2::plan)
     SCR_BN_POLYMUL = 23,      // bn_polymul.hip: the cell of poly_degree's atomic maximum (poly_fma has no working buffer)
+    SCR_WTNS = 24,            // wtns_exec.hip: the cell of a checked gather's atomic minimum, the first sMap index that names no signal
     N_SCRATCH
 };
 int scratch(ScratchSlot slot, u64 nWords, u64 **out);

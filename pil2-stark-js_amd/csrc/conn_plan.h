@@ -1,5 +1,6 @@
 // Host-only half of the connection polynomials (conn_pols.hip): what the entries refuse, how many digit passes the sort takes, the launch
-// geometry and where every part of the working buffer lies.  No HIP header: it builds with the plain C++ compiler.
+// geometry and where every part of the working buffer lies.  No HIP header: it builds with the plain C++ compiler.  What it shares with
+// wtns_plan.h (workgroup size, the stride kernels' grid, the signal limit, the sMap's narrowing) is smap_plan.h's.
 //
 // The working buffer, every part on 16 bytes, cells = nRows nCols, T = nCols 2^loBits + 2^hiBits table elements:
 //   16                       the first bad cell (8 bytes used)
@@ -10,10 +11,11 @@
 // which stays below 16 cells + cells / 4 + cells / 16384 + 8 elemWords T + 2048 bytes: 16.26 bytes a cell and the two small tables.
 #pragma once
 #include <stdint.h>
+#include "smap_plan.h"
 
 namespace connplan {
 
-constexpr uint32_t THREADS = 256;                    // lanes per workgroup of every kernel of conn_pols.hip
+using smapplan::THREADS;                             // lanes per workgroup of every kernel of conn_pols.hip; init, link, tables and fill take smapplan::blocks
 constexpr uint32_t WAVES = THREADS / 64;
 constexpr uint32_t ROUNDS = 16;                      // 64-cell rounds a wave walks in a sort pass
 constexpr uint32_t TILE = THREADS * ROUNDS;          // cells per workgroup of a sort pass: wave v owns cells [v 64 ROUNDS, (v + 1) 64 ROUNDS) of it
@@ -21,10 +23,9 @@ constexpr uint32_t BINS = 256;                       // 8-bit digits
 static_assert(BINS == THREADS, "lane t of a workgroup owns digit t");
 constexpr uint32_t SCAN_ITEMS = 16;                  // histogram entries per lane of the scan
 constexpr uint32_t SCAN_CHUNK = THREADS * SCAN_ITEMS;
-constexpr uint32_t MAX_BLOCKS = 2048;                // the grid-stride kernels (init, link, tables, fill): 8 workgroups a compute unit
 constexpr uint32_t MAX_COLS = 64;                    // ks' travels as a kernel argument (2 KiB for Fr)
 constexpr uint32_t MAX_N_BITS = 32;
-constexpr uint64_t MAX_CELLS = 1ull << 32;           // cells and signals stay below: 32-bit keys, cells and histogram counts
+constexpr uint64_t MAX_CELLS = 1ull << 32;           // cells stay below, as signals stay below smapplan::MAX_SIGNALS: 32-bit keys, cells and histogram counts
 
 struct Plan {
     uint64_t cells;
@@ -34,10 +35,6 @@ struct Plan {
 };
 
 inline uint64_t r16(uint64_t bytes) { return (bytes + 15) & ~15ull; }
-inline uint32_t blocks(uint64_t items) {
-    const uint64_t want = (items + THREADS - 1) / THREADS;
-    return (uint32_t)(want < MAX_BLOCKS ? (want ? want : 1) : MAX_BLOCKS);
-}
 
 // 0, or a message for PIL2GL_EINVAL
 inline const char *check(uint64_t nRows, uint64_t nCols, uint64_t nW, uint64_t N, uint32_t elemWords) {
@@ -45,7 +42,7 @@ inline const char *check(uint64_t nRows, uint64_t nCols, uint64_t nW, uint64_t N
     if (nCols > MAX_COLS) return "at most 64 columns";
     if (N == 0 || (N & (N - 1)) || N > (1ull << MAX_N_BITS)) return "N must be a power of two, at most 2^32";
     if (nRows > N) return "nRows must not exceed N";
-    if (nW >= MAX_CELLS) return "nW must stay below 2^32";
+    if (nW >= smapplan::MAX_SIGNALS) return "nW must stay below 2^32";
     if (nCols && nRows >= (MAX_CELLS + nCols - 1) / nCols) return "nRows nCols must stay below 2^32";
     return nullptr;
 }

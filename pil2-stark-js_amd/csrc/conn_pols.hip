@@ -26,9 +26,9 @@
 //
 // Safety: sMap values are only compared and sorted, never used as an address.  The scatter's slots follow from the histogram of the same
 // cells and are checked against the cell count all the same; pred entries are checked against it before they index the tables.
+// Shared with wtns_exec.hip: the bad-cell report, the cell walk, the fields as template parameters (smap_cells.cuh); grid, overlap, narrowing (smap_plan.h).
 #include "common.h"
-#include "gl_field.cuh"
-#include "bn_elem.cuh"
+#include "smap_cells.cuh"
 #include "conn_plan.h"
 #include <string.h>
 #include <vector>
@@ -37,18 +37,11 @@ using namespace pil2gl;
 
 namespace {
 
-using connplan::BINS;
-using connplan::MAX_COLS;
-using connplan::ROUNDS;
-using connplan::SCAN_CHUNK;
-using connplan::SCAN_ITEMS;
-using connplan::THREADS;
-using connplan::TILE;
-using connplan::WAVES;
-constexpr u64 NO_BAD = ~0ull;
+using namespace smapcells;
+using namespace smapplan;
+using namespace connplan;
 
-struct GlConsts { u64 w; u64 ks[MAX_COLS]; };
-struct FrConsts { u32 w[8]; u32 ks[MAX_COLS][8]; };
+template <class F> struct Consts { typename F::Elem w, ks[MAX_COLS]; };      // w and ks' as the caller gave them, a kernel argument
 
 // ---- step 1: predecessor links ----
 __global__ void __launch_bounds__(THREADS) conn_init_kernel(const u32 *__restrict__ sMap, u32 n, u32 nW, u32 *__restrict__ keys, u32 *__restrict__ cells,
@@ -60,9 +53,7 @@ __global__ void __launch_bounds__(THREADS) conn_init_kernel(const u32 *__restric
         keys[c] = s;
         cells[c] = (u32)c;
     }
-    if (!firstBad) return;
-    for (int o = 32; o > 0; o >>= 1) { const u64 other = __shfl_xor(best, o, 64); best = other < best ? other : best; }
-    if ((threadIdx.x & 63) == 0 && best != NO_BAD) atomicMin(firstBad, (unsigned long long)best);
+    report_bad(best, firstBad);
 }
 
 __global__ void __launch_bounds__(THREADS) conn_hist_kernel(const u32 *__restrict__ keys, u32 n, u32 shift, u32 *__restrict__ hist, u32 nBlocks) {
@@ -184,46 +175,15 @@ __global__ void __launch_bounds__(THREADS) conn_link_kernel(const u32 *__restric
 }
 
 // ---- step 2: fill ----
-__global__ void __launch_bounds__(THREADS) conn_tables_gl_kernel(GlConsts c, u32 nCols, u32 loBits, u32 hiBits, u64 *__restrict__ hi, u64 *__restrict__ lo) {
+template <class F>
+__global__ void __launch_bounds__(THREADS) conn_tables_kernel(Consts<F> c, u32 nCols, u32 loBits, u32 hiBits, typename F::Mem *__restrict__ hi,
+                                                              typename F::Mem *__restrict__ lo) {
     const u64 nHi = 1ull << hiBits, total = nHi + ((u64)nCols << loBits);
-    const u64 w = gl::canon(c.w);
+    const typename F::Elem w = F::reduce(c.w);
     for (u64 k = (u64)blockIdx.x * THREADS + threadIdx.x; k < total; k += (u64)gridDim.x * THREADS) {
-        if (k < nHi) { hi[k] = gl::pow(w, k << loBits); continue; }
+        if (k < nHi) { F::store(hi, k, F::pow(w, k << loBits)); continue; }
         const u64 e = k - nHi;
-        lo[e] = gl::mul(gl::pow(w, e & ((1ull << loBits) - 1)), c.ks[e >> loBits]);
-    }
-}
-
-// Montgomery in and out
-__device__ __forceinline__ void fr_pow(u32 out[8], const u32 base[8], u64 e) {
-    u32 b[8], one[8] = { 1, 0, 0, 0, 0, 0, 0, 0 }, r2[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) { b[i] = base[i]; r2[i] = bn::r2_limb(i); }
-    bn::fr_mul(out, r2, one);                        // R^2 / R: one
-    while (e) {
-        if (e & 1) bn::fr_mul(out, out, b);
-        bn::fr_mul(b, b, b);
-        e >>= 1;
-    }
-}
-
-__global__ void __launch_bounds__(THREADS) conn_tables_fr_kernel(FrConsts c, u32 nCols, u32 loBits, u32 hiBits, uint4 *__restrict__ hi, uint4 *__restrict__ lo) {
-    const u64 nHi = 1ull << hiBits, total = nHi + ((u64)nCols << loBits);
-    u32 w[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) w[i] = c.w[i];
-    bn::reduce256(w);
-    for (u64 k = (u64)blockIdx.x * THREADS + threadIdx.x; k < total; k += (u64)gridDim.x * THREADS) {
-        u32 x[8];
-        if (k < nHi) { fr_pow(x, w, k << loBits); bn::st_elem(hi + 2 * k, x); continue; }
-        const u64 e = k - nHi;
-        u32 ks[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) ks[i] = c.ks[e >> loBits][i];
-        bn::reduce256(ks);
-        fr_pow(x, w, e & ((1ull << loBits) - 1));
-        bn::fr_mul(x, x, ks);
-        bn::st_elem(lo + 2 * e, x);
+        F::store(lo, e, F::mul(F::pow(w, e & ((1ull << loBits) - 1)), F::reduce(c.ks[e >> loBits])));
     }
 }
 
@@ -235,46 +195,18 @@ __device__ __forceinline__ u32 source_cell(const u32 *__restrict__ pred, u64 r, 
     return from < n ? from : (u32)c;
 }
 
-__global__ void __launch_bounds__(THREADS) conn_fill_gl_kernel(const u32 *__restrict__ pred, u64 nRows, u32 nCols, u32 n, u64 N, u32 loBits,
-                                                               const u64 *__restrict__ hi, const u64 *__restrict__ lo, u64 *__restrict__ dst,
-                                                               u64 dstStride, u64 dstOffset) {
-    const u64 tid = (u64)blockIdx.x * THREADS + threadIdx.x, stride = (u64)gridDim.x * THREADS;
-    const u64 stepRows = stride / nCols, stepCols = stride % nCols;
-    u64 r = tid / nCols, j = tid % nCols;
-    while (r < N) {
-        u64 pi = r, pj = j;
-        if (r < nRows) { const u32 from = source_cell(pred, r, j, nRows, nCols, n); pi = from / nCols; pj = from - pi * nCols; }
-        dst[r * dstStride + dstOffset + j] = gl::mul(lo[(pj << loBits) + (pi & ((1ull << loBits) - 1))], hi[pi >> loBits]);
-        r += stepRows; j += stepCols;
-        if (j >= nCols) { j -= nCols; r++; }
-    }
-}
-
-__global__ void __launch_bounds__(THREADS) conn_fill_fr_kernel(const u32 *__restrict__ pred, u64 nRows, u32 nCols, u32 n, u64 N, u32 loBits,
-                                                               const uint4 *__restrict__ hi, const uint4 *__restrict__ lo, uint4 *__restrict__ dst,
-                                                               u64 dstStride, u64 dstOffset) {
-    const u64 tid = (u64)blockIdx.x * THREADS + threadIdx.x, stride = (u64)gridDim.x * THREADS;
-    const u64 stepRows = stride / nCols, stepCols = stride % nCols;
-    u64 r = tid / nCols, j = tid % nCols;
-    while (r < N) {
-        u64 pi = r, pj = j;
-        if (r < nRows) { const u32 from = source_cell(pred, r, j, nRows, nCols, n); pi = from / nCols; pj = from - pi * nCols; }
-        u32 x[8], y[8];
-        bn::ld_elem(lo + 2 * ((pj << loBits) + (pi & ((1ull << loBits) - 1))), x);
-        bn::ld_elem(hi + 2 * (pi >> loBits), y);
-        bn::fr_mul(x, x, y);
-        bn::st_elem(dst + 2 * (r * dstStride + dstOffset + j), x);
-        r += stepRows; j += stepCols;
-        if (j >= nCols) { j -= nCols; r++; }
+template <class F>
+__global__ void __launch_bounds__(THREADS) conn_fill_kernel(const u32 *__restrict__ pred, u64 nRows, u32 nCols, u32 n, u64 N, u32 loBits,
+                                                            const typename F::Mem *__restrict__ hi, const typename F::Mem *__restrict__ lo,
+                                                            typename F::Mem *__restrict__ dst, u64 dstStride, u64 dstOffset) {
+    for (CellWalk c((u64)blockIdx.x * THREADS + threadIdx.x, (u64)gridDim.x * THREADS, nCols); c.r < N; c.next()) {
+        u64 pi = c.r, pj = c.j;
+        if (c.r < nRows) { const u32 from = source_cell(pred, c.r, c.j, nRows, nCols, n); pi = from / nCols; pj = from - pi * nCols; }
+        F::store(dst, c.r * dstStride + dstOffset + c.j, F::mul(F::load(lo, (pj << loBits) + (pi & ((1ull << loBits) - 1))), F::load(hi, pi >> loBits)));
     }
 }
 
 // ---- host side ----
-bool meets(const void *a, u64 aBytes, const void *b, u64 bBytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return aBytes && bBytes && x < y + bBytes && y < x + aBytes;
-}
-
 // every launch of a call, on st; the arguments have passed the checks.  ks1 and w are read before this returns (they travel as kernel arguments).
 int launch(const uint32_t *sMap, u64 nRows, u64 nCols, u64 nW, u64 N, const u64 *w, const u64 *ks1, u64 *dst, u64 dstStride, u64 dstOffset,
            void *scratch, const connplan::Plan &p, u32 words, u64 *hostFirstBad, hipStream_t st) {
@@ -286,7 +218,7 @@ int launch(const uint32_t *sMap, u64 nRows, u64 nCols, u64 nW, u64 N, const u64 
     if (hostFirstBad) HIP_TRY(hipMemsetAsync(bad, 0xFF, 8, st));
     const u32 *pred = keys[1];
     if (n) {
-        conn_init_kernel<<<connplan::blocks(n), THREADS, 0, st>>>(sMap, n, (u32)nW, keys[0], cells[0], hostFirstBad ? bad : nullptr);
+        conn_init_kernel<<<blocks(n), THREADS, 0, st>>>(sMap, n, (u32)nW, keys[0], cells[0], hostFirstBad ? bad : nullptr);
         KERNEL_CHECK();
         u32 in = 0;
         for (u32 pass = 0; pass < p.passes; pass++, in ^= 1) {
@@ -302,29 +234,24 @@ int launch(const uint32_t *sMap, u64 nRows, u64 nCols, u64 nW, u64 N, const u64 
             conn_scatter_kernel<<<p.sortBlocks, THREADS, 0, st>>>(keys[in], cells[in], n, shift, hist, p.sortBlocks, keys[in ^ 1], cells[in ^ 1]);
             KERNEL_CHECK();
         }
-        conn_link_kernel<<<connplan::blocks(n), THREADS, 0, st>>>(keys[in], cells[in], n, keys[in ^ 1]);
+        conn_link_kernel<<<blocks(n), THREADS, 0, st>>>(keys[in], cells[in], n, keys[in ^ 1]);
         KERNEL_CHECK();
         pred = keys[in ^ 1];
     }
-    const u32 tableBlocks = connplan::blocks(p.tableElems), fillBlocks = connplan::blocks(N * nCols);
-    if (words == 1) {
-        GlConsts c{};
-        c.w = w[0];
-        for (u64 j = 0; j < nCols; j++) c.ks[j] = ks1[j];
-        u64 *hi = (u64 *)(s + p.offHi), *lo = (u64 *)(s + p.offLo);
-        conn_tables_gl_kernel<<<tableBlocks, THREADS, 0, st>>>(c, (u32)nCols, p.loBits, p.hiBits, hi, lo);
+    auto fillOf = [&](auto field) -> int {             // tables and fill in one field
+        typedef decltype(field) F;
+        typedef typename F::Mem Mem;
+        Consts<F> c{};
+        memcpy(&c.w, w, sizeof c.w);
+        memcpy(c.ks, ks1, sizeof c.w * nCols);
+        Mem *hi = (Mem *)(s + p.offHi), *lo = (Mem *)(s + p.offLo);
+        conn_tables_kernel<F><<<blocks(p.tableElems), THREADS, 0, st>>>(c, (u32)nCols, p.loBits, p.hiBits, hi, lo);
         KERNEL_CHECK();
-        conn_fill_gl_kernel<<<fillBlocks, THREADS, 0, st>>>(pred, nRows, (u32)nCols, n, N, p.loBits, hi, lo, dst, dstStride, dstOffset);
-    } else {
-        FrConsts c{};
-        memcpy(c.w, w, 32);
-        memcpy(c.ks, ks1, 32 * nCols);
-        uint4 *hi = (uint4 *)(s + p.offHi), *lo = (uint4 *)(s + p.offLo);
-        conn_tables_fr_kernel<<<tableBlocks, THREADS, 0, st>>>(c, (u32)nCols, p.loBits, p.hiBits, hi, lo);
+        conn_fill_kernel<F><<<blocks(N * nCols), THREADS, 0, st>>>(pred, nRows, (u32)nCols, n, N, p.loBits, hi, lo, (Mem *)dst, dstStride, dstOffset);
         KERNEL_CHECK();
-        conn_fill_fr_kernel<<<fillBlocks, THREADS, 0, st>>>(pred, nRows, (u32)nCols, n, N, p.loBits, hi, lo, (uint4 *)dst, dstStride, dstOffset);
-    }
-    KERNEL_CHECK();
+        return PIL2GL_OK;
+    };
+    P2_TRY(words == 1 ? fillOf(GlField{}) : fillOf(FrField{}));
     if (hostFirstBad) {
         HIP_TRY(hipMemcpyAsync(hostFirstBad, bad, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -359,16 +286,12 @@ int conn_host(const void *hostSMap, int layout, u64 nRows, u64 nCols, u64 nW, u6
     if (!nCols) return PIL2GL_OK;
     const connplan::Plan p = connplan::plan(nRows, nCols, nW, N, words);
     if (!hostDst || !w || !ks1 || (p.cells && !hostSMap)) return fail(PIL2GL_EINVAL, "null buffer");
-    const u64 mapWords = (p.cells + 1) / 2 + ((p.cells + 1) / 2 & 1);        // staged parts start on 16 bytes
-    std::vector<u64> packed(mapWords, 0);
-    uint32_t *sMap = (uint32_t *)packed.data();
-    for (u64 i = 0; i < nRows; i++)
-        for (u64 j = 0; j < nCols; j++) {
-            const u64 v = layout == PIL2GL_CONN_SMAP_ROWS_U64 ? ((const u64 *)hostSMap)[i * nCols + j] : ((const uint32_t *)hostSMap)[j * N + i];
-            if (v >= nW) return fail(PIL2GL_EINVAL, "sMap cell %llu (row %llu, column %llu) = %llu names no signal (nW = %llu)", (unsigned long long)(i * nCols + j),
-                                     (unsigned long long)i, (unsigned long long)j, (unsigned long long)v, (unsigned long long)nW);
-            sMap[i * nCols + j] = (uint32_t)v;
-        }
+    const u64 mapWords = smapplan::packed_words(p.cells);
+    std::vector<u64> packed(mapWords);
+    u64 badCell, v;
+    if (!smapplan::narrow(hostSMap, layout == PIL2GL_CONN_SMAP_COLS_U32, N, nRows, nCols, nW, packed.data(), &badCell, &v))
+        return fail(PIL2GL_EINVAL, "sMap cell %llu (row %llu, column %llu) = %llu names no signal (nW = %llu)", (unsigned long long)badCell,
+                    (unsigned long long)(badCell / nCols), (unsigned long long)(badCell % nCols), (unsigned long long)v, (unsigned long long)nW);
     const u64 outWords = N * nCols * words;
     if (meets(hostDst, outWords * 8, hostSMap, layout == PIL2GL_CONN_SMAP_ROWS_U64 ? 8 * p.cells : 4 * N * nCols)) return fail(PIL2GL_EINVAL, "dst overlaps sMap");
     Stage s(mapWords + p.bytes / 8 + outWords);

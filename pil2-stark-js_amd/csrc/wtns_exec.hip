@@ -14,11 +14,11 @@
 // happens per gathered cell (fr_mul by R^2), which costs a product per cell and saves a pass over w and a second copy of it.
 //
 // Safety: no index read from a table is used unchecked.  An addition whose a or b is >= nW, or whose dst is outside [nWitness, nW), writes
-// nothing.  A gather index >= nW writes zero and lowers the bad cell to its flat index (i nCols + j) by an atomic minimum.  The level
-// table is a host array and is checked before the first launch.
+// nothing.  A gather index >= nW writes zero and lowers the bad cell (scratch slot SCR_WTNS) to its flat index (i nCols + j) by an atomic
+// minimum.  The level table is a host array and is checked before the first launch.  Shared with conn_pols.hip: that report, the cell walk
+// and the fields as template parameters (smap_cells.cuh); the grid, the overlap test and the sMap's narrowing (smap_plan.h).
 #include "common.h"
-#include "gl_field.cuh"
-#include "bn_elem.cuh"
+#include "smap_cells.cuh"
 #include "wtns_plan.h"
 #include <string.h>
 #include <vector>
@@ -27,65 +27,39 @@ using namespace pil2gl;
 
 namespace {
 
-using wtnsplan::THREADS;
-constexpr u64 NO_BAD = ~0ull;
+using namespace smapcells;
+using namespace smapplan;
 
 // ---- additions ----
-__global__ void __launch_bounds__(THREADS) wtns_adds_gl_kernel(u64 *w, u32 nWitness, u32 nW, const uint4 *__restrict__ adds,
-                                                               const ulonglong2 *__restrict__ coefs, u32 count) {
-    for (u64 k = (u64)blockIdx.x * THREADS + threadIdx.x; k < count; k += (u64)gridDim.x * THREADS) {      // 64 bits: a level near 2^32 records must not wrap
-        const uint4 r = adds[k];
-        const ulonglong2 c = coefs[k];
-        if (r.x >= nW || r.y >= nW || r.z < nWitness || r.z >= nW) continue;
-        w[r.z] = gl::add(gl::mul(w[r.x], c.x), gl::mul(w[r.y], c.y));
-    }
-}
-
-// w: 2 halves an element; coefs: 4 halves an addition (ca, cb)
-__global__ void __launch_bounds__(THREADS) wtns_adds_fr_kernel(uint4 *w, u32 nWitness, u32 nW, const uint4 *__restrict__ adds,
-                                                               const uint4 *__restrict__ coefs, u32 count) {
+// coefs: two elements an addition (ca, cb), in the records' order.  w times a coefficient: for Fr normal x Montgomery = the normal-form
+// product, canonical
+template <class F>
+__global__ void __launch_bounds__(THREADS) wtns_adds_kernel(typename F::Mem *w, u32 nWitness, u32 nW, const uint4 *__restrict__ adds,
+                                                            const typename F::Mem *__restrict__ coefs, u32 count) {
     for (u64 k = (u64)blockIdx.x * THREADS + threadIdx.x; k < count; k += (u64)gridDim.x * THREADS) {      // 64 bits: a level near 2^32 records must not wrap
         const uint4 r = adds[k];
         if (r.x >= nW || r.y >= nW || r.z < nWitness || r.z >= nW) continue;
-        u32 x[8], y[8], c[8];
-        bn::ld_elem(w + 2 * (size_t)r.x, x);
-        bn::ld_elem(coefs + 4 * (size_t)k, c);
-        bn::reduce256(c);
-        bn::fr_mul(x, x, c);                         // normal x Montgomery = the normal-form product, canonical
-        bn::ld_elem(w + 2 * (size_t)r.y, y);
-        bn::ld_elem(coefs + 4 * (size_t)k + 2, c);
-        bn::reduce256(c);
-        bn::fr_mul(y, y, c);
-        bn::fr_add(x, y);
-        bn::st_elem(w + 2 * (size_t)r.z, x);
+        const typename F::Elem x = F::mul(F::load(w, r.x), F::reduce(F::load(coefs, 2 * k)));
+        const typename F::Elem y = F::mul(F::load(w, r.y), F::reduce(F::load(coefs, 2 * k + 1)));
+        F::store(w, r.z, F::add(x, y));
     }
 }
 
 // ---- gather ----
-// the wave's smallest bad index, one atomic per wave that saw one; every lane of the wave arrives here
-__device__ __forceinline__ void report_bad(u64 best, unsigned long long *firstBad) {
-    if (!firstBad) return;
-    for (int o = 32; o > 0; o >>= 1) { const u64 other = __shfl_xor(best, o, 64); best = other < best ? other : best; }
-    if ((threadIdx.x & 63) == 0 && best != NO_BAD) atomicMin(firstBad, (unsigned long long)best);
-}
-
-// (row, column) of a lane's first cell comes from one division; the grid stride then advances it by a precomputed (rows, columns) step
+// Two kernels on purpose: the Fr one is another algorithm (two lanes a cell, the halves exchanged within the pair), not the Goldilocks one
+// over another element.  Both walk the dstCols-wide output by CellWalk and report through report_bad.
 __global__ void __launch_bounds__(THREADS) wtns_gather_gl_kernel(const u64 *__restrict__ w, u32 nW, const u32 *__restrict__ sMap, u64 nRows,
                                                                  u64 nCols, u64 *__restrict__ dst, u64 dstCols, unsigned long long *firstBad) {
-    const u64 tid = (u64)blockIdx.x * THREADS + threadIdx.x, stride = (u64)gridDim.x * THREADS;
-    const u64 stepRows = stride / dstCols, stepCols = stride % dstCols;
-    u64 r = tid / dstCols, j = tid % dstCols, best = NO_BAD;
-    while (r < nRows) {
+    u64 best = NO_BAD;
+    for (CellWalk c((u64)blockIdx.x * THREADS + threadIdx.x, (u64)gridDim.x * THREADS, dstCols); c.r < nRows; c.next()) {
         u64 v = 0;
-        if (j < nCols) {
-            const u64 flat = r * nCols + j;
+        if (c.j < nCols) {
+            const u64 flat = c.r * nCols + c.j;
             const u32 s = sMap[flat];
             if (s >= nW) best = flat < best ? flat : best;
             else if (s) v = gl::canon(w[s]);
         }
-        dst[r * dstCols + j] = v;
-        r += stepRows; j += stepCols;
-        if (j >= dstCols) { j -= dstCols; r++; }
+        dst[c.r * dstCols + c.j] = v;
     }
     report_bad(best, firstBad);
 }
@@ -95,14 +69,12 @@ __global__ void __launch_bounds__(THREADS) wtns_gather_fr_kernel(const uint4 *__
                                                                  u64 nCols, uint4 *__restrict__ dst, u64 dstCols, int toMontgomery,
                                                                  unsigned long long *firstBad) {
     const u32 h = threadIdx.x & 1;
-    const u64 cid = ((u64)blockIdx.x * THREADS + threadIdx.x) >> 1, stride = (u64)gridDim.x * (THREADS / 2);
-    const u64 stepRows = stride / dstCols, stepCols = stride % dstCols;
-    u64 r = cid / dstCols, j = cid % dstCols, best = NO_BAD;
-    while (r < nRows) {
+    u64 best = NO_BAD;
+    for (CellWalk c(((u64)blockIdx.x * THREADS + threadIdx.x) >> 1, (u64)gridDim.x * (THREADS / 2), dstCols); c.r < nRows; c.next()) {
         uint4 mine = make_uint4(0, 0, 0, 0);
         bool live = false;                           // the same for both lanes of a cell
-        if (j < nCols) {
-            const u64 flat = r * nCols + j;
+        if (c.j < nCols) {
+            const u64 flat = c.r * nCols + c.j;
             const u32 s = sMap[flat];
             if (s >= nW) best = flat < best ? flat : best;
             else if (s) { mine = w[2 * (size_t)s + h]; live = true; }
@@ -116,27 +88,19 @@ __global__ void __launch_bounds__(THREADS) wtns_gather_fr_kernel(const uint4 *__
             bn::unpack(h ? other : mine, h ? mine : other, x);
             if (toMontgomery) {
                 u32 r2[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) r2[i] = bn::r2_limb(i);
+                bn::ld_r2(r2);
                 bn::fr_mul(x, x, r2);
             } else {
                 bn::reduce256(x);
             }
             out = h ? make_uint4(x[4], x[5], x[6], x[7]) : make_uint4(x[0], x[1], x[2], x[3]);
         }
-        dst[2 * (r * dstCols + j) + h] = out;
-        r += stepRows; j += stepCols;
-        if (j >= dstCols) { j -= dstCols; r++; }
+        dst[2 * (c.r * dstCols + c.j) + h] = out;
     }
     report_bad(best, firstBad);
 }
 
 // ---- host side ----
-bool meets(const void *a, u64 aBytes, const void *b, u64 bBytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return aBytes && bBytes && x < y + bBytes && y < x + aBytes;
-}
-
 // everything the additions refuse, before any device call; words = 1 (Goldilocks) or 4 (Fr) 64-bit words an element
 int check_adds(const void *w, u64 nWitness, const void *adds, const void *coefs, u64 nAdds, const uint32_t *levelStart, u32 nLevels, u32 words) {
     if (const char *m = wtnsplan::check_sizes(nWitness, nAdds)) return fail(PIL2GL_EINVAL, "%s", m);
@@ -156,17 +120,18 @@ int check_adds(const void *w, u64 nWitness, const void *adds, const void *coefs,
 int launch_adds(u64 *w, u64 nWitness, const uint32_t *adds, const u64 *coefs, u64 nAdds, const uint32_t *levelStart, u32 nLevels, u32 words,
                 hipStream_t st) {
     const u32 nW = (u32)(nWitness + nAdds);
-    for (u32 l = 0; l < nLevels; l++) {
-        const u32 first = levelStart[l], count = levelStart[l + 1] - first;
-        if (!count) continue;
-        const uint4 *recs = (const uint4 *)adds + first;
-        if (words == 1)
-            wtns_adds_gl_kernel<<<wtnsplan::blocks(count), THREADS, 0, st>>>(w, (u32)nWitness, nW, recs, (const ulonglong2 *)coefs + first, count);
-        else
-            wtns_adds_fr_kernel<<<wtnsplan::blocks(count), THREADS, 0, st>>>((uint4 *)w, (u32)nWitness, nW, recs, (const uint4 *)coefs + 4 * (size_t)first, count);
-        KERNEL_CHECK();
-    }
-    return PIL2GL_OK;
+    auto levelsOf = [&](auto field) -> int {           // every level's launch in one field
+        typedef decltype(field) F;
+        for (u32 l = 0; l < nLevels; l++) {
+            const u32 first = levelStart[l], count = levelStart[l + 1] - first;
+            if (!count) continue;
+            wtns_adds_kernel<F><<<blocks(count), THREADS, 0, st>>>((typename F::Mem *)w, (u32)nWitness, nW, (const uint4 *)adds + first,
+                                                                   (const typename F::Mem *)coefs + 2 * (size_t)first, count);
+            KERNEL_CHECK();
+        }
+        return PIL2GL_OK;
+    };
+    return words == 1 ? levelsOf(GlField{}) : levelsOf(FrField{});
 }
 
 // everything the gather refuses, before any device call; *nothing: no cell to write
@@ -187,22 +152,18 @@ int check_gather(const void *w, u64 nW, const void *sMap, u64 nRows, u64 nCols, 
 
 int launch_gather(const u64 *w, u64 nW, const uint32_t *sMap, u64 nRows, u64 nCols, u64 *dst, u64 dstCols, u32 words, int toMontgomery,
                   u64 *hostFirstBad, hipStream_t st) {
-    // The bad cell lives for the call: a checked gather blocks for its answer anyway.  NOT a pattern to copy: hipFree synchronises the whole
-    // device, tolerable only because the check is a diagnostic.  The intended home is a scratch slot of its own (SCR_WTNS after
-    // SCR_BN_POLYMUL in common.h, one 8-byte cell kept across calls), to be taken once the shared header is open to this unit.
-    struct Cell { unsigned long long *p = nullptr; ~Cell() { if (p) (void)hipFree(p); } } cell;
-    unsigned long long *bad = nullptr;
+    // the bad cell of a checked gather: SCR_WTNS, kept across calls and reset to NO_BAD on this call's stream before every launch
+    u64 *cell = nullptr;
     if (hostFirstBad) {
-        HIP_TRY(hipMalloc((void **)&cell.p, 8));
-        bad = cell.p;
-        HIP_TRY(hipMemsetAsync(bad, 0xFF, 8, st));
+        P2_TRY(scratch(SCR_WTNS, 2, &cell));
+        HIP_TRY(hipMemsetAsync(cell, 0xFF, 8, st));
     }
+    unsigned long long *bad = (unsigned long long *)cell;
     const u64 cells = nRows * dstCols;
     if (words == 1)
-        wtns_gather_gl_kernel<<<wtnsplan::blocks(cells), THREADS, 0, st>>>(w, (u32)nW, sMap, nRows, nCols, dst, dstCols, bad);
+        wtns_gather_gl_kernel<<<blocks(cells), THREADS, 0, st>>>(w, (u32)nW, sMap, nRows, nCols, dst, dstCols, bad);
     else
-        wtns_gather_fr_kernel<<<wtnsplan::blocks(2 * cells), THREADS, 0, st>>>((const uint4 *)w, (u32)nW, sMap, nRows, nCols, (uint4 *)dst, dstCols,
-                                                                              toMontgomery, bad);
+        wtns_gather_fr_kernel<<<blocks(2 * cells), THREADS, 0, st>>>((const uint4 *)w, (u32)nW, sMap, nRows, nCols, (uint4 *)dst, dstCols, toMontgomery, bad);
     KERNEL_CHECK();
     if (hostFirstBad) {
         HIP_TRY(hipMemcpyAsync(hostFirstBad, bad, 8, hipMemcpyDeviceToHost, st));
@@ -228,8 +189,6 @@ int adds_dev(u64 *w, u64 nWitness, const uint32_t *adds, const u64 *coefs, u64 n
     return launch_adds(w, nWitness, adds, coefs, nAdds, levelStart, nLevels, words, as_stream(stream));
 }
 
-u64 even(u64 nWords) { return (nWords + 1) & ~1ull; }           // staged parts start on 16 bytes
-
 // plan, stage, compute, copy out.  idx / coef strides as the files hold the tables: Goldilocks 4 and 4, Fr 2 and 8.
 int exec_host(const u64 *hostW, u64 nWitness, const u64 *idx, u64 idxStride, const u64 *coef, u64 coefStride, u64 nAdds, const u64 *sMap64,
               u64 nRows, u64 nCols, u64 *hostDst, u32 words, int toMontgomery) {
@@ -244,26 +203,24 @@ int exec_host(const u64 *hostW, u64 nWitness, const u64 *idx, u64 idxStride, con
     if (!wtnsplan::levels(idx, idxStride, nAdds, nWitness, level, &nLevels, err, sizeof err)) return fail(PIL2GL_EINVAL, "%s", err);
     levelStart.resize(nLevels + 1);
     wtnsplan::emit(idx, idxStride, nAdds, nWitness, level, nLevels, coef, coefStride, words, recs.data(), coefs.data(), levelStart.data());
-    std::vector<uint32_t> sMap(cells);
-    for (u64 k = 0; k < cells; k++) {
-        if (sMap64[k] >= nW) return fail(PIL2GL_EINVAL, "sMap[%llu] = %llu names no signal (nWitness + nAdds = %llu)", (unsigned long long)k,
-                                         (unsigned long long)sMap64[k], (unsigned long long)nW);
-        sMap[k] = (uint32_t)sMap64[k];
-    }
+    const u64 recWords = pad16(2 * nAdds), mapWords = smapplan::packed_words(cells);
+    std::vector<u64> packed(recWords + mapWords);                 // the 32-bit tables travel as whole words
+    if (nAdds) memcpy(packed.data(), recs.data(), 16 * nAdds);
+    u64 badCell, badValue;
+    if (!smapplan::narrow(sMap64, false, 0, nRows, nCols, nW, packed.data() + recWords, &badCell, &badValue))
+        return fail(PIL2GL_EINVAL, "sMap[%llu] = %llu names no signal (nWitness + nAdds = %llu)", (unsigned long long)badCell,
+                    (unsigned long long)badValue, (unsigned long long)nW);
     const u64 dBytes = cells * 8 * words;
     if (meets(hostDst, dBytes, hostW, nWitness * 8 * words) || meets(hostDst, dBytes, sMap64, cells * 8) ||
         meets(hostDst, dBytes, idx, nAdds ? ((nAdds - 1) * idxStride + 2) * 8 : 0) ||
         meets(hostDst, dBytes, coef, nAdds ? ((nAdds - 1) * coefStride + 2 * words) * 8 : 0))
         return fail(PIL2GL_EINVAL, "dst overlaps w or a table");
     if (!cells) return PIL2GL_OK;
-    const u64 wWords = even(nW * words), recWords = even(2 * nAdds), coefWords = even(coefs.size()), mapWords = even((cells + 1) / 2);
+    const u64 wWords = pad16(nW * words), coefWords = pad16(coefs.size());
     Stage s(wWords + recWords + coefWords + mapWords + cells * words);
     P2_TRY(s.rc());
     u64 *dW = s.take(wWords);
     if (dW && nWitness) HIP_TRY(hipMemcpy(dW, hostW, nWitness * 8 * words, hipMemcpyHostToDevice));
-    std::vector<u64> packed(recWords + mapWords);                 // the 32-bit tables travel as whole words
-    if (nAdds) memcpy(packed.data(), recs.data(), 16 * nAdds);
-    memcpy(packed.data() + recWords, sMap.data(), 4 * cells);
     const u64 *dTab = s.put(packed.data(), packed.size());
     const u64 *dCoef = nAdds ? s.put(coefs.data(), coefWords) : nullptr;
     u64 *dDst = s.take(cells * words);
@@ -309,7 +266,7 @@ int pil2gl_debug_wtns_plan(const uint64_t *hostAddIdx, uint64_t idxStride, uint6
     for (uint64_t i = 0; i < nAdds; i++) width[level[i]]++;
     uint32_t widest = 0;
     for (uint32_t l = 0; l < n; l++) { if (width[l] > widest) widest = width[l]; if (outWidths && l < widthCap) outWidths[l] = width[l]; }
-    outInfo[0] = n; outInfo[1] = n; outInfo[2] = widest; outInfo[3] = THREADS; outInfo[4] = n ? wtnsplan::blocks(widest) : 0;
+    outInfo[0] = n; outInfo[1] = n; outInfo[2] = widest; outInfo[3] = THREADS; outInfo[4] = n ? blocks(widest) : 0;
     return PIL2GL_OK;
 }
 

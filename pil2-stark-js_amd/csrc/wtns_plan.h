@@ -1,6 +1,6 @@
 // Host-only half of the recursion witness expansion (wtns_exec.hip): what the entries refuse about the additions of an `exec` file, and
 // the order in which the device runs them.  No HIP header: it builds with the plain C++ compiler (tests/wtns_plan_dump.cpp runs it under
-// the sanitizers).
+// the sanitizers).  The launch grid, the signal limit and the sMap's narrowing are smap_plan.h's, shared with conn_plan.h.
 //
 // The reference runs the additions serially, w.push(w[a] ca + w[b] cb) (src/compressor/compressor_exec.js:17-19,
 // src/final/main_final_exec.js:55-57); a_i, b_i may name an earlier addition.  On the device every addition whose operands are ready
@@ -22,18 +22,12 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <vector>
+#include "smap_plan.h"
 
 namespace wtnsplan {
 
-constexpr uint32_t THREADS = 256;                    // lanes per workgroup of every kernel of wtns_exec.hip
-constexpr uint32_t MAX_BLOCKS = 2048;                // a grid sized to the chip (8 workgroups a compute unit); the stride loops take the rest
-constexpr uint64_t MAX_SIGNALS = 1ull << 32;         // nWitness + nAdds stays below
-
-// workgroups of a launch over `items` lanes' worth of work
-inline uint32_t blocks(uint64_t items) {
-    const uint64_t want = (items + THREADS - 1) / THREADS;
-    return (uint32_t)(want < MAX_BLOCKS ? (want ? want : 1) : MAX_BLOCKS);
-}
+using smapplan::MAX_SIGNALS;
+using smapplan::blocks;                              // the additions' grid, under the name this planner's callers know
 
 // 0, or a message for PIL2GL_EINVAL
 inline const char *check_sizes(uint64_t nWitness, uint64_t nAdds) {

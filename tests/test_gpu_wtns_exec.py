@@ -263,6 +263,57 @@ def test_fr_level_of_70000_additions_and_one_over_its_far_end(wt):
     assert ref.fr_ints(host(out).reshape(-1, 4)) == [full[s] % R for s in s_map]
 
 
+@pytest.mark.parametrize("field", ["gl", "bn128"])
+def test_checked_gathers_reset_their_cell_and_share_none_with_conn_pols(wt, field):
+    """The bad cell of a checked gather is a scratch slot kept across calls, so every checked call must reset it on its own stream: the
+    reduction is a minimum, and a stale 5 would come back from the call whose only bad cell is 70.  One prepare() of 2 rows x 65 columns:
+    130 cells are more than a wave, and for Fr 260 lanes are more than a workgroup.  Between the gathers a checked conn_pols_dev over the
+    same resident tables reports its own cell: its cell lies in its working buffer, not in the slot.  conn_pols takes at most 64 columns,
+    so it reads prepare()'s tables as 65 rows x 2 columns -- the flat cells, and with them the reported index, are the same."""
+    import conn_pols_ref as cref
+    n_rows, n_cols = 2, 65
+    q = P if field == "gl" else R
+    w, adds = gl_case(31, 6) if field == "gl" else fr_case(31, 6)
+    n_w = len(w) + len(adds)
+    s_map = s_map_for(ref.rng(31), n_w, n_rows, n_cols)
+    if field == "gl":
+        prep = wt.prepare(gl_exec(w, adds, s_map, n_rows, n_cols))
+        w_dev = dev(np.array(w + [0] * len(adds), np.uint64))
+        full = ref.additions(w, adds, P)
+        words = lambda rows: np.array(rows, np.uint64)                                             # noqa: E731
+    else:
+        prep = wt.prepare(fr_exec(w, adds, s_map, n_rows, n_cols))
+        w_dev = dev(np.concatenate([ref.fr_words(w), np.zeros((len(adds), 4), np.uint64)]))
+        full = ref.additions(w, fr_values(adds), R)
+        words = lambda rows: ref.fr_words([v for r in rows for v in r]).reshape(n_rows, n_cols, 4)  # noqa: E731
+    wt.adds_dev(prep, w_dev)
+
+    def gather(bad_cells, first):
+        table = list(s_map)
+        for c, v in bad_cells:
+            table[c] = v
+        out, got = wt.gather_dev(prep, w_dev, montgomery=False, check=True, s_map=dev(np.array(table, np.uint32).view(np.uint64)))
+        assert got == first
+        zeroed = [0 if s >= n_w else s for s in table]
+        assert (host(out) == words(ref.gather(full, zeroed, n_rows, n_cols, n_cols, q))).all()
+
+    gather([(5, n_w), (99, (1 << 32) - 1)], 5)
+    gather([], None)
+    table = list(s_map)
+    table[9] = n_w + 1
+    as_rows = dict(prep, nRows=n_cols, nCols=n_rows)                                               # 65 x 2 over the same device tables
+    root, ks = cref.root(q, 7), cref.get_ks(q, 1)
+    out, got = wt.conn_pols_dev(as_rows, 128, *cref.consts(root, ks, q), check=True, s_map=dev(np.array(table, np.uint32).view(np.uint64)))
+    assert got == 9
+    table[9] = 0
+    assert np.array_equal(host(out), cref.words(cref.conn_pols(table, n_cols, n_rows, 128, root, ks, q), q))
+    gather([(70, (1 << 32) - 1)], 70)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(torch.cuda.Stream()):
+        gather([(70, n_w)], 70)
+    torch.cuda.synchronize()
+
+
 def test_fr_expanded_trace_feeds_ifft_unchanged(wt):
     from pil2gl import bn128
     w, adds = fr_case(11)

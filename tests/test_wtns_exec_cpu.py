@@ -1,6 +1,7 @@
 """The recursion witness expansion without a device: the checker (tests/wtns_exec_ref.py) against a second formulation of itself, the file
 readers of pil2gl.wtns against the checker's writers, the planner through the library's host-only call, the ABI surface (every refusal
-before any device call, ENODEV otherwise), and the planner header under the sanitizers in a program of its own.
+before any device call, ENODEV otherwise), and the planner header and the header it shares with the connection polynomials under the
+sanitizers, each in a program of its own.
 The reference tree ships no .exec or .wtns and its setups need pilcom / circom_runtime, which are not available, so no reference-written
 fixture exists; the writers restate writeExecFile (compressor/exec_helpers.js:26-47, final/exec_helpers.js:93-187)."""
 import ctypes as C
@@ -240,7 +241,52 @@ def test_compute_entries_refuse_before_any_device_call(lib):
             wtns.exec_gl(w, {"field": "gl", "adds": tab, "nAdds": 2, "nSMap": 2, "nCols": 2, "sMap": s_map})
 
 
-# ---- the planner header under the sanitizers, in a program of its own ----
+# ---- the planner headers under the sanitizers, each in a program of its own ----
+def test_shared_smap_header_under_the_sanitizers(tmp_path):
+    """csrc/smap_plan.h: the narrowing of a host sMap in both layouts against a transposition made here, the overlap test, the grid"""
+    exe = str(tmp_path / "smap_plan_dump")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "smap_plan_dump.cpp"), "-o", exe])
+    rng = ref.rng(900)
+    narrow = []                                                               # (colsU32, colLen, nRows, nCols, nW, values in memory order, rows)
+    for n_rows, n_cols in ((4, 3), (5, 3), (1, 1), (7, 6), (0, 3), (3, 0)):   # 15 and 1 cells are odd counts: a padding half-word
+        n_w = 1 << 20
+        rows = [[rng.randrange(n_w) for _ in range(n_cols)] for _ in range(n_rows)]
+        narrow.append((0, 0, n_rows, n_cols, n_w, [v for r in rows for v in r], rows))
+        col_len = n_rows + 3                                                  # the setups' columns are N long, rows past nRows are not read
+        cols = [[rows[i][j] if i < n_rows else 0xFFFFFFFF for i in range(col_len)] for j in range(n_cols)]
+        narrow.append((1, col_len, n_rows, n_cols, n_w, [v for c in cols for v in c], rows))
+    refused = [((0, 0, 2, 3, 9, [1, 2, 3, 4, 9, 0]), (4, 9)),                 # a value equal to nW, at its position; cell 5 is never read
+               ((0, 0, 2, 2, 3, [1, 2, (1 << 32) + 1, 0]), (2, (1 << 32) + 1)),  # the 64-bit value decides: its low half, 1, names a signal
+               ((1, 2, 2, 2, 9, [1, 2, 9, 4]), (1, 9)),                       # columns of u32: memory position 2 is row 0, column 1 = cell 1
+               ((0, 0, 1, 2, 1, [0, 1]), (1, 1))]
+    accepted = (0, 0, 1, 3, 9, [8, 0, 8], [[8, 0, 8]])                        # nW - 1
+    meets = [((0, 0, 0, 8), 0), ((0, 8, 4, 0), 0), ((8, 0, 8, 0), 0),         # a zero length on either side, inside the other range or not
+             ((0, 8, 8, 8), 0), ((8, 8, 0, 8), 0),                            # touching
+             ((0, 9, 8, 8), 1), ((8, 8, 0, 9), 1), ((0, 64, 20, 1), 1), ((0, 8, 16, 8), 0)]      # one byte shared, either order; inside; apart
+    blocks = [(0, 1), (1, 1), (256, 1), (257, 2), (2048 * 256, 2048), (2048 * 256 + 1, 2048), (1 << 40, 2048)]
+    with open(tmp_path / "cmds.txt", "w") as f:
+        f.write("consts\n")
+        for c in narrow + [accepted] + [r for r, _ in refused]:
+            f.write("narrow %d %d %d %d %d %s\n" % (*c[:5], " ".join(map(str, c[5]))))
+        f.write("".join("meets %d %d %d %d\n" % m for m, _ in meets) + "".join("blocks %d\n" % b for b, _ in blocks))
+    run = subprocess.run([exe, str(tmp_path / "cmds.txt")], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stderr == "", "sanitizer report:\n" + run.stderr[-4000:]
+    out = [json.loads(l) for l in run.stdout.splitlines()]
+    assert out[0] == {"threads": 256, "maxBlocks": 2048} and len(out) == 1 + len(narrow) + 1 + len(refused) + len(meets) + len(blocks)
+    for c, got in zip(narrow + [accepted], out[1:]):
+        flat = [v for r in c[6] for v in r]
+        halves = [h for word in got["words"] for h in (word & 0xFFFFFFFF, word >> 32)]
+        assert got["ok"] == 1 and len(got["words"]) == ((len(flat) + 1) // 2 + 1) // 2 * 2, c[:5]     # whole words, an even number of them
+        assert halves[:len(flat)] == flat and not any(halves[len(flat):]), c[:5]
+    at = 2 + len(narrow)
+    for (c, (cell, value)), got in zip(refused, out[at:]):
+        assert got == {"ok": 0, "cell": cell, "value": value}, c
+    at += len(refused)
+    assert [g["meets"] for g in out[at:at + len(meets)]] == [m for _, m in meets]
+    assert [g["blocks"] for g in out[at + len(meets):]] == [b for _, b in blocks]
+
+
 def test_planner_header_under_the_sanitizers(tmp_path):
     exe = str(tmp_path / "wtns_plan_dump")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,

@@ -9,6 +9,9 @@ runs timed with device events, of
                   the HBM rate DESIGN.md section 5 uses (8 TB/s) -- the gather is a random access, so the floor is far below its cost
   upload w        the pinned asynchronous upload of the witness through the host leg (pil2gl_dev_upload_async + copy_sync)
   upload trace    the same upload of the finished trace: what the host-side *_exec step needs today
+and, in a line of its own per shape, of
+  conn_pols_dev   the connection polynomials (csrc/conn_pols.hip) from the same resident sMap, N = the rows, unchecked, the working buffer
+                  taken from torch's allocator inside the timed call as pil2gl.wtns.conn_pols_dev does for every caller
   python tools/bench_wtns_exec.py [--limit SECONDS] [--out FILE] [--small]        one JSON line per case"""
 import argparse
 import ctypes as C
@@ -79,6 +82,13 @@ def synthetic(field, n_rows, n_cols, n_witness, n_adds, seed):
     return ex
 
 
+def rng_words(seed, n, words):
+    """n elements as words below the moduli: uint64 for Goldilocks, (n, 4) for Fr"""
+    a = np.random.default_rng(seed).integers(0, 1 << 62, (n, words), dtype=np.uint64)
+    a[:, words - 1] >>= np.uint64(2)
+    return a.reshape(-1) if words == 1 else a
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--limit", type=int, default=300)
@@ -118,7 +128,18 @@ def main():
                "times": "median, min, max of five"}
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
-        del w, dst, prep
+        del w, dst
+        # the connection polynomials from the same resident sMap (csrc/conn_pols.hip), N = the rows; w and ks' are multiplied as given, so any words do
+        cw = rng_words(bits, 1, words)
+        ks = rng_words(bits + 1, n_cols - 1, words)
+        plan = wtns.conn_plan(n_rows, n_cols, n_w, n_rows, field)
+        s_cols = torch.empty(n_rows * n_cols * words, dtype=torch.int64, device="cuda")
+        conn = timed(lambda: wtns.conn_pols_dev(prep, n_rows, cw, ks, dst=s_cols))
+        rec = {"op": "conn_pols_dev", "shape": name, "field": field, "rows": n_rows, "cols": n_cols, "nW": n_w, "passes": plan["passes"],
+               "launches": plan["launches"], "scratch_bytes": plan["scratchBytes"], "conn_ms": [round(x, 3) for x in conn], "times": "median, min, max of five"}
+        lines.append(json.dumps(rec))
+        print(lines[-1], flush=True)
+        del s_cols, prep
         torch.cuda.empty_cache()
     if a.out:
         with open(a.out, "w") as f_:
