@@ -33,7 +33,7 @@
  *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi[_step] / cols_dot_ext /
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
  *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, compute_fri_pol, build_lev (small host tables),
- *      h1h2 and bn128_h1h2 (the missing row comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
+ *      h1h2 and bn128_h1h2 (the missing row comes back), conn_check and bn128_conn_check (the report comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
  *      land_rows, wtns_gather, bn128_wtns_gather, conn_pols and bn128_conn_pols with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
  *    So do the host-pointer verifier calls roots_from_group_proofs and bn128_roots_from_group_proofs (roots copied to host memory).
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -825,6 +825,50 @@ int pil2gl_conn_pols(const void *hostSMap, int sMapLayout, uint64_t nRows, uint6
                      const uint64_t *hostKs1, uint64_t *hostDst);
 int pil2gl_bn128_conn_pols(const void *hostSMap, int sMapLayout, uint64_t nRows, uint64_t nCols, uint64_t nW, uint64_t N, const uint64_t *hostW,
                            const uint64_t *hostKs1, uint64_t *hostDst);
+
+/* ---- connection check: does a trace meet `{a[0 .. nCols)} connect {S[0 .. nCols)}` (csrc/conn_check.hip, csrc/conn_check_plan.h) ----
+ * The reference checks a recursion circuit's witness with pilcom's verifyPil (src/compressor/main_compressor_pil_verify.js:36, which loads
+ * the .const and .commit files); beyond polynomial identities the compressor and final PILs state one identity,
+ * `{a[0], ..., a[n-1]} connect {S[0], ..., S[n-1]}` (src/compressor/compressor12.pil.ejs:352, compressor18.pil.ejs:374,
+ * src/final/final6.pil.ejs:151, final9.pil.ejs:156, finalfflonk.pil.ejs:54).  pilcom is not part of the reference checkout; the statement checked here is this header's own:
+ *   id(i, j) = w^i ks1[j] for i < N, j < nCols, ks1[0] = 1; cells in flat order c = i nCols + j; for every cell c, S[c] must equal id(c')
+ *   of exactly one cell c' and a[c] must equal a[c'], both compared as field values.
+ * hostReport[0] = the smallest failing flat cell, UINT64_MAX when the trace is clean; [1] = the cell its S names, UINT64_MAX when it names
+ * none; [2] = the kind: 0 clean, 1 S names no cell, 2 the values differ, 3 the identities are not distinct (two cells share one id: a bad
+ * ks1 or w) -- then [0] is the first cell, in flat order, whose id an earlier cell has, [1] the first cell with that id, and a and S are
+ * not judged.  An element is one u64 (Goldilocks: words in [p, 2^64) count as their value mod p) or four u64 (Fr: MONTGOMERY words, any
+ * 256-bit pattern counting as its value mod r), as pil2gl_[bn128_]conn_pols writes S and pil2gl_[bn128_]wtns_gather_dev the trace.
+ * w (1 element) and ks1 (nCols elements, ks1[0] included) are HOST pointers in every form.
+ *
+ * pil2gl_conn_check_plan: host-only, no device.  outInfo[0] = log2 of the hash table's capacity, the smallest power of two >= 2 N nCols
+ * and >= 16 (one 32-bit cell index a slot; the load factor never exceeds 1 / 2); [1] = threads per workgroup; [2], [3] = bits of the low
+ * and high power tables (as pil2gl_conn_plan's [5], [6]); [4], [5] = workgroups of the build and of the check; [6] = lanes a cell of the
+ * check (1, Fr 2); [7] = kernel launches of a call, 4.  *scratchBytes = the working buffer, a multiple of 16:
+ * 64 + 4 2^[0] + r16(8 elemWords 2^[3]) + r16(8 elemWords nCols 2^[2]) where r16 rounds up to 16; 0 for nCols = 0.  PIL2GL_EINVAL:
+ * N nCols >= 2^32, N no power of two or above 2^32, nCols > 64, elemWords not 1 or 4.
+ * pil2gl_[bn128_]conn_check_dev: a, S = device; element (i, j) of either at ptr[(i stride + offset + j) elemWords], the column contract
+ * of csrc/bn_column.h applied to nCols adjacent columns of a row-major matrix `stride` elements wide (where conn_pols_dev wrote S and
+ * wtns_gather_dev the trace); a and S may be one matrix at different offsets, they are only read.  scratch = device, 16-byte aligned,
+ * scratchBytes >= the plan's.  The call BLOCKS until the three words of hostReport are on the host (as pil2gl_bn128_h1h2_dev blocks for
+ * its missing row).  PIL2GL_EINVAL: what the plan refuses, stride < offset + nCols or stride >= 2^32 for a or S, a scratch that is too
+ * small or overlaps a or S, a null or misaligned buffer (a, S 8-byte, Fr 16-byte), a null hostReport.  nCols = 0 is PIL2GL_OK, clean,
+ * and needs no device.
+ * pil2gl_[bn128_]conn_check: host pointers, hostA and hostS N x nCols elements each, row-major; stage (every part on 16 bytes), compute.
+ * Every refusal comes before the first device call; without a device the compute calls return PIL2GL_ENODEV. */
+int pil2gl_conn_check_plan(uint64_t N, uint64_t nCols, uint32_t elemWords, uint32_t *outInfo /* [8] */, uint64_t *scratchBytes);
+int pil2gl_conn_check_dev(const uint64_t *a, uint64_t aStride, uint64_t aOffset, const uint64_t *S, uint64_t sStride, uint64_t sOffset, uint64_t N,
+                          uint64_t nCols, const uint64_t *hostW, const uint64_t *hostKs1, uint64_t *scratch, uint64_t scratchBytes,
+                          uint64_t *hostReport /* [3] */, void *stream);
+int pil2gl_bn128_conn_check_dev(const uint64_t *a, uint64_t aStride, uint64_t aOffset, const uint64_t *S, uint64_t sStride, uint64_t sOffset, uint64_t N,
+                                uint64_t nCols, const uint64_t *hostW, const uint64_t *hostKs1, uint64_t *scratch, uint64_t scratchBytes,
+                                uint64_t *hostReport /* [3] */, void *stream);
+int pil2gl_conn_check(const uint64_t *hostA, const uint64_t *hostS, uint64_t N, uint64_t nCols, const uint64_t *hostW, const uint64_t *hostKs1,
+                      uint64_t *hostReport /* [3] */);
+int pil2gl_bn128_conn_check(const uint64_t *hostA, const uint64_t *hostS, uint64_t N, uint64_t nCols, const uint64_t *hostW, const uint64_t *hostKs1,
+                            uint64_t *hostReport /* [3] */);
+/* host-only, no device: the longest distance, in slots, between a key of the last call's hash table and its home slot (0: every key at
+ * home, or no call yet) -- what shows that a test reached the probing past the home slot */
+uint64_t pil2gl_debug_conn_check_probe(void);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

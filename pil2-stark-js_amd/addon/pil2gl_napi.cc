@@ -584,6 +584,36 @@ static napi_value conn_pols_host(napi_env env, napi_callback_info info, uint32_t
 FN(ConnPols) { return conn_pols_host(env, info, 1); }
 FN(Bn128ConnPols) { return conn_pols_host(env, info, 4); }
 
+// ---- connection check: does a trace meet {a} connect {S} (csrc/conn_check.hip; js/witness_exec.js) ----
+FN(ConnCheckPlan) {        // (N, nCols, elemWords) -> { capBits, threads, loBits, hiBits, buildBlocks, checkBlocks, lanesPerCell, launches, scratchBytes }
+    Args a(env, info); uint64_t N = a.u64(0), nCols = a.u64(1); uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
+    uint32_t out[8]; uint64_t bytes = 0;
+    P2(env, pil2gl_conn_check_plan(N, nCols, ew, out, &bytes));
+    static const char *names[8] = { "capBits", "threads", "loBits", "hiBits", "buildBlocks", "checkBlocks", "lanesPerCell", "launches" };
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 8; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
+    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "scratchBytes", v);
+    return o;
+}
+// (dA, aStride, aOffset, dS, sStride, sOffset, N, nCols, consts = w then ks1 (1 + nCols elements), dScratch, scratchBytes, report BigUint64Array(3))
+static napi_value conn_check_dev(napi_env env, napi_callback_info info, uint32_t ew) {
+    Args a(env, info); uint64_t *da = DP(0); uint64_t as = a.u64(1), ao = a.u64(2); uint64_t *ds = DP(3); uint64_t ss = a.u64(4), so = a.u64(5);
+    uint64_t N = a.u64(6), nCols = a.u64(7); uint64_t *c = a.arr(8, ew * (1 + nCols)); uint64_t *scr = DP(9); uint64_t bytes = a.u64(10);
+    uint64_t *rep = a.arr(11, 3); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_conn_check_dev : pil2gl_conn_check_dev)(da, as, ao, ds, ss, so, N, nCols, c, c + ew, scr, bytes, rep, nullptr));
+    return mk_undefined(env);
+}
+FN(ConnCheckDev) { return conn_check_dev(env, info, 1); }
+FN(Bn128ConnCheckDev) { return conn_check_dev(env, info, 4); }
+// (a, S (N nCols elements each, row-major), N, nCols, consts, report BigUint64Array(3))
+static napi_value conn_check_host(napi_env env, napi_callback_info info, uint32_t ew) {
+    Args a(env, info); uint64_t N = a.u64(2), nCols = a.u64(3);
+    uint64_t *ha = a.arr(0, ew * N * nCols), *hs = a.arr(1, ew * N * nCols), *c = a.arr(4, ew * (1 + nCols)), *rep = a.arr(5, 3); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_conn_check : pil2gl_conn_check)(ha, hs, N, nCols, c, c + ew, rep)); return mk_undefined(env);
+}
+FN(ConnCheck) { return conn_check_host(env, info, 1); }
+FN(Bn128ConnCheck) { return conn_check_host(env, info, 4); }
+
 // ---- BN128 Merkle commitment (merklehash_bn128_p.js / merklehash_bn128_worker.js) ----
 FN(Bn128Poseidon) {  // (in BigUint64Array(4*nIn*count) normal form, init BigUint64Array(4*count)|null, count, nIn, nOut, out(4*nOut*count))
     Args a(env, info); uint64_t count = a.u64(2), nIn = a.u64(3), nOut = a.u64(4);
@@ -770,6 +800,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128H1h2Dev", Bn128H1h2Dev },
         { "wtnsAddsPlan", WtnsAddsPlan }, { "wtnsAddsDev", WtnsAddsDev }, { "wtnsGatherDev", WtnsGatherDev }, { "wtnsExec", WtnsExec }, { "bn128WtnsExec", Bn128WtnsExec },
         { "connPlan", ConnPlan }, { "connPolsDev", ConnPolsDev }, { "bn128ConnPolsDev", Bn128ConnPolsDev }, { "connPols", ConnPols }, { "bn128ConnPols", Bn128ConnPols },
+        { "connCheckPlan", ConnCheckPlan }, { "connCheckDev", ConnCheckDev }, { "bn128ConnCheckDev", Bn128ConnCheckDev }, { "connCheck", ConnCheck }, { "bn128ConnCheck", Bn128ConnCheck },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

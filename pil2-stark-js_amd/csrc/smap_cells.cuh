@@ -1,4 +1,4 @@
-// Device half of what the units built on the resident sMap share (wtns_exec.hip, conn_pols.hip), gfx950: the report of the first cell whose
+// Device half of what the units built on the resident sMap share (wtns_exec.hip, conn_pols.hip, conn_check.hip), gfx950: the report of the first cell whose
 // index names no signal, the (row, column) walk of a grid-stride lane over a row-major table, and the element of either field as a kernel's
 // template parameter.  The host half is smap_plan.h.
 #pragma once

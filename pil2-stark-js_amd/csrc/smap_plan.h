@@ -1,4 +1,4 @@
-// What the host-only planners of the units built on the resident sMap share (wtns_plan.h, conn_plan.h): the grid of their stride kernels,
+// What the host-only planners of the units built on the resident sMap share (wtns_plan.h, conn_plan.h, conn_check_plan.h): the grid of their stride kernels,
 // the signal limit, the overlap test of the entries, the 16-byte rule of staged parts and the narrowing of a host sMap into the packed
 // 32-bit table the device reads.  No HIP header: it builds with the plain C++ compiler (tests/smap_plan_dump.cpp runs it under the
 // sanitizers).  The device half is smap_cells.cuh.

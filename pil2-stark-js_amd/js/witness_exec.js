@@ -18,6 +18,12 @@
 //   connectionPolsDev(prepared, dConst, { N, ks, w, stride, offset, check })   the same from prepareExec's resident sMap into columns
 //                                            [offset, offset + nCols) of dConst, a DevBuffer of N rows of `stride` elements (made when
 //                                            absent, stride = nCols); nothing is copied to the host; check: throw on a bad index
+//   checkConnections(F, a, S, N, ks, { w })  does the trace meet `{a} connect {S}`, the connection half of pilcom's verifyPil
+//                                            (main_compressor_pil_verify.js:36; csrc/conn_check.hip): a, S = [nCols][N] arrays (BigInts, 32-byte
+//                                            Montgomery Uint8Arrays) or the flat N x nCols matrices -> null when clean, else
+//                                            { row, col, toRow, toCol, kind, message() } of the first failing cell
+//   checkConnectionsDev(aCol, SCol, { N, ks, w })   the same on resident columns { buf, stride, offset }: where execDev wrote the trace
+//                                            and connectionPolsDev the constants; message() reads two elements back
 // Node 12: no optional chaining.
 "use strict";
 const fs = require("fs");
@@ -189,4 +195,78 @@ function connectionPolsDev(p, dConst, opts) {
     return dConst;
 }
 
-module.exports = { readExecFile, readWtns, compressorExec, finalExec, prepareExec, execDev, connectionPols, connectionPolsDev };
+// ---- connection check ----
+const GL_P = 0xFFFFFFFF00000001n;
+const FR = 21888242871839275222246405745257275088548364400416034343698204186575808495617n;
+const FR_R_INV = 9915499612839321149637521777990102151350674507940716049588462388200839649614n;       // (2^256)^-1 mod r
+const NONE = 0xFFFFFFFFFFFFFFFFn;
+// an element's words as the decimal the reference's F.toString prints: the value mod p, the normal form of Montgomery words
+function decimalOf(wordsOfElem) {
+    if (wordsOfElem.length === 1) return (wordsOfElem[0] % GL_P).toString();
+    let v = 0n;
+    for (let k = 3; k >= 0; k--) v = (v << 64n) | wordsOfElem[k];
+    return (v % FR * FR_R_INV % FR).toString();
+}
+// the library's three words and a reader of element (cell) of a or S -> null when clean, else the failing cell with a message().
+// The wording, once (INTEGRATION.md): kind 2 "connect: a[col][row] = X differs from a[toCol][toRow] = Y, the cell S[col][row] names";
+// kind 1 "connect: S[col][row] = X names no cell (a[col][row] = Y)"; kind 3 "connect: the identities of row, column and toRow, toCol are
+// equal (w or ks is wrong)".  Two elements are read, and only when message() is called.
+function connReport(rep, nCols, read) {
+    const kind = Number(rep[2]);
+    if (!kind) return null;
+    const cell = Number(rep[0]), named = rep[1] !== NONE, to = named ? Number(rep[1]) : null;
+    const r = { row: Math.floor(cell / nCols), col: cell % nCols, toRow: named ? Math.floor(to / nCols) : null, toCol: named ? to % nCols : null, kind };
+    const at = "[" + r.col + "][" + r.row + "]";
+    r.message = () => {
+        if (kind === 3) return "connect: the identities of row " + r.row + ", column " + r.col + " and row " + r.toRow + ", column " + r.toCol + " are equal (w or ks is wrong)";
+        if (kind === 1) return "connect: S" + at + " = " + decimalOf(read("S", cell)) + " names no cell (a" + at + " = " + decimalOf(read("a", cell)) + ")";
+        return "connect: a" + at + " = " + decimalOf(read("a", cell)) + " differs from a[" + r.toCol + "][" + r.toRow + "] = " + decimalOf(read("a", to)) + ", the cell S" + at + " names";
+    };
+    return r;
+}
+// a or S of the host form as N x nCols row-major words: the cmPols shape [nCols][N] (BigInts, 32-byte Uint8Arrays) or the flat matrix itself
+function connMatrix(x, N, nCols, ew, what) {
+    if (x instanceof BigUint64Array || x instanceof Uint8Array) {
+        const m = words(x);
+        if (m.length !== N * nCols * ew) throw new Error("checkConnections: " + what + " holds " + m.length + " words, " + N + " x " + nCols + " elements expected");
+        return m;
+    }
+    if (!Array.isArray(x) || x.length !== nCols) throw new Error("checkConnections: " + what + " must hold nCols = " + nCols + " columns");
+    const m = new BigUint64Array(N * nCols * ew), bytes = new Uint8Array(m.buffer);
+    for (let j = 0; j < nCols; j++) {
+        if (x[j].length !== N) throw new Error("checkConnections: " + what + "[" + j + "] holds " + x[j].length + " entries, N = " + N + " expected");
+        for (let i = 0; i < N; i++) { if (ew === 4) bytes.set(x[j][i], 32 * (i * nCols + j)); else m[i * nCols + j] = BigInt(x[j][i]); }
+    }
+    return m;
+}
+function checkConnections(F, a, S, N, ks, opts) {
+    const bn128 = F.n8 === 32, ew = bn128 ? 4 : 1, nCols = ks.length + 1;
+    const consts = connConsts(bn128, nCols, opts && opts.w !== undefined ? opts.w : F.w[Math.log2(N)], F.one, ks);
+    const ma = connMatrix(a, N, nCols, ew, "a"), mS = connMatrix(S, N, nCols, ew, "S"), rep = new BigUint64Array(3);
+    (bn128 ? addon.bn128ConnCheck : addon.connCheck)(ma, mS, N, nCols, consts, rep);
+    return connReport(rep, nCols, (which, cell) => (which === "a" ? ma : mS).subarray(cell * ew, (cell + 1) * ew));
+}
+// aCol, SCol: { buf: DevBuffer, stride, offset }, nCols adjacent columns from `offset` on of a matrix of N rows of `stride` elements (the
+// columns polutils_bn128.js takes, stride defaulting to offset + nCols here); the field is Fr when w is a Uint8Array, or as opts.bn128 says
+function checkConnectionsDev(aCol, SCol, opts) {
+    const bn128 = opts.bn128 !== undefined ? !!opts.bn128 : opts.w instanceof Uint8Array, ew = bn128 ? 4 : 1, N = opts.N, nCols = opts.ks.length + 1;
+    const col = (c, what) => {
+        if (!c || !isDev(c.buf)) throw new Error("checkConnectionsDev: " + what + " must be { buf: DevBuffer, stride, offset }");
+        const offset = c.offset || 0, stride = c.stride === undefined ? offset + nCols : c.stride;
+        if (c.buf.length < ((N - 1) * stride + offset + nCols) * ew) throw new Error("checkConnectionsDev: " + what + " holds " + c.buf.length + " words, N = " + N + " rows of " + stride + " elements need more");
+        return { buf: c.buf, stride, offset };
+    };
+    const A = col(aCol, "a"), Sc = col(SCol, "S");
+    const consts = connConsts(bn128, nCols, opts.w, bn128 ? FR_ONE : 1n, opts.ks);
+    const plan = addon.connCheckPlan(N, nCols, ew), rep = new BigUint64Array(3);
+    const work = new DevBuffer(plan.scratchBytes / 8);
+    try {
+        (bn128 ? addon.bn128ConnCheckDev : addon.connCheckDev)(A.buf.ptr, A.stride, A.offset, Sc.buf.ptr, Sc.stride, Sc.offset, N, nCols, consts, work.ptr, plan.scratchBytes, rep);
+    } finally { work.free(); }
+    return connReport(rep, nCols, (which, cell) => {
+        const c = which === "a" ? A : Sc, at = (Math.floor(cell / nCols) * c.stride + c.offset + cell % nCols) * ew;
+        return c.buf.slice(at, at + ew);
+    });
+}
+
+module.exports = { readExecFile, readWtns, compressorExec, finalExec, prepareExec, execDev, connectionPols, connectionPolsDev, checkConnections, checkConnectionsDev };

@@ -13,6 +13,11 @@ The same resident sMap drives the setups' connection polynomials (csrc/conn_pols
 
     S = conn_pols(s_map, n_cols, N, w, ks)                   # host arrays in, the (N, nCols) columns out
     S = conn_pols_dev(prep, N, w, ks)                        # from what prepare() left in HBM, into a device matrix
+
+and whether a trace meets the copy constraints those columns state (csrc/conn_check.hip), the connection half of pilcom's verifyPil:
+
+    bad = conn_check(a, S, n_cols, N, w, ks)                 # host arrays in; None, or the first failing cell, its partner and the kind
+    bad = conn_check_dev(trace, S, n_cols, N, w, ks)         # on the device matrices exec_dev and conn_pols_dev wrote
 """
 import ctypes as C
 import os
@@ -233,6 +238,67 @@ def conn_pols_dev(prep, N, w, ks, dst=None, dst_stride=None, dst_offset=0, check
     if check:
         return dst, (None if bad.value == 0xFFFFFFFFFFFFFFFF else bad.value)
     return dst
+
+
+# ---- connection check ----
+_NONE = 0xFFFFFFFFFFFFFFFF
+
+
+def conn_check_plan(N, n_cols, field="gl"):
+    """pil2gl_conn_check_plan (host-only): the hash table's capacity, the launch geometry, the working buffer"""
+    info = (C.c_uint32 * 8)()
+    nbytes = C.c_uint64()
+    call("pil2gl_conn_check_plan", N, n_cols, _WORDS[field], info, C.byref(nbytes))
+    names = ("capBits", "threads", "loBits", "hiBits", "buildBlocks", "checkBlocks", "lanesPerCell", "launches")
+    return dict(zip(names, (int(x) for x in info)), scratchBytes=nbytes.value)
+
+
+def _report(rep):
+    """the library's three words -> None when clean, else {"cell", "partner" (None when S names no cell), "kind"}"""
+    if rep[2] == 0:
+        return None
+    return {"cell": int(rep[0]), "partner": None if rep[1] == _NONE else int(rep[1]), "kind": int(rep[2])}
+
+
+def conn_check(a, S, n_cols, N, w, ks, field="gl"):
+    """does the trace `a` meet {a} connect {S}: host arrays of N x nCols elements each (uint64 words; Fr Montgomery, 4 words an element),
+    w and ks as conn_pols takes them -> None when clean, else the first failing cell (see _report; the kinds are pil2gl.h's)"""
+    words = _WORDS[field]
+    a = np.ascontiguousarray(a, np.uint64).reshape(-1)
+    S = np.ascontiguousarray(S, np.uint64).reshape(-1)
+    if a.size != N * n_cols * words or S.size != a.size:
+        raise Pil2glError("a holds %d words and S %d; %d x %d elements of %d words expected" % (a.size, S.size, N, n_cols, words))
+    w, ks1 = _conn_consts(w, ks, n_cols, words)
+    rep = (C.c_uint64 * 3)()
+    call("pil2gl_conn_check" if words == 1 else "pil2gl_bn128_conn_check", _np_ptr(a), _np_ptr(S), N, n_cols, _np_ptr(w), _np_ptr(ks1), rep)
+    return _report(rep)
+
+
+def conn_check_dev(a, S, n_cols, N, w, ks, field="gl", a_stride=None, a_offset=0, s_stride=None, s_offset=0):
+    """the same on device matrices of N rows: a in columns [a_offset, a_offset + nCols) of rows a_stride elements wide (default nCols +
+    a_offset), S alike -- where exec_dev wrote the trace and conn_pols_dev the constants; a and S may be one tensor.  The working buffer
+    comes from the plan and lives for the call; blocks for the report."""
+    words = _WORDS[field]
+    a_stride = n_cols + a_offset if a_stride is None else a_stride
+    s_stride = n_cols + s_offset if s_stride is None else s_stride
+    for name, t, stride, offset in (("a", a, a_stride, a_offset), ("S", S, s_stride, s_offset)):
+        if not _is_dev(t):
+            raise Pil2glError("conn_check_dev takes device tensors (conn_check takes host arrays)")
+        if n_cols and t.numel() < ((N - 1) * stride + offset + n_cols) * words:
+            raise Pil2glError("%s holds %d words, %d rows of stride %d need more" % (name, t.numel(), N, stride))
+    plan = conn_check_plan(N, n_cols, field)
+    w, ks1 = _conn_consts(w, ks, n_cols, words)
+    work = torch.empty(max(plan["scratchBytes"] // 8, 2), dtype=torch.int64, device=a.device)
+    rep = (C.c_uint64 * 3)()
+    call("pil2gl_conn_check_dev" if words == 1 else "pil2gl_bn128_conn_check_dev", _ptr(a), a_stride, a_offset, _ptr(S), s_stride, s_offset, N, n_cols,
+         _np_ptr(w), _np_ptr(ks1), _ptr(work), plan["scratchBytes"], rep, _stream())
+    return _report(rep)
+
+
+def conn_check_probe():
+    """pil2gl_debug_conn_check_probe: the longest distance between a key of the last call's hash table and its home slot"""
+    from ._lib import load
+    return int(load().pil2gl_debug_conn_check_probe())
 
 
 # ---- files ----

@@ -12,6 +12,8 @@ runs timed with device events, of
 and, in a line of its own per shape, of
   conn_pols_dev   the connection polynomials (csrc/conn_pols.hip) from the same resident sMap, N = the rows, unchecked, the working buffer
                   taken from torch's allocator inside the timed call as pil2gl.wtns.conn_pols_dev does for every caller
+  conn_check_dev  the connection check (csrc/conn_check.hip) of the gathered trace against those S columns: a clean pair, so every cell is
+                  probed and compared; the call blocks for its report, the working buffer is taken inside the timed call as above
   python tools/bench_wtns_exec.py [--limit SECONDS] [--out FILE] [--small]        one JSON line per case"""
 import argparse
 import ctypes as C
@@ -128,7 +130,7 @@ def main():
                "times": "median, min, max of five"}
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
-        del w, dst
+        del dst
         # the connection polynomials from the same resident sMap (csrc/conn_pols.hip), N = the rows; w and ks' are multiplied as given, so any words do
         cw = rng_words(bits, 1, words)
         ks = rng_words(bits + 1, n_cols - 1, words)
@@ -139,7 +141,20 @@ def main():
                "launches": plan["launches"], "scratch_bytes": plan["scratchBytes"], "conn_ms": [round(x, 3) for x in conn], "times": "median, min, max of five"}
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
-        del s_cols, prep
+        # the connection check (csrc/conn_check.hip) of the trace against those columns: clean, so every cell is probed and compared
+        trace = wtns.gather_dev(prep, w)
+        cplan = wtns.conn_check_plan(n_rows, n_cols, field)
+        verdict = []
+        chk = timed(lambda: verdict.append(wtns.conn_check_dev(trace, s_cols, n_cols, n_rows, cw, ks, field=field)))
+        assert all(v is None for v in verdict), verdict[0]
+        floor_bytes = cells * (8 + 24 * words)         # a slot written and read, S, a and the partner's a read
+        rec = {"op": "conn_check_dev", "shape": name, "field": field, "rows": n_rows, "cols": n_cols, "capBits": cplan["capBits"],
+               "launches": cplan["launches"], "scratch_bytes": cplan["scratchBytes"], "longest_probe": wtns.conn_check_probe(),
+               "check_ms": [round(x, 3) for x in chk], "floor_bytes": floor_bytes, "GBps_of_floor_bytes": round(floor_bytes / chk[0] / 1e6, 1),
+               "times": "median, min, max of five; the call blocks for its report"}
+        lines.append(json.dumps(rec))
+        print(lines[-1], flush=True)
+        del s_cols, prep, trace, w
         torch.cuda.empty_cache()
     if a.out:
         with open(a.out, "w") as f_:
