@@ -33,7 +33,7 @@
  *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi[_step] / cols_dot_ext /
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
  *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, compute_fri_pol, build_lev (small host tables),
- *      h1h2 and bn128_h1h2 (the missing row comes back), conn_check and bn128_conn_check (the report comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
+ *      h1h2 and bn128_h1h2 (the missing row comes back), conn_check and bn128_conn_check, tuple_check and bn128_tuple_check (the report comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
  *      land_rows, wtns_gather, bn128_wtns_gather, conn_pols and bn128_conn_pols with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
  *    So do the host-pointer verifier calls roots_from_group_proofs and bn128_roots_from_group_proofs (roots copied to host memory).
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -869,6 +869,69 @@ int pil2gl_bn128_conn_check(const uint64_t *hostA, const uint64_t *hostS, uint64
 /* host-only, no device: the longest distance, in slots, between a key of the last call's hash table and its home slot (0: every key at
  * home, or no call yet) -- what shows that a test reached the probing past the home slot */
 uint64_t pil2gl_debug_conn_check_probe(void);
+
+/* ---- lookup and permutation checks: does a trace meet `selF {f0..fk-1} in selT {t0..tk-1}` (plookup) or `selF {f0..fk-1} is selT {t0..tk-1}`
+ * (permutation) (csrc/tuple_check.hip, csrc/tuple_check_plan.h) ----
+ * The two non-polynomial identity kinds of PIL beside `connect`.  Without this block a witness that breaks one is found in stage 2 only:
+ * a permutation as the boundary constraint of Z at row N - 1, which names no row of f or t; a lookup as h1h2's missing row of the
+ * challenge-compressed value, columns and selectors already folded into one element.  pilcom is not part of the reference checkout; the
+ * statement checked here is this header's own (tests/tuple_check_ref.py restates it as one dictionary):
+ *   n rows, k columns, 1 <= k <= 16.  f = k columns of a row-major matrix: element j of row i at f[(i fStride + hostFCols[j]) elemWords];
+ *   the cols are element offsets within a row, need not be adjacent or increasing, and their order is the tuple's order.  t alike, with
+ *   its own base, stride and cols.  selF, selT: one column (base, stride, col) of a matrix of its own each, or NULL.
+ *   An element counts as its field value: one u64 (Goldilocks: words in [p, 2^64) count mod p) or four u64 (Fr: MONTGOMERY words, any
+ *   256-bit pattern counting mod r), pil2gl_[bn128_]conn_pols' rule.  Two tuples are equal when all k values are equal, in order.  A row
+ *   is SELECTED when its selector is NULL or its selector's value is non-zero; a selector value other than 0 or 1 is a polynomial
+ *   identity's business and is not judged here.  A cubic-extension column is three columns to this block.
+ *   cntF(v) = the selected rows of f with tuple v, cntT(v) = the selected rows of t with tuple v.
+ *   mode 0, lookup (`in`): the trace fails when a selected row of f has cntT = 0; the row reported is the smallest such, the kind 1.
+ *   mode 1, permutation (`is`): the trace fails when cntF(v) != cntT(v) for some v.  If any selected row of f has cntF > cntT the report
+ *   is the smallest such row, kind 1 when cntT = 0 and 2 otherwise; if none has, it is the smallest selected row of t with cntT > cntF,
+ *   kind 3.  A serial checker that walks f and decrements the counts of t would name the (cntT + 1)-th occurrence of an over-subscribed
+ *   tuple; this block names the tuple's FIRST occurrence in f and gives both counts.  Both name the same tuple; the first occurrence
+ *   needs no order of traversal to be defined, and cntF - cntT says how many occurrences are in excess, which the serial walk does not.
+ * hostReport[0] = kind (0 clean); [1] = row; [2] = partner, the smallest selected row on the OTHER side (t for kinds 1 and 2, f for kind 3)
+ * that holds the same tuple, UINT64_MAX when there is none; [3] = cntF and [4] = cntT of the reported row's tuple.  All five words
+ * describe one tuple.  A clean trace gives (0, UINT64_MAX, UINT64_MAX, 0, 0).  The report does not depend on the order in which the
+ * device's atomics land.
+ *
+ * pil2gl_tuple_check_plan: host-only, no device.  outInfo[0] = log2 of the hash table's capacity, the smallest power of two >= 4 n and
+ * >= 16 (both sides' rows share one table: at most 2 n rows are inserted, so the load factor never exceeds 1 / 2 whatever the data);
+ * [1] = threads per workgroup; [2] = workgroups of the build and of the judge; [3] = kernel launches of a call, 3; [4] = bytes of the
+ * header, 64; [5] = bytes a slot, 16 (a 32-bit row index, the tuple's smallest f row, a 64-bit counter).  *scratchBytes = the working
+ * buffer, 64 + 16 2^[0], every part on 16 bytes; 0 for n = 0.  PIL2GL_EINVAL: n > 2^28, k outside 1 .. 16, elemWords not 1 or 4, a mode
+ * other than 0 or 1.
+ * pil2gl_[bn128_]tuple_check_dev: f, t, selF, selT = device, 16-byte aligned, only read: they may overlap each other freely and one
+ * matrix may serve both sides.  hostFCols, hostTCols = HOST pointers, k entries each.  scratch = device, 16-byte aligned,
+ * scratchBytes >= the plan's.  The call BLOCKS until the five words of hostReport are on the host.  PIL2GL_EINVAL, before any device
+ * call: what the plan refuses, a column >= its stride (f, t or a selector; a stride >= 2^32), a null f, t, cols, scratch or hostReport, a
+ * misaligned device pointer, a scratch that is too small or overlaps f, t or a selector.  n = 0 is PIL2GL_OK, clean, and needs no device.
+ * pil2gl_[bn128_]tuple_check: host pointers; each matrix is staged up to the last element touched ((n - 1) stride + the highest column + 1
+ * elements, every part on 16 bytes) and the working buffer is taken inside.
+ * Without a device the compute calls return PIL2GL_ENODEV. */
+int pil2gl_tuple_check_plan(uint64_t n, uint64_t k, uint32_t elemWords, uint32_t mode, uint32_t *outInfo /* [6] */, uint64_t *scratchBytes);
+int pil2gl_tuple_check_dev(const uint64_t *f, uint64_t fStride, const uint64_t *hostFCols, const uint64_t *t, uint64_t tStride,
+                           const uint64_t *hostTCols, const uint64_t *selF, uint64_t selFStride, uint64_t selFCol, const uint64_t *selT,
+                           uint64_t selTStride, uint64_t selTCol, uint64_t n, uint64_t k, uint32_t mode, uint64_t *scratch,
+                           uint64_t scratchBytes, uint64_t *hostReport /* [5] */, void *stream);
+int pil2gl_bn128_tuple_check_dev(const uint64_t *f, uint64_t fStride, const uint64_t *hostFCols, const uint64_t *t, uint64_t tStride,
+                                 const uint64_t *hostTCols, const uint64_t *selF, uint64_t selFStride, uint64_t selFCol, const uint64_t *selT,
+                                 uint64_t selTStride, uint64_t selTCol, uint64_t n, uint64_t k, uint32_t mode, uint64_t *scratch,
+                                 uint64_t scratchBytes, uint64_t *hostReport /* [5] */, void *stream);
+int pil2gl_tuple_check(const uint64_t *hostF, uint64_t fStride, const uint64_t *hostFCols, const uint64_t *hostT, uint64_t tStride,
+                       const uint64_t *hostTCols, const uint64_t *hostSelF, uint64_t selFStride, uint64_t selFCol, const uint64_t *hostSelT,
+                       uint64_t selTStride, uint64_t selTCol, uint64_t n, uint64_t k, uint32_t mode, uint64_t *hostReport /* [5] */);
+int pil2gl_bn128_tuple_check(const uint64_t *hostF, uint64_t fStride, const uint64_t *hostFCols, const uint64_t *hostT, uint64_t tStride,
+                             const uint64_t *hostTCols, const uint64_t *hostSelF, uint64_t selFStride, uint64_t selFCol,
+                             const uint64_t *hostSelT, uint64_t selTStride, uint64_t selTCol, uint64_t n, uint64_t k, uint32_t mode,
+                             uint64_t *hostReport /* [5] */);
+/* host-only, no device: the home slot of a tuple in a table of `capacity` slots (a power of two), from the one hash function host and
+ * device share: words = k elemWords CANONICAL 64-bit words (Goldilocks values below p; Fr Montgomery words below r), column after
+ * column.  UINT64_MAX for k outside 1 .. 16, elemWords not 1 or 4, a capacity that is no power of two, null words. */
+uint64_t pil2gl_debug_tuple_home(const uint64_t *words, uint64_t k, uint32_t elemWords, uint64_t capacity);
+/* host-only, no device: the longest distance, in slots, between a tuple of the last call's hash table and its home slot (0: every tuple
+ * at home, or no call yet) -- what shows that a test reached the probing past the home slot */
+uint64_t pil2gl_debug_tuple_check_probe(void);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

@@ -614,6 +614,61 @@ static napi_value conn_check_host(napi_env env, napi_callback_info info, uint32_
 FN(ConnCheck) { return conn_check_host(env, info, 1); }
 FN(Bn128ConnCheck) { return conn_check_host(env, info, 4); }
 
+// ---- lookup and permutation checks: selF {f..} in / is selT {t..} as statements about the trace (csrc/tuple_check.hip; js/pil_checks.js) ----
+FN(TupleCheckPlan) {       // (n, k, elemWords, mode) -> { capBits, threads, blocks, launches, headerBytes, slotBytes, scratchBytes }
+    Args a(env, info); uint64_t n = a.u64(0), k = a.u64(1); uint32_t ew = (uint32_t)a.u64(2), mode = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
+    uint32_t out[6]; uint64_t bytes = 0;
+    P2(env, pil2gl_tuple_check_plan(n, k, ew, mode, out, &bytes));
+    static const char *names[6] = { "capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes" };
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 6; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
+    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "scratchBytes", v);
+    return o;
+}
+// A call's description, one BigUint64Array: [0] f, [1] fStride, [2] t, [3] tStride, [4] selF (0: none), [5] selFStride, [6] selFCol, [7] selT,
+// [8] selTStride, [9] selTCol, [10] n, [11] k, [12] mode, then k columns of f and k columns of t.  The pointer words are device addresses
+// for tupleCheckDev and are not read by tupleCheck, which takes the host matrices as arguments of their own.
+enum { TD_F, TD_F_STRIDE, TD_T, TD_T_STRIDE, TD_SELF, TD_SELF_STRIDE, TD_SELF_COL, TD_SELT, TD_SELT_STRIDE, TD_SELT_COL, TD_N, TD_K, TD_MODE, TD_COLS };
+static uint64_t *tuple_desc(Args &a, size_t i) {
+    uint64_t len = 0; uint64_t *d = a.arr(i, TD_COLS, &len);
+    if (a.ok && (d[TD_K] > 16 || len < TD_COLS + 2 * d[TD_K])) a.fail("the description holds 13 words and 2 k columns, k <= 16");
+    return d;
+}
+// the words a host matrix must hold for the library to read it: 0 where the library refuses the shape before it reads anything
+static uint64_t tuple_span(uint64_t n, uint64_t stride, const uint64_t *cols, uint64_t k, uint32_t ew) {
+    uint64_t top = 0;
+    for (uint64_t j = 0; j < k; j++) { if (cols[j] >= stride) return 0; top = cols[j] > top ? cols[j] : top; }
+    return n && n <= (1ull << 28) && !(stride >> 32) && n * stride <= (1ull << 58) ? ((n - 1) * stride + top + 1) * ew : 0;
+}
+FN(TupleCheckDev) {        // (description, dScratch, scratchBytes, report BigUint64Array(5), elemWords)
+    Args a(env, info); uint64_t *d = tuple_desc(a, 0); uint64_t *scr = DP(1); uint64_t bytes = a.u64(2); uint64_t *rep = a.arr(3, 5);
+    uint32_t ew = (uint32_t)a.u64(4); if (!a.ok) return nullptr;
+    const uint64_t k = d[TD_K];
+    P2(env, (ew == 4 ? pil2gl_bn128_tuple_check_dev : pil2gl_tuple_check_dev)(
+        (const uint64_t *)(uintptr_t)d[TD_F], d[TD_F_STRIDE], d + TD_COLS, (const uint64_t *)(uintptr_t)d[TD_T], d[TD_T_STRIDE], d + TD_COLS + k,
+        (const uint64_t *)(uintptr_t)d[TD_SELF], d[TD_SELF_STRIDE], d[TD_SELF_COL], (const uint64_t *)(uintptr_t)d[TD_SELT], d[TD_SELT_STRIDE], d[TD_SELT_COL],
+        d[TD_N], k, (uint32_t)d[TD_MODE], scr, bytes, rep, nullptr));
+    return mk_undefined(env);
+}
+FN(TupleCheck) {           // (description, f, t, selF | null, selT | null, report BigUint64Array(5), elemWords): host matrices as BigUint64Array
+    Args a(env, info); uint64_t *d = tuple_desc(a, 0); uint32_t ew = (uint32_t)a.u64(6); if (!a.ok) return nullptr;
+    if (ew != 1 && ew != 4) { a.fail("elemWords is 1 or 4"); return nullptr; }
+    const uint64_t k = d[TD_K], n = d[TD_N];
+    uint64_t *f = a.arr(1, tuple_span(n, d[TD_F_STRIDE], d + TD_COLS, k, ew)), *t = a.arr(2, tuple_span(n, d[TD_T_STRIDE], d + TD_COLS + k, k, ew));
+    uint64_t *sf = a.is_nullish(3) ? nullptr : a.arr(3, tuple_span(n, d[TD_SELF_STRIDE], d + TD_SELF_COL, 1, ew));
+    uint64_t *st = a.is_nullish(4) ? nullptr : a.arr(4, tuple_span(n, d[TD_SELT_STRIDE], d + TD_SELT_COL, 1, ew));
+    uint64_t *rep = a.arr(5, 5); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_tuple_check : pil2gl_tuple_check)(f, d[TD_F_STRIDE], d + TD_COLS, t, d[TD_T_STRIDE], d + TD_COLS + k, sf, d[TD_SELF_STRIDE],
+                                                                      d[TD_SELF_COL], st, d[TD_SELT_STRIDE], d[TD_SELT_COL], n, k, (uint32_t)d[TD_MODE], rep));
+    return mk_undefined(env);
+}
+FN(TupleHome) {            // (canonical words BigUint64Array(k elemWords), k, elemWords, capacity) -> the home slot as BigInt (2^64-1: refused)
+    Args a(env, info); uint64_t k = a.u64(1); uint32_t ew = (uint32_t)a.u64(2); uint64_t cap = a.u64(3);
+    uint64_t *w = a.arr(0, k <= 16 && ew <= 4 ? k * ew : 0); if (!a.ok) return nullptr;
+    return mk_bigint(env, pil2gl_debug_tuple_home(w, k, ew, cap));
+}
+FN(TupleCheckProbe) { return mk_bigint(env, pil2gl_debug_tuple_check_probe()); }
+
 // ---- BN128 Merkle commitment (merklehash_bn128_p.js / merklehash_bn128_worker.js) ----
 FN(Bn128Poseidon) {  // (in BigUint64Array(4*nIn*count) normal form, init BigUint64Array(4*count)|null, count, nIn, nOut, out(4*nOut*count))
     Args a(env, info); uint64_t count = a.u64(2), nIn = a.u64(3), nOut = a.u64(4);
@@ -801,6 +856,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "wtnsAddsPlan", WtnsAddsPlan }, { "wtnsAddsDev", WtnsAddsDev }, { "wtnsGatherDev", WtnsGatherDev }, { "wtnsExec", WtnsExec }, { "bn128WtnsExec", Bn128WtnsExec },
         { "connPlan", ConnPlan }, { "connPolsDev", ConnPolsDev }, { "bn128ConnPolsDev", Bn128ConnPolsDev }, { "connPols", ConnPols }, { "bn128ConnPols", Bn128ConnPols },
         { "connCheckPlan", ConnCheckPlan }, { "connCheckDev", ConnCheckDev }, { "bn128ConnCheckDev", Bn128ConnCheckDev }, { "connCheck", ConnCheck }, { "bn128ConnCheck", Bn128ConnCheck },
+        { "tupleCheckPlan", TupleCheckPlan }, { "tupleCheckDev", TupleCheckDev }, { "tupleCheck", TupleCheck }, { "tupleHome", TupleHome }, { "tupleCheckProbe", TupleCheckProbe },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

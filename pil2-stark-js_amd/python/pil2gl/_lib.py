@@ -229,6 +229,13 @@ SIGNATURES = {
     "pil2gl_conn_check": (_I, [vp, vp, _U64, _U64, vp, vp, vp]),
     "pil2gl_bn128_conn_check": (_I, [vp, vp, _U64, _U64, vp, vp, vp]),
     "pil2gl_debug_conn_check_probe": (_U64, []),
+    "pil2gl_tuple_check_plan": (_I, [_U64, _U64, _U32, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_tuple_check_dev": (_I, [vp, _U64, vp, vp, _U64, vp, vp, _U64, _U64, vp, _U64, _U64, _U64, _U64, _U32, vp, _U64, vp, vp]),
+    "pil2gl_bn128_tuple_check_dev": (_I, [vp, _U64, vp, vp, _U64, vp, vp, _U64, _U64, vp, _U64, _U64, _U64, _U64, _U32, vp, _U64, vp, vp]),
+    "pil2gl_tuple_check": (_I, [vp, _U64, vp, vp, _U64, vp, vp, _U64, _U64, vp, _U64, _U64, _U64, _U64, _U32, vp]),
+    "pil2gl_bn128_tuple_check": (_I, [vp, _U64, vp, vp, _U64, vp, vp, _U64, _U64, vp, _U64, _U64, _U64, _U64, _U32, vp]),
+    "pil2gl_debug_tuple_home": (_U64, [vp, _U64, _U32, _U64]),
+    "pil2gl_debug_tuple_check_probe": (_U64, []),
     "pil2gl_selftest_field":(_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_ext": (_I, [vp, vp, _U64, vp, vp]),
     "pil2gl_selftest_products": (_I, [vp, vp, _U64, vp, vp, vp]),

@@ -1,0 +1,119 @@
+"""PIL's two non-polynomial identity kinds beside `connect`, checked on the device as statements about the trace (csrc/tuple_check.hip):
+
+    selF {f0..fk-1} in selT {t0..tk-1}     plookup        lookup_check / lookup_check_dev
+    selF {f0..fk-1} is selT {t0..tk-1}     permutation    perm_check / perm_check_dev
+
+    rep = lookup_check(f, [0, 1, 2], t, [0, 1, 2], n)                      # host matrices in
+    rep = perm_check_dev(cm1, [7, 3], cm1, [4, 5], n, sel_f=(cm1, 9))     # column sets of one resident matrix, a selector column
+
+A matrix is (rows, stride) uint64 words over Goldilocks and (rows, stride, 4) Montgomery words over Fr (or flat, with the stride given);
+cols are element offsets within a row, in the tuple's order; a selector is (matrix, col) or (matrix, col, stride), or None.  Every form
+returns the library's five words (kind, row, partner, cntF, cntT) -- include/pil2gl.h states them; a clean trace gives
+(0, NONE, NONE, 0, 0).  No arithmetic happens here: hashing, counting and judging are the library's.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import Pil2glError, call, load
+from . import _is_dev, _ptr, _stream, torch
+
+NONE = 0xFFFFFFFFFFFFFFFF
+LOOKUP, PERMUTATION = 0, 1
+_WORDS = {"gl": 1, "bn128": 4}
+
+
+def tuple_check_plan(n, k, field="gl", mode=LOOKUP):
+    """pil2gl_tuple_check_plan (host-only): the hash table's capacity, the launch geometry, the working buffer"""
+    info = (C.c_uint32 * 6)()
+    nbytes = C.c_uint64()
+    call("pil2gl_tuple_check_plan", n, k, _WORDS[field], mode, info, C.byref(nbytes))
+    names = ("capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes")
+    return dict(zip(names, (int(x) for x in info)), scratchBytes=nbytes.value)
+
+
+def tuple_home(words, k, field="gl", capacity=16):
+    """pil2gl_debug_tuple_home (host-only): the home slot of a tuple of k CANONICAL elements given as words (k, or (k, 4) over Fr)"""
+    w = np.ascontiguousarray(words, np.uint64).reshape(-1)
+    if w.size != k * _WORDS[field]:
+        raise Pil2glError("the tuple holds %d words, k = %d elements of %d words expected" % (w.size, k, _WORDS[field]))
+    home = int(load().pil2gl_debug_tuple_home(C.c_void_p(w.ctypes.data), k, _WORDS[field], capacity))
+    if home == NONE:
+        raise Pil2glError("tuple_home: k is 1 .. 16 and the capacity a power of two")
+    return home
+
+
+def tuple_check_probe():
+    """pil2gl_debug_tuple_check_probe: the longest distance between a tuple of the last call's hash table and its home slot"""
+    return int(load().pil2gl_debug_tuple_check_probe())
+
+
+def _matrix(m, stride, words, dev, what):
+    """a matrix as (buffer, words it holds, stride in elements)"""
+    if _is_dev(m) != dev:
+        raise Pil2glError("%s: the _dev forms take device tensors, the others host arrays" % what)
+    if not dev:
+        m = np.ascontiguousarray(m, np.uint64)
+    shape = tuple(m.shape)
+    if stride is None:
+        if len(shape) != (2 if words == 1 else 3) or (words == 4 and shape[2] != 4):
+            raise Pil2glError("%s: give a (rows, stride%s) matrix or its stride" % (what, ", 4" if words == 4 else ""))
+        stride = shape[1]
+    return m, (m.numel() if dev else m.size), stride
+
+
+def _side(m, cols, stride, sel, n, words, dev, what):
+    """one side as the entries take it: (buffer, stride, cols array, selector buffer, its stride, its column); sizes checked here, because
+    the library cannot know where a buffer ends"""
+    m, held, stride = _matrix(m, stride, words, dev, what)
+    cols = np.ascontiguousarray(cols, np.uint64).reshape(-1)
+    if n and cols.size and held < ((n - 1) * stride + int(cols.max()) + 1) * words:
+        raise Pil2glError("%s holds %d words, %d rows of stride %d need more" % (what, held, n, stride))
+    if sel is None:
+        return m, stride, cols, None, 0, 0
+    sm, sheld, sstride = _matrix(sel[0], sel[2] if len(sel) > 2 else None, words, dev, "the selector of " + what)
+    if n and sheld < ((n - 1) * sstride + sel[1] + 1) * words:
+        raise Pil2glError("the selector of %s holds %d words, %d rows of stride %d need more" % (what, sheld, n, sstride))
+    return m, stride, cols, sm, sstride, sel[1]
+
+
+def _check(mode, dev, f, f_cols, t, t_cols, n, field, f_stride, t_stride, sel_f, sel_t):
+    words = _WORDS[field]
+    F = _side(f, f_cols, f_stride, sel_f, n, words, dev, "f")
+    T = _side(t, t_cols, t_stride, sel_t, n, words, dev, "t")
+    k = F[2].size
+    if T[2].size != k:
+        raise Pil2glError("f has %d columns and t %d" % (k, T[2].size))
+    ptr = _ptr if dev else (lambda a: None if a is None else C.c_void_p(a.ctypes.data))
+    cp = lambda c: C.c_void_p(c.ctypes.data)                                     # noqa: E731
+    args = [ptr(F[0]), F[1], cp(F[2]), ptr(T[0]), T[1], cp(T[2]), ptr(F[3]), F[4], F[5], ptr(T[3]), T[4], T[5], n, k, mode]
+    rep = (C.c_uint64 * 5)()
+    name = "pil2gl_tuple_check" if words == 1 else "pil2gl_bn128_tuple_check"
+    if dev:
+        plan = tuple_check_plan(n, k, field, mode)
+        work = torch.empty(max(plan["scratchBytes"] // 8, 2), dtype=torch.int64, device=F[0].device)
+        call(name + "_dev", *args, _ptr(work), plan["scratchBytes"], rep, _stream())
+    else:
+        call(name, *args, rep)
+    return tuple(int(x) for x in rep)
+
+
+def lookup_check(f, f_cols, t, t_cols, n, field="gl", f_stride=None, t_stride=None, sel_f=None, sel_t=None):
+    """does every selected row of f occur among the selected rows of t: host matrices -> (kind, row, partner, cntF, cntT)"""
+    return _check(LOOKUP, False, f, f_cols, t, t_cols, n, field, f_stride, t_stride, sel_f, sel_t)
+
+
+def perm_check(f, f_cols, t, t_cols, n, field="gl", f_stride=None, t_stride=None, sel_f=None, sel_t=None):
+    """are the selected rows of f a permutation of the selected rows of t: host matrices -> (kind, row, partner, cntF, cntT)"""
+    return _check(PERMUTATION, False, f, f_cols, t, t_cols, n, field, f_stride, t_stride, sel_f, sel_t)
+
+
+def lookup_check_dev(f, f_cols, t, t_cols, n, field="gl", f_stride=None, t_stride=None, sel_f=None, sel_t=None):
+    """lookup_check on device tensors, e.g. column sets of the stage-1 buffer before it is committed; the working buffer comes from the
+    plan and lives for the call; blocks for the report"""
+    return _check(LOOKUP, True, f, f_cols, t, t_cols, n, field, f_stride, t_stride, sel_f, sel_t)
+
+
+def perm_check_dev(f, f_cols, t, t_cols, n, field="gl", f_stride=None, t_stride=None, sel_f=None, sel_t=None):
+    """perm_check on device tensors"""
+    return _check(PERMUTATION, True, f, f_cols, t, t_cols, n, field, f_stride, t_stride, sel_f, sel_t)
