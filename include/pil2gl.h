@@ -33,7 +33,7 @@
  *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi[_step] / cols_dot_ext /
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
  *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, compute_fri_pol, build_lev (small host tables),
- *      h1h2 and bn128_h1h2 (the missing row comes back), conn_check and bn128_conn_check, tuple_check and bn128_tuple_check (the report comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
+ *      h1h2 and bn128_h1h2 (the missing row comes back), conn_check and bn128_conn_check, tuple_check and bn128_tuple_check, lookup_mult and bn128_lookup_mult (the report comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
  *      land_rows, wtns_gather, bn128_wtns_gather, conn_pols and bn128_conn_pols with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
  *    So do the host-pointer verifier calls roots_from_group_proofs and bn128_roots_from_group_proofs (roots copied to host memory).
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -932,6 +932,63 @@ uint64_t pil2gl_debug_tuple_home(const uint64_t *words, uint64_t k, uint32_t ele
 /* host-only, no device: the longest distance, in slots, between a tuple of the last call's hash table and its home slot (0: every tuple
  * at home, or no call yet) -- what shows that a test reached the probing past the home slot */
 uint64_t pil2gl_debug_tuple_check_probe(void);
+
+/* ---- lookup multiplicities: the logUp column m of `selF_s {f_s} in selT {t}`, s < nF (csrc/lookup_mult.hip, csrc/lookup_mult_plan.h) ----
+ * pil2 states a lookup as a grand sum, sum selF / (f + gamma) - sum m / (t + gamma) = 0; m is a stage-1 witness column: m[j] = how often
+ * the tuple of row j of t is looked up.  The block above says whether a lookup holds; this one produces the column that proves it, without
+ * f and t leaving the device.  The statement is this header's own (tests/lookup_mult_ref.py restates it as one dictionary):
+ *   n rows every side, n <= 2^28; k columns a tuple, 1 <= k <= 16; 1 <= nF <= 8 sides of f, so nF n <= 2^31 and a count fits 32 bits.
+ *   One side is a pil2gl_tuple_side: k columns `hostCols` (element offsets within a row, in the tuple's order, a HOST pointer) of the
+ *   row-major matrix (base, stride), and an optional selector column (sel, selStride, selCol) of a matrix of its own (sel NULL: none).
+ *   Elements, equality of tuples and SELECTED rows are the block above's: an element counts as its field value (Goldilocks words in
+ *   [p, 2^64) mod p, any 256-bit Fr Montgomery pattern mod r); a row is selected when its selector is NULL or non-zero.
+ *   t is one side; f_0 .. f_{nF-1} are nF sides, each with its own matrix, columns and selector.
+ *   cnt(v) = the sum over s of the selected rows of f_s with tuple v.
+ *   m = column mCol of a matrix (m, mStride) of elemWords-word elements, written for EVERY row j < n:  m[j] = cnt(tuple of t[j]) when j is
+ *   selected in t and is the smallest selected row of t with that tuple; m[j] = 0 otherwise.  The value is a canonical field element: one
+ *   u64 below p, or the Montgomery form of the count, below r.
+ * hostReport[0] = kind: 0 clean; 1 = some selected row of some f_s holds a tuple that no selected row of t holds.  [1] = side, [2] = row:
+ * for kind 1 the lexicographically smallest failing (side, row); both UINT64_MAX when clean.  [3] = matched, the selected rows of all f
+ * sides whose tuple t holds.  The sum of m over all rows is `matched`, always; on kind 1 m is still written in full and counts the rows
+ * that matched.  Neither m nor the report depends on the order in which the device's atomics land.
+ *
+ * pil2gl_lookup_mult_plan: host-only, no device.  outInfo[0] = log2 of the hash table's capacity, the smallest power of two >= 2 n and
+ * >= 16 (only t's selected rows are inserted: the load factor never exceeds 1 / 2); [1] = threads per workgroup; [2] = workgroups of the
+ * build, of each count and of the write; [3] = kernel launches of a call, 3 + nF (init, build, one count a side of f, write); [4] = bytes
+ * of the header, 64; [5] = bytes a slot, 8 (the tuple's smallest selected row of t, a 32-bit counter).  *scratchBytes = the working
+ * buffer, 64 + 8 2^[0]; 0 for n = 0.  PIL2GL_EINVAL: n > 2^28, k outside 1 .. 16, nF outside 1 .. 8, elemWords not 1 or 4.
+ * pil2gl_[bn128_]lookup_mult_dev: hostF (nF entries) and hostT are HOST pointers to sides whose base and sel are device pointers, 16-byte
+ * aligned, only read; the read matrices may overlap each other freely and one matrix may serve several sides.  m = device, 16-byte
+ * aligned.  Aliasing rule of m: m's span (from m to the end of row n - 1's element of column mCol) may meet the span of a matrix that is
+ * read (t, an f, a selector's) only when it has that matrix's base and stride and mCol is none of the columns read of it -- m as one more
+ * column of t's or of an f's matrix is the normal case.  scratch = device, 16-byte aligned, scratchBytes >= the plan's, meeting no
+ * matrix, m's included.  The call BLOCKS until the four words of hostReport are on the host.  PIL2GL_EINVAL, before any device call: what
+ * the plan refuses, a column >= its stride (t, an f, a selector or m), a stride >= 2^32 or n stride > 2^58 elements, a null side list,
+ * cols, base, m, scratch or hostReport, a misaligned device pointer, a scratch that is too small or overlaps a matrix, an m that breaks
+ * the aliasing rule.  A refused call leaves a clean report.  n = 0 is PIL2GL_OK, clean, writes nothing and needs no device.
+ * pil2gl_[bn128_]lookup_mult: host pointers throughout; each matrix is staged up to the last element touched, every part on 16 bytes,
+ * m's matrix (up to column mCol of row n - 1) goes up as it is and is downloaded again with the column written; the working buffer is
+ * taken inside.  The aliasing rule holds for the host pointers alike.  Without a device the compute calls return PIL2GL_ENODEV. */
+typedef struct pil2gl_tuple_side {
+    const uint64_t *base;                /* the matrix: element j of row i at base[(i stride + hostCols[j]) elemWords] */
+    uint64_t stride;
+    const uint64_t *hostCols;            /* k element offsets, a HOST pointer in every form */
+    const uint64_t *sel;                 /* the selector's matrix, or NULL */
+    uint64_t selStride, selCol;
+} pil2gl_tuple_side;
+int pil2gl_lookup_mult_plan(uint64_t n, uint64_t k, uint64_t nF, uint32_t elemWords, uint32_t *outInfo /* [6] */, uint64_t *scratchBytes);
+int pil2gl_lookup_mult_dev(const pil2gl_tuple_side *hostF, uint64_t nF, const pil2gl_tuple_side *hostT, uint64_t *m, uint64_t mStride,
+                           uint64_t mCol, uint64_t n, uint64_t k, uint64_t *scratch, uint64_t scratchBytes, uint64_t *hostReport /* [4] */,
+                           void *stream);
+int pil2gl_bn128_lookup_mult_dev(const pil2gl_tuple_side *hostF, uint64_t nF, const pil2gl_tuple_side *hostT, uint64_t *m, uint64_t mStride,
+                                 uint64_t mCol, uint64_t n, uint64_t k, uint64_t *scratch, uint64_t scratchBytes,
+                                 uint64_t *hostReport /* [4] */, void *stream);
+int pil2gl_lookup_mult(const pil2gl_tuple_side *hostF, uint64_t nF, const pil2gl_tuple_side *hostT, uint64_t *hostM, uint64_t mStride,
+                       uint64_t mCol, uint64_t n, uint64_t k, uint64_t *hostReport /* [4] */);
+int pil2gl_bn128_lookup_mult(const pil2gl_tuple_side *hostF, uint64_t nF, const pil2gl_tuple_side *hostT, uint64_t *hostM, uint64_t mStride,
+                             uint64_t mCol, uint64_t n, uint64_t k, uint64_t *hostReport /* [4] */);
+/* host-only, no device: the longest distance, in slots, between a tuple of the last call's hash table and its home slot */
+uint64_t pil2gl_debug_lookup_mult_probe(void);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

@@ -669,6 +669,74 @@ FN(TupleHome) {            // (canonical words BigUint64Array(k elemWords), k, e
 }
 FN(TupleCheckProbe) { return mk_bigint(env, pil2gl_debug_tuple_check_probe()); }
 
+// ---- lookup multiplicities: the logUp column m of `selF_s {f_s} in selT {t}` (csrc/lookup_mult.hip; js/pil_checks.js) ----
+FN(LookupMultPlan) {       // (n, k, nF, elemWords) -> { capBits, threads, blocks, launches, headerBytes, slotBytes, scratchBytes }
+    Args a(env, info); uint64_t n = a.u64(0), k = a.u64(1), nF = a.u64(2); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
+    uint32_t out[6]; uint64_t bytes = 0;
+    P2(env, pil2gl_lookup_mult_plan(n, k, nF, ew, out, &bytes));
+    static const char *names[6] = { "capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes" };
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 6; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
+    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "scratchBytes", v);
+    return o;
+}
+// A call's description, one BigUint64Array: [0] n, [1] k, [2] nF, [3] m, [4] mStride, [5] mCol, then 1 + nF sides of six words in
+// pil2gl_tuple_side's order -- t first, then f_0 .. f_{nF-1}: base, stride, (unused: the columns' place), sel (0: none), selStride, selCol --
+// then the sides' k columns each, in the same order.  The pointer words are device addresses for lookupMultDev and are not read by
+// lookupMult, which takes the host matrices as an array of its own.
+enum { MD_N, MD_K, MD_NF, MD_M, MD_M_STRIDE, MD_M_COL, MD_SIDES, MD_SIDE_WORDS = 6 };
+struct MultDesc { uint64_t *d; uint64_t n, k, nF; pil2gl_tuple_side side[9]; };             // side[0]: t
+static bool mult_desc(Args &a, size_t i, MultDesc &m) {
+    uint64_t len = 0; m.d = a.arr(i, MD_SIDES, &len);
+    if (!a.ok) return false;
+    m.n = m.d[MD_N]; m.k = m.d[MD_K]; m.nF = m.d[MD_NF];
+    if (m.k > 16 || m.nF > 8 || len < MD_SIDES + (1 + m.nF) * (MD_SIDE_WORDS + m.k)) return a.fail("the description holds 6 words, then 1 + nF sides of 6 words and k columns, k <= 16, nF <= 8");
+    uint64_t *cols = m.d + MD_SIDES + (1 + m.nF) * MD_SIDE_WORDS;
+    for (uint64_t s = 0; s <= m.nF; s++) {
+        const uint64_t *w = m.d + MD_SIDES + s * MD_SIDE_WORDS;
+        m.side[s] = pil2gl_tuple_side{ (const uint64_t *)(uintptr_t)w[0], w[1], cols + s * m.k, (const uint64_t *)(uintptr_t)w[3], w[4], w[5] };
+    }
+    return true;
+}
+FN(LookupMultDev) {        // (description, dScratch, scratchBytes, report BigUint64Array(4), elemWords)
+    Args a(env, info); MultDesc m; if (!mult_desc(a, 0, m)) return nullptr;
+    uint64_t *scr = DP(1); uint64_t bytes = a.u64(2); uint64_t *rep = a.arr(3, 4); uint32_t ew = (uint32_t)a.u64(4); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_lookup_mult_dev : pil2gl_lookup_mult_dev)(m.side + 1, m.nF, m.side, (uint64_t *)(uintptr_t)m.d[MD_M], m.d[MD_M_STRIDE], m.d[MD_M_COL],
+                                                                              m.n, m.k, scr, bytes, rep, nullptr));
+    return mk_undefined(env);
+}
+// (description, matrices, report BigUint64Array(4), elemWords): matrices = an Array of BigUint64Array, [2 s] the matrix of side s (t first),
+// [2 s + 1] its selector's or null, [2 (1 + nF)] m's matrix, which is written in place
+FN(LookupMult) {
+    Args a(env, info); MultDesc m; if (!mult_desc(a, 0, m)) return nullptr;
+    uint64_t *rep = a.arr(2, 4); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
+    if (ew != 1 && ew != 4) { a.fail("elemWords is 1 or 4"); return nullptr; }
+    bool isArray = false; uint32_t count = 0;
+    if (a.argc < 2 || napi_is_array(env, a.argv[1], &isArray) != napi_ok || !isArray) { a.fail("expected an Array of matrices"); return nullptr; }
+    napi_get_array_length(env, a.argv[1], &count);
+    if (count != 2 * (1 + m.nF) + 1) { a.fail("expected a matrix and a selector or null for t and every f, then m's matrix"); return nullptr; }
+    auto words = [&](uint32_t i, uint64_t minWords, bool optional) -> uint64_t * {       // element i as a BigUint64Array of at least minWords
+        napi_value v; napi_valuetype t; napi_get_element(env, a.argv[1], i, &v); napi_typeof(env, v, &t);
+        if (optional && (t == napi_undefined || t == napi_null)) return nullptr;
+        bool is = false; napi_is_typedarray(env, v, &is);
+        napi_typedarray_type ty = napi_int8_array; size_t n = 0; void *data = nullptr; napi_value ab; size_t off;
+        if (is) napi_get_typedarray_info(env, v, &ty, &n, &data, &ab, &off);
+        if (!is || (ty != napi_biguint64_array && ty != napi_bigint64_array)) { a.fail("expected a BigUint64Array"); return nullptr; }
+        if (n < minWords) { a.fail("buffer too small"); return nullptr; }
+        return (uint64_t *)data;
+    };
+    for (uint64_t s = 0; s <= m.nF && a.ok; s++) {
+        pil2gl_tuple_side &x = m.side[s];
+        x.base = words((uint32_t)(2 * s), tuple_span(m.n, x.stride, x.hostCols, m.k, ew), false);
+        x.sel = a.ok ? words((uint32_t)(2 * s + 1), tuple_span(m.n, x.selStride, &x.selCol, 1, ew), true) : nullptr;
+    }
+    uint64_t *hm = a.ok ? words((uint32_t)(2 * (1 + m.nF)), tuple_span(m.n, m.d[MD_M_STRIDE], m.d + MD_M_COL, 1, ew), false) : nullptr;
+    if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_lookup_mult : pil2gl_lookup_mult)(m.side + 1, m.nF, m.side, hm, m.d[MD_M_STRIDE], m.d[MD_M_COL], m.n, m.k, rep));
+    return mk_undefined(env);
+}
+FN(LookupMultProbe) { return mk_bigint(env, pil2gl_debug_lookup_mult_probe()); }
+
 // ---- BN128 Merkle commitment (merklehash_bn128_p.js / merklehash_bn128_worker.js) ----
 FN(Bn128Poseidon) {  // (in BigUint64Array(4*nIn*count) normal form, init BigUint64Array(4*count)|null, count, nIn, nOut, out(4*nOut*count))
     Args a(env, info); uint64_t count = a.u64(2), nIn = a.u64(3), nOut = a.u64(4);
@@ -857,6 +925,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "connPlan", ConnPlan }, { "connPolsDev", ConnPolsDev }, { "bn128ConnPolsDev", Bn128ConnPolsDev }, { "connPols", ConnPols }, { "bn128ConnPols", Bn128ConnPols },
         { "connCheckPlan", ConnCheckPlan }, { "connCheckDev", ConnCheckDev }, { "bn128ConnCheckDev", Bn128ConnCheckDev }, { "connCheck", ConnCheck }, { "bn128ConnCheck", Bn128ConnCheck },
         { "tupleCheckPlan", TupleCheckPlan }, { "tupleCheckDev", TupleCheckDev }, { "tupleCheck", TupleCheck }, { "tupleHome", TupleHome }, { "tupleCheckProbe", TupleCheckProbe },
+        { "lookupMultPlan", LookupMultPlan }, { "lookupMultDev", LookupMultDev }, { "lookupMult", LookupMult }, { "lookupMultProbe", LookupMultProbe },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },

@@ -12,6 +12,13 @@
 //      kinds 1 and 2, "t" for kind 3; message() reads the reported row's k elements back, and only when it is called
 //   formatReport(report, values, name)   the message from the five words and the tuple's values as decimal strings
 //   tupleHome(words, k, capacity, bn128), tupleCheckProbe()   the library's two debug entries
+// and the multiplicity column a pil2 grand sum needs to PROVE the lookups `selF_s {f_s} in selT {t}` (csrc/lookup_mult.hip):
+//   lookupMultiplicities(fs, t, m, n, opts) / lookupMultiplicitiesDev(fs, t, m, n, opts)
+//       fs: 1 .. 8 sides as above, t: one side, m: { buf, stride, col } -- the column written, for every row j < n: how many selected rows of
+//       all fs hold the tuple of row j of t, at the tuple's first selected row of t, 0 elsewhere; m may be a spare column of t's or an f's buffer
+//   -> { matched, missing: null | { side, row, message() } }: matched = the selected f rows whose tuple t holds (the sum of m); missing = the
+//      smallest (side, row) of f whose tuple no selected row of t holds; m is written in full either way
+//   formatMissing(missing, values)   the message; lookupMultProbe()   the library's debug entry
 // Node 12: no optional chaining.
 "use strict";
 const { addon, DevBuffer, isDev } = require("./native.js");
@@ -96,4 +103,42 @@ function tupleHome(words, k, capacity, bn128) {
 }
 const tupleCheckProbe = () => Number(addon.tupleCheckProbe());
 
-module.exports = { checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };
+// ---- lookup multiplicities ----
+// The wording, once (INTEGRATION.md):
+//   "lookup: f side S row R = (v0, v1, ..) occurs in no selected row of t"
+const formatMissing = (x, values) => "lookup: f side " + x.side + " row " + x.row + " = (" + values.join(", ") + ") occurs in no selected row of t";
+function multiplicities(dev, fsIn, tIn, mIn, n, opts) {
+    const ew = opts && opts.bn128 ? 4 : 1;
+    if (!Array.isArray(fsIn) || fsIn.length < 1 || fsIn.length > 8) throw new Error("fs must be an array of 1 .. 8 sides");
+    if (!mIn || !(mIn.stride > 0) || !(mIn.col >= 0)) throw new Error("m must be { buf, stride, col }");
+    const t = side(tIn, "t", n, ew, dev), fs = fsIn.map((f, s) => side(f, "f " + s, n, ew, dev)), k = t.cols.length;
+    fs.forEach((f, s) => { if (f.cols.length !== k) throw new Error("t has " + k + " columns and f " + s + " " + f.cols.length); });
+    const m = side({ buf: mIn.buf, stride: mIn.stride, cols: [mIn.col] }, "m", n, ew, dev);
+    const sides = [t].concat(fs), ptr = (b) => dev && b ? b.ptr : 0n;
+    const head = [n, k, fs.length, ptr(m.buf), m.stride, mIn.col];
+    const six = sides.map((x) => [ptr(x.buf), x.stride, 0].concat(x.sel ? [ptr(x.sel.buf), x.sel.stride, x.sel.col] : [0n, 0, 0]));
+    const desc = BigUint64Array.from(head.concat(...six, ...sides.map((x) => x.cols)).map((v) => BigInt(v)));
+    const rep = new BigUint64Array(4);
+    let read;
+    if (!dev) {
+        addon.lookupMult(desc, [].concat(...sides.map((x) => [x.buf, x.sel ? x.sel.buf : null]), [m.buf]), rep, ew);
+        if (m.buf.buffer !== mIn.buf.buffer) new Uint8Array(mIn.buf.buffer, mIn.buf.byteOffset, mIn.buf.byteLength).set(new Uint8Array(m.buf.buffer));      // bytes off 8: asWords copied
+        read = (buf, at, len) => buf.subarray(at, at + len);
+    } else {
+        const plan = addon.lookupMultPlan(n, k, fs.length, ew);
+        const work = new DevBuffer(Math.max(2, plan.scratchBytes / 8));
+        try { addon.lookupMultDev(desc, work.ptr, plan.scratchBytes, rep, ew); } finally { work.free(); }
+        read = (buf, at, len) => buf.slice(at, at + len);
+    }
+    const out = { matched: Number(rep[3]), missing: null };
+    if (rep[0] !== 0n) {
+        const x = out.missing = { side: Number(rep[1]), row: Number(rep[2]) };
+        x.message = () => { const f = fs[x.side]; return formatMissing(x, f.cols.map((c) => decimalOf(read(f.buf, (x.row * f.stride + c) * ew, ew)))); };
+    }
+    return out;
+}
+const lookupMultiplicities = (fs, t, m, n, opts) => multiplicities(false, fs, t, m, n, opts);
+const lookupMultiplicitiesDev = (fs, t, m, n, opts) => multiplicities(true, fs, t, m, n, opts);
+const lookupMultProbe = () => Number(addon.lookupMultProbe());
+
+module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };

@@ -51,6 +51,12 @@ class EvalDesc(C.Structure):
                 ("dim", C.c_uint32), ("levIndex", C.c_uint32)]
 
 
+class TupleSide(C.Structure):
+    """include/pil2gl.h pil2gl_tuple_side: one side of a lookup (its matrix, its columns on the host, its selector column or NULL)"""
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_uint64), ("hostCols", C.c_void_p), ("sel", C.c_void_p),
+                ("selStride", C.c_uint64), ("selCol", C.c_uint64)]
+
+
 class G1Poly(C.Structure):
     """include/pil2gl.h pil2gl_g1_poly: one packed polynomial of a G1 commit batch"""
     _fields_ = [("first", C.c_uint64), ("rows", C.c_uint64), ("m", C.c_uint32), ("reserved", C.c_uint32)]
@@ -236,6 +242,12 @@ SIGNATURES = {
     "pil2gl_bn128_tuple_check": (_I, [vp, _U64, vp, vp, _U64, vp, vp, _U64, _U64, vp, _U64, _U64, _U64, _U64, _U32, vp]),
     "pil2gl_debug_tuple_home": (_U64, [vp, _U64, _U32, _U64]),
     "pil2gl_debug_tuple_check_probe": (_U64, []),
+    "pil2gl_lookup_mult_plan": (_I, [_U64, _U64, _U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_lookup_mult_dev": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), vp, _U64, _U64, _U64, _U64, vp, _U64, vp, vp]),
+    "pil2gl_bn128_lookup_mult_dev": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), vp, _U64, _U64, _U64, _U64, vp, _U64, vp, vp]),
+    "pil2gl_lookup_mult": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), vp, _U64, _U64, _U64, _U64, vp]),
+    "pil2gl_bn128_lookup_mult": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), vp, _U64, _U64, _U64, _U64, vp]),
+    "pil2gl_debug_lookup_mult_probe": (_U64, []),
     "pil2gl_selftest_field":(_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_ext": (_I, [vp, vp, _U64, vp, vp]),
     "pil2gl_selftest_products": (_I, [vp, vp, _U64, vp, vp, vp]),

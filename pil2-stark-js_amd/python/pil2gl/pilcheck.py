@@ -10,6 +10,9 @@ A matrix is (rows, stride) uint64 words over Goldilocks and (rows, stride, 4) Mo
 cols are element offsets within a row, in the tuple's order; a selector is (matrix, col) or (matrix, col, stride), or None.  Every form
 returns the library's five words (kind, row, partner, cntF, cntT) -- include/pil2gl.h states them; a clean trace gives
 (0, NONE, NONE, 0, 0).  No arithmetic happens here: hashing, counting and judging are the library's.
+
+The column that PROVES a lookup in pil2, the multiplicities of its grand sum (csrc/lookup_mult.hip), is lookup_mult / lookup_mult_dev at the
+end of this module.
 """
 import ctypes as C
 
@@ -117,3 +120,66 @@ def lookup_check_dev(f, f_cols, t, t_cols, n, field="gl", f_stride=None, t_strid
 def perm_check_dev(f, f_cols, t, t_cols, n, field="gl", f_stride=None, t_stride=None, sel_f=None, sel_t=None):
     """perm_check on device tensors"""
     return _check(PERMUTATION, True, f, f_cols, t, t_cols, n, field, f_stride, t_stride, sel_f, sel_t)
+
+
+# ---- lookup multiplicities: the logUp column m of `selF_s {f_s} in selT {t}` (csrc/lookup_mult.hip) ----
+#     rep = lookup_mult_dev([(cm1, [7, 3]), (cm1, [4, 5], (cm1, 9))], (cm1, [0, 1]), (cm1, 12), n)
+# A side is (matrix, cols), (matrix, cols, sel) or (matrix, cols, sel, stride) with sel a selector as above or None; m is (matrix, col) or
+# (matrix, col, stride) and may be a spare column of t's or of an f's matrix.  The column is written in place -- the host form takes m's
+# matrix as a C-contiguous uint64 array -- and the four words (kind, side, row, matched) come back; clean is (0, NONE, NONE, matched).
+def lookup_mult_plan(n, k, n_f=1, field="gl"):
+    """pil2gl_lookup_mult_plan (host-only): the hash table's capacity, the launch geometry, the working buffer"""
+    info = (C.c_uint32 * 6)()
+    nbytes = C.c_uint64()
+    call("pil2gl_lookup_mult_plan", n, k, n_f, _WORDS[field], info, C.byref(nbytes))
+    names = ("capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes")
+    return dict(zip(names, (int(x) for x in info)), scratchBytes=nbytes.value)
+
+
+def lookup_mult_probe():
+    """pil2gl_debug_lookup_mult_probe: the longest distance between a tuple of the last call's hash table and its home slot"""
+    return int(load().pil2gl_debug_lookup_mult_probe())
+
+
+def _mult(dev, fs, t, m, n, field):
+    from ._lib import TupleSide
+    words = _WORDS[field]
+    ptr = (lambda a: _ptr(a)) if dev else (lambda a: None if a is None else a.ctypes.data)
+    keep = []                                                                    # the column arrays live until the call returns
+
+    def struct(spec, what):
+        spec = tuple(spec) + (None,) * (4 - len(spec))
+        b, stride, cols, sm, sstride, scol = _side(spec[0], spec[1], spec[3], spec[2], n, words, dev, what)
+        keep.extend((b, cols, sm))
+        return TupleSide(ptr(b), stride, cols.ctypes.data, ptr(sm), sstride, scol), cols.size
+    sides = [struct(s, "f %d" % i) for i, s in enumerate(fs)]
+    T, k = struct(t, "t")
+    if any(kk != k for _, kk in sides):
+        raise Pil2glError("t has %d columns, every f must have as many" % k)
+    if not dev and not (isinstance(m[0], np.ndarray) and m[0].dtype == np.uint64 and m[0].flags.c_contiguous and m[0].flags.writeable):
+        raise Pil2glError("m: the host form writes in place and takes a C-contiguous writeable uint64 array")
+    mm, held, mstride = _matrix(m[0], m[2] if len(m) > 2 else None, words, dev, "m")
+    if n and held < ((n - 1) * mstride + m[1] + 1) * words:
+        raise Pil2glError("m holds %d words, %d rows of stride %d need more" % (held, n, mstride))
+    F = (TupleSide * max(len(sides), 1))(*[s for s, _ in sides])
+    rep = (C.c_uint64 * 4)()
+    name = "pil2gl_lookup_mult" if words == 1 else "pil2gl_bn128_lookup_mult"
+    args = [F, len(sides), C.byref(T), ptr(mm), mstride, m[1], n, k]
+    if dev:
+        plan = lookup_mult_plan(n, k, min(max(len(sides), 1), 8), field)
+        work = torch.empty(max(plan["scratchBytes"] // 8, 2), dtype=torch.int64, device=mm.device)
+        call(name + "_dev", *args, _ptr(work), plan["scratchBytes"], rep, _stream())
+    else:
+        call(name, *args, rep)
+    return tuple(int(x) for x in rep)
+
+
+def lookup_mult(fs, t, m, n, field="gl"):
+    """the multiplicity column of the lookups `f_s in t`: host matrices; m's column is written in place -> (kind, side, row, matched)"""
+    return _mult(False, fs, t, m, n, field)
+
+
+def lookup_mult_dev(fs, t, m, n, field="gl"):
+    """lookup_mult on device tensors, e.g. columns of the stage-1 buffer with m one more column of it; the working buffer comes from the
+    plan and lives for the call; blocks for the report"""
+    return _mult(True, fs, t, m, n, field)
