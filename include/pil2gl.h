@@ -391,13 +391,25 @@ int pil2gl_first_nonzero_row_dev(const uint64_t *col, uint32_t dim, uint64_t fir
  * calculateZ(F,num,den)  polutils.js:128-143: out[0] = 1, out[i] = out[i-1]*num[i-1]/den[i-1]   (num, den: n rows)
  * calculateS(F,num,den)  polutils.js:145-164: out[i] = out[i-1] + num/den[i]                    (num: ONE element)
  * dimNum/dimDen in {1,3} (base or cubic-extension columns, row-major); out has dimension 3 if either has, else 1.
- * A zero denominator yields 0 for that ratio (the reference's batchInverse would poison the whole column). */
+ * A zero denominator yields 0 for that ratio (the reference's batchInverse would poison the whole column).
+ * out must not overlap num or den. */
 int pil2gl_gprod_dev(const uint64_t *num, uint32_t dimNum, const uint64_t *den, uint32_t dimDen, uint64_t n, uint64_t *out, void *stream);
 int pil2gl_gsum_dev(const uint64_t *num, uint32_t dimNum, const uint64_t *den, uint32_t dimDen, uint64_t n, uint64_t *out, void *stream);
 /* calculateH1H2(F,f,t)  polutils.js:105-126: the multiset f (every value must occur in t) merged into t; h1[i], h2[i] =
  * entries 2i, 2i+1 of the merged sequence.  f, t, h1, h2: n rows of dimension dim (1 or 3).  Returns PIL2GL_EINVAL with
- * the reference's "Number not included" message when some f[j] is missing from t (synchronises the stream). */
+ * the reference's "Number not included" message when some f[j] is missing from t (synchronises the stream).
+ * h1 and h2 must not overlap f, t or each other. */
 int pil2gl_h1h2_dev(const uint64_t *f, const uint64_t *t, uint64_t n, uint32_t dim, uint64_t *h1, uint64_t *h2, void *stream);
+/* host-only, no device: how the three calls above run n rows (csrc/hint_plan.h).  outInfo[0] = lanes of a workgroup of the scan;
+ * [1] = consecutive rows a lane takes (it inverts their denominators together); [2] = rows a block, [0] [1]; [3] = blocks of the first
+ * pass, ceil(n / [2]); [4] = block totals a lane of the second pass (ONE workgroup) walks, ceil([3] / [0]); [5] = log2 of the capacity of
+ * pil2gl_h1h2_dev's hash table, the smallest power of two >= 2 n and >= 2, or 0 for n > 2^30, which that call refuses.
+ * PIL2GL_EINVAL: more than 2^31 - 1 blocks. */
+int pil2gl_debug_hint_plan(uint64_t n, uint32_t *outInfo /* [6] */);
+/* host-only, no device: the home slot of a key of pil2gl_h1h2_dev in a table of `capacity` slots (a power of two), from the one hash
+ * function host and device share: words = dim CANONICAL 64-bit words.  UINT64_MAX for a dim other than 1 or 3, a capacity that is no
+ * power of two, null words. */
+uint64_t pil2gl_debug_h1h2_home(const uint64_t *words, uint32_t dim, uint64_t capacity);
 
 /* ---- BN128 (BN254 scalar field) Merkle commitment: merklehash_bn128_p.js, merklehash_bn128_worker.js -------------
  * Field elements are 4 little-endian u64 words.  tree.nodes and leaf digests are in MONTGOMERY form (R = 2^256), exactly

@@ -8,13 +8,15 @@
 // extension (dim 3) columns, row-major; the result is dim 3 if either operand is, else dim 1.
 #include "common.h"
 #include "gl_field.cuh"
+#include "hint_plan.h"
 
 using namespace gl;
 using namespace pil2gl;
+using hintplan::SCAN_THREADS;
+using hintplan::SCAN_ITEMS;
+using hintplan::SCAN_CHUNK;
 
 namespace {
-
-constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 8, SCAN_CHUNK = SCAN_THREADS * SCAN_ITEMS;
 
 __device__ __forceinline__ E3 ld_dim(const u64 *p, u64 i, u32 dim) { return dim == 3 ? E3{ { p[3 * i], p[3 * i + 1], p[3 * i + 2] } } : E3{ { p[i], 0, 0 } }; }
 __device__ __forceinline__ void st3(u64 *p, u64 i, const E3 &v) { p[3 * i] = v.v[0]; p[3 * i + 1] = v.v[1]; p[3 * i + 2] = v.v[2]; }
@@ -92,7 +94,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) hint_scan1(const u64 *__restrict
 template <bool PROD>
 __global__ void __launch_bounds__(SCAN_THREADS) hint_scan2(u64 *__restrict__ totals, u64 nb) {
     __shared__ E3 sh[SCAN_THREADS];
-    const u64 per = (nb + SCAN_THREADS - 1) / SCAN_THREADS, b0 = (u64)threadIdx.x * per;
+    const u64 per = hintplan::totals_per_lane(nb), b0 = (u64)threadIdx.x * per;
     E3 run = ident<PROD>();
     for (u64 k = 0; k < per; k++) { const u64 i = b0 + k; if (i < nb) run = comb<PROD>(run, ld_dim(totals, i, 3)); }
     E3 bt;
@@ -120,7 +122,7 @@ int run_hint(const u64 *num, u32 dimNum, const u64 *den, u32 dimDen, u64 n, u64 
     if (n == 0) return PIL2GL_OK;
     if (!num || !den || !out) return fail(PIL2GL_EINVAL, "null buffer");
     if ((dimNum != 1 && dimNum != 3) || (dimDen != 1 && dimDen != 3)) return fail(PIL2GL_EINVAL, "dimensions must be 1 or 3");
-    const u64 nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    const u64 nb = hintplan::blocks(n);
     if (nb > 0x7fffffffull) return fail(PIL2GL_EINVAL, "grid too large");
     u64 *tmp, *totals;
     P2_TRY(scratch(SCR_HINT_TMP, n * 3, &tmp));
@@ -160,11 +162,7 @@ namespace {
 
 constexpr u64 H_EMPTY = ~0ull;
 
-__device__ __forceinline__ u64 key_hash(const u64 *p, u64 i, u32 dim) {
-    u64 h = 0x9E3779B97F4A7C15ull;
-    for (u32 k = 0; k < dim; k++) { h ^= p[i * dim + k] + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 31; }
-    return h;
-}
+__device__ __forceinline__ u64 key_hash(const u64 *p, u64 i, u32 dim) { return hintplan::key_hash(p + i * dim, dim); }
 __device__ __forceinline__ bool key_eq(const u64 *a, u64 i, const u64 *b, u64 j, u32 dim) {
     for (u32 k = 0; k < dim; k++) if (a[i * dim + k] != b[j * dim + k]) return false;
     return true;
@@ -242,15 +240,15 @@ extern "C" int pil2gl_h1h2_dev(const uint64_t *f, const uint64_t *t, uint64_t n,
     if (n == 0) return PIL2GL_OK;
     if (!f || !t || !h1 || !h2) return fail(PIL2GL_EINVAL, "null buffer");
     if (dim != 1 && dim != 3) return fail(PIL2GL_EINVAL, "dimension must be 1 or 3");
-    if (n > (1ull << 30)) return fail(PIL2GL_EINVAL, "column too long");
+    if (n > hintplan::H1H2_MAX_N) return fail(PIL2GL_EINVAL, "column too long");
     hipStream_t st = as_stream(stream);
-    u64 cap = 2; while (cap < 2 * n) cap <<= 1;
-    const u64 nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    u64 *ws;                                             // table[cap] | cnt[n] | start[n] | totals[nb] | missing[1]
-    P2_TRY(scratch(SCR_HINT_WORK, cap + 2 * n + nb + 1, &ws));
-    unsigned long long *table = (unsigned long long *)ws, *cnt = table + cap;
-    u64 *start = ws + cap + n, *totals = start + n;
-    unsigned long long *missing = (unsigned long long *)(totals + nb);
+    const hintplan::H1H2Work w = hintplan::h1h2_work(n);  // table[cap] | cnt[n] | start[n] | totals[nb] | missing[1]
+    const u64 cap = w.capacity, nb = hintplan::blocks(n);
+    u64 *ws;
+    P2_TRY(scratch(SCR_HINT_WORK, w.words, &ws));
+    unsigned long long *table = (unsigned long long *)(ws + w.offTable), *cnt = (unsigned long long *)(ws + w.offCnt);
+    u64 *start = ws + w.offStart, *totals = ws + w.offTotals;
+    unsigned long long *missing = (unsigned long long *)(ws + w.offMissing);
     HIP_TRY(hipMemsetAsync(table, 0xFF, cap * 8, st));
     HIP_TRY(hipMemsetAsync(cnt, 0, n * 8, st));
     HIP_TRY(hipMemsetAsync(missing, 0xFF, 8, st));
@@ -273,3 +271,23 @@ extern "C" int pil2gl_h1h2_dev(const uint64_t *f, const uint64_t *t, uint64_t n,
     if (miss != H_EMPTY) return fail(PIL2GL_EINVAL, "Number not included: w:%llu", miss);     // polutils.js:115
     return PIL2GL_OK;
 }
+
+extern "C" {
+
+int pil2gl_debug_hint_plan(uint64_t n, uint32_t *outInfo) {
+    const u64 nb = hintplan::blocks(n);
+    if (nb > 0x7fffffffull) return fail(PIL2GL_EINVAL, "grid too large");
+    if (outInfo) {
+        outInfo[0] = SCAN_THREADS; outInfo[1] = SCAN_ITEMS; outInfo[2] = SCAN_CHUNK; outInfo[3] = (uint32_t)nb;
+        outInfo[4] = (uint32_t)hintplan::totals_per_lane(nb);
+        outInfo[5] = n <= hintplan::H1H2_MAX_N ? hintplan::h1h2_capacity_bits(n) : 0;
+    }
+    return PIL2GL_OK;
+}
+
+uint64_t pil2gl_debug_h1h2_home(const uint64_t *words, uint32_t dim, uint64_t capacity) {
+    if (!words || (dim != 1 && dim != 3) || !capacity || (capacity & (capacity - 1))) return hintplan::NONE;
+    return hintplan::h1h2_home(words, dim, capacity);
+}
+
+}  // extern "C"

@@ -228,6 +228,29 @@ def calculateH1H2(f, t, dim=1):
     return h1, h2
 
 
+HINT_PLAN = ("threads", "items", "chunk", "blocks", "totalsPerLane", "h1h2CapBits")
+
+
+def hint_plan(n):
+    """pil2gl_debug_hint_plan (no device): how calculateZ / calculateS / calculateH1H2 run n rows -> {threads (lanes of a workgroup), items
+    (rows a lane), chunk (rows a block), blocks, totalsPerLane (block totals a lane of the second pass walks), h1h2CapBits (log2 of the
+    hash table's capacity; 0 above 2^30 rows)}"""
+    info = (C.c_uint32 * 6)()
+    call("pil2gl_debug_hint_plan", n, info)
+    return dict(zip(HINT_PLAN, (int(v) for v in info)))
+
+
+def h1h2_home(words, dim, capacity):
+    """pil2gl_debug_h1h2_home (host-only): the home slot of a key of calculateH1H2, dim CANONICAL words, in a table of `capacity` slots"""
+    w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if w.size != dim:
+        raise Pil2glError("h1h2_home: a key is dim words")
+    home = int(load().pil2gl_debug_h1h2_home(C.c_void_p(w.ctypes.data), dim, capacity))
+    if home == 0xFFFFFFFFFFFFFFFF:
+        raise Pil2glError("h1h2_home: dim is 1 or 3 and the capacity a power of two")
+    return home
+
+
 def firstNonZeroRow(col, dim, first, last):
     """the device half of calculateExps(ctx, code, dom, debug = true) (prover_helpers.js:46-70): the first row of [first, last) where a
     constraint's value column (dim 1 or 3 words per row, device buffer) is not zero -> (row, [value words]) or None"""
