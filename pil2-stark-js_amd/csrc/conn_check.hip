@@ -4,23 +4,19 @@
 // every S[c] must be id(c') of exactly one cell c', and a[c] must equal a[c'], both as field values.
 //   tables   hi[t] = w^(t 2^loBits), lo[j][t] = w^t ks'[j]: conn_pols.hip's two-level tables, a lane per entry, so that id(c) is ONE product
 //            for any cell (about sqrt N entries a column, no N-element table, no serial chain, no discrete logarithm).
-//   build    a lane per cell: key = id(c), slot = hash(key) & mask, linear probing over a table of 32-bit cell indices (conn_check_plan.h:
-//            capacity >= 2 cells).  An EMPTY slot is claimed by atomicCAS; a slot whose cell has the SAME identity (the key is re-derived
-//            from the cell, one product) takes the smaller cell by atomicMin and the larger of the two lowers the duplicate cell.  Whatever
-//            the order of arrival some lane of a group reports the group's second smallest cell and none reports a smaller one, so the
-//            minimum over groups is the first cell, in flat order, whose identity an earlier cell already has.
+//   build    a lane per cell puts it into the index table (index_table.cuh) under the key id(c), re-derived from a cell by one product.  A
+//            cell that meets another of its identity lowers the duplicate cell to the larger of the two: by the table's argument the
+//            minimum over all cells is the first cell, in flat order, whose identity an earlier cell already has.
 //   check    Goldilocks a lane a cell, Fr two neighbouring lanes a cell, each moving one 16-byte half (wtns_exec.hip's gather): reduce S[c],
 //            probe, compare a[c] with a[c'] after reducing both; the smallest failing cell by the wave-minimum rule, one atomic a wave.
 //   finish   one workgroup, one lane: partner and kind are recomputed for the winning cell alone, so the three words describe one cell.
 // Goldilocks: words in [p, 2^64) count as their value mod p.  Fr: Montgomery words, any 256-bit pattern counting as its value mod r.
 //
-// Safety: nothing read from S or a is used as an address.  A slot's content is checked against the cell count before it addresses the
-// tables or a; every probe loop runs at most `capacity` times whatever the data.  Plain vector stores and global atomics only.
-// Shared: the bad-cell report, the cell walk and the fields as template parameters (smap_cells.cuh); grid and overlap test (smap_plan.h);
-// the table shapes (conn_plan.h).  The key mixing is bn_h1h2.hip's (32-bit multiplies, murmur3's finaliser), run twice with other seeds
-// because the table may have more than 2^32 slots.
+// Safety: nothing read from S or a is used as an address; a slot's content addresses the tables or a only below the cell count (the hash
+// table's `limit`).  Shared: the hash table (index_table.cuh); the bad-cell report, the cell walk and the fields as template parameters
+// (smap_cells.cuh); grid and overlap test (smap_plan.h); the table shapes (conn_plan.h).
 #include "common.h"
-#include "smap_cells.cuh"
+#include "index_table.cuh"
 #include "conn_check_plan.h"
 #include <string.h>
 
@@ -28,11 +24,10 @@ using namespace pil2gl;
 
 namespace {
 
-using namespace smapcells;
+using namespace indextable;
 using namespace smapplan;
 using namespace conncheckplan;
 
-constexpr u32 EMPTY = 0xFFFFFFFFu;
 uint64_t g_lastProbe = 0;                            // the longest displacement of the last build (pil2gl_debug_conn_check_probe)
 
 template <class F> struct Consts { typename F::Elem w, ks[connplan::MAX_COLS]; };       // w and ks' as the caller gave them, a kernel argument
@@ -43,26 +38,6 @@ template <class F> struct Table {
     const typename F::Mem *hi, *lo;
 };
 
-// ---- what the two fields do not share: equality of canonical elements and their limbs for the hash ----
-__device__ __forceinline__ bool same(u64 a, u64 b) { return a == b; }
-__device__ __forceinline__ bool same(const FrField::Elem &a, const FrField::Elem &b) {
-    return ((a.v[0] ^ b.v[0]) | (a.v[1] ^ b.v[1]) | (a.v[2] ^ b.v[2]) | (a.v[3] ^ b.v[3]) |
-            (a.v[4] ^ b.v[4]) | (a.v[5] ^ b.v[5]) | (a.v[6] ^ b.v[6]) | (a.v[7] ^ b.v[7])) == 0;
-}
-template <int LIMBS> __device__ __forceinline__ u64 mix(const u32 (&w)[LIMBS]) {
-    u32 h = 0x9E3779B9u, g = 0x7F4A7C15u;
-#pragma unroll
-    for (int i = 0; i < LIMBS; i++) {
-        h = (h ^ w[i]) * 0x85EBCA6Bu; h ^= h >> 15;
-        g = (g ^ w[i]) * 0xC2B2AE35u; g ^= g >> 13;
-    }
-    h *= 0xC2B2AE35u; h ^= h >> 16;
-    g *= 0x85EBCA6Bu; g ^= g >> 16;
-    return ((u64)g << 32) | h;
-}
-__device__ __forceinline__ u64 key_hash(u64 k) { const u32 w[2] = { (u32)k, (u32)(k >> 32) }; return mix(w); }
-__device__ __forceinline__ u64 key_hash(const FrField::Elem &k) { return mix(k.v); }
-
 // id of a cell below t.cells: one product of two table entries
 template <class F> __device__ __forceinline__ typename F::Elem id_of(const Table<F> &t, u32 cell) {
     const u32 i = cell / t.nCols, j = cell - i * t.nCols;
@@ -71,13 +46,7 @@ template <class F> __device__ __forceinline__ typename F::Elem id_of(const Table
 
 // the cell whose identity is the canonical `key`, EMPTY when there is none; after the build
 template <class F> __device__ __forceinline__ u32 lookup(const Table<F> &t, const typename F::Elem &key) {
-    u64 s = key_hash(key) & t.mask;
-    for (u64 probe = 0; probe <= t.mask; probe++, s = (s + 1) & t.mask) {
-        const u32 cur = t.slots[s];
-        if (cur >= t.cells) return EMPTY;            // an empty slot ends the run
-        if (same(key, id_of(t, cur))) return cur;
-    }
-    return EMPTY;
+    return find<1>(t.slots, t.mask, hash_of(key), t.cells, [&](u32 cur) { return same(key, id_of(t, cur)); }).met;
 }
 
 // ---- tables: conn_pols.hip's, lo[j][t] = w^t ks'[j] and hi[t] = w^(t 2^loBits) ----
@@ -100,28 +69,15 @@ __global__ void __launch_bounds__(THREADS) cc_build_kernel(Table<F> t, unsigned 
     u32 longest = 0;
     for (u64 c = (u64)blockIdx.x * THREADS + threadIdx.x; c < t.cells; c += (u64)gridDim.x * THREADS) {
         const typename F::Elem key = id_of(t, (u32)c);
-        u64 s = key_hash(key) & t.mask;
-        for (u64 probe = 0; probe <= t.mask; probe++, s = (s + 1) & t.mask) {
-            u32 cur = t.slots[s];
-            if (cur == EMPTY) {
-                cur = atomicCAS(&t.slots[s], EMPTY, (u32)c);
-                if (cur == EMPTY) {                                          // claimed, `probe` slots past its home
-                    const u32 d = probe > EMPTY ? EMPTY : (u32)probe;
-                    longest = d > longest ? d : longest;
-                    break;
-                }
-            }
-            if (cur < t.cells && same(key, id_of(t, cur))) {                 // the same identity: the slot keeps the smaller cell
-                const u32 old = atomicMin(&t.slots[s], (u32)c);
-                const u64 larger = old > c ? old : c;
-                dup = larger < dup ? larger : dup;
-                break;
-            }
+        const Hit h = insert<1>(t.slots, t.mask, hash_of(key), (u32)c, t.cells, [&](u32 cur) { return same(key, id_of(t, cur)); });
+        longest = h.displaced > longest ? h.displaced : longest;
+        if (h.met != EMPTY) {                                                // another cell of this identity: the larger of the two
+            const u64 larger = h.met > c ? h.met : c;
+            dup = larger < dup ? larger : dup;
         }
     }
     report_bad(dup, hdr + H_DUP);
-    for (int o = 32; o > 0; o >>= 1) { const u32 other = __shfl_xor(longest, o, 64); longest = other > longest ? other : longest; }
-    if ((threadIdx.x & 63) == 0 && longest) atomicMax(hdr + H_PROBE, (unsigned long long)longest);
+    report_probe(longest, hdr + H_PROBE);
 }
 
 // ---- check ----

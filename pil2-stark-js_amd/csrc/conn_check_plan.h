@@ -1,9 +1,9 @@
 // Host-only half of the connection check (conn_check.hip): what the entries refuse, the capacity of the hash table, the launch geometry and
 // where every part of the working buffer lies.  No HIP header: it builds with the plain C++ compiler (tests/conn_check_plan_dump.cpp runs
-// it under the sanitizers).  The limits are conn_plan.h's, the grid and the overlap test smap_plan.h's.
+// it under the sanitizers).  The limits are conn_plan.h's, the grid and the overlap test smap_plan.h's, the table's capacity
+// index_table_plan.h's.
 //
-// The table: open addressing, linear probing, one 32-bit cell index a slot (EMPTY = 2^32 - 1; a cell stays below 2^32 - 1), capacity the
-// smallest power of two >= 2 cells and >= MIN_CAPACITY: the load factor never exceeds 1 / 2, whatever the shape.
+// The table: one 32-bit cell index a slot (a cell stays below 2^32 - 1 = EMPTY), capacity for N nCols cells.
 // The working buffer, every part on 16 bytes, cells = N nCols, T = nCols 2^loBits + 2^hiBits table elements:
 //   HEADER_BYTES             the report's three words, the longest probe of the build, the check's smallest failing cell, the build's
 //                            smallest cell that shares its identity with a smaller one (six u64, the rest unused)
@@ -13,12 +13,12 @@
 #pragma once
 #include <stdint.h>
 #include "conn_plan.h"
+#include "index_table_plan.h"
 
 namespace conncheckplan {
 
 using smapplan::THREADS;
 constexpr uint64_t HEADER_BYTES = 64;
-constexpr uint64_t MIN_CAPACITY = 16;
 constexpr uint32_t LAUNCHES = 4;                     // tables, build, check, finish
 // the header's words
 enum : uint32_t { H_CELL = 0, H_PARTNER = 1, H_KIND = 2, H_PROBE = 3, H_FAIL = 4, H_DUP = 5 };
@@ -57,9 +57,8 @@ inline Plan plan(uint64_t N, uint64_t nCols, uint32_t elemWords) {
     while ((1ull << p.nBits) < N) p.nBits++;
     p.loBits = (p.nBits + 1) / 2;
     p.hiBits = p.nBits - p.loBits;
-    p.capacity = MIN_CAPACITY;
-    while (p.capacity < 2 * p.cells) p.capacity <<= 1;
-    while ((1ull << p.capBits) < p.capacity) p.capBits++;
+    const indextable::Capacity c = indextable::capacity_for(p.cells);
+    p.capacity = c.slots; p.capBits = c.bits;
     p.lanesPerCell = elemWords == 4 ? 2 : 1;
     p.buildBlocks = smapplan::blocks(p.cells);
     p.checkBlocks = smapplan::blocks(p.cells * p.lanesPerCell);

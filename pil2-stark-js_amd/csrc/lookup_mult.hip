@@ -2,12 +2,11 @@
 // pil2 grand sum  sum selF / (f + gamma) - sum m / (t + gamma) = 0  needs: m[j] = how many selected rows of all f sides hold the tuple of
 // row j of t, written at the tuple's smallest selected row of t, 0 at every other row.  The statement is include/pil2gl.h's;
 // tests/lookup_mult_ref.py restates it as one dictionary.  tuple_check.hip says whether the lookup holds; this unit produces what proves it.
-//   the table  open addressing, linear probing over t's selected rows only.  A slot is 8 bytes: the tuple's smallest selected row of t
-//            (EMPTY = 2^32 - 1), never the key -- the key is re-read from t and reduced -- and beside it, in the same 8 bytes, the counter.
+//   the table  an index table (index_table.cuh) over t's selected rows only, the key a row's tuple, re-read from t and reduced.  Slots lie
+//            two words apart: a slot is 8 bytes, the tuple's smallest selected row of t and beside it the counter.
 //   init     every slot to (EMPTY, 0), the header to (no failing row, 0 matched, probe 0): one launch instead of two memsets, because row and
 //            counter are neighbours and start from different bytes.
-//   build    a lane per row of t: hash the k canonical elements, find or claim the tuple's slot -- atomicCAS claims an EMPTY slot, an equal
-//            tuple lowers the slot's row by atomicMin.  A slot never moves and its row only falls.
+//   build    a lane per row of t puts its row into the table.
 //   count    one launch a side of f, a lane per row: find the tuple's slot; add 1 to its counter, or note the row as failing.  Lanes of a wave
 //            that reached the same slot are merged before the atomic (below).  The wave's smallest failing (side << 32 | row) goes up by
 //            one atomicMin a wave that saw one (smap_cells.cuh report_bad), the wave's matched rows by one atomicAdd.
@@ -21,10 +20,10 @@
 // ONE atomic; lanes left after the rounds add 1 each.  One tuple: one atomic a wave instead of 64 on one address.  All distinct: four
 // rounds of a readlane, a compare and a ballot retire four lanes, the other sixty add as before.  No LDS.
 //
-// Safety: nothing read from f, t or a selector is used as an address.  A slot's row is checked against n before it indexes t; every probe
-// loop runs at most `capacity` times whatever the data.  Plain vector loads and stores and global atomics only.
+// Safety: nothing read from f, t or a selector is used as an address.  A slot's row is checked against n before it indexes t (the table's
+// `limit`).  Plain vector loads and stores and global atomics only.
 #include "common.h"
-#include "smap_cells.cuh"
+#include "tuple_side.cuh"
 #include "lookup_mult_plan.h"
 #include <string.h>
 
@@ -32,17 +31,12 @@ using namespace pil2gl;
 
 namespace {
 
-using namespace smapcells;
+using namespace tupleside;
 using namespace smapplan;
 using namespace lookupmultplan;
-using tuplecheckplan::TupleHash;
 
-constexpr u32 EMPTY = 0xFFFFFFFFu;
 constexpr int MERGE_ROUNDS = 4;
 uint64_t g_lastProbe = 0;                            // the longest displacement of the last build (pil2gl_debug_lookup_mult_probe)
-
-// one side as the kernels take it: the matrix and its k columns, the selector column of a matrix of its own (sel null: every row is selected)
-template <class F> struct Side { const typename F::Mem *base, *sel; u64 stride, selStride, selCol; u32 cols[MAX_K]; };
 
 template <class F> struct Job {
     Side<F> t;
@@ -51,19 +45,6 @@ template <class F> struct Job {
     u64 mask;                                        // capacity - 1
 };
 
-// ---- what the two fields do not share: zero and equality of canonical elements, their limbs for the hash, a count as an element ----
-__device__ __forceinline__ bool is_zero(u64 a) { return a == 0; }
-__device__ __forceinline__ bool is_zero(const FrField::Elem &a) { return bn::is_zero(a.v); }
-__device__ __forceinline__ bool same(u64 a, u64 b) { return a == b; }
-__device__ __forceinline__ bool same(const FrField::Elem &a, const FrField::Elem &b) {
-    return ((a.v[0] ^ b.v[0]) | (a.v[1] ^ b.v[1]) | (a.v[2] ^ b.v[2]) | (a.v[3] ^ b.v[3]) |
-            (a.v[4] ^ b.v[4]) | (a.v[5] ^ b.v[5]) | (a.v[6] ^ b.v[6]) | (a.v[7] ^ b.v[7])) == 0;
-}
-__device__ __forceinline__ void absorb(TupleHash &x, u64 e) { x.absorb((u32)e); x.absorb((u32)(e >> 32)); }
-__device__ __forceinline__ void absorb(TupleHash &x, const FrField::Elem &e) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) x.absorb(e.v[i]);
-}
 // a count below 2^32 in canonical form: itself over Goldilocks, count R mod r over Fr
 template <class F> __device__ __forceinline__ typename F::Elem as_element(u32 c);
 template <> __device__ __forceinline__ u64 as_element<GlField>(u32 c) { return c; }
@@ -74,32 +55,9 @@ template <> __device__ __forceinline__ FrField::Elem as_element<FrField>(u32 c) 
     return FrField::mul(r2, x);
 }
 
-template <class F> __device__ __forceinline__ bool selected(const Side<F> &S, u64 i) {
-    return !S.sel || !is_zero(F::reduce(F::load(S.sel, i * S.selStride + S.selCol)));
-}
-// element j of the tuple of row i, canonical
-template <class F> __device__ __forceinline__ typename F::Elem elem_of(const Side<F> &S, u64 i, u32 j) {
-    return F::reduce(F::load(S.base, i * S.stride + S.cols[j]));
-}
-template <class F> __device__ __forceinline__ bool same_tuple(const Side<F> &A, u64 a, const Side<F> &B, u64 b, u32 k) {
-    for (u32 j = 0; j < k; j++)
-        if (!same(elem_of(A, a, j), elem_of(B, b, j))) return false;
-    return true;
-}
-template <class F> __device__ __forceinline__ u64 home_of(const Job<F> &J, const Side<F> &S, u64 i) {
-    TupleHash x;
-    for (u32 j = 0; j < J.k; j++) absorb(x, elem_of(S, i, j));
-    return x.finish() & J.mask;
-}
 // the slot that holds the tuple of row i of S, NONE when no slot does; after the build.  self: the row itself when S is t, else EMPTY
-template <class F> __device__ __forceinline__ u64 find(const Job<F> &J, const Side<F> &S, u64 i, u32 self) {
-    u64 s = home_of(J, S, i);
-    for (u64 probe = 0; probe <= J.mask; probe++, s = (s + 1) & J.mask) {
-        const u32 cur = J.slots[2 * s];
-        if (cur >= J.n) return NONE;                 // an empty slot ends the run
-        if (cur == self || same_tuple(S, i, J.t, cur, J.k)) return s;
-    }
-    return NONE;
+template <class F> __device__ __forceinline__ u64 find_row(const Job<F> &J, const Side<F> &S, u64 i, u32 self) {
+    return find<2>(J.slots, J.mask, home_of(S, i, J.k, J.mask), J.n, [&](u32 cur) { return cur == self || same_tuple(S, i, J.t, cur, J.k); }).slot;
 }
 
 // ---- init: header and slots ----
@@ -114,26 +72,11 @@ template <class F>
 __global__ void __launch_bounds__(THREADS) lm_build_kernel(Job<F> J, unsigned long long *hdr) {
     u32 longest = 0;
     for (u64 r = (u64)blockIdx.x * THREADS + threadIdx.x; r < J.n; r += (u64)gridDim.x * THREADS) {
-        const u32 idx = (u32)r;
         if (!selected(J.t, r)) continue;
-        u64 s = home_of(J, J.t, r);
-        for (u64 probe = 0; probe <= J.mask; probe++, s = (s + 1) & J.mask) {       // the load factor is at most 1 / 2: it ends by a break
-            u32 cur = J.slots[2 * s];
-            if (cur == EMPTY) {
-                cur = atomicCAS(&J.slots[2 * s], EMPTY, idx);
-                if (cur == EMPTY) {                                                  // claimed, `probe` slots past its home
-                    longest = (u32)probe > longest ? (u32)probe : longest;
-                    break;
-                }
-            }
-            if (cur < J.n && same_tuple(J.t, r, J.t, cur, J.k)) {                    // the same tuple: the slot keeps the smaller row
-                if (idx < cur) atomicMin(&J.slots[2 * s], idx);
-                break;
-            }
-        }
+        const Hit h = insert<2>(J.slots, J.mask, home_of(J.t, r, J.k, J.mask), (u32)r, J.n, [&](u32 cur) { return same_tuple(J.t, r, J.t, cur, J.k); });
+        longest = h.displaced > longest ? h.displaced : longest;
     }
-    for (int o = 32; o > 0; o >>= 1) { const u32 other = __shfl_xor(longest, o, 64); longest = other > longest ? other : longest; }
-    if ((threadIdx.x & 63) == 0 && longest) atomicMax(hdr + H_PROBE, (unsigned long long)longest);
+    report_probe(longest, hdr + H_PROBE);
 }
 
 // one add to the counter of slot s for every lane with `add` set, lanes on one slot merged; every lane of the wave arrives here
@@ -161,7 +104,7 @@ __global__ void __launch_bounds__(THREADS) lm_count_kernel(Job<F> J, Side<F> f, 
     for (u64 first = (u64)blockIdx.x * THREADS; first < J.n; first += (u64)gridDim.x * THREADS) {
         const u64 r = first + threadIdx.x;
         const bool live = r < J.n && selected(f, r);
-        const u64 s = live ? find(J, f, r, EMPTY) : NONE;
+        const u64 s = live ? find_row(J, f, r, EMPTY) : NONE;
         const bool hit = s != NONE;
         if (live && !hit) bad = r < bad ? r : bad;
         matched += hit;
@@ -178,7 +121,7 @@ __global__ void __launch_bounds__(THREADS) lm_write_kernel(Job<F> J, typename F:
     for (u64 r = (u64)blockIdx.x * THREADS + threadIdx.x; r < J.n; r += (u64)gridDim.x * THREADS) {
         u32 c = 0;
         if (selected(J.t, r)) {
-            const u64 s = find(J, J.t, r, (u32)r);
+            const u64 s = find_row(J, J.t, r, (u32)r);
             if (s != NONE && J.slots[2 * s] == (u32)r) c = J.slots[2 * s + 1];
         }
         F::store(m, r * mStride + mCol, as_element<F>(c));
@@ -190,13 +133,6 @@ typedef pil2gl_tuple_side HostSide;
 struct Out { u64 *m; u64 stride, col; };
 
 void clean(u64 *report) { if (report) { report[0] = CLEAN; report[1] = report[2] = NONE; report[3] = 0; } }
-
-template <class F> Side<F> device_side(const HostSide &h, u32 k) {
-    typedef typename F::Mem Mem;
-    Side<F> s{ (const Mem *)h.base, (const Mem *)h.sel, h.stride, h.selStride, h.selCol, {} };
-    for (u32 j = 0; j < k; j++) s.cols[j] = (u32)h.hostCols[j];
-    return s;
-}
 
 // every launch of a call, on st; the arguments have passed the checks.  Blocks for the report.
 template <class F>
@@ -249,11 +185,11 @@ int check_call(const HostSide *f, u64 nF, const HostSide *t, const Out &out, u64
     if (const char *msg = lookupmultplan::check(n, k, nF, words)) return fail(PIL2GL_EINVAL, "%s", msg);
     if (!hostReport) return fail(PIL2GL_EINVAL, "null hostReport");
     if (!f || !t) return fail(PIL2GL_EINVAL, "null sides");
-    if (const char *msg = check_columns(n, t->stride, t->hostCols, k)) return fail(PIL2GL_EINVAL, "t: %s", msg);
-    if (t->sel) if (const char *msg = check_columns(n, t->selStride, &t->selCol, 1)) return fail(PIL2GL_EINVAL, "selT: %s", msg);
+    char why[80];
+    if (check_side("t", *t, n, k, why)) return fail(PIL2GL_EINVAL, "%s", why);
     for (u64 i = 0; i < nF; i++) {
-        if (const char *msg = check_columns(n, f[i].stride, f[i].hostCols, k)) return fail(PIL2GL_EINVAL, "f %llu: %s", (unsigned long long)i, msg);
-        if (f[i].sel) if (const char *msg = check_columns(n, f[i].selStride, &f[i].selCol, 1)) return fail(PIL2GL_EINVAL, "selF %llu: %s", (unsigned long long)i, msg);
+        const char name[4] = { 'f', ' ', (char)('0' + i), 0 };                  // nF <= MAX_SIDES = 8: one digit
+        if (check_side(name, f[i], n, k, why)) return fail(PIL2GL_EINVAL, "%s", why);
     }
     if (const char *msg = check_columns(n, out.stride, &out.col, 1)) return fail(PIL2GL_EINVAL, "m: %s", msg);
     if (!n) return PIL2GL_OK;
@@ -296,19 +232,12 @@ int mult_host(const HostSide *f, u64 nF, const HostSide *t, const Out &out, u64 
     sides[0] = *t;
     for (u64 i = 0; i < nF; i++) sides[1 + i] = f[i];
     const u64 mWords = span_bytes(n, out.stride, out.col, words) / 8;
-    u64 len[1 + MAX_SIDES][2], total = p.bytes / 8 + pad16(mWords);
-    for (u64 i = 0; i <= nF; i++) {
-        len[i][0] = span_bytes(n, sides[i].stride, top_column(sides[i].hostCols, k), words) / 8;
-        len[i][1] = sides[i].sel ? span_bytes(n, sides[i].selStride, sides[i].selCol, words) / 8 : 0;
-        total += pad16(len[i][0]) + pad16(len[i][1]);
-    }
-    Stage s(total);                                  // staged parts start on 16 bytes
+    u64 total = p.bytes / 8 + pad16(mWords);
+    for (u64 i = 0; i <= nF; i++) total += staged_words(sides[i], n, k, words);
+    Stage s(total);
     P2_TRY(s.rc());
     u64 *dScratch = s.take(p.bytes / 8);
-    for (u64 i = 0; i <= nF; i++) {
-        sides[i].base = s.put(sides[i].base, len[i][0]); s.take(pad16(len[i][0]) - len[i][0]);
-        sides[i].sel = s.put(sides[i].sel, len[i][1]); s.take(pad16(len[i][1]) - len[i][1]);
-    }
+    for (u64 i = 0; i <= nF; i++) stage_side(s, sides[i], n, k, words);
     const Out dOut{ (u64 *)s.put(out.m, mWords), out.stride, out.col };
     P2_TRY(s.rc());
     P2_TRY(launch(sides + 1, (u32)nF, sides[0], dOut, n, (u32)k, dScratch, p, words, hostReport, 0));

@@ -1,29 +1,23 @@
 // Host-only half of the lookup multiplicities (lookup_mult.hip): what the entries refuse, the capacity of the hash table, the launch
 // geometry, where the parts of the working buffer lie, and the aliasing rule of the output column m.  No HIP header: it builds with the
-// plain C++ compiler (tests/lookup_mult_plan_dump.cpp runs it under the sanitizers).  The hash, the column and span checks are
-// tuple_check_plan.h's; the grid and the overlap test are smap_plan.h's.
+// plain C++ compiler (tests/lookup_mult_plan_dump.cpp runs it under the sanitizers).  The table's capacity is index_table_plan.h's, a
+// side's limits, column and span checks tuple_side_plan.h's, the grid and the overlap test smap_plan.h's.
 //
-// The table: open addressing, linear probing over t's selected rows ONLY (the f sides are counted, not inserted), capacity the smallest
-// power of two >= 2 n and >= MIN_CAPACITY: the load factor never exceeds 1 / 2, whatever the data and the selector.  A slot is 8 bytes:
-// the tuple's smallest selected row of t (EMPTY = 2^32 - 1; n <= 2^28 stays far below) and beside it the 32-bit counter (nF n <= 2^31).
+// The table: over t's selected rows ONLY (the f sides are counted, not inserted), capacity for n rows.  A slot is 8 bytes: the tuple's
+// smallest selected row of t (n <= 2^28 stays far below EMPTY) and beside it the 32-bit counter (nF n <= 2^31).
 // The working buffer, every part on 16 bytes:
 //   HEADER_BYTES             the smallest failing (side << 32 | row), the matched rows, the longest probe of the build
 //   8 capacity               the slots
 #pragma once
 #include <stdint.h>
-#include "tuple_check_plan.h"
+#include "index_table_plan.h"
+#include "tuple_side_plan.h"
 
 namespace lookupmultplan {
 
 using smapplan::THREADS;
-using tuplecheckplan::MAX_N;
-using tuplecheckplan::MAX_K;
-using tuplecheckplan::NONE;
-using tuplecheckplan::check_columns;
-using tuplecheckplan::span_bytes;
-using tuplecheckplan::top_column;
+using indextable::NONE;
 constexpr uint64_t HEADER_BYTES = 64;
-constexpr uint64_t MIN_CAPACITY = 16;
 constexpr uint64_t SLOT_BYTES = 8;
 constexpr uint32_t MAX_SIDES = 8;
 constexpr uint32_t REPORT_WORDS = 4;
@@ -41,18 +35,17 @@ struct Plan {
 // 0, or a message for PIL2GL_EINVAL
 inline const char *check(uint64_t n, uint64_t k, uint64_t nF, uint32_t elemWords) {
     if (elemWords != 1 && elemWords != 4) return "elemWords is 1 (Goldilocks) or 4 (BN254 Fr)";
-    if (k < 1 || k > MAX_K) return "k must be 1 .. 16 columns";
+    if (k < 1 || k > tupleside::MAX_K) return "k must be 1 .. 16 columns";
     if (nF < 1 || nF > MAX_SIDES) return "nF must be 1 .. 8 sides of f";
-    if (n > MAX_N) return "n must be at most 2^28 rows";
+    if (n > tupleside::MAX_N) return "n must be at most 2^28 rows";
     return nullptr;
 }
 
 // the arguments have passed check(): init, build, one count a side of f, write (the report's words are made on the host from the header)
 inline Plan plan(uint64_t n, uint64_t nF) {
     Plan p{};
-    p.capacity = MIN_CAPACITY;
-    while (p.capacity < 2 * n) p.capacity <<= 1;
-    while ((1ull << p.capBits) < p.capacity) p.capBits++;
+    const indextable::Capacity c = indextable::capacity_for(n);
+    p.capacity = c.slots; p.capBits = c.bits;
     p.blocks = smapplan::blocks(n);
     p.launches = (uint32_t)(3 + nF);
     p.offHeader = 0;
@@ -68,6 +61,7 @@ struct ReadMatrix { const void *base; uint64_t stride; const uint64_t *cols; uin
 // column mCol) may meet the span of a matrix that is read only when it IS that matrix -- the same base and the same stride -- and mCol is
 // none of the columns read of it.  The arguments have passed check_columns().
 inline bool m_allowed(const void *mBase, uint64_t mStride, uint64_t mCol, const ReadMatrix &r, uint64_t n, uint32_t elemWords) {
+    using namespace tupleside;
     if (!smapplan::meets(mBase, span_bytes(n, mStride, mCol, elemWords), r.base, span_bytes(n, r.stride, top_column(r.cols, r.k), elemWords))) return true;
     if (mBase != r.base || mStride != r.stride) return false;
     for (uint64_t j = 0; j < r.k; j++) if (r.cols[j] == mCol) return false;

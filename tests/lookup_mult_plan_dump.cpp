@@ -31,7 +31,7 @@ int main(int argc, char **argv) {
             std::vector<uint64_t> cols(a[7]);
             for (uint64_t &c : cols) if (!rd(f, &c)) return 2;
             const uint64_t n = a[0], mStride = a[3], mCol = a[4], rStride = a[6];
-            const bool columns = !lookupmultplan::check_columns(n, mStride, &mCol, 1) && !lookupmultplan::check_columns(n, rStride, cols.empty() ? nullptr : cols.data(), cols.size());
+            const bool columns = !tupleside::check_columns(n, mStride, &mCol, 1) && !tupleside::check_columns(n, rStride, cols.empty() ? nullptr : cols.data(), cols.size());
             const lookupmultplan::ReadMatrix r{ (const void *)(uintptr_t)a[5], rStride, cols.data(), cols.size() };
             const bool ok = columns && lookupmultplan::m_allowed((const void *)(uintptr_t)a[2], mStride, mCol, r, n, (uint32_t)a[1]);
             printf("{\"ok\": %d, \"columns\": %d}\n", ok ? 1 : 0, columns ? 1 : 0);

@@ -233,6 +233,34 @@ def test_three_tuples_that_share_a_home_slot(field):
 
 
 @pytest.mark.parametrize("field", list(FIELDS))
+def test_a_probe_run_that_wraps_past_the_last_slot(field):
+    n, k = 4, 3
+    cap = 1 << pilcheck.lookup_mult_plan(n, k, 1, field)["capBits"]
+    assert cap == 16
+    ew = 1 if field == "gl" else 4
+    last, other = [], None
+    for i in range(4096):                                                        # the first four small integers at home in the last slot, the first elsewhere
+        tup = np.zeros((k, ew), np.uint64)
+        tup[0, 0] = i
+        if pilcheck.tuple_home(tup, k, field, cap) == cap - 1:
+            last.append(i)
+        elif other is None:
+            other = i
+        if len(last) == 4 and other is not None:
+            break
+    assert len(last) == 4 and other is not None, "too few candidates at home in slot 15"
+    t = [[v, 0, 0] for v in last[:3] + [other]]                                  # slots 15, 0 and 1 whatever the order of arrival
+    f = [t[2], t[0], t[2], t[3]]
+    m, rep = run(field, {"T": t, "F": f}, [("F", [0, 1, 2])], ("T", [0, 1, 2]), ("M", 0), n)
+    assert pilcheck.lookup_mult_probe() >= 2, "three tuples at home in the last slot: one of them lies in slot 1"
+    assert m == [1, 0, 2, 1] and rep == (0, NONE, NONE, n)
+    g = [list(r) for r in f]
+    g[1] = [last[3], 0, 0]                                                       # in no row of t, and its search walks the wrapped run to its end
+    m, rep = run(field, {"T": t, "F": g}, [("F", [0, 1, 2])], ("T", [0, 1, 2]), ("M", 0), n)
+    assert m == [0, 0, 2, 1] and rep == (1, 0, 1, n - 1)
+
+
+@pytest.mark.parametrize("field", list(FIELDS))
 def test_absent_rows_in_two_sides(field):
     n = 300
     t = distinct(n, 2)

@@ -235,6 +235,33 @@ def test_three_tuples_that_share_a_home_slot(field):
     assert check(field, L, words(field, g), [0, 1, 2], words(field, rows), [0, 1, 2], n) == (1, 5, NONE, 1, 0)
 
 
+@pytest.mark.parametrize("field", list(FIELDS))
+def test_a_probe_run_that_wraps_past_the_last_slot(field):
+    n, k, cols = 4, 3, [0, 1, 2]
+    cap = 1 << pilcheck.tuple_check_plan(n, k, field)["capBits"]
+    assert cap == 16
+    ew = 1 if field == "gl" else 4
+    last, other = [], None
+    for i in range(4096):                                                        # the first four small integers at home in the last slot, the first elsewhere
+        tup = np.zeros((k, ew), np.uint64)
+        tup[0, 0] = i
+        if pilcheck.tuple_home(tup, k, field, cap) == cap - 1:
+            last.append(i)
+        elif other is None:
+            other = i
+        if len(last) == 4 and other is not None:
+            break
+    assert len(last) == 4 and other is not None, "too few candidates at home in slot 15"
+    t = [[v, 0, 0] for v in last[:3] + [other]]                                  # slots 15, 0 and 1 whatever the order of arrival
+    f = [t[2], t[3], t[0], t[1]]
+    g = [list(r) for r in f]
+    g[2] = [last[3], 0, 0]                                                       # in no row of t, and its search walks the wrapped run to its end
+    for mode in (L, M):
+        assert check(field, mode, words(field, f), cols, words(field, t), cols, n) == CLEAN
+        assert pilcheck.tuple_check_probe() >= 2, "three tuples at home in the last slot: one of them lies in slot 1"
+        assert check(field, mode, words(field, g), cols, words(field, t), cols, n) == (1, 2, NONE, 1, 0)
+
+
 def test_python_resident_forms_and_refusals_with_a_device():
     lib = _lib.load()
     t = distinct(64, 2)

@@ -29,15 +29,15 @@ int main(int argc, char **argv) {
             if (a[2] > 64) return 2;
             std::vector<uint64_t> cols(a[2]);
             for (uint64_t &c : cols) if (!rd(f, &c)) return 2;
-            printf("{\"ok\": %d}\n", tuplecheckplan::check_columns(a[0], a[1], cols.empty() ? nullptr : cols.data(), a[2]) ? 0 : 1);
+            printf("{\"ok\": %d}\n", tupleside::check_columns(a[0], a[1], cols.empty() ? nullptr : cols.data(), a[2]) ? 0 : 1);
             continue;
         }
-        if (!strcmp(cmd, "span")) { printf("{\"bytes\": %" PRIu64 "}\n", tuplecheckplan::span_bytes(a[0], a[1], a[2], (uint32_t)a[3])); continue; }
+        if (!strcmp(cmd, "span")) { printf("{\"bytes\": %" PRIu64 "}\n", tupleside::span_bytes(a[0], a[1], a[2], (uint32_t)a[3])); continue; }
         if (!strcmp(cmd, "home")) {
-            if (a[0] > tuplecheckplan::MAX_K || a[1] > 4) return 2;
+            if (a[0] > tupleside::MAX_K || a[1] > 4) return 2;
             std::vector<uint64_t> words(a[0] * a[1]);
             for (uint64_t &w : words) if (!rd(f, &w)) return 2;
-            printf("{\"home\": %" PRIu64 "}\n", tuplecheckplan::home(words.data(), a[0], (uint32_t)a[1], a[2]));
+            printf("{\"home\": %" PRIu64 "}\n", indextable::home(words.data(), a[0], (uint32_t)a[1], a[2]));
             continue;
         }
         if (const char *why = tuplecheckplan::check(a[0], a[1], (uint32_t)a[2], (uint32_t)a[3])) { printf("{\"ok\": 0, \"why\": \"%s\"}\n", why); continue; }
