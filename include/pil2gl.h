@@ -24,7 +24,7 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod and bn128_gsum; land_rows with a null hostFirstBad;
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; land_rows with a null hostFirstBad;
  *      wtns_adds and bn128_wtns_adds, wtns_gather and bn128_wtns_gather with a null hostFirstBad, conn_pols and bn128_conn_pols with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, logup_sum_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -395,6 +395,9 @@ int pil2gl_first_nonzero_row_dev(const uint64_t *col, uint32_t dim, uint64_t fir
  * out must not overlap num or den. */
 int pil2gl_gprod_dev(const uint64_t *num, uint32_t dimNum, const uint64_t *den, uint32_t dimDen, uint64_t n, uint64_t *out, void *stream);
 int pil2gl_gsum_dev(const uint64_t *num, uint32_t dimNum, const uint64_t *den, uint32_t dimDen, uint64_t n, uint64_t *out, void *stream);
+/* the grand sum with a COLUMN numerator (a pil2 gsum hint whose numerator is a multiplicity or a selector): num has n rows like den,
+ * out[i] = out[i-1] + num[i]/den[i].  Dimensions, zeros, aliasing and limits as gsum's.  Only enqueues. */
+int pil2gl_gsum_col_dev(const uint64_t *num, uint32_t dimNum, const uint64_t *den, uint32_t dimDen, uint64_t n, uint64_t *out, void *stream);
 /* calculateH1H2(F,f,t)  polutils.js:105-126: the multiset f (every value must occur in t) merged into t; h1[i], h2[i] =
  * entries 2i, 2i+1 of the merged sequence.  f, t, h1, h2: n rows of dimension dim (1 or 3).  Returns PIL2GL_EINVAL with
  * the reference's "Number not included" message when some f[j] is missing from t (synchronises the stream).
@@ -692,6 +695,12 @@ int pil2gl_bn128_gprod_dev(const uint64_t *num, uint64_t numStride, const uint64
 int pil2gl_bn128_gsum(const uint64_t hostNum[4], const uint64_t *den, uint64_t denStride, uint64_t n, uint64_t *out, uint64_t outStride);
 int pil2gl_bn128_gsum_dev(const uint64_t hostNum[4], const uint64_t *den, uint64_t denStride, uint64_t n,
                           uint64_t *out, uint64_t outStride, void *stream);
+/* gsum with a COLUMN numerator: out[i] = out[i-1] + num[i] / den[i], num a column of n elements like gprod's.  Addressing, zeros,
+ * aliasing (out shares no element with num or den), limits and the two forms as gprod's. */
+int pil2gl_bn128_gsum_col(const uint64_t *num, uint64_t numStride, const uint64_t *den, uint64_t denStride, uint64_t n,
+                          uint64_t *out, uint64_t outStride);
+int pil2gl_bn128_gsum_col_dev(const uint64_t *num, uint64_t numStride, const uint64_t *den, uint64_t denStride, uint64_t n,
+                              uint64_t *out, uint64_t outStride, void *stream);
 /* host-only, no device: how the three run on n rows.  op: 0 batch_inverse, 1 gprod, 2 gsum, 3 batch_inverse in place.  The rows are cut
  * into segments, a lane each; the segment totals are the same problem one level up, until a level has at most 64 items, which one lane
  * finishes (the inversion's single Fermat ladder is there).  outInfo[0] = L, rows per segment; [1] = S, segments (L * S >= n,
@@ -1001,6 +1010,59 @@ int pil2gl_bn128_lookup_mult(const pil2gl_tuple_side *hostF, uint64_t nF, const 
                              uint64_t mCol, uint64_t n, uint64_t k, uint64_t *hostReport /* [4] */);
 /* host-only, no device: the longest distance, in slots, between a tuple of the last call's hash table and its home slot */
 uint64_t pil2gl_debug_lookup_mult_probe(void);
+
+/* ---- lookup grand sum: the logUp column s of `selF_s {f_s} in selT {t}` from f, t and m (csrc/logup_sum_plan.h, hints.hip, bn_scan.hip) ----
+ * The column that consumes the block above's m: the running sum of a pil2 lookup stated as  sum selF / (f + gamma) - sum m / (t + gamma),
+ * in the shape pil2's std library gives a @gsum hint (a tuple Horner-compressed with std_alpha, first column highest, a bus id as the
+ * last Horner term, + std_beta; the numerator a constant on the assume side and a multiplicity on the prove side), computed in one call
+ * with the sides read where they lie.  The statement is this header's own (tests/logup_sum_ref.py restates it over Python integers):
+ *   s[i] = s[i-1] + sum_{u < nTerms} coef_u w_u[i] / D_u[i]            s[-1] = 0,  i < n
+ *   D_u[i] = ((..((v_0 alpha + v_1) alpha + v_2).. + v_{k_u-1}) alpha + busId_u) + beta
+ *   n <= 2^28 rows; 1 <= nTerms <= 9 (eight f sides and t).  One term is a pil2gl_logup_term: a pil2gl_tuple_side, its k (1 .. 16, a
+ *   term's own), coef and busId, HOST base-field elements: over Goldilocks word 0, canonical (else PIL2GL_EINVAL); over Fr four
+ *   Montgomery words.  v_j = column hostCols[j] of the side's matrix at row i.  w_u[i] = the FIELD VALUE of the side's sel column at
+ *   row i, 1 when sel is NULL: for a 0/1 selector that is the block above's "selected"; for t the sel column is m and coef is -1.
+ *   Elements count as field values by the rules above (Goldilocks words in [p, 2^64) mod p, any Fr pattern mod r).
+ *   alpha, beta: HOST pointers; over Goldilocks three words each, an element of the cubic extension (x^3 = x + 1, as the hints above),
+ *   over Fr four Montgomery words each.
+ *   out: column outCol of the matrix (out, outStride), written for every row.  Goldilocks: the matrix is rows of outStride u64 words
+ *   and s[i] the three words outCol .. outCol + 2 of row i, canonical.  Fr: rows of outStride elements, s[i] one canonical Montgomery
+ *   element.  Words between a strided destination's elements stay as they are.
+ *   Zeros: the convention of the hints above.  A term whose D_u[i] is zero adds 0 at that row and spoils no other term or row.
+ *   The hint's `result` is s[n-1]: the caller copies it, as with gsum.
+ * pil2gl_logup_sum_plan: host-only, no device.  outInfo[0] = threads per workgroup of the first pass; [1] = rows a lane of it takes (8:
+ * it inverts their denominators together; Fr 1); [2] = its workgroups; [3] = kernel launches of a call (Goldilocks 3: the fused first
+ * pass, the block totals' scan, the fix-up; Fr 4 levels - 1: the compress, then bn128_gprod's inversion and gsum's scan); [4] =
+ * Goldilocks: block totals a lane of the second pass walks, Fr: levels of pil2gl_debug_bn128_scan_plan; [5] = u64 words of an output
+ * element's columns (3, or 1 element).  *workBytes = the working memory, taken from the library's own slots as gsum's is, growing with
+ * neither nTerms nor k: Goldilocks 24 n + 24 ceil(n / 2048), what gsum takes; Fr the scan plan's bytes + 64 n (the product D of a row's
+ * denominators and its numerator N).  PIL2GL_EINVAL: n > 2^28, nTerms outside 1 .. 9, elemWords not 1 or 4.
+ * pil2gl_[bn128_]logup_sum_dev: hostTerms is a HOST pointer to terms whose side.base and side.sel are device pointers, 16-byte aligned,
+ * only read; matrices may overlap each other freely and one matrix may serve several terms.  out = device, 16-byte aligned.  Aliasing
+ * rule of out: lookup_mult's rule of m over each of out's word columns -- out may meet a read matrix (a term's, a numerator's) only with
+ * that matrix's base and stride and with none of its read columns; s as spare columns of t's matrix is the normal case.  The call only
+ * ENQUEUES on the caller's stream: the term table travels as a kernel argument, nothing is copied.  (On first use the working slots are
+ * allocated, with a device synchronise when they grow; they are one per process.)  PIL2GL_EINVAL, before any device call: what the plan
+ * refuses, k outside 1 .. 16, a column >= its stride (outCol + 2 over Goldilocks), a stride >= 2^32 or n stride > 2^58 elements, null
+ * terms, cols, base, out, alpha or beta, a non-canonical Goldilocks coef or busId, a misaligned device pointer, an out that breaks the
+ * aliasing rule.  n = 0 is PIL2GL_OK, touches nothing and needs no device.
+ * pil2gl_[bn128_]logup_sum: host pointers throughout; each matrix staged up to the last element touched, every part on 16 bytes, out's
+ * matrix goes up as it is and comes back with the column written.  Without a device the compute calls return PIL2GL_ENODEV. */
+typedef struct pil2gl_logup_term {
+    pil2gl_tuple_side side;              /* the tuple's columns; side.sel = the numerator column w, or NULL for 1 */
+    uint64_t k;                          /* columns of this term's tuple, 1 .. 16 */
+    uint64_t coef[4];                    /* Goldilocks: word 0, canonical.  Fr: 4 Montgomery words */
+    uint64_t busId[4];
+} pil2gl_logup_term;
+int pil2gl_logup_sum_plan(uint64_t n, uint64_t nTerms, uint32_t elemWords, uint32_t *outInfo /* [6] */, uint64_t *workBytes);
+int pil2gl_logup_sum_dev(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha /* [3] */, const uint64_t *hostBeta /* [3] */,
+                         uint64_t *out, uint64_t outStride, uint64_t outCol, uint64_t n, void *stream);
+int pil2gl_bn128_logup_sum_dev(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha /* [4] */, const uint64_t *hostBeta /* [4] */,
+                               uint64_t *out, uint64_t outStride, uint64_t outCol, uint64_t n, void *stream);
+int pil2gl_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                     uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
+int pil2gl_bn128_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                           uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

@@ -6,6 +6,7 @@
 // function names and signatures.  Calls are synchronous (the reference awaits each one anyway).
 #include <node_api.h>
 #include <stdint.h>
+#include <stddef.h>
 #include <string.h>
 #include <string>
 #include <vector>
@@ -317,6 +318,11 @@ FN(Bn128GsumDev) {           // (num BigUint64Array(4), dDen, denStride, n, dOut
     if (!a.ok) return nullptr;
     P2(env, pil2gl_bn128_gsum_dev(nu, de, ds, n, o, os, a.stream(6))); return mk_undefined(env);
 }
+FN(Bn128GsumColDev) {        // (dNum, numStride, dDen, denStride, n, dOut, outStride[, stream]): gsum with a column numerator
+    Args a(env, info); uint64_t *nu = DP(0); uint64_t ns = a.u64(1); uint64_t *de = DP(2); uint64_t ds = a.u64(3), n = a.u64(4); uint64_t *o = DP(5); uint64_t os = a.u64(6);
+    if (!a.ok) return nullptr;
+    P2(env, pil2gl_bn128_gsum_col_dev(nu, ns, de, ds, n, o, os, a.stream(7))); return mk_undefined(env);
+}
 // the plookup hint over curve.Fr (calculateH1H2).  A value of f that is not in t is no exception here: the row comes back, and
 // js/polutils_bn128.js throws the reference's full message, which needs the element
 FN(Bn128H1h2Dev) {           // (dF, fStride, dT, tStride, n, dH1, h1Stride, dH2, h2Stride[, stream]) -> undefined, or the lowest missing row as a BigInt
@@ -489,6 +495,10 @@ FN(GprodDev) {         // (dNum, dimNum, dDen, dimDen, n, dOut)  polutils.js:128
 FN(GsumDev) {          // (dNum (one element), dimNum, dDen, dimDen, n, dOut)  polutils.js:145-164
     Args a(env, info); uint64_t *num = DP(0); uint32_t dn = (uint32_t)a.u64(1); uint64_t *den = DP(2); uint32_t dd = (uint32_t)a.u64(3); uint64_t n = a.u64(4); uint64_t *o = DP(5); if (!a.ok) return nullptr;
     P2(env, pil2gl_gsum_dev(num, dn, den, dd, n, o, a.stream(6))); return mk_undefined(env);
+}
+FN(GsumColDev) {       // (dNum (n rows), dimNum, dDen, dimDen, n, dOut): gsum with a column numerator
+    Args a(env, info); uint64_t *num = DP(0); uint32_t dn = (uint32_t)a.u64(1); uint64_t *den = DP(2); uint32_t dd = (uint32_t)a.u64(3); uint64_t n = a.u64(4); uint64_t *o = DP(5); if (!a.ok) return nullptr;
+    P2(env, pil2gl_gsum_col_dev(num, dn, den, dd, n, o, a.stream(6))); return mk_undefined(env);
 }
 FN(H1H2Dev) {          // (dF, dT, n, dim, dH1, dH2)  polutils.js:105-126
     Args a(env, info); uint64_t *f = DP(0), *t = DP(1); uint64_t n = a.u64(2); uint32_t dim = (uint32_t)a.u64(3); uint64_t *h1 = DP(4), *h2 = DP(5); if (!a.ok) return nullptr;
@@ -705,6 +715,18 @@ FN(LookupMultDev) {        // (description, dScratch, scratchBytes, report BigUi
                                                                               m.n, m.k, scr, bytes, rep, nullptr));
     return mk_undefined(env);
 }
+// element i of the Array `arr` as a BigUint64Array of at least minWords; optional: null / undefined give nullptr
+static uint64_t *array_words(Args &a, napi_value arr, uint32_t i, uint64_t minWords, bool optional) {
+    napi_env env = a.env;
+    napi_value v; napi_valuetype t; napi_get_element(env, arr, i, &v); napi_typeof(env, v, &t);
+    if (optional && (t == napi_undefined || t == napi_null)) return nullptr;
+    bool is = false; napi_is_typedarray(env, v, &is);
+    napi_typedarray_type ty = napi_int8_array; size_t n = 0; void *data = nullptr; napi_value ab; size_t off;
+    if (is) napi_get_typedarray_info(env, v, &ty, &n, &data, &ab, &off);
+    if (!is || (ty != napi_biguint64_array && ty != napi_bigint64_array)) { a.fail("expected a BigUint64Array"); return nullptr; }
+    if (n < minWords) { a.fail("buffer too small"); return nullptr; }
+    return (uint64_t *)data;
+}
 // (description, matrices, report BigUint64Array(4), elemWords): matrices = an Array of BigUint64Array, [2 s] the matrix of side s (t first),
 // [2 s + 1] its selector's or null, [2 (1 + nF)] m's matrix, which is written in place
 FN(LookupMult) {
@@ -715,16 +737,7 @@ FN(LookupMult) {
     if (a.argc < 2 || napi_is_array(env, a.argv[1], &isArray) != napi_ok || !isArray) { a.fail("expected an Array of matrices"); return nullptr; }
     napi_get_array_length(env, a.argv[1], &count);
     if (count != 2 * (1 + m.nF) + 1) { a.fail("expected a matrix and a selector or null for t and every f, then m's matrix"); return nullptr; }
-    auto words = [&](uint32_t i, uint64_t minWords, bool optional) -> uint64_t * {       // element i as a BigUint64Array of at least minWords
-        napi_value v; napi_valuetype t; napi_get_element(env, a.argv[1], i, &v); napi_typeof(env, v, &t);
-        if (optional && (t == napi_undefined || t == napi_null)) return nullptr;
-        bool is = false; napi_is_typedarray(env, v, &is);
-        napi_typedarray_type ty = napi_int8_array; size_t n = 0; void *data = nullptr; napi_value ab; size_t off;
-        if (is) napi_get_typedarray_info(env, v, &ty, &n, &data, &ab, &off);
-        if (!is || (ty != napi_biguint64_array && ty != napi_bigint64_array)) { a.fail("expected a BigUint64Array"); return nullptr; }
-        if (n < minWords) { a.fail("buffer too small"); return nullptr; }
-        return (uint64_t *)data;
-    };
+    auto words = [&](uint32_t i, uint64_t minWords, bool optional) { return array_words(a, a.argv[1], i, minWords, optional); };
     for (uint64_t s = 0; s <= m.nF && a.ok; s++) {
         pil2gl_tuple_side &x = m.side[s];
         x.base = words((uint32_t)(2 * s), tuple_span(m.n, x.stride, x.hostCols, m.k, ew), false);
@@ -736,6 +749,76 @@ FN(LookupMult) {
     return mk_undefined(env);
 }
 FN(LookupMultProbe) { return mk_bigint(env, pil2gl_debug_lookup_mult_probe()); }
+
+// ---- lookup grand sum: the logUp column s from f, t and m (csrc/logup_sum_plan.h; js/pil_checks.js) ----
+FN(LogupSumPlan) {         // (n, nTerms, elemWords) -> { threads, items, blocks, launches, depth, outWidth, workBytes }
+    Args a(env, info); uint64_t n = a.u64(0), nT = a.u64(1); uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
+    uint32_t out[6]; uint64_t bytes = 0;
+    P2(env, pil2gl_logup_sum_plan(n, nT, ew, out, &bytes));
+    static const char *names[6] = { "threads", "items", "blocks", "launches", "depth", "outWidth" };
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 6; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
+    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "workBytes", v);
+    return o;
+}
+FN(LogupTermLayout) {      // -> { size, side, k, coef, busId }: sizeof and offsetof of pil2gl_logup_term as this addon was compiled
+    static const char *names[5] = { "size", "side", "k", "coef", "busId" };
+    const size_t at[5] = { sizeof(pil2gl_logup_term), offsetof(pil2gl_logup_term, side), offsetof(pil2gl_logup_term, k), offsetof(pil2gl_logup_term, coef),
+                           offsetof(pil2gl_logup_term, busId) };
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 5; i++) { napi_create_uint32(env, (uint32_t)at[i], &v); napi_set_named_property(env, o, names[i], v); }
+    return o;
+}
+// A call's description, one BigUint64Array: [0] n, [1] nTerms, [2] out, [3] outStride, [4] outCol, [5..8] alpha, [9..12] beta (three words
+// used over Goldilocks), then nTerms terms of 14 words -- base, stride, k, sel (0: none), selStride, selCol, coef[4], busId[4] -- then 16
+// column slots a term, the first k used.  The pointer words are device addresses for logupSumDev and are not read by logupSum, which
+// takes the host matrices as an array of its own.
+enum { LD_N, LD_NTERMS, LD_OUT, LD_OUT_STRIDE, LD_OUT_COL, LD_ALPHA, LD_BETA = LD_ALPHA + 4, LD_TERMS = LD_BETA + 4, LD_TERM_WORDS = 14, LD_COL_SLOTS = 16 };
+struct LogupDesc { uint64_t *d; uint64_t n, nTerms; pil2gl_logup_term term[9]; };
+static bool logup_desc(Args &a, size_t i, LogupDesc &L) {
+    uint64_t len = 0; L.d = a.arr(i, LD_TERMS, &len);
+    if (!a.ok) return false;
+    L.n = L.d[LD_N]; L.nTerms = L.d[LD_NTERMS];
+    if (L.nTerms < 1 || L.nTerms > 9 || len < LD_TERMS + L.nTerms * (LD_TERM_WORDS + LD_COL_SLOTS)) return a.fail("the description holds 13 words, then 1 .. 9 terms of 14 words and 16 column slots each");
+    uint64_t *cols = L.d + LD_TERMS + L.nTerms * LD_TERM_WORDS;
+    for (uint64_t u = 0; u < L.nTerms; u++) {
+        const uint64_t *w = L.d + LD_TERMS + u * LD_TERM_WORDS;
+        pil2gl_logup_term &t = L.term[u];
+        t.side = pil2gl_tuple_side{ (const uint64_t *)(uintptr_t)w[0], w[1], cols + u * LD_COL_SLOTS, (const uint64_t *)(uintptr_t)w[3], w[4], w[5] };
+        t.k = w[2];
+        for (int c = 0; c < 4; c++) { t.coef[c] = w[6 + c]; t.busId[c] = w[10 + c]; }
+    }
+    return true;
+}
+FN(LogupSumDev) {          // (description, elemWords[, stream]): only enqueues
+    Args a(env, info); LogupDesc L; if (!logup_desc(a, 0, L)) return nullptr;
+    uint32_t ew = (uint32_t)a.u64(1); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_logup_sum_dev : pil2gl_logup_sum_dev)(L.term, L.nTerms, L.d + LD_ALPHA, L.d + LD_BETA, (uint64_t *)(uintptr_t)L.d[LD_OUT], L.d[LD_OUT_STRIDE],
+                                                                          L.d[LD_OUT_COL], L.n, a.stream(2)));
+    return mk_undefined(env);
+}
+// (description, matrices, elemWords): matrices = an Array of BigUint64Array, [2 u] the matrix of term u, [2 u + 1] its numerator's or null,
+// [2 nTerms] out's matrix, which is written in place
+FN(LogupSum) {
+    Args a(env, info); LogupDesc L; if (!logup_desc(a, 0, L)) return nullptr;
+    uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
+    if (ew != 1 && ew != 4) { a.fail("elemWords is 1 or 4"); return nullptr; }
+    bool isArray = false; uint32_t count = 0;
+    if (a.argc < 2 || napi_is_array(env, a.argv[1], &isArray) != napi_ok || !isArray) { a.fail("expected an Array of matrices"); return nullptr; }
+    napi_get_array_length(env, a.argv[1], &count);
+    if (count != 2 * L.nTerms + 1) { a.fail("expected a matrix and a numerator's matrix or null for every term, then out's matrix"); return nullptr; }
+    for (uint64_t u = 0; u < L.nTerms && a.ok; u++) {
+        pil2gl_logup_term &t = L.term[u];
+        if (t.k < 1 || t.k > 16) { a.fail("k must be 1 .. 16 columns"); return nullptr; }
+        t.side.base = array_words(a, a.argv[1], (uint32_t)(2 * u), tuple_span(L.n, t.side.stride, t.side.hostCols, t.k, ew), false);
+        t.side.sel = a.ok ? array_words(a, a.argv[1], (uint32_t)(2 * u + 1), tuple_span(L.n, t.side.selStride, &t.side.selCol, 1, ew), true) : nullptr;
+    }
+    const uint64_t top = L.d[LD_OUT_COL] + (ew == 1 ? 2 : 0);
+    uint64_t *ho = a.ok ? array_words(a, a.argv[1], (uint32_t)(2 * L.nTerms), tuple_span(L.n, L.d[LD_OUT_STRIDE], &top, 1, ew), false) : nullptr;
+    if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_logup_sum : pil2gl_logup_sum)(L.term, L.nTerms, L.d + LD_ALPHA, L.d + LD_BETA, ho, L.d[LD_OUT_STRIDE], L.d[LD_OUT_COL], L.n));
+    return mk_undefined(env);
+}
 
 // ---- BN128 Merkle commitment (merklehash_bn128_p.js / merklehash_bn128_worker.js) ----
 FN(Bn128Poseidon) {  // (in BigUint64Array(4*nIn*count) normal form, init BigUint64Array(4*count)|null, count, nIn, nOut, out(4*nOut*count))
@@ -919,16 +1002,17 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "bn128G1MsmDev", Bn128G1MsmDev }, { "bn128G1CommitDev", Bn128G1CommitDev }, { "bn128EvalProgramDev", Bn128EvalProgramDev }, { "bn128FirstNonzeroRowDev", Bn128FirstNonzeroRowDev },
         { "bn128PolyDivDev", Bn128PolyDivDev }, { "bn128PolyEvalDev", Bn128PolyEvalDev },
         { "bn128PolyFmaDev", Bn128PolyFmaDev }, { "bn128PolyDegreeDev", Bn128PolyDegreeDev },
-        { "bn128BatchInverseDev", Bn128BatchInverseDev }, { "bn128GprodDev", Bn128GprodDev }, { "bn128GsumDev", Bn128GsumDev },
+        { "bn128BatchInverseDev", Bn128BatchInverseDev }, { "bn128GprodDev", Bn128GprodDev }, { "bn128GsumDev", Bn128GsumDev }, { "bn128GsumColDev", Bn128GsumColDev },
         { "bn128H1h2Dev", Bn128H1h2Dev },
         { "wtnsAddsPlan", WtnsAddsPlan }, { "wtnsAddsDev", WtnsAddsDev }, { "wtnsGatherDev", WtnsGatherDev }, { "wtnsExec", WtnsExec }, { "bn128WtnsExec", Bn128WtnsExec },
         { "connPlan", ConnPlan }, { "connPolsDev", ConnPolsDev }, { "bn128ConnPolsDev", Bn128ConnPolsDev }, { "connPols", ConnPols }, { "bn128ConnPols", Bn128ConnPols },
         { "connCheckPlan", ConnCheckPlan }, { "connCheckDev", ConnCheckDev }, { "bn128ConnCheckDev", Bn128ConnCheckDev }, { "connCheck", ConnCheck }, { "bn128ConnCheck", Bn128ConnCheck },
         { "tupleCheckPlan", TupleCheckPlan }, { "tupleCheckDev", TupleCheckDev }, { "tupleCheck", TupleCheck }, { "tupleHome", TupleHome }, { "tupleCheckProbe", TupleCheckProbe },
         { "lookupMultPlan", LookupMultPlan }, { "lookupMultDev", LookupMultDev }, { "lookupMult", LookupMult }, { "lookupMultProbe", LookupMultProbe },
+        { "logupSumPlan", LogupSumPlan }, { "logupTermLayout", LogupTermLayout }, { "logupSumDev", LogupSumDev }, { "logupSum", LogupSum },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
-        { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "h1h2Dev", H1H2Dev },
+        { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "gsumColDev", GsumColDev }, { "h1h2Dev", H1H2Dev },
         { "rowsDotExtDev", RowsDotExtDev }, { "rowsDotExtMultiDev", RowsDotExtMultiDev }, { "friCombineDev", FriCombineDev }, { "colsDotExtDev", ColsDotExtDev }, { "colsDotExtMultiDev", ColsDotExtMultiDev }, { "synthFibonacciDev", SynthFibonacciDev },
         { "friFoldDev", FriFoldDev }, { "friTransposeDev", FriTransposeDev },
         { "friFold", FriFold }, { "friVerifyFold", FriVerifyFold }, { "friTranspose", FriTranspose }, { "evalProgramDev", EvalProgramDev }, { "jitCacheSetDir", JitCacheSetDir }, { "jitCacheStats", JitCacheStats }, { "precompileProgram", PrecompileProgram }, { "firstNonzeroRowDev", FirstNonzeroRowDev },

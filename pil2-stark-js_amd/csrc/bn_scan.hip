@@ -5,6 +5,8 @@
 //     batch_inverse   dst[i] = src[i]^-1
 //     gprod           z[0] = 1,  z[i] = z[i - 1] num[i - 1] / den[i - 1]
 //     gsum            s[i] = s[i - 1] + num / den[i],  s[0] = num / den[0]          (num: ONE element, on the host)
+//     gsum_col        s[i] = s[i - 1] + num[i] / den[i]                              (num: a column, as gprod's)
+//     logup_sum       the lookup grand sum of include/pil2gl.h: gsum_col over a row's terms folded into one fraction (at the end of this file)
 //
 // Elements are 32 bytes of Montgomery words, canonical in and out, moved as two 16-byte halves; element i of a column lies at word
 // 4 i stride, so a column of a row-major section is worked on where it is (as poly_div and g1_msm take theirs).
@@ -37,6 +39,8 @@
 #include "bn_elem.cuh"
 #include "bn_params.h"
 #include "bn_scan_plan.h"
+#include "logup_sum_plan.h"
+#include "tuple_side.cuh"
 
 using namespace pil2gl;
 using bn::u32;
@@ -249,7 +253,7 @@ int run(u32 op, const u64 *num, u64 numStride, const u64 *hostNum, const u64 *de
     if (p.elems) P2_TRY(scratch(SCR_BN_SCAN, 4 * p.elems, &d));
     uint4 *base = (uint4 *)d, *y = (uint4 *)out;
     uint4 *q = inPlace ? base + 2 * p.q0Off : y;
-    const u32 mode = op == bnscan::OP_GPROD ? MODE_COLUMN : op == bnscan::OP_GSUM ? MODE_CONST : MODE_NONE;
+    const u32 mode = op == bnscan::OP_GPROD || (op == bnscan::OP_GSUM && num) ? MODE_COLUMN : op == bnscan::OP_GSUM ? MODE_CONST : MODE_NONE;   // gsum with num: gsum_col
     Elem mul{};
     if (hostNum) bnp::bn_limbs(hostNum, mul.w);
     P2_TRY(inverse_launch(p, base, (const uint4 *)den, denStride, y, outStride, q, inPlace ? 1 : outStride, mode, (const uint4 *)num, numStride, mul, st));
@@ -333,6 +337,15 @@ int pil2gl_bn128_gsum_dev(const uint64_t hostNum[4], const uint64_t *den, uint64
     return run(bnscan::OP_GSUM, nullptr, 0, hostNum, den, denStride, n, out, outStride, as_stream(stream));
 }
 
+int pil2gl_bn128_gsum_col_dev(const uint64_t *num, uint64_t numStride, const uint64_t *den, uint64_t denStride, uint64_t n,
+                              uint64_t *out, uint64_t outStride, void *stream) {
+    P2_TRY(check_gprod(num, numStride, den, denStride, n, out, outStride));
+    if (n == 0) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    P2_TRY(check_aligned16({ num, den, out }));
+    return run(bnscan::OP_GSUM, num, numStride, nullptr, den, denStride, n, out, outStride, as_stream(stream));
+}
+
 int pil2gl_bn128_batch_inverse(const uint64_t *src, uint64_t srcStride, uint64_t n, uint64_t *dst, uint64_t dstStride) {
     P2_TRY(check_inverse(src, srcStride, n, dst, dstStride));
     if (n == 0) return PIL2GL_OK;
@@ -350,6 +363,116 @@ int pil2gl_bn128_gsum(const uint64_t hostNum[4], const uint64_t *den, uint64_t d
     P2_TRY(check_gsum(hostNum, den, denStride, n, out, outStride));
     if (n == 0) return PIL2GL_OK;
     return run_host(bnscan::OP_GSUM, nullptr, 0, hostNum, den, denStride, n, out, outStride);
+}
+
+int pil2gl_bn128_gsum_col(const uint64_t *num, uint64_t numStride, const uint64_t *den, uint64_t denStride, uint64_t n,
+                          uint64_t *out, uint64_t outStride) {
+    P2_TRY(check_gprod(num, numStride, den, denStride, n, out, outStride));
+    if (n == 0) return PIL2GL_OK;
+    return run_host(bnscan::OP_GSUM, num, numStride, nullptr, den, denStride, n, out, outStride);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The lookup grand sum over Fr (include/pil2gl.h states it):  s[i] = s[i-1] + sum_u coef_u w_u[i] / D_u[i],
+//   D_u[i] = ((..(v_0 alpha + v_1) alpha .. + v_{k-1}) alpha + busId_u) + beta.
+// One compress kernel, a lane a row, folds the row's terms into ONE fraction N / D (N <- N D_u + coef_u w_u D, D <- D D_u; a zero D_u is
+// left out of both, so D is never zero) and writes D and N into the working buffer; then the operators above as they are:
+// inverse_launch(MODE_COLUMN) leaves N / D in the output column -- its prefixes live there meanwhile, which is why N cannot -- and
+// scan_launch<true> sums in place.  One Fermat ladder a call.  Products a row: nTerms (k + 4) in the compress (k Horner steps, coef w, three
+// for the fold; a NULL numerator column saves one), then gsum_col's 5.
+// The term table is a kernel argument read with wave-uniform indices: no copy to the device, nothing in a private segment.
+namespace {
+
+using tupleside::FrField;
+typedef FrField::Elem FrE;
+
+struct FrLogupTerm { tupleside::Side<FrField> s; u32 k; FrE coef, bus; };
+struct FrLogupJob {
+    FrLogupTerm t[logupplan::MAX_TERMS];
+    FrE alpha, beta, one;                            // one: 1 in Montgomery form
+    u32 nTerms;
+    u64 n;
+    FrField::Mem *D, *N;                             // dense, n elements each
+};
+
+__global__ void __launch_bounds__(smapplan::THREADS) bn_logup_compress_kernel(const FrLogupJob J) {
+    const FrE alpha = FrField::reduce(J.alpha), beta = FrField::reduce(J.beta);
+    for (u64 i = (u64)blockIdx.x * smapplan::THREADS + threadIdx.x; i < J.n; i += (u64)gridDim.x * smapplan::THREADS) {
+        FrE N{}, D = J.one;
+        for (u32 u = 0; u < J.nTerms; u++) {
+            const FrLogupTerm &T = J.t[u];
+            FrE d = tupleside::elem_of(T.s, i, 0);
+            for (u32 j = 1; j < T.k; j++) d = FrField::add(FrField::mul(d, alpha), tupleside::elem_of(T.s, i, j));
+            d = FrField::add(FrField::add(FrField::mul(d, alpha), FrField::reduce(T.bus)), beta);
+            if (bn::is_zero(d.v)) continue;           // a zero D_u: the term adds 0 and is left out of the product
+            FrE c = FrField::reduce(T.coef);
+            if (T.s.sel) c = FrField::mul(FrField::load(T.s.sel, i * T.s.selStride + T.s.selCol), c);
+            N = FrField::add(FrField::mul(N, d), FrField::mul(D, c));
+            D = FrField::mul(D, d);
+        }
+        FrField::store(J.D, i, D);
+        FrField::store(J.N, i, N);
+    }
+}
+
+// every launch of a call, on st; the arguments have passed logupplan::check_call() and n > 0, the pointers are the device's
+int bn_logup_launch(const pil2gl_logup_term *terms, u32 nTerms, const u64 *alpha, const u64 *beta, u64 *out, u64 outStride, u64 outCol, u64 n, hipStream_t st) {
+    const bnscan::Plan p = bnscan::plan(n, false);
+    u64 *d;
+    P2_TRY(scratch(SCR_BN_SCAN, 4 * p.elems + 8 * n, &d));        // the plan's levels, then D and N
+    FrLogupJob J{};
+    for (u32 u = 0; u < nTerms; u++) {
+        J.t[u].s = tupleside::device_side<FrField>(terms[u].side, (u32)terms[u].k);
+        J.t[u].k = (u32)terms[u].k;
+        bnp::bn_limbs(terms[u].coef, J.t[u].coef.v);
+        bnp::bn_limbs(terms[u].busId, J.t[u].bus.v);
+    }
+    bnp::bn_limbs(alpha, J.alpha.v); bnp::bn_limbs(beta, J.beta.v); bnp::bn_limbs(bnp::bn_mont_one().w, J.one.v);
+    J.nTerms = nTerms; J.n = n;
+    J.D = (FrField::Mem *)(d + 4 * p.elems); J.N = J.D + n;
+    bn_logup_compress_kernel<<<smapplan::blocks(n), smapplan::THREADS, 0, st>>>(J);
+    KERNEL_CHECK();
+    uint4 *base = (uint4 *)d, *y = (uint4 *)(out + 4 * outCol);
+    P2_TRY(inverse_launch(p, base, (const uint4 *)J.D, 1, y, outStride, y, outStride, MODE_COLUMN, (const uint4 *)J.N, 1, Elem{}, st));
+    return scan_launch<true>(p, base, y, outStride, st);
+}
+
+int bn_logup_check(const pil2gl_logup_term *terms, u64 nTerms, const u64 *alpha, const u64 *beta, const u64 *out, u64 outStride, u64 outCol, u64 n, bool dev) {
+    char why[96];
+    if (const char *msg = logupplan::check_call(terms, nTerms, alpha, beta, out, outStride, outCol, n, 4, dev, why)) return fail(PIL2GL_EINVAL, "%s", msg);
+    return PIL2GL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_bn128_logup_sum_dev(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                               uint64_t *out, uint64_t outStride, uint64_t outCol, uint64_t n, void *stream) {
+    P2_TRY(bn_logup_check(hostTerms, nTerms, hostAlpha, hostBeta, out, outStride, outCol, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return bn_logup_launch(hostTerms, (u32)nTerms, hostAlpha, hostBeta, out, outStride, outCol, n, as_stream(stream));
+}
+
+// host matrices, each staged up to the last element touched; out's matrix goes up as it is and comes back with the column written
+int pil2gl_bn128_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                           uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n) {
+    P2_TRY(bn_logup_check(hostTerms, nTerms, hostAlpha, hostBeta, hostOut, outStride, outCol, n, false));
+    if (!n) return PIL2GL_OK;
+    pil2gl_logup_term terms[logupplan::MAX_TERMS];
+    const u64 outWords = tupleside::span_bytes(n, outStride, outCol, 4) / 8;
+    u64 total = smapplan::pad16(outWords);
+    for (u64 u = 0; u < nTerms; u++) { terms[u] = hostTerms[u]; total += tupleside::staged_words(terms[u].side, n, terms[u].k, 4); }
+    Stage s(total);
+    P2_TRY(s.rc());
+    for (u64 u = 0; u < nTerms; u++) tupleside::stage_side(s, terms[u].side, n, terms[u].k, 4);
+    u64 *dOut = (u64 *)s.put(hostOut, outWords);
+    P2_TRY(s.rc());
+    P2_TRY(bn_logup_launch(terms, (u32)nTerms, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0));
+    return s.get(hostOut, dOut, outWords);
 }
 
 }  // extern "C"

@@ -5,10 +5,13 @@
 // arithmetic after one batch inversion; here a thread inverts its eight denominators together (one field inversion per
 // eight rows) and the running product / sum is a three-kernel scan: per-block inclusive scan + block totals, scan of the
 // totals, then the fix-up (for the product: shifted by one row, z[0] = 1).  Operands may be base (dim 1) or cubic
-// extension (dim 3) columns, row-major; the result is dim 3 if either operand is, else dim 1.
+// extension (dim 3) columns, row-major; the result is dim 3 if either operand is, else dim 1.  gsum_col is the sum with a column
+// numerator; the lookup grand sum further down folds a lookup's sides into the sum's first pass.
 #include "common.h"
 #include "gl_field.cuh"
 #include "hint_plan.h"
+#include "logup_sum_plan.h"
+#include <utility>
 
 using namespace gl;
 using namespace pil2gl;
@@ -42,15 +45,16 @@ __device__ E3 block_exclusive(E3 total, E3 *sh, E3 *blockTotal) {
     return ex;
 }
 
-// pass 1: ratios, block-local inclusive scan into tmp (n x 3), block totals
-template <bool PROD>
+// pass 1: ratios, block-local inclusive scan into tmp (n x 3), block totals.  COLNUM: the numerator is a column of n rows (always for the
+// product; for the sum it is ONE element unless asked for)
+template <bool PROD, bool COLNUM = PROD>
 __global__ void __launch_bounds__(SCAN_THREADS) hint_scan1(const u64 *__restrict__ num, u32 dimNum, const u64 *__restrict__ den, u32 dimDen, u64 n,
                                                           u64 *__restrict__ tmp, u64 *__restrict__ totals) {
     __shared__ E3 sh[SCAN_THREADS];
     const u64 base = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_ITEMS;
     E3 loc[SCAN_ITEMS];
     E3 run = ident<PROD>();
-    const E3 numS = PROD ? ident<true>() : ld_dim(num, 0, dimNum);
+    const E3 numS = COLNUM ? ident<true>() : ld_dim(num, 0, dimNum);
     // the thread's SCAN_ITEMS denominators are inverted together (Montgomery's trick, what the reference's F.batchInverse does for the whole
     // column, polutils.js:134): ONE field inversion -- an exponentiation, ~130 products -- and three extension products per row instead
     // of an inversion per row.  A zero denominator inverts to zero, as it does alone (0^(p-2)): it is kept out of the running product.
@@ -79,7 +83,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) hint_scan1(const u64 *__restrict
     for (int k = 0; k < SCAN_ITEMS; k++) {
         const u64 i = base + k;
         if (i < n) {
-            const E3 r = e3_mul(PROD ? ld_dim(num, i, dimNum) : numS, loc[k]);
+            const E3 r = e3_mul(COLNUM ? ld_dim(num, i, dimNum) : numS, loc[k]);
             run = comb<PROD>(run, r);
         }
         loc[k] = run;
@@ -105,8 +109,9 @@ __global__ void __launch_bounds__(SCAN_THREADS) hint_scan2(u64 *__restrict__ tot
     }
 }
 // pass 3: add the block prefix; the product column is the EXCLUSIVE scan (z[0] = 1), the sum column the inclusive one
+// out: element i at word i outStride + outCol (a dense column: outStride = dimOut, outCol = 0)
 template <bool PROD>
-__global__ void hint_scan3(const u64 *__restrict__ tmp, const u64 *__restrict__ totals, u64 n, u32 dimOut, u64 *__restrict__ out) {
+__global__ void hint_scan3(const u64 *__restrict__ tmp, const u64 *__restrict__ totals, u64 n, u32 dimOut, u64 *__restrict__ out, u64 outStride, u64 outCol) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     E3 v;
@@ -114,10 +119,12 @@ __global__ void hint_scan3(const u64 *__restrict__ tmp, const u64 *__restrict__ 
         if (i == 0) v = ident<true>();
         else { const u64 j = i - 1; v = comb<true>(ld_dim(totals, j / SCAN_CHUNK, 3), ld_dim(tmp, j, 3)); }
     } else v = comb<false>(ld_dim(totals, i / SCAN_CHUNK, 3), ld_dim(tmp, i, 3));
-    if (dimOut == 3) st3(out, i, v); else out[i] = v.v[0];
+    u64 *o = out + i * outStride + outCol;
+    o[0] = v.v[0];
+    if (dimOut == 3) { o[1] = v.v[1]; o[2] = v.v[2]; }
 }
 
-template <bool PROD>
+template <bool PROD, bool COLNUM = PROD>
 int run_hint(const u64 *num, u32 dimNum, const u64 *den, u32 dimDen, u64 n, u64 *out, hipStream_t st) {
     if (n == 0) return PIL2GL_OK;
     if (!num || !den || !out) return fail(PIL2GL_EINVAL, "null buffer");
@@ -127,11 +134,12 @@ int run_hint(const u64 *num, u32 dimNum, const u64 *den, u32 dimDen, u64 n, u64 
     u64 *tmp, *totals;
     P2_TRY(scratch(SCR_HINT_TMP, n * 3, &tmp));
     P2_TRY(scratch(SCR_HINT_TOTALS, nb * 3, &totals));
-    hint_scan1<PROD><<<(unsigned)nb, SCAN_THREADS, 0, st>>>(num, dimNum, den, dimDen, n, tmp, totals);
+    hint_scan1<PROD, COLNUM><<<(unsigned)nb, SCAN_THREADS, 0, st>>>(num, dimNum, den, dimDen, n, tmp, totals);
     KERNEL_CHECK();
     hint_scan2<PROD><<<1, SCAN_THREADS, 0, st>>>(totals, nb);
     KERNEL_CHECK();
-    hint_scan3<PROD><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tmp, totals, n, (dimNum == 3 || dimDen == 3) ? 3u : 1u, out);
+    const u32 dimOut = (dimNum == 3 || dimDen == 3) ? 3u : 1u;
+    hint_scan3<PROD><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tmp, totals, n, dimOut, out, dimOut, 0);
     KERNEL_CHECK();
     return PIL2GL_OK;
 }
@@ -147,6 +155,179 @@ int pil2gl_gprod_dev(const uint64_t *num, uint32_t dimNum, const uint64_t *den, 
 int pil2gl_gsum_dev(const uint64_t *num, uint32_t dimNum, const uint64_t *den, uint32_t dimDen, uint64_t n, uint64_t *out, void *stream) {
     P2_TRY(ensure_init());
     return run_hint<false>(num, dimNum, den, dimDen, n, out, as_stream(stream));
+}
+int pil2gl_gsum_col_dev(const uint64_t *num, uint32_t dimNum, const uint64_t *den, uint32_t dimDen, uint64_t n, uint64_t *out, void *stream) {
+    P2_TRY(ensure_init());
+    return run_hint<false, true>(num, dimNum, den, dimDen, n, out, as_stream(stream));
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The lookup grand sum (include/pil2gl.h states it; tests/logup_sum_ref.py restates it over integers):
+//   s[i] = s[i-1] + sum_u coef_u w_u[i] / D_u[i],   D_u[i] = sum_j v_j[i] alpha^(k_u - j) + busId_u + beta
+// One fused first pass beside hint_scan1, then hint_scan2<false> and hint_scan3<false> as they are.  A lane takes its SCAN_ITEMS rows;
+// for each row it folds the terms into ONE fraction N / D in registers,
+//   N <- N D_u + (coef_u w_u) D,   D <- D D_u        (a zero D_u is left out of both: the term adds 0 and spoils nothing)
+// so that a row costs one inverse whatever nTerms is, and the lane inverts its rows' D together: one e3_inv a lane, as hint_scan1.
+// No denominator column is ever written.  The powers of alpha and busId + beta are made on the host, so a tuple column costs three
+// base products (a base value scaling an extension power), not an extension product.  Base products a row, nTerms terms of k columns:
+// nTerms (3 k + 16) for the fold (two extension products of 6, a scaling of 3, coef w), 6 + 6 + 6 for the shared inversion and the
+// ratio, and 1/8 of the lane's e3_inv.
+// The term table travels as a kernel argument and is read with wave-uniform indices (scalar loads from the kernel-argument segment):
+// nothing is copied to the device and nothing lies in a private segment.
+// Safety: nothing read from a matrix is used as an address; a row index is checked against n before any load.
+namespace {
+
+using logupplan::MAX_TERMS;
+
+struct LogupTerm {
+    const u64 *base, *sel;                           // sel null: w = 1
+    u64 stride, selStride, selCol;
+    u32 cols[tupleside::MAX_K];
+    u32 k;
+    u64 coef;
+    E3 cst;                                          // busId + beta
+};
+struct LogupJob {
+    LogupTerm t[MAX_TERMS];
+    E3 apow[tupleside::MAX_K + 1];                   // apow[e] = alpha^e, e = 1 .. 16
+    u32 nTerms;
+    u64 n;
+};
+
+// f(k) for k = 0 .. SCAN_ITEMS - 1 with k a compile-time constant: the lane's per-row arrays are indexed by constants from the start
+// and live in registers (a #pragma unroll around loops with run-time trip counts left them in the private segment)
+template <class Fn, int... K> __device__ __forceinline__ void each_item(Fn f, std::integer_sequence<int, K...>) { (f(std::integral_constant<int, K>{}), ...); }
+template <class Fn> __device__ __forceinline__ void each_item(Fn f) { each_item(f, std::make_integer_sequence<int, SCAN_ITEMS>{}); }
+template <class Fn, int... K> __device__ __forceinline__ void each_item_down(Fn f, std::integer_sequence<int, K...>) { (f(std::integral_constant<int, SCAN_ITEMS - 1 - K>{}), ...); }
+template <class Fn> __device__ __forceinline__ void each_item_down(Fn f) { each_item_down(f, std::make_integer_sequence<int, SCAN_ITEMS>{}); }
+
+__global__ void __launch_bounds__(SCAN_THREADS) logup_scan1(const LogupJob J, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
+    __shared__ E3 sh[SCAN_THREADS];
+    const u64 base = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_ITEMS;
+    // the lane's rows as fractions num / den, den never zero; rows at or past n stay 0 / 1.  The terms are the outer loop, so that a term's
+    // table entries are read once for the lane's rows and the rows' loads of one column are in flight together
+    E3 num[SCAN_ITEMS], den[SCAN_ITEMS], loc[SCAN_ITEMS];
+    each_item([&](auto k) { num[k] = ident<false>(); den[k] = ident<true>(); });
+    for (u32 u = 0; u < J.nTerms; u++) {
+        const LogupTerm &T = J.t[u];
+        const E3 cst = T.cst;
+        each_item([&](auto k) { loc[k] = cst; });
+        for (u32 j = 0; j < T.k; j++) {
+            const E3 ap = J.apow[T.k - j];
+            const u64 *p = T.base + base * T.stride + T.cols[j];
+            each_item([&](auto k) { if (base + k < J.n) loc[k] = e3_add(loc[k], e3_scale(ap, p[k * T.stride])); });
+        }
+        each_item([&](auto k) {
+            const u64 i = base + k;
+            const E3 d = loc[k];
+            if (i >= J.n || !(d.v[0] | d.v[1] | d.v[2])) return;             // a zero D_u: the term adds 0 and is left out of the product
+            const u64 c = T.sel ? mul(T.sel[i * T.selStride + T.selCol], T.coef) : T.coef;
+            num[k] = e3_add(e3_mul(num[k], d), e3_scale(den[k], c));
+            den[k] = e3_mul(den[k], d);
+        });
+    }
+    E3 acc = ident<true>();
+    each_item([&](auto k) {
+        loc[k] = acc;                                   // the product of the rows' den before this one
+        acc = e3_mul(acc, den[k]);
+    });
+    E3 ai = (acc.v[1] | acc.v[2]) ? e3_inv(acc) : E3{ { inv(acc.v[0]), 0, 0 } };
+    each_item_down([&](auto k) {
+        const E3 di = e3_mul(ai, loc[k]);               // 1 / den_k
+        ai = e3_mul(ai, den[k]);
+        loc[k] = e3_mul(num[k], di);
+    });
+    E3 run = ident<false>();
+    each_item([&](auto k) { run = e3_add(run, loc[k]); loc[k] = run; });      // rows at or past n hold num = 0
+    E3 bt;
+    const E3 ex = block_exclusive<false>(run, sh, &bt);
+    each_item([&](auto k) { const u64 i = base + k; if (i < J.n) st3(tmp, i, e3_add(ex, loc[k])); });
+    if (threadIdx.x == 0) st3(totals, blockIdx.x, bt);
+}
+
+u64 h_canon(u64 a) { return a >= P ? a - P : a; }
+
+// every launch of a call, on st; the arguments have passed logupplan::check_call() and n > 0, the pointers are the device's
+int logup_launch(const pil2gl_logup_term *terms, u32 nTerms, const u64 *alpha, const u64 *beta, u64 *out, u64 outStride, u64 outCol, u64 n, hipStream_t st) {
+    LogupJob J{};
+    const u64 a[3] = { h_canon(alpha[0]), h_canon(alpha[1]), h_canon(alpha[2]) };
+    u64 pw[3] = { 1, 0, 0 };
+    for (u32 e = 1; e <= tupleside::MAX_K; e++) {
+        u64 r[3];
+        h_e3_mul(pw, a, r);
+        for (int c = 0; c < 3; c++) J.apow[e].v[c] = pw[c] = r[c];
+    }
+    for (u32 u = 0; u < nTerms; u++) {
+        const pil2gl_tuple_side &s = terms[u].side;
+        LogupTerm &T = J.t[u];
+        T.base = s.base; T.sel = s.sel; T.stride = s.stride; T.selStride = s.selStride; T.selCol = s.selCol;
+        T.k = (u32)terms[u].k;
+        for (u32 j = 0; j < T.k; j++) T.cols[j] = (u32)s.hostCols[j];
+        T.coef = terms[u].coef[0];
+        T.cst = E3{ { h_add(h_canon(beta[0]), terms[u].busId[0]), h_canon(beta[1]), h_canon(beta[2]) } };
+    }
+    J.nTerms = nTerms; J.n = n;
+    const u64 nb = hintplan::blocks(n);
+    u64 *tmp, *totals;
+    P2_TRY(scratch(SCR_HINT_TMP, n * 3, &tmp));
+    P2_TRY(scratch(SCR_HINT_TOTALS, nb * 3, &totals));
+    logup_scan1<<<(unsigned)nb, SCAN_THREADS, 0, st>>>(J, tmp, totals);
+    KERNEL_CHECK();
+    hint_scan2<false><<<1, SCAN_THREADS, 0, st>>>(totals, nb);
+    KERNEL_CHECK();
+    hint_scan3<false><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tmp, totals, n, 3, out, outStride, outCol);
+    KERNEL_CHECK();
+    return PIL2GL_OK;
+}
+
+int logup_check(const pil2gl_logup_term *terms, u64 nTerms, const u64 *alpha, const u64 *beta, const u64 *out, u64 outStride, u64 outCol, u64 n, bool dev) {
+    char why[96];
+    if (const char *msg = logupplan::check_call(terms, nTerms, alpha, beta, out, outStride, outCol, n, 1, dev, why)) return fail(PIL2GL_EINVAL, "%s", msg);
+    return PIL2GL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_logup_sum_plan(uint64_t n, uint64_t nTerms, uint32_t elemWords, uint32_t *outInfo, uint64_t *workBytes) {
+    if (workBytes) *workBytes = 0;
+    if (const char *msg = logupplan::check(n, nTerms, elemWords)) return fail(PIL2GL_EINVAL, "%s", msg);
+    const logupplan::Plan p = logupplan::plan(n, elemWords);
+    if (outInfo) {
+        outInfo[0] = p.threads; outInfo[1] = p.items; outInfo[2] = p.blocks; outInfo[3] = p.launches; outInfo[4] = p.depth;
+        outInfo[5] = logupplan::out_width(elemWords);
+    }
+    if (workBytes) *workBytes = p.bytes;
+    return PIL2GL_OK;
+}
+
+int pil2gl_logup_sum_dev(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                         uint64_t *out, uint64_t outStride, uint64_t outCol, uint64_t n, void *stream) {
+    P2_TRY(logup_check(hostTerms, nTerms, hostAlpha, hostBeta, out, outStride, outCol, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return logup_launch(hostTerms, (u32)nTerms, hostAlpha, hostBeta, out, outStride, outCol, n, as_stream(stream));
+}
+
+// host matrices, each staged up to the last element touched; out's matrix goes up as it is and comes back with the column written
+int pil2gl_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                     uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n) {
+    P2_TRY(logup_check(hostTerms, nTerms, hostAlpha, hostBeta, hostOut, outStride, outCol, n, false));
+    if (!n) return PIL2GL_OK;
+    pil2gl_logup_term terms[MAX_TERMS];
+    const u64 outWords = tupleside::span_bytes(n, outStride, outCol + 2, 1) / 8;
+    u64 total = smapplan::pad16(outWords);
+    for (u64 u = 0; u < nTerms; u++) { terms[u] = hostTerms[u]; total += tupleside::staged_words(terms[u].side, n, terms[u].k, 1); }
+    Stage s(total);
+    P2_TRY(s.rc());
+    for (u64 u = 0; u < nTerms; u++) tupleside::stage_side(s, terms[u].side, n, terms[u].k, 1);
+    u64 *dOut = (u64 *)s.put(hostOut, outWords);
+    P2_TRY(s.rc());
+    P2_TRY(logup_launch(terms, (u32)nTerms, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0));
+    return s.get(hostOut, dOut, outWords);
 }
 
 }  // extern "C"

@@ -19,6 +19,14 @@
 //   -> { matched, missing: null | { side, row, message() } }: matched = the selected f rows whose tuple t holds (the sum of m); missing = the
 //      smallest (side, row) of f whose tuple no selected row of t holds; m is written in full either way
 //   formatMissing(missing, values)   the message; lookupMultProbe()   the library's debug entry
+// and the grand-sum column that consumes m (csrc/logup_sum_plan.h; include/pil2gl.h states it):
+//   logupSum(terms, alpha, beta, out, n, opts) / logupSumDev(terms, alpha, beta, out, n, opts)
+//       terms: 1 .. 9 sides as above, each with coef and busId beside buf / stride / cols / sel: a BigInt (canonical) over Goldilocks, a
+//       BigUint64Array(4) or Uint8Array(32) of Montgomery words with opts.bn128; sel is the NUMERATOR column (its field value multiplies
+//       coef; for t it is m) or undefined for 1.  alpha, beta: BigUint64Array(3), a cubic-extension element; BigUint64Array(4) /
+//       Uint8Array(32) with opts.bn128.  out: { buf, stride, col }: over Goldilocks the words col .. col + 2 of a row of `stride` words,
+//       over Fr one element.  Written in place for every row; s[n-1] is the hint's result.  logupSumDev only enqueues (opts.stream).
+//   logupSumPlan(n, nTerms, bn128)   the library's plan
 // Node 12: no optional chaining.
 "use strict";
 const { addon, DevBuffer, isDev } = require("./native.js");
@@ -141,4 +149,36 @@ const lookupMultiplicities = (fs, t, m, n, opts) => multiplicities(false, fs, t,
 const lookupMultiplicitiesDev = (fs, t, m, n, opts) => multiplicities(true, fs, t, m, n, opts);
 const lookupMultProbe = () => Number(addon.lookupMultProbe());
 
-module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };
+// ---- lookup grand sum ----
+function logup(dev, termsIn, alpha, beta, outIn, n, opts) {
+    const bn = !!(opts && opts.bn128), ew = bn ? 4 : 1, width = bn ? 1 : 3;
+    if (!Array.isArray(termsIn) || termsIn.length < 1 || termsIn.length > 9) throw new Error("terms must be an array of 1 .. 9 terms");
+    if (!outIn || !(outIn.stride > 0) || !(outIn.col >= 0)) throw new Error("out must be { buf, stride, col }");
+    const elem = (v, what, words) => {
+        if (!bn && words === 1) { if (typeof v !== "bigint") throw new Error(what + " must be a BigInt"); return [v, 0n, 0n, 0n]; }
+        const w = Array.from(stage.asWords(v));
+        if (w.length !== words) throw new Error(what + " must hold " + words + " words");
+        return w.concat([0n, 0n, 0n, 0n]).slice(0, 4);
+    };
+    const terms = termsIn.map((t, u) => {
+        const s = side(t, "term " + u, n, ew, dev);
+        if (s.cols.length < 1 || s.cols.length > 16) throw new Error("term " + u + ": 1 .. 16 columns");
+        s.coef = elem(t.coef, "coef of term " + u, ew); s.busId = elem(t.busId, "busId of term " + u, ew);
+        return s;
+    });
+    const out = side({ buf: outIn.buf, stride: outIn.stride, cols: [outIn.col, outIn.col + width - 1] }, "out", n, ew, dev);
+    const ptr = (b) => dev && b ? b.ptr : 0n;
+    const head = [n, terms.length, ptr(out.buf), out.stride, outIn.col].concat(elem(alpha, "alpha", bn ? 4 : 3), elem(beta, "beta", bn ? 4 : 3));
+    const fourteen = terms.map((x) => [ptr(x.buf), x.stride, x.cols.length].concat(x.sel ? [ptr(x.sel.buf), x.sel.stride, x.sel.col] : [0n, 0, 0], x.coef, x.busId));
+    const slots = terms.map((x) => x.cols.concat(new Array(16 - x.cols.length).fill(0)));
+    const desc = BigUint64Array.from(head.concat(...fourteen, ...slots).map((v) => BigInt(v)));
+    if (dev) { addon.logupSumDev(desc, ew, opts && opts.stream); return outIn; }
+    addon.logupSum(desc, [].concat(...terms.map((x) => [x.buf, x.sel ? x.sel.buf : null]), [out.buf]), ew);
+    if (out.buf.buffer !== outIn.buf.buffer) new Uint8Array(outIn.buf.buffer, outIn.buf.byteOffset, outIn.buf.byteLength).set(new Uint8Array(out.buf.buffer));      // bytes off 8: asWords copied
+    return outIn;
+}
+const logupSum = (terms, alpha, beta, out, n, opts) => logup(false, terms, alpha, beta, out, n, opts);
+const logupSumDev = (terms, alpha, beta, out, n, opts) => logup(true, terms, alpha, beta, out, n, opts);
+const logupSumPlan = (n, nTerms, bn128) => addon.logupSumPlan(n, nTerms, bn128 ? 4 : 1);
+
+module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, logupSum, logupSumDev, logupSumPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };

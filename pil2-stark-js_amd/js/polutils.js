@@ -3,6 +3,9 @@
 //   buildOneRowZerofierInv(buffTo, offset, F, buffZhInv, nBits, nBitsExt, rowIndex, stark)  polutils.js:57-71
 //   buildFrameZerofierInv(buffTo, offset, F, buffZhInv, nBits, nBitsExt, frame, stark)      polutils.js:74-102
 //   calculateZ(F, num, den), calculateS(F, num, den), calculateH1H2(F, f, t)                polutils.js:105-164
+// and, beside them, the grand sum with a COLUMN numerator that a pil2 gsum hint over a multiplicity needs (no reference counterpart):
+//   calculateSCol(F, num, den)                          s[i] = s[i-1] + num[i] / den[i], num an array like den
+//   calculateSColDev(num, dimNum, den, dimDen, n, out, stream)   the same on DevBuffers (dense columns of dim 1 or 3); only enqueues; -> out
 // `F` and `buffZhInv` are accepted and ignored (the field is Goldilocks, the device rebuilds what it needs).
 // Only the stark = true forms exist (coset 7 * <w>): the plain-subgroup forms invert zero and are not used by the prover.
 // One deviation, on purpose: buildZhInv honours `offset` when it fills rows >= 2^extendBits; the reference's second loop
@@ -74,6 +77,19 @@ module.exports.calculateS = async function calculateS(F, num, den) {
     const N = den.length, pn = pack([num]), pd = pack(den), dimOut = Math.max(pn.dim, pd.dim);
     const [s] = onDevice([pn.a, pd.a], [N * dimOut], ([dn, dd], [ds]) => addon.gsumDev(dn, pn.dim, dd, pd.dim, N, ds));
     return unpack(s, dimOut);
+};
+module.exports.calculateSCol = async function calculateSCol(F, num, den) {
+    const N = den.length, pn = pack(num), pd = pack(den), dimOut = Math.max(pn.dim, pd.dim);
+    if (num.length !== N) throw new Error("calculateSCol: num and den must have the same length");
+    const [s] = onDevice([pn.a, pd.a], [N * dimOut], ([dn, dd], [ds]) => addon.gsumColDev(dn, pn.dim, dd, pd.dim, N, ds));
+    return unpack(s, dimOut);
+};
+module.exports.calculateSColDev = function calculateSColDev(num, dimNum, den, dimDen, n, out, stream) {
+    const dimOut = Math.max(dimNum, dimDen);
+    for (const [b, words, what] of [[num, n * dimNum, "num"], [den, n * dimDen, "den"], [out, n * dimOut, "out"]])
+        if (!isDev(b) || b.length < words) throw new Error("calculateSColDev: " + what + " must be a DevBuffer of at least " + words + " words");
+    addon.gsumColDev(num.ptr, dimNum, den.ptr, dimDen, n, out.ptr, stream);
+    return out;
 };
 module.exports.calculateH1H2 = function calculateH1H2(F, f, t) {
     const pf = pack(f), pt = pack(t);

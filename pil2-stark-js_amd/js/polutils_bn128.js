@@ -2,12 +2,13 @@
 // resolves its gprod / gsum hints over (src/prover/hints_helpers.js:92-113), computed by libpil2gl on the MI355X (csrc/bn_scan.hip).
 //   calculateZ(F, num, den)   z[0] = 1, z[i] = z[i-1] num[i-1] / den[i-1]
 //   calculateS(F, num, den)   s[i] = s[i-1] + num / den[i], num ONE element
+//   calculateSCol(F, num, den)   s[i] = s[i-1] + num[i] / den[i], num a column like den (a pil2 gsum hint over a multiplicity; no reference counterpart)
 //   batchInverse(F, a)        a[i]^-1
 //   calculateH1H2(F, f, t)    [h1, h2] of polutils.js:105-130, the h1h2 hint (hints_helpers.js:115-121; csrc/bn_h1h2.hip): elements are
 //                             compared as their 32 bytes; a value of f that t lacks throws the reference's message
 // Array forms: arrays of Uint8Array(32), Fr Montgomery bytes (what curve.Fr keeps), in and out; `F` is accepted and ignored.  They are
 // packed, staged through device copies and unpacked, as js/polutils.js does for Goldilocks.
-// Resident forms (calculateZDev, calculateSDev, batchInverseDev): a column is { buf: DevBuffer, stride = 1, offset = 0 }, element i at
+// Resident forms (calculateZDev, calculateSDev, calculateSColDev, batchInverseDev): a column is { buf: DevBuffer, stride = 1, offset = 0 }, element i at
 // element offset + i * stride of buf (a section of prover_helpers_bn128.js: stride = its width, offset = the column).  Nothing is staged;
 // the result is written into the `out` column and `out` is returned.  The hint's `result` field is element n - 1: lastElement(out, n).
 // calculateH1H2Dev(f, t, n, h1, h2, stream) writes two columns and returns [h1, h2]; h1 and h2 may be two columns of one section, and
@@ -42,6 +43,11 @@ async function calculateZ(F, num, den) {
 async function calculateS(F, num, den) {
     const n = den.length, c = pack([num], "num");
     return onDevice([pack(den, "den")], n, 1, ([dd, ds]) => addon.bn128GsumDev(c, dd, 1, n, ds, 1))[0];
+}
+async function calculateSCol(F, num, den) {
+    const n = den.length;
+    if (num.length !== n) throw new Error("polutils_bn128: num and den must have the same length");
+    return onDevice([pack(num, "num"), pack(den, "den")], n, 1, ([dn, dd, ds]) => addon.bn128GsumColDev(dn, 1, dd, 1, n, ds, 1))[0];
 }
 function batchInverse(F, a) {
     const n = a.length;
@@ -92,6 +98,11 @@ function calculateSDev(num, den, n, out, stream) {
     addon.bn128GsumDev(pack([num], "num"), b.ptr, b.stride, n, o.ptr, o.stride, stream);
     return out;
 }
+function calculateSColDev(num, den, n, out, stream) {
+    const a = column(num, rows(n), "num"), b = column(den, n, "den"), o = column(out, n, "out");
+    addon.bn128GsumColDev(a.ptr, a.stride, b.ptr, b.stride, n, o.ptr, o.stride, stream);
+    return out;
+}
 // out may be the same column as src (in place)
 function batchInverseDev(src, n, out, stream) {
     const a = column(src, rows(n), "src"), o = column(out, n, "out");
@@ -115,4 +126,4 @@ function lastElement(col, n) {
     return new Uint8Array(col.buf.slice(off, off + 4).buffer);
 }
 
-module.exports = { calculateZ, calculateS, batchInverse, calculateH1H2, calculateZDev, calculateSDev, batchInverseDev, calculateH1H2Dev, lastElement };
+module.exports = { calculateZ, calculateS, calculateSCol, batchInverse, calculateH1H2, calculateZDev, calculateSDev, calculateSColDev, batchInverseDev, calculateH1H2Dev, lastElement };

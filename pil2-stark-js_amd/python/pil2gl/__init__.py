@@ -218,6 +218,14 @@ def calculateS(num, den, dimNum=3, dimDen=3, out=None):
     return _hint("pil2gl_gsum_dev", num, den, dimNum, dimDen, out)
 
 
+def calculateS_col(num, den, dimNum=1, dimDen=3, out=None):
+    """calculateS with a COLUMN numerator (a pil2 gsum hint whose numerator is a multiplicity): s[i] = s[i-1] + num[i] / den[i]"""
+    n = int(np.prod(den.shape)) // dimDen
+    if int(np.prod(num.shape)) < n * dimNum:                          # the library cannot know where a buffer ends
+        raise Pil2glError("num holds %d words, %d rows of dimension %d need more" % (int(np.prod(num.shape)), n, dimNum))
+    return _hint("pil2gl_gsum_col_dev", num, den, dimNum, dimDen, out)
+
+
 def calculateH1H2(f, t, dim=1):
     """polutils.js:105 calculateH1H2(F, f, t) on device columns -> (h1, h2)"""
     n = int(np.prod(t.shape)) // dim

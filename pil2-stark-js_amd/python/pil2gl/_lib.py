@@ -57,6 +57,11 @@ class TupleSide(C.Structure):
                 ("selStride", C.c_uint64), ("selCol", C.c_uint64)]
 
 
+class LogupTerm(C.Structure):
+    """include/pil2gl.h pil2gl_logup_term: one term of the lookup grand sum (its side, its k, coef and busId as host elements)"""
+    _fields_ = [("side", TupleSide), ("k", C.c_uint64), ("coef", C.c_uint64 * 4), ("busId", C.c_uint64 * 4)]
+
+
 class G1Poly(C.Structure):
     """include/pil2gl.h pil2gl_g1_poly: one packed polynomial of a G1 commit batch"""
     _fields_ = [("first", C.c_uint64), ("rows", C.c_uint64), ("m", C.c_uint32), ("reserved", C.c_uint32)]
@@ -162,6 +167,7 @@ SIGNATURES = {
     "pil2gl_debug_transform_walk_cover": (_I, [_U32, _U32, _U64, _U32, _U32, _U32, C.POINTER(_U64)]),
     "pil2gl_gprod_dev": (_I, [vp, _U32, vp, _U32, _U64, vp, vp]),
     "pil2gl_gsum_dev": (_I, [vp, _U32, vp, _U32, _U64, vp, vp]),
+    "pil2gl_gsum_col_dev": (_I, [vp, _U32, vp, _U32, _U64, vp, vp]),
     "pil2gl_h1h2_dev": (_I, [vp, vp, _U64, _U32, vp, vp, vp]),
     "pil2gl_debug_hint_plan": (_I, [_U64, C.POINTER(_U32)]),
     "pil2gl_debug_h1h2_home": (_U64, [vp, _U32, _U64]),
@@ -214,6 +220,8 @@ SIGNATURES = {
     "pil2gl_bn128_gprod_dev": (_I, [vp, _U64, vp, _U64, _U64, vp, _U64, vp]),
     "pil2gl_bn128_gsum": (_I, [vp, vp, _U64, _U64, vp, _U64]),
     "pil2gl_bn128_gsum_dev": (_I, [vp, vp, _U64, _U64, vp, _U64, vp]),
+    "pil2gl_bn128_gsum_col": (_I, [vp, _U64, vp, _U64, _U64, vp, _U64]),
+    "pil2gl_bn128_gsum_col_dev": (_I, [vp, _U64, vp, _U64, _U64, vp, _U64, vp]),
     "pil2gl_debug_bn128_scan_plan": (_I, [_U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
     "pil2gl_bn128_h1h2": (_I, [vp, _U64, vp, _U64, _U64, vp, _U64, vp, _U64, C.POINTER(_U64)]),
     "pil2gl_bn128_h1h2_dev": (_I, [vp, _U64, vp, _U64, _U64, vp, _U64, vp, _U64, C.POINTER(_U64), vp]),
@@ -250,6 +258,11 @@ SIGNATURES = {
     "pil2gl_lookup_mult": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), vp, _U64, _U64, _U64, _U64, vp]),
     "pil2gl_bn128_lookup_mult": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), vp, _U64, _U64, _U64, _U64, vp]),
     "pil2gl_debug_lookup_mult_probe": (_U64, []),
+    "pil2gl_logup_sum_plan": (_I, [_U64, _U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_logup_sum_dev": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_bn128_logup_sum_dev": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_logup_sum": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64]),
+    "pil2gl_bn128_logup_sum": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64]),
     "pil2gl_selftest_field":(_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_ext": (_I, [vp, vp, _U64, vp, vp]),
     "pil2gl_selftest_products": (_I, [vp, vp, _U64, vp, vp, vp]),

@@ -11,7 +11,7 @@
                                   <-> src/prover/prover_helpers.js:31-259 calculateExps over ctx.F = curve.Fr (Montgomery words in and out)
   poly_div / poly_eval / poly_plan <-> Polynomial.divZh / divByXNSubValue / evaluate as fflonk_prover_helpers.js:147-148, :212 use them
   poly_fma / poly_degree          <-> Polynomial.add / sub / mulScalar / byXSubValue / byXNSubValue / degree as shplonkjs open (:212) uses them
-  batch_inverse / gprod / gsum / scan_plan
+  batch_inverse / gprod / gsum / gsum_col / scan_plan
                                   <-> F.batchInverse, calculateZ, calculateS of src/helpers/polutils.js:132-164 over curve.Fr, as
                                       hints_helpers.js:92-113 resolves gprod / gsum hints (Montgomery words in and out)
   h1h2 / h1h2_plan                <-> calculateH1H2 of src/helpers/polutils.js:105-130 over curve.Fr, the h1h2 hint (hints_helpers.js:115-121)
@@ -451,6 +451,16 @@ def gsum(num_elem, den, n=None, den_stride=1, out=None, out_stride=1):
     out = _out_column(den, n, out_stride, out)
     e = _host_elems(num_elem, "num_elem", 1)
     _dispatch("pil2gl_bn128_gsum", den, _ptr(e), _ptr(den), den_stride, n, _ptr(out), out_stride)
+    return out
+
+
+def gsum_col(num, den, n=None, num_stride=1, den_stride=1, out=None, out_stride=1):
+    """calculateS with a COLUMN numerator: out[i] = out[i-1] + num[i] / den[i]; columns, strides, zeros and aliasing as gprod's"""
+    _same_side(num, den, out)
+    n = _column(den, n, den_stride, "den")
+    _column(num, n, num_stride, "num")
+    out = _out_column(den, n, out_stride, out)
+    _dispatch("pil2gl_bn128_gsum_col", den, _ptr(num), num_stride, _ptr(den), den_stride, n, _ptr(out), out_stride)
     return out
 
 

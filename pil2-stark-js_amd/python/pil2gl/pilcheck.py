@@ -12,7 +12,7 @@ returns the library's five words (kind, row, partner, cntF, cntT) -- include/pil
 (0, NONE, NONE, 0, 0).  No arithmetic happens here: hashing, counting and judging are the library's.
 
 The column that PROVES a lookup in pil2, the multiplicities of its grand sum (csrc/lookup_mult.hip), is lookup_mult / lookup_mult_dev at the
-end of this module.
+end of this module, and after it the grand sum that consumes it (logup_sum / logup_sum_dev).
 """
 import ctypes as C
 
@@ -183,3 +183,65 @@ def lookup_mult_dev(fs, t, m, n, field="gl"):
     """lookup_mult on device tensors, e.g. columns of the stage-1 buffer with m one more column of it; the working buffer comes from the
     plan and lives for the call; blocks for the report"""
     return _mult(True, fs, t, m, n, field)
+
+
+# ---- lookup grand sum: the logUp column s from f, t and m (csrc/logup_sum_plan.h; include/pil2gl.h states it) ----
+#     lookup_mult_dev([(cm1, [7, 3])], (cm1, [0, 1]), (cm1, 12), n)
+#     logup_sum_dev([(cm1, [7, 3], None, 1, bus), (cm1, [0, 1], (cm1, 12), P - 1, bus)], alpha, beta, (cm2, 0), n)
+# A term is (matrix, cols, numerator-or-None, coef, bus_id) or that with the matrix's stride as a sixth part; the numerator is a selector
+# as above (its FIELD VALUE multiplies coef; for t it is m).  coef and bus_id are integers over Goldilocks (canonical) and 4 Montgomery
+# words over Fr; alpha and beta are 3 words of a cubic-extension element, or 4 Montgomery words.  out is (matrix, col) or (matrix, col,
+# stride): over Goldilocks a matrix of u64 words whose columns col .. col + 2 take s, over Fr one element column.  Written in place.
+def logup_sum_plan(n, n_terms=1, field="gl"):
+    """pil2gl_logup_sum_plan (host-only): the launch geometry, the launches and the working bytes"""
+    info = (C.c_uint32 * 6)()
+    nbytes = C.c_uint64()
+    call("pil2gl_logup_sum_plan", n, n_terms, _WORDS[field], info, C.byref(nbytes))
+    names = ("threads", "items", "blocks", "launches", "depth", "outWidth")
+    return dict(zip(names, (int(x) for x in info)), workBytes=nbytes.value)
+
+
+def _logup(dev, terms, alpha, beta, out, n, field):
+    from ._lib import LogupTerm, TupleSide
+    words = _WORDS[field]
+    ptr = (lambda a: _ptr(a)) if dev else (lambda a: None if a is None else a.ctypes.data)
+    keep = []                                                                    # the column arrays live until the call returns
+    T = (LogupTerm * max(len(terms), 1))()
+    for u, spec in enumerate(terms[:len(T)]):
+        spec = tuple(spec) + (None,) * (6 - len(spec))
+        b, stride, cols, sm, sstride, scol = _side(spec[0], spec[1], spec[5], spec[2], n, words, dev, "term %d" % u)
+        keep.extend((b, cols, sm))
+        T[u].side = TupleSide(ptr(b), stride, cols.ctypes.data, ptr(sm), sstride, scol)
+        T[u].k = cols.size
+        for name, v in (("coef", spec[3]), ("busId", spec[4])):
+            w = np.ascontiguousarray([v] if words == 1 else v, np.uint64).reshape(-1)
+            if w.size != words:
+                raise Pil2glError("term %d: %s is %d words" % (u, name, words))
+            for i in range(words):
+                getattr(T[u], name)[i] = int(w[i])
+    ch = [np.ascontiguousarray(c, np.uint64).reshape(-1) for c in (alpha, beta)]
+    if any(c.size != (3 if words == 1 else 4) for c in ch):
+        raise Pil2glError("alpha and beta are %d words each" % (3 if words == 1 else 4))
+    if not dev and not (isinstance(out[0], np.ndarray) and out[0].dtype == np.uint64 and out[0].flags.c_contiguous and out[0].flags.writeable):
+        raise Pil2glError("out: the host form writes in place and takes a C-contiguous writeable uint64 array")
+    om, held, ostride = _matrix(out[0], out[2] if len(out) > 2 else None, words, dev, "out")
+    top = out[1] + (2 if words == 1 else 0)
+    if n and held < ((n - 1) * ostride + top + 1) * words:
+        raise Pil2glError("out holds %d words, %d rows of stride %d need more" % (held, n, ostride))
+    name = "pil2gl_logup_sum" if words == 1 else "pil2gl_bn128_logup_sum"
+    args = [T, len(terms), C.c_void_p(ch[0].ctypes.data), C.c_void_p(ch[1].ctypes.data), ptr(om), ostride, out[1], n]
+    if dev:
+        call(name + "_dev", *args, _stream())
+    else:
+        call(name, *args)
+    return out[0]
+
+
+def logup_sum(terms, alpha, beta, out, n, field="gl"):
+    """the grand-sum column of a lookup: host matrices; out's column is written in place -> out's matrix (s[n-1] is the hint's result)"""
+    return _logup(False, terms, alpha, beta, out, n, field)
+
+
+def logup_sum_dev(terms, alpha, beta, out, n, field="gl"):
+    """logup_sum on device tensors, e.g. columns of the stage-1 buffer with m one of them; only enqueues on the current stream"""
+    return _logup(True, terms, alpha, beta, out, n, field)
