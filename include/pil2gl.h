@@ -33,7 +33,7 @@
  *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi[_step] / cols_dot_ext /
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
  *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, compute_fri_pol, build_lev (small host tables),
- *      h1h2 and bn128_h1h2 (the missing row comes back), conn_check and bn128_conn_check, tuple_check and bn128_tuple_check, lookup_mult and bn128_lookup_mult (the report comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
+ *      h1h2 and bn128_h1h2 (the missing row comes back), conn_check and bn128_conn_check, tuple_check and bn128_tuple_check, lookup_mult and bn128_lookup_mult, range_mult and bn128_range_mult (the report comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
  *      land_rows, wtns_gather, bn128_wtns_gather, conn_pols and bn128_conn_pols with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
  *    So do the host-pointer verifier calls roots_from_group_proofs and bn128_roots_from_group_proofs (roots copied to host memory).
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, logup_sum_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, logup_sum_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -1010,6 +1010,58 @@ int pil2gl_bn128_lookup_mult(const pil2gl_tuple_side *hostF, uint64_t nF, const 
                              uint64_t mCol, uint64_t n, uint64_t k, uint64_t *hostReport /* [4] */);
 /* host-only, no device: the longest distance, in slots, between a tuple of the last call's hash table and its home slot */
 uint64_t pil2gl_debug_lookup_mult_probe(void);
+
+/* ---- range-check multiplicities: the logUp column m of `selF_s f_s in [lo, lo + size)`, s < nF (csrc/range_mult.hip, csrc/range_mult_plan.h) ----
+ * The commonest lookup of a pil2 witness is a range check.  Its table is an arithmetic progression: the counter of a value v is v - lo, and
+ * the block above would hash, probe and build for nothing -- and need the range materialised as a column t.  This block counts by direct
+ * addressing and takes no t.  The statement is this header's own (tests/range_mult_ref.py restates it over Python integers):
+ *   n rows, n <= 2^28; 1 <= nF <= 8 sides of f, each a pil2gl_tuple_side of which only hostCols[0] is read (k = 1); the optional selector,
+ *   elements and SELECTED rows are the block above's (Goldilocks words in [p, 2^64) mod p, any 256-bit Fr Montgomery pattern mod r).
+ *   The range is lo, a SIGNED 64-bit integer (negative allowed), and size, 1 <= size <= 2^28; its field elements are lo + j mod p|r, j < size.
+ *   A value v is IN RANGE when (v - lo) mod p|r < size, the difference taken as a full field element (over Fr of the normal form, not of the
+ *   Montgomery pattern).  cnt(j) = the selected rows, over all sides, whose value is lo + j.
+ *   m = column mCol of a matrix (m, mStride) of elemWords-word elements, written for EVERY row i < n: cnt(i - row0) for
+ *   row0 <= i < row0 + size, 0 elsewhere; row0 + size <= n.  The value is a canonical element as the block above writes it: one u64, or the
+ *   Montgomery form of the count.
+ * hostReport is the block above's four words: [0] = kind, 0 clean, 1 = some selected row is out of range; [1] = side, [2] = row: the
+ * lexicographically smallest failing (side, row), both UINT64_MAX when clean; [3] = matched.  The sum of m is `matched`, always; on kind 1 m is
+ * still written in full.  Neither m nor the report depends on the order in which the device's atomics land.
+ * Equivalence: with row0 = 0 the result, m and report, is word for word what pil2gl_[bn128_]lookup_mult gives with k = 1 on the materialised
+ * column t[i] = field(lo + min(i, size - 1)) -- the padding a fixed range column holds; the first-occurrence rule puts its count at row size - 1.
+ * ONE range a call: several ranges stacked in one m column are out of scope; make one call per range, into separate columns.
+ *
+ * pil2gl_range_mult_plan: host-only, no device.  outInfo[0] = path: 0 = a workgroup counts in LDS counters of its own and flushes them once
+ * (size <= the threshold, csrc/range_mult_plan.h), 1 = merged atomics on the global counters; [1] = threads a workgroup of a count launch;
+ * [2] = workgroups of a count launch; [3] = kernel launches of a call, 2 + nF (init, one count a side, write); [4] = bytes of the header, 64;
+ * [5] = counters a workgroup holds in LDS, 0 on path 1.  *scratchBytes = the working buffer, 64 + 4 size rounded up to 16; 0 for n = 0.
+ * PIL2GL_EINVAL: n > 2^28, size outside 1 .. 2^28 or (n > 0) above n, nF outside 1 .. 8, elemWords not 1 or 4.
+ * pil2gl_[bn128_]range_mult_dev: hostF (nF entries) is a HOST pointer to sides whose base and sel are device pointers, 16-byte aligned, only
+ * read.  m = device, 16-byte aligned; its aliasing rule is the block above's: m may meet a matrix that is read only as that matrix (its base,
+ * its stride) with a column that is not read.  scratch = device, 16-byte aligned, scratchBytes >= the plan's, meeting no matrix, m's
+ * included.  The call BLOCKS until the four words of hostReport are on the host.  PIL2GL_EINVAL, before any device call: what the plan
+ * refuses, row0 + size > n, a column >= its stride (an f, a selector or m), a stride >= 2^32 or n stride > 2^58 elements, a null side list,
+ * cols, base, m, scratch or hostReport, a misaligned device pointer, a scratch that is too small or overlaps a matrix, an m that breaks the
+ * aliasing rule.  A refused call leaves a clean report.  n = 0 is PIL2GL_OK, clean, writes nothing and needs no device.
+ * pil2gl_[bn128_]range_mult: host pointers throughout; each matrix is staged up to the last element touched, every part on 16 bytes, m's
+ * matrix goes up as it is and is downloaded again with the column written; the working buffer is taken inside.  Without a device the
+ * compute calls return PIL2GL_ENODEV.
+ * The two debug_ entries are the plan and the resident form with the count path given (0, 1, or 2 = the planner's choice; path 0 takes
+ * size <= 8192), for the tests and tools/bench_range_mult.py; elemWords selects the field. */
+int pil2gl_range_mult_plan(uint64_t n, uint64_t size, uint64_t nF, uint32_t elemWords, uint32_t *outInfo /* [6] */, uint64_t *scratchBytes);
+int pil2gl_range_mult_dev(const pil2gl_tuple_side *hostF, uint64_t nF, int64_t lo, uint64_t size, uint64_t row0, uint64_t *m, uint64_t mStride,
+                          uint64_t mCol, uint64_t n, uint64_t *scratch, uint64_t scratchBytes, uint64_t *hostReport /* [4] */, void *stream);
+int pil2gl_bn128_range_mult_dev(const pil2gl_tuple_side *hostF, uint64_t nF, int64_t lo, uint64_t size, uint64_t row0, uint64_t *m,
+                                uint64_t mStride, uint64_t mCol, uint64_t n, uint64_t *scratch, uint64_t scratchBytes,
+                                uint64_t *hostReport /* [4] */, void *stream);
+int pil2gl_range_mult(const pil2gl_tuple_side *hostF, uint64_t nF, int64_t lo, uint64_t size, uint64_t row0, uint64_t *hostM, uint64_t mStride,
+                      uint64_t mCol, uint64_t n, uint64_t *hostReport /* [4] */);
+int pil2gl_bn128_range_mult(const pil2gl_tuple_side *hostF, uint64_t nF, int64_t lo, uint64_t size, uint64_t row0, uint64_t *hostM,
+                            uint64_t mStride, uint64_t mCol, uint64_t n, uint64_t *hostReport /* [4] */);
+int pil2gl_debug_range_mult_plan(uint64_t n, uint64_t size, uint64_t nF, uint32_t elemWords, uint32_t path, uint32_t *outInfo /* [6] */,
+                                 uint64_t *scratchBytes);
+int pil2gl_debug_range_mult_dev(const pil2gl_tuple_side *hostF, uint64_t nF, int64_t lo, uint64_t size, uint64_t row0, uint64_t *m,
+                                uint64_t mStride, uint64_t mCol, uint64_t n, uint64_t *scratch, uint64_t scratchBytes,
+                                uint64_t *hostReport /* [4] */, void *stream, uint32_t elemWords, uint32_t path);
 
 /* ---- lookup grand sum: the logUp column s of `selF_s {f_s} in selT {t}` from f, t and m (csrc/logup_sum_plan.h, hints.hip, bn_scan.hip) ----
  * The column that consumes the block above's m: the running sum of a pil2 lookup stated as  sum selF / (f + gamma) - sum m / (t + gamma),

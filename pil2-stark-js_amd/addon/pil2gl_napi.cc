@@ -750,6 +750,64 @@ FN(LookupMult) {
 }
 FN(LookupMultProbe) { return mk_bigint(env, pil2gl_debug_lookup_mult_probe()); }
 
+// ---- range-check multiplicities: the column m of `selF_s f_s in [lo, lo + size)` (csrc/range_mult.hip; js/pil_checks.js) ----
+FN(RangeMultPlan) {        // (n, size, nF, elemWords, path | undefined) -> { path, threads, blocks, launches, headerBytes, ldsCounters, scratchBytes }
+    Args a(env, info); uint64_t n = a.u64(0), size = a.u64(1), nF = a.u64(2); uint32_t ew = (uint32_t)a.u64(3);
+    const uint32_t path = a.argc > 4 && !a.is_nullish(4) ? (uint32_t)a.u64(4) : 2; if (!a.ok) return nullptr;
+    uint32_t out[6]; uint64_t bytes = 0;
+    P2(env, pil2gl_debug_range_mult_plan(n, size, nF, ew, path, out, &bytes));
+    static const char *names[6] = { "path", "threads", "blocks", "launches", "headerBytes", "ldsCounters" };
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 6; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
+    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "scratchBytes", v);
+    return o;
+}
+// A call's description, one BigUint64Array: [0] n, [1] nF, [2] lo as a two's-complement word, [3] size, [4] row0, [5] m, [6] mStride,
+// [7] mCol, then nF sides of six words in pil2gl_tuple_side's order, the column itself in the columns' place: base, stride, col, sel
+// (0: none), selStride, selCol.  The pointer words are device addresses for rangeMultDev and are not read by rangeMult, which takes the
+// host matrices as an array of its own.
+enum { RD_N, RD_NF, RD_LO, RD_SIZE, RD_ROW0, RD_M, RD_M_STRIDE, RD_M_COL, RD_SIDES, RD_SIDE_WORDS = 6 };
+struct RangeDesc { uint64_t *d; uint64_t n, nF; pil2gl_tuple_side side[8]; };
+static bool range_desc(Args &a, size_t i, RangeDesc &r) {
+    uint64_t len = 0; r.d = a.arr(i, RD_SIDES, &len);
+    if (!a.ok) return false;
+    r.n = r.d[RD_N]; r.nF = r.d[RD_NF];
+    if (r.nF > 8 || len < RD_SIDES + r.nF * RD_SIDE_WORDS) return a.fail("the description holds 8 words, then nF sides of 6 words, nF <= 8");
+    for (uint64_t s = 0; s < r.nF; s++) {
+        const uint64_t *w = r.d + RD_SIDES + s * RD_SIDE_WORDS;
+        r.side[s] = pil2gl_tuple_side{ (const uint64_t *)(uintptr_t)w[0], w[1], w + 2, (const uint64_t *)(uintptr_t)w[3], w[4], w[5] };
+    }
+    return true;
+}
+FN(RangeMultDev) {         // (description, dScratch, scratchBytes, report BigUint64Array(4), elemWords)
+    Args a(env, info); RangeDesc r; if (!range_desc(a, 0, r)) return nullptr;
+    uint64_t *scr = DP(1); uint64_t bytes = a.u64(2); uint64_t *rep = a.arr(3, 4); uint32_t ew = (uint32_t)a.u64(4); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_range_mult_dev : pil2gl_range_mult_dev)(r.side, r.nF, (int64_t)r.d[RD_LO], r.d[RD_SIZE], r.d[RD_ROW0], (uint64_t *)(uintptr_t)r.d[RD_M],
+                                                                            r.d[RD_M_STRIDE], r.d[RD_M_COL], r.n, scr, bytes, rep, nullptr));
+    return mk_undefined(env);
+}
+// (description, matrices, report BigUint64Array(4), elemWords): matrices = an Array of BigUint64Array, [2 s] the matrix of side s,
+// [2 s + 1] its selector's or null, [2 nF] m's matrix, which is written in place
+FN(RangeMult) {
+    Args a(env, info); RangeDesc r; if (!range_desc(a, 0, r)) return nullptr;
+    uint64_t *rep = a.arr(2, 4); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
+    if (ew != 1 && ew != 4) { a.fail("elemWords is 1 or 4"); return nullptr; }
+    bool isArray = false; uint32_t count = 0;
+    if (a.argc < 2 || napi_is_array(env, a.argv[1], &isArray) != napi_ok || !isArray) { a.fail("expected an Array of matrices"); return nullptr; }
+    napi_get_array_length(env, a.argv[1], &count);
+    if (count != 2 * r.nF + 1) { a.fail("expected a matrix and a selector or null for every f, then m's matrix"); return nullptr; }
+    auto words = [&](uint32_t i, uint64_t minWords, bool optional) { return array_words(a, a.argv[1], i, minWords, optional); };
+    for (uint64_t s = 0; s < r.nF && a.ok; s++) {
+        pil2gl_tuple_side &x = r.side[s];
+        x.base = words((uint32_t)(2 * s), tuple_span(r.n, x.stride, x.hostCols, 1, ew), false);
+        x.sel = a.ok ? words((uint32_t)(2 * s + 1), tuple_span(r.n, x.selStride, &x.selCol, 1, ew), true) : nullptr;
+    }
+    uint64_t *hm = a.ok ? words((uint32_t)(2 * r.nF), tuple_span(r.n, r.d[RD_M_STRIDE], r.d + RD_M_COL, 1, ew), false) : nullptr;
+    if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_range_mult : pil2gl_range_mult)(r.side, r.nF, (int64_t)r.d[RD_LO], r.d[RD_SIZE], r.d[RD_ROW0], hm, r.d[RD_M_STRIDE], r.d[RD_M_COL], r.n, rep));
+    return mk_undefined(env);
+}
+
 // ---- lookup grand sum: the logUp column s from f, t and m (csrc/logup_sum_plan.h; js/pil_checks.js) ----
 FN(LogupSumPlan) {         // (n, nTerms, elemWords) -> { threads, items, blocks, launches, depth, outWidth, workBytes }
     Args a(env, info); uint64_t n = a.u64(0), nT = a.u64(1); uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
@@ -1009,6 +1067,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "connCheckPlan", ConnCheckPlan }, { "connCheckDev", ConnCheckDev }, { "bn128ConnCheckDev", Bn128ConnCheckDev }, { "connCheck", ConnCheck }, { "bn128ConnCheck", Bn128ConnCheck },
         { "tupleCheckPlan", TupleCheckPlan }, { "tupleCheckDev", TupleCheckDev }, { "tupleCheck", TupleCheck }, { "tupleHome", TupleHome }, { "tupleCheckProbe", TupleCheckProbe },
         { "lookupMultPlan", LookupMultPlan }, { "lookupMultDev", LookupMultDev }, { "lookupMult", LookupMult }, { "lookupMultProbe", LookupMultProbe },
+        { "rangeMultPlan", RangeMultPlan }, { "rangeMultDev", RangeMultDev }, { "rangeMult", RangeMult },
         { "logupSumPlan", LogupSumPlan }, { "logupTermLayout", LogupTermLayout }, { "logupSumDev", LogupSumDev }, { "logupSum", LogupSum },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },

@@ -18,13 +18,14 @@
 // The merge: a range check sends every row of f to a handful of counters.  Up to MERGE_ROUNDS times the wave takes its first lane with an
 // add still to make, reads that lane's slot (v_readlane), ballots the lanes on the same slot and lets the first lane add their number in
 // ONE atomic; lanes left after the rounds add 1 each.  One tuple: one atomic a wave instead of 64 on one address.  All distinct: four
-// rounds of a readlane, a compare and a ballot retire four lanes, the other sixty add as before.  No LDS.
+// rounds of a readlane, a compare and a ballot retire four lanes, the other sixty add as before.  No LDS.  (wave_merge.cuh, shared with range_mult.hip)
 //
 // Safety: nothing read from f, t or a selector is used as an address.  A slot's row is checked against n before it indexes t (the table's
 // `limit`).  Plain vector loads and stores and global atomics only.
 #include "common.h"
 #include "tuple_side.cuh"
 #include "lookup_mult_plan.h"
+#include "wave_merge.cuh"
 #include <string.h>
 
 using namespace pil2gl;
@@ -35,7 +36,6 @@ using namespace tupleside;
 using namespace smapplan;
 using namespace lookupmultplan;
 
-constexpr int MERGE_ROUNDS = 4;
 uint64_t g_lastProbe = 0;                            // the longest displacement of the last build (pil2gl_debug_lookup_mult_probe)
 
 template <class F> struct Job {
@@ -79,22 +79,6 @@ __global__ void __launch_bounds__(THREADS) lm_build_kernel(Job<F> J, unsigned lo
     report_probe(longest, hdr + H_PROBE);
 }
 
-// one add to the counter of slot s for every lane with `add` set, lanes on one slot merged; every lane of the wave arrives here
-__device__ __forceinline__ void add_merged(u32 *slots, u32 s, bool add) {
-    u64 todo = __ballot(add);
-    const u32 lane = threadIdx.x & 63;
-    for (int round = 0; round < MERGE_ROUNDS && todo; round++) {
-        const u32 first = (u32)__ffsll((unsigned long long)todo) - 1;
-        const u32 slot = (u32)__builtin_amdgcn_readlane((int)s, (int)first);
-        const bool mine = add && s == slot;
-        const u64 group = __ballot(mine);
-        if (lane == first) atomicAdd(&slots[2 * (u64)slot + 1], (u32)__popcll((unsigned long long)group));
-        add = add && !mine;
-        todo &= ~group;
-    }
-    if (add) atomicAdd(&slots[2 * (u64)s + 1], 1u);
-}
-
 // ---- count: the rows of one side of f ----
 template <class F>
 __global__ void __launch_bounds__(THREADS) lm_count_kernel(Job<F> J, Side<F> f, u32 side, unsigned long long *hdr) {
@@ -108,7 +92,7 @@ __global__ void __launch_bounds__(THREADS) lm_count_kernel(Job<F> J, Side<F> f, 
         const bool hit = s != NONE;
         if (live && !hit) bad = r < bad ? r : bad;
         matched += hit;
-        add_merged(J.slots, (u32)s, hit);                                            // a slot's number is below 2^30
+        wavemerge::add_merged<2, 1>(J.slots, (u32)s, hit);                           // a slot's number is below 2^30; the counter lies beside it
     }
     report_bad(bad == NO_BAD ? NO_BAD : (u64)side << 32 | bad, hdr + H_FAIL);
     for (int o = 32; o > 0; o >>= 1) matched += __shfl_xor(matched, o, 64);

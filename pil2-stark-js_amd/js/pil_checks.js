@@ -19,6 +19,12 @@
 //   -> { matched, missing: null | { side, row, message() } }: matched = the selected f rows whose tuple t holds (the sum of m); missing = the
 //      smallest (side, row) of f whose tuple no selected row of t holds; m is written in full either way
 //   formatMissing(missing, values)   the message; lookupMultProbe()   the library's debug entry
+// and the same column for a range check `selF_s f_s in [lo, lo + size)`, which has no table column (csrc/range_mult.hip):
+//   rangeMultiplicities(fs, lo, size, m, n, opts) / rangeMultiplicitiesDev(fs, lo, size, m, n, opts)
+//       fs: 1 .. 8 sides as above with ONE column each; lo: a BigInt or an integer, negative allowed (a signed 64-bit value); size: 1 .. 2^28;
+//       m: { buf, stride, col }: rows opts.row0 (0) .. row0 + size - 1 take the counts of lo, lo + 1, ..; every other row of the n takes 0
+//   -> { matched, missing: null | { side, row, message() } } as above; missing = the smallest (side, row) whose value is out of range
+//   formatOutOfRange(missing, value, lo, size)   the message; rangeMultPlan(n, size, nF, bn128)   the library's plan
 // and the grand-sum column that consumes m (csrc/logup_sum_plan.h; include/pil2gl.h states it):
 //   logupSum(terms, alpha, beta, out, n, opts) / logupSumDev(terms, alpha, beta, out, n, opts)
 //       terms: 1 .. 9 sides as above, each with coef and busId beside buf / stride / cols / sel: a BigInt (canonical) over Goldilocks, a
@@ -149,6 +155,46 @@ const lookupMultiplicities = (fs, t, m, n, opts) => multiplicities(false, fs, t,
 const lookupMultiplicitiesDev = (fs, t, m, n, opts) => multiplicities(true, fs, t, m, n, opts);
 const lookupMultProbe = () => Number(addon.lookupMultProbe());
 
+// ---- range-check multiplicities ----
+// The wording, once (INTEGRATION.md):
+//   "range: f side S row R = V is outside [LO, HI]"
+const formatOutOfRange = (x, value, lo, size) => "range: f side " + x.side + " row " + x.row + " = " + value + " is outside [" + lo + ", " + (lo + BigInt(size) - 1n) + "]";
+function rangeCounts(dev, fsIn, loIn, size, mIn, n, opts) {
+    const ew = opts && opts.bn128 ? 4 : 1, row0 = opts && opts.row0 ? opts.row0 : 0;
+    if (!Array.isArray(fsIn) || fsIn.length < 1 || fsIn.length > 8) throw new Error("fs must be an array of 1 .. 8 sides");
+    if (!mIn || !(mIn.stride > 0) || !(mIn.col >= 0)) throw new Error("m must be { buf, stride, col }");
+    const lo = BigInt(loIn);
+    if (lo < -(1n << 63n) || lo >= 1n << 63n) throw new Error("lo must be a signed 64-bit integer");
+    const fs = fsIn.map((f, s) => side(f, "f " + s, n, ew, dev));
+    fs.forEach((f, s) => { if (f.cols.length !== 1) throw new Error("f " + s + " must have one column"); });
+    const m = side({ buf: mIn.buf, stride: mIn.stride, cols: [mIn.col] }, "m", n, ew, dev);
+    const ptr = (b) => dev && b ? b.ptr : 0n;
+    const head = [n, fs.length, BigInt.asUintN(64, lo), size, row0, ptr(m.buf), m.stride, mIn.col];
+    const six = fs.map((x) => [ptr(x.buf), x.stride, x.cols[0]].concat(x.sel ? [ptr(x.sel.buf), x.sel.stride, x.sel.col] : [0n, 0, 0]));
+    const desc = BigUint64Array.from(head.concat(...six).map((v) => BigInt(v)));
+    const rep = new BigUint64Array(4);
+    let read;
+    if (!dev) {
+        addon.rangeMult(desc, [].concat(...fs.map((x) => [x.buf, x.sel ? x.sel.buf : null]), [m.buf]), rep, ew);
+        if (m.buf.buffer !== mIn.buf.buffer) new Uint8Array(mIn.buf.buffer, mIn.buf.byteOffset, mIn.buf.byteLength).set(new Uint8Array(m.buf.buffer));      // bytes off 8: asWords copied
+        read = (buf, at, len) => buf.subarray(at, at + len);
+    } else {
+        const plan = addon.rangeMultPlan(n, size, fs.length, ew);
+        const work = new DevBuffer(Math.max(2, plan.scratchBytes / 8));
+        try { addon.rangeMultDev(desc, work.ptr, plan.scratchBytes, rep, ew); } finally { work.free(); }
+        read = (buf, at, len) => buf.slice(at, at + len);
+    }
+    const out = { matched: Number(rep[3]), missing: null };
+    if (rep[0] !== 0n) {
+        const x = out.missing = { side: Number(rep[1]), row: Number(rep[2]) };
+        x.message = () => { const f = fs[x.side]; return formatOutOfRange(x, decimalOf(read(f.buf, (x.row * f.stride + f.cols[0]) * ew, ew)), lo, size); };
+    }
+    return out;
+}
+const rangeMultiplicities = (fs, lo, size, m, n, opts) => rangeCounts(false, fs, lo, size, m, n, opts);
+const rangeMultiplicitiesDev = (fs, lo, size, m, n, opts) => rangeCounts(true, fs, lo, size, m, n, opts);
+const rangeMultPlan = (n, size, nF, bn128) => addon.rangeMultPlan(n, size, nF, bn128 ? 4 : 1);
+
 // ---- lookup grand sum ----
 function logup(dev, termsIn, alpha, beta, outIn, n, opts) {
     const bn = !!(opts && opts.bn128), ew = bn ? 4 : 1, width = bn ? 1 : 3;
@@ -181,4 +227,4 @@ const logupSum = (terms, alpha, beta, out, n, opts) => logup(false, terms, alpha
 const logupSumDev = (terms, alpha, beta, out, n, opts) => logup(true, terms, alpha, beta, out, n, opts);
 const logupSumPlan = (n, nTerms, bn128) => addon.logupSumPlan(n, nTerms, bn128 ? 4 : 1);
 
-module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, logupSum, logupSumDev, logupSumPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };
+module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, logupSum, logupSumDev, logupSumPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };

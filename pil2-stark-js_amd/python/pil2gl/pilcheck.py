@@ -12,7 +12,8 @@ returns the library's five words (kind, row, partner, cntF, cntT) -- include/pil
 (0, NONE, NONE, 0, 0).  No arithmetic happens here: hashing, counting and judging are the library's.
 
 The column that PROVES a lookup in pil2, the multiplicities of its grand sum (csrc/lookup_mult.hip), is lookup_mult / lookup_mult_dev at the
-end of this module, and after it the grand sum that consumes it (logup_sum / logup_sum_dev).
+end of this module, then its form for a range check, which needs no table column (range_mult / range_mult_dev, csrc/range_mult.hip), and
+after them the grand sum that consumes the column (logup_sum / logup_sum_dev).
 """
 import ctypes as C
 
@@ -183,6 +184,70 @@ def lookup_mult_dev(fs, t, m, n, field="gl"):
     """lookup_mult on device tensors, e.g. columns of the stage-1 buffer with m one more column of it; the working buffer comes from the
     plan and lives for the call; blocks for the report"""
     return _mult(True, fs, t, m, n, field)
+
+
+# ---- range-check multiplicities: the column m of `selF_s f_s in [lo, lo + size)` (csrc/range_mult.hip; include/pil2gl.h states it) ----
+#     rep = range_mult_dev([(cm1, [7]), (cm1, [4], (cm1, 9))], -128, 256, (cm1, 12), n)
+# The sides, m and the four words that come back are lookup_mult's; a side has ONE column.  There is no t: the table is the integers
+# lo .. lo + size - 1 as field elements, and m's rows row0 .. row0 + size - 1 take their counts, every other row 0.  path: the count kernel,
+# for the tests and the benchmark (0 LDS, 1 global, None the planner's choice).
+def range_mult_plan(n, size, n_f=1, field="gl", path=None):
+    """pil2gl_range_mult_plan (host-only): the count path, the launch geometry, the working buffer"""
+    info = (C.c_uint32 * 6)()
+    nbytes = C.c_uint64()
+    if path is None:
+        call("pil2gl_range_mult_plan", n, size, n_f, _WORDS[field], info, C.byref(nbytes))
+    else:
+        call("pil2gl_debug_range_mult_plan", n, size, n_f, _WORDS[field], path, info, C.byref(nbytes))
+    names = ("path", "threads", "blocks", "launches", "headerBytes", "ldsCounters")
+    return dict(zip(names, (int(x) for x in info)), scratchBytes=nbytes.value)
+
+
+def _range(dev, fs, lo, size, m, n, field, row0, path):
+    from ._lib import TupleSide
+    words = _WORDS[field]
+    ptr = (lambda a: _ptr(a)) if dev else (lambda a: None if a is None else a.ctypes.data)
+    keep = []                                                                    # the column arrays live until the call returns
+
+    def struct(spec, what):
+        spec = tuple(spec) + (None,) * (4 - len(spec))
+        b, stride, cols, sm, sstride, scol = _side(spec[0], spec[1], spec[3], spec[2], n, words, dev, what)
+        if cols.size != 1:
+            raise Pil2glError("%s: a side of a range check has one column" % what)
+        keep.extend((b, cols, sm))
+        return TupleSide(ptr(b), stride, cols.ctypes.data, ptr(sm), sstride, scol)
+    sides = [struct(s, "f %d" % i) for i, s in enumerate(fs)]
+    if not dev and not (isinstance(m[0], np.ndarray) and m[0].dtype == np.uint64 and m[0].flags.c_contiguous and m[0].flags.writeable):
+        raise Pil2glError("m: the host form writes in place and takes a C-contiguous writeable uint64 array")
+    mm, held, mstride = _matrix(m[0], m[2] if len(m) > 2 else None, words, dev, "m")
+    if n and held < ((n - 1) * mstride + m[1] + 1) * words:
+        raise Pil2glError("m holds %d words, %d rows of stride %d need more" % (held, n, mstride))
+    F = (TupleSide * max(len(sides), 1))(*sides)
+    rep = (C.c_uint64 * 4)()
+    name = "pil2gl_range_mult" if words == 1 else "pil2gl_bn128_range_mult"
+    args = [F, len(sides), lo, size, row0, ptr(mm), mstride, m[1], n]
+    if dev:
+        plan = range_mult_plan(n, size, min(max(len(sides), 1), 8), field, path)
+        work = torch.empty(max(plan["scratchBytes"] // 8, 2), dtype=torch.int64, device=mm.device)
+        if path is None:
+            call(name + "_dev", *args, _ptr(work), plan["scratchBytes"], rep, _stream())
+        else:
+            call("pil2gl_debug_range_mult_dev", *args, _ptr(work), plan["scratchBytes"], rep, _stream(), words, path)
+    else:
+        call(name, *args, rep)
+    return tuple(int(x) for x in rep)
+
+
+def range_mult(fs, lo, size, m, n, field="gl", row0=0):
+    """the multiplicity column of the range checks `f_s in [lo, lo + size)`: host matrices; m's column is written in place
+    -> (kind, side, row, matched)"""
+    return _range(False, fs, lo, size, m, n, field, row0, None)
+
+
+def range_mult_dev(fs, lo, size, m, n, field="gl", row0=0, path=None):
+    """range_mult on device tensors, e.g. columns of the stage-1 buffer with m one more column of it; the working buffer comes from the
+    plan and lives for the call; blocks for the report"""
+    return _range(True, fs, lo, size, m, n, field, row0, path)
 
 
 # ---- lookup grand sum: the logUp column s from f, t and m (csrc/logup_sum_plan.h; include/pil2gl.h states it) ----
