@@ -625,15 +625,19 @@ FN(ConnCheck) { return conn_check_host(env, info, 1); }
 FN(Bn128ConnCheck) { return conn_check_host(env, info, 4); }
 
 // ---- lookup and permutation checks: selF {f..} in / is selT {t..} as statements about the trace (csrc/tuple_check.hip; js/pil_checks.js) ----
+// a plan entry's result: the six words under their names, and the byte count under its own
+static napi_value plan_object(napi_env env, const char *const (&names)[6], const uint32_t (&out)[6], const char *bytesName, uint64_t bytes) {
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 6; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
+    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, bytesName, v);
+    return o;
+}
+static const char *const TABLE_PLAN[6] = { "capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes" };
 FN(TupleCheckPlan) {       // (n, k, elemWords, mode) -> { capBits, threads, blocks, launches, headerBytes, slotBytes, scratchBytes }
     Args a(env, info); uint64_t n = a.u64(0), k = a.u64(1); uint32_t ew = (uint32_t)a.u64(2), mode = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
     uint32_t out[6]; uint64_t bytes = 0;
     P2(env, pil2gl_tuple_check_plan(n, k, ew, mode, out, &bytes));
-    static const char *names[6] = { "capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes" };
-    napi_value o, v; napi_create_object(env, &o);
-    for (int i = 0; i < 6; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
-    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "scratchBytes", v);
-    return o;
+    return plan_object(env, TABLE_PLAN, out, "scratchBytes", bytes);
 }
 // A call's description, one BigUint64Array: [0] f, [1] fStride, [2] t, [3] tStride, [4] selF (0: none), [5] selFStride, [6] selFCol, [7] selT,
 // [8] selTStride, [9] selTCol, [10] n, [11] k, [12] mode, then k columns of f and k columns of t.  The pointer words are device addresses
@@ -684,11 +688,7 @@ FN(LookupMultPlan) {       // (n, k, nF, elemWords) -> { capBits, threads, block
     Args a(env, info); uint64_t n = a.u64(0), k = a.u64(1), nF = a.u64(2); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
     uint32_t out[6]; uint64_t bytes = 0;
     P2(env, pil2gl_lookup_mult_plan(n, k, nF, ew, out, &bytes));
-    static const char *names[6] = { "capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes" };
-    napi_value o, v; napi_create_object(env, &o);
-    for (int i = 0; i < 6; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
-    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "scratchBytes", v);
-    return o;
+    return plan_object(env, TABLE_PLAN, out, "scratchBytes", bytes);
 }
 // A call's description, one BigUint64Array: [0] n, [1] k, [2] nF, [3] m, [4] mStride, [5] mCol, then 1 + nF sides of six words in
 // pil2gl_tuple_side's order -- t first, then f_0 .. f_{nF-1}: base, stride, (unused: the columns' place), sel (0: none), selStride, selCol --
@@ -727,23 +727,31 @@ static uint64_t *array_words(Args &a, napi_value arr, uint32_t i, uint64_t minWo
     if (n < minWords) { a.fail("buffer too small"); return nullptr; }
     return (uint64_t *)data;
 }
+// The host matrices of a call, argument 1: an Array of BigUint64Array, [2 s] the matrix of side s of ks[s] columns, [2 s + 1] its selector's or
+// null, [2 count] the matrix that is written in place, its highest column outTop.  Fills base and sel of every side -> the written matrix;
+// nullptr after a.fail().  expected: what the entry says when the array's length is another
+static uint64_t *host_matrices(Args &a, pil2gl_tuple_side *const *sides, const uint64_t *ks, uint64_t count, uint64_t n, uint64_t outStride, uint64_t outTop,
+                               uint32_t ew, const char *expected) {
+    bool isArray = false; uint32_t len = 0;
+    if (a.argc < 2 || napi_is_array(a.env, a.argv[1], &isArray) != napi_ok || !isArray) { a.fail("expected an Array of matrices"); return nullptr; }
+    napi_get_array_length(a.env, a.argv[1], &len);
+    if (len != 2 * count + 1) { a.fail(expected); return nullptr; }
+    for (uint64_t s = 0; s < count && a.ok; s++) {
+        pil2gl_tuple_side &x = *sides[s];
+        x.base = array_words(a, a.argv[1], (uint32_t)(2 * s), tuple_span(n, x.stride, x.hostCols, ks[s], ew), false);
+        x.sel = a.ok ? array_words(a, a.argv[1], (uint32_t)(2 * s + 1), tuple_span(n, x.selStride, &x.selCol, 1, ew), true) : nullptr;
+    }
+    return a.ok ? array_words(a, a.argv[1], (uint32_t)(2 * count), tuple_span(n, outStride, &outTop, 1, ew), false) : nullptr;
+}
 // (description, matrices, report BigUint64Array(4), elemWords): matrices = an Array of BigUint64Array, [2 s] the matrix of side s (t first),
 // [2 s + 1] its selector's or null, [2 (1 + nF)] m's matrix, which is written in place
 FN(LookupMult) {
     Args a(env, info); MultDesc m; if (!mult_desc(a, 0, m)) return nullptr;
     uint64_t *rep = a.arr(2, 4); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
     if (ew != 1 && ew != 4) { a.fail("elemWords is 1 or 4"); return nullptr; }
-    bool isArray = false; uint32_t count = 0;
-    if (a.argc < 2 || napi_is_array(env, a.argv[1], &isArray) != napi_ok || !isArray) { a.fail("expected an Array of matrices"); return nullptr; }
-    napi_get_array_length(env, a.argv[1], &count);
-    if (count != 2 * (1 + m.nF) + 1) { a.fail("expected a matrix and a selector or null for t and every f, then m's matrix"); return nullptr; }
-    auto words = [&](uint32_t i, uint64_t minWords, bool optional) { return array_words(a, a.argv[1], i, minWords, optional); };
-    for (uint64_t s = 0; s <= m.nF && a.ok; s++) {
-        pil2gl_tuple_side &x = m.side[s];
-        x.base = words((uint32_t)(2 * s), tuple_span(m.n, x.stride, x.hostCols, m.k, ew), false);
-        x.sel = a.ok ? words((uint32_t)(2 * s + 1), tuple_span(m.n, x.selStride, &x.selCol, 1, ew), true) : nullptr;
-    }
-    uint64_t *hm = a.ok ? words((uint32_t)(2 * (1 + m.nF)), tuple_span(m.n, m.d[MD_M_STRIDE], m.d + MD_M_COL, 1, ew), false) : nullptr;
+    pil2gl_tuple_side *sides[9]; uint64_t ks[9];
+    for (uint64_t s = 0; s <= m.nF; s++) { sides[s] = &m.side[s]; ks[s] = m.k; }
+    uint64_t *hm = host_matrices(a, sides, ks, 1 + m.nF, m.n, m.d[MD_M_STRIDE], m.d[MD_M_COL], ew, "expected a matrix and a selector or null for t and every f, then m's matrix");
     if (!a.ok) return nullptr;
     P2(env, (ew == 4 ? pil2gl_bn128_lookup_mult : pil2gl_lookup_mult)(m.side + 1, m.nF, m.side, hm, m.d[MD_M_STRIDE], m.d[MD_M_COL], m.n, m.k, rep));
     return mk_undefined(env);
@@ -756,11 +764,8 @@ FN(RangeMultPlan) {        // (n, size, nF, elemWords, path | undefined) -> { pa
     const uint32_t path = a.argc > 4 && !a.is_nullish(4) ? (uint32_t)a.u64(4) : 2; if (!a.ok) return nullptr;
     uint32_t out[6]; uint64_t bytes = 0;
     P2(env, pil2gl_debug_range_mult_plan(n, size, nF, ew, path, out, &bytes));
-    static const char *names[6] = { "path", "threads", "blocks", "launches", "headerBytes", "ldsCounters" };
-    napi_value o, v; napi_create_object(env, &o);
-    for (int i = 0; i < 6; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
-    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "scratchBytes", v);
-    return o;
+    static const char *const names[6] = { "path", "threads", "blocks", "launches", "headerBytes", "ldsCounters" };
+    return plan_object(env, names, out, "scratchBytes", bytes);
 }
 // A call's description, one BigUint64Array: [0] n, [1] nF, [2] lo as a two's-complement word, [3] size, [4] row0, [5] m, [6] mStride,
 // [7] mCol, then nF sides of six words in pil2gl_tuple_side's order, the column itself in the columns' place: base, stride, col, sel
@@ -792,17 +797,9 @@ FN(RangeMult) {
     Args a(env, info); RangeDesc r; if (!range_desc(a, 0, r)) return nullptr;
     uint64_t *rep = a.arr(2, 4); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
     if (ew != 1 && ew != 4) { a.fail("elemWords is 1 or 4"); return nullptr; }
-    bool isArray = false; uint32_t count = 0;
-    if (a.argc < 2 || napi_is_array(env, a.argv[1], &isArray) != napi_ok || !isArray) { a.fail("expected an Array of matrices"); return nullptr; }
-    napi_get_array_length(env, a.argv[1], &count);
-    if (count != 2 * r.nF + 1) { a.fail("expected a matrix and a selector or null for every f, then m's matrix"); return nullptr; }
-    auto words = [&](uint32_t i, uint64_t minWords, bool optional) { return array_words(a, a.argv[1], i, minWords, optional); };
-    for (uint64_t s = 0; s < r.nF && a.ok; s++) {
-        pil2gl_tuple_side &x = r.side[s];
-        x.base = words((uint32_t)(2 * s), tuple_span(r.n, x.stride, x.hostCols, 1, ew), false);
-        x.sel = a.ok ? words((uint32_t)(2 * s + 1), tuple_span(r.n, x.selStride, &x.selCol, 1, ew), true) : nullptr;
-    }
-    uint64_t *hm = a.ok ? words((uint32_t)(2 * r.nF), tuple_span(r.n, r.d[RD_M_STRIDE], r.d + RD_M_COL, 1, ew), false) : nullptr;
+    pil2gl_tuple_side *sides[8]; uint64_t ks[8];
+    for (uint64_t s = 0; s < r.nF; s++) { sides[s] = &r.side[s]; ks[s] = 1; }
+    uint64_t *hm = host_matrices(a, sides, ks, r.nF, r.n, r.d[RD_M_STRIDE], r.d[RD_M_COL], ew, "expected a matrix and a selector or null for every f, then m's matrix");
     if (!a.ok) return nullptr;
     P2(env, (ew == 4 ? pil2gl_bn128_range_mult : pil2gl_range_mult)(r.side, r.nF, (int64_t)r.d[RD_LO], r.d[RD_SIZE], r.d[RD_ROW0], hm, r.d[RD_M_STRIDE], r.d[RD_M_COL], r.n, rep));
     return mk_undefined(env);
@@ -813,11 +810,8 @@ FN(LogupSumPlan) {         // (n, nTerms, elemWords) -> { threads, items, blocks
     Args a(env, info); uint64_t n = a.u64(0), nT = a.u64(1); uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
     uint32_t out[6]; uint64_t bytes = 0;
     P2(env, pil2gl_logup_sum_plan(n, nT, ew, out, &bytes));
-    static const char *names[6] = { "threads", "items", "blocks", "launches", "depth", "outWidth" };
-    napi_value o, v; napi_create_object(env, &o);
-    for (int i = 0; i < 6; i++) { napi_create_uint32(env, out[i], &v); napi_set_named_property(env, o, names[i], v); }
-    napi_create_double(env, (double)bytes, &v); napi_set_named_property(env, o, "workBytes", v);
-    return o;
+    static const char *const names[6] = { "threads", "items", "blocks", "launches", "depth", "outWidth" };
+    return plan_object(env, names, out, "workBytes", bytes);
 }
 FN(LogupTermLayout) {      // -> { size, side, k, coef, busId }: sizeof and offsetof of pil2gl_logup_term as this addon was compiled
     static const char *names[5] = { "size", "side", "k", "coef", "busId" };
@@ -861,18 +855,13 @@ FN(LogupSum) {
     Args a(env, info); LogupDesc L; if (!logup_desc(a, 0, L)) return nullptr;
     uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
     if (ew != 1 && ew != 4) { a.fail("elemWords is 1 or 4"); return nullptr; }
-    bool isArray = false; uint32_t count = 0;
-    if (a.argc < 2 || napi_is_array(env, a.argv[1], &isArray) != napi_ok || !isArray) { a.fail("expected an Array of matrices"); return nullptr; }
-    napi_get_array_length(env, a.argv[1], &count);
-    if (count != 2 * L.nTerms + 1) { a.fail("expected a matrix and a numerator's matrix or null for every term, then out's matrix"); return nullptr; }
-    for (uint64_t u = 0; u < L.nTerms && a.ok; u++) {
-        pil2gl_logup_term &t = L.term[u];
-        if (t.k < 1 || t.k > 16) { a.fail("k must be 1 .. 16 columns"); return nullptr; }
-        t.side.base = array_words(a, a.argv[1], (uint32_t)(2 * u), tuple_span(L.n, t.side.stride, t.side.hostCols, t.k, ew), false);
-        t.side.sel = a.ok ? array_words(a, a.argv[1], (uint32_t)(2 * u + 1), tuple_span(L.n, t.side.selStride, &t.side.selCol, 1, ew), true) : nullptr;
+    pil2gl_tuple_side *sides[9]; uint64_t ks[9];
+    for (uint64_t u = 0; u < L.nTerms; u++) {
+        sides[u] = &L.term[u].side; ks[u] = L.term[u].k;
+        if (ks[u] < 1 || ks[u] > 16) { a.fail("k must be 1 .. 16 columns"); return nullptr; }
     }
-    const uint64_t top = L.d[LD_OUT_COL] + (ew == 1 ? 2 : 0);
-    uint64_t *ho = a.ok ? array_words(a, a.argv[1], (uint32_t)(2 * L.nTerms), tuple_span(L.n, L.d[LD_OUT_STRIDE], &top, 1, ew), false) : nullptr;
+    uint64_t *ho = host_matrices(a, sides, ks, L.nTerms, L.n, L.d[LD_OUT_STRIDE], L.d[LD_OUT_COL] + (ew == 1 ? 2 : 0), ew,
+                                 "expected a matrix and a numerator's matrix or null for every term, then out's matrix");
     if (!a.ok) return nullptr;
     P2(env, (ew == 4 ? pil2gl_bn128_logup_sum : pil2gl_logup_sum)(L.term, L.nTerms, L.d + LD_ALPHA, L.d + LD_BETA, ho, L.d[LD_OUT_STRIDE], L.d[LD_OUT_COL], L.n));
     return mk_undefined(env);

@@ -1,7 +1,7 @@
 // Host-only half of the lookup grand sum (hints.hip over Goldilocks, bn_scan.hip over BN254 Fr): what the entries refuse, the launch
 // geometry, the working bytes and the aliasing rule of the output column.  No HIP header: it builds with the plain C++ compiler
 // (tests/logup_sum_plan_dump.cpp runs it under the sanitizers).  A term's side, its limits, column and span checks are
-// tuple_side_plan.h's, the aliasing rule lookup_mult_plan.h's m_allowed over every word column of an output element, the scan's geometry
+// tuple_side_plan.h's, the aliasing rule mult_column_plan.h's m_allowed over every word column of an output element, the scan's geometry
 // hint_plan.h's (Goldilocks) and bn_scan_plan.h's (Fr).
 //
 // Working memory, neither growing with nTerms or k:
@@ -12,7 +12,7 @@
 #include <stdio.h>
 #include "hint_plan.h"
 #include "bn_scan_plan.h"
-#include "lookup_mult_plan.h"
+#include "mult_column_plan.h"
 
 namespace logupplan {
 
@@ -56,9 +56,9 @@ inline Plan plan(uint64_t n, uint32_t elemWords) {
 // The aliasing rule of out, the `width` word columns outCol .. outCol + width - 1 of (base, stride): m_allowed for each of them.  When the
 // widest span meets a read matrix the others do (one base, none empty), so this is: out may meet a read matrix only with that matrix's
 // base and stride, and with none of its read columns.
-inline bool out_allowed(const void *base, uint64_t stride, uint64_t col, uint32_t width, const lookupmultplan::ReadMatrix &r, uint64_t n, uint32_t elemWords) {
+inline bool out_allowed(const void *base, uint64_t stride, uint64_t col, uint32_t width, const multcolumn::ReadMatrix &r, uint64_t n, uint32_t elemWords) {
     for (uint32_t w = width; w-- > 0;)
-        if (!lookupmultplan::m_allowed(base, stride, col + w, r, n, elemWords)) return false;
+        if (!multcolumn::m_allowed(base, stride, col + w, r, n, elemWords)) return false;
     return true;
 }
 
@@ -93,7 +93,7 @@ inline const char *check_call(const pil2gl_logup_term *terms, uint64_t nTerms, c
     if (dev && (bits & 15)) return "every matrix, every numerator column and out must be 16-byte aligned";
     for (uint64_t u = 0; u < nTerms; u++) {
         const pil2gl_tuple_side &s = terms[u].side;
-        const lookupmultplan::ReadMatrix reads[2] = { { s.base, s.stride, s.hostCols, terms[u].k }, { s.sel, s.selStride, &s.selCol, 1 } };
+        const multcolumn::ReadMatrix reads[2] = { { s.base, s.stride, s.hostCols, terms[u].k }, { s.sel, s.selStride, &s.selCol, 1 } };
         for (int i = 0; i < (s.sel ? 2 : 1); i++)
             if (!out_allowed(out, outStride, outCol, width, reads[i], n, elemWords))
                 return "out overlaps a matrix that is read: it may only be columns of that matrix (its base, its stride) that are not read";

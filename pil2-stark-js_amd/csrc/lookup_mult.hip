@@ -5,15 +5,17 @@
 //   the table  an index table (index_table.cuh) over t's selected rows only, the key a row's tuple, re-read from t and reduced.  Slots lie
 //            two words apart: a slot is 8 bytes, the tuple's smallest selected row of t and beside it the counter.
 //   init     every slot to (EMPTY, 0), the header to (no failing row, 0 matched, probe 0): one launch instead of two memsets, because row and
-//            counter are neighbours and start from different bytes.
+//            counter are neighbours and start from different bytes.  (mult_column.cuh's init kernel, with the slot pair as its fill)
 //   build    a lane per row of t puts its row into the table.
 //   count    one launch a side of f, a lane per row: find the tuple's slot; add 1 to its counter, or note the row as failing.  Lanes of a wave
 //            that reached the same slot are merged before the atomic (below).  The wave's smallest failing (side << 32 | row) goes up by
-//            one atomicMin a wave that saw one (smap_cells.cuh report_bad), the wave's matched rows by one atomicAdd.
+//            one atomicMin a wave that saw one (smap_cells.cuh report_bad), the wave's matched rows by one atomicAdd.  The walk over the
+//            rows and that report are mult_column.cuh's count_rows, shared with range_mult.hip.
 //   write    a lane per row of t: find the slot again; the count when the slot's row is this row, else 0; unselected rows 0.  Over Fr the
 //            count goes through one Montgomery product with R^2.
-// The report's four words are made on the host from the header's two.  Counters and `matched` are sums, the slot rows and the failing pair
-// minima: neither m nor the report depends on the order in which atomics land (the probe figure, a debug value, does).
+// The report's four words are made on the host from the header's two (mult_column_plan.h, as are the checks of a call's buffers).
+// Counters and `matched` are sums, the slot rows and the failing pair minima: neither m nor the report depends on the order in which
+// atomics land (the probe figure, a debug value, does).
 //
 // The merge: a range check sends every row of f to a handful of counters.  Up to MERGE_ROUNDS times the wave takes its first lane with an
 // add still to make, reads that lane's slot (v_readlane), ballots the lanes on the same slot and lets the first lane add their number in
@@ -25,6 +27,7 @@
 #include "common.h"
 #include "tuple_side.cuh"
 #include "lookup_mult_plan.h"
+#include "mult_column.cuh"
 #include "wave_merge.cuh"
 #include <string.h>
 
@@ -35,6 +38,7 @@ namespace {
 using namespace tupleside;
 using namespace smapplan;
 using namespace lookupmultplan;
+using namespace multcolumn;
 
 uint64_t g_lastProbe = 0;                            // the longest displacement of the last build (pil2gl_debug_lookup_mult_probe)
 
@@ -45,26 +49,9 @@ template <class F> struct Job {
     u64 mask;                                        // capacity - 1
 };
 
-// a count below 2^32 in canonical form: itself over Goldilocks, count R mod r over Fr
-template <class F> __device__ __forceinline__ typename F::Elem as_element(u32 c);
-template <> __device__ __forceinline__ u64 as_element<GlField>(u32 c) { return c; }
-template <> __device__ __forceinline__ FrField::Elem as_element<FrField>(u32 c) {
-    FrField::Elem r2, x = { { c, 0, 0, 0, 0, 0, 0, 0 } };
-    if (!c) return x;
-    bn::ld_r2(r2.v);
-    return FrField::mul(r2, x);
-}
-
 // the slot that holds the tuple of row i of S, NONE when no slot does; after the build.  self: the row itself when S is t, else EMPTY
 template <class F> __device__ __forceinline__ u64 find_row(const Job<F> &J, const Side<F> &S, u64 i, u32 self) {
     return find<2>(J.slots, J.mask, home_of(S, i, J.k, J.mask), J.n, [&](u32 cur) { return cur == self || same_tuple(S, i, J.t, cur, J.k); }).slot;
-}
-
-// ---- init: header and slots ----
-__global__ void __launch_bounds__(THREADS) lm_init_kernel(uint4 *buf, u64 quads) {
-    static_assert(HEADER_BYTES == 64 && H_FAIL == 0 && H_MATCHED == 1, "the first 16 bytes: no failing pair, nothing matched");
-    for (u64 q = (u64)blockIdx.x * THREADS + threadIdx.x; q < quads; q += (u64)gridDim.x * THREADS)
-        buf[q] = q == 0 ? make_uint4(EMPTY, EMPTY, 0, 0) : q < HEADER_BYTES / 16 ? make_uint4(0, 0, 0, 0) : make_uint4(EMPTY, 0, EMPTY, 0);
 }
 
 // ---- build ----
@@ -82,21 +69,11 @@ __global__ void __launch_bounds__(THREADS) lm_build_kernel(Job<F> J, unsigned lo
 // ---- count: the rows of one side of f ----
 template <class F>
 __global__ void __launch_bounds__(THREADS) lm_count_kernel(Job<F> J, Side<F> f, u32 side, unsigned long long *hdr) {
-    u64 bad = NO_BAD;
-    u32 matched = 0;
-    // whole workgroups walk the rows, so that every lane of a wave reaches the merge
-    for (u64 first = (u64)blockIdx.x * THREADS; first < J.n; first += (u64)gridDim.x * THREADS) {
-        const u64 r = first + threadIdx.x;
-        const bool live = r < J.n && selected(f, r);
+    count_rows<THREADS>(f, side, J.n, hdr, [&](u64 r, bool live) {
         const u64 s = live ? find_row(J, f, r, EMPTY) : NONE;
-        const bool hit = s != NONE;
-        if (live && !hit) bad = r < bad ? r : bad;
-        matched += hit;
-        wavemerge::add_merged<2, 1>(J.slots, (u32)s, hit);                           // a slot's number is below 2^30; the counter lies beside it
-    }
-    report_bad(bad == NO_BAD ? NO_BAD : (u64)side << 32 | bad, hdr + H_FAIL);
-    for (int o = 32; o > 0; o >>= 1) matched += __shfl_xor(matched, o, 64);
-    if ((threadIdx.x & 63) == 0 && matched) atomicAdd(hdr + H_MATCHED, (unsigned long long)matched);
+        wavemerge::add_merged<2, 1>(J.slots, (u32)s, s != NONE);                      // a slot's number is below 2^30; the counter lies beside it
+        return s != NONE;
+    });
 }
 
 // ---- write: m for every row of t ----
@@ -113,11 +90,6 @@ __global__ void __launch_bounds__(THREADS) lm_write_kernel(Job<F> J, typename F:
 }
 
 // ---- host side ----
-typedef pil2gl_tuple_side HostSide;
-struct Out { u64 *m; u64 stride, col; };
-
-void clean(u64 *report) { if (report) { report[0] = CLEAN; report[1] = report[2] = NONE; report[3] = 0; } }
-
 // every launch of a call, on st; the arguments have passed the checks.  Blocks for the report.
 template <class F>
 int launch_field(const HostSide *f, u32 nF, const HostSide &t, const Out &out, u64 n, u32 k, void *scratch, const Plan &p, u64 *hostReport, hipStream_t st) {
@@ -129,7 +101,7 @@ int launch_field(const HostSide *f, u32 nF, const HostSide &t, const Out &out, u
     J.slots = (u32 *)(s + p.offSlots);
     J.mask = p.capacity - 1;
     const u64 quads = p.bytes / 16;
-    lm_init_kernel<<<blocks(quads), THREADS, 0, st>>>((uint4 *)s, quads);
+    mc_init_kernel<<<blocks(quads), THREADS, 0, st>>>((uint4 *)s, quads, make_uint4(EMPTY, 0, EMPTY, 0));
     KERNEL_CHECK();
     lm_build_kernel<F><<<p.blocks, THREADS, 0, st>>>(J, hdr);
     KERNEL_CHECK();
@@ -142,11 +114,7 @@ int launch_field(const HostSide *f, u32 nF, const HostSide &t, const Out &out, u
     u64 h[HEADER_WORDS_USED];
     HIP_TRY(hipMemcpyAsync(h, hdr, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const bool failed = h[H_FAIL] != NONE;
-    hostReport[0] = failed ? F_NOT_IN_T : CLEAN;
-    hostReport[1] = failed ? h[H_FAIL] >> 32 : NONE;
-    hostReport[2] = failed ? h[H_FAIL] & 0xFFFFFFFFull : NONE;
-    hostReport[3] = h[H_MATCHED];
+    report_of(h, hostReport);
     g_lastProbe = h[H_PROBE];
     return PIL2GL_OK;
 }
@@ -154,13 +122,6 @@ int launch_field(const HostSide *f, u32 nF, const HostSide &t, const Out &out, u
 int launch(const HostSide *f, u32 nF, const HostSide &t, const Out &out, u64 n, u32 k, void *scratch, const Plan &p, u32 words, u64 *hostReport, hipStream_t st) {
     return words == 1 ? launch_field<GlField>(f, nF, t, out, n, k, scratch, p, hostReport, st)
                       : launch_field<FrField>(f, nF, t, out, n, k, scratch, p, hostReport, st);
-}
-
-// the matrices a call reads: t, its selector, then each side of f and its selector; at most 2 + 2 MAX_SIDES
-struct Reads { ReadMatrix r[2 + 2 * MAX_SIDES]; u32 count = 0; };
-void add_reads(Reads &all, const HostSide &s, u64 k) {
-    all.r[all.count++] = ReadMatrix{ s.base, s.stride, s.hostCols, k };
-    if (s.sel) all.r[all.count++] = ReadMatrix{ s.sel, s.selStride, &s.selCol, 1 };
 }
 
 // what both forms refuse: 0, or the code after fail().  dev: the pointers are the device's -- aligned, and beside a scratch
@@ -177,24 +138,12 @@ int check_call(const HostSide *f, u64 nF, const HostSide *t, const Out &out, u64
     }
     if (const char *msg = check_columns(n, out.stride, &out.col, 1)) return fail(PIL2GL_EINVAL, "m: %s", msg);
     if (!n) return PIL2GL_OK;
-    Reads all;
-    add_reads(all, *t, k);
-    for (u64 i = 0; i < nF; i++) add_reads(all, f[i], k);
-    uintptr_t bits = (uintptr_t)out.m | (uintptr_t)scratch;
-    bool null = !out.m || (dev && !scratch);
-    for (u32 i = 0; i < all.count; i++) { bits |= (uintptr_t)all.r[i].base; null = null || !all.r[i].base; }
-    if (null) return fail(PIL2GL_EINVAL, "null buffer");
-    if (dev && (bits & 15)) return fail(PIL2GL_EINVAL, "t, every f, the selectors, m and the scratch must be 16-byte aligned");
-    if (dev) {
-        const Plan p = lookupmultplan::plan(n, nF);
-        if (scratchBytes < p.bytes) return fail(PIL2GL_EINVAL, "the scratch holds %llu bytes, %llu needed", (unsigned long long)scratchBytes, (unsigned long long)p.bytes);
-        bool hit = meets(scratch, p.bytes, out.m, span_bytes(n, out.stride, out.col, words));
-        for (u32 i = 0; i < all.count; i++) hit = hit || meets(scratch, p.bytes, all.r[i].base, span_bytes(n, all.r[i].stride, top_column(all.r[i].cols, all.r[i].k), words));
-        if (hit) return fail(PIL2GL_EINVAL, "the scratch overlaps t, an f, a selector or m");
-    }
-    for (u32 i = 0; i < all.count; i++)
-        if (!m_allowed(out.m, out.stride, out.col, all.r[i], n, words))
-            return fail(PIL2GL_EINVAL, "m overlaps a matrix that is read: it may only be a column of that matrix (its base, its stride) that is not read");
+    Reads all;                                       // t, its selector, then each side of f and its selector
+    all.add(*t, k);
+    for (u64 i = 0; i < nF; i++) all.add(f[i], k);
+    char buffers[128];
+    if (const char *msg = check_buffers(all, out, n, words, dev, scratch, scratchBytes, lookupmultplan::plan(n, nF).bytes, "t, every f", "t, an f", buffers))
+        return fail(PIL2GL_EINVAL, "%s", msg);
     return PIL2GL_OK;
 }
 
@@ -215,17 +164,9 @@ int mult_host(const HostSide *f, u64 nF, const HostSide *t, const Out &out, u64 
     HostSide sides[1 + MAX_SIDES];
     sides[0] = *t;
     for (u64 i = 0; i < nF; i++) sides[1 + i] = f[i];
-    const u64 mWords = span_bytes(n, out.stride, out.col, words) / 8;
-    u64 total = p.bytes / 8 + pad16(mWords);
-    for (u64 i = 0; i <= nF; i++) total += staged_words(sides[i], n, k, words);
-    Stage s(total);
-    P2_TRY(s.rc());
-    u64 *dScratch = s.take(p.bytes / 8);
-    for (u64 i = 0; i <= nF; i++) stage_side(s, sides[i], n, k, words);
-    const Out dOut{ (u64 *)s.put(out.m, mWords), out.stride, out.col };
-    P2_TRY(s.rc());
-    P2_TRY(launch(sides + 1, (u32)nF, sides[0], dOut, n, (u32)k, dScratch, p, words, hostReport, 0));
-    return s.get(out.m, dOut.m, mWords);
+    return staged(sides, 1 + (u32)nF, k, out, n, words, p.bytes, [&](const Out &dOut, u64 *dScratch) {
+        return launch(sides + 1, (u32)nF, sides[0], dOut, n, (u32)k, dScratch, p, words, hostReport, 0);
+    });
 }
 
 }  // namespace

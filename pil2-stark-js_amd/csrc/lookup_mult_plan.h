@@ -1,7 +1,8 @@
 // Host-only half of the lookup multiplicities (lookup_mult.hip): what the entries refuse, the capacity of the hash table, the launch
-// geometry, where the parts of the working buffer lie, and the aliasing rule of the output column m.  No HIP header: it builds with the
+// geometry and where the parts of the working buffer lie.  No HIP header: it builds with the
 // plain C++ compiler (tests/lookup_mult_plan_dump.cpp runs it under the sanitizers).  The table's capacity is index_table_plan.h's, a
-// side's limits, column and span checks tuple_side_plan.h's, the grid and the overlap test smap_plan.h's.
+// side's limits, column and span checks tuple_side_plan.h's, the grid smap_plan.h's; the header's first two words, the report, the
+// aliasing rule of m and the checks of a call's buffers are mult_column_plan.h's, shared with range_mult_plan.h.
 //
 // The table: over t's selected rows ONLY (the f sides are counted, not inserted), capacity for n rows.  A slot is 8 bytes: the tuple's
 // smallest selected row of t (n <= 2^28 stays far below EMPTY) and beside it the 32-bit counter (nF n <= 2^31).
@@ -12,19 +13,16 @@
 #include <stdint.h>
 #include "index_table_plan.h"
 #include "tuple_side_plan.h"
+#include "mult_column_plan.h"
 
 namespace lookupmultplan {
 
 using smapplan::THREADS;
-using indextable::NONE;
-constexpr uint64_t HEADER_BYTES = 64;
+using multcolumn::HEADER_BYTES;
+using multcolumn::MAX_SIDES;
 constexpr uint64_t SLOT_BYTES = 8;
-constexpr uint32_t MAX_SIDES = 8;
-constexpr uint32_t REPORT_WORDS = 4;
-// the header's words
-enum : uint32_t { H_FAIL = 0, H_MATCHED = 1, H_PROBE = 2, HEADER_WORDS_USED = 3 };
-// the kinds of report[0]
-enum : uint64_t { CLEAN = 0, F_NOT_IN_T = 1 };
+// the header's words behind mult_column_plan.h's two
+enum : uint32_t { H_PROBE = 2, HEADER_WORDS_USED = 3 };
 
 struct Plan {
     uint64_t capacity;
@@ -52,20 +50,6 @@ inline Plan plan(uint64_t n, uint64_t nF) {
     p.offSlots = HEADER_BYTES;
     p.bytes = n ? HEADER_BYTES + SLOT_BYTES * p.capacity : 0;
     return p;
-}
-
-// one matrix a call reads: its base, its stride, the columns read of it
-struct ReadMatrix { const void *base; uint64_t stride; const uint64_t *cols; uint64_t k; };
-
-// The aliasing rule of m, column mCol of (mBase, mStride): its span (from the matrix's first element to the end of row n - 1's element of
-// column mCol) may meet the span of a matrix that is read only when it IS that matrix -- the same base and the same stride -- and mCol is
-// none of the columns read of it.  The arguments have passed check_columns().
-inline bool m_allowed(const void *mBase, uint64_t mStride, uint64_t mCol, const ReadMatrix &r, uint64_t n, uint32_t elemWords) {
-    using namespace tupleside;
-    if (!smapplan::meets(mBase, span_bytes(n, mStride, mCol, elemWords), r.base, span_bytes(n, r.stride, top_column(r.cols, r.k), elemWords))) return true;
-    if (mBase != r.base || mStride != r.stride) return false;
-    for (uint64_t j = 0; j < r.k; j++) if (r.cols[j] == mCol) return false;
-    return true;
 }
 
 }  // namespace lookupmultplan

@@ -2,7 +2,7 @@
 // lookup_mult.hip would give on the materialised range column -- cnt(j) = how many selected rows of all f sides hold lo + j, written at row
 // row0 + j of m, 0 at every other row -- without that column: the table is an arithmetic progression, the counter of a value v is v - lo,
 // and there is nothing to hash, probe or build.  The statement is include/pil2gl.h's; tests/range_mult_ref.py restates it.
-//   init     the counters and the header to zero, the failing pair to none: 16 bytes a lane.
+//   init     the counters and the header to zero, the failing pair to none: 16 bytes a lane (mult_column.cuh's init kernel, filling zero).
 //   count    one launch a side of f, so that the side's column is a kernel argument.  A lane decodes its row: the element made canonical
 //            (over Fr one Montgomery product by 1 first: the normal form), minus lo as a FIELD element, compared with size as a full element.
 //            Only a difference below size becomes a counter's index.
@@ -11,10 +11,11 @@
 //                      unit, at a cost measured below that of the wave merge in front of the add, so the add is plain.
 //              path 1  larger ranges: lookup_mult.hip's merged add (wave_merge.cuh) on the global counters.  No LDS.
 //            The wave's smallest failing (side << 32 | row) goes up by one atomicMin a wave that saw one (smap_cells.cuh report_bad), the
-//            wave's matched rows by one atomicAdd.  Whole workgroups walk the rows, so that every lane reaches the wave-level steps.
+//            wave's matched rows by one atomicAdd.  Whole workgroups walk the rows, so that every lane reaches the wave-level steps:
+//            the walk and that report are mult_column.cuh's count_rows, shared with lookup_mult.hip.
 //   write    a lane per row of m: the counter of row - row0 inside the table, 0 outside.  Over Fr the count goes through one Montgomery
-//            product with R^2, as lookup_mult.hip's write does.
-// The report's four words are made on the host from the header's two.  Counters and `matched` are sums, the failing pair a minimum: neither m
+//            product with R^2, as lookup_mult.hip's write does (mult_column.cuh's as_element).
+// The report's four words are made on the host from the header's two (mult_column_plan.h, as are the checks of a call's buffers).  Counters and `matched` are sums, the failing pair a minimum: neither m
 // nor the report depends on the order in which atomics land.
 //
 // Safety: a counter's index is used only after its comparison with size; nothing else read from a matrix is used as an address; every loop is
@@ -22,6 +23,7 @@
 #include "common.h"
 #include "tuple_side.cuh"
 #include "range_mult_plan.h"
+#include "mult_column.cuh"
 #include "wave_merge.cuh"
 
 using namespace pil2gl;
@@ -31,12 +33,7 @@ namespace {
 using namespace tupleside;
 using namespace smapplan;
 using namespace rangemultplan;
-using lookupmultplan::H_FAIL;
-using lookupmultplan::H_MATCHED;
-using lookupmultplan::CLEAN;
-using lookupmultplan::F_NOT_IN_T;
-using lookupmultplan::ReadMatrix;
-using lookupmultplan::m_allowed;
+using namespace multcolumn;
 
 // the range as the kernels take it: lo as a canonical element of the field (normal form over Fr), size
 template <class F> struct Range;
@@ -58,71 +55,34 @@ __device__ __forceinline__ bool decode(const Side<FrField> &f, u64 i, const Rang
     return (v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7]) == 0 && v.v[0] < rg.size;
 }
 
-// a count below 2^32 in canonical form: itself over Goldilocks, count R mod r over Fr (lookup_mult.hip's, which stays as it is)
-template <class F> __device__ __forceinline__ typename F::Elem as_element(u32 c);
-template <> __device__ __forceinline__ u64 as_element<GlField>(u32 c) { return c; }
-template <> __device__ __forceinline__ FrField::Elem as_element<FrField>(u32 c) {
-    FrField::Elem r2, x = { { c, 0, 0, 0, 0, 0, 0, 0 } };
-    if (!c) return x;
-    bn::ld_r2(r2.v);
-    return FrField::mul(r2, x);
-}
-
-// ---- init: header and counters ----
-__global__ void __launch_bounds__(THREADS) rm_init_kernel(uint4 *buf, u64 quads) {
-    static_assert(HEADER_BYTES == 64 && H_FAIL == 0 && H_MATCHED == 1, "the first 16 bytes: no failing pair, nothing matched");
-    for (u64 q = (u64)blockIdx.x * THREADS + threadIdx.x; q < quads; q += (u64)gridDim.x * THREADS)
-        buf[q] = q == 0 ? make_uint4(EMPTY, EMPTY, 0, 0) : make_uint4(0, 0, 0, 0);
-}
-
-// what a count kernel's lanes hand up at its end; every lane of the wave arrives here
-__device__ __forceinline__ void report(u64 bad, u32 matched, u32 side, unsigned long long *hdr) {
-    report_bad(bad == NO_BAD ? NO_BAD : (u64)side << 32 | bad, hdr + H_FAIL);
-    for (int o = 32; o > 0; o >>= 1) matched += __shfl_xor(matched, o, 64);
-    if ((threadIdx.x & 63) == 0 && matched) atomicAdd(hdr + H_MATCHED, (unsigned long long)matched);
-}
-
 // ---- count, path 0: the rows of one side of f into the workgroup's own counters ----
 template <class F>
 __global__ void __launch_bounds__(LDS_THREADS) rm_count_lds_kernel(Side<F> f, u32 side, Range<F> rg, u32 n, u32 *counters, unsigned long long *hdr) {
     extern __shared__ u32 local[];                   // rg.size counters
     for (u32 j = threadIdx.x; j < rg.size; j += LDS_THREADS) local[j] = 0;
     __syncthreads();
-    u64 bad = NO_BAD;
-    u32 matched = 0;
-    for (u64 first = (u64)blockIdx.x * LDS_THREADS; first < n; first += (u64)gridDim.x * LDS_THREADS) {
-        const u64 r = first + threadIdx.x;
+    count_rows<LDS_THREADS>(f, side, n, hdr, [&](u64 r, bool live) {
         u32 idx = 0;
-        const bool live = r < n && selected(f, r);
         const bool hit = live && decode(f, r, rg, idx);
-        if (live && !hit) bad = r < bad ? r : bad;
-        matched += hit;
         if (hit) atomicAdd(&local[idx], 1u);
-    }
+        return hit;
+    });
     __syncthreads();
     for (u32 j = threadIdx.x; j < rg.size; j += LDS_THREADS) {
         const u32 c = local[j];
         if (c) atomicAdd(&counters[j], c);
     }
-    report(bad, matched, side, hdr);
 }
 
 // ---- count, path 1: the rows of one side of f onto the global counters ----
 template <class F>
 __global__ void __launch_bounds__(THREADS) rm_count_global_kernel(Side<F> f, u32 side, Range<F> rg, u32 n, u32 *counters, unsigned long long *hdr) {
-    u64 bad = NO_BAD;
-    u32 matched = 0;
-    // whole workgroups walk the rows, so that every lane of a wave reaches the merge
-    for (u64 first = (u64)blockIdx.x * THREADS; first < n; first += (u64)gridDim.x * THREADS) {
-        const u64 r = first + threadIdx.x;
+    count_rows<THREADS>(f, side, n, hdr, [&](u64 r, bool live) {
         u32 idx = 0;
-        const bool live = r < n && selected(f, r);
         const bool hit = live && decode(f, r, rg, idx);
-        if (live && !hit) bad = r < bad ? r : bad;
-        matched += hit;
         wavemerge::add_merged<1, 0>(counters, idx, hit);                              // idx < size where hit
-    }
-    report(bad, matched, side, hdr);
+        return hit;
+    });
 }
 
 // ---- write: m for every row ----
@@ -136,11 +96,7 @@ __global__ void __launch_bounds__(THREADS) rm_write_kernel(const u32 *counters, 
 }
 
 // ---- host side ----
-typedef pil2gl_tuple_side HostSide;
-struct Out { u64 *m; u64 stride, col; };
 struct Call { int64_t lo; u64 size, row0, n; u32 nF, words, force; };
-
-void clean(u64 *report) { if (report) { report[0] = CLEAN; report[1] = report[2] = NONE; report[3] = 0; } }
 
 template <class F> Range<F> device_range(int64_t lo, u64 size);
 template <> Range<GlField> device_range<GlField>(int64_t lo, u64 size) { return Range<GlField>{ lo_mod_p(lo), (u32)size }; }
@@ -161,7 +117,7 @@ int launch_field(const HostSide *f, const Call &c, const Out &out, void *scratch
     u32 *counters = (u32 *)(s + p.offCounters);
     const Range<F> rg = device_range<F>(c.lo, c.size);
     const u64 quads = p.bytes / 16;
-    rm_init_kernel<<<blocks(quads), THREADS, 0, st>>>((uint4 *)s, quads);
+    mc_init_kernel<<<blocks(quads), THREADS, 0, st>>>((uint4 *)s, quads, make_uint4(0, 0, 0, 0));
     KERNEL_CHECK();
     for (u32 i = 0; i < c.nF; i++) {
         if (p.path == PATH_LDS) rm_count_lds_kernel<F><<<p.blocks, LDS_THREADS, 4 * p.ldsCounters, st>>>(device_side<F>(f[i], 1), i, rg, (u32)c.n, counters, hdr);
@@ -173,20 +129,13 @@ int launch_field(const HostSide *f, const Call &c, const Out &out, void *scratch
     u64 h[2];
     HIP_TRY(hipMemcpyAsync(h, hdr, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const bool failed = h[H_FAIL] != NONE;
-    hostReport[0] = failed ? F_NOT_IN_T : CLEAN;
-    hostReport[1] = failed ? h[H_FAIL] >> 32 : NONE;
-    hostReport[2] = failed ? h[H_FAIL] & 0xFFFFFFFFull : NONE;
-    hostReport[3] = h[H_MATCHED];
+    report_of(h, hostReport);
     return PIL2GL_OK;
 }
 
 int launch(const HostSide *f, const Call &c, const Out &out, void *scratch, const Plan &p, u64 *hostReport, hipStream_t st) {
     return c.words == 1 ? launch_field<GlField>(f, c, out, scratch, p, hostReport, st) : launch_field<FrField>(f, c, out, scratch, p, hostReport, st);
 }
-
-// the matrices a call reads: each side of f and its selector; at most 2 MAX_SIDES
-struct Reads { ReadMatrix r[2 * MAX_SIDES]; u32 count = 0; };
 
 // what both forms refuse: 0, or the code after fail().  dev: the pointers are the device's -- aligned, and beside a scratch
 int check_call(const HostSide *f, const Call &c, const Out &out, u64 *hostReport, bool dev, const void *scratch, u64 scratchBytes) {
@@ -201,26 +150,11 @@ int check_call(const HostSide *f, const Call &c, const Out &out, u64 *hostReport
     if (const char *msg = check_columns(c.n, out.stride, &out.col, 1)) return fail(PIL2GL_EINVAL, "m: %s", msg);
     if (!c.n) return PIL2GL_OK;
     if (const char *msg = check_rows(c.n, c.size, c.row0)) return fail(PIL2GL_EINVAL, "%s", msg);
-    Reads all;
-    for (u32 i = 0; i < c.nF; i++) {
-        all.r[all.count++] = ReadMatrix{ f[i].base, f[i].stride, f[i].hostCols, 1 };
-        if (f[i].sel) all.r[all.count++] = ReadMatrix{ f[i].sel, f[i].selStride, &f[i].selCol, 1 };
-    }
-    uintptr_t bits = (uintptr_t)out.m | (uintptr_t)scratch;
-    bool null = !out.m || (dev && !scratch);
-    for (u32 i = 0; i < all.count; i++) { bits |= (uintptr_t)all.r[i].base; null = null || !all.r[i].base; }
-    if (null) return fail(PIL2GL_EINVAL, "null buffer");
-    if (dev && (bits & 15)) return fail(PIL2GL_EINVAL, "every f, the selectors, m and the scratch must be 16-byte aligned");
-    if (dev) {
-        const Plan p = rangemultplan::plan(c.n, c.size, c.nF, c.force);
-        if (scratchBytes < p.bytes) return fail(PIL2GL_EINVAL, "the scratch holds %llu bytes, %llu needed", (unsigned long long)scratchBytes, (unsigned long long)p.bytes);
-        bool hit = meets(scratch, p.bytes, out.m, span_bytes(c.n, out.stride, out.col, c.words));
-        for (u32 i = 0; i < all.count; i++) hit = hit || meets(scratch, p.bytes, all.r[i].base, span_bytes(c.n, all.r[i].stride, all.r[i].cols[0], c.words));
-        if (hit) return fail(PIL2GL_EINVAL, "the scratch overlaps an f, a selector or m");
-    }
-    for (u32 i = 0; i < all.count; i++)
-        if (!m_allowed(out.m, out.stride, out.col, all.r[i], c.n, c.words))
-            return fail(PIL2GL_EINVAL, "m overlaps a matrix that is read: it may only be a column of that matrix (its base, its stride) that is not read");
+    Reads all;                                       // each side of f and its selector
+    for (u32 i = 0; i < c.nF; i++) all.add(f[i], 1);
+    char buffers[128];
+    if (const char *msg = check_buffers(all, out, c.n, c.words, dev, scratch, scratchBytes, rangemultplan::plan(c.n, c.size, c.nF, c.force).bytes, "every f", "an f", buffers))
+        return fail(PIL2GL_EINVAL, "%s", msg);
     return PIL2GL_OK;
 }
 
@@ -240,17 +174,7 @@ int range_host(const HostSide *f, const Call &c, const Out &out, u64 *hostReport
     const Plan p = rangemultplan::plan(c.n, c.size, c.nF, c.force);
     HostSide sides[MAX_SIDES];
     for (u32 i = 0; i < c.nF; i++) sides[i] = f[i];
-    const u64 mWords = span_bytes(c.n, out.stride, out.col, c.words) / 8;
-    u64 total = p.bytes / 8 + pad16(mWords);
-    for (u32 i = 0; i < c.nF; i++) total += staged_words(sides[i], c.n, 1, c.words);
-    Stage s(total);
-    P2_TRY(s.rc());
-    u64 *dScratch = s.take(p.bytes / 8);
-    for (u32 i = 0; i < c.nF; i++) stage_side(s, sides[i], c.n, 1, c.words);
-    const Out dOut{ (u64 *)s.put(out.m, mWords), out.stride, out.col };
-    P2_TRY(s.rc());
-    P2_TRY(launch(sides, c, dOut, dScratch, p, hostReport, 0));
-    return s.get(out.m, dOut.m, mWords);
+    return staged(sides, c.nF, 1, out, c.n, c.words, p.bytes, [&](const Out &dOut, u64 *dScratch) { return launch(sides, c, dOut, dScratch, p, hostReport, 0); });
 }
 
 // nF as the checks take it: anything above 8 is refused there

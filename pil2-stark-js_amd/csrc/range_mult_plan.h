@@ -1,8 +1,8 @@
 // Host-only half of the range-check multiplicities (range_mult.hip): what the entries refuse, which of the two count kernels a call takes,
 // the launch geometry, where the parts of the working buffer lie, and the range's first element in either field.  No HIP header: it builds
-// with the plain C++ compiler (tests/range_mult_plan_dump.cpp runs it under the sanitizers).  The aliasing rule of the output column m is
-// lookup_mult_plan.h's m_allowed, called here and not copied; a side's limits, column and span checks are tuple_side_plan.h's, the overlap
-// test smap_plan.h's.
+// with the plain C++ compiler (tests/range_mult_plan_dump.cpp runs it under the sanitizers).  The header's two words, the report, the
+// aliasing rule of m and the checks of a call's buffers are mult_column_plan.h's, shared with lookup_mult_plan.h; a side's limits, column
+// and span checks are tuple_side_plan.h's.
 //
 // The table is implicit: the range [lo, lo + size) of one column, the counter of a value v is (v - lo) mod p|r.  Nothing is hashed, probed
 // or built.  The working buffer, every part on 16 bytes:
@@ -14,13 +14,13 @@
 //   PATH_GLOBAL  larger ranges: lookup_mult's merged add (wave_merge.cuh) on the global counters, smap_plan.h's grid.
 #pragma once
 #include <stdint.h>
-#include "lookup_mult_plan.h"
+#include "mult_column_plan.h"
 
 namespace rangemultplan {
 
 using smapplan::THREADS;
-using lookupmultplan::HEADER_BYTES;
-using lookupmultplan::MAX_SIDES;
+using multcolumn::HEADER_BYTES;
+using multcolumn::MAX_SIDES;
 constexpr uint64_t MAX_SIZE = 1ull << 28;
 constexpr uint32_t LDS_THREADS = 1024;               // lanes a workgroup of the LDS count kernel
 constexpr uint32_t LDS_BLOCKS = 512;                 // its workgroups at most: two a compute unit

@@ -121,35 +121,55 @@ const tupleCheckProbe = () => Number(addon.tupleCheckProbe());
 // The wording, once (INTEGRATION.md):
 //   "lookup: f side S row R = (v0, v1, ..) occurs in no selected row of t"
 const formatMissing = (x, values) => "lookup: f side " + x.side + " row " + x.row + " = (" + values.join(", ") + ") occurs in no selected row of t";
-function multiplicities(dev, fsIn, tIn, mIn, n, opts) {
-    const ew = opts && opts.bn128 ? 4 : 1;
+// What the two multiplicity calls share.  The arguments every one refuses alike:
+function checkMultArgs(fsIn, mIn) {
     if (!Array.isArray(fsIn) || fsIn.length < 1 || fsIn.length > 8) throw new Error("fs must be an array of 1 .. 8 sides");
     if (!mIn || !(mIn.stride > 0) || !(mIn.col >= 0)) throw new Error("m must be { buf, stride, col }");
-    const t = side(tIn, "t", n, ew, dev), fs = fsIn.map((f, s) => side(f, "f " + s, n, ew, dev)), k = t.cols.length;
-    fs.forEach((f, s) => { if (f.cols.length !== k) throw new Error("t has " + k + " columns and f " + s + " " + f.cols.length); });
+}
+// the caller's bytes from the words the addon wrote, where asWords copied (bytes off 8)
+function copyBack(words, given) {
+    if (words.buffer !== given.buffer) new Uint8Array(given.buffer, given.byteOffset, given.byteLength).set(new Uint8Array(words.buffer));
+}
+// the host matrices as the addon's array takes them: a side's matrix, then its selector's or null
+const matrices = (sides) => [].concat(...sides.map((x) => [x.buf, x.sel ? x.sel.buf : null]));
+// The call itself: the sides (tIn null: no table side), their six words in pil2gl_tuple_side's order, m written and copied back, the scratch
+// of the device form from the plan and for the call, and { matched, missing } with a message() that reads the row only when it is called.
+// unit: columns(fs, t) -> k, or throws; third(x): the word in the columns' place of a side's six; desc(k, m's three words, the sides' six
+// words, sides) -> the description; plan(k, nF), host, dev: the addon's entries; format(missing, the row's values)
+function multColumn(dev, tIn, fsIn, mIn, n, ew, unit) {
+    const t = tIn ? side(tIn, "t", n, ew, dev) : null, fs = fsIn.map((f, s) => side(f, "f " + s, n, ew, dev)), k = unit.columns(fs, t);
     const m = side({ buf: mIn.buf, stride: mIn.stride, cols: [mIn.col] }, "m", n, ew, dev);
-    const sides = [t].concat(fs), ptr = (b) => dev && b ? b.ptr : 0n;
-    const head = [n, k, fs.length, ptr(m.buf), m.stride, mIn.col];
-    const six = sides.map((x) => [ptr(x.buf), x.stride, 0].concat(x.sel ? [ptr(x.sel.buf), x.sel.stride, x.sel.col] : [0n, 0, 0]));
-    const desc = BigUint64Array.from(head.concat(...six, ...sides.map((x) => x.cols)).map((v) => BigInt(v)));
+    const sides = (t ? [t] : []).concat(fs), ptr = (b) => dev && b ? b.ptr : 0n;
+    const six = sides.map((x) => [ptr(x.buf), x.stride, unit.third(x)].concat(x.sel ? [ptr(x.sel.buf), x.sel.stride, x.sel.col] : [0n, 0, 0]));
+    const desc = BigUint64Array.from(unit.desc(k, [ptr(m.buf), m.stride, mIn.col], six, sides).map((v) => BigInt(v)));
     const rep = new BigUint64Array(4);
     let read;
     if (!dev) {
-        addon.lookupMult(desc, [].concat(...sides.map((x) => [x.buf, x.sel ? x.sel.buf : null]), [m.buf]), rep, ew);
-        if (m.buf.buffer !== mIn.buf.buffer) new Uint8Array(mIn.buf.buffer, mIn.buf.byteOffset, mIn.buf.byteLength).set(new Uint8Array(m.buf.buffer));      // bytes off 8: asWords copied
+        unit.host(desc, matrices(sides).concat([m.buf]), rep, ew);
+        copyBack(m.buf, mIn.buf);
         read = (buf, at, len) => buf.subarray(at, at + len);
     } else {
-        const plan = addon.lookupMultPlan(n, k, fs.length, ew);
+        const plan = unit.plan(k, fs.length);
         const work = new DevBuffer(Math.max(2, plan.scratchBytes / 8));
-        try { addon.lookupMultDev(desc, work.ptr, plan.scratchBytes, rep, ew); } finally { work.free(); }
+        try { unit.dev(desc, work.ptr, plan.scratchBytes, rep, ew); } finally { work.free(); }
         read = (buf, at, len) => buf.slice(at, at + len);
     }
     const out = { matched: Number(rep[3]), missing: null };
     if (rep[0] !== 0n) {
         const x = out.missing = { side: Number(rep[1]), row: Number(rep[2]) };
-        x.message = () => { const f = fs[x.side]; return formatMissing(x, f.cols.map((c) => decimalOf(read(f.buf, (x.row * f.stride + c) * ew, ew)))); };
+        x.message = () => { const f = fs[x.side]; return unit.format(x, f.cols.map((c) => decimalOf(read(f.buf, (x.row * f.stride + c) * ew, ew)))); };
     }
     return out;
+}
+function multiplicities(dev, fsIn, tIn, mIn, n, opts) {
+    const ew = opts && opts.bn128 ? 4 : 1;
+    checkMultArgs(fsIn, mIn);
+    return multColumn(dev, tIn || {}, fsIn, mIn, n, ew, {                        // {}: refused as a side, where null would say "no table side"
+        columns: (fs, t) => { const k = t.cols.length; fs.forEach((f, s) => { if (f.cols.length !== k) throw new Error("t has " + k + " columns and f " + s + " " + f.cols.length); }); return k; },
+        third: () => 0,
+        desc: (k, m, six, sides) => [n, k, sides.length - 1].concat(m, ...six, ...sides.map((x) => x.cols)),
+        plan: (k, nF) => addon.lookupMultPlan(n, k, nF, ew), host: addon.lookupMult, dev: addon.lookupMultDev, format: formatMissing,
+    });
 }
 const lookupMultiplicities = (fs, t, m, n, opts) => multiplicities(false, fs, t, m, n, opts);
 const lookupMultiplicitiesDev = (fs, t, m, n, opts) => multiplicities(true, fs, t, m, n, opts);
@@ -161,35 +181,16 @@ const lookupMultProbe = () => Number(addon.lookupMultProbe());
 const formatOutOfRange = (x, value, lo, size) => "range: f side " + x.side + " row " + x.row + " = " + value + " is outside [" + lo + ", " + (lo + BigInt(size) - 1n) + "]";
 function rangeCounts(dev, fsIn, loIn, size, mIn, n, opts) {
     const ew = opts && opts.bn128 ? 4 : 1, row0 = opts && opts.row0 ? opts.row0 : 0;
-    if (!Array.isArray(fsIn) || fsIn.length < 1 || fsIn.length > 8) throw new Error("fs must be an array of 1 .. 8 sides");
-    if (!mIn || !(mIn.stride > 0) || !(mIn.col >= 0)) throw new Error("m must be { buf, stride, col }");
+    checkMultArgs(fsIn, mIn);
     const lo = BigInt(loIn);
     if (lo < -(1n << 63n) || lo >= 1n << 63n) throw new Error("lo must be a signed 64-bit integer");
-    const fs = fsIn.map((f, s) => side(f, "f " + s, n, ew, dev));
-    fs.forEach((f, s) => { if (f.cols.length !== 1) throw new Error("f " + s + " must have one column"); });
-    const m = side({ buf: mIn.buf, stride: mIn.stride, cols: [mIn.col] }, "m", n, ew, dev);
-    const ptr = (b) => dev && b ? b.ptr : 0n;
-    const head = [n, fs.length, BigInt.asUintN(64, lo), size, row0, ptr(m.buf), m.stride, mIn.col];
-    const six = fs.map((x) => [ptr(x.buf), x.stride, x.cols[0]].concat(x.sel ? [ptr(x.sel.buf), x.sel.stride, x.sel.col] : [0n, 0, 0]));
-    const desc = BigUint64Array.from(head.concat(...six).map((v) => BigInt(v)));
-    const rep = new BigUint64Array(4);
-    let read;
-    if (!dev) {
-        addon.rangeMult(desc, [].concat(...fs.map((x) => [x.buf, x.sel ? x.sel.buf : null]), [m.buf]), rep, ew);
-        if (m.buf.buffer !== mIn.buf.buffer) new Uint8Array(mIn.buf.buffer, mIn.buf.byteOffset, mIn.buf.byteLength).set(new Uint8Array(m.buf.buffer));      // bytes off 8: asWords copied
-        read = (buf, at, len) => buf.subarray(at, at + len);
-    } else {
-        const plan = addon.rangeMultPlan(n, size, fs.length, ew);
-        const work = new DevBuffer(Math.max(2, plan.scratchBytes / 8));
-        try { addon.rangeMultDev(desc, work.ptr, plan.scratchBytes, rep, ew); } finally { work.free(); }
-        read = (buf, at, len) => buf.slice(at, at + len);
-    }
-    const out = { matched: Number(rep[3]), missing: null };
-    if (rep[0] !== 0n) {
-        const x = out.missing = { side: Number(rep[1]), row: Number(rep[2]) };
-        x.message = () => { const f = fs[x.side]; return formatOutOfRange(x, decimalOf(read(f.buf, (x.row * f.stride + f.cols[0]) * ew, ew)), lo, size); };
-    }
-    return out;
+    return multColumn(dev, null, fsIn, mIn, n, ew, {
+        columns: (fs) => { fs.forEach((f, s) => { if (f.cols.length !== 1) throw new Error("f " + s + " must have one column"); }); return 1; },
+        third: (x) => x.cols[0],
+        desc: (k, m, six, sides) => [n, sides.length, BigInt.asUintN(64, lo), size, row0].concat(m, ...six),
+        plan: (k, nF) => addon.rangeMultPlan(n, size, nF, ew), host: addon.rangeMult, dev: addon.rangeMultDev,
+        format: (x, values) => formatOutOfRange(x, values[0], lo, size),
+    });
 }
 const rangeMultiplicities = (fs, lo, size, m, n, opts) => rangeCounts(false, fs, lo, size, m, n, opts);
 const rangeMultiplicitiesDev = (fs, lo, size, m, n, opts) => rangeCounts(true, fs, lo, size, m, n, opts);
@@ -219,8 +220,8 @@ function logup(dev, termsIn, alpha, beta, outIn, n, opts) {
     const slots = terms.map((x) => x.cols.concat(new Array(16 - x.cols.length).fill(0)));
     const desc = BigUint64Array.from(head.concat(...fourteen, ...slots).map((v) => BigInt(v)));
     if (dev) { addon.logupSumDev(desc, ew, opts && opts.stream); return outIn; }
-    addon.logupSum(desc, [].concat(...terms.map((x) => [x.buf, x.sel ? x.sel.buf : null]), [out.buf]), ew);
-    if (out.buf.buffer !== outIn.buf.buffer) new Uint8Array(outIn.buf.buffer, outIn.buf.byteOffset, outIn.buf.byteLength).set(new Uint8Array(out.buf.buffer));      // bytes off 8: asWords copied
+    addon.logupSum(desc, matrices(terms).concat([out.buf]), ew);
+    copyBack(out.buf, outIn.buf);
     return outIn;
 }
 const logupSum = (terms, alpha, beta, out, n, opts) => logup(false, terms, alpha, beta, out, n, opts);

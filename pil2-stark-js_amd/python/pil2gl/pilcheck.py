@@ -27,13 +27,20 @@ LOOKUP, PERMUTATION = 0, 1
 _WORDS = {"gl": 1, "bn128": 4}
 
 
-def tuple_check_plan(n, k, field="gl", mode=LOOKUP):
-    """pil2gl_tuple_check_plan (host-only): the hash table's capacity, the launch geometry, the working buffer"""
+def _plan(entry, args, names, bytes_name="scratchBytes"):
+    """a host-only plan entry: six words under their names and a byte count"""
     info = (C.c_uint32 * 6)()
     nbytes = C.c_uint64()
-    call("pil2gl_tuple_check_plan", n, k, _WORDS[field], mode, info, C.byref(nbytes))
-    names = ("capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes")
-    return dict(zip(names, (int(x) for x in info)), scratchBytes=nbytes.value)
+    call(entry, *args, info, C.byref(nbytes))
+    return dict(zip(names, (int(x) for x in info)), **{bytes_name: nbytes.value})
+
+
+_TABLE_PLAN = ("capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes")
+
+
+def tuple_check_plan(n, k, field="gl", mode=LOOKUP):
+    """pil2gl_tuple_check_plan (host-only): the hash table's capacity, the launch geometry, the working buffer"""
+    return _plan("pil2gl_tuple_check_plan", (n, k, _WORDS[field], mode), _TABLE_PLAN)
 
 
 def tuple_home(words, k, field="gl", capacity=16):
@@ -130,11 +137,7 @@ def perm_check_dev(f, f_cols, t, t_cols, n, field="gl", f_stride=None, t_stride=
 # matrix as a C-contiguous uint64 array -- and the four words (kind, side, row, matched) come back; clean is (0, NONE, NONE, matched).
 def lookup_mult_plan(n, k, n_f=1, field="gl"):
     """pil2gl_lookup_mult_plan (host-only): the hash table's capacity, the launch geometry, the working buffer"""
-    info = (C.c_uint32 * 6)()
-    nbytes = C.c_uint64()
-    call("pil2gl_lookup_mult_plan", n, k, n_f, _WORDS[field], info, C.byref(nbytes))
-    names = ("capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes")
-    return dict(zip(names, (int(x) for x in info)), scratchBytes=nbytes.value)
+    return _plan("pil2gl_lookup_mult_plan", (n, k, n_f, _WORDS[field]), _TABLE_PLAN)
 
 
 def lookup_mult_probe():
@@ -142,37 +145,57 @@ def lookup_mult_probe():
     return int(load().pil2gl_debug_lookup_mult_probe())
 
 
-def _mult(dev, fs, t, m, n, field):
-    from ._lib import TupleSide
-    words = _WORDS[field]
-    ptr = (lambda a: _ptr(a)) if dev else (lambda a: None if a is None else a.ctypes.data)
-    keep = []                                                                    # the column arrays live until the call returns
+def _dev_ptr(dev):
+    """a buffer's address as the entries take it; None stays null"""
+    return (lambda a: _ptr(a)) if dev else (lambda a: None if a is None else a.ctypes.data)
 
-    def struct(spec, what):
-        spec = tuple(spec) + (None,) * (4 - len(spec))
-        b, stride, cols, sm, sstride, scol = _side(spec[0], spec[1], spec[3], spec[2], n, words, dev, what)
+
+def _sides(specs, whats, at, n, words, dev):
+    """side specs (matrix, cols, sel, .., stride at `at`) as a TupleSide array (one element at least), each side's column count, and what
+    must stay alive until the call returns: the buffers and the column arrays"""
+    from ._lib import TupleSide
+    ptr, keep, ks = _dev_ptr(dev), [], []
+    arr = (TupleSide * max(len(specs), 1))()
+    for i, (spec, what) in enumerate(zip(specs, whats)):
+        spec = tuple(spec) + (None,) * (at + 1 - len(spec))
+        b, stride, cols, sm, sstride, scol = _side(spec[0], spec[1], spec[at], spec[2], n, words, dev, what)
         keep.extend((b, cols, sm))
-        return TupleSide(ptr(b), stride, cols.ctypes.data, ptr(sm), sstride, scol), cols.size
-    sides = [struct(s, "f %d" % i) for i, s in enumerate(fs)]
-    T, k = struct(t, "t")
-    if any(kk != k for _, kk in sides):
-        raise Pil2glError("t has %d columns, every f must have as many" % k)
+        ks.append(cols.size)
+        arr[i] = TupleSide(ptr(b), stride, cols.ctypes.data, ptr(sm), sstride, scol)
+    return arr, ks, keep
+
+
+def _column(m, what, width, n, words, dev):
+    """a column written in place, (matrix, col) or (matrix, col, stride), `width` words wide: its address, stride and column"""
     if not dev and not (isinstance(m[0], np.ndarray) and m[0].dtype == np.uint64 and m[0].flags.c_contiguous and m[0].flags.writeable):
-        raise Pil2glError("m: the host form writes in place and takes a C-contiguous writeable uint64 array")
-    mm, held, mstride = _matrix(m[0], m[2] if len(m) > 2 else None, words, dev, "m")
-    if n and held < ((n - 1) * mstride + m[1] + 1) * words:
-        raise Pil2glError("m holds %d words, %d rows of stride %d need more" % (held, n, mstride))
-    F = (TupleSide * max(len(sides), 1))(*[s for s, _ in sides])
+        raise Pil2glError("%s: the host form writes in place and takes a C-contiguous writeable uint64 array" % what)
+    mm, held, stride = _matrix(m[0], m[2] if len(m) > 2 else None, words, dev, what)
+    if n and held < ((n - 1) * stride + m[1] + width) * words:
+        raise Pil2glError("%s holds %d words, %d rows of stride %d need more" % (what, held, n, stride))
+    return mm, [_dev_ptr(dev)(mm), stride, m[1]]
+
+
+def _report4(dev, host_entry, dev_entry, args, plan, like, *dev_tail):
+    """a multiplicity entry -> its four words; the device form takes its scratch from plan() on like's device"""
     rep = (C.c_uint64 * 4)()
-    name = "pil2gl_lookup_mult" if words == 1 else "pil2gl_bn128_lookup_mult"
-    args = [F, len(sides), C.byref(T), ptr(mm), mstride, m[1], n, k]
     if dev:
-        plan = lookup_mult_plan(n, k, min(max(len(sides), 1), 8), field)
-        work = torch.empty(max(plan["scratchBytes"] // 8, 2), dtype=torch.int64, device=mm.device)
-        call(name + "_dev", *args, _ptr(work), plan["scratchBytes"], rep, _stream())
+        nbytes = plan()["scratchBytes"]
+        work = torch.empty(max(nbytes // 8, 2), dtype=torch.int64, device=like.device)
+        call(dev_entry, *args, _ptr(work), nbytes, rep, _stream(), *dev_tail)
     else:
-        call(name, *args, rep)
+        call(host_entry, *args, rep)
     return tuple(int(x) for x in rep)
+
+
+def _mult(dev, fs, t, m, n, field):
+    words = _WORDS[field]
+    F, ks, keep = _sides(fs, ["f %d" % i for i in range(len(fs))], 3, n, words, dev)
+    T, (k,), keep_t = _sides([t], ["t"], 3, n, words, dev)
+    if any(kk != k for kk in ks):
+        raise Pil2glError("t has %d columns, every f must have as many" % k)
+    mm, col = _column(m, "m", 1, n, words, dev)
+    name = "pil2gl_lookup_mult" if words == 1 else "pil2gl_bn128_lookup_mult"
+    return _report4(dev, name, name + "_dev", [F, len(fs), T] + col + [n, k], lambda: lookup_mult_plan(n, k, min(max(len(fs), 1), 8), field), mm)
 
 
 def lookup_mult(fs, t, m, n, field="gl"):
@@ -193,49 +216,23 @@ def lookup_mult_dev(fs, t, m, n, field="gl"):
 # for the tests and the benchmark (0 LDS, 1 global, None the planner's choice).
 def range_mult_plan(n, size, n_f=1, field="gl", path=None):
     """pil2gl_range_mult_plan (host-only): the count path, the launch geometry, the working buffer"""
-    info = (C.c_uint32 * 6)()
-    nbytes = C.c_uint64()
-    if path is None:
-        call("pil2gl_range_mult_plan", n, size, n_f, _WORDS[field], info, C.byref(nbytes))
-    else:
-        call("pil2gl_debug_range_mult_plan", n, size, n_f, _WORDS[field], path, info, C.byref(nbytes))
     names = ("path", "threads", "blocks", "launches", "headerBytes", "ldsCounters")
-    return dict(zip(names, (int(x) for x in info)), scratchBytes=nbytes.value)
+    if path is None:
+        return _plan("pil2gl_range_mult_plan", (n, size, n_f, _WORDS[field]), names)
+    return _plan("pil2gl_debug_range_mult_plan", (n, size, n_f, _WORDS[field], path), names)
 
 
 def _range(dev, fs, lo, size, m, n, field, row0, path):
-    from ._lib import TupleSide
     words = _WORDS[field]
-    ptr = (lambda a: _ptr(a)) if dev else (lambda a: None if a is None else a.ctypes.data)
-    keep = []                                                                    # the column arrays live until the call returns
-
-    def struct(spec, what):
-        spec = tuple(spec) + (None,) * (4 - len(spec))
-        b, stride, cols, sm, sstride, scol = _side(spec[0], spec[1], spec[3], spec[2], n, words, dev, what)
-        if cols.size != 1:
+    whats = ["f %d" % i for i in range(len(fs))]
+    F, ks, keep = _sides(fs, whats, 3, n, words, dev)
+    for what, k in zip(whats, ks):
+        if k != 1:
             raise Pil2glError("%s: a side of a range check has one column" % what)
-        keep.extend((b, cols, sm))
-        return TupleSide(ptr(b), stride, cols.ctypes.data, ptr(sm), sstride, scol)
-    sides = [struct(s, "f %d" % i) for i, s in enumerate(fs)]
-    if not dev and not (isinstance(m[0], np.ndarray) and m[0].dtype == np.uint64 and m[0].flags.c_contiguous and m[0].flags.writeable):
-        raise Pil2glError("m: the host form writes in place and takes a C-contiguous writeable uint64 array")
-    mm, held, mstride = _matrix(m[0], m[2] if len(m) > 2 else None, words, dev, "m")
-    if n and held < ((n - 1) * mstride + m[1] + 1) * words:
-        raise Pil2glError("m holds %d words, %d rows of stride %d need more" % (held, n, mstride))
-    F = (TupleSide * max(len(sides), 1))(*sides)
-    rep = (C.c_uint64 * 4)()
+    mm, col = _column(m, "m", 1, n, words, dev)
     name = "pil2gl_range_mult" if words == 1 else "pil2gl_bn128_range_mult"
-    args = [F, len(sides), lo, size, row0, ptr(mm), mstride, m[1], n]
-    if dev:
-        plan = range_mult_plan(n, size, min(max(len(sides), 1), 8), field, path)
-        work = torch.empty(max(plan["scratchBytes"] // 8, 2), dtype=torch.int64, device=mm.device)
-        if path is None:
-            call(name + "_dev", *args, _ptr(work), plan["scratchBytes"], rep, _stream())
-        else:
-            call("pil2gl_debug_range_mult_dev", *args, _ptr(work), plan["scratchBytes"], rep, _stream(), words, path)
-    else:
-        call(name, *args, rep)
-    return tuple(int(x) for x in rep)
+    dev_entry, tail = (name + "_dev", ()) if path is None else ("pil2gl_debug_range_mult_dev", (words, path))
+    return _report4(dev, name, dev_entry, [F, len(fs), lo, size, row0] + col + [n], lambda: range_mult_plan(n, size, min(max(len(fs), 1), 8), field, path), mm, *tail)
 
 
 def range_mult(fs, lo, size, m, n, field="gl", row0=0):
@@ -259,25 +256,19 @@ def range_mult_dev(fs, lo, size, m, n, field="gl", row0=0, path=None):
 # stride): over Goldilocks a matrix of u64 words whose columns col .. col + 2 take s, over Fr one element column.  Written in place.
 def logup_sum_plan(n, n_terms=1, field="gl"):
     """pil2gl_logup_sum_plan (host-only): the launch geometry, the launches and the working bytes"""
-    info = (C.c_uint32 * 6)()
-    nbytes = C.c_uint64()
-    call("pil2gl_logup_sum_plan", n, n_terms, _WORDS[field], info, C.byref(nbytes))
-    names = ("threads", "items", "blocks", "launches", "depth", "outWidth")
-    return dict(zip(names, (int(x) for x in info)), workBytes=nbytes.value)
+    return _plan("pil2gl_logup_sum_plan", (n, n_terms, _WORDS[field]), ("threads", "items", "blocks", "launches", "depth", "outWidth"), "workBytes")
 
 
 def _logup(dev, terms, alpha, beta, out, n, field):
-    from ._lib import LogupTerm, TupleSide
+    from ._lib import LogupTerm
     words = _WORDS[field]
-    ptr = (lambda a: _ptr(a)) if dev else (lambda a: None if a is None else a.ctypes.data)
-    keep = []                                                                    # the column arrays live until the call returns
     T = (LogupTerm * max(len(terms), 1))()
-    for u, spec in enumerate(terms[:len(T)]):
+    keep = []
+    for u, spec in enumerate(terms):
         spec = tuple(spec) + (None,) * (6 - len(spec))
-        b, stride, cols, sm, sstride, scol = _side(spec[0], spec[1], spec[5], spec[2], n, words, dev, "term %d" % u)
-        keep.extend((b, cols, sm))
-        T[u].side = TupleSide(ptr(b), stride, cols.ctypes.data, ptr(sm), sstride, scol)
-        T[u].k = cols.size
+        side, (T[u].k,), kept = _sides([spec], ["term %d" % u], 5, n, words, dev)
+        T[u].side = side[0]
+        keep.append(kept)
         for name, v in (("coef", spec[3]), ("busId", spec[4])):
             w = np.ascontiguousarray([v] if words == 1 else v, np.uint64).reshape(-1)
             if w.size != words:
@@ -287,14 +278,9 @@ def _logup(dev, terms, alpha, beta, out, n, field):
     ch = [np.ascontiguousarray(c, np.uint64).reshape(-1) for c in (alpha, beta)]
     if any(c.size != (3 if words == 1 else 4) for c in ch):
         raise Pil2glError("alpha and beta are %d words each" % (3 if words == 1 else 4))
-    if not dev and not (isinstance(out[0], np.ndarray) and out[0].dtype == np.uint64 and out[0].flags.c_contiguous and out[0].flags.writeable):
-        raise Pil2glError("out: the host form writes in place and takes a C-contiguous writeable uint64 array")
-    om, held, ostride = _matrix(out[0], out[2] if len(out) > 2 else None, words, dev, "out")
-    top = out[1] + (2 if words == 1 else 0)
-    if n and held < ((n - 1) * ostride + top + 1) * words:
-        raise Pil2glError("out holds %d words, %d rows of stride %d need more" % (held, n, ostride))
+    om, col = _column(out, "out", 3 if words == 1 else 1, n, words, dev)
     name = "pil2gl_logup_sum" if words == 1 else "pil2gl_bn128_logup_sum"
-    args = [T, len(terms), C.c_void_p(ch[0].ctypes.data), C.c_void_p(ch[1].ctypes.data), ptr(om), ostride, out[1], n]
+    args = [T, len(terms), C.c_void_p(ch[0].ctypes.data), C.c_void_p(ch[1].ctypes.data)] + col + [n]
     if dev:
         call(name + "_dev", *args, _stream())
     else:

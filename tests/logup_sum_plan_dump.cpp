@@ -41,7 +41,7 @@ int main(int argc, char **argv) {
             const uint32_t width = logupplan::out_width((uint32_t)a[1]);
             const uint64_t oCols[3] = { oCol, oCol + 1, oCol + 2 };
             const bool columns = !tupleside::check_columns(n, oStride, oCols, width) && !tupleside::check_columns(n, rStride, cols.empty() ? nullptr : cols.data(), cols.size());
-            const lookupmultplan::ReadMatrix r{ (const void *)(uintptr_t)a[5], rStride, cols.data(), cols.size() };
+            const multcolumn::ReadMatrix r{ (const void *)(uintptr_t)a[5], rStride, cols.data(), cols.size() };
             const bool ok = columns && logupplan::out_allowed((const void *)(uintptr_t)a[2], oStride, oCol, width, r, n, (uint32_t)a[1]);
             printf("{\"ok\": %d, \"columns\": %d}\n", ok ? 1 : 0, columns ? 1 : 0);
             continue;

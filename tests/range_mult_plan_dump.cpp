@@ -6,7 +6,7 @@
 //     rows n size row0                            {"ok": 0 | 1}   do the table's rows [row0, row0 + size) lie within n rows
 //     lo L                                        {"p": lo mod p, "r": [four 64-bit limbs of lo mod r]}   L a signed 64-bit integer
 //     alias n words mBase mStride mCol rBase rStride k c0 .. ck-1
-//                                                  {"ok": 0 | 1, "columns": 0 | 1}   lookup_mult_plan.h's m_allowed, as this unit calls it
+//                                                  {"ok": 0 | 1, "columns": 0 | 1}   mult_column_plan.h's m_allowed, as this unit calls it
 // Exits non-zero when a command cannot be read.
 #include <stdio.h>
 #include <inttypes.h>
@@ -41,8 +41,8 @@ int main(int argc, char **argv) {
             for (uint64_t &c : cols) if (!rd(f, &c)) return 2;
             const uint64_t n = a[0], mStride = a[3], mCol = a[4], rStride = a[6];
             const bool columns = !tupleside::check_columns(n, mStride, &mCol, 1) && !tupleside::check_columns(n, rStride, cols.empty() ? nullptr : cols.data(), cols.size());
-            const lookupmultplan::ReadMatrix r{ (const void *)(uintptr_t)a[5], rStride, cols.data(), cols.size() };
-            const bool ok = columns && lookupmultplan::m_allowed((const void *)(uintptr_t)a[2], mStride, mCol, r, n, (uint32_t)a[1]);
+            const multcolumn::ReadMatrix r{ (const void *)(uintptr_t)a[5], rStride, cols.data(), cols.size() };
+            const bool ok = columns && multcolumn::m_allowed((const void *)(uintptr_t)a[2], mStride, mCol, r, n, (uint32_t)a[1]);
             printf("{\"ok\": %d, \"columns\": %d}\n", ok ? 1 : 0, columns ? 1 : 0);
             continue;
         }

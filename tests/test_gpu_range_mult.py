@@ -133,6 +133,19 @@ def test_range_shapes_on_the_planners_path(field, size, n):
 
 @pytest.mark.parametrize("field", list(FIELDS))
 @pytest.mark.parametrize("path", [0, 1])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+def test_wave_edges_on_each_count_kernel(field, path, n):
+    """the end of a count kernel is wave-level (csrc/mult_column.cuh): one lane, a wave less one, a whole wave, a wave and one, a workgroup of
+    path 1 and one, each with its only failing row in the last lane that has one"""
+    size, lo = min(3, n), -1
+    f = [lo + i % size for i in range(n)]
+    f[n - 1] = lo + size
+    m, rep = run(field, {"F": column(field, f)}, [("F", 0)], lo, size, ("M", 1), n, path=path, host=False)
+    assert rep == (1, 0, n - 1, n - 1) and sum(m) == n - 1
+
+
+@pytest.mark.parametrize("field", list(FIELDS))
+@pytest.mark.parametrize("path", [0, 1])
 def test_several_workgroups_flush_into_the_same_counters(field, path):
     n, size = (1 << 13) + 3, 256
     assert pilcheck.range_mult_plan(n, size, 1, field, path)["blocks"] >= 3 and pilcheck.range_mult_plan(n, size, 1, field, path)["path"] == path

@@ -153,6 +153,44 @@ def test_planner_and_aliasing_rule_under_the_sanitizers(tmp_path):
     assert [(g["ok"], g["columns"]) for g in out[at:]] == [w for _, w in alias]
 
 
+def test_shared_buffer_check_under_the_sanitizers(tmp_path):
+    """csrc/mult_column_plan.h's check_buffers, the one copy that lookup_mult.hip and range_mult.hip call, over addresses that are never
+    dereferenced: n = 8 rows of 4 words, t (column 1: a span of 240 bytes), one f with a selector, m and a scratch of 192 bytes"""
+    exe = str(tmp_path / "lookup_mult_plan_dump")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "lookup_mult_plan_dump.cpp"), "-o", exe])
+    B = 1 << 40
+    T, F, SEL, M, W, NEED = B, B + 0x1000, B + 0x2000, B + 0x3000, B + 0x4000, 192
+    ALIGNED, SHORT, OVER = "t, every f, the selectors, m and the scratch must be 16-byte aligned", "the scratch holds 191 bytes, 192 needed", \
+        "the scratch overlaps t, an f, a selector or m"
+
+    def cmd(dev, n=8, work=W, have=NEED, need=NEED, m=M, m_col=3, t=T, f=F, sel=SEL, sel_col=2, t_col=1):
+        sides = "%d 4 0 0 0 %d  %d 4 %d 4 %d 0" % (t, t_col, f, sel, sel_col)
+        return "buffers %d %d 1 %d %d %d %d 4 %d 1 2 %s\n" % (dev, n, work if dev else 0, have if dev else 0, need, m, m_col, sides)
+    cases = [(cmd(1), ""), (cmd(0), "")]
+    cases += [(cmd(d, m=0), "null buffer") for d in (0, 1)] + [(cmd(d, f=0), "null buffer") for d in (0, 1)] + [(cmd(d, sel=0, sel_col=9), "") for d in (0, 1)]
+    cases += [(cmd(1, work=0), "null buffer"), (cmd(0, work=0), "")]                     # a null scratch: the device form only
+    for key, at in (("t", T), ("f", F), ("sel", SEL), ("m", M), ("work", W)):            # one misaligned pointer of each kind
+        cases += [(cmd(1, **{key: at + 8}), ALIGNED)]
+        cases += [(cmd(0, **{key: at + 8}), "")] if key != "work" else []
+    cases += [(cmd(1, have=NEED - 1), SHORT), (cmd(1, have=NEED), ""), (cmd(1, have=NEED + 1), "")]
+    cases += [(cmd(1, work=T + 224), OVER), (cmd(1, work=T + 240), "")]                  # t's last byte is 239
+    cases += [(cmd(1, work=T + 224, t_col=0), OVER), (cmd(1, work=T + 240, t_col=0), "")]       # ... or 231, inside the scratch's first 16 bytes
+    cases += [(cmd(1, work=M - NEED, need=NEED + 1, have=NEED + 1), OVER), (cmd(1, work=M - NEED), "")]      # the scratch's last byte on m's first
+    cases += [(cmd(1, work=SEL + 16), OVER), (cmd(1, work=F - NEED + 16), OVER)]
+    cases += [(cmd(d, m=T, m_col=1), "m overlaps") for d in (0, 1)] + [(cmd(d, m=T, m_col=0), "") for d in (0, 1)]
+    cases += [(cmd(d, m=SEL, m_col=2), "m overlaps") for d in (0, 1)] + [(cmd(d, m=SEL, m_col=2, sel=0), "") for d in (0, 1)]      # an absent selector meets nothing
+    cases += [(cmd(1, n=0, m=T, m_col=1, work=T), ""), (cmd(0, n=0, m=T, m_col=1), ""), (cmd(1, n=0, m=0), "null buffer")]      # no rows: nothing meets
+    with open(tmp_path / "cmds.txt", "w") as f:
+        f.write("".join(c for c, _ in cases))
+    run = subprocess.run([exe, str(tmp_path / "cmds.txt")], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stderr == "", "sanitizer report:\n" + run.stderr[-4000:]
+    out = [json.loads(line)["why"] for line in run.stdout.splitlines()]
+    assert len(out) == len(cases)
+    for (c, want), got in zip(cases, out):
+        assert got == want if want in ("", ALIGNED, SHORT, OVER, "null buffer") else got.startswith(want), (c, got)
+
+
 # ---- the compute entries ----
 def test_compute_entries_refuse_before_any_device_call(lib):
     buf = np.zeros(16384, np.uint64)
