@@ -24,7 +24,7 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; land_rows with a null hostFirstBad;
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; grand_prod and bn128_grand_prod; land_rows with a null hostFirstBad;
  *      wtns_adds and bn128_wtns_adds, wtns_gather and bn128_wtns_gather with a null hostFirstBad, conn_pols and bn128_conn_pols with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, logup_sum_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, logup_sum_plan, grand_prod_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -1115,6 +1115,73 @@ int pil2gl_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const 
                      uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
 int pil2gl_bn128_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
                            uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
+
+/* ---- grand product: the column z of a permutation or a connection from the trace columns (csrc/grand_prod_plan.h, hints.hip, bn_scan.hip) ----
+ * The sibling of the block above for the `gprod` hints (grandProductPermutation.js:121-126, grandProductConnection.js:131-136): z in one
+ * call from the columns where they lie, without the two extension columns num and den (the hints' tmp fields) that gprod needs ready.
+ * The statement is this header's own (tests/grand_prod_ref.py restates it over Python integers):
+ *   z[0] = 1,   z[i] = z[i-1] R[i-1]                          i < n   (calculateZ, polutils.js:132-145: the EXCLUSIVE product)
+ *   R[i]   = prod_{u: den_u = 0} D_u[i]  /  prod_{u: den_u = 1} D_u[i]          an empty product is 1
+ *   D_u[i] = B_u[i] + idCoef_u id_u[i] + gamma                 (id NULL: no such summand)
+ *   B_u[i] = H_u[i]                                           when the term's side has no selector
+ *          = (H_u[i] - beta) sel_u[i] + beta                  when it has one: sel's FIELD VALUE, not "non-zero"
+ *   H_u[i] = (..(v_0 alpha + v_1) alpha .. ) alpha + v_{k_u-1}  first column highest; there is no bus id
+ *   n <= 2^28 rows; 1 <= nTerms <= 40; the k of all terms add up to at most 64.  One term is a pil2gl_grand_prod_term: a
+ *   pil2gl_tuple_side, its k (1 .. 16), den (0: a factor of the numerator, 1: of the denominator), an optional id column -- column idCol
+ *   of the matrix (id, idStride) -- and idCoef, a HOST element of the challenges' field: over Goldilocks three canonical words of a
+ *   cubic-extension element (else PIL2GL_EINVAL), over Fr four Montgomery words.  alpha, beta, gamma: HOST pointers, three words each
+ *   over Goldilocks (x^3 = x + 1), four Montgomery words over Fr; all three must be given even where no term uses them.
+ *   Elements count as field values by the rules above (Goldilocks words in [p, 2^64) mod p, any Fr pattern mod r).
+ *   out: the block above's -- column outCol of (out, outStride); Goldilocks the three canonical words outCol .. outCol + 2 of a row
+ *   of u64 words, Fr one canonical Montgomery element.  Words between a strided destination's elements stay as they are.
+ *   Zeros: gprod's convention (stage-2 hints and the Fr block).  If any den factor of row i is zero, R[i] = 0 and every later z is 0; a
+ *   zero num factor is plain arithmetic.  The hint's `result` is z[n-1]: the caller copies it.
+ *   Equivalence: the column is word for word what pil2gl_gprod_dev(num, 3, den, 3, ..) / pil2gl_bn128_gprod_dev give on the two
+ *   materialised product columns.
+ * How the reference's identities map:
+ *   permutation (grandProductPermutation.js:35-48 the tuples' compression tExp = alpha tExp + e, 57-70 the same for f, 97 and 105
+ *   (exp - beta) sel + beta and + gamma): one term den = 0 with pi.f and selF, one term den = 1 with pi.t and selT; alpha, beta, gamma =
+ *   std_alpha, std_beta, std_gamma.  Several permutations share one z by listing more terms.
+ *   connection (grandProductConnection.js:35-45 the ks of the columns, 59-85 numExp *= a_j + delta ks'_j x + gamma and denExp *= a_j +
+ *   delta S_j + gamma): per column j of ci.pols one term den = 0 with k = 1, column a_j, id = the x column (over Goldilocks
+ *   pil2gl_build_x_dev(nBits, 1, ..)'s; over Fr the caller's own) and idCoef = delta ks'_j (ks' = 1, ks[0], ks[1], .., made on the
+ *   host), and one term den = 1 with column a_j, id = column S_j, idCoef = delta; gamma = std_gamma; alpha and beta are unused but must
+ *   be non-null.  A 12-column compressor takes 24 terms, an 18-column one 36: hence the limit of 40.
+ *   Out of scope: pil2 std's bus-id form of a product bus, a gamma per term, and pil2gl/stark.py's resolve_hints_info, which sees tmp
+ *   fields and not the identity's structure and stays as it is.
+ * pil2gl_grand_prod_plan: host-only, no device.  outInfo is logup_sum_plan's: [0] = threads per workgroup of the first pass; [1] = rows
+ * a lane of it takes (8, Fr 1); [2] = its workgroups; [3] = kernel launches of a call (Goldilocks 3: the fused first pass, the block
+ * totals' scan, the fix-up; Fr 4 levels - 1: the compress, then bn128_gprod's inversion and scan); [4] = Goldilocks: block totals a lane
+ * of the second pass walks, Fr: levels; [5] = u64 words of an output element's columns (3, or 1 element).  *workBytes = the working
+ * memory, from the library's own slots: Goldilocks gsum's 24 n + 24 ceil(n / 2048); Fr the scan plan's bytes + 64 n (N and D of every
+ * row).  PIL2GL_EINVAL: n > 2^28, nTerms outside 1 .. 40, sumK outside nTerms .. min(64, 16 nTerms), elemWords not 1 or 4.
+ * pil2gl_[bn128_]grand_prod_dev: hostTerms is a HOST pointer to terms whose side.base, side.sel and id are device pointers, 16-byte
+ * aligned, only read; matrices may overlap each other freely.  out = device, 16-byte aligned; its aliasing rule is logup_sum's, with the
+ * id and selector matrices counted as read matrices: z as spare columns of t's matrix is the normal case.  The call only ENQUEUES on the
+ * caller's stream: the packed term table travels as a kernel argument, nothing is copied and the host does not wait.  (On first use the
+ * working slots are allocated, with a device synchronise when they grow.)  PIL2GL_EINVAL, before any device call: what the plan refuses,
+ * k outside 1 .. 16, den above 1, a column >= its stride (outCol + 2 over Goldilocks), a stride >= 2^32 or n stride > 2^58 elements,
+ * null terms, cols, base, out, alpha, beta or gamma, a non-canonical Goldilocks idCoef, a misaligned device pointer, an out that breaks
+ * the aliasing rule.  n = 0 is PIL2GL_OK, touches nothing and needs no device.
+ * pil2gl_[bn128_]grand_prod: host pointers throughout; each matrix staged up to the last element touched, every part on 16 bytes, out's
+ * matrix goes up as it is and comes back with the column written.  Without a device the compute calls return PIL2GL_ENODEV. */
+typedef struct pil2gl_grand_prod_term {
+    pil2gl_tuple_side side;              /* the tuple's columns and the optional selector */
+    uint64_t k;                          /* columns of this term's tuple, 1 .. 16 */
+    uint64_t den;                        /* 0: the term multiplies the numerator, 1: the denominator */
+    const uint64_t *id;                  /* the id column's matrix, or NULL */
+    uint64_t idStride, idCol;
+    uint64_t idCoef[4];                  /* Goldilocks: 3 canonical words.  Fr: 4 Montgomery words */
+} pil2gl_grand_prod_term;
+int pil2gl_grand_prod_plan(uint64_t n, uint64_t nTerms, uint64_t sumK, uint32_t elemWords, uint32_t *outInfo /* [6] */, uint64_t *workBytes);
+int pil2gl_grand_prod_dev(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha /* [3] */, const uint64_t *hostBeta /* [3] */,
+                          const uint64_t *hostGamma /* [3] */, uint64_t *out, uint64_t outStride, uint64_t outCol, uint64_t n, void *stream);
+int pil2gl_bn128_grand_prod_dev(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha /* [4] */, const uint64_t *hostBeta /* [4] */,
+                                const uint64_t *hostGamma /* [4] */, uint64_t *out, uint64_t outStride, uint64_t outCol, uint64_t n, void *stream);
+int pil2gl_grand_prod(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                      const uint64_t *hostGamma, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
+int pil2gl_bn128_grand_prod(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                            const uint64_t *hostGamma, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

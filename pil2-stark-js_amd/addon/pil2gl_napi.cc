@@ -867,6 +867,74 @@ FN(LogupSum) {
     return mk_undefined(env);
 }
 
+// ---- grand product: the column z of a permutation or a connection (csrc/grand_prod_plan.h; js/pil_checks.js) ----
+FN(GrandProdPlan) {        // (n, nTerms, sumK, elemWords) -> { threads, items, blocks, launches, depth, outWidth, workBytes }
+    Args a(env, info); uint64_t n = a.u64(0), nT = a.u64(1), sumK = a.u64(2); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
+    uint32_t out[6]; uint64_t bytes = 0;
+    P2(env, pil2gl_grand_prod_plan(n, nT, sumK, ew, out, &bytes));
+    static const char *const names[6] = { "threads", "items", "blocks", "launches", "depth", "outWidth" };
+    return plan_object(env, names, out, "workBytes", bytes);
+}
+FN(GrandProdTermLayout) {  // -> sizeof and offsetof of pil2gl_grand_prod_term as this addon was compiled
+    static const char *names[8] = { "size", "side", "k", "den", "id", "idStride", "idCol", "idCoef" };
+    typedef pil2gl_grand_prod_term T;
+    const size_t at[8] = { sizeof(T), offsetof(T, side), offsetof(T, k), offsetof(T, den), offsetof(T, id), offsetof(T, idStride), offsetof(T, idCol), offsetof(T, idCoef) };
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 8; i++) { napi_create_uint32(env, (uint32_t)at[i], &v); napi_set_named_property(env, o, names[i], v); }
+    return o;
+}
+// A call's description, one BigUint64Array: [0] n, [1] nTerms, [2] out, [3] outStride, [4] outCol, [5..8] alpha, [9..12] beta, [13..16] gamma
+// (three words used over Goldilocks), then nTerms terms of 14 words -- base, stride, k, sel (0: none), selStride, selCol, den, id (0: none),
+// idStride, idCol, idCoef[4] -- then 16 column slots a term, the first k used.  The pointer words are device addresses for grandProdDev
+// and are not read by grandProd, which takes the host matrices as an array of its own.
+enum { GD_N, GD_NTERMS, GD_OUT, GD_OUT_STRIDE, GD_OUT_COL, GD_ALPHA, GD_BETA = GD_ALPHA + 4, GD_GAMMA = GD_BETA + 4, GD_TERMS = GD_GAMMA + 4, GD_TERM_WORDS = 14,
+       GD_COL_SLOTS = 16, GD_MAX_TERMS = 40 };
+struct GrandProdDesc { uint64_t *d; uint64_t n, nTerms; pil2gl_grand_prod_term term[GD_MAX_TERMS]; };
+static bool grand_prod_desc(Args &a, size_t i, GrandProdDesc &G) {
+    uint64_t len = 0; G.d = a.arr(i, GD_TERMS, &len);
+    if (!a.ok) return false;
+    G.n = G.d[GD_N]; G.nTerms = G.d[GD_NTERMS];
+    if (G.nTerms < 1 || G.nTerms > GD_MAX_TERMS || len < GD_TERMS + G.nTerms * (GD_TERM_WORDS + GD_COL_SLOTS))
+        return a.fail("the description holds 17 words, then 1 .. 40 terms of 14 words and 16 column slots each");
+    uint64_t *cols = G.d + GD_TERMS + G.nTerms * GD_TERM_WORDS;
+    for (uint64_t u = 0; u < G.nTerms; u++) {
+        const uint64_t *w = G.d + GD_TERMS + u * GD_TERM_WORDS;
+        pil2gl_grand_prod_term &t = G.term[u];
+        t.side = pil2gl_tuple_side{ (const uint64_t *)(uintptr_t)w[0], w[1], cols + u * GD_COL_SLOTS, (const uint64_t *)(uintptr_t)w[3], w[4], w[5] };
+        t.k = w[2]; t.den = w[6]; t.id = (const uint64_t *)(uintptr_t)w[7]; t.idStride = w[8]; t.idCol = w[9];
+        for (int c = 0; c < 4; c++) t.idCoef[c] = w[10 + c];
+    }
+    return true;
+}
+FN(GrandProdDev) {         // (description, elemWords[, stream]): only enqueues
+    Args a(env, info); GrandProdDesc G; if (!grand_prod_desc(a, 0, G)) return nullptr;
+    uint32_t ew = (uint32_t)a.u64(1); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_grand_prod_dev : pil2gl_grand_prod_dev)(G.term, G.nTerms, G.d + GD_ALPHA, G.d + GD_BETA, G.d + GD_GAMMA, (uint64_t *)(uintptr_t)G.d[GD_OUT],
+                                                                            G.d[GD_OUT_STRIDE], G.d[GD_OUT_COL], G.n, a.stream(2)));
+    return mk_undefined(env);
+}
+// (description, matrices, elemWords): matrices = an Array of BigUint64Array, four a term -- [4 u] the term's matrix, [4 u + 1] its selector's
+// or null, [4 u + 2] the term's matrix again, [4 u + 3] its id column's or null -- then out's matrix, which is written in place: the id
+// column travels through host_matrices as the selector of a second side over the same matrix
+FN(GrandProd) {
+    Args a(env, info); GrandProdDesc G; if (!grand_prod_desc(a, 0, G)) return nullptr;
+    uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
+    if (ew != 1 && ew != 4) { a.fail("elemWords is 1 or 4"); return nullptr; }
+    pil2gl_tuple_side ids[GD_MAX_TERMS], *sides[2 * GD_MAX_TERMS]; uint64_t ks[2 * GD_MAX_TERMS];
+    for (uint64_t u = 0; u < G.nTerms; u++) {
+        pil2gl_grand_prod_term &t = G.term[u];
+        if (t.k < 1 || t.k > 16) { a.fail("k must be 1 .. 16 columns"); return nullptr; }
+        ids[u] = t.side; ids[u].selStride = t.idStride; ids[u].selCol = t.idCol;
+        sides[2 * u] = &t.side; sides[2 * u + 1] = &ids[u]; ks[2 * u] = ks[2 * u + 1] = t.k;
+    }
+    uint64_t *ho = host_matrices(a, sides, ks, 2 * G.nTerms, G.n, G.d[GD_OUT_STRIDE], G.d[GD_OUT_COL] + (ew == 1 ? 2 : 0), ew,
+                                 "expected a matrix, a selector's or null, the matrix again and an id column's or null for every term, then out's matrix");
+    if (!a.ok) return nullptr;
+    for (uint64_t u = 0; u < G.nTerms; u++) G.term[u].id = ids[u].sel;
+    P2(env, (ew == 4 ? pil2gl_bn128_grand_prod : pil2gl_grand_prod)(G.term, G.nTerms, G.d + GD_ALPHA, G.d + GD_BETA, G.d + GD_GAMMA, ho, G.d[GD_OUT_STRIDE], G.d[GD_OUT_COL], G.n));
+    return mk_undefined(env);
+}
+
 // ---- BN128 Merkle commitment (merklehash_bn128_p.js / merklehash_bn128_worker.js) ----
 FN(Bn128Poseidon) {  // (in BigUint64Array(4*nIn*count) normal form, init BigUint64Array(4*count)|null, count, nIn, nOut, out(4*nOut*count))
     Args a(env, info); uint64_t count = a.u64(2), nIn = a.u64(3), nOut = a.u64(4);
@@ -1058,6 +1126,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "lookupMultPlan", LookupMultPlan }, { "lookupMultDev", LookupMultDev }, { "lookupMult", LookupMult }, { "lookupMultProbe", LookupMultProbe },
         { "rangeMultPlan", RangeMultPlan }, { "rangeMultDev", RangeMultDev }, { "rangeMult", RangeMult },
         { "logupSumPlan", LogupSumPlan }, { "logupTermLayout", LogupTermLayout }, { "logupSumDev", LogupSumDev }, { "logupSum", LogupSum },
+        { "grandProdPlan", GrandProdPlan }, { "grandProdTermLayout", GrandProdTermLayout }, { "grandProdDev", GrandProdDev }, { "grandProd", GrandProd },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "gsumColDev", GsumColDev }, { "h1h2Dev", H1H2Dev },

@@ -6,7 +6,8 @@
 //     gprod           z[0] = 1,  z[i] = z[i - 1] num[i - 1] / den[i - 1]
 //     gsum            s[i] = s[i - 1] + num / den[i],  s[0] = num / den[0]          (num: ONE element, on the host)
 //     gsum_col        s[i] = s[i - 1] + num[i] / den[i]                              (num: a column, as gprod's)
-//     logup_sum       the lookup grand sum of include/pil2gl.h: gsum_col over a row's terms folded into one fraction (at the end of this file)
+//     logup_sum       the lookup grand sum of include/pil2gl.h: gsum_col over a row's terms folded into one fraction (near the end of this file)
+//     grand_prod      the grand product of a permutation or a connection: gprod over a row's terms multiplied into N and D (at the end)
 //
 // Elements are 32 bytes of Montgomery words, canonical in and out, moved as two 16-byte halves; element i of a column lies at word
 // 4 i stride, so a column of a row-major section is worked on where it is (as poly_div and g1_msm take theirs).
@@ -40,6 +41,7 @@
 #include "bn_params.h"
 #include "bn_scan_plan.h"
 #include "logup_sum_plan.h"
+#include "grand_prod_plan.h"
 #include "tuple_side.cuh"
 
 using namespace pil2gl;
@@ -472,6 +474,112 @@ int pil2gl_bn128_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, 
     u64 *dOut = (u64 *)s.put(hostOut, outWords);
     P2_TRY(s.rc());
     P2_TRY(bn_logup_launch(terms, (u32)nTerms, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0));
+    return s.get(hostOut, dOut, outWords);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The grand product of a permutation or a connection over Fr (include/pil2gl.h states it):  z[0] = 1, z[i] = z[i-1] R[i-1],
+//   R = prod_{num terms} D_u / prod_{den terms} D_u,  D_u = B_u + idCoef_u id_u + gamma,  B_u = H_u or (H_u - beta) sel_u + beta,
+//   H_u = (..(v_0 alpha + v_1) alpha ..) alpha + v_{k-1}.
+// One compress kernel, a lane a row, multiplies the row's terms into N and D and writes both into the working buffer; then gprod's own
+// operators as they are: inverse_launch(MODE_COLUMN) leaves N / D in the output column, a zero D giving 0, and scan_launch<false> is the
+// exclusive running product in place.  One Fermat ladder a call.  Products a row: a term's k (k - 1 Horner steps and the one into N or
+// D), one more for a selector and for an id column each; then gprod's 7.
+// The packed term table (grand_prod_plan.h) is a kernel argument read with wave-uniform indices.
+namespace {
+
+typedef grandprodplan::Term<4> FrGprodTerm;
+typedef grandprodplan::FrJob FrGprodJob;
+
+__device__ __forceinline__ FrE fr_of(const uint64_t w[4]) {
+    FrE x;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { x.v[2 * i] = (u32)w[i]; x.v[2 * i + 1] = (u32)(w[i] >> 32); }
+    return FrField::reduce(x);
+}
+__device__ __forceinline__ FrE fr_at(const void *m, u64 at) { return FrField::reduce(FrField::load((const FrField::Mem *)m, at)); }
+
+__global__ void __launch_bounds__(smapplan::THREADS) bn_gprod_compress_kernel(const FrGprodJob J, const FrE one, FrField::Mem *__restrict__ D, FrField::Mem *__restrict__ N) {
+    const FrE alpha = fr_of(J.apow[0]), beta = fr_of(J.beta), gamma = fr_of(J.gamma);
+    for (u64 i = (u64)blockIdx.x * smapplan::THREADS + threadIdx.x; i < J.n; i += (u64)gridDim.x * smapplan::THREADS) {
+        FrE num = one, den = one;
+        for (u32 u = 0; u < J.nTerms; u++) {
+            const FrGprodTerm &T = J.t[u];
+            const u64 row = i * T.stride;
+            FrE d = fr_at(T.base, row + J.cols[T.start]);
+            for (u32 j = 1; j < T.k; j++) d = FrField::add(FrField::mul(d, alpha), fr_at(T.base, row + J.cols[T.start + j]));
+            if (T.sel) {
+                bn::fr_sub(d.v, beta.v);
+                d = FrField::add(FrField::mul(d, fr_at(T.sel, i * T.selStride + T.selCol)), beta);
+            }
+            if (T.id) d = FrField::add(d, FrField::mul(fr_of(T.idCoef), fr_at(T.id, i * T.idStride + T.idCol)));
+            d = FrField::add(d, gamma);
+            if (T.den) den = FrField::mul(den, d);
+            else num = FrField::mul(num, d);
+        }
+        FrField::store(D, i, den);
+        FrField::store(N, i, num);
+    }
+}
+
+// every launch of a call, on st; the arguments have passed grandprodplan::check_call() and n > 0, the pointers are the device's
+int bn_gprod_fold_launch(const pil2gl_grand_prod_term *terms, u32 nTerms, const u64 *alpha, const u64 *beta, const u64 *gamma, u64 *out, u64 outStride,
+                         u64 outCol, u64 n, hipStream_t st) {
+    const bnscan::Plan p = bnscan::plan(n, false);
+    u64 *d;
+    P2_TRY(scratch(SCR_BN_SCAN, 4 * p.elems + 8 * n, &d));        // the plan's levels, then D and N
+    FrGprodJob J{};
+    const u64 (*a)[4] = (const u64 (*)[4])alpha;
+    grandprodplan::pack(terms, nTerms, a, beta, gamma, n, J);
+    FrE one;
+    bnp::bn_limbs(bnp::bn_mont_one().w, one.v);
+    FrField::Mem *D = (FrField::Mem *)(d + 4 * p.elems), *N = D + n;
+    bn_gprod_compress_kernel<<<smapplan::blocks(n), smapplan::THREADS, 0, st>>>(J, one, D, N);
+    KERNEL_CHECK();
+    uint4 *base = (uint4 *)d, *y = (uint4 *)(out + 4 * outCol);
+    P2_TRY(inverse_launch(p, base, (const uint4 *)D, 1, y, outStride, y, outStride, MODE_COLUMN, (const uint4 *)N, 1, Elem{}, st));
+    return scan_launch<false>(p, base, y, outStride, st);
+}
+
+int bn_gprod_fold_check(const pil2gl_grand_prod_term *terms, u64 nTerms, const u64 *alpha, const u64 *beta, const u64 *gamma, const u64 *out, u64 outStride,
+                        u64 outCol, u64 n, bool dev) {
+    char why[96];
+    if (const char *msg = grandprodplan::check_call(terms, nTerms, alpha, beta, gamma, out, outStride, outCol, n, 4, dev, why)) return fail(PIL2GL_EINVAL, "%s", msg);
+    return PIL2GL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_bn128_grand_prod_dev(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                                const uint64_t *hostGamma, uint64_t *out, uint64_t outStride, uint64_t outCol, uint64_t n, void *stream) {
+    P2_TRY(bn_gprod_fold_check(hostTerms, nTerms, hostAlpha, hostBeta, hostGamma, out, outStride, outCol, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return bn_gprod_fold_launch(hostTerms, (u32)nTerms, hostAlpha, hostBeta, hostGamma, out, outStride, outCol, n, as_stream(stream));
+}
+
+// host matrices, each staged up to the last element touched; out's matrix goes up as it is and comes back with the column written
+int pil2gl_bn128_grand_prod(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                            const uint64_t *hostGamma, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n) {
+    P2_TRY(bn_gprod_fold_check(hostTerms, nTerms, hostAlpha, hostBeta, hostGamma, hostOut, outStride, outCol, n, false));
+    if (!n) return PIL2GL_OK;
+    pil2gl_grand_prod_term terms[grandprodplan::MAX_TERMS];
+    const u64 outWords = tupleside::span_bytes(n, outStride, outCol, 4) / 8;
+    u64 total = smapplan::pad16(outWords);
+    for (u64 u = 0; u < nTerms; u++) {
+        terms[u] = hostTerms[u];
+        total += tupleside::staged_words(terms[u].side, n, terms[u].k, 4) + smapplan::pad16(grandprodplan::id_words(terms[u], n, 4));
+    }
+    Stage s(total);
+    P2_TRY(s.rc());
+    for (u64 u = 0; u < nTerms; u++) { tupleside::stage_side(s, terms[u].side, n, terms[u].k, 4); grandprodplan::stage_id(s, terms[u], n, 4); }
+    u64 *dOut = (u64 *)s.put(hostOut, outWords);
+    P2_TRY(s.rc());
+    P2_TRY(bn_gprod_fold_launch(terms, (u32)nTerms, hostAlpha, hostBeta, hostGamma, dOut, outStride, outCol, n, 0));
     return s.get(hostOut, dOut, outWords);
 }
 

@@ -6,11 +6,13 @@
 // eight rows) and the running product / sum is a three-kernel scan: per-block inclusive scan + block totals, scan of the
 // totals, then the fix-up (for the product: shifted by one row, z[0] = 1).  Operands may be base (dim 1) or cubic
 // extension (dim 3) columns, row-major; the result is dim 3 if either operand is, else dim 1.  gsum_col is the sum with a column
-// numerator; the lookup grand sum further down folds a lookup's sides into the sum's first pass.
+// numerator; the lookup grand sum further down folds a lookup's sides into the sum's first pass, and the grand product behind it a
+// permutation's or a connection's terms into the product's.
 #include "common.h"
 #include "gl_field.cuh"
 #include "hint_plan.h"
 #include "logup_sum_plan.h"
+#include "grand_prod_plan.h"
 #include <utility>
 
 using namespace gl;
@@ -327,6 +329,163 @@ int pil2gl_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const 
     u64 *dOut = (u64 *)s.put(hostOut, outWords);
     P2_TRY(s.rc());
     P2_TRY(logup_launch(terms, (u32)nTerms, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0));
+    return s.get(hostOut, dOut, outWords);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The grand product of a permutation or a connection (include/pil2gl.h states it; tests/grand_prod_ref.py restates it over integers):
+//   z[0] = 1, z[i] = z[i-1] R[i-1],   R = prod_{num terms} D_u / prod_{den terms} D_u,   D_u = B_u + idCoef_u id_u + gamma,
+//   B_u = H_u or (H_u - beta) sel_u + beta,   H_u = sum_j v_j alpha^(k_u - 1 - j)
+// One fused first pass beside hint_scan1 and logup_scan1, then hint_scan2<true> and hint_scan3<true> as they are (the shift by one row
+// that makes the product exclusive is hint_scan3's).  A lane takes its SCAN_ITEMS rows and keeps each row's N and D as extension elements
+// in registers, N <- N D_u or D <- D D_u; it inverts its rows' D together, one e3_inv a lane, a zero D inverting to zero as in hint_scan1,
+// so that a zero den factor gives R = 0; then the block-local product scan into tmp.  Neither num nor den is ever a column.
+// The powers of alpha come from the host: a tuple column costs three base products, the last column none.  Base products a row, a term
+// of k columns: 3 (k - 1) for H, 3 for a selector, 3 for an id, 6 for the product into N or D; then 18 for the shared inversion and the
+// ratio, 6 for the lane's running product, 6 for the block prefix and 1/8 of the lane's e3_inv.
+// The packed term table (grand_prod_plan.h) travels as a kernel argument and is read with wave-uniform indices.
+// Safety: nothing read from a matrix is used as an address; a row index is checked against n before any load.
+namespace {
+
+typedef grandprodplan::Term<3> GprodTerm;
+typedef grandprodplan::GlJob GprodJob;
+
+__device__ __forceinline__ E3 e3_of(const u64 w[3]) { return E3{ { w[0], w[1], w[2] } }; }
+
+__global__ void __launch_bounds__(SCAN_THREADS) gprod_fold_scan1(const GprodJob J, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
+    __shared__ E3 sh[SCAN_THREADS];
+    const u64 base = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_ITEMS;
+    const E3 beta = e3_of(J.beta), gamma = e3_of(J.gamma);
+    // the lane's rows as N and D; rows at or past n stay 1 / 1.  The terms are the outer loop, so that a term's table entries are read once
+    // for the lane's rows and the rows' loads of one column are in flight together
+    E3 num[SCAN_ITEMS], den[SCAN_ITEMS], loc[SCAN_ITEMS];
+    each_item([&](auto k) { num[k] = ident<true>(); den[k] = ident<true>(); });
+    for (u32 u = 0; u < J.nTerms; u++) {
+        const GprodTerm &T = J.t[u];
+        const u64 stride = T.stride;
+        const u64 *rows = (const u64 *)T.base + base * stride;
+        each_item([&](auto k) { loc[k] = ident<false>(); });
+        for (u32 j = 0; j + 1 < T.k; j++) {
+            const E3 ap = e3_of(J.apow[T.k - 2 - j]);                            // alpha^(k - 1 - j)
+            const u64 *p = rows + J.cols[T.start + j];
+            each_item([&](auto k) { if (base + k < J.n) loc[k] = e3_add(loc[k], e3_scale(ap, p[k * stride])); });
+        }
+        {
+            const u64 *p = rows + J.cols[T.start + T.k - 1];
+            each_item([&](auto k) { if (base + k < J.n) loc[k].v[0] = add(loc[k].v[0], canon(p[k * stride])); });
+        }
+        if (T.sel) {
+            const u64 ss = T.selStride;
+            const u64 *p = (const u64 *)T.sel + base * ss + T.selCol;
+            each_item([&](auto k) { if (base + k < J.n) loc[k] = e3_add(e3_scale(e3_sub(loc[k], beta), p[k * ss]), beta); });
+        }
+        if (T.id) {
+            const E3 c = e3_of(T.idCoef);
+            const u64 is = T.idStride;
+            const u64 *p = (const u64 *)T.id + base * is + T.idCol;
+            each_item([&](auto k) { if (base + k < J.n) loc[k] = e3_add(loc[k], e3_scale(c, p[k * is])); });
+        }
+        if (T.den) each_item([&](auto k) { if (base + k < J.n) den[k] = e3_mul(den[k], e3_add(loc[k], gamma)); });
+        else each_item([&](auto k) { if (base + k < J.n) num[k] = e3_mul(num[k], e3_add(loc[k], gamma)); });
+    }
+    // hint_scan1's inversion: a zero D is kept out of the running product and its row's ratio is 0
+    u32 zero = 0;
+    E3 acc = ident<true>();
+    each_item([&](auto k) {
+        if (!(den[k].v[0] | den[k].v[1] | den[k].v[2])) { zero |= 1u << k; den[k] = ident<true>(); }
+        loc[k] = acc;                                   // the product of the rows' D before this one
+        acc = e3_mul(acc, den[k]);
+    });
+    E3 ai = (acc.v[1] | acc.v[2]) ? e3_inv(acc) : E3{ { inv(acc.v[0]), 0, 0 } };
+    each_item_down([&](auto k) {
+        const E3 di = e3_mul(ai, loc[k]);               // 1 / D_k
+        ai = e3_mul(ai, den[k]);
+        loc[k] = ((zero >> k) & 1) ? ident<false>() : e3_mul(num[k], di);
+    });
+    E3 run = ident<true>();
+    each_item([&](auto k) { run = e3_mul(run, loc[k]); loc[k] = run; });        // rows at or past n hold 1 / 1
+    E3 bt;
+    const E3 ex = block_exclusive<true>(run, sh, &bt);
+    each_item([&](auto k) { const u64 i = base + k; if (i < J.n) st3(tmp, i, e3_mul(ex, loc[k])); });
+    if (threadIdx.x == 0) st3(totals, blockIdx.x, bt);
+}
+
+// every launch of a call, on st; the arguments have passed grandprodplan::check_call() and n > 0, the pointers are the device's
+int gprod_fold_launch(const pil2gl_grand_prod_term *terms, u32 nTerms, const u64 *alpha, const u64 *beta, const u64 *gamma, u64 *out, u64 outStride,
+                      u64 outCol, u64 n, hipStream_t st) {
+    GprodJob J{};
+    const u64 a[3] = { h_canon(alpha[0]), h_canon(alpha[1]), h_canon(alpha[2]) };
+    const u64 b[3] = { h_canon(beta[0]), h_canon(beta[1]), h_canon(beta[2]) }, g[3] = { h_canon(gamma[0]), h_canon(gamma[1]), h_canon(gamma[2]) };
+    u64 pw[tupleside::MAX_K - 1][3], cur[3] = { 1, 0, 0 };
+    for (u32 e = 0; e < tupleside::MAX_K - 1; e++) {
+        h_e3_mul(cur, a, pw[e]);
+        for (int c = 0; c < 3; c++) cur[c] = pw[e][c];
+    }
+    grandprodplan::pack(terms, nTerms, pw, b, g, n, J);
+    const u64 nb = hintplan::blocks(n);
+    u64 *tmp, *totals;
+    P2_TRY(scratch(SCR_HINT_TMP, n * 3, &tmp));
+    P2_TRY(scratch(SCR_HINT_TOTALS, nb * 3, &totals));
+    gprod_fold_scan1<<<(unsigned)nb, SCAN_THREADS, 0, st>>>(J, tmp, totals);
+    KERNEL_CHECK();
+    hint_scan2<true><<<1, SCAN_THREADS, 0, st>>>(totals, nb);
+    KERNEL_CHECK();
+    hint_scan3<true><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tmp, totals, n, 3, out, outStride, outCol);
+    KERNEL_CHECK();
+    return PIL2GL_OK;
+}
+
+int gprod_fold_check(const pil2gl_grand_prod_term *terms, u64 nTerms, const u64 *alpha, const u64 *beta, const u64 *gamma, const u64 *out, u64 outStride,
+                     u64 outCol, u64 n, bool dev) {
+    char why[96];
+    if (const char *msg = grandprodplan::check_call(terms, nTerms, alpha, beta, gamma, out, outStride, outCol, n, 1, dev, why)) return fail(PIL2GL_EINVAL, "%s", msg);
+    return PIL2GL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_grand_prod_plan(uint64_t n, uint64_t nTerms, uint64_t sumK, uint32_t elemWords, uint32_t *outInfo, uint64_t *workBytes) {
+    if (workBytes) *workBytes = 0;
+    if (const char *msg = grandprodplan::check(n, nTerms, sumK, elemWords)) return fail(PIL2GL_EINVAL, "%s", msg);
+    const grandprodplan::Plan p = grandprodplan::plan(n, elemWords);
+    if (outInfo) {
+        outInfo[0] = p.threads; outInfo[1] = p.items; outInfo[2] = p.blocks; outInfo[3] = p.launches; outInfo[4] = p.depth;
+        outInfo[5] = grandprodplan::out_width(elemWords);
+    }
+    if (workBytes) *workBytes = p.bytes;
+    return PIL2GL_OK;
+}
+
+int pil2gl_grand_prod_dev(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                          const uint64_t *hostGamma, uint64_t *out, uint64_t outStride, uint64_t outCol, uint64_t n, void *stream) {
+    P2_TRY(gprod_fold_check(hostTerms, nTerms, hostAlpha, hostBeta, hostGamma, out, outStride, outCol, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return gprod_fold_launch(hostTerms, (u32)nTerms, hostAlpha, hostBeta, hostGamma, out, outStride, outCol, n, as_stream(stream));
+}
+
+// host matrices, each staged up to the last element touched; out's matrix goes up as it is and comes back with the column written
+int pil2gl_grand_prod(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
+                      const uint64_t *hostGamma, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n) {
+    P2_TRY(gprod_fold_check(hostTerms, nTerms, hostAlpha, hostBeta, hostGamma, hostOut, outStride, outCol, n, false));
+    if (!n) return PIL2GL_OK;
+    pil2gl_grand_prod_term terms[grandprodplan::MAX_TERMS];
+    const u64 outWords = tupleside::span_bytes(n, outStride, outCol + 2, 1) / 8;
+    u64 total = smapplan::pad16(outWords);
+    for (u64 u = 0; u < nTerms; u++) {
+        terms[u] = hostTerms[u];
+        total += tupleside::staged_words(terms[u].side, n, terms[u].k, 1) + smapplan::pad16(grandprodplan::id_words(terms[u], n, 1));
+    }
+    Stage s(total);
+    P2_TRY(s.rc());
+    for (u64 u = 0; u < nTerms; u++) { tupleside::stage_side(s, terms[u].side, n, terms[u].k, 1); grandprodplan::stage_id(s, terms[u], n, 1); }
+    u64 *dOut = (u64 *)s.put(hostOut, outWords);
+    P2_TRY(s.rc());
+    P2_TRY(gprod_fold_launch(terms, (u32)nTerms, hostAlpha, hostBeta, hostGamma, dOut, outStride, outCol, n, 0));
     return s.get(hostOut, dOut, outWords);
 }
 

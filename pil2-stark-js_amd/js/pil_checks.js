@@ -33,6 +33,9 @@
 //       Uint8Array(32) with opts.bn128.  out: { buf, stride, col }: over Goldilocks the words col .. col + 2 of a row of `stride` words,
 //       over Fr one element.  Written in place for every row; s[n-1] is the hint's result.  logupSumDev only enqueues (opts.stream).
 //   logupSumPlan(n, nTerms, bn128)   the library's plan
+//   grandProduct(terms, alpha, beta, gamma, out, n, opts) / grandProductDev(..) / grandProductPlan(n, nTerms, sumK, bn128)
+//       the column z of a permutation or a connection from the trace columns (include/pil2gl.h states it); permutationTerms and
+//       connectionTerms build the term lists of the reference's two identities
 // Node 12: no optional chaining.
 "use strict";
 const { addon, DevBuffer, isDev } = require("./native.js");
@@ -228,4 +231,47 @@ const logupSum = (terms, alpha, beta, out, n, opts) => logup(false, terms, alpha
 const logupSumDev = (terms, alpha, beta, out, n, opts) => logup(true, terms, alpha, beta, out, n, opts);
 const logupSumPlan = (n, nTerms, bn128) => addon.logupSumPlan(n, nTerms, bn128 ? 4 : 1);
 
-module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, logupSum, logupSumDev, logupSumPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };
+// ---- grand product of a permutation or a connection ----
+// A term is a side { buf, stride, cols, sel } with den: 0 | 1 and optionally id: { buf, stride, col } and idCoef (3 words over Goldilocks,
+// 4 Montgomery words over Fr); alpha, beta, gamma are 3 or 4 words each; out is logupSum's.  z[n-1] is the hint's result.
+function grandProd(dev, termsIn, alpha, beta, gamma, outIn, n, opts) {
+    const bn = !!(opts && opts.bn128), ew = bn ? 4 : 1, width = bn ? 1 : 3, cw = bn ? 4 : 3;
+    if (!Array.isArray(termsIn) || termsIn.length < 1 || termsIn.length > 40) throw new Error("terms must be an array of 1 .. 40 terms");
+    if (!outIn || !(outIn.stride > 0) || !(outIn.col >= 0)) throw new Error("out must be { buf, stride, col }");
+    const elem = (v, what) => {
+        const w = Array.from(stage.asWords(v));
+        if (w.length !== cw) throw new Error(what + " must hold " + cw + " words");
+        return w.concat([0n]).slice(0, 4);
+    };
+    const terms = termsIn.map((t, u) => {
+        const s = side(t, "term " + u, n, ew, dev);
+        if (s.cols.length < 1 || s.cols.length > 16) throw new Error("term " + u + ": 1 .. 16 columns");
+        s.den = t.den ? 1 : 0;
+        s.id = t.id ? side({ buf: t.id.buf, stride: t.id.stride, cols: [t.id.col] }, "the id of term " + u, n, ew, dev) : null;
+        s.idCoef = t.id ? elem(t.idCoef, "idCoef of term " + u) : [0n, 0n, 0n, 0n];
+        return s;
+    });
+    const out = side({ buf: outIn.buf, stride: outIn.stride, cols: [outIn.col, outIn.col + width - 1] }, "out", n, ew, dev);
+    const ptr = (b) => dev && b ? b.ptr : 0n;
+    const head = [n, terms.length, ptr(out.buf), out.stride, outIn.col].concat(elem(alpha, "alpha"), elem(beta, "beta"), elem(gamma, "gamma"));
+    const fourteen = terms.map((x) => [ptr(x.buf), x.stride, x.cols.length].concat(x.sel ? [ptr(x.sel.buf), x.sel.stride, x.sel.col] : [0n, 0, 0], [x.den],
+        x.id ? [ptr(x.id.buf), x.id.stride, x.id.cols[0]] : [0n, 0, 0], x.idCoef));
+    const slots = terms.map((x) => x.cols.concat(new Array(16 - x.cols.length).fill(0)));
+    const desc = BigUint64Array.from(head.concat(...fourteen, ...slots).map((v) => BigInt(v)));
+    if (dev) { addon.grandProdDev(desc, ew, opts && opts.stream); return outIn; }
+    const four = [].concat(...terms.map((x) => [x.buf, x.sel ? x.sel.buf : null, x.buf, x.id ? x.id.buf : null]));
+    addon.grandProd(desc, four.concat([out.buf]), ew);
+    copyBack(out.buf, outIn.buf);
+    return outIn;
+}
+const grandProduct = (terms, alpha, beta, gamma, out, n, opts) => grandProd(false, terms, alpha, beta, gamma, out, n, opts);
+const grandProductDev = (terms, alpha, beta, gamma, out, n, opts) => grandProd(true, terms, alpha, beta, gamma, out, n, opts);
+const grandProductPlan = (n, nTerms, sumK, bn128) => addon.grandProdPlan(n, nTerms, sumK, bn128 ? 4 : 1);
+// the term lists of the reference's two identities (grandProductPermutation.js, grandProductConnection.js); deltaKs[j] = delta ks'_j, made
+// by the caller with its field (ks' = 1, ks[0], ks[1], ..)
+const permutationTerms = (f, t) => [Object.assign({}, f, { den: 0 }), Object.assign({}, t, { den: 1 })];
+const connectionTerms = (aCols, sCols, x, delta, deltaKs) => [].concat(...aCols.map((a, j) => [
+    { buf: a.buf, stride: a.stride, cols: [a.col], den: 0, id: x, idCoef: deltaKs[j] },
+    { buf: a.buf, stride: a.stride, cols: [a.col], den: 1, id: sCols[j], idCoef: delta }]));
+
+module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, logupSum, logupSumDev, logupSumPlan, grandProduct, grandProductDev, grandProductPlan, permutationTerms, connectionTerms, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };

@@ -98,3 +98,22 @@ module.exports.calculateH1H2 = function calculateH1H2(F, f, t) {
     const [h1, h2] = onDevice([pf.a, pt.a], [n * pt.dim, n * pt.dim], ([df, dt], [d1, d2]) => addon.h1h2Dev(df, dt, n, pt.dim, d1, d2));
     return [unpack(h1, pt.dim), unpack(h2, pt.dim)];
 };
+
+
+// The grand product of a permutation or a connection from the trace columns in one call (js/pil_checks.js grandProduct; include/pil2gl.h
+// states it): what calculateZ gives on the two product columns of grandProductPermutation.js / grandProductConnection.js, without them.
+// f, t = { buf, stride, cols, sel }; aCols, sCols = arrays of { buf, stride, col }, x = { buf, stride, col }; deltaKs[j] = delta ks'_j;
+// out = { buf, stride, col }.  The Dev forms take DevBuffers and only enqueue; the others take host words and write out in place.
+function zPermutation(dev, f, t, alpha, beta, gamma, out, n, stream) {
+    const pc = require("./pil_checks.js");
+    return (dev ? pc.grandProductDev : pc.grandProduct)(pc.permutationTerms(f, t), alpha, beta, gamma, out, n, { bn128: false, stream });
+}
+function zConnection(dev, aCols, sCols, x, gamma, delta, deltaKs, out, n, stream) {
+    const pc = require("./pil_checks.js");
+    return (dev ? pc.grandProductDev : pc.grandProduct)(pc.connectionTerms(aCols, sCols, x, delta, deltaKs), gamma, gamma, gamma, out, n, { bn128: false, stream });
+}
+const calculateZPermutation = (f, t, alpha, beta, gamma, out, n) => zPermutation(false, f, t, alpha, beta, gamma, out, n);
+const calculateZPermutationDev = (f, t, alpha, beta, gamma, out, n, stream) => zPermutation(true, f, t, alpha, beta, gamma, out, n, stream);
+const calculateZConnection = (aCols, sCols, x, gamma, delta, deltaKs, out, n) => zConnection(false, aCols, sCols, x, gamma, delta, deltaKs, out, n);
+const calculateZConnectionDev = (aCols, sCols, x, gamma, delta, deltaKs, out, n, stream) => zConnection(true, aCols, sCols, x, gamma, delta, deltaKs, out, n, stream);
+Object.assign(module.exports, { calculateZPermutation, calculateZPermutationDev, calculateZConnection, calculateZConnectionDev });

@@ -126,4 +126,22 @@ function lastElement(col, n) {
     return new Uint8Array(col.buf.slice(off, off + 4).buffer);
 }
 
-module.exports = { calculateZ, calculateS, calculateSCol, batchInverse, calculateH1H2, calculateZDev, calculateSDev, calculateSColDev, batchInverseDev, calculateH1H2Dev, lastElement };
+
+// The grand product of a permutation or a connection from the trace columns in one call (js/pil_checks.js grandProduct; include/pil2gl.h
+// states it): what calculateZ gives on the two product columns of grandProductPermutation.js / grandProductConnection.js, without them.
+// f, t = { buf, stride, cols, sel }; aCols, sCols = arrays of { buf, stride, col }, x = { buf, stride, col }; deltaKs[j] = delta ks'_j;
+// out = { buf, stride, col }.  The Dev forms take DevBuffers and only enqueue; the others take host words and write out in place.
+function zPermutation(dev, f, t, alpha, beta, gamma, out, n, stream) {
+    const pc = require("./pil_checks.js");
+    return (dev ? pc.grandProductDev : pc.grandProduct)(pc.permutationTerms(f, t), alpha, beta, gamma, out, n, { bn128: true, stream });
+}
+function zConnection(dev, aCols, sCols, x, gamma, delta, deltaKs, out, n, stream) {
+    const pc = require("./pil_checks.js");
+    return (dev ? pc.grandProductDev : pc.grandProduct)(pc.connectionTerms(aCols, sCols, x, delta, deltaKs), gamma, gamma, gamma, out, n, { bn128: true, stream });
+}
+const calculateZPermutation = (f, t, alpha, beta, gamma, out, n) => zPermutation(false, f, t, alpha, beta, gamma, out, n);
+const calculateZPermutationDev = (f, t, alpha, beta, gamma, out, n, stream) => zPermutation(true, f, t, alpha, beta, gamma, out, n, stream);
+const calculateZConnection = (aCols, sCols, x, gamma, delta, deltaKs, out, n) => zConnection(false, aCols, sCols, x, gamma, delta, deltaKs, out, n);
+const calculateZConnectionDev = (aCols, sCols, x, gamma, delta, deltaKs, out, n, stream) => zConnection(true, aCols, sCols, x, gamma, delta, deltaKs, out, n, stream);
+
+module.exports = { calculateZPermutation, calculateZPermutationDev, calculateZConnection, calculateZConnectionDev, calculateZ, calculateS, calculateSCol, batchInverse, calculateH1H2, calculateZDev, calculateSDev, calculateSColDev, batchInverseDev, calculateH1H2Dev, lastElement };

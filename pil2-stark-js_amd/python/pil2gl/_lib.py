@@ -62,6 +62,13 @@ class LogupTerm(C.Structure):
     _fields_ = [("side", TupleSide), ("k", C.c_uint64), ("coef", C.c_uint64 * 4), ("busId", C.c_uint64 * 4)]
 
 
+class GrandProdTerm(C.Structure):
+    """include/pil2gl.h pil2gl_grand_prod_term: one term of a grand product (its side, its k, numerator or denominator, the id column and
+    its host coefficient)"""
+    _fields_ = [("side", TupleSide), ("k", C.c_uint64), ("den", C.c_uint64), ("id", C.c_void_p), ("idStride", C.c_uint64), ("idCol", C.c_uint64),
+                ("idCoef", C.c_uint64 * 4)]
+
+
 class G1Poly(C.Structure):
     """include/pil2gl.h pil2gl_g1_poly: one packed polynomial of a G1 commit batch"""
     _fields_ = [("first", C.c_uint64), ("rows", C.c_uint64), ("m", C.c_uint32), ("reserved", C.c_uint32)]
@@ -270,6 +277,11 @@ SIGNATURES = {
     "pil2gl_bn128_logup_sum_dev": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),
     "pil2gl_logup_sum": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64]),
     "pil2gl_bn128_logup_sum": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64]),
+    "pil2gl_grand_prod_plan": (_I, [_U64, _U64, _U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_grand_prod_dev": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_bn128_grand_prod_dev": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_grand_prod": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64]),
+    "pil2gl_bn128_grand_prod": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64]),
     "pil2gl_selftest_field":(_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_ext": (_I, [vp, vp, _U64, vp, vp]),
     "pil2gl_selftest_products": (_I, [vp, vp, _U64, vp, vp, vp]),

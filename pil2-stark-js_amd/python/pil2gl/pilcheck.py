@@ -13,7 +13,8 @@ returns the library's five words (kind, row, partner, cntF, cntT) -- include/pil
 
 The column that PROVES a lookup in pil2, the multiplicities of its grand sum (csrc/lookup_mult.hip), is lookup_mult / lookup_mult_dev at the
 end of this module, then its form for a range check, which needs no table column (range_mult / range_mult_dev, csrc/range_mult.hip), and
-after them the grand sum that consumes the column (logup_sum / logup_sum_dev).
+after them the grand sum that consumes the column (logup_sum / logup_sum_dev) and the grand product of a permutation or a connection
+(grand_prod / grand_prod_dev, with perm_prod and conn_prod as spellings of the two identities).
 """
 import ctypes as C
 
@@ -296,3 +297,106 @@ def logup_sum(terms, alpha, beta, out, n, field="gl"):
 def logup_sum_dev(terms, alpha, beta, out, n, field="gl"):
     """logup_sum on device tensors, e.g. columns of the stage-1 buffer with m one of them; only enqueues on the current stream"""
     return _logup(True, terms, alpha, beta, out, n, field)
+
+
+# ---- grand product: the column z of a permutation or a connection (csrc/grand_prod_plan.h; include/pil2gl.h states it) ----
+#     perm_prod_dev((cm1, [7, 3], (cm1, 9)), (cm1, [4, 5], (cm1, 10)), alpha, beta, gamma, (cm2, 0), n)
+#     conn_prod_dev([(cm1, 0), (cm1, 1)], [(const, 4), (const, 5)], (x, 0), ks, gamma, delta, (cm2, 0), n)
+# A term is (matrix, cols, selector-or-None, den, id-or-None, id_coef) or that with the matrix's stride as a seventh part; den is 0 for a
+# factor of the numerator and 1 for one of the denominator; id is a column as a selector is, (matrix, col) or (matrix, col, stride), and
+# id_coef its coefficient: 3 canonical words over Goldilocks, 4 Montgomery words over Fr (None with no id).  alpha, beta, gamma are 3
+# words of a cubic-extension element, or 4 Montgomery words.  out is logup_sum's.  Written in place; z[n-1] is the hint's result.
+def grand_prod_plan(n, n_terms=1, sum_k=None, field="gl"):
+    """pil2gl_grand_prod_plan (host-only): the launch geometry, the launches and the working bytes"""
+    names = ("threads", "items", "blocks", "launches", "depth", "outWidth")
+    return _plan("pil2gl_grand_prod_plan", (n, n_terms, n_terms if sum_k is None else sum_k, _WORDS[field]), names, "workBytes")
+
+
+def _grand_prod(dev, terms, alpha, beta, gamma, out, n, field):
+    from ._lib import GrandProdTerm
+    words = _WORDS[field]
+    cw = 3 if words == 1 else 4
+    T = (GrandProdTerm * max(len(terms), 1))()
+    keep = []
+    for u, spec in enumerate(terms):
+        spec = tuple(spec) + (None,) * (7 - len(spec))
+        side, (T[u].k,), kept = _sides([(spec[0], spec[1], spec[2], spec[6])], ["term %d" % u], 3, n, words, dev)
+        T[u].side = side[0]
+        T[u].den = int(spec[3] or 0)
+        keep.append(kept)
+        if spec[4] is not None:
+            idc = tuple(spec[4]) + (None,)
+            idm, id_stride = _side(idc[0], [idc[1]], idc[2], None, n, words, dev, "the id of term %d" % u)[:2]
+            keep.append(idm)
+            T[u].id, T[u].idStride, T[u].idCol = _dev_ptr(dev)(idm), id_stride, idc[1]
+            w = np.ascontiguousarray(spec[5], np.uint64).reshape(-1)
+            if w.size != cw:
+                raise Pil2glError("term %d: idCoef is %d words" % (u, cw))
+            for i in range(cw):
+                T[u].idCoef[i] = int(w[i])
+    ch = [np.ascontiguousarray(c, np.uint64).reshape(-1) for c in (alpha, beta, gamma)]
+    if any(c.size != cw for c in ch):
+        raise Pil2glError("alpha, beta and gamma are %d words each" % cw)
+    om, col = _column(out, "out", 3 if words == 1 else 1, n, words, dev)
+    name = "pil2gl_grand_prod" if words == 1 else "pil2gl_bn128_grand_prod"
+    args = [T, len(terms)] + [C.c_void_p(c.ctypes.data) for c in ch] + col + [n]
+    if dev:
+        call(name + "_dev", *args, _stream())
+    else:
+        call(name, *args)
+    return out[0]
+
+
+def grand_prod(terms, alpha, beta, gamma, out, n, field="gl"):
+    """the grand-product column of a permutation or a connection: host matrices; out's column is written in place -> out's matrix"""
+    return _grand_prod(False, terms, alpha, beta, gamma, out, n, field)
+
+
+def grand_prod_dev(terms, alpha, beta, gamma, out, n, field="gl"):
+    """grand_prod on device tensors, e.g. columns of the stage-1 buffer and of the constants; only enqueues on the current stream"""
+    return _grand_prod(True, terms, alpha, beta, gamma, out, n, field)
+
+
+def perm_terms(f, t):
+    """the two terms of `selF {f} is selT {t}` (grandProductPermutation.js): f, t = (matrix, cols[, sel[, stride]])"""
+    f, t = (tuple(s) + (None, None) for s in (f, t))
+    return [(f[0], f[1], f[2], 0, None, None, f[3]), (t[0], t[1], t[2], 1, None, None, t[3])]
+
+
+def conn_terms(a_cols, S_cols, x, ks, delta, field="gl"):
+    """the 2 len(a_cols) terms of `{a} connect {S}` (grandProductConnection.js): a_cols, S_cols = lists of (matrix, col[, stride]), x = the
+    column of the domain's points, ks = the cosets' shifts k_1 .. (column 0 takes 1), delta = the challenge's words.  Builds lists only: the
+    one product here is delta ks'_j, by the library's scalar multiply over Goldilocks and on the Montgomery words as integers over Fr"""
+    if len(S_cols) != len(a_cols) or len(ks) < len(a_cols) - 1:
+        raise Pil2glError("a connection of %d columns takes as many S columns and %d shifts" % (len(a_cols), len(a_cols) - 1))
+    delta = [int(v) for v in np.ascontiguousarray(delta, np.uint64).reshape(-1)]
+    terms = []
+    for j, (a, S) in enumerate(zip(a_cols, S_cols)):
+        k = 1 if j == 0 else int(ks[j - 1])
+        if _WORDS[field] == 1:
+            coef = [int(load().pil2gl_mul(d, k)) for d in delta]
+        else:
+            from .bn128 import _ints, _words
+            coef = _words([_ints(delta)[0] * k])[0]
+        a = tuple(a) + (None,)
+        terms.append((a[0], [a[1]], None, 0, x, coef, a[2]))
+        terms.append((a[0], [a[1]], None, 1, S, delta, a[2]))
+    return terms
+
+
+def perm_prod(f, t, alpha, beta, gamma, out, n, field="gl"):
+    """z of one permutation, host matrices: grand_prod over perm_terms(f, t)"""
+    return grand_prod(perm_terms(f, t), alpha, beta, gamma, out, n, field)
+
+
+def perm_prod_dev(f, t, alpha, beta, gamma, out, n, field="gl"):
+    return grand_prod_dev(perm_terms(f, t), alpha, beta, gamma, out, n, field)
+
+
+def conn_prod(a_cols, S_cols, x, ks, gamma, delta, out, n, field="gl"):
+    """z of one connection, host matrices: grand_prod over conn_terms(..); alpha and beta are unused by its terms and passed as gamma"""
+    return grand_prod(conn_terms(a_cols, S_cols, x, ks, delta, field), gamma, gamma, gamma, out, n, field)
+
+
+def conn_prod_dev(a_cols, S_cols, x, ks, gamma, delta, out, n, field="gl"):
+    return grand_prod_dev(conn_terms(a_cols, S_cols, x, ks, delta, field), gamma, gamma, gamma, out, n, field)
