@@ -24,7 +24,7 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; grand_prod and bn128_grand_prod; land_rows with a null hostFirstBad;
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; grand_prod and bn128_grand_prod; plookup_fold, plookup_prod and their bn128_ twins; land_rows with a null hostFirstBad;
  *      wtns_adds and bn128_wtns_adds, wtns_gather and bn128_wtns_gather with a null hostFirstBad, conn_pols and bn128_conn_pols with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, logup_sum_plan, grand_prod_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, logup_sum_plan, grand_prod_plan, plookup_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -1182,6 +1182,86 @@ int pil2gl_grand_prod(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, 
                       const uint64_t *hostGamma, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
 int pil2gl_bn128_grand_prod(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
                             const uint64_t *hostGamma, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
+
+/* ---- plookup: pil1's lookup argument from the trace columns, h1 and h2 (csrc/plookup_plan.h, hints.hip, bn_scan.hip) ----
+ * The third pil1 argument library, grandProductPlookup.js, beside the two of the block above: its stage-1 half (the two kept expressions
+ * that the h1h2 hint merges) and its stage-2 half (the gprod hint's z) without the extension columns num and den.  The statement is this
+ * header's own (tests/plookup_ref.py restates it over Python integers); alpha, beta = std_alpha, std_beta (grandProductPlookup.js:10-11),
+ * gamma, delta = std_gamma, std_delta (:12-13):
+ *   H_t[i] = (..(t_0 alpha + t_1) alpha ..) alpha + t_{kT-1}                          :42-50  (first column highest)
+ *   T[i]   = H_t[i]                               without selT
+ *          = (H_t[i] - beta) selT[i] + beta       with selT: its FIELD VALUE          :51-55
+ *   H_f[i] likewise over the kF columns of f                                           :64-72
+ *   F[i]   = H_f[i]                               without selF
+ *          = (H_f[i] - T[i]) selF[i] + T[i]       with selF: blended towards T of the SAME row, not towards beta    :73-77
+ *   g      = gamma (1 + delta)
+ *   num[i] = (F[i] + gamma) (T[i] + delta T[i+1] + g) (1 + delta)                      :120-135
+ *   den[i] = (h1[i] + delta h2[i] + g) (h2[i] + delta h1[i+1] + g)                     :143-164
+ *   i+1 is taken mod n: row n - 1's neighbour is row 0
+ *   z[0] = 1,  z[i] = z[i-1] num[i-1] / den[i-1]                                      (calculateZ, polutils.js:132-145)
+ *   n <= 2^28 rows.  f and t are pil2gl_tuple_sides of kF and kT columns, each 1 .. 16 and not tied to each other.  Elements count as
+ *   field values by the rules above (Goldilocks words in [p, 2^64) mod p, any Fr pattern mod r).  The challenges are HOST pointers: three
+ *   words each over Goldilocks (x^3 = x + 1), canonical or not -- the entry canonicalises them -- or four Montgomery words over Fr.
+ *   h1, h2: columns (ptr, stride, col) of hDim words an element, over Goldilocks hDim = 1 (a base column, word col of a row of `stride`
+ *   words) or 3 (words col .. col + 2), over Fr hDim = 1: one element.  The reference makes h a base column exactly when kF = kT = 1 and
+ *   there is no selT (:91, hDim = max(fDim, tDim)); the product takes hDim as given and does not enforce that.
+ *   Zeros: gprod's convention.  If either factor of den[i] is zero, the ratio of row i is 0 and every later z is 0; a zero num is plain
+ *   arithmetic.  No read goes past row n - 1 of any matrix.  num[n-1] / den[n-1] does not enter z (for a valid lookup it closes the
+ *   product: z[n-1] num[n-1] / den[n-1] = 1).  The hint's `result` is z[n-1]: the caller copies it.
+ *   Equivalence: z is word for word what pil2gl_gprod_dev(num, 3, den, 3, ..) / pil2gl_bn128_gprod_dev give on the two materialised columns.
+ *   Out of scope: more than one plookup per z, and pil2gl/stark.py's resolve_hints_info, which sees tmp fields and stays as it is.
+ * pil2gl_plookup_plan: host-only, no device.  outInfo is logup_sum_plan's, for the PRODUCT call: [0] threads per workgroup of the first
+ * pass; [1] rows a lane of it takes (8, Fr 1); [2] its workgroups; [3] kernel launches (Goldilocks 3: the fused first pass, the block
+ * totals' scan, the fix-up; Fr 4 levels - 1: the compress, then bn128_gprod's inversion and scan); [4] Goldilocks: block totals a lane of
+ * the second pass walks, Fr: levels; [5] u64 words of an output element's columns (3, or 1 element).  *workBytes = the product's working
+ * memory, from the library's own slots: Goldilocks gsum's 24 n + 24 ceil(n / 2048); Fr the scan plan's bytes + 64 n.  The fold is one
+ * launch and takes no working memory.  PIL2GL_EINVAL: n > 2^28, kF or kT outside 1 .. 16, elemWords not 1 or 4.
+ * pil2gl_[bn128_]plookup_fold[_dev], the stage-1 half: writes F into column colF of (outF, strideF) and T into column colT of (outT,
+ * strideT), hDim words an element, canonical (Fr: one canonical Montgomery element).  Over Goldilocks hDim = 1 is PIL2GL_EINVAL unless
+ * kF = kT = 1 and selT is NULL (alpha and beta are then unused but must be non-null); with hDim = 3 and dense outputs (stride 3, col 0)
+ * they are what pil2gl_h1h2_dev takes; over Fr they are strided columns for pil2gl_bn128_h1h2_dev.  One kernel, a lane a row; the _dev
+ * form only ENQUEUES.
+ * pil2gl_[bn128_]plookup_prod[_dev], the stage-2 half: z into (out, outStride, outCol) as logup_sum writes s -- Goldilocks the three
+ * canonical words outCol .. outCol + 2, Fr one canonical Montgomery element; words between a strided destination's elements stay as they
+ * are.  The _dev form only ENQUEUES on the caller's stream: the job travels as a kernel argument, nothing is copied and the host does not
+ * wait.  (On first use the working slots are allocated, with a device synchronise when they grow.)
+ * Buffers: _dev pointers (side.base, side.sel, h1, h2, the outputs) are device pointers, 16-byte aligned; everything but the outputs is
+ * only read and may overlap freely.  An output obeys logup_sum's aliasing rule with the selector and the h matrices counted as read
+ * matrices: z as spare columns of t's matrix is the normal case; outF and outT may be distinct columns of one matrix.  PIL2GL_EINVAL,
+ * before any device call: what the plan refuses, an hDim that is not allowed, a column >= its stride (col + 2 for three-word elements), a
+ * stride >= 2^32 or n stride > 2^58 elements, a null side, cols, base, column, output or challenge, a misaligned device pointer, an
+ * output that breaks the aliasing rule.  n = 0 is PIL2GL_OK, touches nothing and needs no device.
+ * The forms without _dev take host pointers throughout; each matrix is staged up to the last element touched, every part on 16 bytes, an
+ * output's matrix goes up as it is and comes back with the column written.  Without a device the compute calls return PIL2GL_ENODEV. */
+int pil2gl_plookup_plan(uint64_t n, uint64_t kF, uint64_t kT, uint32_t elemWords, uint32_t *outInfo /* [6] */, uint64_t *workBytes);
+int pil2gl_plookup_fold_dev(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostAlpha /* [3] */,
+                            const uint64_t *hostBeta /* [3] */, uint32_t hDim, uint64_t *outF, uint64_t strideF, uint64_t colF, uint64_t *outT, uint64_t strideT,
+                            uint64_t colT, uint64_t n, void *stream);
+int pil2gl_bn128_plookup_fold_dev(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostAlpha /* [4] */,
+                                  const uint64_t *hostBeta /* [4] */, uint32_t hDim, uint64_t *outF, uint64_t strideF, uint64_t colF, uint64_t *outT, uint64_t strideT,
+                                  uint64_t colT, uint64_t n, void *stream);
+int pil2gl_plookup_fold(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostAlpha,
+                        const uint64_t *hostBeta, uint32_t hDim, uint64_t *hostOutF, uint64_t strideF, uint64_t colF, uint64_t *hostOutT, uint64_t strideT,
+                        uint64_t colT, uint64_t n);
+int pil2gl_bn128_plookup_fold(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostAlpha,
+                              const uint64_t *hostBeta, uint32_t hDim, uint64_t *hostOutF, uint64_t strideF, uint64_t colF, uint64_t *hostOutT, uint64_t strideT,
+                              uint64_t colT, uint64_t n);
+int pil2gl_plookup_prod_dev(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *h1, uint64_t h1Stride,
+                            uint64_t h1Col, const uint64_t *h2, uint64_t h2Stride, uint64_t h2Col, uint32_t hDim, const uint64_t *hostAlpha /* [3] */,
+                            const uint64_t *hostBeta /* [3] */, const uint64_t *hostGamma /* [3] */, const uint64_t *hostDelta /* [3] */, uint64_t *out,
+                            uint64_t outStride, uint64_t outCol, uint64_t n, void *stream);
+int pil2gl_bn128_plookup_prod_dev(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *h1, uint64_t h1Stride,
+                                  uint64_t h1Col, const uint64_t *h2, uint64_t h2Stride, uint64_t h2Col, uint32_t hDim, const uint64_t *hostAlpha /* [4] */,
+                                  const uint64_t *hostBeta /* [4] */, const uint64_t *hostGamma /* [4] */, const uint64_t *hostDelta /* [4] */, uint64_t *out,
+                                  uint64_t outStride, uint64_t outCol, uint64_t n, void *stream);
+int pil2gl_plookup_prod(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostH1, uint64_t h1Stride,
+                        uint64_t h1Col, const uint64_t *hostH2, uint64_t h2Stride, uint64_t h2Col, uint32_t hDim, const uint64_t *hostAlpha,
+                        const uint64_t *hostBeta, const uint64_t *hostGamma, const uint64_t *hostDelta, uint64_t *hostOut, uint64_t outStride, uint64_t outCol,
+                        uint64_t n);
+int pil2gl_bn128_plookup_prod(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostH1, uint64_t h1Stride,
+                              uint64_t h1Col, const uint64_t *hostH2, uint64_t h2Stride, uint64_t h2Col, uint32_t hDim, const uint64_t *hostAlpha,
+                              const uint64_t *hostBeta, const uint64_t *hostGamma, const uint64_t *hostDelta, uint64_t *hostOut, uint64_t outStride,
+                              uint64_t outCol, uint64_t n);
 
 /* ---- synthetic workload for bench.py / tests (not a reference operator) ----
  * witness of nPairs independent Fibonacci machines (test/state_machines/sm_fibonacci/sm_fibonacci.js:12-23):

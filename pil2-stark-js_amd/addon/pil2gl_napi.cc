@@ -935,6 +935,90 @@ FN(GrandProd) {
     return mk_undefined(env);
 }
 
+// ---- plookup: the fold of F and T and the column z from f, t, h1 and h2 (csrc/plookup_plan.h; js/pil_checks.js) ----
+FN(PlookupPlan) {          // (n, kF, kT, elemWords) -> { threads, items, blocks, launches, depth, outWidth, workBytes }
+    Args a(env, info); uint64_t n = a.u64(0), kF = a.u64(1), kT = a.u64(2); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
+    uint32_t out[6]; uint64_t bytes = 0;
+    P2(env, pil2gl_plookup_plan(n, kF, kT, ew, out, &bytes));
+    static const char *const names[6] = { "threads", "items", "blocks", "launches", "depth", "outWidth" };
+    return plan_object(env, names, out, "workBytes", bytes);
+}
+// A call's description, one BigUint64Array: [0] n, [1] kF, [2] kT, [3] hDim, [4..7] alpha, [8..11] beta, [12..15] gamma, [16..19] delta (three
+// words used over Goldilocks; the fold reads no gamma and delta), then f and t as five words each -- base, stride, sel (0: none), selStride,
+// selCol -- then three columns of three words each -- base, stride, col: the product's h1, h2 and out, the fold's outF and outT (the third
+// unused) -- then 16 column slots for f and 16 for t, the first k used.  The pointer words are device addresses for the Dev entries and are
+// not read by the others, which take the host matrices as an array of their own.
+enum { PD_N, PD_KF, PD_KT, PD_HDIM, PD_ALPHA, PD_BETA = PD_ALPHA + 4, PD_GAMMA = PD_BETA + 4, PD_DELTA = PD_GAMMA + 4, PD_F = PD_DELTA + 4, PD_T = PD_F + 5,
+       PD_COLS = PD_T + 5, PD_F_SLOTS = PD_COLS + 9, PD_T_SLOTS = PD_F_SLOTS + 16, PD_WORDS = PD_T_SLOTS + 16 };
+struct PlookupDesc { uint64_t *d; uint64_t n, kF, kT; uint32_t hDim; pil2gl_tuple_side f, t; };
+static bool plookup_desc(Args &a, size_t i, PlookupDesc &L) {
+    L.d = a.arr(i, PD_WORDS);
+    if (!a.ok) return false;
+    L.n = L.d[PD_N]; L.kF = L.d[PD_KF]; L.kT = L.d[PD_KT]; L.hDim = (uint32_t)L.d[PD_HDIM];
+    const uint64_t *f = L.d + PD_F, *t = L.d + PD_T;
+    L.f = pil2gl_tuple_side{ (const uint64_t *)(uintptr_t)f[0], f[1], L.d + PD_F_SLOTS, (const uint64_t *)(uintptr_t)f[2], f[3], f[4] };
+    L.t = pil2gl_tuple_side{ (const uint64_t *)(uintptr_t)t[0], t[1], L.d + PD_T_SLOTS, (const uint64_t *)(uintptr_t)t[2], t[3], t[4] };
+    return true;
+}
+#define PD_PTR(L, c) ((uint64_t *)(uintptr_t)(L).d[PD_COLS + 3 * (c)])
+#define PD_STRIDE(L, c) ((L).d[PD_COLS + 3 * (c) + 1])
+#define PD_COL(L, c) ((L).d[PD_COLS + 3 * (c) + 2])
+FN(PlookupFoldDev) {       // (description, elemWords[, stream]): only enqueues
+    Args a(env, info); PlookupDesc L; if (!plookup_desc(a, 0, L)) return nullptr;
+    uint32_t ew = (uint32_t)a.u64(1); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_plookup_fold_dev : pil2gl_plookup_fold_dev)(&L.f, L.kF, &L.t, L.kT, L.d + PD_ALPHA, L.d + PD_BETA, L.hDim, PD_PTR(L, 0), PD_STRIDE(L, 0),
+                                                                                PD_COL(L, 0), PD_PTR(L, 1), PD_STRIDE(L, 1), PD_COL(L, 1), L.n, a.stream(2)));
+    return mk_undefined(env);
+}
+FN(PlookupProdDev) {       // (description, elemWords[, stream]): only enqueues
+    Args a(env, info); PlookupDesc L; if (!plookup_desc(a, 0, L)) return nullptr;
+    uint32_t ew = (uint32_t)a.u64(1); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_plookup_prod_dev : pil2gl_plookup_prod_dev)(&L.f, L.kF, &L.t, L.kT, PD_PTR(L, 0), PD_STRIDE(L, 0), PD_COL(L, 0), PD_PTR(L, 1),
+                                                                                PD_STRIDE(L, 1), PD_COL(L, 1), L.hDim, L.d + PD_ALPHA, L.d + PD_BETA, L.d + PD_GAMMA,
+                                                                                L.d + PD_DELTA, PD_PTR(L, 2), PD_STRIDE(L, 2), PD_COL(L, 2), L.n, a.stream(2)));
+    return mk_undefined(env);
+}
+// the host forms: a column travels through host_matrices as a side of one column (its highest word) over its matrix
+static bool plookup_host(Args &a, PlookupDesc &L, uint32_t &ew) {
+    if (!plookup_desc(a, 0, L)) return false;
+    ew = (uint32_t)a.u64(2); if (!a.ok) return false;
+    if (ew != 1 && ew != 4) return a.fail("elemWords is 1 or 4");
+    if (L.kF < 1 || L.kF > 16 || L.kT < 1 || L.kT > 16) return a.fail("kF and kT must be 1 .. 16 columns");
+    if (L.hDim != 1 && L.hDim != 3) return a.fail("hDim is 1 or 3");
+    return true;
+}
+// (description, matrices, elemWords): matrices = [f's matrix, selF's or null, t's matrix, selT's or null, outF's matrix, null, outT's matrix];
+// both outputs are written in place (one matrix given twice is one matrix)
+FN(PlookupFold) {
+    Args a(env, info); PlookupDesc L; uint32_t ew; if (!plookup_host(a, L, ew)) return nullptr;
+    const uint64_t hw = ew == 1 ? L.hDim : 1;
+    uint64_t topF = PD_COL(L, 0) + hw - 1;
+    pil2gl_tuple_side oF{ nullptr, PD_STRIDE(L, 0), &topF, nullptr, 0, 0 }, *sides[3] = { &L.f, &L.t, &oF };
+    const uint64_t ks[3] = { L.kF, L.kT, 1 };
+    uint64_t *oT = host_matrices(a, sides, ks, 3, L.n, PD_STRIDE(L, 1), PD_COL(L, 1) + hw - 1, ew,
+                                 "expected f's matrix, selF's or null, t's matrix, selT's or null, outF's matrix, null, then outT's matrix");
+    if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_plookup_fold : pil2gl_plookup_fold)(&L.f, L.kF, &L.t, L.kT, L.d + PD_ALPHA, L.d + PD_BETA, L.hDim, (uint64_t *)oF.base, PD_STRIDE(L, 0),
+                                                                        PD_COL(L, 0), oT, PD_STRIDE(L, 1), PD_COL(L, 1), L.n));
+    return mk_undefined(env);
+}
+// (description, matrices, elemWords): matrices = [f's matrix, selF's or null, t's matrix, selT's or null, h1's matrix, null, h2's matrix, null,
+// out's matrix], the last written in place
+FN(PlookupProd) {
+    Args a(env, info); PlookupDesc L; uint32_t ew; if (!plookup_host(a, L, ew)) return nullptr;
+    const uint64_t hw = ew == 1 ? L.hDim : 1;
+    uint64_t top1 = PD_COL(L, 0) + hw - 1, top2 = PD_COL(L, 1) + hw - 1;
+    pil2gl_tuple_side h1{ nullptr, PD_STRIDE(L, 0), &top1, nullptr, 0, 0 }, h2{ nullptr, PD_STRIDE(L, 1), &top2, nullptr, 0, 0 }, *sides[4] = { &L.f, &L.t, &h1, &h2 };
+    const uint64_t ks[4] = { L.kF, L.kT, 1, 1 };
+    uint64_t *ho = host_matrices(a, sides, ks, 4, L.n, PD_STRIDE(L, 2), PD_COL(L, 2) + (ew == 1 ? 2 : 0), ew,
+                                 "expected f's matrix, selF's or null, t's matrix, selT's or null, h1's matrix, null, h2's matrix, null, then out's matrix");
+    if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_plookup_prod : pil2gl_plookup_prod)(&L.f, L.kF, &L.t, L.kT, h1.base, PD_STRIDE(L, 0), PD_COL(L, 0), h2.base, PD_STRIDE(L, 1), PD_COL(L, 1),
+                                                                        L.hDim, L.d + PD_ALPHA, L.d + PD_BETA, L.d + PD_GAMMA, L.d + PD_DELTA, ho, PD_STRIDE(L, 2),
+                                                                        PD_COL(L, 2), L.n));
+    return mk_undefined(env);
+}
+
 // ---- BN128 Merkle commitment (merklehash_bn128_p.js / merklehash_bn128_worker.js) ----
 FN(Bn128Poseidon) {  // (in BigUint64Array(4*nIn*count) normal form, init BigUint64Array(4*count)|null, count, nIn, nOut, out(4*nOut*count))
     Args a(env, info); uint64_t count = a.u64(2), nIn = a.u64(3), nOut = a.u64(4);
@@ -1127,6 +1211,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "rangeMultPlan", RangeMultPlan }, { "rangeMultDev", RangeMultDev }, { "rangeMult", RangeMult },
         { "logupSumPlan", LogupSumPlan }, { "logupTermLayout", LogupTermLayout }, { "logupSumDev", LogupSumDev }, { "logupSum", LogupSum },
         { "grandProdPlan", GrandProdPlan }, { "grandProdTermLayout", GrandProdTermLayout }, { "grandProdDev", GrandProdDev }, { "grandProd", GrandProd },
+        { "plookupPlan", PlookupPlan }, { "plookupFoldDev", PlookupFoldDev }, { "plookupFold", PlookupFold }, { "plookupProdDev", PlookupProdDev }, { "plookupProd", PlookupProd },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },
         { "buildFrameZerofierDev", BuildFrameZerofierDev }, { "computeQSplitDev", ComputeQSplitDev }, { "computeQSplitBrevDev", ComputeQSplitBrevDev }, { "extendCoefsBrevDev", ExtendCoefsBrevDev }, { "xDivXSubXiDev", XDivXSubXiDev },
         { "buildLevDev", BuildLevDev }, { "computeEvalsDev", ComputeEvalsDev }, { "gprodDev", GprodDev }, { "gsumDev", GsumDev }, { "gsumColDev", GsumColDev }, { "h1h2Dev", H1H2Dev },

@@ -7,7 +7,8 @@
 //     gsum            s[i] = s[i - 1] + num / den[i],  s[0] = num / den[0]          (num: ONE element, on the host)
 //     gsum_col        s[i] = s[i - 1] + num[i] / den[i]                              (num: a column, as gprod's)
 //     logup_sum       the lookup grand sum of include/pil2gl.h: gsum_col over a row's terms folded into one fraction (near the end of this file)
-//     grand_prod      the grand product of a permutation or a connection: gprod over a row's terms multiplied into N and D (at the end)
+//     grand_prod      the grand product of a permutation or a connection: gprod over a row's terms multiplied into N and D (near the end)
+//     plookup         pil1's plookup argument: the fold of F and T, and gprod over a row's num and den made from f, t, h1, h2 (at the end)
 //
 // Elements are 32 bytes of Montgomery words, canonical in and out, moved as two 16-byte halves; element i of a column lies at word
 // 4 i stride, so a column of a row-major section is worked on where it is (as poly_div and g1_msm take theirs).
@@ -42,6 +43,7 @@
 #include "bn_scan_plan.h"
 #include "logup_sum_plan.h"
 #include "grand_prod_plan.h"
+#include "plookup_plan.h"
 #include "tuple_side.cuh"
 
 using namespace pil2gl;
@@ -581,6 +583,171 @@ int pil2gl_bn128_grand_prod(const pil2gl_grand_prod_term *hostTerms, uint64_t nT
     P2_TRY(s.rc());
     P2_TRY(bn_gprod_fold_launch(terms, (u32)nTerms, hostAlpha, hostBeta, hostGamma, dOut, outStride, outCol, n, 0));
     return s.get(hostOut, dOut, outWords);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The plookup argument of pil1 over Fr (include/pil2gl.h states it):
+//   T = H_t or (H_t - beta) selT + beta,   F = H_f or (H_f - T) selF + T,   g = gamma (1 + delta),
+//   num[i] = (F[i] + gamma) (T[i] + delta T[i+1] + g) (1 + delta),   den[i] = (h1[i] + delta h2[i] + g) (h2[i] + delta h1[i+1] + g),
+//   z[0] = 1, z[i] = z[i-1] num[i-1] / den[i-1],   row n - 1's neighbour is row 0.
+// The fold is one kernel, a lane a row, writing F and T as strided columns for bn128_h1h2.  The product is one compress kernel, a lane a
+// row -- it makes T of its row and of the next from the trace, so t's tuple is read twice -- that writes num and den into the working
+// buffer; then gprod's own operators as grand_prod above runs them.  g and 1 + delta are made by the kernel, once a lane.  Products a row:
+// kF - 1 + 2 (kT - 1) Horner steps, one a selector (selT two), 2 + 3 + 3 for num and den; then gprod's 7.
+namespace {
+
+typedef plookupplan::FrJob FrPlJob;
+typedef plookupplan::Side FrPlSide;
+typedef plookupplan::Column FrPlColumn;
+
+// H of the side's row i, blended towards `to` by the selector's value where there is one
+__device__ __forceinline__ FrE fr_pl_side(const FrPlSide &S, u64 i, const FrE &alpha, const FrE &to) {
+    const u64 row = i * S.stride;
+    FrE d = fr_at(S.base, row + S.cols[0]);
+    for (u32 j = 1; j < S.k; j++) d = FrField::add(FrField::mul(d, alpha), fr_at(S.base, row + S.cols[j]));
+    if (S.sel) {
+        bn::fr_sub(d.v, to.v);
+        d = FrField::add(FrField::mul(d, fr_at(S.sel, i * S.selStride + S.selCol)), to);
+    }
+    return d;
+}
+
+__global__ void __launch_bounds__(smapplan::THREADS) bn_plookup_compress_kernel(const FrPlJob J, const FrE one, FrField::Mem *__restrict__ D, FrField::Mem *__restrict__ N) {
+    const FrE alpha = fr_of(J.apow[0]), beta = fr_of(J.beta), gamma = fr_of(J.gamma), delta = fr_of(J.delta);
+    const FrE opd = FrField::add(one, delta), g = FrField::mul(gamma, opd);
+    for (u64 i = (u64)blockIdx.x * smapplan::THREADS + threadIdx.x; i < J.n; i += (u64)gridDim.x * smapplan::THREADS) {
+        const u64 nx = i + 1 < J.n ? i + 1 : 0;                                // row n - 1's neighbour is row 0
+        const FrE T = fr_pl_side(J.t, i, alpha, beta), Tn = fr_pl_side(J.t, nx, alpha, beta), F = fr_pl_side(J.f, i, alpha, T);
+        FrE num = FrField::mul(FrField::add(F, gamma), FrField::add(FrField::add(T, FrField::mul(delta, Tn)), g));
+        num = FrField::mul(num, opd);
+        const FrE a = fr_at(J.h1.base, i * J.h1.stride + J.h1.col), b = fr_at(J.h2.base, i * J.h2.stride + J.h2.col);
+        const FrE an = fr_at(J.h1.base, nx * J.h1.stride + J.h1.col);
+        const FrE den = FrField::mul(FrField::add(FrField::add(a, FrField::mul(delta, b)), g), FrField::add(FrField::add(b, FrField::mul(delta, an)), g));
+        FrField::store(D, i, den);
+        FrField::store(N, i, num);
+    }
+}
+
+__global__ void __launch_bounds__(smapplan::THREADS) bn_plookup_fold_kernel(const FrPlJob J, FrField::Mem *__restrict__ outF, u64 strideF, u64 colF,
+                                                                           FrField::Mem *__restrict__ outT, u64 strideT, u64 colT) {
+    const FrE alpha = fr_of(J.apow[0]), beta = fr_of(J.beta);
+    for (u64 i = (u64)blockIdx.x * smapplan::THREADS + threadIdx.x; i < J.n; i += (u64)gridDim.x * smapplan::THREADS) {
+        const FrE T = fr_pl_side(J.t, i, alpha, beta), F = fr_pl_side(J.f, i, alpha, T);
+        FrField::store(outF, i * strideF + colF, F);
+        FrField::store(outT, i * strideT + colT, T);
+    }
+}
+
+// every launch of a product call, on st; the arguments have passed plookupplan::check_call() and n > 0, the pointers are the device's
+int bn_plookup_prod_launch(const pil2gl_tuple_side &f, u64 kF, const pil2gl_tuple_side &t, u64 kT, const FrPlColumn &h1, const FrPlColumn &h2, const u64 *const *ch,
+                           const FrPlColumn &out, u64 n, hipStream_t st) {
+    const bnscan::Plan p = bnscan::plan(n, false);
+    u64 *d;
+    P2_TRY(scratch(SCR_BN_SCAN, 4 * p.elems + 8 * n, &d));        // the plan's levels, then D and N
+    FrPlJob J{};
+    plookupplan::pack(f, kF, t, kT, &h1, &h2, 1, (const u64 (*)[4])ch[0], ch[1], ch[2], ch[3], (const u64 *)nullptr, (const u64 *)nullptr, n, J);
+    FrE one;
+    bnp::bn_limbs(bnp::bn_mont_one().w, one.v);
+    FrField::Mem *D = (FrField::Mem *)(d + 4 * p.elems), *N = D + n;
+    bn_plookup_compress_kernel<<<smapplan::blocks(n), smapplan::THREADS, 0, st>>>(J, one, D, N);
+    KERNEL_CHECK();
+    uint4 *base = (uint4 *)d, *y = (uint4 *)((u64 *)out.base + 4 * out.col);
+    P2_TRY(inverse_launch(p, base, (const uint4 *)D, 1, y, out.stride, y, out.stride, MODE_COLUMN, (const uint4 *)N, 1, Elem{}, st));
+    return scan_launch<false>(p, base, y, out.stride, st);
+}
+
+int bn_plookup_fold_launch(const pil2gl_tuple_side &f, u64 kF, const pil2gl_tuple_side &t, u64 kT, const u64 *const *ch, const FrPlColumn *out, u64 n, hipStream_t st) {
+    FrPlJob J{};
+    plookupplan::pack(f, kF, t, kT, (const FrPlColumn *)nullptr, (const FrPlColumn *)nullptr, 1, (const u64 (*)[4])ch[0], ch[1], (const u64 *)nullptr,
+                      (const u64 *)nullptr, (const u64 *)nullptr, (const u64 *)nullptr, n, J);
+    bn_plookup_fold_kernel<<<smapplan::blocks(n), smapplan::THREADS, 0, st>>>(J, (FrField::Mem *)out[0].base, out[0].stride, out[0].col, (FrField::Mem *)out[1].base,
+                                                                            out[1].stride, out[1].col);
+    KERNEL_CHECK();
+    return PIL2GL_OK;
+}
+
+int bn_plookup_check(const pil2gl_tuple_side *f, u64 kF, const pil2gl_tuple_side *t, u64 kT, const FrPlColumn *read, u32 nRead, u32 hDim, const u64 *const *ch, u32 nCh,
+                     const FrPlColumn *out, u32 nOut, u64 n, bool dev) {
+    char why[96];
+    if (const char *msg = plookupplan::check_call(f, kF, t, kT, read, nRead, hDim, ch, nCh, out, nOut, n, 4, dev, why)) return fail(PIL2GL_EINVAL, "%s", msg);
+    return PIL2GL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_bn128_plookup_fold_dev(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostAlpha,
+                                  const uint64_t *hostBeta, uint32_t hDim, uint64_t *outF, uint64_t strideF, uint64_t colF, uint64_t *outT, uint64_t strideT,
+                                  uint64_t colT, uint64_t n, void *stream) {
+    const u64 *const ch[2] = { hostAlpha, hostBeta };
+    const FrPlColumn out[2] = { { outF, strideF, colF }, { outT, strideT, colT } };
+    P2_TRY(bn_plookup_check(hostF, kF, hostT, kT, nullptr, 0, hDim, ch, 2, out, 2, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return bn_plookup_fold_launch(*hostF, kF, *hostT, kT, ch, out, n, as_stream(stream));
+}
+
+// host matrices, each staged up to the last element touched; an output's matrix goes up as it is and comes back with the column written
+// (outF and outT of one matrix: that matrix once)
+int pil2gl_bn128_plookup_fold(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostAlpha,
+                              const uint64_t *hostBeta, uint32_t hDim, uint64_t *hostOutF, uint64_t strideF, uint64_t colF, uint64_t *hostOutT, uint64_t strideT,
+                              uint64_t colT, uint64_t n) {
+    const u64 *const ch[2] = { hostAlpha, hostBeta };
+    FrPlColumn out[2] = { { hostOutF, strideF, colF }, { hostOutT, strideT, colT } };
+    P2_TRY(bn_plookup_check(hostF, kF, hostT, kT, nullptr, 0, hDim, ch, 2, out, 2, n, false));
+    if (!n) return PIL2GL_OK;
+    pil2gl_tuple_side f = *hostF, t = *hostT;
+    const bool same = hostOutF == hostOutT;
+    u64 wF = plookupplan::column_words(out[0], 1, n, 4), wT = plookupplan::column_words(out[1], 1, n, 4);
+    if (same) wF = wT = wF > wT ? wF : wT;
+    Stage s(tupleside::staged_words(f, n, kF, 4) + tupleside::staged_words(t, n, kT, 4) + smapplan::pad16(wF) + (same ? 0 : smapplan::pad16(wT)));
+    P2_TRY(s.rc());
+    tupleside::stage_side(s, f, n, kF, 4);
+    tupleside::stage_side(s, t, n, kT, 4);
+    out[0].base = s.put(hostOutF, wF); s.take(smapplan::pad16(wF) - wF);
+    out[1].base = same ? out[0].base : s.put(hostOutT, wT);
+    P2_TRY(s.rc());
+    P2_TRY(bn_plookup_fold_launch(f, kF, t, kT, ch, out, n, 0));
+    P2_TRY(s.get(hostOutF, out[0].base, wF));
+    return same ? PIL2GL_OK : s.get(hostOutT, out[1].base, wT);
+}
+
+int pil2gl_bn128_plookup_prod_dev(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *h1, uint64_t h1Stride,
+                                  uint64_t h1Col, const uint64_t *h2, uint64_t h2Stride, uint64_t h2Col, uint32_t hDim, const uint64_t *hostAlpha,
+                                  const uint64_t *hostBeta, const uint64_t *hostGamma, const uint64_t *hostDelta, uint64_t *out, uint64_t outStride,
+                                  uint64_t outCol, uint64_t n, void *stream) {
+    const u64 *const ch[4] = { hostAlpha, hostBeta, hostGamma, hostDelta };
+    const FrPlColumn h[2] = { { h1, h1Stride, h1Col }, { h2, h2Stride, h2Col } }, o = { out, outStride, outCol };
+    P2_TRY(bn_plookup_check(hostF, kF, hostT, kT, h, 2, hDim, ch, 4, &o, 1, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return bn_plookup_prod_launch(*hostF, kF, *hostT, kT, h[0], h[1], ch, o, n, as_stream(stream));
+}
+
+int pil2gl_bn128_plookup_prod(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostH1, uint64_t h1Stride,
+                              uint64_t h1Col, const uint64_t *hostH2, uint64_t h2Stride, uint64_t h2Col, uint32_t hDim, const uint64_t *hostAlpha,
+                              const uint64_t *hostBeta, const uint64_t *hostGamma, const uint64_t *hostDelta, uint64_t *hostOut, uint64_t outStride,
+                              uint64_t outCol, uint64_t n) {
+    const u64 *const ch[4] = { hostAlpha, hostBeta, hostGamma, hostDelta };
+    FrPlColumn h[2] = { { hostH1, h1Stride, h1Col }, { hostH2, h2Stride, h2Col } }, o = { hostOut, outStride, outCol };
+    P2_TRY(bn_plookup_check(hostF, kF, hostT, kT, h, 2, hDim, ch, 4, &o, 1, n, false));
+    if (!n) return PIL2GL_OK;
+    pil2gl_tuple_side f = *hostF, t = *hostT;
+    const u64 outWords = plookupplan::column_words(o, 1, n, 4);
+    Stage s(tupleside::staged_words(f, n, kF, 4) + tupleside::staged_words(t, n, kT, 4) + smapplan::pad16(plookupplan::column_words(h[0], 1, n, 4)) +
+            smapplan::pad16(plookupplan::column_words(h[1], 1, n, 4)) + smapplan::pad16(outWords));
+    P2_TRY(s.rc());
+    tupleside::stage_side(s, f, n, kF, 4);
+    tupleside::stage_side(s, t, n, kT, 4);
+    plookupplan::stage_column(s, h[0], 1, n, 4);
+    plookupplan::stage_column(s, h[1], 1, n, 4);
+    o.base = s.put(hostOut, outWords);
+    P2_TRY(s.rc());
+    P2_TRY(bn_plookup_prod_launch(f, kF, t, kT, h[0], h[1], ch, o, n, 0));
+    return s.get(hostOut, o.base, outWords);
 }
 
 }  // extern "C"

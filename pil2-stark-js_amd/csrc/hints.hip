@@ -6,13 +6,14 @@
 // eight rows) and the running product / sum is a three-kernel scan: per-block inclusive scan + block totals, scan of the
 // totals, then the fix-up (for the product: shifted by one row, z[0] = 1).  Operands may be base (dim 1) or cubic
 // extension (dim 3) columns, row-major; the result is dim 3 if either operand is, else dim 1.  gsum_col is the sum with a column
-// numerator; the lookup grand sum further down folds a lookup's sides into the sum's first pass, and the grand product behind it a
-// permutation's or a connection's terms into the product's.
+// numerator; the lookup grand sum further down folds a lookup's sides into the sum's first pass, the grand product behind it a
+// permutation's or a connection's terms into the product's, and the plookup section behind that pil1's plookup argument.
 #include "common.h"
 #include "gl_field.cuh"
 #include "hint_plan.h"
 #include "logup_sum_plan.h"
 #include "grand_prod_plan.h"
+#include "plookup_plan.h"
 #include <utility>
 
 using namespace gl;
@@ -487,6 +488,273 @@ int pil2gl_grand_prod(const pil2gl_grand_prod_term *hostTerms, uint64_t nTerms, 
     P2_TRY(s.rc());
     P2_TRY(gprod_fold_launch(terms, (u32)nTerms, hostAlpha, hostBeta, hostGamma, dOut, outStride, outCol, n, 0));
     return s.get(hostOut, dOut, outWords);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The plookup argument of pil1 (include/pil2gl.h states it; tests/plookup_ref.py restates it over integers):
+//   T = H_t or (H_t - beta) selT + beta,   F = H_f or (H_f - T) selF + T,   g = gamma (1 + delta),
+//   num[i] = (F[i] + gamma) (T[i] + delta T[i+1] + g) (1 + delta),   den[i] = (h1[i] + delta h2[i] + g) (h2[i] + delta h1[i+1] + g),
+//   z[0] = 1, z[i] = z[i-1] num[i-1] / den[i-1],   row n - 1's neighbour is row 0.
+// The fold (stage 1) is one kernel, a lane a row, that writes F and T for h1h2.  The product (stage 2) is one fused first pass beside
+// gprod_fold_scan1, then hint_scan2<true> and hint_scan3<true> as they are.  A lane takes its SCAN_ITEMS rows and needs T and h1 at nine:
+// its eight and the row behind them -- the next lane's first, the next block's first, or row 0 behind row n - 1.  The ninth T is computed
+// from the trace like the others (k more loads a lane; no exchange through LDS, which would put a barrier between the loads and the
+// products).  N and D of a row are built in registers, the eight D inverted together, a zero D inverting to zero as in hint_scan1, so that a
+// zero den factor gives ratio 0; then the block-local product scan into tmp.  Neither num nor den is ever a column.
+// Base products a row: 3 (k - 1) a side for H (9/8 of that for t), 3 a selector, 6 for delta T', 6 + 6 for N, 2 x 3 (hDim 1) or 2 x 6
+// (hDim 3) for delta h, 6 for D; then gprod_fold_scan1's 18 + 6 + 6 and 1/8 of the lane's e3_inv.
+// The job (plookup_plan.h) travels as a kernel argument and is read with wave-uniform indices.
+// Safety: nothing read from a matrix is used as an address; a row index is below n before any load (the ninth row is base + 8 < n, or 0).
+namespace {
+
+typedef plookupplan::Side PlSide;
+typedef plookupplan::HCol PlCol;
+typedef plookupplan::GlJob PlJob;
+typedef plookupplan::Column PlColumn;
+
+constexpr int PL_ROWS = SCAN_ITEMS + 1;
+
+// the side's H at ROWS rows r[k] (ok[k]: the row exists) and, with a selector, its blend towards to(k); a row that is not there stays 0
+template <int ROWS, class To>
+__device__ __forceinline__ void pl_side(const PlSide &S, const PlJob &J, const u64 (&r)[PL_ROWS], const bool (&ok)[PL_ROWS], E3 (&v)[ROWS], To to) {
+    const std::make_integer_sequence<int, ROWS> rows{};
+    const u64 stride = S.stride;
+    const u64 *m = (const u64 *)S.base;
+    each_item([&](auto k) { v[k] = ident<false>(); }, rows);
+    // the columns are the outer loop: a column's loads of the lane's rows are in flight together
+    for (u32 j = 0; j + 1 < S.k; j++) {
+        const E3 ap = e3_of(J.apow[S.k - 2 - j]);                                // alpha^(k - 1 - j)
+        const u64 *p = m + S.cols[j];
+        each_item([&](auto k) { if (ok[k]) v[k] = e3_add(v[k], e3_scale(ap, p[r[k] * stride])); }, rows);
+    }
+    {
+        const u64 *p = m + S.cols[S.k - 1];
+        each_item([&](auto k) { if (ok[k]) v[k].v[0] = add(v[k].v[0], canon(p[r[k] * stride])); }, rows);
+    }
+    if (S.sel) {
+        const u64 ss = S.selStride;
+        const u64 *p = (const u64 *)S.sel + S.selCol;
+        each_item([&](auto k) { if (ok[k]) { const E3 b = to(k); v[k] = e3_add(e3_scale(e3_sub(v[k], b), p[r[k] * ss]), b); } }, rows);
+    }
+}
+
+__device__ __forceinline__ E3 pl_h(const PlCol &c, u32 hDim, u64 row) {
+    const u64 *p = (const u64 *)c.base + row * c.stride + c.col;
+    return hDim == 3 ? E3{ { canon(p[0]), canon(p[1]), canon(p[2]) } } : E3{ { canon(p[0]), 0, 0 } };
+}
+// delta x, x an h element: a scaling when h is a base column
+__device__ __forceinline__ E3 pl_dh(const E3 &delta, const E3 &x, u32 hDim) { return hDim == 3 ? e3_mul(delta, x) : e3_scale(delta, x.v[0]); }
+
+__global__ void __launch_bounds__(SCAN_THREADS) plookup_fold_scan1(const PlJob J, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
+    __shared__ E3 sh[SCAN_THREADS];
+    const u64 base = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_ITEMS, n = J.n;
+    const std::make_integer_sequence<int, PL_ROWS> nine{};
+    // the lane's rows and the row behind them; past row n - 1 comes row 0
+    u64 r[PL_ROWS];
+    bool ok[PL_ROWS];
+    each_item([&](auto k) { r[k] = base + k; ok[k] = base + k < n; });
+    r[SCAN_ITEMS] = base + SCAN_ITEMS < n ? base + SCAN_ITEMS : 0;
+    ok[SCAN_ITEMS] = true;
+    const E3 beta = e3_of(J.beta), gamma = e3_of(J.gamma), delta = e3_of(J.delta), g = e3_of(J.g), opd = e3_of(J.onePlusDelta);
+    E3 tv[PL_ROWS], num[SCAN_ITEMS], den[SCAN_ITEMS], loc[SCAN_ITEMS];
+    pl_side(J.t, J, r, ok, tv, [&](auto) { return beta; });
+    pl_side(J.f, J, r, ok, num, [&](auto k) { return tv[k]; });                // F: blended towards T of the same row
+    each_item([&](auto k) {
+        if (!ok[k]) { num[k] = ident<true>(); return; }                         // rows at or past n stay 1 / 1
+        E3 tn = tv[SCAN_ITEMS];
+        if constexpr (decltype(k)::value + 1 < SCAN_ITEMS) { if (ok[k + 1]) tn = tv[k + 1]; }
+        num[k] = e3_mul(e3_mul(e3_add(num[k], gamma), e3_add(e3_add(tv[k], e3_mul(delta, tn)), g)), opd);
+    });
+    {
+        E3 a[PL_ROWS];
+        const u32 hDim = J.hDim;
+        each_item([&](auto k) { a[k] = ok[k] ? pl_h(J.h1, hDim, r[k]) : ident<false>(); }, nine);
+        each_item([&](auto k) { den[k] = ok[k] ? pl_h(J.h2, hDim, r[k]) : ident<false>(); });
+        each_item([&](auto k) {
+            if (!ok[k]) { den[k] = ident<true>(); return; }
+            E3 an = a[SCAN_ITEMS];
+            if constexpr (decltype(k)::value + 1 < SCAN_ITEMS) { if (ok[k + 1]) an = a[k + 1]; }
+            const E3 b = den[k];
+            den[k] = e3_mul(e3_add(e3_add(a[k], pl_dh(delta, b, hDim)), g), e3_add(e3_add(b, pl_dh(delta, an, hDim)), g));
+        });
+    }
+    // hint_scan1's inversion: a zero D is kept out of the running product and its row's ratio is 0
+    u32 zero = 0;
+    E3 acc = ident<true>();
+    each_item([&](auto k) {
+        if (!(den[k].v[0] | den[k].v[1] | den[k].v[2])) { zero |= 1u << k; den[k] = ident<true>(); }
+        loc[k] = acc;                                   // the product of the rows' D before this one
+        acc = e3_mul(acc, den[k]);
+    });
+    E3 ai = (acc.v[1] | acc.v[2]) ? e3_inv(acc) : E3{ { inv(acc.v[0]), 0, 0 } };
+    each_item_down([&](auto k) {
+        const E3 di = e3_mul(ai, loc[k]);               // 1 / D_k
+        ai = e3_mul(ai, den[k]);
+        loc[k] = ((zero >> k) & 1) ? ident<false>() : e3_mul(num[k], di);
+    });
+    E3 run = ident<true>();
+    each_item([&](auto k) { run = e3_mul(run, loc[k]); loc[k] = run; });        // rows at or past n hold 1 / 1
+    E3 bt;
+    const E3 ex = block_exclusive<true>(run, sh, &bt);
+    each_item([&](auto k) { const u64 i = base + k; if (i < n) st3(tmp, i, e3_mul(ex, loc[k])); });
+    if (threadIdx.x == 0) st3(totals, blockIdx.x, bt);
+}
+
+// the fold: F and T of row i as columns of hDim words; with hDim = 1 the entry has seen kF = kT = 1 and no selT
+__global__ void __launch_bounds__(256) plookup_fold_kernel(const PlJob J, u64 *__restrict__ outF, u64 strideF, u64 colF, u64 *__restrict__ outT, u64 strideT, u64 colT) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= J.n) return;
+    const E3 beta = e3_of(J.beta);
+    auto side = [&](const PlSide &S, const E3 &to) {
+        const u64 *p = (const u64 *)S.base + i * S.stride;
+        E3 v = ident<false>();
+        for (u32 j = 0; j + 1 < S.k; j++) v = e3_add(v, e3_scale(e3_of(J.apow[S.k - 2 - j]), p[S.cols[j]]));
+        v.v[0] = add(v.v[0], canon(p[S.cols[S.k - 1]]));
+        if (S.sel) v = e3_add(e3_scale(e3_sub(v, to), ((const u64 *)S.sel)[i * S.selStride + S.selCol]), to);
+        return v;
+    };
+    const E3 T = side(J.t, beta), F = side(J.f, T);
+    u64 *f = outF + i * strideF + colF, *t = outT + i * strideT + colT;
+    f[0] = F.v[0]; t[0] = T.v[0];
+    if (J.hDim == 3) { f[1] = F.v[1]; f[2] = F.v[2]; t[1] = T.v[1]; t[2] = T.v[2]; }
+}
+
+// the job of either entry: the challenges canonical, the powers of alpha, g and 1 + delta (gamma and delta null: the fold)
+void pl_job(const pil2gl_tuple_side &f, u64 kF, const pil2gl_tuple_side &t, u64 kT, const PlColumn *h1, const PlColumn *h2, u32 hDim, const u64 *alpha,
+            const u64 *beta, const u64 *gamma, const u64 *delta, u64 n, PlJob &J) {
+    auto canon3 = [](const u64 *x, u64 (&y)[3]) { for (int c = 0; c < 3; c++) y[c] = x ? h_canon(x[c]) : 0; };
+    u64 a[3], b[3], ga[3], de[3], g[3], opd[3];
+    canon3(alpha, a); canon3(beta, b); canon3(gamma, ga); canon3(delta, de);
+    opd[0] = h_add(de[0], 1); opd[1] = de[1]; opd[2] = de[2];
+    h_e3_mul(ga, opd, g);
+    u64 pw[tupleside::MAX_K - 1][3], cur[3] = { 1, 0, 0 };
+    for (u32 e = 0; e < tupleside::MAX_K - 1; e++) {
+        h_e3_mul(cur, a, pw[e]);
+        for (int c = 0; c < 3; c++) cur[c] = pw[e][c];
+    }
+    plookupplan::pack(f, kF, t, kT, h1, h2, hDim, pw, b, ga, de, g, opd, n, J);
+}
+
+int plookup_prod_launch(const pil2gl_tuple_side &f, u64 kF, const pil2gl_tuple_side &t, u64 kT, const PlColumn &h1, const PlColumn &h2, u32 hDim, const u64 *const *ch,
+                        const PlColumn &out, u64 n, hipStream_t st) {
+    PlJob J{};
+    pl_job(f, kF, t, kT, &h1, &h2, hDim, ch[0], ch[1], ch[2], ch[3], n, J);
+    const u64 nb = hintplan::blocks(n);
+    u64 *tmp, *totals;
+    P2_TRY(scratch(SCR_HINT_TMP, n * 3, &tmp));
+    P2_TRY(scratch(SCR_HINT_TOTALS, nb * 3, &totals));
+    plookup_fold_scan1<<<(unsigned)nb, SCAN_THREADS, 0, st>>>(J, tmp, totals);
+    KERNEL_CHECK();
+    hint_scan2<true><<<1, SCAN_THREADS, 0, st>>>(totals, nb);
+    KERNEL_CHECK();
+    hint_scan3<true><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tmp, totals, n, 3, (u64 *)out.base, out.stride, out.col);
+    KERNEL_CHECK();
+    return PIL2GL_OK;
+}
+
+int plookup_fold_launch(const pil2gl_tuple_side &f, u64 kF, const pil2gl_tuple_side &t, u64 kT, u32 hDim, const u64 *const *ch, const PlColumn *out, u64 n,
+                        hipStream_t st) {
+    PlJob J{};
+    pl_job(f, kF, t, kT, nullptr, nullptr, hDim, ch[0], ch[1], nullptr, nullptr, n, J);
+    plookup_fold_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(J, (u64 *)out[0].base, out[0].stride, out[0].col, (u64 *)out[1].base, out[1].stride, out[1].col);
+    KERNEL_CHECK();
+    return PIL2GL_OK;
+}
+
+int plookup_check(const pil2gl_tuple_side *f, u64 kF, const pil2gl_tuple_side *t, u64 kT, const PlColumn *read, u32 nRead, u32 hDim, const u64 *const *ch, u32 nCh,
+                  const PlColumn *out, u32 nOut, u64 n, bool dev) {
+    char why[96];
+    if (const char *msg = plookupplan::check_call(f, kF, t, kT, read, nRead, hDim, ch, nCh, out, nOut, n, 1, dev, why)) return fail(PIL2GL_EINVAL, "%s", msg);
+    return PIL2GL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_plookup_plan(uint64_t n, uint64_t kF, uint64_t kT, uint32_t elemWords, uint32_t *outInfo, uint64_t *workBytes) {
+    if (workBytes) *workBytes = 0;
+    if (const char *msg = plookupplan::check(n, kF, kT, elemWords)) return fail(PIL2GL_EINVAL, "%s", msg);
+    const plookupplan::Plan p = plookupplan::plan(n, elemWords);
+    if (outInfo) {
+        outInfo[0] = p.threads; outInfo[1] = p.items; outInfo[2] = p.blocks; outInfo[3] = p.launches; outInfo[4] = p.depth;
+        outInfo[5] = plookupplan::out_width(elemWords);
+    }
+    if (workBytes) *workBytes = p.bytes;
+    return PIL2GL_OK;
+}
+
+int pil2gl_plookup_fold_dev(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostAlpha,
+                            const uint64_t *hostBeta, uint32_t hDim, uint64_t *outF, uint64_t strideF, uint64_t colF, uint64_t *outT, uint64_t strideT,
+                            uint64_t colT, uint64_t n, void *stream) {
+    const u64 *const ch[2] = { hostAlpha, hostBeta };
+    const PlColumn out[2] = { { outF, strideF, colF }, { outT, strideT, colT } };
+    P2_TRY(plookup_check(hostF, kF, hostT, kT, nullptr, 0, hDim, ch, 2, out, 2, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return plookup_fold_launch(*hostF, kF, *hostT, kT, hDim, ch, out, n, as_stream(stream));
+}
+
+// host matrices, each staged up to the last element touched; an output's matrix goes up as it is and comes back with the column written
+// (outF and outT of one matrix: that matrix once)
+int pil2gl_plookup_fold(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostAlpha,
+                        const uint64_t *hostBeta, uint32_t hDim, uint64_t *hostOutF, uint64_t strideF, uint64_t colF, uint64_t *hostOutT, uint64_t strideT,
+                        uint64_t colT, uint64_t n) {
+    const u64 *const ch[2] = { hostAlpha, hostBeta };
+    PlColumn out[2] = { { hostOutF, strideF, colF }, { hostOutT, strideT, colT } };
+    P2_TRY(plookup_check(hostF, kF, hostT, kT, nullptr, 0, hDim, ch, 2, out, 2, n, false));
+    if (!n) return PIL2GL_OK;
+    pil2gl_tuple_side f = *hostF, t = *hostT;
+    const bool one = hostOutF == hostOutT;
+    u64 wF = plookupplan::column_words(out[0], hDim, n, 1), wT = plookupplan::column_words(out[1], hDim, n, 1);
+    if (one) wF = wT = wF > wT ? wF : wT;
+    Stage s(tupleside::staged_words(f, n, kF, 1) + tupleside::staged_words(t, n, kT, 1) + smapplan::pad16(wF) + (one ? 0 : smapplan::pad16(wT)));
+    P2_TRY(s.rc());
+    tupleside::stage_side(s, f, n, kF, 1);
+    tupleside::stage_side(s, t, n, kT, 1);
+    out[0].base = s.put(hostOutF, wF); s.take(smapplan::pad16(wF) - wF);
+    out[1].base = one ? out[0].base : s.put(hostOutT, wT);
+    P2_TRY(s.rc());
+    P2_TRY(plookup_fold_launch(f, kF, t, kT, hDim, ch, out, n, 0));
+    P2_TRY(s.get(hostOutF, out[0].base, wF));
+    return one ? PIL2GL_OK : s.get(hostOutT, out[1].base, wT);
+}
+
+int pil2gl_plookup_prod_dev(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *h1, uint64_t h1Stride,
+                            uint64_t h1Col, const uint64_t *h2, uint64_t h2Stride, uint64_t h2Col, uint32_t hDim, const uint64_t *hostAlpha,
+                            const uint64_t *hostBeta, const uint64_t *hostGamma, const uint64_t *hostDelta, uint64_t *out, uint64_t outStride, uint64_t outCol,
+                            uint64_t n, void *stream) {
+    const u64 *const ch[4] = { hostAlpha, hostBeta, hostGamma, hostDelta };
+    const PlColumn h[2] = { { h1, h1Stride, h1Col }, { h2, h2Stride, h2Col } }, o = { out, outStride, outCol };
+    P2_TRY(plookup_check(hostF, kF, hostT, kT, h, 2, hDim, ch, 4, &o, 1, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return plookup_prod_launch(*hostF, kF, *hostT, kT, h[0], h[1], hDim, ch, o, n, as_stream(stream));
+}
+
+int pil2gl_plookup_prod(const pil2gl_tuple_side *hostF, uint64_t kF, const pil2gl_tuple_side *hostT, uint64_t kT, const uint64_t *hostH1, uint64_t h1Stride,
+                        uint64_t h1Col, const uint64_t *hostH2, uint64_t h2Stride, uint64_t h2Col, uint32_t hDim, const uint64_t *hostAlpha,
+                        const uint64_t *hostBeta, const uint64_t *hostGamma, const uint64_t *hostDelta, uint64_t *hostOut, uint64_t outStride, uint64_t outCol,
+                        uint64_t n) {
+    const u64 *const ch[4] = { hostAlpha, hostBeta, hostGamma, hostDelta };
+    PlColumn h[2] = { { hostH1, h1Stride, h1Col }, { hostH2, h2Stride, h2Col } }, o = { hostOut, outStride, outCol };
+    P2_TRY(plookup_check(hostF, kF, hostT, kT, h, 2, hDim, ch, 4, &o, 1, n, false));
+    if (!n) return PIL2GL_OK;
+    pil2gl_tuple_side f = *hostF, t = *hostT;
+    const u64 outWords = plookupplan::column_words(o, 3, n, 1);
+    Stage s(tupleside::staged_words(f, n, kF, 1) + tupleside::staged_words(t, n, kT, 1) + smapplan::pad16(plookupplan::column_words(h[0], hDim, n, 1)) +
+            smapplan::pad16(plookupplan::column_words(h[1], hDim, n, 1)) + smapplan::pad16(outWords));
+    P2_TRY(s.rc());
+    tupleside::stage_side(s, f, n, kF, 1);
+    tupleside::stage_side(s, t, n, kT, 1);
+    plookupplan::stage_column(s, h[0], hDim, n, 1);
+    plookupplan::stage_column(s, h[1], hDim, n, 1);
+    o.base = s.put(hostOut, outWords);
+    P2_TRY(s.rc());
+    P2_TRY(plookup_prod_launch(f, kF, t, kT, h[0], h[1], hDim, ch, o, n, 0));
+    return s.get(hostOut, o.base, outWords);
 }
 
 }  // extern "C"

@@ -36,6 +36,10 @@
 //   grandProduct(terms, alpha, beta, gamma, out, n, opts) / grandProductDev(..) / grandProductPlan(n, nTerms, sumK, bn128)
 //       the column z of a permutation or a connection from the trace columns (include/pil2gl.h states it); permutationTerms and
 //       connectionTerms build the term lists of the reference's two identities
+//   plookupFold(f, t, alpha, beta, outF, outT, n, opts) / plookupFoldDev(..)      the two kept expressions F and T of a pil1 plookup
+//   plookupProduct(f, t, h1, h2, alpha, beta, gamma, delta, out, n, opts) / plookupProductDev(..) / plookupPlan(n, kF, kT, bn128)
+//       the column z of a pil1 plookup from f, t, h1 and h2 (include/pil2gl.h states it); opts.hDim: words of an h element over
+//       Goldilocks (3, or 1 for a base column)
 // Node 12: no optional chaining.
 "use strict";
 const { addon, DevBuffer, isDev } = require("./native.js");
@@ -274,4 +278,43 @@ const connectionTerms = (aCols, sCols, x, delta, deltaKs) => [].concat(...aCols.
     { buf: a.buf, stride: a.stride, cols: [a.col], den: 0, id: x, idCoef: deltaKs[j] },
     { buf: a.buf, stride: a.stride, cols: [a.col], den: 1, id: sCols[j], idCoef: delta }]));
 
-module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, logupSum, logupSumDev, logupSumPlan, grandProduct, grandProductDev, grandProductPlan, permutationTerms, connectionTerms, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };
+// ---- plookup of pil1: the fold of F and T, and z from f, t, h1 and h2 ----
+// f and t are sides { buf, stride, cols, sel } with their own column counts; h1, h2 and the outputs are columns { buf, stride, col } of hDim
+// words an element (Goldilocks: opts.hDim, 3 by default; Fr: one element); the challenges are 3 or 4 words each.  z[n-1] is the hint's result.
+function plookup(dev, prod, fIn, tIn, colsIn, chs, n, opts) {
+    const bn = !!(opts && opts.bn128), ew = bn ? 4 : 1, cw = bn ? 4 : 3;
+    const hDim = bn ? 1 : (opts && opts.hDim !== undefined ? opts.hDim : 3), hw = bn ? 1 : hDim, zw = bn ? 1 : 3;
+    if (hDim !== 1 && hDim !== 3) throw new Error("hDim is 1 or 3");
+    const elem = (v, what) => {
+        const w = Array.from(stage.asWords(v));
+        if (w.length !== cw) throw new Error(what + " must hold " + cw + " words");
+        return w.concat([0n]).slice(0, 4);
+    };
+    const names = prod ? ["h1", "h2", "out"] : ["outF", "outT"], chNames = ["alpha", "beta", "gamma", "delta"];
+    const f = side(fIn, "f", n, ew, dev), t = side(tIn, "t", n, ew, dev);
+    for (const [x, what] of [[f, "f"], [t, "t"]]) if (x.cols.length < 1 || x.cols.length > 16) throw new Error(what + ": 1 .. 16 columns");
+    const cols = colsIn.map((c, i) => {
+        if (!c || !(c.stride > 0) || !(c.col >= 0)) throw new Error(names[i] + " must be { buf, stride, col }");
+        return side({ buf: c.buf, stride: c.stride, cols: [c.col, c.col + (prod && i === 2 ? zw : hw) - 1] }, names[i], n, ew, dev);
+    });
+    if (!prod && colsIn[0].buf === colsIn[1].buf) cols[1].buf = cols[0].buf;      // one matrix for both outputs: one copy where asWords copied
+    const ptr = (b) => dev && b ? b.ptr : 0n;
+    const five = (x) => [ptr(x.buf), x.stride].concat(x.sel ? [ptr(x.sel.buf), x.sel.stride, x.sel.col] : [0n, 0, 0]);
+    const four = [0, 1, 2, 3].map((i) => i < chs.length ? elem(chs[i], chNames[i]) : [0n, 0n, 0n, 0n]);
+    const three = [0, 1, 2].map((i) => i < cols.length ? [ptr(cols[i].buf), cols[i].stride, colsIn[i].col] : [0n, 0, 0]);
+    const slots = (x) => x.cols.concat(new Array(16 - x.cols.length).fill(0));
+    const desc = BigUint64Array.from([n, f.cols.length, t.cols.length, hDim].concat(...four, five(f), five(t), ...three, slots(f), slots(t)).map((v) => BigInt(v)));
+    const written = prod ? [colsIn[2]] : colsIn;
+    if (dev) { (prod ? addon.plookupProdDev : addon.plookupFoldDev)(desc, ew, opts && opts.stream); return prod ? written[0] : written; }
+    const mats = matrices([f, t]).concat(prod ? [cols[0].buf, null, cols[1].buf, null, cols[2].buf] : [cols[0].buf, null, cols[1].buf]);
+    (prod ? addon.plookupProd : addon.plookupFold)(desc, mats, ew);
+    (prod ? [cols[2]] : cols).forEach((c, i) => copyBack(c.buf, written[i].buf));
+    return prod ? written[0] : written;
+}
+const plookupFold = (f, t, alpha, beta, outF, outT, n, opts) => plookup(false, false, f, t, [outF, outT], [alpha, beta], n, opts);
+const plookupFoldDev = (f, t, alpha, beta, outF, outT, n, opts) => plookup(true, false, f, t, [outF, outT], [alpha, beta], n, opts);
+const plookupProduct = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, opts) => plookup(false, true, f, t, [h1, h2, out], [alpha, beta, gamma, delta], n, opts);
+const plookupProductDev = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, opts) => plookup(true, true, f, t, [h1, h2, out], [alpha, beta, gamma, delta], n, opts);
+const plookupPlan = (n, kF, kT, bn128) => addon.plookupPlan(n, kF, kT, bn128 ? 4 : 1);
+
+module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, logupSum, logupSumDev, logupSumPlan, grandProduct, grandProductDev, grandProductPlan, permutationTerms, connectionTerms, plookupFold, plookupFoldDev, plookupProduct, plookupProductDev, plookupPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };

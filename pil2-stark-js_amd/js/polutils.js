@@ -11,7 +11,7 @@
 // One deviation, on purpose: buildZhInv honours `offset` when it fills rows >= 2^extendBits; the reference's second loop
 // (polutils.js:51-53) ignores it and overwrites the table at offset 0 (harmless there because everyRow is boundary 0).
 "use strict";
-const { addon, isFlat, isDev, download } = require("./native.js");
+const { addon, isFlat, isDev, download, DevBuffer } = require("./native.js");
 
 function setRange(buffTo, offset, tmp) {
     if (isFlat(buffTo)) buffTo.set(tmp, offset); else buffTo.set(tmp, offset);
@@ -117,3 +117,35 @@ const calculateZPermutationDev = (f, t, alpha, beta, gamma, out, n, stream) => z
 const calculateZConnection = (aCols, sCols, x, gamma, delta, deltaKs, out, n) => zConnection(false, aCols, sCols, x, gamma, delta, deltaKs, out, n);
 const calculateZConnectionDev = (aCols, sCols, x, gamma, delta, deltaKs, out, n, stream) => zConnection(true, aCols, sCols, x, gamma, delta, deltaKs, out, n, stream);
 Object.assign(module.exports, { calculateZPermutation, calculateZPermutationDev, calculateZConnection, calculateZConnectionDev });
+
+
+// The plookup argument of pil1 from the trace columns (js/pil_checks.js plookupFold / plookupProduct; include/pil2gl.h states it).
+// f, t = { buf, stride, cols, sel } with their own column counts; hDim = words of an h element (3, or 1 when kF = kT = 1 and there is no selT).
+//   calculateH1H2Plookup(f, t, alpha, beta, n, hDim)        host words -> [h1, h2], dense BigUint64Arrays of n hDim words: the fold into
+//                                                           scratch, then calculateH1H2's device call; a value of f that t lacks throws its error
+//   calculateH1H2PlookupDev(f, t, alpha, beta, n, hDim, stream)   DevBuffers -> [h1, h2], new dense DevBuffers (the caller frees them)
+//   calculateZPlookup(f, t, h1, h2, alpha, beta, gamma, delta, out, n, hDim)   h1, h2, out = { buf, stride, col }; writes z in place -> out
+//   calculateZPlookupDev(.., hDim, stream)                  the same on DevBuffers; only enqueues
+function h1h2Plookup(dev, f, t, alpha, beta, n, hDim, stream) {
+    const pc = require("./pil_checks.js"), dim = hDim === undefined ? 3 : hDim, opts = { bn128: false, hDim: dim, stream };
+    if (!dev) {
+        const F = new BigUint64Array(n * dim), T = new BigUint64Array(n * dim);
+        pc.plookupFold(f, t, alpha, beta, { buf: F, stride: dim, col: 0 }, { buf: T, stride: dim, col: 0 }, n, opts);
+        return onDevice([F, T], [n * dim, n * dim], ([df, dt], [d1, d2]) => addon.h1h2Dev(df, dt, n, dim, d1, d2));
+    }
+    const bufs = [0, 1, 2, 3].map(() => new DevBuffer(n * dim));
+    try {
+        pc.plookupFoldDev(f, t, alpha, beta, { buf: bufs[0], stride: dim, col: 0 }, { buf: bufs[1], stride: dim, col: 0 }, n, opts);
+        addon.h1h2Dev(bufs[0].ptr, bufs[1].ptr, n, dim, bufs[2].ptr, bufs[3].ptr, stream);
+    } catch (e) { bufs[2].free(); bufs[3].free(); throw e; } finally { bufs[0].free(); bufs[1].free(); }
+    return [bufs[2], bufs[3]];
+}
+function zPlookup(dev, f, t, h1, h2, alpha, beta, gamma, delta, out, n, hDim, stream) {
+    const pc = require("./pil_checks.js");
+    return (dev ? pc.plookupProductDev : pc.plookupProduct)(f, t, h1, h2, alpha, beta, gamma, delta, out, n, { bn128: false, hDim: hDim === undefined ? 3 : hDim, stream });
+}
+const calculateH1H2Plookup = (f, t, alpha, beta, n, hDim) => h1h2Plookup(false, f, t, alpha, beta, n, hDim);
+const calculateH1H2PlookupDev = (f, t, alpha, beta, n, hDim, stream) => h1h2Plookup(true, f, t, alpha, beta, n, hDim, stream);
+const calculateZPlookup = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, hDim) => zPlookup(false, f, t, h1, h2, alpha, beta, gamma, delta, out, n, hDim);
+const calculateZPlookupDev = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, hDim, stream) => zPlookup(true, f, t, h1, h2, alpha, beta, gamma, delta, out, n, hDim, stream);
+Object.assign(module.exports, { calculateH1H2Plookup, calculateH1H2PlookupDev, calculateZPlookup, calculateZPlookupDev });

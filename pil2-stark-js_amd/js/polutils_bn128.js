@@ -15,7 +15,7 @@
 // overlap nothing otherwise.
 // A zero denominator inverts to zero and stays out of every running product (include/pil2gl.h): its ratio is 0.
 "use strict";
-const { addon, isDev } = require("./native.js");
+const { addon, isDev, DevBuffer } = require("./native.js");
 const { scope, input, output } = require("./bn128_stage.js").native();
 
 function pack(col, what) {
@@ -144,4 +144,35 @@ const calculateZPermutationDev = (f, t, alpha, beta, gamma, out, n, stream) => z
 const calculateZConnection = (aCols, sCols, x, gamma, delta, deltaKs, out, n) => zConnection(false, aCols, sCols, x, gamma, delta, deltaKs, out, n);
 const calculateZConnectionDev = (aCols, sCols, x, gamma, delta, deltaKs, out, n, stream) => zConnection(true, aCols, sCols, x, gamma, delta, deltaKs, out, n, stream);
 
-module.exports = { calculateZPermutation, calculateZPermutationDev, calculateZConnection, calculateZConnectionDev, calculateZ, calculateS, calculateSCol, batchInverse, calculateH1H2, calculateZDev, calculateSDev, calculateSColDev, batchInverseDev, calculateH1H2Dev, lastElement };
+// The plookup argument of pil1 from the trace columns (js/pil_checks.js plookupFold / plookupProduct; include/pil2gl.h states it).
+// f, t = { buf, stride, cols, sel } with their own column counts, strides and columns in elements.
+//   calculateH1H2Plookup(f, t, alpha, beta, n)            host words -> [h1, h2] as calculateH1H2 returns them (arrays of Uint8Array(32)): the
+//                                                         fold into scratch, then calculateH1H2; a value of f that t lacks throws its message
+//   calculateH1H2PlookupDev(f, t, alpha, beta, n, stream) DevBuffers -> [h1, h2], the two columns { buf, stride: 2, offset } of ONE new DevBuffer
+//                                                         (the caller frees h1.buf), through calculateH1H2Dev
+//   calculateZPlookup(f, t, h1, h2, alpha, beta, gamma, delta, out, n)   h1, h2, out = { buf, stride, col }; writes z in place -> out
+//   calculateZPlookupDev(.., n, stream)                   the same on DevBuffers; only enqueues
+function h1h2Plookup(dev, f, t, alpha, beta, n, stream) {
+    const pc = require("./pil_checks.js"), opts = { bn128: true, stream };
+    if (!dev) {
+        const FT = new BigUint64Array(8 * n), bytes = new Uint8Array(FT.buffer);
+        pc.plookupFold(f, t, alpha, beta, { buf: FT, stride: 2, col: 0 }, { buf: FT, stride: 2, col: 1 }, n, opts);
+        const col = (c) => Array.from({ length: n }, (_, i) => bytes.slice(64 * i + 32 * c, 64 * i + 32 * c + 32));
+        return calculateH1H2(null, col(0), col(1));
+    }
+    const FT = new DevBuffer(8 * n), H = new DevBuffer(8 * n);
+    try {
+        pc.plookupFoldDev(f, t, alpha, beta, { buf: FT, stride: 2, col: 0 }, { buf: FT, stride: 2, col: 1 }, n, opts);
+        return calculateH1H2Dev({ buf: FT, stride: 2, offset: 0 }, { buf: FT, stride: 2, offset: 1 }, n, { buf: H, stride: 2, offset: 0 }, { buf: H, stride: 2, offset: 1 }, stream);
+    } catch (e) { H.free(); throw e; } finally { FT.free(); }
+}
+function zPlookup(dev, f, t, h1, h2, alpha, beta, gamma, delta, out, n, stream) {
+    const pc = require("./pil_checks.js");
+    return (dev ? pc.plookupProductDev : pc.plookupProduct)(f, t, h1, h2, alpha, beta, gamma, delta, out, n, { bn128: true, stream });
+}
+const calculateH1H2Plookup = (f, t, alpha, beta, n) => h1h2Plookup(false, f, t, alpha, beta, n);
+const calculateH1H2PlookupDev = (f, t, alpha, beta, n, stream) => h1h2Plookup(true, f, t, alpha, beta, n, stream);
+const calculateZPlookup = (f, t, h1, h2, alpha, beta, gamma, delta, out, n) => zPlookup(false, f, t, h1, h2, alpha, beta, gamma, delta, out, n);
+const calculateZPlookupDev = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, stream) => zPlookup(true, f, t, h1, h2, alpha, beta, gamma, delta, out, n, stream);
+
+module.exports = { calculateH1H2Plookup, calculateH1H2PlookupDev, calculateZPlookup, calculateZPlookupDev, calculateZPermutation, calculateZPermutationDev, calculateZConnection, calculateZConnectionDev, calculateZ, calculateS, calculateSCol, batchInverse, calculateH1H2, calculateZDev, calculateSDev, calculateSColDev, batchInverseDev, calculateH1H2Dev, lastElement };

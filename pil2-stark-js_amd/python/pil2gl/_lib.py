@@ -282,6 +282,15 @@ SIGNATURES = {
     "pil2gl_bn128_grand_prod_dev": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64, vp]),
     "pil2gl_grand_prod": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64]),
     "pil2gl_bn128_grand_prod": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64]),
+    "pil2gl_plookup_plan": (_I, [_U64, _U64, _U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_plookup_fold_dev": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), _U64, vp, vp, _U32, vp, _U64, _U64, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_plookup_fold": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), _U64, vp, vp, _U32, vp, _U64, _U64, vp, _U64, _U64, _U64]),
+    "pil2gl_plookup_prod_dev": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), _U64, vp, _U64, _U64, vp, _U64, _U64, _U32, vp, vp, vp, vp, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_plookup_prod": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), _U64, vp, _U64, _U64, vp, _U64, _U64, _U32, vp, vp, vp, vp, vp, _U64, _U64, _U64]),
+    "pil2gl_bn128_plookup_fold_dev": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), _U64, vp, vp, _U32, vp, _U64, _U64, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_bn128_plookup_fold": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), _U64, vp, vp, _U32, vp, _U64, _U64, vp, _U64, _U64, _U64]),
+    "pil2gl_bn128_plookup_prod_dev": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), _U64, vp, _U64, _U64, vp, _U64, _U64, _U32, vp, vp, vp, vp, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_bn128_plookup_prod": (_I, [C.POINTER(TupleSide), _U64, C.POINTER(TupleSide), _U64, vp, _U64, _U64, vp, _U64, _U64, _U32, vp, vp, vp, vp, vp, _U64, _U64, _U64]),
     "pil2gl_selftest_field":(_I, [vp, vp, _U64, vp, vp, vp]),
     "pil2gl_selftest_ext": (_I, [vp, vp, _U64, vp, vp]),
     "pil2gl_selftest_products": (_I, [vp, vp, _U64, vp, vp, vp]),

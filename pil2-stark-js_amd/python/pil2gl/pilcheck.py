@@ -14,7 +14,8 @@ returns the library's five words (kind, row, partner, cntF, cntT) -- include/pil
 The column that PROVES a lookup in pil2, the multiplicities of its grand sum (csrc/lookup_mult.hip), is lookup_mult / lookup_mult_dev at the
 end of this module, then its form for a range check, which needs no table column (range_mult / range_mult_dev, csrc/range_mult.hip), and
 after them the grand sum that consumes the column (logup_sum / logup_sum_dev) and the grand product of a permutation or a connection
-(grand_prod / grand_prod_dev, with perm_prod and conn_prod as spellings of the two identities).
+(grand_prod / grand_prod_dev, with perm_prod and conn_prod as spellings of the two identities), and last pil1's plookup argument
+(plookup_fold, plookup_h1h2, plookup_prod and their _dev forms).
 """
 import ctypes as C
 
@@ -400,3 +401,125 @@ def conn_prod(a_cols, S_cols, x, ks, gamma, delta, out, n, field="gl"):
 
 def conn_prod_dev(a_cols, S_cols, x, ks, gamma, delta, out, n, field="gl"):
     return grand_prod_dev(conn_terms(a_cols, S_cols, x, ks, delta, field), gamma, gamma, gamma, out, n, field)
+
+
+# ---- plookup: pil1's lookup argument from the trace columns, h1 and h2 (csrc/plookup_plan.h; include/pil2gl.h states it) ----
+#     F, T = plookup_fold_dev((cm1, [7, 3], (cm1, 9)), (const, [4, 5], (const, 10)), alpha, beta, (work, 0), (work, 3), n)
+#     h1, h2 = plookup_h1h2_dev((cm1, [7, 3], (cm1, 9)), (const, [4, 5], (const, 10)), alpha, beta, n)
+#     plookup_prod_dev(f, t, (cm2, 0), (cm2, 3), alpha, beta, gamma, delta, (cm3, 0), n)
+# f and t are sides (matrix, cols[, sel[, stride]]) with their own column counts; h1, h2 and the outputs are columns (matrix, col) or
+# (matrix, col, stride) of h_dim words an element (Goldilocks 1 or 3; Fr one element); the challenges are 3 words of a cubic-extension
+# element, or 4 Montgomery words.  Written in place; z[n-1] is the hint's result.
+def plookup_plan(n, k_f=1, k_t=1, field="gl"):
+    """pil2gl_plookup_plan (host-only): the product call's launch geometry, its launches and its working bytes"""
+    names = ("threads", "items", "blocks", "launches", "depth", "outWidth")
+    return _plan("pil2gl_plookup_plan", (n, k_f, k_t, _WORDS[field]), names, "workBytes")
+
+
+def _plookup_sides(f, t, n, words, dev):
+    sides, ks, keep = _sides([f, t], ["f", "t"], 3, n, words, dev)
+    return [C.pointer(sides[0]), ks[0], C.pointer(sides[1]), ks[1]], (sides, keep)
+
+
+def _challenges(chs, names, words):
+    cw = 3 if words == 1 else 4
+    ch = [np.ascontiguousarray(c, np.uint64).reshape(-1) for c in chs]
+    if any(c.size != cw for c in ch):
+        raise Pil2glError("%s are %d words each" % (names, cw))
+    return ch, [C.c_void_p(c.ctypes.data) for c in ch]
+
+
+def _plookup_fold(dev, f, t, alpha, beta, out_f, out_t, n, field, h_dim):
+    words = _WORDS[field]
+    sides, keep = _plookup_sides(f, t, n, words, dev)
+    ch, chp = _challenges((alpha, beta), "alpha and beta", words)
+    width = h_dim if words == 1 else 1
+    cols = _column(out_f, "outF", width, n, words, dev)[1] + _column(out_t, "outT", width, n, words, dev)[1]
+    name = "pil2gl_plookup_fold" if words == 1 else "pil2gl_bn128_plookup_fold"
+    args = sides + chp + [h_dim] + cols + [n]
+    if dev:
+        call(name + "_dev", *args, _stream())
+    else:
+        call(name, *args)
+    return out_f[0], out_t[0]
+
+
+def plookup_fold(f, t, alpha, beta, out_f, out_t, n, field="gl", h_dim=None):
+    """the two kept expressions F and T of a plookup (its stage-1 half): host matrices; the two columns are written in place -> their
+    matrices.  h_dim defaults to 3 over Goldilocks and is 1 over Fr"""
+    return _plookup_fold(False, f, t, alpha, beta, out_f, out_t, n, field, (3 if field == "gl" else 1) if h_dim is None else h_dim)
+
+
+def plookup_fold_dev(f, t, alpha, beta, out_f, out_t, n, field="gl", h_dim=None):
+    """plookup_fold on device tensors; only enqueues on the current stream"""
+    return _plookup_fold(True, f, t, alpha, beta, out_f, out_t, n, field, (3 if field == "gl" else 1) if h_dim is None else h_dim)
+
+
+def _plookup_prod(dev, f, t, h1, h2, alpha, beta, gamma, delta, out, n, field, h_dim):
+    words = _WORDS[field]
+    sides, keep = _plookup_sides(f, t, n, words, dev)
+    ch, chp = _challenges((alpha, beta, gamma, delta), "alpha, beta, gamma and delta", words)
+    width = h_dim if words == 1 else 1
+    hcols = []
+    for h, what in ((h1, "h1"), (h2, "h2")):
+        h = tuple(h) + (None,)
+        hm, hs = _side(h[0], [h[1] + width - 1], h[2], None, n, words, dev, what)[:2]
+        keep = (keep, hm)
+        hcols += [_dev_ptr(dev)(hm), hs, h[1]]
+    om, col = _column(out, "out", 3 if words == 1 else 1, n, words, dev)
+    name = "pil2gl_plookup_prod" if words == 1 else "pil2gl_bn128_plookup_prod"
+    args = sides + hcols + [h_dim] + chp + col + [n]
+    if dev:
+        call(name + "_dev", *args, _stream())
+    else:
+        call(name, *args)
+    return out[0]
+
+
+def plookup_prod(f, t, h1, h2, alpha, beta, gamma, delta, out, n, field="gl", h_dim=None):
+    """the grand-product column z of a plookup (its stage-2 half) from f, t, h1 and h2: host matrices; out's column is written in place
+    -> out's matrix.  h_dim defaults to 3 over Goldilocks and is 1 over Fr"""
+    return _plookup_prod(False, f, t, h1, h2, alpha, beta, gamma, delta, out, n, field, (3 if field == "gl" else 1) if h_dim is None else h_dim)
+
+
+def plookup_prod_dev(f, t, h1, h2, alpha, beta, gamma, delta, out, n, field="gl", h_dim=None):
+    """plookup_prod on device tensors, e.g. columns of the stage buffers with z spare columns of one of them; only enqueues on the current
+    stream"""
+    return _plookup_prod(True, f, t, h1, h2, alpha, beta, gamma, delta, out, n, field, (3 if field == "gl" else 1) if h_dim is None else h_dim)
+
+
+def _plookup_h1h2(dev, f, t, alpha, beta, n, field, h_dim):
+    """fold into scratch, then the field's own h1h2: a value of F that is not in T comes back as that call reports it"""
+    import pil2gl
+    from . import bn128
+    if field == "gl":
+        h_dim = 3 if h_dim is None else h_dim
+        if dev:
+            like = f[0]
+            F = torch.empty(n * h_dim, dtype=torch.int64, device=like.device)
+            T = torch.empty_like(F)
+            _plookup_fold(True, f, t, alpha, beta, (F, 0, h_dim), (T, 0, h_dim), n, field, h_dim)
+            return pil2gl.calculateH1H2(F, T, h_dim)
+        F = np.zeros((n, h_dim), np.uint64)
+        T = np.zeros((n, h_dim), np.uint64)
+        _plookup_fold(False, f, t, alpha, beta, (F, 0), (T, 0), n, field, h_dim)
+        h1, h2 = pil2gl.calculateH1H2(torch.from_numpy(F.view(np.int64).reshape(-1)).cuda(), torch.from_numpy(T.view(np.int64).reshape(-1)).cuda(), h_dim)
+        return tuple(h.cpu().numpy().view(np.uint64).reshape(n, h_dim) for h in (h1, h2))
+    if dev:
+        FT = torch.empty((n, 2, 4), dtype=torch.int64, device=f[0].device)
+    else:
+        FT = np.zeros((n, 2, 4), np.uint64)
+    _plookup_fold(dev, f, t, alpha, beta, (FT, 0), (FT, 1), n, field, 1)
+    flat = FT.reshape(-1)
+    return bn128.h1h2(flat, flat[4:], n, 2, 2)
+
+
+def plookup_h1h2(f, t, alpha, beta, n, field="gl", h_dim=None):
+    """h1 and h2 of a plookup from the trace columns, host matrices: plookup_fold into scratch, then calculateH1H2 of the field (over
+    Goldilocks that one is resident: F and T go up for it and h1, h2 come back) -> (h1, h2) as new arrays"""
+    return _plookup_h1h2(False, f, t, alpha, beta, n, field, h_dim)
+
+
+def plookup_h1h2_dev(f, t, alpha, beta, n, field="gl", h_dim=None):
+    """plookup_h1h2 on device tensors -> (h1, h2) as new dense device columns; blocks as the field's h1h2 does, for the missing row"""
+    return _plookup_h1h2(True, f, t, alpha, beta, n, field, h_dim)
