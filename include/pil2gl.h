@@ -24,7 +24,7 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; grand_prod and bn128_grand_prod; plookup_fold, plookup_prod and their bn128_ twins; land_rows with a null hostFirstBad;
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; range_sum and bn128_range_sum; grand_prod and bn128_grand_prod; plookup_fold, plookup_prod and their bn128_ twins; land_rows with a null hostFirstBad;
  *      wtns_adds and bn128_wtns_adds, wtns_gather and bn128_wtns_gather with a null hostFirstBad, conn_pols and bn128_conn_pols with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, logup_sum_plan, grand_prod_plan, plookup_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, logup_sum_plan, range_sum_plan, grand_prod_plan, plookup_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -1115,6 +1115,58 @@ int pil2gl_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const 
                      uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
 int pil2gl_bn128_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const uint64_t *hostAlpha, const uint64_t *hostBeta,
                            uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
+
+/* ---- range-check grand sum: the logUp column s of range checks from f, m and the ranges as NUMBERS (csrc/range_sum_plan.h, hints.hip, bn_scan.hip) ----
+ * range_mult above takes no t; with logup_sum the argument as a whole still takes one, as the tuple column of m's term.  This block is
+ * logup_sum with the table side of a range given as (lo, size, row0): no t column is made, uploaded or read.  nF = 0 is the range table's
+ * own AIR in pil2's std library, whose @gsum holds only the -m_r / (t_r + gamma) terms, one per range.  The statement is this header's
+ * own (tests/range_sum_ref.py restates it over Python integers):
+ *   s[i] = s[i-1] + sum_{u < nF} coef_u w_u[i] / D_u[i]
+ *                 + sum_{r < nR} coefR_r [row0_r <= i < row0_r + size_r] m_r[i] / E_r[i]            s[-1] = 0,  i < n
+ *   D_u[i]  the block above's, of a pil2gl_logup_term: its own k in 1 .. 16, the sel column as numerator, busId, + beta
+ *   E_r[i] = field(lo_r + (i - row0_r)) alpha + busId_r + beta
+ *   n <= 2^28 rows; 0 <= nF <= 8, 1 <= nR <= 8, nF + nR <= 9.  One range is a pil2gl_range_term: the column mCol of the matrix (m, mStride)
+ *   of elemWords-word elements; lo, a SIGNED 64-bit integer, size, 1 .. 2^28, and row0 with row0 + size <= n: field(lo + j) is range_mult's,
+ *   lo + j mod p|r; coef (usually -1) and busId as in pil2gl_logup_term.
+ *   Window: outside rows row0 .. row0 + size - 1 a range adds 0 and m is NOT READ there: whatever those rows of m hold does not change s.
+ *   Inside it m_r[i] counts as its field value by the rules above (Goldilocks words in [p, 2^64) mod p, any Fr pattern mod r).
+ *   Zeros: a zero E_r[i] or D_u[i] adds 0 at that row and spoils no other term or row.
+ *   out, outStride, outCol, alpha and beta: the block above's (three words a row over Goldilocks, one element over Fr).
+ * Equivalence: s is word for word what pil2gl_[bn128_]logup_sum gives when each range is replaced by a k = 1 term with the tuple column
+ * t_r[i] = field(lo_r + clamp(i - row0_r, 0, size_r - 1)), the numerator column m_r zeroed outside the window, the same coef and busId.
+ * pil2gl_range_sum_plan: host-only, no device.  outInfo and *workBytes are logup_sum_plan's, with its values for the same n: the working
+ * memory grows with neither nF nor nR.  PIL2GL_EINVAL: n > 2^28, nR outside 1 .. 8, nF > 8, nF + nR > 9, elemWords not 1 or 4.
+ * pil2gl_[bn128_]range_sum_dev: hostTerms (nF entries; may be NULL when nF = 0) and hostRanges (nR entries) are HOST pointers; side.base,
+ * side.sel and m are device pointers, 16-byte aligned, only read.  out = device, 16-byte aligned; its aliasing rule is the block above's
+ * with every m_r counted as a read column of its matrix (all n rows of it): s as spare columns of m's matrix is the normal case.  The call
+ * only ENQUEUES on the caller's stream: both tables travel as the kernel argument, nothing is copied (working slots as the block above).
+ * PIL2GL_EINVAL, before any device call: what the plan refuses; everything the block above refuses for the f terms and out; size outside
+ * 1 .. 2^28; row0 + size > n (n > 0); mCol >= mStride, a stride >= 2^32 or n mStride > 2^58 elements; a null or misaligned m; a
+ * non-canonical Goldilocks coef or busId of a range; null hostRanges, or null hostTerms with nF > 0; an out that breaks the aliasing rule.
+ * n = 0 is PIL2GL_OK, touches nothing and needs no device.
+ * pil2gl_[bn128_]range_sum: host pointers throughout; each matrix staged up to the last element touched (an m up to its window's last
+ * row), every part on 16 bytes, out's matrix goes up as it is and comes back with the column written.  Without a device the compute calls
+ * return PIL2GL_ENODEV. */
+typedef struct pil2gl_range_term {
+    const uint64_t *m;                   /* the multiplicities: element of row i at m[(i mStride + mCol) elemWords] */
+    uint64_t mStride, mCol;
+    int64_t lo;                          /* the range's first value, signed */
+    uint64_t size;                       /* its values, 1 .. 2^28 */
+    uint64_t row0;                       /* the row of m that counts lo; row0 + size <= n */
+    uint64_t coef[4];                    /* Goldilocks: word 0, canonical.  Fr: 4 Montgomery words */
+    uint64_t busId[4];
+} pil2gl_range_term;
+int pil2gl_range_sum_plan(uint64_t n, uint64_t nF, uint64_t nR, uint32_t elemWords, uint32_t *outInfo /* [6] */, uint64_t *workBytes);
+int pil2gl_range_sum_dev(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR,
+                         const uint64_t *hostAlpha /* [3] */, const uint64_t *hostBeta /* [3] */, uint64_t *out, uint64_t outStride, uint64_t outCol,
+                         uint64_t n, void *stream);
+int pil2gl_bn128_range_sum_dev(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR,
+                               const uint64_t *hostAlpha /* [4] */, const uint64_t *hostBeta /* [4] */, uint64_t *out, uint64_t outStride,
+                               uint64_t outCol, uint64_t n, void *stream);
+int pil2gl_range_sum(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR, const uint64_t *hostAlpha,
+                     const uint64_t *hostBeta, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
+int pil2gl_bn128_range_sum(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR,
+                           const uint64_t *hostAlpha, const uint64_t *hostBeta, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
 
 /* ---- grand product: the column z of a permutation or a connection from the trace columns (csrc/grand_prod_plan.h, hints.hip, bn_scan.hip) ----
  * The sibling of the block above for the `gprod` hints (grandProductPermutation.js:121-126, grandProductConnection.js:131-136): z in one

@@ -867,6 +867,82 @@ FN(LogupSum) {
     return mk_undefined(env);
 }
 
+// ---- range-check grand sum: the logUp column s from f, m and the ranges as numbers (csrc/range_sum_plan.h; js/pil_checks.js) ----
+FN(RangeSumPlan) {         // (n, nF, nR, elemWords) -> { threads, items, blocks, launches, depth, outWidth, workBytes }
+    Args a(env, info); uint64_t n = a.u64(0), nF = a.u64(1), nR = a.u64(2); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
+    uint32_t out[6]; uint64_t bytes = 0;
+    P2(env, pil2gl_range_sum_plan(n, nF, nR, ew, out, &bytes));
+    static const char *const names[6] = { "threads", "items", "blocks", "launches", "depth", "outWidth" };
+    return plan_object(env, names, out, "workBytes", bytes);
+}
+FN(RangeTermLayout) {      // -> sizeof and offsetof of pil2gl_range_term as this addon was compiled
+    static const char *names[9] = { "size", "m", "mStride", "mCol", "lo", "rangeSize", "row0", "coef", "busId" };
+    const size_t at[9] = { sizeof(pil2gl_range_term), offsetof(pil2gl_range_term, m), offsetof(pil2gl_range_term, mStride), offsetof(pil2gl_range_term, mCol),
+                           offsetof(pil2gl_range_term, lo), offsetof(pil2gl_range_term, size), offsetof(pil2gl_range_term, row0), offsetof(pil2gl_range_term, coef),
+                           offsetof(pil2gl_range_term, busId) };
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 9; i++) { napi_create_uint32(env, (uint32_t)at[i], &v); napi_set_named_property(env, o, names[i], v); }
+    return o;
+}
+// A call's description, one BigUint64Array: [0] n, [1] nF, [2] nR, [3] out, [4] outStride, [5] outCol, [6..9] alpha, [10..13] beta (three
+// words used over Goldilocks), then nF terms of logupSum's 14 words, then nR ranges of 14 words -- m, mStride, mCol, lo as a
+// two's-complement word, size, row0, coef[4], busId[4] -- then 16 column slots an f term, the first k used.  The pointer words are device
+// addresses for rangeSumDev and are not read by rangeSum, which takes the host matrices as an array of its own.
+enum { SD_N, SD_NF, SD_NR, SD_OUT, SD_OUT_STRIDE, SD_OUT_COL, SD_ALPHA, SD_BETA = SD_ALPHA + 4, SD_TERMS = SD_BETA + 4, SD_TERM_WORDS = 14, SD_COL_SLOTS = 16 };
+struct RangeSumDesc { uint64_t *d; uint64_t n, nF, nR; pil2gl_logup_term term[8]; pil2gl_range_term range[8]; };
+static bool range_sum_desc(Args &a, size_t i, RangeSumDesc &L) {
+    uint64_t len = 0; L.d = a.arr(i, SD_TERMS, &len);
+    if (!a.ok) return false;
+    L.n = L.d[SD_N]; L.nF = L.d[SD_NF]; L.nR = L.d[SD_NR];
+    if (L.nF > 8 || L.nR < 1 || L.nR > 8 || len < SD_TERMS + (L.nF + L.nR) * SD_TERM_WORDS + L.nF * SD_COL_SLOTS)
+        return a.fail("the description holds 14 words, then 0 .. 8 terms and 1 .. 8 ranges of 14 words, then 16 column slots a term");
+    uint64_t *cols = L.d + SD_TERMS + (L.nF + L.nR) * SD_TERM_WORDS;
+    for (uint64_t u = 0; u < L.nF; u++) {
+        const uint64_t *w = L.d + SD_TERMS + u * SD_TERM_WORDS;
+        pil2gl_logup_term &t = L.term[u];
+        t.side = pil2gl_tuple_side{ (const uint64_t *)(uintptr_t)w[0], w[1], cols + u * SD_COL_SLOTS, (const uint64_t *)(uintptr_t)w[3], w[4], w[5] };
+        t.k = w[2];
+        for (int c = 0; c < 4; c++) { t.coef[c] = w[6 + c]; t.busId[c] = w[10 + c]; }
+    }
+    for (uint64_t r = 0; r < L.nR; r++) {
+        const uint64_t *w = L.d + SD_TERMS + (L.nF + r) * SD_TERM_WORDS;
+        pil2gl_range_term &t = L.range[r];
+        t.m = (const uint64_t *)(uintptr_t)w[0]; t.mStride = w[1]; t.mCol = w[2]; t.lo = (int64_t)w[3]; t.size = w[4]; t.row0 = w[5];
+        for (int c = 0; c < 4; c++) { t.coef[c] = w[6 + c]; t.busId[c] = w[10 + c]; }
+    }
+    return true;
+}
+FN(RangeSumDev) {          // (description, elemWords[, stream]): only enqueues
+    Args a(env, info); RangeSumDesc L; if (!range_sum_desc(a, 0, L)) return nullptr;
+    uint32_t ew = (uint32_t)a.u64(1); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_range_sum_dev : pil2gl_range_sum_dev)(L.term, L.nF, L.range, L.nR, L.d + SD_ALPHA, L.d + SD_BETA, (uint64_t *)(uintptr_t)L.d[SD_OUT],
+                                                                          L.d[SD_OUT_STRIDE], L.d[SD_OUT_COL], L.n, a.stream(2)));
+    return mk_undefined(env);
+}
+// (description, matrices, elemWords): matrices = an Array of BigUint64Array, [2 u] the matrix of term u, [2 u + 1] its numerator's or null,
+// [2 (nF + r)] the m matrix of range r, [2 (nF + r) + 1] null, [2 (nF + nR)] out's matrix, which is written in place
+FN(RangeSum) {
+    Args a(env, info); RangeSumDesc L; if (!range_sum_desc(a, 0, L)) return nullptr;
+    uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
+    if (ew != 1 && ew != 4) { a.fail("elemWords is 1 or 4"); return nullptr; }
+    pil2gl_tuple_side mSide[8] = {};
+    pil2gl_tuple_side *sides[16]; uint64_t ks[16];
+    for (uint64_t u = 0; u < L.nF; u++) {
+        sides[u] = &L.term[u].side; ks[u] = L.term[u].k;
+        if (ks[u] < 1 || ks[u] > 16) { a.fail("k must be 1 .. 16 columns"); return nullptr; }
+    }
+    for (uint64_t r = 0; r < L.nR; r++) {            // an m column as a side of one column without a selector
+        mSide[r].stride = L.range[r].mStride; mSide[r].hostCols = &L.range[r].mCol;
+        sides[L.nF + r] = &mSide[r]; ks[L.nF + r] = 1;
+    }
+    uint64_t *ho = host_matrices(a, sides, ks, L.nF + L.nR, L.n, L.d[SD_OUT_STRIDE], L.d[SD_OUT_COL] + (ew == 1 ? 2 : 0), ew,
+                                 "expected a matrix and a numerator's matrix or null for every term, m's matrix and null for every range, then out's matrix");
+    if (!a.ok) return nullptr;
+    for (uint64_t r = 0; r < L.nR; r++) L.range[r].m = mSide[r].base;
+    P2(env, (ew == 4 ? pil2gl_bn128_range_sum : pil2gl_range_sum)(L.term, L.nF, L.range, L.nR, L.d + SD_ALPHA, L.d + SD_BETA, ho, L.d[SD_OUT_STRIDE], L.d[SD_OUT_COL], L.n));
+    return mk_undefined(env);
+}
+
 // ---- grand product: the column z of a permutation or a connection (csrc/grand_prod_plan.h; js/pil_checks.js) ----
 FN(GrandProdPlan) {        // (n, nTerms, sumK, elemWords) -> { threads, items, blocks, launches, depth, outWidth, workBytes }
     Args a(env, info); uint64_t n = a.u64(0), nT = a.u64(1), sumK = a.u64(2); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
@@ -1210,6 +1286,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "lookupMultPlan", LookupMultPlan }, { "lookupMultDev", LookupMultDev }, { "lookupMult", LookupMult }, { "lookupMultProbe", LookupMultProbe },
         { "rangeMultPlan", RangeMultPlan }, { "rangeMultDev", RangeMultDev }, { "rangeMult", RangeMult },
         { "logupSumPlan", LogupSumPlan }, { "logupTermLayout", LogupTermLayout }, { "logupSumDev", LogupSumDev }, { "logupSum", LogupSum },
+        { "rangeSumPlan", RangeSumPlan }, { "rangeTermLayout", RangeTermLayout }, { "rangeSumDev", RangeSumDev }, { "rangeSum", RangeSum },
         { "grandProdPlan", GrandProdPlan }, { "grandProdTermLayout", GrandProdTermLayout }, { "grandProdDev", GrandProdDev }, { "grandProd", GrandProd },
         { "plookupPlan", PlookupPlan }, { "plookupFoldDev", PlookupFoldDev }, { "plookupFold", PlookupFold }, { "plookupProdDev", PlookupProdDev }, { "plookupProd", PlookupProd },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },

@@ -7,6 +7,7 @@
 //     gsum            s[i] = s[i - 1] + num / den[i],  s[0] = num / den[0]          (num: ONE element, on the host)
 //     gsum_col        s[i] = s[i - 1] + num[i] / den[i]                              (num: a column, as gprod's)
 //     logup_sum       the lookup grand sum of include/pil2gl.h: gsum_col over a row's terms folded into one fraction (near the end of this file)
+//     range_sum       that sum with the table side of a range check given as numbers, no t column (behind it)
 //     grand_prod      the grand product of a permutation or a connection: gprod over a row's terms multiplied into N and D (near the end)
 //     plookup         pil1's plookup argument: the fold of F and T, and gprod over a row's num and den made from f, t, h1, h2 (at the end)
 //
@@ -42,6 +43,7 @@
 #include "bn_params.h"
 #include "bn_scan_plan.h"
 #include "logup_sum_plan.h"
+#include "range_sum_plan.h"
 #include "grand_prod_plan.h"
 #include "plookup_plan.h"
 #include "tuple_side.cuh"
@@ -401,24 +403,34 @@ struct FrLogupJob {
     FrField::Mem *D, *N;                             // dense, n elements each
 };
 
+// one f term of row i folded into the row's fraction N / D
+__device__ __forceinline__ void fr_logup_fold(const FrLogupTerm &T, u64 i, const FrE &alpha, const FrE &beta, FrE &N, FrE &D) {
+    FrE d = tupleside::elem_of(T.s, i, 0);
+    for (u32 j = 1; j < T.k; j++) d = FrField::add(FrField::mul(d, alpha), tupleside::elem_of(T.s, i, j));
+    d = FrField::add(FrField::add(FrField::mul(d, alpha), FrField::reduce(T.bus)), beta);
+    if (bn::is_zero(d.v)) return;                     // a zero D_u: the term adds 0 and is left out of the product
+    FrE c = FrField::reduce(T.coef);
+    if (T.s.sel) c = FrField::mul(FrField::load(T.s.sel, i * T.s.selStride + T.s.selCol), c);
+    N = FrField::add(FrField::mul(N, d), FrField::mul(D, c));
+    D = FrField::mul(D, d);
+}
+
 __global__ void __launch_bounds__(smapplan::THREADS) bn_logup_compress_kernel(const FrLogupJob J) {
     const FrE alpha = FrField::reduce(J.alpha), beta = FrField::reduce(J.beta);
     for (u64 i = (u64)blockIdx.x * smapplan::THREADS + threadIdx.x; i < J.n; i += (u64)gridDim.x * smapplan::THREADS) {
         FrE N{}, D = J.one;
-        for (u32 u = 0; u < J.nTerms; u++) {
-            const FrLogupTerm &T = J.t[u];
-            FrE d = tupleside::elem_of(T.s, i, 0);
-            for (u32 j = 1; j < T.k; j++) d = FrField::add(FrField::mul(d, alpha), tupleside::elem_of(T.s, i, j));
-            d = FrField::add(FrField::add(FrField::mul(d, alpha), FrField::reduce(T.bus)), beta);
-            if (bn::is_zero(d.v)) continue;           // a zero D_u: the term adds 0 and is left out of the product
-            FrE c = FrField::reduce(T.coef);
-            if (T.s.sel) c = FrField::mul(FrField::load(T.s.sel, i * T.s.selStride + T.s.selCol), c);
-            N = FrField::add(FrField::mul(N, d), FrField::mul(D, c));
-            D = FrField::mul(D, d);
-        }
+        for (u32 u = 0; u < J.nTerms; u++) fr_logup_fold(J.t[u], i, alpha, beta, N, D);
         FrField::store(J.D, i, D);
         FrField::store(J.N, i, N);
     }
+}
+
+// a term's table entry from the entry's term, its pointers the device's
+void fill_term(FrLogupTerm &T, const pil2gl_logup_term &t) {
+    T.s = tupleside::device_side<FrField>(t.side, (u32)t.k);
+    T.k = (u32)t.k;
+    bnp::bn_limbs(t.coef, T.coef.v);
+    bnp::bn_limbs(t.busId, T.bus.v);
 }
 
 // every launch of a call, on st; the arguments have passed logupplan::check_call() and n > 0, the pointers are the device's
@@ -427,12 +439,7 @@ int bn_logup_launch(const pil2gl_logup_term *terms, u32 nTerms, const u64 *alpha
     u64 *d;
     P2_TRY(scratch(SCR_BN_SCAN, 4 * p.elems + 8 * n, &d));        // the plan's levels, then D and N
     FrLogupJob J{};
-    for (u32 u = 0; u < nTerms; u++) {
-        J.t[u].s = tupleside::device_side<FrField>(terms[u].side, (u32)terms[u].k);
-        J.t[u].k = (u32)terms[u].k;
-        bnp::bn_limbs(terms[u].coef, J.t[u].coef.v);
-        bnp::bn_limbs(terms[u].busId, J.t[u].bus.v);
-    }
+    for (u32 u = 0; u < nTerms; u++) fill_term(J.t[u], terms[u]);
     bnp::bn_limbs(alpha, J.alpha.v); bnp::bn_limbs(beta, J.beta.v); bnp::bn_limbs(bnp::bn_mont_one().w, J.one.v);
     J.nTerms = nTerms; J.n = n;
     J.D = (FrField::Mem *)(d + 4 * p.elems); J.N = J.D + n;
@@ -476,6 +483,121 @@ int pil2gl_bn128_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, 
     u64 *dOut = (u64 *)s.put(hostOut, outWords);
     P2_TRY(s.rc());
     P2_TRY(bn_logup_launch(terms, (u32)nTerms, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0));
+    return s.get(hostOut, dOut, outWords);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The range-check grand sum over Fr (include/pil2gl.h states it): the lookup grand sum above with the table side of a range as numbers,
+//   E_r[i] = field(lo_r + (i - row0_r)) alpha + busId_r + beta   inside the window row0_r <= i < row0_r + size_r, the range adding 0 outside.
+// One compress kernel, a lane a row, writing D and N as bn_logup_compress_kernel does (its f terms through the same fr_logup_fold), then
+// inverse_launch(MODE_COLUMN) and scan_launch<true> as they are.  field(lo + j) is a PLAIN integer mod r: lo mod r from the host (normal
+// form, range_mult_plan.h) plus j, one modular addition.  The host also makes alpha R^2 (h_to_mont of alpha's Montgomery words, canonical
+// for any pattern), so that ONE Montgomery product of it with the plain integer is alpha field(lo + j) in Montgomery form.  Products a
+// range-row inside the window: that one, coef m, three for the fold -- 5, what the block above's k = 1 term takes; what is saved is t's
+// 32-byte load and its reduction.  Outside the window a range costs no product and no load.
+namespace {
+
+struct FrRangeTerm { const FrField::Mem *m; u64 stride, col, row0, end; FrE lo, coef, bus; };      // lo: lo mod r, normal form
+struct FrRangeJob {
+    FrLogupTerm t[rangesumplan::MAX_F];
+    FrRangeTerm r[rangesumplan::MAX_RANGES];
+    FrE alpha, alphaR2, beta, one;                   // alphaR2: alpha 2^512 mod r; one: 1 in Montgomery form
+    u32 nTerms, nRanges;
+    u64 n;
+    FrField::Mem *D, *N;                             // dense, n elements each
+};
+
+__global__ void __launch_bounds__(smapplan::THREADS) bn_range_compress_kernel(const FrRangeJob J) {
+    const FrE alpha = FrField::reduce(J.alpha), beta = FrField::reduce(J.beta);
+    for (u64 i = (u64)blockIdx.x * smapplan::THREADS + threadIdx.x; i < J.n; i += (u64)gridDim.x * smapplan::THREADS) {
+        FrE N{}, D = J.one;
+        for (u32 u = 0; u < J.nTerms; u++) fr_logup_fold(J.t[u], i, alpha, beta, N, D);
+        for (u32 r = 0; r < J.nRanges; r++) {
+            const FrRangeTerm &T = J.r[r];
+            if (i < T.row0 || i >= T.end) continue;   // outside the window: adds 0, m is not read.  end <= n
+            FrE v = { { (u32)(i - T.row0), 0, 0, 0, 0, 0, 0, 0 } };                // j < 2^28
+            v = FrField::add(v, T.lo);                // field(lo + j), both below r
+            FrE d = FrField::add(FrField::add(FrField::mul(J.alphaR2, v), FrField::reduce(T.bus)), beta);
+            if (bn::is_zero(d.v)) continue;           // a zero E_r: the range adds 0 and is left out of the product
+            const FrE c = FrField::mul(FrField::load(T.m, i * T.stride + T.col), FrField::reduce(T.coef));
+            N = FrField::add(FrField::mul(N, d), FrField::mul(D, c));
+            D = FrField::mul(D, d);
+        }
+        FrField::store(J.D, i, D);
+        FrField::store(J.N, i, N);
+    }
+}
+
+// every launch of a call, on st; the arguments have passed rangesumplan::check_call() and n > 0, the pointers are the device's
+int bn_range_sum_launch(const pil2gl_logup_term *terms, u32 nF, const pil2gl_range_term *ranges, u32 nR, const u64 *alpha, const u64 *beta, u64 *out,
+                        u64 outStride, u64 outCol, u64 n, hipStream_t st) {
+    const bnscan::Plan p = bnscan::plan(n, false);
+    u64 *d;
+    P2_TRY(scratch(SCR_BN_SCAN, 4 * p.elems + 8 * n, &d));        // the plan's levels, then D and N
+    FrRangeJob J{};
+    for (u32 u = 0; u < nF; u++) fill_term(J.t[u], terms[u]);
+    for (u32 r = 0; r < nR; r++) {
+        const pil2gl_range_term &R = ranges[r];
+        FrRangeTerm &T = J.r[r];
+        T.m = (const FrField::Mem *)R.m; T.stride = R.mStride; T.col = R.mCol; T.row0 = R.row0; T.end = R.row0 + R.size;
+        u64 lo[4];
+        rangemultplan::lo_mod_r(R.lo, lo);
+        bnp::bn_limbs(lo, T.lo.v); bnp::bn_limbs(R.coef, T.coef.v); bnp::bn_limbs(R.busId, T.bus.v);
+    }
+    const bnp::U256 a = { { alpha[0], alpha[1], alpha[2], alpha[3] } };
+    bnp::bn_limbs(alpha, J.alpha.v); bnp::bn_limbs(bnp::h_to_mont(a).w, J.alphaR2.v); bnp::bn_limbs(beta, J.beta.v); bnp::bn_limbs(bnp::bn_mont_one().w, J.one.v);
+    J.nTerms = nF; J.nRanges = nR; J.n = n;
+    J.D = (FrField::Mem *)(d + 4 * p.elems); J.N = J.D + n;
+    bn_range_compress_kernel<<<smapplan::blocks(n), smapplan::THREADS, 0, st>>>(J);
+    KERNEL_CHECK();
+    uint4 *base = (uint4 *)d, *y = (uint4 *)(out + 4 * outCol);
+    P2_TRY(inverse_launch(p, base, (const uint4 *)J.D, 1, y, outStride, y, outStride, MODE_COLUMN, (const uint4 *)J.N, 1, Elem{}, st));
+    return scan_launch<true>(p, base, y, outStride, st);
+}
+
+int bn_range_sum_check(const pil2gl_logup_term *terms, u64 nF, const pil2gl_range_term *ranges, u64 nR, const u64 *alpha, const u64 *beta, const u64 *out,
+                       u64 outStride, u64 outCol, u64 n, bool dev) {
+    char why[96];
+    if (const char *msg = rangesumplan::check_call(terms, nF, ranges, nR, alpha, beta, out, outStride, outCol, n, 4, dev, why)) return fail(PIL2GL_EINVAL, "%s", msg);
+    return PIL2GL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_bn128_range_sum_dev(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR, const uint64_t *hostAlpha,
+                               const uint64_t *hostBeta, uint64_t *out, uint64_t outStride, uint64_t outCol, uint64_t n, void *stream) {
+    P2_TRY(bn_range_sum_check(hostTerms, nF, hostRanges, nR, hostAlpha, hostBeta, out, outStride, outCol, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return bn_range_sum_launch(hostTerms, (u32)nF, hostRanges, (u32)nR, hostAlpha, hostBeta, out, outStride, outCol, n, as_stream(stream));
+}
+
+// host matrices, each staged up to the last element touched (an m up to its window's last row); out's matrix goes up as it is and comes back
+// with the column written
+int pil2gl_bn128_range_sum(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR, const uint64_t *hostAlpha,
+                           const uint64_t *hostBeta, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n) {
+    P2_TRY(bn_range_sum_check(hostTerms, nF, hostRanges, nR, hostAlpha, hostBeta, hostOut, outStride, outCol, n, false));
+    if (!n) return PIL2GL_OK;
+    pil2gl_logup_term terms[rangesumplan::MAX_F];
+    pil2gl_range_term ranges[rangesumplan::MAX_RANGES];
+    const u64 outWords = tupleside::span_bytes(n, outStride, outCol, 4) / 8;
+    u64 total = smapplan::pad16(outWords);
+    for (u64 u = 0; u < nF; u++) { terms[u] = hostTerms[u]; total += tupleside::staged_words(terms[u].side, n, terms[u].k, 4); }
+    for (u64 r = 0; r < nR; r++) { ranges[r] = hostRanges[r]; total += smapplan::pad16(rangesumplan::m_words(ranges[r], 4)); }
+    Stage s(total);
+    P2_TRY(s.rc());
+    for (u64 u = 0; u < nF; u++) tupleside::stage_side(s, terms[u].side, n, terms[u].k, 4);
+    for (u64 r = 0; r < nR; r++) {
+        const u64 w = rangesumplan::m_words(ranges[r], 4);
+        ranges[r].m = s.put(ranges[r].m, w); s.take(smapplan::pad16(w) - w);
+    }
+    u64 *dOut = (u64 *)s.put(hostOut, outWords);
+    P2_TRY(s.rc());
+    P2_TRY(bn_range_sum_launch(terms, (u32)nF, ranges, (u32)nR, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0));
     return s.get(hostOut, dOut, outWords);
 }
 

@@ -12,6 +12,7 @@
 #include "gl_field.cuh"
 #include "hint_plan.h"
 #include "logup_sum_plan.h"
+#include "range_sum_plan.h"
 #include "grand_prod_plan.h"
 #include "plookup_plan.h"
 #include <utility>
@@ -206,13 +207,11 @@ template <class Fn> __device__ __forceinline__ void each_item(Fn f) { each_item(
 template <class Fn, int... K> __device__ __forceinline__ void each_item_down(Fn f, std::integer_sequence<int, K...>) { (f(std::integral_constant<int, SCAN_ITEMS - 1 - K>{}), ...); }
 template <class Fn> __device__ __forceinline__ void each_item_down(Fn f) { each_item_down(f, std::make_integer_sequence<int, SCAN_ITEMS>{}); }
 
-__global__ void __launch_bounds__(SCAN_THREADS) logup_scan1(const LogupJob J, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
-    __shared__ E3 sh[SCAN_THREADS];
-    const u64 base = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_ITEMS;
-    // the lane's rows as fractions num / den, den never zero; rows at or past n stay 0 / 1.  The terms are the outer loop, so that a term's
-    // table entries are read once for the lane's rows and the rows' loads of one column are in flight together
-    E3 num[SCAN_ITEMS], den[SCAN_ITEMS], loc[SCAN_ITEMS];
-    each_item([&](auto k) { num[k] = ident<false>(); den[k] = ident<true>(); });
+// the f terms of a lane's rows folded into its fractions num / den (den never zero; rows at or past n stay as they are).  The terms are the
+// outer loop, so that a term's table entries are read once for the lane's rows and the rows' loads of one column are in flight together.
+// Job: a kernel argument with t[], nTerms, apow[] and n, read with wave-uniform indices
+template <class Job>
+__device__ __forceinline__ void logup_fold(const Job &J, u64 base, E3 (&num)[SCAN_ITEMS], E3 (&den)[SCAN_ITEMS], E3 (&loc)[SCAN_ITEMS]) {
     for (u32 u = 0; u < J.nTerms; u++) {
         const LogupTerm &T = J.t[u];
         const E3 cst = T.cst;
@@ -225,12 +224,16 @@ __global__ void __launch_bounds__(SCAN_THREADS) logup_scan1(const LogupJob J, u6
         each_item([&](auto k) {
             const u64 i = base + k;
             const E3 d = loc[k];
-            if (i >= J.n || !(d.v[0] | d.v[1] | d.v[2])) return;             // a zero D_u: the term adds 0 and is left out of the product
+            if (i >= J.n || !(d.v[0] | d.v[1] | d.v[2])) return;               // a zero D_u: the term adds 0 and is left out of the product
             const u64 c = T.sel ? mul(T.sel[i * T.selStride + T.selCol], T.coef) : T.coef;
             num[k] = e3_add(e3_mul(num[k], d), e3_scale(den[k], c));
             den[k] = e3_mul(den[k], d);
         });
     }
+}
+// the lane's fractions to ratios with one inversion, their running sum, the block-local scan into tmp and the block's total
+__device__ __forceinline__ void logup_finish(E3 (&num)[SCAN_ITEMS], E3 (&den)[SCAN_ITEMS], E3 (&loc)[SCAN_ITEMS], E3 *sh, u64 base, u64 n,
+                                             u64 *__restrict__ tmp, u64 *__restrict__ totals) {
     E3 acc = ident<true>();
     each_item([&](auto k) {
         loc[k] = acc;                                   // the product of the rows' den before this one
@@ -246,15 +249,26 @@ __global__ void __launch_bounds__(SCAN_THREADS) logup_scan1(const LogupJob J, u6
     each_item([&](auto k) { run = e3_add(run, loc[k]); loc[k] = run; });      // rows at or past n hold num = 0
     E3 bt;
     const E3 ex = block_exclusive<false>(run, sh, &bt);
-    each_item([&](auto k) { const u64 i = base + k; if (i < J.n) st3(tmp, i, e3_add(ex, loc[k])); });
+    each_item([&](auto k) { const u64 i = base + k; if (i < n) st3(tmp, i, e3_add(ex, loc[k])); });
     if (threadIdx.x == 0) st3(totals, blockIdx.x, bt);
+}
+
+__global__ void __launch_bounds__(SCAN_THREADS) logup_scan1(const LogupJob J, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
+    __shared__ E3 sh[SCAN_THREADS];
+    const u64 base = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_ITEMS;
+    // the lane's rows as fractions num / den, den never zero; rows at or past n stay 0 / 1
+    E3 num[SCAN_ITEMS], den[SCAN_ITEMS], loc[SCAN_ITEMS];
+    each_item([&](auto k) { num[k] = ident<false>(); den[k] = ident<true>(); });
+    logup_fold(J, base, num, den, loc);
+    logup_finish(num, den, loc, sh, base, J.n, tmp, totals);
 }
 
 u64 h_canon(u64 a) { return a >= P ? a - P : a; }
 
 // every launch of a call, on st; the arguments have passed logupplan::check_call() and n > 0, the pointers are the device's
-int logup_launch(const pil2gl_logup_term *terms, u32 nTerms, const u64 *alpha, const u64 *beta, u64 *out, u64 outStride, u64 outCol, u64 n, hipStream_t st) {
-    LogupJob J{};
+// the f terms of a job (logup_scan1's, range_scan1's): the powers of alpha, each term's table entry with busId + beta
+template <class Job>
+void logup_fill(Job &J, const pil2gl_logup_term *terms, u32 nTerms, const u64 *alpha, const u64 *beta, u64 n) {
     const u64 a[3] = { h_canon(alpha[0]), h_canon(alpha[1]), h_canon(alpha[2]) };
     u64 pw[3] = { 1, 0, 0 };
     for (u32 e = 1; e <= tupleside::MAX_K; e++) {
@@ -272,6 +286,11 @@ int logup_launch(const pil2gl_logup_term *terms, u32 nTerms, const u64 *alpha, c
         T.cst = E3{ { h_add(h_canon(beta[0]), terms[u].busId[0]), h_canon(beta[1]), h_canon(beta[2]) } };
     }
     J.nTerms = nTerms; J.n = n;
+}
+
+int logup_launch(const pil2gl_logup_term *terms, u32 nTerms, const u64 *alpha, const u64 *beta, u64 *out, u64 outStride, u64 outCol, u64 n, hipStream_t st) {
+    LogupJob J{};
+    logup_fill(J, terms, nTerms, alpha, beta, n);
     const u64 nb = hintplan::blocks(n);
     u64 *tmp, *totals;
     P2_TRY(scratch(SCR_HINT_TMP, n * 3, &tmp));
@@ -330,6 +349,146 @@ int pil2gl_logup_sum(const pil2gl_logup_term *hostTerms, uint64_t nTerms, const 
     u64 *dOut = (u64 *)s.put(hostOut, outWords);
     P2_TRY(s.rc());
     P2_TRY(logup_launch(terms, (u32)nTerms, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0));
+    return s.get(hostOut, dOut, outWords);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The range-check grand sum (include/pil2gl.h states it; tests/range_sum_ref.py restates it over integers): the lookup grand sum above
+// with the table side of a range given as numbers,
+//   s[i] = s[i-1] + sum_u coef_u w_u[i] / D_u[i] + sum_r coefR_r [row0_r <= i < row0_r + size_r] m_r[i] / E_r[i],
+//   E_r[i] = field(lo_r + (i - row0_r)) alpha + busId_r + beta.
+// One fused first pass, range_scan1, beside logup_scan1, sharing its fold of the f terms (logup_fold) and its tail (logup_finish); then
+// hint_scan2<false> and hint_scan3<false> as they are.  A range is an arithmetic progression in the extension: with c0 = alpha field(lo) +
+// busId + beta made on the host, E at the lane's first in-window row is c0 + alpha (row - row0) -- ONE scaling of alpha by a base value, three
+// base products a lane -- and every next row's is E + alpha, an extension addition.  No t column exists; m is loaded only inside the window
+// (into loc, which the fold does not need meanwhile), so a range-row costs one 8-byte load where logup_scan1's k = 1 term costs two, and
+// 16 base products (coef m, the two extension products and the scaling of the fold) + 3/8 where that term costs 16 + 3.
+// The ranges are the outer loop, as the terms are in logup_fold.  Both tables travel as the kernel argument.
+// Safety: nothing read from a matrix is used as an address; m is loaded at row i only after row0 <= i < row0 + size <= n.
+namespace {
+
+struct RangeTermD {
+    const u64 *m;
+    u64 stride, col, row0, end;                      // the window: rows row0 .. end - 1
+    u64 coef;
+    E3 c0;                                           // alpha field(lo) + busId + beta
+};
+struct RangeJob {
+    LogupTerm t[rangesumplan::MAX_F];
+    E3 apow[tupleside::MAX_K + 1];                   // apow[e] = alpha^e, e = 1 .. 16
+    RangeTermD r[rangesumplan::MAX_RANGES];
+    u32 nTerms, nRanges;                             // nTerms: the f terms, 0 .. 8
+    u64 n;
+};
+
+__global__ void __launch_bounds__(SCAN_THREADS) range_scan1(const RangeJob J, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
+    __shared__ E3 sh[SCAN_THREADS];
+    const u64 base = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_ITEMS;
+    E3 num[SCAN_ITEMS], den[SCAN_ITEMS], loc[SCAN_ITEMS];
+    each_item([&](auto k) { num[k] = ident<false>(); den[k] = ident<true>(); });
+    logup_fold(J, base, num, den, loc);
+    const E3 alpha = J.apow[1];
+    for (u32 r = 0; r < J.nRanges; r++) {
+        const RangeTermD &T = J.r[r];
+        const u64 row0 = T.row0, end = T.end, coef = T.coef;
+        const u64 first = base > row0 ? base : row0;                            // the lane's first in-window row, if it has one
+        const u64 *p = T.m + base * T.stride + T.col;
+        each_item([&](auto k) { const u64 i = base + k; if (i >= first && i < end) loc[k].v[0] = p[k * T.stride]; });     // end <= n
+        E3 e = e3_add(T.c0, e3_scale(alpha, first - row0));                      // first - row0 < 2^28: a base value
+        each_item([&](auto k) {
+            const u64 i = base + k;
+            if (i < first || i >= end) return;
+            const E3 d = e;
+            e = e3_add(e, alpha);                                                // the next row's, whether this one is zero or not
+            if (!(d.v[0] | d.v[1] | d.v[2])) return;                             // a zero E_r: the range adds 0 and is left out of the product
+            num[k] = e3_add(e3_mul(num[k], d), e3_scale(den[k], mul(loc[k].v[0], coef)));
+            den[k] = e3_mul(den[k], d);
+        });
+    }
+    logup_finish(num, den, loc, sh, base, J.n, tmp, totals);
+}
+
+// every launch of a call, on st; the arguments have passed rangesumplan::check_call() and n > 0, the pointers are the device's
+int range_sum_launch(const pil2gl_logup_term *terms, u32 nF, const pil2gl_range_term *ranges, u32 nR, const u64 *alpha, const u64 *beta, u64 *out,
+                     u64 outStride, u64 outCol, u64 n, hipStream_t st) {
+    RangeJob J{};
+    logup_fill(J, terms, nF, alpha, beta, n);
+    const u64 a[3] = { h_canon(alpha[0]), h_canon(alpha[1]), h_canon(alpha[2]) }, b[3] = { h_canon(beta[0]), h_canon(beta[1]), h_canon(beta[2]) };
+    for (u32 r = 0; r < nR; r++) {
+        const pil2gl_range_term &R = ranges[r];
+        RangeTermD &T = J.r[r];
+        T.m = R.m; T.stride = R.mStride; T.col = R.mCol; T.row0 = R.row0; T.end = R.row0 + R.size; T.coef = R.coef[0];
+        rangesumplan::gl_c0(R, a, b, h_mul, h_add, T.c0.v);
+    }
+    J.nRanges = nR;
+    const u64 nb = hintplan::blocks(n);
+    u64 *tmp, *totals;
+    P2_TRY(scratch(SCR_HINT_TMP, n * 3, &tmp));
+    P2_TRY(scratch(SCR_HINT_TOTALS, nb * 3, &totals));
+    range_scan1<<<(unsigned)nb, SCAN_THREADS, 0, st>>>(J, tmp, totals);
+    KERNEL_CHECK();
+    hint_scan2<false><<<1, SCAN_THREADS, 0, st>>>(totals, nb);
+    KERNEL_CHECK();
+    hint_scan3<false><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tmp, totals, n, 3, out, outStride, outCol);
+    KERNEL_CHECK();
+    return PIL2GL_OK;
+}
+
+int range_sum_check(const pil2gl_logup_term *terms, u64 nF, const pil2gl_range_term *ranges, u64 nR, const u64 *alpha, const u64 *beta, const u64 *out,
+                    u64 outStride, u64 outCol, u64 n, bool dev) {
+    char why[96];
+    if (const char *msg = rangesumplan::check_call(terms, nF, ranges, nR, alpha, beta, out, outStride, outCol, n, 1, dev, why)) return fail(PIL2GL_EINVAL, "%s", msg);
+    return PIL2GL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_range_sum_plan(uint64_t n, uint64_t nF, uint64_t nR, uint32_t elemWords, uint32_t *outInfo, uint64_t *workBytes) {
+    if (workBytes) *workBytes = 0;
+    if (const char *msg = rangesumplan::check(n, nF, nR, elemWords)) return fail(PIL2GL_EINVAL, "%s", msg);
+    const rangesumplan::Plan p = rangesumplan::plan(n, elemWords);
+    if (outInfo) {
+        outInfo[0] = p.threads; outInfo[1] = p.items; outInfo[2] = p.blocks; outInfo[3] = p.launches; outInfo[4] = p.depth;
+        outInfo[5] = logupplan::out_width(elemWords);
+    }
+    if (workBytes) *workBytes = p.bytes;
+    return PIL2GL_OK;
+}
+
+int pil2gl_range_sum_dev(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR, const uint64_t *hostAlpha,
+                         const uint64_t *hostBeta, uint64_t *out, uint64_t outStride, uint64_t outCol, uint64_t n, void *stream) {
+    P2_TRY(range_sum_check(hostTerms, nF, hostRanges, nR, hostAlpha, hostBeta, out, outStride, outCol, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return range_sum_launch(hostTerms, (u32)nF, hostRanges, (u32)nR, hostAlpha, hostBeta, out, outStride, outCol, n, as_stream(stream));
+}
+
+// host matrices, each staged up to the last element touched (an m up to its window's last row); out's matrix goes up as it is and comes back
+// with the column written
+int pil2gl_range_sum(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR, const uint64_t *hostAlpha,
+                     const uint64_t *hostBeta, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n) {
+    P2_TRY(range_sum_check(hostTerms, nF, hostRanges, nR, hostAlpha, hostBeta, hostOut, outStride, outCol, n, false));
+    if (!n) return PIL2GL_OK;
+    pil2gl_logup_term terms[rangesumplan::MAX_F];
+    pil2gl_range_term ranges[rangesumplan::MAX_RANGES];
+    const u64 outWords = tupleside::span_bytes(n, outStride, outCol + 2, 1) / 8;
+    u64 total = smapplan::pad16(outWords);
+    for (u64 u = 0; u < nF; u++) { terms[u] = hostTerms[u]; total += tupleside::staged_words(terms[u].side, n, terms[u].k, 1); }
+    for (u64 r = 0; r < nR; r++) { ranges[r] = hostRanges[r]; total += smapplan::pad16(rangesumplan::m_words(ranges[r], 1)); }
+    Stage s(total);
+    P2_TRY(s.rc());
+    for (u64 u = 0; u < nF; u++) tupleside::stage_side(s, terms[u].side, n, terms[u].k, 1);
+    for (u64 r = 0; r < nR; r++) {
+        const u64 w = rangesumplan::m_words(ranges[r], 1);
+        ranges[r].m = s.put(ranges[r].m, w); s.take(smapplan::pad16(w) - w);
+    }
+    u64 *dOut = (u64 *)s.put(hostOut, outWords);
+    P2_TRY(s.rc());
+    P2_TRY(range_sum_launch(terms, (u32)nF, ranges, (u32)nR, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0));
     return s.get(hostOut, dOut, outWords);
 }
 

@@ -33,6 +33,10 @@
 //       Uint8Array(32) with opts.bn128.  out: { buf, stride, col }: over Goldilocks the words col .. col + 2 of a row of `stride` words,
 //       over Fr one element.  Written in place for every row; s[n-1] is the hint's result.  logupSumDev only enqueues (opts.stream).
 //   logupSumPlan(n, nTerms, bn128)   the library's plan
+//   rangeSum(terms, ranges, alpha, beta, out, n, opts) / rangeSumDev(..) / rangeSumPlan(n, nF, nR, bn128)
+//       logupSum with the table side of a range check given as numbers (csrc/range_sum_plan.h): terms: 0 .. 8 f terms as above; ranges:
+//       1 .. 8 of { m: { buf, stride, col }, lo, size, row0, coef, busId } -- lo a BigInt or an integer (signed 64-bit), coef and busId as a
+//       term's.  No t column exists; outside rows row0 .. row0 + size - 1 a range adds 0 and m is not read.  rangeSumDev only enqueues.
 //   grandProduct(terms, alpha, beta, gamma, out, n, opts) / grandProductDev(..) / grandProductPlan(n, nTerms, sumK, bn128)
 //       the column z of a permutation or a connection from the trace columns (include/pil2gl.h states it); permutationTerms and
 //       connectionTerms build the term lists of the reference's two identities
@@ -235,6 +239,47 @@ const logupSum = (terms, alpha, beta, out, n, opts) => logup(false, terms, alpha
 const logupSumDev = (terms, alpha, beta, out, n, opts) => logup(true, terms, alpha, beta, out, n, opts);
 const logupSumPlan = (n, nTerms, bn128) => addon.logupSumPlan(n, nTerms, bn128 ? 4 : 1);
 
+// ---- range-check grand sum ----
+function rangeLogup(dev, termsIn, rangesIn, alpha, beta, outIn, n, opts) {
+    const bn = !!(opts && opts.bn128), ew = bn ? 4 : 1, width = bn ? 1 : 3;
+    if (!Array.isArray(termsIn) || termsIn.length > 8) throw new Error("terms must be an array of 0 .. 8 terms");
+    if (!Array.isArray(rangesIn) || rangesIn.length < 1 || rangesIn.length > 8 || termsIn.length + rangesIn.length > 9) throw new Error("ranges must be an array of 1 .. 8 ranges, 9 with the terms at most");
+    if (!outIn || !(outIn.stride > 0) || !(outIn.col >= 0)) throw new Error("out must be { buf, stride, col }");
+    const elem = (v, what, words) => {
+        if (!bn && words === 1) { if (typeof v !== "bigint") throw new Error(what + " must be a BigInt"); return [v, 0n, 0n, 0n]; }
+        const w = Array.from(stage.asWords(v));
+        if (w.length !== words) throw new Error(what + " must hold " + words + " words");
+        return w.concat([0n, 0n, 0n, 0n]).slice(0, 4);
+    };
+    const terms = termsIn.map((t, u) => {
+        const s = side(t, "term " + u, n, ew, dev);
+        if (s.cols.length < 1 || s.cols.length > 16) throw new Error("term " + u + ": 1 .. 16 columns");
+        s.coef = elem(t.coef, "coef of term " + u, ew); s.busId = elem(t.busId, "busId of term " + u, ew);
+        return s;
+    });
+    const ranges = rangesIn.map((r, i) => {
+        if (!r || !r.m || !(r.m.stride > 0) || !(r.m.col >= 0)) throw new Error("range " + i + " must be { m: { buf, stride, col }, lo, size, row0, coef, busId }");
+        const lo = BigInt(r.lo);
+        if (lo < -(1n << 63n) || lo >= 1n << 63n) throw new Error("range " + i + ": lo must be a signed 64-bit integer");
+        const s = side({ buf: r.m.buf, stride: r.m.stride, cols: [r.m.col] }, "m of range " + i, n, ew, dev);
+        return Object.assign(s, { lo: BigInt.asUintN(64, lo), size: r.size, row0: r.row0 || 0, coef: elem(r.coef, "coef of range " + i, ew), busId: elem(r.busId, "busId of range " + i, ew) });
+    });
+    const out = side({ buf: outIn.buf, stride: outIn.stride, cols: [outIn.col, outIn.col + width - 1] }, "out", n, ew, dev);
+    const ptr = (b) => dev && b ? b.ptr : 0n;
+    const head = [n, terms.length, ranges.length, ptr(out.buf), out.stride, outIn.col].concat(elem(alpha, "alpha", bn ? 4 : 3), elem(beta, "beta", bn ? 4 : 3));
+    const fourteen = terms.map((x) => [ptr(x.buf), x.stride, x.cols.length].concat(x.sel ? [ptr(x.sel.buf), x.sel.stride, x.sel.col] : [0n, 0, 0], x.coef, x.busId));
+    const rangeWords = ranges.map((x) => [ptr(x.buf), x.stride, x.cols[0], x.lo, x.size, x.row0].concat(x.coef, x.busId));
+    const slots = terms.map((x) => x.cols.concat(new Array(16 - x.cols.length).fill(0)));
+    const desc = BigUint64Array.from(head.concat(...fourteen, ...rangeWords, ...slots).map((v) => BigInt(v)));
+    if (dev) { addon.rangeSumDev(desc, ew, opts && opts.stream); return outIn; }
+    addon.rangeSum(desc, matrices(terms.concat(ranges)).concat([out.buf]), ew);
+    copyBack(out.buf, outIn.buf);
+    return outIn;
+}
+const rangeSum = (terms, ranges, alpha, beta, out, n, opts) => rangeLogup(false, terms, ranges, alpha, beta, out, n, opts);
+const rangeSumDev = (terms, ranges, alpha, beta, out, n, opts) => rangeLogup(true, terms, ranges, alpha, beta, out, n, opts);
+const rangeSumPlan = (n, nF, nR, bn128) => addon.rangeSumPlan(n, nF, nR, bn128 ? 4 : 1);
+
 // ---- grand product of a permutation or a connection ----
 // A term is a side { buf, stride, cols, sel } with den: 0 | 1 and optionally id: { buf, stride, col } and idCoef (3 words over Goldilocks,
 // 4 Montgomery words over Fr); alpha, beta, gamma are 3 or 4 words each; out is logupSum's.  z[n-1] is the hint's result.
@@ -317,4 +362,4 @@ const plookupProduct = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, opts) =
 const plookupProductDev = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, opts) => plookup(true, true, f, t, [h1, h2, out], [alpha, beta, gamma, delta], n, opts);
 const plookupPlan = (n, kF, kT, bn128) => addon.plookupPlan(n, kF, kT, bn128 ? 4 : 1);
 
-module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, logupSum, logupSumDev, logupSumPlan, grandProduct, grandProductDev, grandProductPlan, permutationTerms, connectionTerms, plookupFold, plookupFoldDev, plookupProduct, plookupProductDev, plookupPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };
+module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, logupSum, logupSumDev, logupSumPlan, rangeSum, rangeSumDev, rangeSumPlan, grandProduct, grandProductDev, grandProductPlan, permutationTerms, connectionTerms, plookupFold, plookupFoldDev, plookupProduct, plookupProductDev, plookupPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };

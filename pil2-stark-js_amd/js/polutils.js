@@ -149,3 +149,11 @@ const calculateH1H2PlookupDev = (f, t, alpha, beta, n, hDim, stream) => h1h2Ploo
 const calculateZPlookup = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, hDim) => zPlookup(false, f, t, h1, h2, alpha, beta, gamma, delta, out, n, hDim);
 const calculateZPlookupDev = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, hDim, stream) => zPlookup(true, f, t, h1, h2, alpha, beta, gamma, delta, out, n, hDim, stream);
 Object.assign(module.exports, { calculateH1H2Plookup, calculateH1H2PlookupDev, calculateZPlookup, calculateZPlookupDev });
+
+// The grand sum of range checks from the f columns, the multiplicities and the ranges as numbers, no t column (js/pil_checks.js rangeSum;
+// include/pil2gl.h states it): terms = 0 .. 8 f terms, ranges = 1 .. 8 of { m, lo, size, row0, coef, busId }, out = { buf, stride, col }.
+//   calculateSRange(terms, ranges, alpha, beta, out, n)               host words; writes s in place -> out
+//   calculateSRangeDev(terms, ranges, alpha, beta, out, n, stream)    the same on DevBuffers; only enqueues
+const calculateSRange = (terms, ranges, alpha, beta, out, n) => require("./pil_checks.js").rangeSum(terms, ranges, alpha, beta, out, n, { bn128: false });
+const calculateSRangeDev = (terms, ranges, alpha, beta, out, n, stream) => require("./pil_checks.js").rangeSumDev(terms, ranges, alpha, beta, out, n, { bn128: false, stream });
+Object.assign(module.exports, { calculateSRange, calculateSRangeDev });

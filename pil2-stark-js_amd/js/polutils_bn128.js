@@ -174,5 +174,8 @@ const calculateH1H2Plookup = (f, t, alpha, beta, n) => h1h2Plookup(false, f, t, 
 const calculateH1H2PlookupDev = (f, t, alpha, beta, n, stream) => h1h2Plookup(true, f, t, alpha, beta, n, stream);
 const calculateZPlookup = (f, t, h1, h2, alpha, beta, gamma, delta, out, n) => zPlookup(false, f, t, h1, h2, alpha, beta, gamma, delta, out, n);
 const calculateZPlookupDev = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, stream) => zPlookup(true, f, t, h1, h2, alpha, beta, gamma, delta, out, n, stream);
+// the grand sum of range checks with the ranges as numbers, no t column (js/pil_checks.js rangeSum): elements are 4 Montgomery words
+const calculateSRange = (terms, ranges, alpha, beta, out, n) => require("./pil_checks.js").rangeSum(terms, ranges, alpha, beta, out, n, { bn128: true });
+const calculateSRangeDev = (terms, ranges, alpha, beta, out, n, stream) => require("./pil_checks.js").rangeSumDev(terms, ranges, alpha, beta, out, n, { bn128: true, stream });
 
-module.exports = { calculateH1H2Plookup, calculateH1H2PlookupDev, calculateZPlookup, calculateZPlookupDev, calculateZPermutation, calculateZPermutationDev, calculateZConnection, calculateZConnectionDev, calculateZ, calculateS, calculateSCol, batchInverse, calculateH1H2, calculateZDev, calculateSDev, calculateSColDev, batchInverseDev, calculateH1H2Dev, lastElement };
+module.exports = { calculateSRange, calculateSRangeDev, calculateH1H2Plookup, calculateH1H2PlookupDev, calculateZPlookup, calculateZPlookupDev, calculateZPermutation, calculateZPermutationDev, calculateZConnection, calculateZConnectionDev, calculateZ, calculateS, calculateSCol, batchInverse, calculateH1H2, calculateZDev, calculateSDev, calculateSColDev, batchInverseDev, calculateH1H2Dev, lastElement };

@@ -62,6 +62,12 @@ class LogupTerm(C.Structure):
     _fields_ = [("side", TupleSide), ("k", C.c_uint64), ("coef", C.c_uint64 * 4), ("busId", C.c_uint64 * 4)]
 
 
+class RangeTerm(C.Structure):
+    """include/pil2gl.h pil2gl_range_term: one range of the range-check grand sum (its m column, lo, size, row0, coef and busId)"""
+    _fields_ = [("m", C.c_void_p), ("mStride", C.c_uint64), ("mCol", C.c_uint64), ("lo", C.c_int64), ("size", C.c_uint64), ("row0", C.c_uint64),
+                ("coef", C.c_uint64 * 4), ("busId", C.c_uint64 * 4)]
+
+
 class GrandProdTerm(C.Structure):
     """include/pil2gl.h pil2gl_grand_prod_term: one term of a grand product (its side, its k, numerator or denominator, the id column and
     its host coefficient)"""
@@ -277,6 +283,11 @@ SIGNATURES = {
     "pil2gl_bn128_logup_sum_dev": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),
     "pil2gl_logup_sum": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64]),
     "pil2gl_bn128_logup_sum": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64]),
+    "pil2gl_range_sum_plan": (_I, [_U64, _U64, _U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_range_sum_dev": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_bn128_range_sum_dev": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_range_sum": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, vp, vp, _U64, _U64, _U64]),
+    "pil2gl_bn128_range_sum": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, vp, vp, _U64, _U64, _U64]),
     "pil2gl_grand_prod_plan": (_I, [_U64, _U64, _U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
     "pil2gl_grand_prod_dev": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64, vp]),
     "pil2gl_bn128_grand_prod_dev": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64, vp]),

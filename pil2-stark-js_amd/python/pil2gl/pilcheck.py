@@ -13,7 +13,8 @@ returns the library's five words (kind, row, partner, cntF, cntT) -- include/pil
 
 The column that PROVES a lookup in pil2, the multiplicities of its grand sum (csrc/lookup_mult.hip), is lookup_mult / lookup_mult_dev at the
 end of this module, then its form for a range check, which needs no table column (range_mult / range_mult_dev, csrc/range_mult.hip), and
-after them the grand sum that consumes the column (logup_sum / logup_sum_dev) and the grand product of a permutation or a connection
+after them the grand sum that consumes the column (logup_sum / logup_sum_dev), its form for range checks, which takes the ranges as
+numbers (range_sum / range_sum_dev, and range_logup for both halves), and the grand product of a permutation or a connection
 (grand_prod / grand_prod_dev, with perm_prod and conn_prod as spellings of the two identities), and last pil1's plookup argument
 (plookup_fold, plookup_h1h2, plookup_prod and their _dev forms).
 """
@@ -261,9 +262,18 @@ def logup_sum_plan(n, n_terms=1, field="gl"):
     return _plan("pil2gl_logup_sum_plan", (n, n_terms, _WORDS[field]), ("threads", "items", "blocks", "launches", "depth", "outWidth"), "workBytes")
 
 
-def _logup(dev, terms, alpha, beta, out, n, field):
+def _elem4(dst, v, words, what):
+    """a host base-field element into a uint64[4] field of a term: an integer over Goldilocks, four Montgomery words over Fr"""
+    w = np.ascontiguousarray([v] if words == 1 else v, np.uint64).reshape(-1)
+    if w.size != words:
+        raise Pil2glError("%s is %d words" % (what, words))
+    for i in range(words):
+        dst[i] = int(w[i])
+
+
+def _logup_terms(terms, n, words, dev):
+    """term specs as a LogupTerm array (one element at least) and what must stay alive until the call returns"""
     from ._lib import LogupTerm
-    words = _WORDS[field]
     T = (LogupTerm * max(len(terms), 1))()
     keep = []
     for u, spec in enumerate(terms):
@@ -272,11 +282,13 @@ def _logup(dev, terms, alpha, beta, out, n, field):
         T[u].side = side[0]
         keep.append(kept)
         for name, v in (("coef", spec[3]), ("busId", spec[4])):
-            w = np.ascontiguousarray([v] if words == 1 else v, np.uint64).reshape(-1)
-            if w.size != words:
-                raise Pil2glError("term %d: %s is %d words" % (u, name, words))
-            for i in range(words):
-                getattr(T[u], name)[i] = int(w[i])
+            _elem4(getattr(T[u], name), v, words, "term %d: %s" % (u, name))
+    return T, keep
+
+
+def _logup(dev, terms, alpha, beta, out, n, field):
+    words = _WORDS[field]
+    T, keep = _logup_terms(terms, n, words, dev)
     ch = [np.ascontiguousarray(c, np.uint64).reshape(-1) for c in (alpha, beta)]
     if any(c.size != (3 if words == 1 else 4) for c in ch):
         raise Pil2glError("alpha and beta are %d words each" % (3 if words == 1 else 4))
@@ -298,6 +310,80 @@ def logup_sum(terms, alpha, beta, out, n, field="gl"):
 def logup_sum_dev(terms, alpha, beta, out, n, field="gl"):
     """logup_sum on device tensors, e.g. columns of the stage-1 buffer with m one of them; only enqueues on the current stream"""
     return _logup(True, terms, alpha, beta, out, n, field)
+
+
+# ---- range-check grand sum: the logUp column s from f, m and the ranges as numbers (csrc/range_sum_plan.h; include/pil2gl.h states it) ----
+#     range_mult_dev([(cm1, [7])], -128, 256, (cm1, 12), n)
+#     range_sum_dev([(cm1, [7], None, 1, bus)], [((cm1, 12), -128, 256, 0, P - 1, bus)], alpha, beta, (cm2, 0), n)
+# The f terms are logup_sum's and may be none (the range table's own AIR).  A range is (m, lo, size, row0, coef, bus_id) with m a column
+# (matrix, col) or (matrix, col, stride): no t column exists; outside rows row0 .. row0 + size - 1 the range adds 0 and m is not read.
+def range_sum_plan(n, n_f=0, n_r=1, field="gl"):
+    """pil2gl_range_sum_plan (host-only): logup_sum_plan's numbers for the same n"""
+    return _plan("pil2gl_range_sum_plan", (n, n_f, n_r, _WORDS[field]), ("threads", "items", "blocks", "launches", "depth", "outWidth"), "workBytes")
+
+
+def _range_sum(dev, terms, ranges, alpha, beta, out, n, field):
+    from ._lib import RangeTerm
+    words = _WORDS[field]
+    T, keep = _logup_terms(terms, n, words, dev)
+    Rg = (RangeTerm * max(len(ranges), 1))()
+    for r, (m, lo, size, row0, coef, bus) in enumerate(ranges):
+        m = tuple(m) + (None,)
+        mm, stride = _side(m[0], [m[1]], m[2], None, n, words, dev, "m of range %d" % r)[:2]
+        keep.append(mm)
+        Rg[r].m, Rg[r].mStride, Rg[r].mCol = _dev_ptr(dev)(mm), stride, m[1]
+        Rg[r].lo, Rg[r].size, Rg[r].row0 = lo, size, row0
+        _elem4(Rg[r].coef, coef, words, "range %d: coef" % r)
+        _elem4(Rg[r].busId, bus, words, "range %d: busId" % r)
+    ch, chp = _challenges((alpha, beta), "alpha and beta", words)
+    om, col = _column(out, "out", 3 if words == 1 else 1, n, words, dev)
+    name = "pil2gl_range_sum" if words == 1 else "pil2gl_bn128_range_sum"
+    args = [T if terms else None, len(terms), Rg, len(ranges)] + chp + col + [n]
+    if dev:
+        call(name + "_dev", *args, _stream())
+    else:
+        call(name, *args)
+    return out[0]
+
+
+def range_sum(terms, ranges, alpha, beta, out, n, field="gl"):
+    """the grand-sum column of range checks: host matrices; out's column is written in place -> out's matrix (s[n-1] is the hint's result)"""
+    return _range_sum(False, terms, ranges, alpha, beta, out, n, field)
+
+
+def range_sum_dev(terms, ranges, alpha, beta, out, n, field="gl"):
+    """range_sum on device tensors, e.g. f and m columns of the stage-1 buffer; only enqueues on the current stream"""
+    return _range_sum(True, terms, ranges, alpha, beta, out, n, field)
+
+
+def range_logup(fs, lo, size, m, alpha, beta, out, n, field="gl", row0=0, bus_id=None):
+    """the whole prove side of the range checks `f_s in [lo, lo + size)` on device tensors: range_mult_dev writes m, then range_sum_dev
+    writes s with coef 1 for every f side (its selector, a field 0 / 1, the numerator), -1 for the range, and one bus id (0 by default)
+    -> (range_mult's report, s[n-1] as a host array of 3 words or of 4 Montgomery words); s[n-1] is zero when the report is clean.  Blocks
+    for the report and for s[n-1]."""
+    words = _WORDS[field]
+    report = range_mult_dev(fs, lo, size, m, n, field, row0)
+    if words == 1:
+        one, minus, bus = 1, 0xFFFFFFFF00000000, 0 if bus_id is None else bus_id
+    else:
+        from .bn128 import _words, R
+        one, minus = _words([(1 << 256) % R])[0], _words([R - (1 << 256) % R])[0]
+        bus = [0, 0, 0, 0] if bus_id is None else bus_id
+    terms = []
+    for f in fs:
+        f = tuple(f) + (None,) * (4 - len(f))
+        terms.append((f[0], f[1], f[2], one, bus, f[3]))
+    range_sum_dev(terms, [(m, lo, size, row0, minus, bus)], alpha, beta, out, n, field)
+    if not n:
+        return report, None
+    width = 3 if words == 1 else 1
+    mat, stride = out[0], (out[2] if len(out) > 2 else None)
+    flat = mat.reshape(-1)
+    if stride is None:
+        stride = mat.shape[1]
+    at = ((n - 1) * stride + out[1]) * words
+    last = flat[at:at + width * words].cpu().numpy().view(np.uint64).copy()
+    return report, last
 
 
 # ---- grand product: the column z of a permutation or a connection (csrc/grand_prod_plan.h; include/pil2gl.h states it) ----
