@@ -24,7 +24,7 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; range_sum and bn128_range_sum; grand_prod and bn128_grand_prod; plookup_fold, plookup_prod and their bn128_ twins; land_rows with a null hostFirstBad;
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; range_sum and bn128_range_sum; logup_cluster and bn128_logup_cluster; grand_prod and bn128_grand_prod; plookup_fold, plookup_prod and their bn128_ twins; land_rows with a null hostFirstBad;
  *      wtns_adds and bn128_wtns_adds, wtns_gather and bn128_wtns_gather with a null hostFirstBad, conn_pols and bn128_conn_pols with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, logup_sum_plan, range_sum_plan, grand_prod_plan, plookup_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, logup_sum_plan, range_sum_plan, logup_cluster_plan, grand_prod_plan, plookup_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -1167,6 +1167,61 @@ int pil2gl_range_sum(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2
                      const uint64_t *hostBeta, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
 int pil2gl_bn128_range_sum(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR,
                            const uint64_t *hostAlpha, const uint64_t *hostBeta, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
+
+/* ---- clustered logUp sum: the im columns and s in one call (csrc/logup_cluster_plan.h, hints.hip, bn_scan.hip) ----
+ * An AIR that carries the s of the two blocks above states (s - 's (1 - L1)) prod D_u - sum .. = 0, of degree nTerms + 1.  pil2's std library
+ * keeps it inside the degree bound by clustering: a cluster c of terms gets a committed stage-2 column im_c, and the sum constraint becomes
+ * s - 's (1 - L1) = sum_c im_c + (the terms left direct).  This block writes s AND every im_c from the trace columns.  The statement is this
+ * header's own (tests/logup_cluster_ref.py restates it over Python integers):
+ *   terms: nF pil2gl_logup_term (D_u, coef_u, w_u of the lookup grand sum above), then nR pil2gl_range_term (E_r, its window, m_r of the block above);
+ *          0 <= nF <= 8, 0 <= nR <= 8, 1 <= nF + nR <= 9
+ *   cluster[u], u < nF + nR: a HOST array, f terms first; each entry 0 .. nIm - 1, or PIL2GL_LOGUP_DIRECT.  1 <= nIm <= 9 and every id
+ *          0 .. nIm - 1 is the cluster of at least one term
+ *   frac_u[i] = coef_u w_u[i] / D_u[i]                        an f term
+ *             = [in window] coefR m_r[i] / E_r[i]             a range
+ *             = 0                                             where the denominator is 0, and outside the window (m is NOT READ there)
+ *   im_c[i]   = sum_{cluster[u] = c} frac_u[i]                                           c < nIm, every row i < n
+ *   s[i]      = s[i-1] + sum_c im_c[i] + sum_{cluster[u] = DIRECT} frac_u[i]             s[-1] = 0
+ * s goes to (out, outStride, outCol) as in the blocks above; im_c to (im[c].base, im[c].stride, im[c].col), an element of s's shape: three
+ * canonical words a row over Goldilocks (col + 2 < stride), one canonical Montgomery element over Fr.  Words between strided elements stay
+ * untouched.  Field arithmetic is exact, so, word for word: s is what pil2gl_[bn128_]logup_sum (nR = 0) or range_sum gives on the same
+ * terms, whatever the clusters; and im_c[i] = s_c[i] - s_c[i-1] with s_c that call on cluster c's terms alone.
+ * pil2gl_logup_cluster_plan: host-only, no device.  outInfo: threads a workgroup, rows a lane of the first pass, workgroups, launches, depth
+ * (logup_sum_plan's), words of an output element; *workBytes: Goldilocks logup_sum's, Fr bn_scan's levels and 32 n -- neither grows with the
+ * terms or with nIm.  PIL2GL_EINVAL: n > 2^28, nF > 8, nR > 8, nF + nR outside 1 .. 9, nIm outside 1 .. 9, elemWords not 1 or 4.
+ * pil2gl_[bn128_]logup_cluster_dev: hostTerms, hostRanges, hostCluster and hostIm are HOST pointers (hostTerms may be NULL when nF = 0,
+ * hostRanges when nR = 0); the matrices and every output are device pointers, 16-byte aligned.  The call only ENQUEUES on the caller's
+ * stream: the tables travel as the kernel argument, working memory is the library's slots.  Aliasing: EVERY output, s and each im_c, obeys
+ * the rule of out in the blocks above against every matrix read (each m_r counted over all n rows), and no two outputs share a word: two
+ * outputs may meet only as different word columns of ONE matrix (the same base, the same stride) -- s and its im columns as neighbouring
+ * stage-2 columns, possibly spare columns of t's matrix, is the normal case.
+ * PIL2GL_EINVAL, before any device call: what the plan refuses; what the blocks above refuse for the terms, the ranges, the challenges and
+ * out; a null cluster array, an id >= nIm that is not PIL2GL_LOGUP_DIRECT, a cluster without a term; null hostIm; for an im column: col + 2 >=
+ * stride over Goldilocks (col >= stride over Fr), a stride >= 2^32, n stride > 2^58, a null or misaligned base; an output on a column that is
+ * read; two outputs sharing a word.  n = 0 is PIL2GL_OK, touches nothing and needs no device.
+ * pil2gl_[bn128_]logup_cluster: host pointers throughout; the read matrices staged as in the blocks above; every DISTINCT output matrix
+ * (base, stride) goes up as it is, to the last word an output writes in it, and comes back with its columns written.  Without a device the
+ * compute calls return PIL2GL_ENODEV. */
+#define PIL2GL_LOGUP_DIRECT (~(uint64_t)0)           /* a cluster entry: the term stays in the sum constraint, in no im column */
+typedef struct pil2gl_logup_im_col {
+    uint64_t *base;                      /* im_c of row i at base[(i stride + col) elemWords]: words col .. col + 2 over Goldilocks */
+    uint64_t stride, col;
+} pil2gl_logup_im_col;
+int pil2gl_logup_cluster_plan(uint64_t n, uint64_t nF, uint64_t nR, uint64_t nIm, uint32_t elemWords, uint32_t *outInfo /* [6] */, uint64_t *workBytes);
+int pil2gl_logup_cluster_dev(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR,
+                             const uint64_t *hostCluster /* [nF + nR] */, const pil2gl_logup_im_col *hostIm, uint64_t nIm,
+                             const uint64_t *hostAlpha /* [3] */, const uint64_t *hostBeta /* [3] */, uint64_t *out, uint64_t outStride, uint64_t outCol,
+                             uint64_t n, void *stream);
+int pil2gl_bn128_logup_cluster_dev(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR,
+                                   const uint64_t *hostCluster, const pil2gl_logup_im_col *hostIm, uint64_t nIm,
+                                   const uint64_t *hostAlpha /* [4] */, const uint64_t *hostBeta /* [4] */, uint64_t *out, uint64_t outStride,
+                                   uint64_t outCol, uint64_t n, void *stream);
+int pil2gl_logup_cluster(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR,
+                         const uint64_t *hostCluster, const pil2gl_logup_im_col *hostIm, uint64_t nIm, const uint64_t *hostAlpha,
+                         const uint64_t *hostBeta, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
+int pil2gl_bn128_logup_cluster(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR,
+                               const uint64_t *hostCluster, const pil2gl_logup_im_col *hostIm, uint64_t nIm, const uint64_t *hostAlpha,
+                               const uint64_t *hostBeta, uint64_t *hostOut, uint64_t outStride, uint64_t outCol, uint64_t n);
 
 /* ---- grand product: the column z of a permutation or a connection from the trace columns (csrc/grand_prod_plan.h, hints.hip, bn_scan.hip) ----
  * The sibling of the block above for the `gprod` hints (grandProductPermutation.js:121-126, grandProductConnection.js:131-136): z in one

@@ -889,6 +889,16 @@ FN(RangeTermLayout) {      // -> sizeof and offsetof of pil2gl_range_term as thi
 // two's-complement word, size, row0, coef[4], busId[4] -- then 16 column slots an f term, the first k used.  The pointer words are device
 // addresses for rangeSumDev and are not read by rangeSum, which takes the host matrices as an array of its own.
 enum { SD_N, SD_NF, SD_NR, SD_OUT, SD_OUT_STRIDE, SD_OUT_COL, SD_ALPHA, SD_BETA = SD_ALPHA + 4, SD_TERMS = SD_BETA + 4, SD_TERM_WORDS = 14, SD_COL_SLOTS = 16 };
+// the 14 words of an f term (its columns in slots of their own) and of a range
+static void term_of_words(const uint64_t *w, const uint64_t *cols, pil2gl_logup_term &t) {
+    t.side = pil2gl_tuple_side{ (const uint64_t *)(uintptr_t)w[0], w[1], cols, (const uint64_t *)(uintptr_t)w[3], w[4], w[5] };
+    t.k = w[2];
+    for (int c = 0; c < 4; c++) { t.coef[c] = w[6 + c]; t.busId[c] = w[10 + c]; }
+}
+static void range_of_words(const uint64_t *w, pil2gl_range_term &t) {
+    t.m = (const uint64_t *)(uintptr_t)w[0]; t.mStride = w[1]; t.mCol = w[2]; t.lo = (int64_t)w[3]; t.size = w[4]; t.row0 = w[5];
+    for (int c = 0; c < 4; c++) { t.coef[c] = w[6 + c]; t.busId[c] = w[10 + c]; }
+}
 struct RangeSumDesc { uint64_t *d; uint64_t n, nF, nR; pil2gl_logup_term term[8]; pil2gl_range_term range[8]; };
 static bool range_sum_desc(Args &a, size_t i, RangeSumDesc &L) {
     uint64_t len = 0; L.d = a.arr(i, SD_TERMS, &len);
@@ -897,19 +907,8 @@ static bool range_sum_desc(Args &a, size_t i, RangeSumDesc &L) {
     if (L.nF > 8 || L.nR < 1 || L.nR > 8 || len < SD_TERMS + (L.nF + L.nR) * SD_TERM_WORDS + L.nF * SD_COL_SLOTS)
         return a.fail("the description holds 14 words, then 0 .. 8 terms and 1 .. 8 ranges of 14 words, then 16 column slots a term");
     uint64_t *cols = L.d + SD_TERMS + (L.nF + L.nR) * SD_TERM_WORDS;
-    for (uint64_t u = 0; u < L.nF; u++) {
-        const uint64_t *w = L.d + SD_TERMS + u * SD_TERM_WORDS;
-        pil2gl_logup_term &t = L.term[u];
-        t.side = pil2gl_tuple_side{ (const uint64_t *)(uintptr_t)w[0], w[1], cols + u * SD_COL_SLOTS, (const uint64_t *)(uintptr_t)w[3], w[4], w[5] };
-        t.k = w[2];
-        for (int c = 0; c < 4; c++) { t.coef[c] = w[6 + c]; t.busId[c] = w[10 + c]; }
-    }
-    for (uint64_t r = 0; r < L.nR; r++) {
-        const uint64_t *w = L.d + SD_TERMS + (L.nF + r) * SD_TERM_WORDS;
-        pil2gl_range_term &t = L.range[r];
-        t.m = (const uint64_t *)(uintptr_t)w[0]; t.mStride = w[1]; t.mCol = w[2]; t.lo = (int64_t)w[3]; t.size = w[4]; t.row0 = w[5];
-        for (int c = 0; c < 4; c++) { t.coef[c] = w[6 + c]; t.busId[c] = w[10 + c]; }
-    }
+    for (uint64_t u = 0; u < L.nF; u++) term_of_words(L.d + SD_TERMS + u * SD_TERM_WORDS, cols + u * SD_COL_SLOTS, L.term[u]);
+    for (uint64_t r = 0; r < L.nR; r++) range_of_words(L.d + SD_TERMS + (L.nF + r) * SD_TERM_WORDS, L.range[r]);
     return true;
 }
 FN(RangeSumDev) {          // (description, elemWords[, stream]): only enqueues
@@ -940,6 +939,81 @@ FN(RangeSum) {
     if (!a.ok) return nullptr;
     for (uint64_t r = 0; r < L.nR; r++) L.range[r].m = mSide[r].base;
     P2(env, (ew == 4 ? pil2gl_bn128_range_sum : pil2gl_range_sum)(L.term, L.nF, L.range, L.nR, L.d + SD_ALPHA, L.d + SD_BETA, ho, L.d[SD_OUT_STRIDE], L.d[SD_OUT_COL], L.n));
+    return mk_undefined(env);
+}
+
+// ---- clustered logUp sum: the im columns and s in one call (csrc/logup_cluster_plan.h; js/pil_checks.js) ----
+FN(LogupClusterPlan) {     // (n, nF, nR, nIm, elemWords) -> { threads, items, blocks, launches, depth, outWidth, workBytes }
+    Args a(env, info); uint64_t n = a.u64(0), nF = a.u64(1), nR = a.u64(2), nIm = a.u64(3); uint32_t ew = (uint32_t)a.u64(4); if (!a.ok) return nullptr;
+    uint32_t out[6]; uint64_t bytes = 0;
+    P2(env, pil2gl_logup_cluster_plan(n, nF, nR, nIm, ew, out, &bytes));
+    static const char *const names[6] = { "threads", "items", "blocks", "launches", "depth", "outWidth" };
+    return plan_object(env, names, out, "workBytes", bytes);
+}
+FN(LogupImColLayout) {     // -> sizeof and offsetof of pil2gl_logup_im_col as this addon was compiled
+    static const char *names[4] = { "size", "base", "stride", "col" };
+    const size_t at[4] = { sizeof(pil2gl_logup_im_col), offsetof(pil2gl_logup_im_col, base), offsetof(pil2gl_logup_im_col, stride), offsetof(pil2gl_logup_im_col, col) };
+    napi_value o, v; napi_create_object(env, &o);
+    for (int i = 0; i < 4; i++) { napi_create_uint32(env, (uint32_t)at[i], &v); napi_set_named_property(env, o, names[i], v); }
+    return o;
+}
+// A call's description, one BigUint64Array: [0] n, [1] nF, [2] nR, [3] nIm, [4] out, [5] outStride, [6] outCol, [7..10] alpha, [11..14] beta
+// (three words used over Goldilocks), then nF terms and nR ranges of rangeSum's 14 words, then nF + nR cluster words (all ones: DIRECT),
+// then nIm im columns of three words -- base, stride, col -- then 16 column slots an f term.  The pointer words are device addresses for
+// logupClusterDev and are not read by logupCluster, which takes the host matrices as an array of its own.
+enum { CD_N, CD_NF, CD_NR, CD_NIM, CD_OUT, CD_OUT_STRIDE, CD_OUT_COL, CD_ALPHA, CD_BETA = CD_ALPHA + 4, CD_TERMS = CD_BETA + 4 };
+struct ClusterDesc { uint64_t *d; uint64_t n, nF, nR, nIm; pil2gl_logup_term term[8]; pil2gl_range_term range[8]; const uint64_t *cluster; pil2gl_logup_im_col im[9]; };
+static bool cluster_desc(Args &a, size_t i, ClusterDesc &L) {
+    uint64_t len = 0; L.d = a.arr(i, CD_TERMS, &len);
+    if (!a.ok) return false;
+    L.n = L.d[CD_N]; L.nF = L.d[CD_NF]; L.nR = L.d[CD_NR]; L.nIm = L.d[CD_NIM];
+    if (L.nF > 8 || L.nR > 8 || L.nIm > 9 || len < CD_TERMS + (L.nF + L.nR) * (SD_TERM_WORDS + 1) + 3 * L.nIm + L.nF * SD_COL_SLOTS)
+        return a.fail("the description holds 15 words, then 0 .. 8 terms and 0 .. 8 ranges of 14 words, a cluster word each, 0 .. 9 im columns of 3 words, then 16 column slots a term");
+    uint64_t *cl = L.d + CD_TERMS + (L.nF + L.nR) * SD_TERM_WORDS, *im = cl + L.nF + L.nR, *cols = im + 3 * L.nIm;
+    for (uint64_t u = 0; u < L.nF; u++) term_of_words(L.d + CD_TERMS + u * SD_TERM_WORDS, cols + u * SD_COL_SLOTS, L.term[u]);
+    for (uint64_t r = 0; r < L.nR; r++) range_of_words(L.d + CD_TERMS + (L.nF + r) * SD_TERM_WORDS, L.range[r]);
+    L.cluster = cl;
+    for (uint64_t c = 0; c < L.nIm; c++) L.im[c] = pil2gl_logup_im_col{ (uint64_t *)(uintptr_t)im[3 * c], im[3 * c + 1], im[3 * c + 2] };
+    return true;
+}
+FN(LogupClusterDev) {      // (description, elemWords[, stream]): only enqueues
+    Args a(env, info); ClusterDesc L; if (!cluster_desc(a, 0, L)) return nullptr;
+    uint32_t ew = (uint32_t)a.u64(1); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_logup_cluster_dev : pil2gl_logup_cluster_dev)(L.term, L.nF, L.range, L.nR, L.cluster, L.im, L.nIm, L.d + CD_ALPHA, L.d + CD_BETA,
+                                                                                  (uint64_t *)(uintptr_t)L.d[CD_OUT], L.d[CD_OUT_STRIDE], L.d[CD_OUT_COL], L.n, a.stream(2)));
+    return mk_undefined(env);
+}
+// (description, matrices, elemWords): matrices = an Array of BigUint64Array, [2 u] the matrix of term u, [2 u + 1] its numerator's or null,
+// [2 (nF + r)] the m matrix of range r and null, [2 (nF + nR + c)] the matrix of im column c and null, then out's matrix; the output
+// matrices are written in place, and outputs of ONE matrix must be given as one array
+FN(LogupCluster) {
+    Args a(env, info); ClusterDesc L; if (!cluster_desc(a, 0, L)) return nullptr;
+    uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
+    if (ew != 1 && ew != 4) { a.fail("elemWords is 1 or 4"); return nullptr; }
+    const uint64_t wide = ew == 1 ? 2 : 0;
+    pil2gl_tuple_side one[17] = {};                  // an m column, an im element's highest word column: sides of one column without a selector
+    uint64_t top[9];
+    pil2gl_tuple_side *sides[25]; uint64_t ks[25];
+    for (uint64_t u = 0; u < L.nF; u++) {
+        sides[u] = &L.term[u].side; ks[u] = L.term[u].k;
+        if (ks[u] < 1 || ks[u] > 16) { a.fail("k must be 1 .. 16 columns"); return nullptr; }
+    }
+    for (uint64_t r = 0; r < L.nR; r++) {
+        one[r].stride = L.range[r].mStride; one[r].hostCols = &L.range[r].mCol;
+        sides[L.nF + r] = &one[r]; ks[L.nF + r] = 1;
+    }
+    for (uint64_t c = 0; c < L.nIm; c++) {
+        top[c] = L.im[c].col + wide;
+        one[8 + c].stride = L.im[c].stride; one[8 + c].hostCols = &top[c];
+        sides[L.nF + L.nR + c] = &one[8 + c]; ks[L.nF + L.nR + c] = 1;
+    }
+    uint64_t *ho = host_matrices(a, sides, ks, L.nF + L.nR + L.nIm, L.n, L.d[CD_OUT_STRIDE], L.d[CD_OUT_COL] + wide, ew,
+                                 "expected a matrix and a numerator's matrix or null for every term, a matrix and null for every range and every im column, then out's matrix");
+    if (!a.ok) return nullptr;
+    for (uint64_t r = 0; r < L.nR; r++) L.range[r].m = one[r].base;
+    for (uint64_t c = 0; c < L.nIm; c++) L.im[c].base = (uint64_t *)one[8 + c].base;
+    P2(env, (ew == 4 ? pil2gl_bn128_logup_cluster : pil2gl_logup_cluster)(L.term, L.nF, L.range, L.nR, L.cluster, L.im, L.nIm, L.d + CD_ALPHA, L.d + CD_BETA, ho,
+                                                                          L.d[CD_OUT_STRIDE], L.d[CD_OUT_COL], L.n));
     return mk_undefined(env);
 }
 
@@ -1287,6 +1361,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "rangeMultPlan", RangeMultPlan }, { "rangeMultDev", RangeMultDev }, { "rangeMult", RangeMult },
         { "logupSumPlan", LogupSumPlan }, { "logupTermLayout", LogupTermLayout }, { "logupSumDev", LogupSumDev }, { "logupSum", LogupSum },
         { "rangeSumPlan", RangeSumPlan }, { "rangeTermLayout", RangeTermLayout }, { "rangeSumDev", RangeSumDev }, { "rangeSum", RangeSum },
+        { "logupClusterPlan", LogupClusterPlan }, { "logupImColLayout", LogupImColLayout }, { "logupClusterDev", LogupClusterDev }, { "logupCluster", LogupCluster },
         { "grandProdPlan", GrandProdPlan }, { "grandProdTermLayout", GrandProdTermLayout }, { "grandProdDev", GrandProdDev }, { "grandProd", GrandProd },
         { "plookupPlan", PlookupPlan }, { "plookupFoldDev", PlookupFoldDev }, { "plookupFold", PlookupFold }, { "plookupProdDev", PlookupProdDev }, { "plookupProd", PlookupProd },
         { "buildXDev", BuildXDev }, { "buildZhInvDev", BuildZhInvDev }, { "buildOneRowZerofierInvDev", BuildOneRowZerofierInvDev },

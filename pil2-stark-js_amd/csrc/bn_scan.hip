@@ -8,6 +8,7 @@
 //     gsum_col        s[i] = s[i - 1] + num[i] / den[i]                              (num: a column, as gprod's)
 //     logup_sum       the lookup grand sum of include/pil2gl.h: gsum_col over a row's terms folded into one fraction (near the end of this file)
 //     range_sum       that sum with the table side of a range check given as numbers, no t column (behind it)
+//     logup_cluster   those sums with the terms gathered into clusters: s and one im column a cluster (behind them)
 //     grand_prod      the grand product of a permutation or a connection: gprod over a row's terms multiplied into N and D (near the end)
 //     plookup         pil1's plookup argument: the fold of F and T, and gprod over a row's num and den made from f, t, h1, h2 (at the end)
 //
@@ -44,6 +45,7 @@
 #include "bn_scan_plan.h"
 #include "logup_sum_plan.h"
 #include "range_sum_plan.h"
+#include "logup_cluster_plan.h"
 #include "grand_prod_plan.h"
 #include "plookup_plan.h"
 #include "tuple_side.cuh"
@@ -509,12 +511,25 @@ struct FrRangeJob {
     FrField::Mem *D, *N;                             // dense, n elements each
 };
 
+// one range of row i folded into the row's fraction N / D: the loop body of bn_range_compress_kernel below as a function, for the clustered
+// sum's kernels (that kernel keeps its own copy: calling this one there moved its register count; a fix here belongs there too)
+__device__ __forceinline__ void fr_range_fold(const FrRangeTerm &T, u64 i, const FrE &alphaR2, const FrE &beta, FrE &N, FrE &D) {
+    if (i < T.row0 || i >= T.end) return;             // outside the window: adds 0, m is not read.  end <= n
+    FrE v = { { (u32)(i - T.row0), 0, 0, 0, 0, 0, 0, 0 } };                        // j < 2^28
+    v = FrField::add(v, T.lo);                        // field(lo + j), both below r
+    FrE d = FrField::add(FrField::add(FrField::mul(alphaR2, v), FrField::reduce(T.bus)), beta);
+    if (bn::is_zero(d.v)) return;                     // a zero E_r: the range adds 0 and is left out of the product
+    const FrE c = FrField::mul(FrField::load(T.m, i * T.stride + T.col), FrField::reduce(T.coef));
+    N = FrField::add(FrField::mul(N, d), FrField::mul(D, c));
+    D = FrField::mul(D, d);
+}
+
 __global__ void __launch_bounds__(smapplan::THREADS) bn_range_compress_kernel(const FrRangeJob J) {
     const FrE alpha = FrField::reduce(J.alpha), beta = FrField::reduce(J.beta);
     for (u64 i = (u64)blockIdx.x * smapplan::THREADS + threadIdx.x; i < J.n; i += (u64)gridDim.x * smapplan::THREADS) {
         FrE N{}, D = J.one;
         for (u32 u = 0; u < J.nTerms; u++) fr_logup_fold(J.t[u], i, alpha, beta, N, D);
-        for (u32 r = 0; r < J.nRanges; r++) {
+        for (u32 r = 0; r < J.nRanges; r++) {           // fr_range_fold above is this body as a function: a fix here belongs there too
             const FrRangeTerm &T = J.r[r];
             if (i < T.row0 || i >= T.end) continue;   // outside the window: adds 0, m is not read.  end <= n
             FrE v = { { (u32)(i - T.row0), 0, 0, 0, 0, 0, 0, 0 } };                // j < 2^28
@@ -530,13 +545,8 @@ __global__ void __launch_bounds__(smapplan::THREADS) bn_range_compress_kernel(co
     }
 }
 
-// every launch of a call, on st; the arguments have passed rangesumplan::check_call() and n > 0, the pointers are the device's
-int bn_range_sum_launch(const pil2gl_logup_term *terms, u32 nF, const pil2gl_range_term *ranges, u32 nR, const u64 *alpha, const u64 *beta, u64 *out,
-                        u64 outStride, u64 outCol, u64 n, hipStream_t st) {
-    const bnscan::Plan p = bnscan::plan(n, false);
-    u64 *d;
-    P2_TRY(scratch(SCR_BN_SCAN, 4 * p.elems + 8 * n, &d));        // the plan's levels, then D and N
-    FrRangeJob J{};
+// a job's tables and constants from the entry's terms and ranges, their pointers the device's
+void fill_range_job(FrRangeJob &J, const pil2gl_logup_term *terms, u32 nF, const pil2gl_range_term *ranges, u32 nR, const u64 *alpha, const u64 *beta, u64 n) {
     for (u32 u = 0; u < nF; u++) fill_term(J.t[u], terms[u]);
     for (u32 r = 0; r < nR; r++) {
         const pil2gl_range_term &R = ranges[r];
@@ -549,6 +559,16 @@ int bn_range_sum_launch(const pil2gl_logup_term *terms, u32 nF, const pil2gl_ran
     const bnp::U256 a = { { alpha[0], alpha[1], alpha[2], alpha[3] } };
     bnp::bn_limbs(alpha, J.alpha.v); bnp::bn_limbs(bnp::h_to_mont(a).w, J.alphaR2.v); bnp::bn_limbs(beta, J.beta.v); bnp::bn_limbs(bnp::bn_mont_one().w, J.one.v);
     J.nTerms = nF; J.nRanges = nR; J.n = n;
+}
+
+// every launch of a call, on st; the arguments have passed rangesumplan::check_call() and n > 0, the pointers are the device's
+int bn_range_sum_launch(const pil2gl_logup_term *terms, u32 nF, const pil2gl_range_term *ranges, u32 nR, const u64 *alpha, const u64 *beta, u64 *out,
+                        u64 outStride, u64 outCol, u64 n, hipStream_t st) {
+    const bnscan::Plan p = bnscan::plan(n, false);
+    u64 *d;
+    P2_TRY(scratch(SCR_BN_SCAN, 4 * p.elems + 8 * n, &d));        // the plan's levels, then D and N
+    FrRangeJob J{};
+    fill_range_job(J, terms, nF, ranges, nR, alpha, beta, n);
     J.D = (FrField::Mem *)(d + 4 * p.elems); J.N = J.D + n;
     bn_range_compress_kernel<<<smapplan::blocks(n), smapplan::THREADS, 0, st>>>(J);
     KERNEL_CHECK();
@@ -599,6 +619,139 @@ int pil2gl_bn128_range_sum(const pil2gl_logup_term *hostTerms, uint64_t nF, cons
     P2_TRY(s.rc());
     P2_TRY(bn_range_sum_launch(terms, (u32)nF, ranges, (u32)nR, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0));
     return s.get(hostOut, dOut, outWords);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The clustered logUp sum over Fr (include/pil2gl.h states it): the two sums above with the terms gathered into clusters, im_c[i] the part
+// of cluster c in row i's increment, written as a column of its own beside s.  Working memory must not grow with nIm, so no D_c column is
+// written: ONE product column P and one inversion a call,
+//   bn_cluster_prod_kernel     a lane a row: P[i] = the product of the row's non-zero denominators over every cluster and the DIRECT part
+//                              (the folds above with the numerator unused), 32 bytes a row into the working buffer
+//   inverse_launch(MODE_NONE)  1 / P into the output column, its prefixes there meanwhile; one Fermat ladder a call
+//   bn_cluster_refold_kernel   a lane a row REFOLDS the row, group by group (the clusters, then the DIRECT part if there is one): group g
+//                              gives N_g / D_g; going up it keeps X_g = N_g prod_{h < g} D_h and D_g in registers, going down r = (1 / P)
+//                              prod_{h > g} D_h = 1 / prod_{h <= g} D_h, so that X_g r = N_g / D_g: 1 / D_g peeled off 1 / P with the
+//                              prefix and the suffix products, 4 products a group.  Writes every im_c and the row's increment into out
+//   scan_launch<true>          sums out in place
+// The refold costs k + 4 products a term again, cheaper than the 64 bytes a cluster-row that D_c and N_c columns would be written and read
+// with.  The per-group registers are indexed by compile-time constants (each_group) and stay out of the private segment.
+// Safety: nothing read from a matrix is used as an address; a lane's row is below n; the group of a term is a wave-uniform kernel-argument read.
+namespace {
+
+using logupclusterplan::MAX_GROUPS;
+
+struct FrImCol { FrField::Mem *base; u64 stride, col; };
+struct FrClusterJob : FrRangeJob {                   // D: the product column P; N unused
+    FrImCol im[logupclusterplan::MAX_IM];
+    u32 group[logupplan::MAX_TERMS];                 // the group of term u (f terms, then ranges): its cluster, or nIm for a DIRECT term
+    u32 nIm, nGroups;                                // nGroups: nIm, + 1 with a DIRECT term.  Every group has a term
+    FrField::Mem *out; u64 outStride, outCol;
+};
+
+template <class Fn, int... G> __device__ __forceinline__ void each_group(Fn f, std::integer_sequence<int, G...>) { (f(std::integral_constant<int, G>{}), ...); }
+template <class Fn> __device__ __forceinline__ void each_group(Fn f) { each_group(f, std::make_integer_sequence<int, (int)MAX_GROUPS>{}); }
+
+__global__ void __launch_bounds__(smapplan::THREADS) bn_cluster_prod_kernel(const FrClusterJob J) {
+    const FrE alpha = FrField::reduce(J.alpha), beta = FrField::reduce(J.beta);
+    for (u64 i = (u64)blockIdx.x * smapplan::THREADS + threadIdx.x; i < J.n; i += (u64)gridDim.x * smapplan::THREADS) {
+        FrE N{}, D = J.one;
+        for (u32 u = 0; u < J.nTerms; u++) fr_logup_fold(J.t[u], i, alpha, beta, N, D);
+        for (u32 r = 0; r < J.nRanges; r++) fr_range_fold(J.r[r], i, J.alphaR2, beta, N, D);
+        FrField::store(J.D, i, D);
+    }
+}
+
+__global__ void __launch_bounds__(smapplan::THREADS) bn_cluster_refold_kernel(const FrClusterJob J) {
+    const FrE alpha = FrField::reduce(J.alpha), beta = FrField::reduce(J.beta);
+    for (u64 i = (u64)blockIdx.x * smapplan::THREADS + threadIdx.x; i < J.n; i += (u64)gridDim.x * smapplan::THREADS) {
+        u32 X[MAX_GROUPS][8] = {}, Dg[MAX_GROUPS][8] = {};      // written and read with selects on the wave-uniform g, never with an index
+        FrE pre = J.one;                              // the product of the groups' D below g
+        for (u32 g = 0; g < J.nGroups; g++) {
+            FrE N{}, D = J.one;                       // every group anew
+            for (u32 u = 0; u < J.nTerms; u++) if (J.group[u] == g) fr_logup_fold(J.t[u], i, alpha, beta, N, D);
+            for (u32 r = 0; r < J.nRanges; r++) if (J.group[J.nTerms + r] == g) fr_range_fold(J.r[r], i, J.alphaR2, beta, N, D);
+            const FrE x = FrField::mul(N, pre);
+            each_group([&](auto G) {
+#pragma unroll
+                for (int l = 0; l < 8; l++) { X[G][l] = G == g ? x.v[l] : X[G][l]; Dg[G][l] = G == g ? D.v[l] : Dg[G][l]; }
+            });
+            pre = FrField::mul(pre, D);
+        }
+        FrE r = FrField::load(J.out, i * J.outStride + J.outCol);                // 1 / P[i]
+        FrE inc{};
+        for (u32 g = J.nGroups; g-- > 0;) {
+            FrE x{}, d{};
+            each_group([&](auto G) {
+#pragma unroll
+                for (int l = 0; l < 8; l++) { x.v[l] = G == g ? X[G][l] : x.v[l]; d.v[l] = G == g ? Dg[G][l] : d.v[l]; }
+            });
+            const FrE v = FrField::mul(x, r);         // N_g / D_g: r = 1 / (the product of the groups' D up to g)
+            r = FrField::mul(r, d);
+            if (g < J.nIm) FrField::store(J.im[g].base, i * J.im[g].stride + J.im[g].col, v);
+            inc = FrField::add(inc, v);
+        }
+        FrField::store(J.out, i * J.outStride + J.outCol, inc);
+    }
+}
+
+// every launch of a call, on st; the arguments have passed logupclusterplan::check_call() and n > 0, the pointers are the device's
+int bn_cluster_launch(const pil2gl_logup_term *terms, u32 nF, const pil2gl_range_term *ranges, u32 nR, const u64 *cluster, const pil2gl_logup_im_col *im,
+                      u32 nIm, const u64 *alpha, const u64 *beta, u64 *out, u64 outStride, u64 outCol, u64 n, hipStream_t st) {
+    const bnscan::Plan p = bnscan::plan(n, false);
+    u64 *d;
+    P2_TRY(scratch(SCR_BN_SCAN, 4 * p.elems + 4 * n, &d));        // the plan's levels, then P
+    FrClusterJob J{};
+    fill_range_job(J, terms, nF, ranges, nR, alpha, beta, n);
+    J.D = (FrField::Mem *)(d + 4 * p.elems);
+    J.nIm = J.nGroups = nIm;
+    for (u32 u = 0; u < nF + nR; u++) {
+        J.group[u] = cluster[u] == logupclusterplan::DIRECT ? nIm : (u32)cluster[u];
+        if (J.group[u] == nIm) J.nGroups = nIm + 1;
+    }
+    for (u32 c = 0; c < nIm; c++) J.im[c] = FrImCol{ (FrField::Mem *)im[c].base, im[c].stride, im[c].col };
+    J.out = (FrField::Mem *)out; J.outStride = outStride; J.outCol = outCol;
+    bn_cluster_prod_kernel<<<smapplan::blocks(n), smapplan::THREADS, 0, st>>>(J);
+    KERNEL_CHECK();
+    uint4 *base = (uint4 *)d, *y = (uint4 *)(out + 4 * outCol);
+    P2_TRY(inverse_launch(p, base, (const uint4 *)J.D, 1, y, outStride, y, outStride, MODE_NONE, nullptr, 0, Elem{}, st));
+    bn_cluster_refold_kernel<<<smapplan::blocks(n), smapplan::THREADS, 0, st>>>(J);
+    KERNEL_CHECK();
+    return scan_launch<true>(p, base, y, outStride, st);
+}
+
+int bn_cluster_check(const pil2gl_logup_term *terms, u64 nF, const pil2gl_range_term *ranges, u64 nR, const u64 *cluster, const pil2gl_logup_im_col *im, u64 nIm,
+                     const u64 *alpha, const u64 *beta, const u64 *out, u64 outStride, u64 outCol, u64 n, bool dev) {
+    char why[96];
+    if (const char *msg = logupclusterplan::check_call(terms, nF, ranges, nR, cluster, im, nIm, alpha, beta, out, outStride, outCol, n, 4, dev, why))
+        return fail(PIL2GL_EINVAL, "%s", msg);
+    return PIL2GL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_bn128_logup_cluster_dev(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR, const uint64_t *hostCluster,
+                                   const pil2gl_logup_im_col *hostIm, uint64_t nIm, const uint64_t *hostAlpha, const uint64_t *hostBeta, uint64_t *out,
+                                   uint64_t outStride, uint64_t outCol, uint64_t n, void *stream) {
+    P2_TRY(bn_cluster_check(hostTerms, nF, hostRanges, nR, hostCluster, hostIm, nIm, hostAlpha, hostBeta, out, outStride, outCol, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return bn_cluster_launch(hostTerms, (u32)nF, hostRanges, (u32)nR, hostCluster, hostIm, (u32)nIm, hostAlpha, hostBeta, out, outStride, outCol, n, as_stream(stream));
+}
+
+// host matrices: logupclusterplan::host_form stages them, the read ones as range_sum's, every distinct output matrix as it is
+int pil2gl_bn128_logup_cluster(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR, const uint64_t *hostCluster,
+                               const pil2gl_logup_im_col *hostIm, uint64_t nIm, const uint64_t *hostAlpha, const uint64_t *hostBeta, uint64_t *hostOut,
+                               uint64_t outStride, uint64_t outCol, uint64_t n) {
+    P2_TRY(bn_cluster_check(hostTerms, nF, hostRanges, nR, hostCluster, hostIm, nIm, hostAlpha, hostBeta, hostOut, outStride, outCol, n, false));
+    if (!n) return PIL2GL_OK;
+    return logupclusterplan::host_form<Stage>(hostTerms, nF, hostRanges, nR, hostIm, nIm, hostOut, outStride, outCol, n, 4,
+        [&](const pil2gl_logup_term *t, const pil2gl_range_term *r, const pil2gl_logup_im_col *im, u64 *dOut) {
+            return bn_cluster_launch(t, (u32)nF, r, (u32)nR, hostCluster, im, (u32)nIm, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0);
+        });
 }
 
 }  // extern "C"

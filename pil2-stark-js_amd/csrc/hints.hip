@@ -13,6 +13,7 @@
 #include "hint_plan.h"
 #include "logup_sum_plan.h"
 #include "range_sum_plan.h"
+#include "logup_cluster_plan.h"
 #include "grand_prod_plan.h"
 #include "plookup_plan.h"
 #include <utility>
@@ -209,10 +210,13 @@ template <class Fn> __device__ __forceinline__ void each_item_down(Fn f) { each_
 
 // the f terms of a lane's rows folded into its fractions num / den (den never zero; rows at or past n stay as they are).  The terms are the
 // outer loop, so that a term's table entries are read once for the lane's rows and the rows' loads of one column are in flight together.
-// Job: a kernel argument with t[], nTerms, apow[] and n, read with wave-uniform indices
-template <class Job>
-__device__ __forceinline__ void logup_fold(const Job &J, u64 base, E3 (&num)[SCAN_ITEMS], E3 (&den)[SCAN_ITEMS], E3 (&loc)[SCAN_ITEMS]) {
+// Job: a kernel argument with t[], nTerms, apow[] and n, read with wave-uniform indices.  keep(u): whether term u takes part (cluster_scan1
+// folds one cluster at a time; the other two passes fold every term)
+struct EveryTerm { __device__ __forceinline__ bool operator()(u32) const { return true; } };
+template <class Job, class Keep = EveryTerm>
+__device__ __forceinline__ void logup_fold(const Job &J, u64 base, E3 (&num)[SCAN_ITEMS], E3 (&den)[SCAN_ITEMS], E3 (&loc)[SCAN_ITEMS], Keep keep = Keep{}) {
     for (u32 u = 0; u < J.nTerms; u++) {
+        if (!keep(u)) continue;
         const LogupTerm &T = J.t[u];
         const E3 cst = T.cst;
         each_item([&](auto k) { loc[k] = cst; });
@@ -231,9 +235,8 @@ __device__ __forceinline__ void logup_fold(const Job &J, u64 base, E3 (&num)[SCA
         });
     }
 }
-// the lane's fractions to ratios with one inversion, their running sum, the block-local scan into tmp and the block's total
-__device__ __forceinline__ void logup_finish(E3 (&num)[SCAN_ITEMS], E3 (&den)[SCAN_ITEMS], E3 (&loc)[SCAN_ITEMS], E3 *sh, u64 base, u64 n,
-                                             u64 *__restrict__ tmp, u64 *__restrict__ totals) {
+// the lane's fractions to ratios in loc with one inversion
+__device__ __forceinline__ void logup_ratios(E3 (&num)[SCAN_ITEMS], E3 (&den)[SCAN_ITEMS], E3 (&loc)[SCAN_ITEMS]) {
     E3 acc = ident<true>();
     each_item([&](auto k) {
         loc[k] = acc;                                   // the product of the rows' den before this one
@@ -245,12 +248,20 @@ __device__ __forceinline__ void logup_finish(E3 (&num)[SCAN_ITEMS], E3 (&den)[SC
         ai = e3_mul(ai, den[k]);
         loc[k] = e3_mul(num[k], di);
     });
+}
+// the running sum of the lane's ratios in loc, the block-local scan into tmp and the block's total
+__device__ __forceinline__ void logup_tail(E3 (&loc)[SCAN_ITEMS], E3 *sh, u64 base, u64 n, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
     E3 run = ident<false>();
     each_item([&](auto k) { run = e3_add(run, loc[k]); loc[k] = run; });      // rows at or past n hold num = 0
     E3 bt;
     const E3 ex = block_exclusive<false>(run, sh, &bt);
     each_item([&](auto k) { const u64 i = base + k; if (i < n) st3(tmp, i, e3_add(ex, loc[k])); });
     if (threadIdx.x == 0) st3(totals, blockIdx.x, bt);
+}
+__device__ __forceinline__ void logup_finish(E3 (&num)[SCAN_ITEMS], E3 (&den)[SCAN_ITEMS], E3 (&loc)[SCAN_ITEMS], E3 *sh, u64 base, u64 n,
+                                             u64 *__restrict__ tmp, u64 *__restrict__ totals) {
+    logup_ratios(num, den, loc);
+    logup_tail(loc, sh, base, n, tmp, totals);
 }
 
 __global__ void __launch_bounds__(SCAN_THREADS) logup_scan1(const LogupJob J, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
@@ -383,14 +394,13 @@ struct RangeJob {
     u64 n;
 };
 
-__global__ void __launch_bounds__(SCAN_THREADS) range_scan1(const RangeJob J, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
-    __shared__ E3 sh[SCAN_THREADS];
-    const u64 base = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_ITEMS;
-    E3 num[SCAN_ITEMS], den[SCAN_ITEMS], loc[SCAN_ITEMS];
-    each_item([&](auto k) { num[k] = ident<false>(); den[k] = ident<true>(); });
-    logup_fold(J, base, num, den, loc);
+// the ranges of a lane's rows folded into its fractions, as logup_fold folds the f terms.  Job: with r[], nRanges and apow[] besides;
+// keep(r): whether range r takes part
+template <class Job, class Keep = EveryTerm>
+__device__ __forceinline__ void range_fold(const Job &J, u64 base, E3 (&num)[SCAN_ITEMS], E3 (&den)[SCAN_ITEMS], E3 (&loc)[SCAN_ITEMS], Keep keep = Keep{}) {
     const E3 alpha = J.apow[1];
     for (u32 r = 0; r < J.nRanges; r++) {
+        if (!keep(r)) continue;
         const RangeTermD &T = J.r[r];
         const u64 row0 = T.row0, end = T.end, coef = T.coef;
         const u64 first = base > row0 ? base : row0;                            // the lane's first in-window row, if it has one
@@ -407,14 +417,21 @@ __global__ void __launch_bounds__(SCAN_THREADS) range_scan1(const RangeJob J, u6
             den[k] = e3_mul(den[k], d);
         });
     }
+}
+
+__global__ void __launch_bounds__(SCAN_THREADS) range_scan1(const RangeJob J, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
+    __shared__ E3 sh[SCAN_THREADS];
+    const u64 base = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_ITEMS;
+    E3 num[SCAN_ITEMS], den[SCAN_ITEMS], loc[SCAN_ITEMS];
+    each_item([&](auto k) { num[k] = ident<false>(); den[k] = ident<true>(); });
+    logup_fold(J, base, num, den, loc);
+    range_fold(J, base, num, den, loc);
     logup_finish(num, den, loc, sh, base, J.n, tmp, totals);
 }
 
-// every launch of a call, on st; the arguments have passed rangesumplan::check_call() and n > 0, the pointers are the device's
-int range_sum_launch(const pil2gl_logup_term *terms, u32 nF, const pil2gl_range_term *ranges, u32 nR, const u64 *alpha, const u64 *beta, u64 *out,
-                     u64 outStride, u64 outCol, u64 n, hipStream_t st) {
-    RangeJob J{};
-    logup_fill(J, terms, nF, alpha, beta, n);
+// a job's ranges: each range's table entry with its host-made constant
+template <class Job>
+void range_fill(Job &J, const pil2gl_range_term *ranges, u32 nR, const u64 *alpha, const u64 *beta) {
     const u64 a[3] = { h_canon(alpha[0]), h_canon(alpha[1]), h_canon(alpha[2]) }, b[3] = { h_canon(beta[0]), h_canon(beta[1]), h_canon(beta[2]) };
     for (u32 r = 0; r < nR; r++) {
         const pil2gl_range_term &R = ranges[r];
@@ -423,6 +440,14 @@ int range_sum_launch(const pil2gl_logup_term *terms, u32 nF, const pil2gl_range_
         rangesumplan::gl_c0(R, a, b, h_mul, h_add, T.c0.v);
     }
     J.nRanges = nR;
+}
+
+// every launch of a call, on st; the arguments have passed rangesumplan::check_call() and n > 0, the pointers are the device's
+int range_sum_launch(const pil2gl_logup_term *terms, u32 nF, const pil2gl_range_term *ranges, u32 nR, const u64 *alpha, const u64 *beta, u64 *out,
+                     u64 outStride, u64 outCol, u64 n, hipStream_t st) {
+    RangeJob J{};
+    logup_fill(J, terms, nF, alpha, beta, n);
+    range_fill(J, ranges, nR, alpha, beta);
     const u64 nb = hintplan::blocks(n);
     u64 *tmp, *totals;
     P2_TRY(scratch(SCR_HINT_TMP, n * 3, &tmp));
@@ -490,6 +515,125 @@ int pil2gl_range_sum(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2
     P2_TRY(s.rc());
     P2_TRY(range_sum_launch(terms, (u32)nF, ranges, (u32)nR, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0));
     return s.get(hostOut, dOut, outWords);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The clustered logUp sum (include/pil2gl.h states it; tests/logup_cluster_ref.py restates it over integers): the two sums above with the
+// terms gathered into clusters, each cluster's part of a row written as a column of its own,
+//   im_c[i] = sum_{cluster[u] = c} frac_u[i],     s[i] = s[i-1] + sum_c im_c[i] + sum_{cluster[u] = DIRECT} frac_u[i].
+// One fused first pass, cluster_scan1, beside logup_scan1 and range_scan1; then hint_scan2<false> and hint_scan3<false> as they are.  The
+// GROUPS are the outer loop -- the clusters 0 .. nIm - 1, then the DIRECT terms if there are any.  For a group the lane folds the group's
+// terms of its SCAN_ITEMS rows into fractions num / den with logup_fold and range_fold (a zero denominator is left out, so den is never
+// zero), turns them into ratios with ONE e3_inv (logup_ratios), stores them as im_c unless the group is the DIRECT one, and adds them into
+// a per-row accumulator; logup_tail then runs the sum over the accumulator.  A row's terms are each folded once, as in the passes above:
+// what the im columns add is an e3_inv a lane-group where those passes have one a lane, the ratio's products a group-row, and 24 bytes
+// stored a cluster-row.  The cluster ids travel in the kernel argument and are read with wave-uniform indices.
+// Safety: nothing read from a matrix is used as an address; a row index is checked against n before any load or store.
+namespace {
+
+using logupclusterplan::MAX_GROUPS;
+
+struct ImColD { u64 *base; u64 stride, col; };
+struct ClusterJob : RangeJob {
+    ImColD im[logupclusterplan::MAX_IM];
+    u32 group[MAX_TERMS];                            // the group of term u (f terms, then ranges): its cluster, or nIm for a DIRECT term
+    u32 nIm, nGroups;                                // nGroups: nIm, + 1 with a DIRECT term.  Every group has a term
+};
+
+__global__ void __launch_bounds__(SCAN_THREADS) cluster_scan1(const ClusterJob J, u64 *__restrict__ tmp, u64 *__restrict__ totals) {
+    __shared__ E3 sh[SCAN_THREADS];
+    const u64 base = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_ITEMS;
+    E3 num[SCAN_ITEMS], den[SCAN_ITEMS], loc[SCAN_ITEMS], sum[SCAN_ITEMS];
+    each_item([&](auto k) { sum[k] = ident<false>(); });
+    for (u32 g = 0; g < J.nGroups; g++) {
+        each_item([&](auto k) { num[k] = ident<false>(); den[k] = ident<true>(); });      // every row anew: a group starts from 0 / 1
+        logup_fold(J, base, num, den, loc, [&](u32 u) { return J.group[u] == g; });
+        range_fold(J, base, num, den, loc, [&](u32 r) { return J.group[J.nTerms + r] == g; });
+        logup_ratios(num, den, loc);                    // rows at or past n hold 0 / 1: ratio 0
+        if (g < J.nIm) {
+            const ImColD &C = J.im[g];
+            u64 *p = C.base + base * C.stride + C.col;
+            each_item([&](auto k) {
+                if (base + k >= J.n) return;
+                u64 *o = p + k * C.stride;
+                o[0] = loc[k].v[0]; o[1] = loc[k].v[1]; o[2] = loc[k].v[2];
+            });
+        }
+        each_item([&](auto k) { sum[k] = e3_add(sum[k], loc[k]); });
+    }
+    logup_tail(sum, sh, base, J.n, tmp, totals);
+}
+
+// every launch of a call, on st; the arguments have passed logupclusterplan::check_call() and n > 0, the pointers are the device's
+int cluster_launch(const pil2gl_logup_term *terms, u32 nF, const pil2gl_range_term *ranges, u32 nR, const u64 *cluster, const pil2gl_logup_im_col *im,
+                   u32 nIm, const u64 *alpha, const u64 *beta, u64 *out, u64 outStride, u64 outCol, u64 n, hipStream_t st) {
+    ClusterJob J{};
+    logup_fill(J, terms, nF, alpha, beta, n);
+    range_fill(J, ranges, nR, alpha, beta);
+    J.nIm = J.nGroups = nIm;
+    for (u32 u = 0; u < nF + nR; u++) {
+        J.group[u] = cluster[u] == logupclusterplan::DIRECT ? nIm : (u32)cluster[u];
+        if (J.group[u] == nIm) J.nGroups = nIm + 1;
+    }
+    for (u32 c = 0; c < nIm; c++) J.im[c] = ImColD{ im[c].base, im[c].stride, im[c].col };
+    const u64 nb = hintplan::blocks(n);
+    u64 *tmp, *totals;
+    P2_TRY(scratch(SCR_HINT_TMP, n * 3, &tmp));
+    P2_TRY(scratch(SCR_HINT_TOTALS, nb * 3, &totals));
+    cluster_scan1<<<(unsigned)nb, SCAN_THREADS, 0, st>>>(J, tmp, totals);
+    KERNEL_CHECK();
+    hint_scan2<false><<<1, SCAN_THREADS, 0, st>>>(totals, nb);
+    KERNEL_CHECK();
+    hint_scan3<false><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tmp, totals, n, 3, out, outStride, outCol);
+    KERNEL_CHECK();
+    return PIL2GL_OK;
+}
+
+int cluster_check(const pil2gl_logup_term *terms, u64 nF, const pil2gl_range_term *ranges, u64 nR, const u64 *cluster, const pil2gl_logup_im_col *im, u64 nIm,
+                  const u64 *alpha, const u64 *beta, const u64 *out, u64 outStride, u64 outCol, u64 n, bool dev) {
+    char why[96];
+    if (const char *msg = logupclusterplan::check_call(terms, nF, ranges, nR, cluster, im, nIm, alpha, beta, out, outStride, outCol, n, 1, dev, why))
+        return fail(PIL2GL_EINVAL, "%s", msg);
+    return PIL2GL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pil2gl_logup_cluster_plan(uint64_t n, uint64_t nF, uint64_t nR, uint64_t nIm, uint32_t elemWords, uint32_t *outInfo, uint64_t *workBytes) {
+    if (workBytes) *workBytes = 0;
+    if (const char *msg = logupclusterplan::check(n, nF, nR, nIm, elemWords)) return fail(PIL2GL_EINVAL, "%s", msg);
+    const logupclusterplan::Plan p = logupclusterplan::plan(n, elemWords);
+    if (outInfo) {
+        outInfo[0] = p.threads; outInfo[1] = p.items; outInfo[2] = p.blocks; outInfo[3] = p.launches; outInfo[4] = p.depth;
+        outInfo[5] = logupplan::out_width(elemWords);
+    }
+    if (workBytes) *workBytes = p.bytes;
+    return PIL2GL_OK;
+}
+
+int pil2gl_logup_cluster_dev(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR, const uint64_t *hostCluster,
+                             const pil2gl_logup_im_col *hostIm, uint64_t nIm, const uint64_t *hostAlpha, const uint64_t *hostBeta, uint64_t *out,
+                             uint64_t outStride, uint64_t outCol, uint64_t n, void *stream) {
+    P2_TRY(cluster_check(hostTerms, nF, hostRanges, nR, hostCluster, hostIm, nIm, hostAlpha, hostBeta, out, outStride, outCol, n, true));
+    if (!n) return PIL2GL_OK;
+    P2_TRY(ensure_init());
+    return cluster_launch(hostTerms, (u32)nF, hostRanges, (u32)nR, hostCluster, hostIm, (u32)nIm, hostAlpha, hostBeta, out, outStride, outCol, n, as_stream(stream));
+}
+
+// host matrices: logupclusterplan::host_form stages them, the read ones as range_sum's, every distinct output matrix as it is
+int pil2gl_logup_cluster(const pil2gl_logup_term *hostTerms, uint64_t nF, const pil2gl_range_term *hostRanges, uint64_t nR, const uint64_t *hostCluster,
+                         const pil2gl_logup_im_col *hostIm, uint64_t nIm, const uint64_t *hostAlpha, const uint64_t *hostBeta, uint64_t *hostOut,
+                         uint64_t outStride, uint64_t outCol, uint64_t n) {
+    P2_TRY(cluster_check(hostTerms, nF, hostRanges, nR, hostCluster, hostIm, nIm, hostAlpha, hostBeta, hostOut, outStride, outCol, n, false));
+    if (!n) return PIL2GL_OK;
+    return logupclusterplan::host_form<Stage>(hostTerms, nF, hostRanges, nR, hostIm, nIm, hostOut, outStride, outCol, n, 1,
+        [&](const pil2gl_logup_term *t, const pil2gl_range_term *r, const pil2gl_logup_im_col *im, u64 *dOut) {
+            return cluster_launch(t, (u32)nF, r, (u32)nR, hostCluster, im, (u32)nIm, hostAlpha, hostBeta, dOut, outStride, outCol, n, 0);
+        });
 }
 
 }  // extern "C"

@@ -37,6 +37,10 @@
 //       logupSum with the table side of a range check given as numbers (csrc/range_sum_plan.h): terms: 0 .. 8 f terms as above; ranges:
 //       1 .. 8 of { m: { buf, stride, col }, lo, size, row0, coef, busId } -- lo a BigInt or an integer (signed 64-bit), coef and busId as a
 //       term's.  No t column exists; outside rows row0 .. row0 + size - 1 a range adds 0 and m is not read.  rangeSumDev only enqueues.
+//   logupCluster(terms, ranges, cluster, im, alpha, beta, out, n, opts) / logupClusterDev(..) / logupClusterPlan(n, nF, nR, nIm, bn128)
+//       s AND one im column a cluster in one call (csrc/logup_cluster_plan.h): terms and ranges as above, either may be empty; cluster: an
+//       entry a term, f terms first, 0 .. im.length - 1 or DIRECT; im: { buf, stride, col } a cluster, of out's shape.  s and the im columns
+//       are normally columns of one matrix: give the same buf.  logupClusterDev only enqueues.
 //   grandProduct(terms, alpha, beta, gamma, out, n, opts) / grandProductDev(..) / grandProductPlan(n, nTerms, sumK, bn128)
 //       the column z of a permutation or a connection from the trace columns (include/pil2gl.h states it); permutationTerms and
 //       connectionTerms build the term lists of the reference's two identities
@@ -280,6 +284,61 @@ const rangeSum = (terms, ranges, alpha, beta, out, n, opts) => rangeLogup(false,
 const rangeSumDev = (terms, ranges, alpha, beta, out, n, opts) => rangeLogup(true, terms, ranges, alpha, beta, out, n, opts);
 const rangeSumPlan = (n, nF, nR, bn128) => addon.rangeSumPlan(n, nF, nR, bn128 ? 4 : 1);
 
+// ---- clustered logUp sum: s and one im column a cluster ----
+// terms and ranges as rangeSum's (either may be empty); cluster: an entry a term, f terms first, a cluster id or DIRECT; im: one
+// { buf, stride, col } a cluster.  A host buffer given twice (s and its im columns in one matrix) is ONE matrix: converted once, written once.
+const DIRECT = NONE;
+function logupClustered(dev, termsIn, rangesIn, clusterIn, imIn, alpha, beta, outIn, n, opts) {
+    const bn = !!(opts && opts.bn128), ew = bn ? 4 : 1, width = bn ? 1 : 3;
+    if (!Array.isArray(termsIn) || termsIn.length > 8) throw new Error("terms must be an array of 0 .. 8 terms");
+    if (!Array.isArray(rangesIn) || rangesIn.length > 8 || termsIn.length + rangesIn.length < 1 || termsIn.length + rangesIn.length > 9) throw new Error("ranges must be an array of 0 .. 8 ranges, 1 .. 9 with the terms");
+    if (!Array.isArray(clusterIn) || clusterIn.length !== termsIn.length + rangesIn.length) throw new Error("cluster must hold an entry for every term and range");
+    if (!Array.isArray(imIn) || imIn.length < 1 || imIn.length > 9) throw new Error("im must be an array of 1 .. 9 columns { buf, stride, col }");
+    if (!outIn || !(outIn.stride > 0) || !(outIn.col >= 0)) throw new Error("out must be { buf, stride, col }");
+    const held = new Map();                          // a host buffer -> its words, made once
+    const own = (b) => { if (dev || !b) return b; if (!held.has(b)) held.set(b, stage.asWords(b)); return held.get(b); };
+    const elem = (v, what, words) => {
+        if (!bn && words === 1) { if (typeof v !== "bigint") throw new Error(what + " must be a BigInt"); return [v, 0n, 0n, 0n]; }
+        const w = Array.from(stage.asWords(v));
+        if (w.length !== words) throw new Error(what + " must hold " + words + " words");
+        return w.concat([0n, 0n, 0n, 0n]).slice(0, 4);
+    };
+    const terms = termsIn.map((t, u) => {
+        const s = side(Object.assign({}, t, { buf: own(t.buf), sel: t.sel ? Object.assign({}, t.sel, { buf: own(t.sel.buf) }) : t.sel }), "term " + u, n, ew, dev);
+        if (s.cols.length < 1 || s.cols.length > 16) throw new Error("term " + u + ": 1 .. 16 columns");
+        s.coef = elem(t.coef, "coef of term " + u, ew); s.busId = elem(t.busId, "busId of term " + u, ew);
+        return s;
+    });
+    const ranges = rangesIn.map((r, i) => {
+        if (!r || !r.m || !(r.m.stride > 0) || !(r.m.col >= 0)) throw new Error("range " + i + " must be { m: { buf, stride, col }, lo, size, row0, coef, busId }");
+        const lo = BigInt(r.lo);
+        if (lo < -(1n << 63n) || lo >= 1n << 63n) throw new Error("range " + i + ": lo must be a signed 64-bit integer");
+        const s = side({ buf: own(r.m.buf), stride: r.m.stride, cols: [r.m.col] }, "m of range " + i, n, ew, dev);
+        return Object.assign(s, { lo: BigInt.asUintN(64, lo), size: r.size, row0: r.row0 || 0, coef: elem(r.coef, "coef of range " + i, ew), busId: elem(r.busId, "busId of range " + i, ew) });
+    });
+    const column = (x, what) => {
+        if (!x || !(x.stride > 0) || !(x.col >= 0)) throw new Error(what + " must be { buf, stride, col }");
+        return Object.assign(side({ buf: own(x.buf), stride: x.stride, cols: [x.col, x.col + width - 1] }, what, n, ew, dev), { col: x.col });
+    };
+    const im = imIn.map((x, c) => column(x, "im " + c)), out = column(outIn, "out");
+    const cluster = clusterIn.map((c) => BigInt.asUintN(64, BigInt(c)));
+    const ptr = (b) => dev && b ? b.ptr : 0n;
+    const head = [n, terms.length, ranges.length, im.length, ptr(out.buf), out.stride, out.col].concat(elem(alpha, "alpha", bn ? 4 : 3), elem(beta, "beta", bn ? 4 : 3));
+    const fourteen = terms.map((x) => [ptr(x.buf), x.stride, x.cols.length].concat(x.sel ? [ptr(x.sel.buf), x.sel.stride, x.sel.col] : [0n, 0, 0], x.coef, x.busId));
+    const rangeWords = ranges.map((x) => [ptr(x.buf), x.stride, x.cols[0], x.lo, x.size, x.row0].concat(x.coef, x.busId));
+    const imWords = im.map((x) => [ptr(x.buf), x.stride, x.col]);
+    const slots = terms.map((x) => x.cols.concat(new Array(16 - x.cols.length).fill(0)));
+    const desc = BigUint64Array.from(head.concat(...fourteen, ...rangeWords, cluster, ...imWords, ...slots).map((v) => BigInt(v)));
+    if (dev) { addon.logupClusterDev(desc, ew, opts && opts.stream); return outIn; }
+    addon.logupCluster(desc, matrices(terms.concat(ranges, im)).concat([out.buf]), ew);
+    const back = new Set();
+    for (const x of imIn.concat([outIn])) if (!back.has(x.buf)) { back.add(x.buf); copyBack(held.get(x.buf), x.buf); }
+    return outIn;
+}
+const logupCluster = (terms, ranges, cluster, im, alpha, beta, out, n, opts) => logupClustered(false, terms, ranges, cluster, im, alpha, beta, out, n, opts);
+const logupClusterDev = (terms, ranges, cluster, im, alpha, beta, out, n, opts) => logupClustered(true, terms, ranges, cluster, im, alpha, beta, out, n, opts);
+const logupClusterPlan = (n, nF, nR, nIm, bn128) => addon.logupClusterPlan(n, nF, nR, nIm, bn128 ? 4 : 1);
+
 // ---- grand product of a permutation or a connection ----
 // A term is a side { buf, stride, cols, sel } with den: 0 | 1 and optionally id: { buf, stride, col } and idCoef (3 words over Goldilocks,
 // 4 Montgomery words over Fr); alpha, beta, gamma are 3 or 4 words each; out is logupSum's.  z[n-1] is the hint's result.
@@ -362,4 +421,4 @@ const plookupProduct = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, opts) =
 const plookupProductDev = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, opts) => plookup(true, true, f, t, [h1, h2, out], [alpha, beta, gamma, delta], n, opts);
 const plookupPlan = (n, kF, kT, bn128) => addon.plookupPlan(n, kF, kT, bn128 ? 4 : 1);
 
-module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, logupSum, logupSumDev, logupSumPlan, rangeSum, rangeSumDev, rangeSumPlan, grandProduct, grandProductDev, grandProductPlan, permutationTerms, connectionTerms, plookupFold, plookupFoldDev, plookupProduct, plookupProductDev, plookupPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };
+module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, logupSum, logupSumDev, logupSumPlan, rangeSum, rangeSumDev, rangeSumPlan, logupCluster, logupClusterDev, logupClusterPlan, DIRECT, grandProduct, grandProductDev, grandProductPlan, permutationTerms, connectionTerms, plookupFold, plookupFoldDev, plookupProduct, plookupProductDev, plookupPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };

@@ -157,3 +157,11 @@ Object.assign(module.exports, { calculateH1H2Plookup, calculateH1H2PlookupDev, c
 const calculateSRange = (terms, ranges, alpha, beta, out, n) => require("./pil_checks.js").rangeSum(terms, ranges, alpha, beta, out, n, { bn128: false });
 const calculateSRangeDev = (terms, ranges, alpha, beta, out, n, stream) => require("./pil_checks.js").rangeSumDev(terms, ranges, alpha, beta, out, n, { bn128: false, stream });
 Object.assign(module.exports, { calculateSRange, calculateSRangeDev });
+
+// s and the im columns of a clustered logUp sum in one call (js/pil_checks.js logupCluster; include/pil2gl.h states it): cluster holds an
+// entry a term, f terms first, a cluster id or pil_checks.DIRECT; im one { buf, stride, col } a cluster.
+//   calculateSClustered(terms, ranges, cluster, im, alpha, beta, out, n)               host words; writes in place -> out
+//   calculateSClusteredDev(terms, ranges, cluster, im, alpha, beta, out, n, stream)    the same on DevBuffers; only enqueues
+const calculateSClustered = (terms, ranges, cluster, im, alpha, beta, out, n) => require("./pil_checks.js").logupCluster(terms, ranges, cluster, im, alpha, beta, out, n, { bn128: false });
+const calculateSClusteredDev = (terms, ranges, cluster, im, alpha, beta, out, n, stream) => require("./pil_checks.js").logupClusterDev(terms, ranges, cluster, im, alpha, beta, out, n, { bn128: false, stream });
+Object.assign(module.exports, { calculateSClustered, calculateSClusteredDev });

@@ -177,5 +177,8 @@ const calculateZPlookupDev = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, s
 // the grand sum of range checks with the ranges as numbers, no t column (js/pil_checks.js rangeSum): elements are 4 Montgomery words
 const calculateSRange = (terms, ranges, alpha, beta, out, n) => require("./pil_checks.js").rangeSum(terms, ranges, alpha, beta, out, n, { bn128: true });
 const calculateSRangeDev = (terms, ranges, alpha, beta, out, n, stream) => require("./pil_checks.js").rangeSumDev(terms, ranges, alpha, beta, out, n, { bn128: true, stream });
+// s and the im columns of a clustered logUp sum (js/pil_checks.js logupCluster): elements are 4 Montgomery words
+const calculateSClustered = (terms, ranges, cluster, im, alpha, beta, out, n) => require("./pil_checks.js").logupCluster(terms, ranges, cluster, im, alpha, beta, out, n, { bn128: true });
+const calculateSClusteredDev = (terms, ranges, cluster, im, alpha, beta, out, n, stream) => require("./pil_checks.js").logupClusterDev(terms, ranges, cluster, im, alpha, beta, out, n, { bn128: true, stream });
 
-module.exports = { calculateSRange, calculateSRangeDev, calculateH1H2Plookup, calculateH1H2PlookupDev, calculateZPlookup, calculateZPlookupDev, calculateZPermutation, calculateZPermutationDev, calculateZConnection, calculateZConnectionDev, calculateZ, calculateS, calculateSCol, batchInverse, calculateH1H2, calculateZDev, calculateSDev, calculateSColDev, batchInverseDev, calculateH1H2Dev, lastElement };
+module.exports = { calculateSClustered, calculateSClusteredDev, calculateSRange, calculateSRangeDev, calculateH1H2Plookup, calculateH1H2PlookupDev, calculateZPlookup, calculateZPlookupDev, calculateZPermutation, calculateZPermutationDev, calculateZConnection, calculateZConnectionDev, calculateZ, calculateS, calculateSCol, batchInverse, calculateH1H2, calculateZDev, calculateSDev, calculateSColDev, batchInverseDev, calculateH1H2Dev, lastElement };

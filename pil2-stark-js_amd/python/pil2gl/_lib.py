@@ -68,6 +68,11 @@ class RangeTerm(C.Structure):
                 ("coef", C.c_uint64 * 4), ("busId", C.c_uint64 * 4)]
 
 
+class LogupImCol(C.Structure):
+    """include/pil2gl.h pil2gl_logup_im_col: where one im column of the clustered logUp sum is written (its matrix, stride and column)"""
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_uint64), ("col", C.c_uint64)]
+
+
 class GrandProdTerm(C.Structure):
     """include/pil2gl.h pil2gl_grand_prod_term: one term of a grand product (its side, its k, numerator or denominator, the id column and
     its host coefficient)"""
@@ -288,6 +293,11 @@ SIGNATURES = {
     "pil2gl_bn128_range_sum_dev": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),
     "pil2gl_range_sum": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, vp, vp, _U64, _U64, _U64]),
     "pil2gl_bn128_range_sum": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, vp, vp, _U64, _U64, _U64]),
+    "pil2gl_logup_cluster_plan": (_I, [_U64, _U64, _U64, _U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_logup_cluster_dev": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, C.POINTER(LogupImCol), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_bn128_logup_cluster_dev": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, C.POINTER(LogupImCol), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),
+    "pil2gl_logup_cluster": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, C.POINTER(LogupImCol), _U64, vp, vp, vp, _U64, _U64, _U64]),
+    "pil2gl_bn128_logup_cluster": (_I, [C.POINTER(LogupTerm), _U64, C.POINTER(RangeTerm), _U64, vp, C.POINTER(LogupImCol), _U64, vp, vp, vp, _U64, _U64, _U64]),
     "pil2gl_grand_prod_plan": (_I, [_U64, _U64, _U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
     "pil2gl_grand_prod_dev": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64, vp]),
     "pil2gl_bn128_grand_prod_dev": (_I, [C.POINTER(GrandProdTerm), _U64, vp, vp, vp, vp, _U64, _U64, _U64, vp]),

@@ -14,7 +14,8 @@ returns the library's five words (kind, row, partner, cntF, cntT) -- include/pil
 The column that PROVES a lookup in pil2, the multiplicities of its grand sum (csrc/lookup_mult.hip), is lookup_mult / lookup_mult_dev at the
 end of this module, then its form for a range check, which needs no table column (range_mult / range_mult_dev, csrc/range_mult.hip), and
 after them the grand sum that consumes the column (logup_sum / logup_sum_dev), its form for range checks, which takes the ranges as
-numbers (range_sum / range_sum_dev, and range_logup for both halves), and the grand product of a permutation or a connection
+numbers (range_sum / range_sum_dev, and range_logup for both halves), the clustered form of both that writes the im columns beside s
+(logup_cluster / logup_cluster_dev, range_logup_clustered), and the grand product of a permutation or a connection
 (grand_prod / grand_prod_dev, with perm_prod and conn_prod as spellings of the two identities), and last pil1's plookup argument
 (plookup_fold, plookup_h1h2, plookup_prod and their _dev forms).
 """
@@ -322,10 +323,9 @@ def range_sum_plan(n, n_f=0, n_r=1, field="gl"):
     return _plan("pil2gl_range_sum_plan", (n, n_f, n_r, _WORDS[field]), ("threads", "items", "blocks", "launches", "depth", "outWidth"), "workBytes")
 
 
-def _range_sum(dev, terms, ranges, alpha, beta, out, n, field):
+def _range_terms(ranges, n, words, dev, keep):
+    """range specs as a RangeTerm array (one element at least); the m matrices are appended to keep"""
     from ._lib import RangeTerm
-    words = _WORDS[field]
-    T, keep = _logup_terms(terms, n, words, dev)
     Rg = (RangeTerm * max(len(ranges), 1))()
     for r, (m, lo, size, row0, coef, bus) in enumerate(ranges):
         m = tuple(m) + (None,)
@@ -335,6 +335,13 @@ def _range_sum(dev, terms, ranges, alpha, beta, out, n, field):
         Rg[r].lo, Rg[r].size, Rg[r].row0 = lo, size, row0
         _elem4(Rg[r].coef, coef, words, "range %d: coef" % r)
         _elem4(Rg[r].busId, bus, words, "range %d: busId" % r)
+    return Rg
+
+
+def _range_sum(dev, terms, ranges, alpha, beta, out, n, field):
+    words = _WORDS[field]
+    T, keep = _logup_terms(terms, n, words, dev)
+    Rg = _range_terms(ranges, n, words, dev, keep)
     ch, chp = _challenges((alpha, beta), "alpha and beta", words)
     om, col = _column(out, "out", 3 if words == 1 else 1, n, words, dev)
     name = "pil2gl_range_sum" if words == 1 else "pil2gl_bn128_range_sum"
@@ -363,6 +370,13 @@ def range_logup(fs, lo, size, m, alpha, beta, out, n, field="gl", row0=0, bus_id
     for the report and for s[n-1]."""
     words = _WORDS[field]
     report = range_mult_dev(fs, lo, size, m, n, field, row0)
+    terms, rng = _range_logup_terms(fs, lo, size, m, row0, bus_id, words)
+    range_sum_dev(terms, [rng], alpha, beta, out, n, field)
+    return report, _last_element(out, n, words)
+
+
+def _range_logup_terms(fs, lo, size, m, row0, bus_id, words):
+    """the terms of `f_s in [lo, lo + size)`: coef 1 for every f side, -1 for the range, one bus id (0 by default)"""
     if words == 1:
         one, minus, bus = 1, 0xFFFFFFFF00000000, 0 if bus_id is None else bus_id
     else:
@@ -373,17 +387,81 @@ def range_logup(fs, lo, size, m, alpha, beta, out, n, field="gl", row0=0, bus_id
     for f in fs:
         f = tuple(f) + (None,) * (4 - len(f))
         terms.append((f[0], f[1], f[2], one, bus, f[3]))
-    range_sum_dev(terms, [(m, lo, size, row0, minus, bus)], alpha, beta, out, n, field)
+    return terms, (m, lo, size, row0, minus, bus)
+
+
+def _last_element(out, n, words):
+    """s[n-1] of a device column (matrix, col[, stride]) as a host array of 3 words or of 4 Montgomery words; None when n = 0"""
     if not n:
-        return report, None
+        return None
     width = 3 if words == 1 else 1
     mat, stride = out[0], (out[2] if len(out) > 2 else None)
     flat = mat.reshape(-1)
     if stride is None:
         stride = mat.shape[1]
     at = ((n - 1) * stride + out[1]) * words
-    last = flat[at:at + width * words].cpu().numpy().view(np.uint64).copy()
-    return report, last
+    return flat[at:at + width * words].cpu().numpy().view(np.uint64).copy()
+
+
+# ---- clustered logUp sum: s and one im column a cluster in one call (csrc/logup_cluster_plan.h; include/pil2gl.h states it) ----
+#     logup_cluster_dev([(cm1, [7], None, 1, bus), (cm1, [8], None, 1, bus)], [((cm1, 12), -128, 256, 0, P - 1, bus)], [0, 0, DIRECT],
+#                       [(cm2, 3)], alpha, beta, (cm2, 0), n)
+# terms and ranges are logup_sum's and range_sum's (either may be empty, nine together at most); cluster holds one entry a term, f terms
+# first: a cluster id 0 .. len(im) - 1, or DIRECT for a term that stays in the sum constraint; im holds one column (matrix, col) or
+# (matrix, col, stride) a cluster, of out's shape.  s and the im columns as neighbouring columns of one matrix is the normal case.
+DIRECT = (1 << 64) - 1
+
+
+def logup_cluster_plan(n, n_f=1, n_r=0, n_im=1, field="gl"):
+    """pil2gl_logup_cluster_plan (host-only): threads a workgroup, rows a lane, workgroups, launches, depth, words of an output element,
+    working bytes"""
+    return _plan("pil2gl_logup_cluster_plan", (n, n_f, n_r, n_im, _WORDS[field]), ("threads", "items", "blocks", "launches", "depth", "outWidth"), "workBytes")
+
+
+def _logup_cluster(dev, terms, ranges, cluster, im, alpha, beta, out, n, field):
+    from ._lib import LogupImCol
+    words = _WORDS[field]
+    T, keep = _logup_terms(terms, n, words, dev)
+    Rg = _range_terms(ranges, n, words, dev, keep)
+    cl = np.ascontiguousarray([int(c) for c in cluster], np.uint64).reshape(-1)
+    if cl.size != len(terms) + len(ranges):
+        raise Pil2glError("cluster holds %d entries for %d terms and ranges" % (cl.size, len(terms) + len(ranges)))
+    width = 3 if words == 1 else 1
+    Im = (LogupImCol * max(len(im), 1))()
+    for c, spec in enumerate(im):
+        mm, col = _column(spec, "im %d" % c, width, n, words, dev)
+        keep.append(mm)
+        Im[c].base, Im[c].stride, Im[c].col = col
+    ch, chp = _challenges((alpha, beta), "alpha and beta", words)
+    om, col = _column(out, "out", width, n, words, dev)
+    name = "pil2gl_logup_cluster" if words == 1 else "pil2gl_bn128_logup_cluster"
+    args = [T if terms else None, len(terms), Rg if ranges else None, len(ranges), C.c_void_p(cl.ctypes.data), Im, len(im)] + chp + col + [n]
+    if dev:
+        call(name + "_dev", *args, _stream())
+    else:
+        call(name, *args)
+    return out[0]
+
+
+def logup_cluster(terms, ranges, cluster, im, alpha, beta, out, n, field="gl"):
+    """s and the im columns of a clustered logUp sum: host matrices, every output column written in place -> out's matrix"""
+    return _logup_cluster(False, terms, ranges, cluster, im, alpha, beta, out, n, field)
+
+
+def logup_cluster_dev(terms, ranges, cluster, im, alpha, beta, out, n, field="gl"):
+    """logup_cluster on device tensors, e.g. s and the im columns as columns of the stage-2 buffer; only enqueues on the current stream"""
+    return _logup_cluster(True, terms, ranges, cluster, im, alpha, beta, out, n, field)
+
+
+def range_logup_clustered(fs, lo, size, m, cluster, im, alpha, beta, out, n, field="gl", row0=0, bus_id=None):
+    """range_logup with the terms clustered: range_mult_dev writes m, then logup_cluster_dev writes s and the im columns, with coef 1 for
+    every f side and -1 for the range; cluster holds an entry for every f side, then the range's -> (range_mult's report, s[n-1] as a host
+    array).  Blocks for the report and for s[n-1]."""
+    words = _WORDS[field]
+    report = range_mult_dev(fs, lo, size, m, n, field, row0)
+    terms, rng = _range_logup_terms(fs, lo, size, m, row0, bus_id, words)
+    logup_cluster_dev(terms, [rng], cluster, im, alpha, beta, out, n, field)
+    return report, _last_element(out, n, words)
 
 
 # ---- grand product: the column z of a permutation or a connection (csrc/grand_prod_plan.h; include/pil2gl.h states it) ----
