@@ -24,7 +24,7 @@
  *    Most of them only ENQUEUE work on that stream and return:
  *      interpolate / interpolate_cosets[_ws] / extend_cosets_unshifted / extend_coefs_brev[_cosets] / fft / ifft, linear_hash_rows, merkelize,
  *      merkelize_level, merkelize_digests, poseidon, fri_fold, fri_verify_fold, fri_transpose, build_x, geometric,
- *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; range_sum and bn128_range_sum; logup_cluster and bn128_logup_cluster; grand_prod and bn128_grand_prod; plookup_fold, plookup_prod and their bn128_ twins; land_rows with a null hostFirstBad;
+ *      x_div_x_sub_xi[_cosets], gprod, gsum, dev_zero, and their bn128_ twins; bn128_eval_program, bn128_poly_div_xk_sub and bn128_poly_eval (after staging: see there); bn128_batch_inverse, bn128_gprod, bn128_gsum and bn128_gsum_col; gsum_col; logup_sum and bn128_logup_sum; range_sum and bn128_range_sum; logup_cluster and bn128_logup_cluster; grand_prod and bn128_grand_prod; plookup_fold, plookup_prod and their bn128_ twins; the open of a lookup_session or range_session and their write with a null hostTotal; land_rows with a null hostFirstBad;
  *      wtns_adds and bn128_wtns_adds, wtns_gather and bn128_wtns_gather with a null hostFirstBad, conn_pols and bn128_conn_pols with a null hostFirstBad.
  *    dev_upload_async / dev_download_async / copy_after / copy_fence take no stream: they ENQUEUE on the library's own copy
  *    stream (or order it against the stream given) and return.
@@ -33,7 +33,7 @@
  *      eval_program (op-list and scalar pool are host temporaries), rows_dot_ext / rows_dot_ext_multi[_step] / cols_dot_ext /
  *      cols_dot_ext_multi / fri_combine / fri_combine_order (host-side weights), compute_evals (returns the evaluations),
  *      build_zhinv, build_one_row_zerofier_inv, build_frame_zerofier, compute_q_split[_brev], compute_q_stark, compute_fri_pol, build_lev (small host tables),
- *      h1h2 and bn128_h1h2 (the missing row comes back), conn_check and bn128_conn_check, tuple_check and bn128_tuple_check, lookup_mult and bn128_lookup_mult, range_mult and bn128_range_mult (the report comes back), synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
+ *      h1h2 and bn128_h1h2 (the missing row comes back), conn_check and bn128_conn_check, tuple_check and bn128_tuple_check, lookup_mult and bn128_lookup_mult, range_mult and bn128_range_mult (the report comes back), the add of a lookup_session or range_session and their write with a hostTotal, synth_fibonacci, group_proof / group_proofs and bn128_group_proof / bn128_group_proofs (openings copied to host memory),
  *      land_rows, wtns_gather, bn128_wtns_gather, conn_pols and bn128_conn_pols with a hostFirstBad (the index comes back), dev_load_file / dev_save_file (the file is read / written
  *      when they return), copy_sync, and dev_upload / dev_download (synchronous copies of pageable memory).
  *    So do the host-pointer verifier calls roots_from_group_proofs and bn128_roots_from_group_proofs (roots copied to host memory).
@@ -46,7 +46,7 @@
  *    rejects the Promise; the addon converts the code back into a JS exception).
  *  - The library has no CPU fallback: without a HIP device every compute entry
  *    point fails with PIL2GL_ENODEV.  Calls that need no device say so where they are declared: merkle_num_nodes, add / mul /
- *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, logup_sum_plan, range_sum_plan, logup_cluster_plan, grand_prod_plan, plookup_plan, the debug_ hooks.
+ *    square, the jit_cache_ and precompile_ calls, wtns_adds_plan, conn_plan, conn_check_plan, tuple_check_plan, lookup_mult_plan, range_mult_plan, lookup_session_plan, range_session_plan, logup_sum_plan, range_sum_plan, logup_cluster_plan, grand_prod_plan, plookup_plan, the debug_ hooks.
  *  - Calls are not thread-safe against each other (the reference issues them
  *    sequentially from one JS thread: src/prover/prover.js, `await` on every step).
  */
@@ -1062,6 +1062,91 @@ int pil2gl_debug_range_mult_plan(uint64_t n, uint64_t size, uint64_t nF, uint32_
 int pil2gl_debug_range_mult_dev(const pil2gl_tuple_side *hostF, uint64_t nF, int64_t lo, uint64_t size, uint64_t row0, uint64_t *m,
                                 uint64_t mStride, uint64_t mCol, uint64_t n, uint64_t *scratch, uint64_t scratchBytes,
                                 uint64_t *hostReport /* [4] */, void *stream, uint32_t elemWords, uint32_t path);
+
+/* ---- multiplicity sessions: m of a table in an AIR of its own, counted over f sides of their own lengths (csrc/mult_session.hip, csrc/mult_session_plan.h) ----
+ * The two blocks above state "n rows every side" and are one shot.  In a pil2 proof a table -- a U16 range, a fixed lookup table -- lives in
+ * an AIR of its own and the rows that look values up lie in other AIRs, with other row counts, in many instances that arrive one at a time.
+ * A session cuts the one call into three: OPEN makes the table, ADD counts f sides of any length, once per arriving instance, WRITE writes
+ * m.  Between the calls the counters live in the caller's scratch.  The statement is this header's own (tests/mult_session_ref.py restates
+ * it over Python integers and one dictionary):
+ *   LOOKUP session: t is one pil2gl_tuple_side of nT <= 2^28 rows, k columns, 1 <= k <= 16.  open does what lookup_mult's init and build do,
+ *   over t's selected rows.  t's matrix and selector must stay UNCHANGED AND RESIDENT until the session's last call: the table keeps row
+ *   numbers and re-reads the keys.  hostT, nT and k are arguments of every call of the session.
+ *   RANGE session: the range is (lo, size) with range_mult's meaning -- lo SIGNED, 1 <= size <= 2^28, the difference v - lo compared with
+ *   size as a full field element.  open zeroes `size` counters.  lo and size are arguments of every later call; passing other values than at
+ *   open is the caller's error and is not detected (a larger size reads past the counters: the scratch is checked against the size GIVEN).
+ *   ADD: 1 <= nF <= 8 sides of f; side s has its OWN row count hostRows[s] <= 2^28, independent of nT and of size.  A side of 0 rows launches
+ *   nothing and its pointers are not looked at.  Selected rows, element values (Goldilocks words in [p, 2^64), any Fr pattern), equality of
+ *   tuples and IN RANGE are exactly the one-shot blocks'.  Every selected row whose tuple or value the table holds adds 1 to that counter.
+ *   hostReport[4] describes THIS ADD ONLY: [0] = kind, 0 clean or 1; [1], [2] = the lexicographically smallest failing (side, row) of this
+ *   add, both UINT64_MAX when clean; [3] = the matched rows of this add.  On kind 1 the rows that matched are still counted.  The call
+ *   BLOCKS for the report.  Adds to one session must be stream-ordered; two adds in flight on one session are outside the statement.
+ *   WRITE, lookup: m = column mCol of (m, mStride), written for every row j < nT: the count of t[j]'s tuple when j is selected in t and is
+ *   the smallest selected row of t with that tuple, 0 otherwise.  WRITE, range: m is written for every row i < nM: cnt(i - row0) inside
+ *   row0 .. row0 + size - 1, 0 outside; row0 + size <= nM <= 2^28.  The value is the canonical element of the accumulated count: one u64, or
+ *   the Montgomery form over Fr.  hostTotal (one u64, may be NULL) receives the matched rows of the whole session, the integer sum of m;
+ *   with NULL the call only enqueues, otherwise it BLOCKS.  write does not end the session: it may be called again after further adds and
+ *   then shows the later state.  Nothing ends a session but the caller reusing the scratch.
+ *   Counters are 64 bits wide.  Counts of 2^64 and above, or of p and above over Goldilocks, are outside the statement (2^33 full adds) and
+ *   are not checked for.
+ * Aliasing: m keeps lookup_mult's rule against t (it may be a spare column of t's matrix).  The scratch meets no matrix of any call.  The
+ * matrices of f may overlap each other freely and one matrix may serve several sides; a side may start at a later row of a matrix, by a
+ * base advanced by whole rows (still 16-byte aligned).
+ * Equivalences: (1) one add whose sides all have hostRows[s] = nT (range: = nM, row0 as given), then write, gives m and the report word for
+ * word as pil2gl_[bn128_]lookup_mult_dev / range_mult_dev give on the same input.  (2) m after a session depends only on the multiset of
+ * selected rows offered, not on how they were cut into adds, sides and row ranges.
+ *
+ * pil2gl_lookup_session_plan / pil2gl_range_session_plan: host-only, no device.  outInfo[0] = log2 of the hash table's capacity (the smallest
+ * power of two >= 2 nT and >= 16), or the range's count path (0 = LDS counters a workgroup, size <= the threshold of csrc/range_mult_plan.h;
+ * 1 = merged atomics on the global counters); [1] = threads a workgroup of a count launch; [2] = workgroups of a count launch over a side of
+ * 2^28 rows -- a launch takes its grid from ITS side's rows, never from the table; [3] = kernel launches of open, of an add with one side
+ * (each further side with rows is one more) and of write, as open | add << 8 | write << 16: 2, 2, 1 for a lookup session (init, build; the
+ * lane that closes the last add's report, count; write) and 1, 2, 1 for a range session; [4] = bytes of the header, 64; [5] = bytes a slot,
+ * 16 (the tuple's smallest selected row of t, a 64-bit counter), or a counter, 8.  *scratchBytes = 64 + 16 2^[0] (0 for nT = 0), or
+ * 64 + 8 size rounded up to 16.  PIL2GL_EINVAL: nT > 2^28, k outside 1 .. 16, size outside 1 .. 2^28, elemWords not 1 or 4.
+ * The compute entries: hostT, hostF (nF entries) and hostRows (nF entries) are HOST pointers; base, sel, m and scratch are device pointers,
+ * 16-byte aligned.  open only ENQUEUES.  PIL2GL_EINVAL, before any device call: what the plans refuse, nF outside 1 .. 8, a hostRows[s]
+ * above 2^28, a column >= its stride, a stride >= 2^32 or rows stride > 2^58 elements -- each side checked against ITS OWN row count, t
+ * against nT, m against nT or nM --, row0 + size > nM, a null hostT, hostF, hostRows, cols, base (of a side with rows), m, scratch or
+ * hostReport, a misaligned device pointer, a scratch that is too small or overlaps a matrix of this call, an m that breaks the aliasing
+ * rule.  A refused add leaves a clean report.  nT = 0 is PIL2GL_OK in all three lookup entries and does nothing.  Without a device the
+ * compute entries return PIL2GL_ENODEV.  There are no host-pointer forms: a session's state is the device's.
+ * The debug_ entries are for the tests and tools/bench_mult_session.py: the open forms with a seed, the u64 every counter starts from
+ * (hostTotal of a later write is then NOT the sum of m: it counts matched rows only); the range plan and add with the count path given
+ * (0, 1, or 2 = the planner's choice; path 0 takes size <= 8192), elemWords selecting the field; and pil2gl_debug_mult_session_grids, host-only: the
+ * workgroups of the count launch of each of the 8 sides of the LAST add of this process, 0 for a side that launched nothing -- what lets a
+ * test see that a launch took its grid from its side's rows. */
+int pil2gl_lookup_session_plan(uint64_t nT, uint64_t k, uint32_t elemWords, uint32_t *outInfo /* [6] */, uint64_t *scratchBytes);
+int pil2gl_range_session_plan(uint64_t size, uint32_t elemWords, uint32_t *outInfo /* [6] */, uint64_t *scratchBytes);
+int pil2gl_lookup_session_open_dev(const pil2gl_tuple_side *hostT, uint64_t nT, uint64_t k, uint64_t *scratch, uint64_t scratchBytes, void *stream);
+int pil2gl_bn128_lookup_session_open_dev(const pil2gl_tuple_side *hostT, uint64_t nT, uint64_t k, uint64_t *scratch, uint64_t scratchBytes,
+                                         void *stream);
+int pil2gl_range_session_open_dev(uint64_t size, uint64_t *scratch, uint64_t scratchBytes, void *stream);
+int pil2gl_lookup_session_add_dev(const pil2gl_tuple_side *hostT, uint64_t nT, uint64_t k, const pil2gl_tuple_side *hostF, const uint64_t *hostRows,
+                                  uint64_t nF, uint64_t *scratch, uint64_t scratchBytes, uint64_t *hostReport /* [4] */, void *stream);
+int pil2gl_bn128_lookup_session_add_dev(const pil2gl_tuple_side *hostT, uint64_t nT, uint64_t k, const pil2gl_tuple_side *hostF,
+                                        const uint64_t *hostRows, uint64_t nF, uint64_t *scratch, uint64_t scratchBytes,
+                                        uint64_t *hostReport /* [4] */, void *stream);
+int pil2gl_range_session_add_dev(int64_t lo, uint64_t size, const pil2gl_tuple_side *hostF, const uint64_t *hostRows, uint64_t nF, uint64_t *scratch,
+                                 uint64_t scratchBytes, uint64_t *hostReport /* [4] */, void *stream);
+int pil2gl_bn128_range_session_add_dev(int64_t lo, uint64_t size, const pil2gl_tuple_side *hostF, const uint64_t *hostRows, uint64_t nF,
+                                       uint64_t *scratch, uint64_t scratchBytes, uint64_t *hostReport /* [4] */, void *stream);
+int pil2gl_lookup_session_write_dev(const pil2gl_tuple_side *hostT, uint64_t nT, uint64_t k, uint64_t *m, uint64_t mStride, uint64_t mCol,
+                                    uint64_t *scratch, uint64_t scratchBytes, uint64_t *hostTotal, void *stream);
+int pil2gl_bn128_lookup_session_write_dev(const pil2gl_tuple_side *hostT, uint64_t nT, uint64_t k, uint64_t *m, uint64_t mStride, uint64_t mCol,
+                                          uint64_t *scratch, uint64_t scratchBytes, uint64_t *hostTotal, void *stream);
+int pil2gl_range_session_write_dev(uint64_t size, uint64_t row0, uint64_t *m, uint64_t mStride, uint64_t mCol, uint64_t nM, uint64_t *scratch,
+                                   uint64_t scratchBytes, uint64_t *hostTotal, void *stream);
+int pil2gl_bn128_range_session_write_dev(uint64_t size, uint64_t row0, uint64_t *m, uint64_t mStride, uint64_t mCol, uint64_t nM, uint64_t *scratch,
+                                         uint64_t scratchBytes, uint64_t *hostTotal, void *stream);
+int pil2gl_debug_lookup_session_open_dev(const pil2gl_tuple_side *hostT, uint64_t nT, uint64_t k, uint64_t *scratch, uint64_t scratchBytes,
+                                         void *stream, uint32_t elemWords, uint64_t seed);
+int pil2gl_debug_range_session_open_dev(uint64_t size, uint64_t *scratch, uint64_t scratchBytes, void *stream, uint64_t seed);
+void pil2gl_debug_mult_session_grids(uint32_t *outGrids /* [8] */);
+int pil2gl_debug_range_session_plan(uint64_t size, uint32_t elemWords, uint32_t path, uint32_t *outInfo /* [6] */, uint64_t *scratchBytes);
+int pil2gl_debug_range_session_add_dev(int64_t lo, uint64_t size, const pil2gl_tuple_side *hostF, const uint64_t *hostRows, uint64_t nF,
+                                       uint64_t *scratch, uint64_t scratchBytes, uint64_t *hostReport /* [4] */, void *stream, uint32_t elemWords,
+                                       uint32_t path);
 
 /* ---- lookup grand sum: the logUp column s of `selF_s {f_s} in selT {t}` from f, t and m (csrc/logup_sum_plan.h, hints.hip, bn_scan.hip) ----
  * The column that consumes the block above's m: the running sum of a pil2 lookup stated as  sum selF / (f + gamma) - sum m / (t + gamma),

@@ -805,6 +805,71 @@ FN(RangeMult) {
     return mk_undefined(env);
 }
 
+// ---- multiplicity sessions: open, add, write (csrc/mult_session.hip; js/pil_checks.js LookupSession, RangeSession) ----
+// The descriptions are the two above with the sides' row counts behind them: lookupMult's, then nF words hostRows (t first among the sides,
+// as there; an open or a write gives nF = 0); rangeMult's with [0] = nM, then nF words hostRows.
+static const char *const LOOKUP_SESSION_PLAN[6] = { "capBits", "threads", "blocks", "launches", "headerBytes", "slotBytes" };
+static const char *const RANGE_SESSION_PLAN[6] = { "path", "threads", "blocks", "launches", "headerBytes", "counterBytes" };
+FN(LookupSessionPlan) {    // (nT, k, elemWords) -> { capBits, threads, blocks, launches: open | add << 8 | write << 16, headerBytes, slotBytes, scratchBytes }
+    Args a(env, info); uint64_t n = a.u64(0), k = a.u64(1); uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
+    uint32_t out[6]; uint64_t bytes = 0;
+    P2(env, pil2gl_lookup_session_plan(n, k, ew, out, &bytes));
+    return plan_object(env, LOOKUP_SESSION_PLAN, out, "scratchBytes", bytes);
+}
+FN(RangeSessionPlan) {     // (size, elemWords) -> { path, threads, blocks, launches, headerBytes, counterBytes, scratchBytes }
+    Args a(env, info); uint64_t size = a.u64(0); uint32_t ew = (uint32_t)a.u64(1); if (!a.ok) return nullptr;
+    uint32_t out[6]; uint64_t bytes = 0;
+    P2(env, pil2gl_range_session_plan(size, ew, out, &bytes));
+    return plan_object(env, RANGE_SESSION_PLAN, out, "scratchBytes", bytes);
+}
+// the row counts behind a description of `used` words
+static const uint64_t *session_rows(Args &a, size_t i, uint64_t used, uint64_t nF) {
+    uint64_t len = 0; const uint64_t *d = a.arr(i, 1, &len);
+    if (a.ok && len < used + nF) a.fail("the description ends before the sides' row counts");
+    return a.ok ? d + used : nullptr;
+}
+FN(LookupSessionOpenDev) { // (description, dScratch, scratchBytes, elemWords)
+    Args a(env, info); MultDesc m; if (!mult_desc(a, 0, m)) return nullptr;
+    uint64_t *scr = DP(1); uint64_t bytes = a.u64(2); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_lookup_session_open_dev : pil2gl_lookup_session_open_dev)(m.side, m.n, m.k, scr, bytes, nullptr));
+    return mk_undefined(env);
+}
+FN(LookupSessionAddDev) {  // (description, dScratch, scratchBytes, report BigUint64Array(4), elemWords)
+    Args a(env, info); MultDesc m; if (!mult_desc(a, 0, m)) return nullptr;
+    const uint64_t *rows = session_rows(a, 0, MD_SIDES + (1 + m.nF) * (MD_SIDE_WORDS + m.k), m.nF);
+    uint64_t *scr = DP(1); uint64_t bytes = a.u64(2); uint64_t *rep = a.arr(3, 4); uint32_t ew = (uint32_t)a.u64(4); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_lookup_session_add_dev : pil2gl_lookup_session_add_dev)(m.side, m.n, m.k, m.side + 1, rows, m.nF, scr, bytes, rep, nullptr));
+    return mk_undefined(env);
+}
+FN(LookupSessionWriteDev) {        // (description, dScratch, scratchBytes, elemWords) -> the session's matched rows
+    Args a(env, info); MultDesc m; if (!mult_desc(a, 0, m)) return nullptr;
+    uint64_t *scr = DP(1); uint64_t bytes = a.u64(2); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
+    uint64_t total = 0;
+    P2(env, (ew == 4 ? pil2gl_bn128_lookup_session_write_dev : pil2gl_lookup_session_write_dev)(m.side, m.n, m.k, (uint64_t *)(uintptr_t)m.d[MD_M], m.d[MD_M_STRIDE],
+                                                                                                m.d[MD_M_COL], scr, bytes, &total, nullptr));
+    return mk_bigint(env, total);
+}
+FN(RangeSessionOpenDev) {  // (size, dScratch, scratchBytes)
+    Args a(env, info); uint64_t size = a.u64(0); uint64_t *scr = DP(1); uint64_t bytes = a.u64(2); if (!a.ok) return nullptr;
+    P2(env, pil2gl_range_session_open_dev(size, scr, bytes, nullptr));
+    return mk_undefined(env);
+}
+FN(RangeSessionAddDev) {   // (description, dScratch, scratchBytes, report BigUint64Array(4), elemWords)
+    Args a(env, info); RangeDesc r; if (!range_desc(a, 0, r)) return nullptr;
+    const uint64_t *rows = session_rows(a, 0, RD_SIDES + r.nF * RD_SIDE_WORDS, r.nF);
+    uint64_t *scr = DP(1); uint64_t bytes = a.u64(2); uint64_t *rep = a.arr(3, 4); uint32_t ew = (uint32_t)a.u64(4); if (!a.ok) return nullptr;
+    P2(env, (ew == 4 ? pil2gl_bn128_range_session_add_dev : pil2gl_range_session_add_dev)((int64_t)r.d[RD_LO], r.d[RD_SIZE], r.side, rows, r.nF, scr, bytes, rep, nullptr));
+    return mk_undefined(env);
+}
+FN(RangeSessionWriteDev) { // (description, dScratch, scratchBytes, elemWords) -> the session's matched rows
+    Args a(env, info); RangeDesc r; if (!range_desc(a, 0, r)) return nullptr;
+    uint64_t *scr = DP(1); uint64_t bytes = a.u64(2); uint32_t ew = (uint32_t)a.u64(3); if (!a.ok) return nullptr;
+    uint64_t total = 0;
+    P2(env, (ew == 4 ? pil2gl_bn128_range_session_write_dev : pil2gl_range_session_write_dev)(r.d[RD_SIZE], r.d[RD_ROW0], (uint64_t *)(uintptr_t)r.d[RD_M], r.d[RD_M_STRIDE],
+                                                                                              r.d[RD_M_COL], r.n, scr, bytes, &total, nullptr));
+    return mk_bigint(env, total);
+}
+
 // ---- lookup grand sum: the logUp column s from f, t and m (csrc/logup_sum_plan.h; js/pil_checks.js) ----
 FN(LogupSumPlan) {         // (n, nTerms, elemWords) -> { threads, items, blocks, launches, depth, outWidth, workBytes }
     Args a(env, info); uint64_t n = a.u64(0), nT = a.u64(1); uint32_t ew = (uint32_t)a.u64(2); if (!a.ok) return nullptr;
@@ -1359,6 +1424,9 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
         { "tupleCheckPlan", TupleCheckPlan }, { "tupleCheckDev", TupleCheckDev }, { "tupleCheck", TupleCheck }, { "tupleHome", TupleHome }, { "tupleCheckProbe", TupleCheckProbe },
         { "lookupMultPlan", LookupMultPlan }, { "lookupMultDev", LookupMultDev }, { "lookupMult", LookupMult }, { "lookupMultProbe", LookupMultProbe },
         { "rangeMultPlan", RangeMultPlan }, { "rangeMultDev", RangeMultDev }, { "rangeMult", RangeMult },
+        { "lookupSessionPlan", LookupSessionPlan }, { "lookupSessionOpenDev", LookupSessionOpenDev }, { "lookupSessionAddDev", LookupSessionAddDev },
+        { "lookupSessionWriteDev", LookupSessionWriteDev }, { "rangeSessionPlan", RangeSessionPlan }, { "rangeSessionOpenDev", RangeSessionOpenDev },
+        { "rangeSessionAddDev", RangeSessionAddDev }, { "rangeSessionWriteDev", RangeSessionWriteDev },
         { "logupSumPlan", LogupSumPlan }, { "logupTermLayout", LogupTermLayout }, { "logupSumDev", LogupSumDev }, { "logupSum", LogupSum },
         { "rangeSumPlan", RangeSumPlan }, { "rangeTermLayout", RangeTermLayout }, { "rangeSumDev", RangeSumDev }, { "rangeSum", RangeSum },
         { "logupClusterPlan", LogupClusterPlan }, { "logupImColLayout", LogupImColLayout }, { "logupClusterDev", LogupClusterDev }, { "logupCluster", LogupCluster },

@@ -24,6 +24,7 @@
 #include "tuple_side.cuh"
 #include "range_mult_plan.h"
 #include "mult_column.cuh"
+#include "range_decode.cuh"
 #include "wave_merge.cuh"
 
 using namespace pil2gl;
@@ -34,26 +35,7 @@ using namespace tupleside;
 using namespace smapplan;
 using namespace rangemultplan;
 using namespace multcolumn;
-
-// the range as the kernels take it: lo as a canonical element of the field (normal form over Fr), size
-template <class F> struct Range;
-template <> struct Range<GlField> { u64 lo; u32 size; };
-template <> struct Range<FrField> { u32 lo[8]; u32 size; };
-
-// row i of side f: is its value in the range, and then its counter.  The difference is a full field element: 64 bits, or 256
-__device__ __forceinline__ bool decode(const Side<GlField> &f, u64 i, const Range<GlField> &rg, u32 &idx) {
-    const u64 d = gl::sub(elem_of(f, i, 0), rg.lo);
-    idx = (u32)d;
-    return d < rg.size;
-}
-__device__ __forceinline__ bool decode(const Side<FrField> &f, u64 i, const Range<FrField> &rg, u32 &idx) {
-    const FrField::Elem one = { { 1, 0, 0, 0, 0, 0, 0, 0 } };
-    // any pattern times 1 over R: the normal form, canonical by FrField::mul's contract (below (2^256 + 2^256 r) / 2^256 before its subtraction)
-    FrField::Elem v = FrField::mul(FrField::load(f.base, i * f.stride + f.cols[0]), one);
-    bn::fr_sub(v.v, rg.lo);
-    idx = v.v[0];
-    return (v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7]) == 0 && v.v[0] < rg.size;
-}
+using namespace rangedecode;                         // the range as the kernels take it and a row's counter in it (shared with mult_session.hip)
 
 // ---- count, path 0: the rows of one side of f into the workgroup's own counters ----
 template <class F>
@@ -97,17 +79,6 @@ __global__ void __launch_bounds__(THREADS) rm_write_kernel(const u32 *counters, 
 
 // ---- host side ----
 struct Call { int64_t lo; u64 size, row0, n; u32 nF, words, force; };
-
-template <class F> Range<F> device_range(int64_t lo, u64 size);
-template <> Range<GlField> device_range<GlField>(int64_t lo, u64 size) { return Range<GlField>{ lo_mod_p(lo), (u32)size }; }
-template <> Range<FrField> device_range<FrField>(int64_t lo, u64 size) {
-    u64 w[4];
-    lo_mod_r(lo, w);
-    Range<FrField> rg{};
-    for (int i = 0; i < 4; i++) { rg.lo[2 * i] = (u32)w[i]; rg.lo[2 * i + 1] = (u32)(w[i] >> 32); }
-    rg.size = (u32)size;
-    return rg;
-}
 
 // every launch of a call, on st; the arguments have passed the checks.  Blocks for the report.
 template <class F>

@@ -31,4 +31,22 @@ __device__ __forceinline__ void add_merged(u32 *words, u32 s, bool add) {
     if (add) atomicAdd(&words[SPACING * (u64)s + OFFSET], 1u);
 }
 
+// the same merge in front of a 64-bit counter (mult_session.hip: a session's counts pass 2^32).  Counter s is the 64-bit word
+// words[SPACING s + OFFSET]; the rounds are the 32-bit form's, the atomic a global_atomic_add_x2 with a zero high half
+template <int SPACING, int OFFSET>
+__device__ __forceinline__ void add_merged64(unsigned long long *words, u32 s, bool add) {
+    u64 todo = __ballot(add);
+    const u32 lane = threadIdx.x & 63;
+    for (int round = 0; round < MERGE_ROUNDS && todo; round++) {
+        const u32 first = (u32)__ffsll((unsigned long long)todo) - 1;
+        const u32 slot = (u32)__builtin_amdgcn_readlane((int)s, (int)first);
+        const bool mine = add && s == slot;
+        const u64 group = __ballot(mine);
+        if (lane == first) atomicAdd(&words[SPACING * (u64)slot + OFFSET], (unsigned long long)__popcll((unsigned long long)group));
+        add = add && !mine;
+        todo &= ~group;
+    }
+    if (add) atomicAdd(&words[SPACING * (u64)s + OFFSET], 1ull);
+}
+
 }  // namespace wavemerge

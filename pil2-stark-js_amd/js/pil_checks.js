@@ -211,6 +211,76 @@ const rangeMultiplicities = (fs, lo, size, m, n, opts) => rangeCounts(false, fs,
 const rangeMultiplicitiesDev = (fs, lo, size, m, n, opts) => rangeCounts(true, fs, lo, size, m, n, opts);
 const rangeMultPlan = (n, size, nF, bn128) => addon.rangeMultPlan(n, size, nF, bn128 ? 4 : 1);
 
+// ---- multiplicity sessions: a table's m counted over the f sides of other AIRs, each of its own length (csrc/mult_session.hip) ----
+//   const s = new RangeSession(lo, size, opts) | new LookupSession(t, nT, opts)     open; the session owns its scratch; t stays unchanged
+//   s.add(fs, rows) -> { matched, missing: null | { side, row } } of THIS add, matched a BigInt; fs: DevBuffer sides as above, rows[i] the rows of side i
+//   s.write(m, nM, row0) | s.write(m) -> the session's matched rows (a BigInt: counts pass 2^32); m: { buf: DevBuffer, stride, col }; may be called again
+//   s.free()                                                                        the scratch
+const sixOf = (x, third) => [x.buf.ptr, x.stride, third].concat(x.sel ? [x.sel.buf.ptr, x.sel.stride, x.sel.col] : [0n, 0, 0]);
+const descWords = (list) => BigUint64Array.from(list.map((v) => BigInt(v)));
+function addReport(rep) {
+    return { matched: rep[3], missing: rep[0] === 0n ? null : { side: Number(rep[1]), row: Number(rep[2]) } };      // matched: a BigInt, as every 64-bit count of a session
+}
+function sessionSides(fsIn, rows, ew, k) {
+    if (!Array.isArray(fsIn) || fsIn.length < 1 || fsIn.length > 8 || !Array.isArray(rows) || rows.length !== fsIn.length) throw new Error("fs must be an array of 1 .. 8 sides, rows their row counts");
+    return fsIn.map((f, s) => {
+        const x = side(f, "f " + s, rows[s], ew, true);
+        if (x.cols.length !== k) throw new Error("f " + s + " must have " + k + " column(s)");
+        return x;
+    });
+}
+class LookupSession {
+    constructor(tIn, nT, opts) {
+        this.ew = opts && opts.bn128 ? 4 : 1;
+        this.nT = nT;
+        this.t = side(tIn, "t", nT, this.ew, true);
+        this.k = this.t.cols.length;
+        this.plan = addon.lookupSessionPlan(nT, this.k, this.ew);
+        this.work = new DevBuffer(Math.max(2, this.plan.scratchBytes / 8));
+        addon.lookupSessionOpenDev(this.desc([], [0n, 1, 0], []), this.work.ptr, this.plan.scratchBytes, this.ew);
+    }
+    desc(fs, m, rows) {
+        const sides = [this.t].concat(fs);
+        return descWords([this.nT, this.k, fs.length].concat(m, ...sides.map((x) => sixOf(x, 0)), ...sides.map((x) => x.cols), rows));
+    }
+    add(fsIn, rows) {
+        const fs = sessionSides(fsIn, rows, this.ew, this.k), rep = new BigUint64Array(4);
+        addon.lookupSessionAddDev(this.desc(fs, [0n, 1, 0], rows), this.work.ptr, this.plan.scratchBytes, rep, this.ew);
+        return addReport(rep);
+    }
+    write(mIn) {
+        const m = side({ buf: mIn.buf, stride: mIn.stride, cols: [mIn.col] }, "m", this.nT, this.ew, true);
+        return addon.lookupSessionWriteDev(this.desc([], [m.buf.ptr, m.stride, mIn.col], []), this.work.ptr, this.plan.scratchBytes, this.ew);
+    }
+    free() { this.work.free(); }
+}
+class RangeSession {
+    constructor(loIn, size, opts) {
+        this.ew = opts && opts.bn128 ? 4 : 1;
+        this.lo = BigInt(loIn);
+        if (this.lo < -(1n << 63n) || this.lo >= 1n << 63n) throw new Error("lo must be a signed 64-bit integer");
+        this.size = size;
+        this.plan = addon.rangeSessionPlan(size, this.ew);
+        this.work = new DevBuffer(Math.max(2, this.plan.scratchBytes / 8));
+        addon.rangeSessionOpenDev(size, this.work.ptr, this.plan.scratchBytes);
+    }
+    desc(nM, fs, row0, m, rows) {
+        return descWords([nM, fs.length, BigInt.asUintN(64, this.lo), this.size, row0].concat(m, ...fs.map((x) => sixOf(x, x.cols[0])), rows));
+    }
+    add(fsIn, rows) {
+        const fs = sessionSides(fsIn, rows, this.ew, 1), rep = new BigUint64Array(4);
+        addon.rangeSessionAddDev(this.desc(0, fs, 0, [0n, 1, 0], rows), this.work.ptr, this.plan.scratchBytes, rep, this.ew);
+        return addReport(rep);
+    }
+    write(mIn, nM, row0) {
+        const m = side({ buf: mIn.buf, stride: mIn.stride, cols: [mIn.col] }, "m", nM, this.ew, true);
+        return addon.rangeSessionWriteDev(this.desc(nM, [], row0 || 0, [m.buf.ptr, m.stride, mIn.col], []), this.work.ptr, this.plan.scratchBytes, this.ew);
+    }
+    free() { this.work.free(); }
+}
+const lookupSessionPlan = (nT, k, bn128) => addon.lookupSessionPlan(nT, k, bn128 ? 4 : 1);
+const rangeSessionPlan = (size, bn128) => addon.rangeSessionPlan(size, bn128 ? 4 : 1);
+
 // ---- lookup grand sum ----
 function logup(dev, termsIn, alpha, beta, outIn, n, opts) {
     const bn = !!(opts && opts.bn128), ew = bn ? 4 : 1, width = bn ? 1 : 3;
@@ -421,4 +491,4 @@ const plookupProduct = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, opts) =
 const plookupProductDev = (f, t, h1, h2, alpha, beta, gamma, delta, out, n, opts) => plookup(true, true, f, t, [h1, h2, out], [alpha, beta, gamma, delta], n, opts);
 const plookupPlan = (n, kF, kT, bn128) => addon.plookupPlan(n, kF, kT, bn128 ? 4 : 1);
 
-module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, logupSum, logupSumDev, logupSumPlan, rangeSum, rangeSumDev, rangeSumPlan, logupCluster, logupClusterDev, logupClusterPlan, DIRECT, grandProduct, grandProductDev, grandProductPlan, permutationTerms, connectionTerms, plookupFold, plookupFoldDev, plookupProduct, plookupProductDev, plookupPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };
+module.exports = { lookupMultiplicities, lookupMultiplicitiesDev, formatMissing, lookupMultProbe, rangeMultiplicities, rangeMultiplicitiesDev, rangeMultPlan, formatOutOfRange, LookupSession, RangeSession, lookupSessionPlan, rangeSessionPlan, logupSum, logupSumDev, logupSumPlan, rangeSum, rangeSumDev, rangeSumPlan, logupCluster, logupClusterDev, logupClusterPlan, DIRECT, grandProduct, grandProductDev, grandProductPlan, permutationTerms, connectionTerms, plookupFold, plookupFoldDev, plookupProduct, plookupProductDev, plookupPlan, checkLookup, checkPermutation, checkLookupDev, checkPermutationDev, formatReport, tupleHome, tupleCheckProbe, LOOKUP, PERMUTATION };

@@ -283,6 +283,24 @@ SIGNATURES = {
     "pil2gl_bn128_range_mult": (_I, [C.POINTER(TupleSide), _U64, C.c_int64, _U64, _U64, vp, _U64, _U64, _U64, vp]),
     "pil2gl_debug_range_mult_plan": (_I, [_U64, _U64, _U64, _U32, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
     "pil2gl_debug_range_mult_dev": (_I, [C.POINTER(TupleSide), _U64, C.c_int64, _U64, _U64, vp, _U64, _U64, _U64, vp, _U64, vp, vp, _U32, _U32]),
+    "pil2gl_lookup_session_plan": (_I, [_U64, _U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_range_session_plan": (_I, [_U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_lookup_session_open_dev": (_I, [C.POINTER(TupleSide), _U64, _U64, vp, _U64, vp]),
+    "pil2gl_bn128_lookup_session_open_dev": (_I, [C.POINTER(TupleSide), _U64, _U64, vp, _U64, vp]),
+    "pil2gl_range_session_open_dev": (_I, [_U64, vp, _U64, vp]),
+    "pil2gl_lookup_session_add_dev": (_I, [C.POINTER(TupleSide), _U64, _U64, C.POINTER(TupleSide), vp, _U64, vp, _U64, vp, vp]),
+    "pil2gl_bn128_lookup_session_add_dev": (_I, [C.POINTER(TupleSide), _U64, _U64, C.POINTER(TupleSide), vp, _U64, vp, _U64, vp, vp]),
+    "pil2gl_range_session_add_dev": (_I, [C.c_int64, _U64, C.POINTER(TupleSide), vp, _U64, vp, _U64, vp, vp]),
+    "pil2gl_bn128_range_session_add_dev": (_I, [C.c_int64, _U64, C.POINTER(TupleSide), vp, _U64, vp, _U64, vp, vp]),
+    "pil2gl_lookup_session_write_dev": (_I, [C.POINTER(TupleSide), _U64, _U64, vp, _U64, _U64, vp, _U64, vp, vp]),
+    "pil2gl_bn128_lookup_session_write_dev": (_I, [C.POINTER(TupleSide), _U64, _U64, vp, _U64, _U64, vp, _U64, vp, vp]),
+    "pil2gl_range_session_write_dev": (_I, [_U64, _U64, vp, _U64, _U64, _U64, vp, _U64, vp, vp]),
+    "pil2gl_bn128_range_session_write_dev": (_I, [_U64, _U64, vp, _U64, _U64, _U64, vp, _U64, vp, vp]),
+    "pil2gl_debug_lookup_session_open_dev": (_I, [C.POINTER(TupleSide), _U64, _U64, vp, _U64, vp, _U32, _U64]),
+    "pil2gl_debug_range_session_open_dev": (_I, [_U64, vp, _U64, vp, _U64]),
+    "pil2gl_debug_mult_session_grids": (None, [C.POINTER(_U32)]),
+    "pil2gl_debug_range_session_plan": (_I, [_U64, _U32, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
+    "pil2gl_debug_range_session_add_dev": (_I, [C.c_int64, _U64, C.POINTER(TupleSide), vp, _U64, vp, _U64, vp, vp, _U32, _U32]),
     "pil2gl_logup_sum_plan": (_I, [_U64, _U64, _U32, C.POINTER(_U32), C.POINTER(_U64)]),
     "pil2gl_logup_sum_dev": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),
     "pil2gl_bn128_logup_sum_dev": (_I, [C.POINTER(LogupTerm), _U64, vp, vp, vp, _U64, _U64, _U64, vp]),

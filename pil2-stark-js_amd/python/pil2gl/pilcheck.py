@@ -14,7 +14,8 @@ returns the library's five words (kind, row, partner, cntF, cntT) -- include/pil
 The column that PROVES a lookup in pil2, the multiplicities of its grand sum (csrc/lookup_mult.hip), is lookup_mult / lookup_mult_dev at the
 end of this module, then its form for a range check, which needs no table column (range_mult / range_mult_dev, csrc/range_mult.hip), and
 after them the grand sum that consumes the column (logup_sum / logup_sum_dev), its form for range checks, which takes the ranges as
-numbers (range_sum / range_sum_dev, and range_logup for both halves), the clustered form of both that writes the im columns beside s
+numbers (range_sum / range_sum_dev, and range_logup for both halves), the sessions that count a table's m over the f sides of other
+AIRs, each of its own length (LookupSession, RangeSession, and range_logup_cross for a table AIR with its user AIRs), the clustered form of both that writes the im columns beside s
 (logup_cluster / logup_cluster_dev, range_logup_clustered), and the grand product of a permutation or a connection
 (grand_prod / grand_prod_dev, with perm_prod and conn_prod as spellings of the two identities), and last pil1's plookup argument
 (plookup_fold, plookup_h1h2, plookup_prod and their _dev forms).
@@ -401,6 +402,147 @@ def _last_element(out, n, words):
         stride = mat.shape[1]
     at = ((n - 1) * stride + out[1]) * words
     return flat[at:at + width * words].cpu().numpy().view(np.uint64).copy()
+
+
+# ---- multiplicity sessions: m of a table in an AIR of its own, counted over f sides of their own lengths (csrc/mult_session.hip) ----
+#     s = RangeSession(0, 1 << 16)                       # the U16 table's AIR
+#     for cm1, n in instances: rep = s.add([(cm1, [7]), (cm1, [4], (cm1, 9))], [n, n])
+#     total = s.write((table_cm1, 0), 1 << 16)
+# open, add, write of include/pil2gl.h as objects that own the scratch.  A side is lookup_mult's spec, (matrix, cols[, sel[, stride]]), and
+# has its own row count; a host array among the sides of an add is staged up for that add.  m is a device column (matrix, col[, stride]).
+def _session_plan(entry, args, first, unit):
+    p = _plan(entry, args, (first, "threads", "blocks", "launches", "headerBytes", unit))
+    w = p.pop("launches")
+    return dict(p, openLaunches=w & 255, addLaunches=w >> 8 & 255, writeLaunches=w >> 16 & 255)
+
+
+def lookup_session_plan(n_t, k, field="gl"):
+    """pil2gl_lookup_session_plan (host-only): the table's capacity, the geometry of a full-size count, the launches, the working buffer"""
+    return _session_plan("pil2gl_lookup_session_plan", (n_t, k, _WORDS[field]), "capBits", "slotBytes")
+
+
+def range_session_plan(size, field="gl", path=None):
+    """pil2gl_range_session_plan (host-only): the count path, the geometry of a full-size count, the launches, the working buffer"""
+    if path is None:
+        return _session_plan("pil2gl_range_session_plan", (size, _WORDS[field]), "path", "counterBytes")
+    return _session_plan("pil2gl_debug_range_session_plan", (size, _WORDS[field], path), "path", "counterBytes")
+
+
+def mult_session_grids():
+    """pil2gl_debug_mult_session_grids (host-only): the workgroups of the count launch of each of the 8 sides of the last add, 0 for a side
+    that launched nothing"""
+    out = (C.c_uint32 * 8)()
+    load().pil2gl_debug_mult_session_grids(out)
+    return [int(x) for x in out]
+
+
+class _Session:
+    def _scratch(self, device):
+        self.bytes = self.plan["scratchBytes"]
+        self.work = torch.empty(max(self.bytes // 8, 2), dtype=torch.int64, device=device)
+
+    def _f_sides(self, fs, rows, k):
+        """the sides of an add as a TupleSide array, each sized against its own rows; host arrays go up for the call"""
+        from ._lib import TupleSide
+        if len(rows) != len(fs):
+            raise Pil2glError("%d sides and %d row counts" % (len(fs), len(rows)))
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).to(self.work.device) if isinstance(a, np.ndarray) else a   # noqa: E731
+        arr, keep = (TupleSide * max(len(fs), 1))(), []
+        for i, (spec, n) in enumerate(zip(fs, rows)):
+            spec = tuple(spec) + (None,) * (4 - len(spec))
+            sel = None if spec[2] is None else (up(spec[2][0]),) + tuple(spec[2][1:])
+            one, (kk,), kept = _sides([(up(spec[0]), spec[1], sel, spec[3])], ["f %d" % i], 3, n, self.words, True)
+            if kk != k:
+                raise Pil2glError("f %d has %d columns, %d expected" % (i, kk, k))
+            arr[i] = one[0]
+            keep.append(kept)
+        return arr, np.ascontiguousarray(rows, np.uint64), keep
+
+    def _total(self, entry, args, total):
+        out = C.c_uint64()
+        call(entry, *args, _ptr(self.work), self.bytes, C.byref(out) if total else None, _stream())
+        return out.value if total else None
+
+
+class LookupSession(_Session):
+    """the multiplicities of the lookup table t = (matrix, cols[, sel[, stride]]) of n_t rows, device tensors that stay unchanged while the
+    session lives.  seed: the debug open, every counter starting from it."""
+
+    def __init__(self, t, n_t, field="gl", seed=None):
+        self.words, self.n_t = _WORDS[field], n_t
+        self.T, (self.k,), self._keep = _sides([t], ["t"], 3, n_t, self.words, True)
+        self.plan = lookup_session_plan(n_t, self.k, field)
+        self._scratch(self._keep[0].device)
+        self._name = "pil2gl_lookup_session_%s_dev" if self.words == 1 else "pil2gl_bn128_lookup_session_%s_dev"
+        head = [self.T, n_t, self.k, _ptr(self.work), self.bytes, _stream()]
+        if seed is None:
+            call(self._name % "open", *head)
+        else:
+            call("pil2gl_debug_lookup_session_open_dev", *head, self.words, seed)
+
+    def add(self, fs, rows):
+        """counts the sides fs, side i over its first rows[i] rows -> this add's (kind, side, row, matched); blocks"""
+        F, R, keep = self._f_sides(fs, rows, self.k)
+        rep = (C.c_uint64 * 4)()
+        call(self._name % "add", self.T, self.n_t, self.k, F, C.c_void_p(R.ctypes.data), len(fs), _ptr(self.work), self.bytes, rep, _stream())
+        return tuple(int(x) for x in rep)
+
+    def write(self, m, total=True):
+        """m = (matrix, col[, stride]), a device column of n_t rows -> the session's matched rows; total=False only enqueues -> None"""
+        mm, col = _column(m, "m", 1, self.n_t, self.words, True)
+        return self._total(self._name % "write", [self.T, self.n_t, self.k] + col, total)
+
+
+class RangeSession(_Session):
+    """the multiplicities of the range table [lo, lo + size).  path: the count kernel of every add, for the tests and the benchmark
+    (0 LDS, 1 global, None the planner's choice); seed: the debug open."""
+
+    def __init__(self, lo, size, field="gl", path=None, seed=None, device="cuda"):
+        self.words, self.lo, self.size, self.path, self.k = _WORDS[field], lo, size, path, 1
+        self.plan = range_session_plan(size, field, path)
+        self._scratch(device)
+        self._name = "pil2gl_range_session_%s_dev" if self.words == 1 else "pil2gl_bn128_range_session_%s_dev"
+        if seed is None:
+            call("pil2gl_range_session_open_dev", size, _ptr(self.work), self.bytes, _stream())
+        else:
+            call("pil2gl_debug_range_session_open_dev", size, _ptr(self.work), self.bytes, _stream(), seed)
+
+    def add(self, fs, rows):
+        """counts the one-column sides fs, side i over its first rows[i] rows -> this add's (kind, side, row, matched); blocks"""
+        F, R, keep = self._f_sides(fs, rows, 1)
+        rep = (C.c_uint64 * 4)()
+        args = [self.lo, self.size, F, C.c_void_p(R.ctypes.data), len(fs), _ptr(self.work), self.bytes, rep, _stream()]
+        if self.path is None:
+            call(self._name % "add", *args)
+        else:
+            call("pil2gl_debug_range_session_add_dev", *args, self.words, self.path)
+        return tuple(int(x) for x in rep)
+
+    def write(self, m, n_m, row0=0, total=True):
+        """m = (matrix, col[, stride]), a device column of n_m rows: the counts at rows row0 .. row0 + size - 1, 0 elsewhere -> the session's
+        matched rows; total=False only enqueues -> None"""
+        mm, col = _column(m, "m", 1, n_m, self.words, True)
+        return self._total(self._name % "write", [self.size, row0] + col + [n_m], total)
+
+
+def range_logup_cross(users, lo, size, m, n_table, alpha, beta, outs, out_table, field="gl", row0=0, bus_id=None):
+    """one range table AIR and several user AIRs end to end, on device tensors.  users: (fs, n) per user AIR, fs range_mult's sides over
+    that AIR's n rows.  One RangeSession takes one add per user AIR and writes m, a column of the table AIR's n_table rows; every user's s
+    is logup_sum_dev with f terms only, into outs[i]; the table's s is range_sum_dev with no f term, into out_table
+    -> (the adds' reports, the session's matched rows, the last element of every s, users first).  The last elements sum to zero in the
+    field (the cubic extension over Goldilocks) when every report is clean."""
+    words = _WORDS[field]
+    session = RangeSession(lo, size, field, device=m[0].device)
+    reports = [session.add(fs, [n] * len(fs)) for fs, n in users]
+    total = session.write(m, n_table, row0)
+    last = []
+    for (fs, n), out in zip(users, outs):
+        terms, rng = _range_logup_terms(fs, lo, size, m, row0, bus_id, words)
+        logup_sum_dev(terms, alpha, beta, out, n, field)
+        last.append(_last_element(out, n, words))
+    range_sum_dev([], [_range_logup_terms([], lo, size, m, row0, bus_id, words)[1]], alpha, beta, out_table, n_table, field)
+    last.append(_last_element(out_table, n_table, words))
+    return reports, total, last
 
 
 # ---- clustered logUp sum: s and one im column a cluster in one call (csrc/logup_cluster_plan.h; include/pil2gl.h states it) ----
