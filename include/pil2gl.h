@@ -294,6 +294,11 @@ int pil2gl_rows_dot_ext_multi_dev(const uint64_t *const *bufs, const uint64_t *w
  * 7 <w_N>.  Same kernels and the same choice among them as the dense call (its rowStepBits = 0 case); rowStepBits: 0..20. */
 int pil2gl_rows_dot_ext_multi_step_dev(const uint64_t *const *bufs, const uint64_t *widths, uint32_t nBufs, uint64_t nRows, uint32_t rowStepBits,
                                        const uint64_t *const *hostCoefs, uint32_t nOut, uint64_t *acc, int accumulate, void *stream);
+/* host-only: how many launches this process has made of the three row-sum kernels behind the calls above -- out[0] the matrix-core
+ * kernel, out[1] the streaming kernel, out[2] the column-tile kernel (a window of a wide matrix is a launch of its own).  The choice
+ * among them hangs on widths, alignment, the device's LDS and two environment switches: the tests read the counts around a call and
+ * assert which kernel took it.  Three host counters stepped at the launch sites; nothing on the device. */
+int pil2gl_debug_rows_dot_launches(uint64_t out[3]);
 /* f[r] = Horner in vf1 over the openings of (acc[r][o] - K_o) * xDivXSubXi[r][o]   (friPolinomial.js:38-50);
  * hostK: nOpen x 3 (K_o = sum_j ev_j vf2^(n_o - j)). */
 int pil2gl_fri_combine_dev(const uint64_t *acc, const uint64_t *hostK, const uint64_t vf1[3], const uint64_t *xDivXSubXi,

@@ -437,6 +437,10 @@ inline unsigned nblk(u64 n, u32 t = 256) { return (unsigned)((n + t - 1) / t); }
 
 using namespace pil2gl;
 
+// launches of rows_dot_mfma_kernel, rows_dot_stream_kernel and rows_dot_kernel by this process (pil2gl_debug_rows_dot_launches)
+enum { RD_MFMA = 0, RD_STREAM = 1, RD_TILE = 2 };
+static uint64_t g_rows_dot_launches[3] = { 0, 0, 0 };
+
 // host side of rows_dot_mfma_kernel: signed base-256 digits of the weights laid out as the MFMA's A operand, the constant per output.
 // Segment k: nRows x widths[k] matrix bufs[k] with weights hostCoefs[k] ([nOut][widths[k]][3]); out = sum over all segments' columns.
 // a segment of the staged row: columns [col0, col0 + width) of an nRows x pitch matrix, with the weights of those columns
@@ -535,6 +539,7 @@ static int launch_rows_dot_mfma(const MfSeg *segs, u32 nBufs, u64 nRows, u32 nOu
     if (NT == 2) { if (odd) RD_LAUNCH(2, true) else RD_LAUNCH(2, false) }
     else { if (odd) RD_LAUNCH(3, true) else RD_LAUNCH(3, false) }
 #undef RD_LAUNCH
+    g_rows_dot_launches[RD_MFMA]++;
     KERNEL_CHECK();
     HIP_TRY(hipStreamSynchronize(st));          // the tables are host temporaries in a shared scratch slot
     return PIL2GL_OK;
@@ -573,6 +578,7 @@ static int rows_dot_ext_plain(const uint64_t *buf, uint64_t width, uint64_t nRow
             default: STREAM_CASE(4) break;
             }
 #undef STREAM_CASE
+            g_rows_dot_launches[RD_STREAM]++;
             KERNEL_CHECK();
             continue;
         }
@@ -582,6 +588,7 @@ static int rows_dot_ext_plain(const uint64_t *buf, uint64_t width, uint64_t nRow
         case 3: rows_dot_kernel<3><<<blocks, 256, 0, st>>>(P); break;
         default: rows_dot_kernel<4><<<blocks, 256, 0, st>>>(P); break;
         }
+        g_rows_dot_launches[RD_TILE]++;
         KERNEL_CHECK();
     }
     HIP_TRY(hipStreamSynchronize(st));      // `limbs` is a host temporary and the scratch slot is reused by the next call
@@ -678,6 +685,12 @@ int pil2gl_rows_dot_ext_multi_step_dev(const uint64_t *const *bufs, const uint64
         if (widths[k] == 0) continue;
         P2_TRY(rows_dot_ext_plain(bufs[k], widths[k], nRows, rowStepBits, hostCoefs[k], nOut, acc, acc1 ? 1 : 0, stream)); acc1 = true;
     }
+    return PIL2GL_OK;
+}
+
+int pil2gl_debug_rows_dot_launches(uint64_t out[3]) {
+    if (!out) return fail(PIL2GL_EINVAL, "null buffer");
+    for (int i = 0; i < 3; i++) out[i] = g_rows_dot_launches[i];
     return PIL2GL_OK;
 }
 

@@ -161,6 +161,7 @@ SIGNATURES = {
     "pil2gl_rows_dot_ext_dev": (_I, [vp, _U64, _U64, vp, _U32, vp, _I, vp]),
     "pil2gl_rows_dot_ext_multi_dev": (_I, [vp, vp, _U32, _U64, vp, _U32, vp, _I, vp]),
     "pil2gl_rows_dot_ext_multi_step_dev": (_I, [vp, vp, _U32, _U64, _U32, vp, _U32, vp, _I, vp]),
+    "pil2gl_debug_rows_dot_launches": (_I, [C.POINTER(_U64)]),
     "pil2gl_fri_combine_dev": (_I, [vp, vp, vp, vp, _U32, _U64, vp, vp]),
     "pil2gl_fri_combine_order_dev": (_I, [vp, vp, vp, vp, _U32, vp, _U64, vp, vp]),
     "pil2gl_compute_fri_pol_dev": (_I, [vp, vp, _U32, vp, _U32, vp, vp, vp, vp, _U32, _U32, vp, vp]),

@@ -1219,8 +1219,11 @@ def test_rows_and_cols_dot_ext(gl, oracle, monkeypatch, mode):
         got = acc.cpu().numpy().view(np.uint64).reshape(n_rows, n_out, 3)
         want = (2 * (m.astype(object) @ coef.astype(object).transpose(1, 0, 2).reshape(width, n_out * 3))) % P
         assert (got.reshape(n_rows, n_out * 3).astype(object) == want).all(), (n_rows, width, n_out, skew)
-    # stages wider than the 1024 terms a lane's unreduced sums can hold (the library cuts them into windows): values and
-    # weights whose every limb is at its maximum, so that a window one column too long would wrap the 64-bit partial sums
+    # stages wider than the 1024 terms a lane's unreduced sums can hold (the library cuts them into windows): that the windows are
+    # cut and accumulated.  NOT a capacity case: P - 1 has a low half of 0 (S[0][*] stay 0) and limbs 0, 0x3FFC00, 0xFFFFF (S[1][0]
+    # stays 0, S[1][2] reaches 2^62); only S[1][1] comes near 2^64, and with every odd row and every third weight random a window
+    # some columns too long would still pass.  The operands that fill each sum, and the proof that a 1025th column wraps it, are in
+    # test_gpu_rows_dot_capacity.py
     for n_rows, width, n_out in [(130, 1500, 2), (70, 5000, 4), (64, 1024, 1), (64, 1025, 1)]:
         m = np.full((n_rows, width), P - 1, dtype=np.uint64); m[1::2] = rand_field(rng, (len(m[1::2]), width))
         coef = np.full((n_out, width, 3), P - 1, dtype=np.uint64); coef[:, ::3] = rand_field(rng, coef[:, ::3].shape)
