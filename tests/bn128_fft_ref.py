@@ -68,6 +68,41 @@ def interpolate(x, n_bits_ext):
     return coefs, ntt(coefs + [0] * ((1 << n_bits_ext) - len(x)))
 
 
+def batch_inverse(vals):
+    """Montgomery's trick: the inverses of non-zero vals with one modular inversion"""
+    prefix, acc = [], 1
+    for v in vals:
+        assert v % R, "zero in a batch inversion"
+        prefix.append(acc)
+        acc = acc * v % R
+    inv = pow(acc, -1, R)
+    out = [0] * len(vals)
+    for i in range(len(vals) - 1, -1, -1):
+        out[i] = inv * prefix[i] % R
+        inv = inv * vals[i] % R
+    return out
+
+
+def geometric_ntt_rows(c, a, n_bits, rows, inverse=False):
+    """rows `rows` of the transform of the geometric column x_j = c a^j, j < n = 2^n_bits, without the transform: with g = w(n_bits),
+    or its inverse for the inverse transform, sum_j c a^j g^(jk) = c ((a g^k)^n - 1) / (a g^k - 1) = c (a^n - 1) / (a g^k - 1),
+    and the inverse transform divides by n.  Needs a^n != 1 (a = 1 and every n-th root of unity are refused): then a g^k != 1 for
+    every k and no denominator is zero."""
+    n = 1 << n_bits
+    c, a = c % R, a % R
+    an = pow(a, n, R)
+    if an == 1:
+        raise ValueError("geometric_ntt_rows: a^n = 1, the closed form has a zero denominator")
+    g = w(n_bits)
+    if inverse:
+        g = pow(g, -1, R)
+    num = c * (an - 1) % R
+    if inverse:
+        num = num * pow(n, -1, R) % R
+    inv = batch_inverse([(a * pow(g, k % n, R) - 1) % R for k in rows])
+    return [num * d % R for d in inv]
+
+
 # ---- the library's words -----------------------------------------------------------------------------------------------------
 def to_mont(v):
     return v % R * MONT % R
@@ -84,6 +119,20 @@ def words_of(vals):
         for k in range(4):
             a[i, k] = (v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF
     return a
+
+
+def pack_words(vals):
+    """words_of for long lists: through int.to_bytes and one np.frombuffer"""
+    return np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype="<u8").reshape(len(vals), 4)
+
+
+def geometric_words(c, a, n_bits):
+    """(2^n_bits, 4) Montgomery words of the column x_j = c a^j: one product per element, starting from the Montgomery form of c"""
+    vals, v = [], to_mont(c)
+    for _ in range(1 << n_bits):
+        vals.append(v)
+        v = v * a % R
+    return pack_words(vals)
 
 
 def ints_of(words):

@@ -61,6 +61,71 @@ def test_montgomery_words_round_trip():
     assert ref.ints_of(wd[1, 0])[0] == cols[0][1] * (1 << 256) % R
 
 
+# ---- the closed form of a geometric column ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_bits", range(1, 11))
+def test_geometric_closed_form_is_the_transform_on_every_row(n_bits):
+    n = 1 << n_bits
+    rng = random.Random(300 + n_bits)
+    for c, a in ((rng.randrange(1, R), rng.randrange(2, R)), (R - 1, 2), (1, R - 2), (rng.randrange(1, R), 0)):
+        assert pow(a, n, R) != 1
+        x = [c * pow(a, j, R) % R for j in range(n)]
+        assert ref.geometric_ntt_rows(c, a, n_bits, range(n)) == ref.ntt(x)
+        assert ref.geometric_ntt_rows(c, a, n_bits, range(n), inverse=True) == ref.intt(x)
+        assert ref.matrix_cols(ref.geometric_words(c, a, n_bits).reshape(n, 1, 4)) == [x]
+    some = [n - 1, 0, n // 2, 0]                                       # any order, repeats allowed
+    assert ref.geometric_ntt_rows(c, a, n_bits, some) == [ref.ntt(x)[k] for k in some]
+
+
+@pytest.mark.parametrize("n_bits", range(1, 11))
+def test_geometric_closed_form_refuses_a_zero_denominator(n_bits):
+    g = ref.w(n_bits)
+    for a in (1, g, pow(g, 3, R), pow(g, -1, R), R - 1, 1 + R):
+        for inverse in (False, True):
+            with pytest.raises(ValueError):
+                ref.geometric_ntt_rows(5, a, n_bits, [0, 1], inverse=inverse)
+    assert ref.geometric_ntt_rows(5, ref.w(n_bits + 1), n_bits, [0]) == [5 * (R - 2) * pow(ref.w(n_bits + 1) - 1, -1, R) % R]   # a^n = -1
+
+
+def test_batch_inverse_and_packed_words():
+    v = _rand(50, 9) + [1, R - 1]
+    assert [a * b % R for a, b in zip(v, ref.batch_inverse(v))] == [1] * len(v)
+    with pytest.raises(AssertionError):
+        ref.batch_inverse([3, 0, 5])
+    assert (ref.pack_words(v) == ref.words_of(v)).all()
+
+
+# ---- chosen words into the twiddle products ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_bits", range(1, 8))
+def test_dif_layers_are_the_transform(n_bits):
+    import bn128_fft_dif as dif
+    x = _rand(1 << n_bits, 500 + n_bits)
+    out, met = dif.dif(x)
+    assert out == ref.ntt(x) and {(t, j) for _, t, j in met} == dif.twiddles_of(n_bits)
+    assert dif.dif(x, inverse=True)[0] == ref.intt(x)
+
+
+@pytest.mark.parametrize("n_bits", (2, 3))
+def test_chosen_words_meet_every_twiddle(n_bits):
+    """the columns of twiddle_cases put each chosen word itself, as the difference a - b, in front of every twiddle of the size"""
+    import bn128_fft_dif as dif
+    from test_gpu_bn128_fft import chosen_pairs
+    words = dif.chosen_words(chosen_pairs())
+    ones = (0x30644e71 << 224) | ((1 << 224) - 1)
+    assert {ones, R - 1, (1 << 255) % R, 1, 1 << 31, 1 << 32, 1 << 63, 1 << 64, 1 << 127, 1 << 128, 1 << 191, 1 << 192,
+            1 << 223, 1 << 224, 1 << 253} <= set(words) and 0 not in words and len(set(words)) == len(words)
+    for x in words:
+        for inverse in (False, True):
+            met = set()
+            for col in dif.twiddle_cases(n_bits, x):
+                assert len(col) == 1 << n_bits and all(0 <= v < R for v in col)
+                out, m = dif.dif(col, inverse)
+                assert out == (ref.intt if inverse else ref.ntt)(col)
+                met |= m
+            assert {(x, t, j) for t, j in dif.twiddles_of(n_bits)} <= met
+            if n_bits == 2:
+                assert (2 * x % R, 1, 1) in met and (0, 1, 0) in met
+
+
 # ---- the library: planner, argument checks, no device ------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib():
